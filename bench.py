@@ -15,7 +15,9 @@ inside the step (--static-boxes sets them once instead).  Inputs are resident
 in HBM before the timed region; every step touches > 256 MiB and the resident batches are
 cycled, so the traffic is real HBM traffic, not Infinity-Cache hits.  The timed region
 runs twice: once plain (-> value) and once with HIP events around the project+label
-kernel (-> roofline).  Rank 0 prints ONE JSON line.
+kernel (-> roofline).  Rank 0 prints ONE JSON line.  --dump-outputs DIR also writes what the last
+timed step computed as DIR/<name>.npy (dump_outputs): the inputs are seeded, so two builds can be
+compared output for output.
 
 Multi-GPU: frames/clouds are independent units, so ranks shard them with no data-path
 collective (weak scaling); the only exchange is one RCCL all-reduce of the aggregate
@@ -645,6 +647,70 @@ def check_frames(torch, out, pts_dev_b, scenes, velo_per_frame, keep_per_frame, 
     return tot
 
 
+DUMP_SAMPLE = 1 << 19             # entries kept of each per-point array and of each index list by --dump-outputs
+DUMP_SEED = 20240607
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+DUMP_SAMPLE_SEEDS = {"point": 1, "inst_idx": 2, "valid_idx": 3}
+
+
+def dump_sample_positions(length, what):
+    """Sorted positions of the fixed seeded sample --dump-outputs keeps of an array of `length` entries: of the step's points
+    (what = "point": u, v, label_bits) or of the frames' lists one after the other ("valid_idx", "inst_idx")."""
+    if length <= DUMP_SAMPLE:
+        return np.arange(length, dtype=np.int64)
+    rng = np.random.default_rng([DUMP_SEED, DUMP_SAMPLE_SEEDS[what]])
+    return np.sort(rng.choice(length, size=DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(torch, out, F, n, M, dirpath):
+    """What one finished step hands its caller, as DIR/<name>.npy in float64 (every value is an integer that float64 holds
+    exactly): the per-frame summaries and the box counts in full; of the per-point outputs (u, v, label_bits) and of the
+    concatenated index lists (valid_idx, instance lists) the entries at dump_sample_positions, at most DUMP_SAMPLE each; and
+    per-frame sums over the full arrays, so that a difference outside the sample still shows.  The summary's overflow flag
+    is not written: with room for every point of a frame in its lists it cannot be set, and a step whose lists did overflow
+    has no complete outputs to write."""
+    from lidar_object_detection_amd._native import SUMMARY_DTYPE
+    os.makedirs(dirpath, exist_ok=True)
+    sm = np.frombuffer(out["summary"].cpu().numpy().tobytes(), SUMMARY_DTYPE)
+    if sm["inst_overflow"].any():
+        raise SystemExit("bench.py --dump-outputs: the instance lists of frames %s overflowed" % np.flatnonzero(sm["inst_overflow"]).tolist())
+    arrays = {"n_valid": sm["n_valid"], "n_labelled": sm["n_labelled"], "inst_count": sm["inst_count"][:, :M],
+              "inst_off": sm["inst_off"][:, :M + 1], "best_box": sm["best_box"][:, :M], "best_cnt": sm["best_cnt"][:, :M],
+              "count_mb": out["count_mb"].cpu().numpy()}
+
+    def sample(length, what):
+        return torch.from_numpy(dump_sample_positions(length, what)).to(out["uv"].device)
+
+    uv = out["uv"].view(F, n, 2)
+    lab = out["label_bits"].view(F, n).to(torch.int64) & 0xFFFFFFFF                  # the bits as uint32
+    pos = sample(F * n, "point")
+    arrays["u_sample"] = out["uv"][:, 0][pos].cpu().numpy()
+    arrays["v_sample"] = out["uv"][:, 1][pos].cpu().numpy()
+    arrays["label_bits_sample"] = lab.view(-1)[pos].cpu().numpy()
+    sums = {"u": uv[:, :, 0].to(torch.int64).sum(1), "v": uv[:, :, 1].to(torch.int64).sum(1), "label_bits": lab.sum(1)}
+    lists = {}
+    if out.get("valid_idx") is not None:
+        lists["valid_idx"] = [out["valid_idx"][f * n:f * n + int(sm[f]["n_valid"])] for f in range(F)]
+    if out.get("inst_idx") is not None:                                              # inst_cap = n entries per frame
+        lists["inst_idx"] = [out["inst_idx"][f * n + min(int(sm[f]["inst_off"][m]), n):f * n + min(int(sm[f]["inst_off"][m + 1]), n)]
+                             for f in range(F) for m in range(M)]
+    for name, parts in lists.items():
+        cat = torch.cat(parts)
+        arrays[name + "_sample"] = cat[sample(cat.numel(), name)].cpu().numpy()
+        sums[name] = torch.stack([p.sum() for p in parts]).view(F, -1).sum(1)
+    for name, s in sums.items():
+        arrays["frame_sum_" + name] = s.cpu().numpy()
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes would be written, the limit is %d" % (total, DUMP_LIMIT_BYTES))
+    for k, v in arrays.items():
+        np.save(os.path.join(dirpath, k + ".npy"), v)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -670,7 +736,11 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configs (N = 1 only anyway)")
     ap.add_argument("--dry-launch", action="store_true", help="print the launcher command of --gpus N and exit (tests)")
     ap.add_argument("--lab", default="", help="diagnosis only (no oracle check, never a reported number): 'nolists', 'noboxes' or 'nomasks'")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (rank 0) as DIR/<name>.npy, float64, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, sys.argv[1:], dry=args.dry_launch)
@@ -723,12 +793,14 @@ def main():
     use_rects = bool(args.mask_rects)
     rects0 = torch.from_numpy(LpfContext.mask_rects(np.stack([sc["masks"] for sc in scenes]))).to(dev)     # [F,8,4] int32
     rects_dev = []
+    perm_gen = torch.Generator(device=dev)                            # the further batches' permutations, the same in every run
+    perm_gen.manual_seed(1000 * rank + 999)                            # (torch's default generators may be seeded per process)
     pts_dev, masks_dev, outs, cam0_host, cam0_dev, velo_ref, keep_ref = [], [], [], [], [], [], []
     for b in range(nbuf):
         if b == 0:
             pts_dev.append(base_pts)
         else:
-            perm = torch.cat([f * n + torch.randperm(n, device=dev) for f in range(F)])
+            perm = torch.cat([f * n + torch.randperm(n, device=dev, generator=perm_gen) for f in range(F)])
             pts_dev.append(base_pts[perm].contiguous())
             del perm
         masks_dev.append(masks0.clone() if b else masks0)
@@ -749,8 +821,9 @@ def main():
         if world > 1:
             dist.barrier()
 
-    def measure(mode, steps, warmup, events):
-        """`steps` timed steps under queueing mode `mode` (+ a second, event-bracketed pass), checked against the oracle."""
+    def measure(mode, steps, warmup, events, dump_dir=""):
+        """`steps` timed steps under queueing mode `mode` (+ a second, event-bracketed pass), checked against the oracle;
+        with dump_dir, the outputs of the last timed step are written there (dump_outputs)."""
         # The context runs on a stream of its own.  Everything above was queued on torch's current stream, and the caching
         # allocator may have carved the output tensors from memory that kernels still queued there read (the index tensors
         # of the gathers): the context gets an explicit device-side edge behind that stream before its first kernel, instead
@@ -812,6 +885,8 @@ def main():
             steps_fn[i % nb]()
         drain()
         el, queued = timed(steps)
+        if dump_dir and rank == 0:
+            dump_outputs(torch, outs[(steps - 1) % nb], F, n, N_MASKS, dump_dir)
         res = {"mode": mode, "steps": steps, "nbuf": nb, "elapsed": el, "queued": queued, "k1_ms": 0.0, "k1_n": 0, "elapsed_ev": None, "empty_ms": 0.0}
         if events:                                          # pass 2: same steps, HIP events around the dominant kernel
             res["empty_ms"] = float(ctx.profile_overhead())           # what an empty bracket measures, live
@@ -837,7 +912,7 @@ def main():
         for o in outs:
             o["valid_idx"] = None
             o["inst_idx"] = None
-    main_run = measure(args.mode, args.steps, args.warmup, not args.no_events)
+    main_run = measure(args.mode, args.steps, args.warmup, not args.no_events, args.dump_outputs)
     # the plain in-order queueing beside it (N = 1 only): what the pipelining buys, and the streaming kernel on its own
     serial_run = None
     if world == 1 and not args.no_secondary and args.mode != "serial" and not args.lab:
