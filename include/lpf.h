@@ -45,7 +45,10 @@ extern "C" {
                                       6: lpf_set_mask_rects, lpf_resize_masks_u8 (added; nothing else changed)
                                       7: lpf_build_id, lpf_host_alloc / lpf_host_free, lpf_run_frame, lpf_erode_masks_u8 (added; nothing else changed)
                                       8: lpf_reader_submit_frame, lpf_reader_boxes, lpf_parse_boxes_json (added); lpf_resize_masks_u8 no longer
-                                         refuses an exact halving (it is cv2.resize's INTER_AREA case) */
+                                         refuses an exact halving (it is cv2.resize's INTER_AREA case)
+                                      8 (continued): LPF_MAX_MASKS_WIDE, lpf_wide_input, lpf_wide_outputs, lpf_run_wide (added; nothing
+                                         else changed) */
+#define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 
 typedef enum lpf_status {
     LPF_OK = 0,
@@ -269,6 +272,53 @@ typedef struct lpf_frame_job {
     lpf_outputs    out;
 } lpf_frame_job;
 int lpf_run_frame(lpf_ctx *ctx, const lpf_frame_job *job);
+
+/* ---- frames with more than 32 masks ------------------------------------------------------------------------------------
+ * lpf_run_wide: a batch of F frames with M masks each, 0 <= M <= LPF_MAX_MASKS_WIDE, in ONE pass: every point is projected and read
+ * once, however many masks the frame has (the reference applies every detection mask of a frame, with no limit: V3:220,
+ * cvs_erosion.py:148-162).  A point's membership is LW = ceil(M / 32) label words: word w, bit b <=> mask 32 w + b.  Every result is
+ * the one the narrow calls give when the frame is run once per group of 32 masks (group w -> word w), concatenated.
+ * Masks, rectangles and erosion come with the call; the boxes are the ones in force (lpf_set_boxes*), the camera and depth window the
+ * ones of lpf_set_camera.  It leaves the masks, boxes and rectangles of the narrow calls as they were.  Not capturable (LPF_ERR_STATE
+ * between lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it first launches what the pipeline owes (no host
+ * wait), then runs in order.  With device outputs the call only enqueues work; with host outputs it returns with them filled. */
+typedef struct lpf_wide_input {
+    const void    *masks;          /* [F][M][H][W]: uint8 (nonzero = member) or float32 under `binarize` (lpf_set_masks_f32's rules) */
+    const int32_t *rects;          /* optional [F][M][4] {x0, y0, x1, y1}: lpf_set_mask_rects' contract (uint8, or float32 with
+                                      binarize 0, and no erosion; ignored otherwise); in the same memory as the masks; or NULL */
+    int32_t  M;
+    int32_t  f32;                  /* 0: uint8 masks, 1: float32 */
+    int32_t  binarize;             /* float32 masks: 0 / 1 / 2 as lpf_set_masks_f32 */
+    int32_t  erode_iters;          /* cv2.erode iterations with the cross element, >= 0 */
+    int32_t  on_device;            /* 0: masks (and rects) in host memory, copied by the call; else device memory lent until the
+                                      run has completed (as on_device = 2 of lpf_set_masks_*) */
+    int32_t  reserved;
+} lpf_wide_input;
+
+/* Outputs of lpf_run_wide.  Any pointer may be NULL (not wanted); all are host or all device memory per on_device.
+ * Ntot = frame_off[F], Btot = boxes in force over the batch, LW = ceil(M / 32). */
+typedef struct lpf_wide_outputs {
+    int32_t  *uv;                  /* [Ntot][2]   as lpf_outputs */
+    double   *depth, *u_f, *v_f;   /* [Ntot]      as lpf_outputs */
+    int64_t  *valid_idx;           /* [Ntot]      as lpf_outputs */
+    int32_t  *uv_valid;            /* [Ntot][2]   as lpf_outputs */
+    uint32_t *label_words;         /* [Ntot][LW]  bit b of word w <=> point valid and inside mask 32 w + b */
+    uint32_t *label_valid_words;   /* [Ntot][LW]  compact, in valid_idx order (frame f's at frame_off[f]) */
+    int64_t  *inst_idx;            /* [F][inst_cap] per frame: the M instance lists in mask order, each ascending */
+    int64_t   inst_cap;
+    int32_t  *count_mb;            /* [M * Btot]  frame f's [M][B_f] block at M * box_off[f] */
+    int64_t  *n_valid;             /* [F] */
+    int64_t  *n_labelled;          /* [F]         points in >= 1 mask */
+    int64_t  *inst_count;          /* [F][M] */
+    int64_t  *inst_off;            /* [F][M + 1]  list m of frame f = inst_idx[f][inst_off[f][m] .. inst_off[f][m + 1]) */
+    int64_t  *best_cnt;            /* [F][M]      0 if none */
+    int32_t  *best_box;            /* [F][M]      first strict maximum into the frame's boxes, -1 if none */
+    int32_t  *inst_overflow;       /* [F]         1 if the frame's lists exceed inst_cap (truncated) */
+    int32_t   on_device;
+    int32_t   reserved;
+} lpf_wide_outputs;
+int lpf_run_wide(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
+                 const lpf_wide_outputs *out);
 
 /* ---- box membership as a stand-alone operator -------------------------------------------
  * inside[b*k + i] = 1 if point i lies in box b, else 0: the boolean arrays the reference's

@@ -15,6 +15,7 @@ import numpy as np
 from . import _build
 
 LPF_MAX_MASKS = 32
+LPF_MAX_MASKS_WIDE = 256                # lpf_run_wide: masks per frame in one pass
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 
@@ -45,6 +46,66 @@ class Outputs(ctypes.Structure):
                 ("valid_idx", _P), ("inst_idx", _P), ("inst_cap", _I64), ("count_mb", _P),
                 ("summary", _P), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("uv_valid", _P), ("label_valid", _P)]
+
+
+class WideInput(ctypes.Structure):
+    """lpf_wide_input (include/lpf.h): the masks of an lpf_run_wide call"""
+    _fields_ = [("masks", _P), ("rects", _P), ("M", ctypes.c_int32), ("f32", ctypes.c_int32), ("binarize", ctypes.c_int32),
+                ("erode_iters", ctypes.c_int32), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class WideOutputs(ctypes.Structure):
+    """lpf_wide_outputs (include/lpf.h)"""
+    _fields_ = [("uv", _P), ("depth", _P), ("u_f", _P), ("v_f", _P), ("valid_idx", _P), ("uv_valid", _P), ("label_words", _P),
+                ("label_valid_words", _P), ("inst_idx", _P), ("inst_cap", _I64), ("count_mb", _P), ("n_valid", _P), ("n_labelled", _P),
+                ("inst_count", _P), ("inst_off", _P), ("best_cnt", _P), ("best_box", _P), ("inst_overflow", _P),
+                ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+def wide_mask_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", binarize_codes=None):
+    """Checks the masks of a wide run before anything reaches the GPU: ``(masks [F,M,H,W], M, is_float, on_device, rects [F,M,4] or
+    None)``.  masks: [M,H,W] (F = 1) or [F,M,H,W], uint8 / bool or float32, a NumPy array or a contiguous GPU tensor; M <= 256."""
+    codes = binarize_codes or {"astype": 0, "v3": 1, "gt0.5": 2}
+    if binarize not in codes:
+        raise ValueError("binarize must be one of %s" % sorted(codes))
+    if int(erode_iters) != erode_iters or erode_iters < 0:
+        raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
+    dev = _is_torch(masks)
+    if not dev:
+        masks = np.asarray(masks)
+    shape = tuple(masks.shape)
+    if len(shape) == 3:
+        shape = (1,) + shape
+        masks = masks.reshape(shape)
+    if len(shape) != 4 or shape[0] != F or (shape[1] and shape[2:] != (H, W)):
+        raise ValueError("masks must be [M,%d,%d] (one frame) or [F=%d,M,%d,%d], got %s" % (H, W, F, H, W, tuple(masks.shape)))
+    M = shape[1]
+    if M > LPF_MAX_MASKS_WIDE:
+        raise ValueError("at most %d masks per frame in one wide run, got %d" % (LPF_MAX_MASKS_WIDE, M))
+    if dev:
+        dt = str(masks.dtype)
+        if dt not in ("torch.float32", "torch.uint8", "torch.bool") or not masks.is_cuda or not masks.is_contiguous():
+            raise ValueError("device masks must be contiguous float32, uint8 or bool GPU tensors")
+        is_f = dt == "torch.float32"
+    else:
+        if masks.dtype.kind not in "fbiu":
+            raise ValueError("masks must be numeric, got %s" % masks.dtype)
+        is_f = masks.dtype.kind == "f"
+        masks = np.ascontiguousarray(masks, dtype=np.float32 if is_f else np.uint8)
+    if rects is not None:
+        if _is_torch(rects) != dev:
+            raise ValueError("the rectangles must live where the masks do")
+        rshape = tuple(rects.shape)
+        if len(rshape) == 2:
+            rshape = (1,) + rshape
+        if rshape != (F, M, 4):
+            raise ValueError("rects must be [F=%d, M=%d, 4], got %s" % (F, M, tuple(rects.shape)))
+        if dev:
+            if str(rects.dtype) != "torch.int32" or not rects.is_contiguous():
+                raise ValueError("device rects must be a contiguous int32 tensor")
+        else:
+            rects = np.ascontiguousarray(np.asarray(rects).reshape(rshape), dtype=np.int32)
+    return masks, M, is_f, dev, rects
 
 
 class FrameJob(ctypes.Structure):
@@ -144,6 +205,7 @@ def load(path=None):
     lib.lpf_run.argtypes = [_P, _P, _I64, ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_batch.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_frame.argtypes = [_P, ctypes.POINTER(FrameJob)]
+    lib.lpf_run_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(WideOutputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
     lib.lpf_depth_image.argtypes = [_P, _P, _I64, ctypes.c_int, _P, _P]
     lib.lpf_prepare_boxes.argtypes = [_P, _P, ctypes.c_int, _P, _P, _P, _P, _P]
@@ -177,7 +239,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_points_in_boxes", "lpf_prepare_boxes", "lpf_depth_image", "lpf_resize_masks_u8", "lpf_erode_masks_u8", "lpf_get_stats", "lpf_profile_enable", "lpf_profile_read", "lpf_profile_overhead",
             "lpf_graph_begin", "lpf_graph_end", "lpf_graph_launch", "lpf_graph_destroy",
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
-            "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json")
+            "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -881,6 +943,103 @@ class LpfContext:
                     r["label_valid"] = labv[a:a + r["n_valid"]]
                 r["inst_lists"] = [iidx[f, int(s["inst_off"][m]):int(s["inst_off"][m + 1])] for m in range(M)] \
                     if iidx is not None else []
+            if self.box_off is not None:
+                b0, b1 = int(self.box_off[f]), int(self.box_off[f + 1])
+                r["count_mb"] = cmb[M * b0:M * b1].reshape(M, b1 - b0).astype(np.int64)
+            else:
+                r["count_mb"] = np.zeros((M, 0), np.int64)
+            res.append(r)
+        return res
+
+    def run_wide(self, frames, masks, erode_iters=0, binarize="astype", rects=None, v3_pipeline=False, want_uv=True, want_float=False,
+                 want_lists=True, want_valid_uv=False, inst_cap=None):
+        """Frames with up to 256 masks each in ONE native pass (lpf_run_wide): every point is projected and read once.
+        frames: list of f32[N_f,4] host arrays, or ONE float32 [N,4] GPU tensor.  masks: [M,H,W] or [F,M,H,W] (uint8 / bool, or
+        float32 under ``binarize`` as set_masks), host or GPU (lent until the call returns: it waits for its results).  rects: the
+        optional [F,M,4] hint of set_mask_rects.  Boxes and camera are the ones in force; the masks, boxes and rectangles of the
+        narrow calls are left as they are.  Returns one dict per frame with what run_batch returns -- inst_count, best_box,
+        best_cnt of length M, count_mb [M, B_f] -- plus label_words [N_f, LW] (bit b of word w = mask 32 w + b; LW = ceil(M / 32)),
+        and with want_valid_uv label_valid_words [n_valid, LW]."""
+        if v3_pipeline:
+            binarize = "v3"
+        dev_pts = frames[0] if (len(frames) == 1 and _is_torch(frames[0])) else None
+        if dev_pts is not None:
+            if dev_pts.ndim != 2 or dev_pts.shape[1] != 4 or str(dev_pts.dtype) != "torch.float32":
+                raise ValueError("device points must be a float32 tensor [N,4]")
+            sizes = [int(dev_pts.shape[0])]
+        else:
+            if any(_is_torch(p) or isinstance(p, Scan) for p in frames):
+                raise ValueError("a GPU tensor of points is processed on its own (one frame per run)")
+            frames = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 4) for p in frames]
+            sizes = [p.shape[0] for p in frames]
+        F = len(sizes)
+        if F == 0:
+            raise ValueError("no frames")
+        masks, M, is_f, mdev, rects = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
+        LW = (M + 31) // 32
+        off = np.zeros(F + 1, np.int64)
+        off[1:] = np.cumsum(sizes)
+        n = int(off[-1])
+        if dev_pts is not None:
+            import torch
+            self.wait_for_stream(torch.cuda.current_stream(dev_pts.device).cuda_stream)
+            pts_ptr, pts_dev, keep_pts = (_dev_ptr(dev_pts, "float32") if n else None), 1, dev_pts
+        else:
+            keep_pts = np.concatenate(frames, axis=0) if F > 1 else frames[0]
+            pts_ptr, pts_dev = (keep_pts.ctypes.data if n else None), 0
+        if mdev:
+            import torch
+            self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
+        inp = WideInput()
+        inp.masks = (masks.data_ptr() if mdev else masks.ctypes.data) if M else None
+        inp.rects = (rects.data_ptr() if mdev else rects.ctypes.data) if (rects is not None and M) else None
+        inp.M, inp.f32, inp.binarize, inp.erode_iters = M, int(is_f), self.BINARIZE[binarize], int(erode_iters)
+        inp.on_device = 1 if mdev else 0
+        Btot = int(self.box_off[-1]) if self.box_off is not None else 0
+        if inst_cap is None:
+            inst_cap = max(max(sizes), 1)
+        while True:
+            o = WideOutputs()
+            o.on_device = 0
+            uv = np.empty((n, 2), np.int32) if want_uv else None
+            dep, uf, vf = [(np.empty(n, np.float64) if want_float else None) for _ in range(3)]
+            words = np.empty((n, LW), np.uint32)
+            vidx = np.empty(n, np.int64) if want_lists else None
+            uvv = np.empty((n, 2), np.int32) if (want_valid_uv and want_lists) else None
+            lvw = np.empty((n, LW), np.uint32) if (want_valid_uv and want_lists) else None
+            iidx = np.empty((F, inst_cap), np.int64) if (want_lists and M) else None
+            cmb = np.zeros(max(M * Btot, 1), np.int32)
+            nv, nl = np.zeros(F, np.int64), np.zeros(F, np.int64)
+            ic, io = np.zeros((F, M), np.int64), np.zeros((F, M + 1), np.int64)
+            bc, bb, ov = np.zeros((F, M), np.int64), np.full((F, M), -1, np.int32), np.zeros(F, np.int32)
+            for name, arr in (("uv", uv), ("depth", dep), ("u_f", uf), ("v_f", vf), ("valid_idx", vidx), ("uv_valid", uvv),
+                              ("label_words", words), ("label_valid_words", lvw), ("inst_idx", iidx), ("count_mb", cmb),
+                              ("n_valid", nv), ("n_labelled", nl), ("inst_count", ic), ("inst_off", io), ("best_cnt", bc),
+                              ("best_box", bb), ("inst_overflow", ov)):
+                setattr(o, name, arr.ctypes.data if (arr is not None and arr.size) else None)
+            o.inst_cap = inst_cap
+            self._check(self._lib.lpf_run_wide(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
+            if iidx is not None and ov.any():
+                inst_cap = int(io[:, M].max())                   # exact size now known: run again
+                continue
+            break
+        del keep_pts
+        res = []
+        for f in range(F):
+            a, b = int(off[f]), int(off[f + 1])
+            r = dict(n_valid=int(nv[f]), n_labelled=int(nl[f]), inst_count=ic[f].copy(), best_box=bb[f].copy(), best_cnt=bc[f].copy(),
+                     label_words=words[a:b])
+            if want_uv:
+                r["u"], r["v"] = uv[a:b, 0], uv[a:b, 1]
+            if want_float:
+                r["depth"], r["uf"], r["vf"] = dep[a:b], uf[a:b], vf[a:b]
+            if want_lists:
+                r["valid_idx"] = vidx[a:a + r["n_valid"]]
+                if uvv is not None:
+                    r["uv_valid"] = uvv[a:a + r["n_valid"]]
+                    r["u_valid"], r["v_valid"] = r["uv_valid"][:, 0], r["uv_valid"][:, 1]
+                    r["label_valid_words"] = lvw[a:a + r["n_valid"]]
+                r["inst_lists"] = [iidx[f, int(io[f, m]):int(io[f, m + 1])] for m in range(M)] if iidx is not None else []
             if self.box_off is not None:
                 b0, b1 = int(self.box_off[f]), int(self.box_off[f + 1])
                 r["count_mb"] = cmb[M * b0:M * b1].reshape(M, b1 - b0).astype(np.int64)

@@ -2,6 +2,7 @@
 // kernels in lpf_kernels.hip.h.  No CPU compute path exists here: every entry point
 // either launches HIP kernels or fails with an error code.
 #include "lpf_kernels.hip.h"
+#include "lpf_wide.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -164,6 +165,9 @@ struct lpf_ctx {
     DevBuf st_pts, st_uv, st_label, st_depth, st_uf, st_vf, st_valid, st_inst, st_count, st_summary;
     std::vector<LpfFrame> h_frames;   // table being built
     std::vector<char> h_tab;          // [frames | segs | blks] being built
+
+    // lpf_run_wide: its own buffers (the narrow masks, label images and staging stay as they are)
+    struct Wide { DevBuf tab, masks, rects, planes_a, planes_b, flags, ccnt, cpre, fcnt, midx, mwords, mpts, cnt, uv, words, pts, out; } wide;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -1889,6 +1893,209 @@ int lpf_profile_read(lpf_ctx *c, double *k1_ms_sum, int64_t *k1_launches, int re
     if (k1_ms_sum) *k1_ms_sum = sum;
     if (k1_launches) *k1_launches = (int64_t)c->ev_used;
     if (reset) c->ev_used = 0;
+    return LPF_OK;
+}
+
+// ---- lpf_run_wide (include/lpf.h): frames of up to LPF_MAX_MASKS_WIDE masks, kernels in lpf_wide.hip.h ----------------------
+int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
+                 const lpf_wide_outputs *out)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (use_device(c)) return LPF_ERR_HIP;
+    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_run_wide cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
+    if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera has not been called");
+    if (!in || !out || !frame_off || F <= 0) return fail(c, LPF_ERR_ARG, "run_wide: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
+    const int M = in->M;
+    if (M < 0 || M > LPF_MAX_MASKS_WIDE)
+        return fail(c, LPF_ERR_ARG, "run_wide: M=%d masks per frame, lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE = %d", M, LPF_MAX_MASKS_WIDE);
+    if (in->erode_iters < 0 || (in->f32 && (in->binarize < 0 || in->binarize > 2)) || (M > 0 && !in->masks))
+        return fail(c, LPF_ERR_ARG, "run_wide: erode_iters=%d f32=%d binarize=%d masks=%p", in->erode_iters, in->f32, in->binarize, in->masks);
+    if (frame_off[0] != 0) return fail(c, LPF_ERR_ARG, "run_wide: frame_off[0] must be 0");
+    for (int f = 0; f < F; ++f) {
+        const int64_t n = frame_off[f + 1] - frame_off[f];
+        if (n < 0 || n > 0x7fffffffll - LPF_WIDE_CHUNK) return fail(c, LPF_ERR_ARG, "run_wide: frame %d has %lld points", f, (long long)n);
+    }
+    const int64_t Ntot = frame_off[F];
+    if (Ntot > 0 && !pts) return fail(c, LPF_ERR_ARG, "run_wide: pts is NULL");
+    if (out->inst_idx && out->inst_cap <= 0) return fail(c, LPF_ERR_ARG, "run_wide: inst_idx given with inst_cap=%lld", (long long)out->inst_cap);
+    lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
+    if (BX.F != 0 && BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, run_wide has %d", BX.F, F);
+    int rc;
+    // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+    if (BX.F && c->cand_dirty && !BX.job_valid) box_rebuild_job(BX);
+    c->cand_dirty = false;
+    if ((rc = launch_box_job(c, BX))) return rc;
+    BX.used = true;
+    BX.last_ref = c->run_seq++;
+
+    const int LW = (M + 31) / 32;
+    const int Btot = BX.F ? BX.box_off[F] : 0;
+    const bool host_io = !out->on_device;
+    const size_t n = (size_t)Ntot, hw = (size_t)c->W * c->H;
+    lpf_ctx::Wide &D = c->wide;
+
+    // frame table
+    std::vector<LpfWideFrame> fr((size_t)F);
+    int nchunk = 0, maxB = 0;
+    for (int f = 0; f < F; ++f) {
+        fr[f].pt_off = frame_off[f];
+        fr[f].N = (int)(frame_off[f + 1] - frame_off[f]);
+        fr[f].chunk_off = nchunk;
+        fr[f].nchunk = (fr[f].N + LPF_WIDE_CHUNK - 1) / LPF_WIDE_CHUNK;
+        fr[f].box_off = BX.F ? BX.box_off[f] : 0;
+        fr[f].B = BX.F ? BX.box_off[f + 1] - BX.box_off[f] : 0;
+        fr[f].pad = 0;
+        nchunk += fr[f].nchunk;
+        maxB = std::max(maxB, fr[f].B);
+    }
+    if ((rc = reserve(c, D.tab, (size_t)F * sizeof(LpfWideFrame)))) return rc;
+    if ((rc = upload(c, D.tab.p, fr.data(), (size_t)F * sizeof(LpfWideFrame)))) return rc;
+
+    LpfWideParams W;
+    memset(&W, 0, sizeof W);
+    memcpy(W.cam.T, c->T, sizeof W.cam.T);
+    memcpy(W.cam.K, c->K, sizeof W.cam.K);
+    W.cam.dmin = c->dmin; W.cam.dmax = c->dmax; W.cam.W = c->W; W.cam.H = c->H;
+    W.F = F; W.M = M; W.LW = LW; W.nchunk = nchunk; W.nbw = (maxB + 63) / 64;
+    W.oriented = BX.oriented; W.inst_cap = out->inst_cap;
+    W.frames = (const LpfWideFrame *)D.tab.p;
+    W.boxp = (const double *)BX.boxp.p; W.boxq = (const float *)BX.boxq.p;
+
+    // inputs: points, masks (host masks are staged; device masks are lent), rectangles
+    if (pts_on_device || n == 0) {
+        W.pts = (const float4 *)pts;
+    } else {
+        if ((rc = reserve(c, D.pts, n * 16))) return rc;
+        LPF_HIP(c, hipMemcpyAsync(D.pts.p, pts, n * 16, hipMemcpyHostToDevice, c->stream));
+        W.pts = (const float4 *)D.pts.p;
+    }
+    const size_t esz = in->f32 ? 4 : 1;
+    const void *d_masks = in->masks;
+    const int32_t *d_rects = in->rects;
+    if (M > 0 && !in->on_device) {
+        const size_t bytes = (size_t)F * M * hw * esz;
+        if ((rc = reserve(c, D.masks, bytes))) return rc;
+        LPF_HIP(c, hipMemcpyAsync(D.masks.p, in->masks, bytes, hipMemcpyHostToDevice, c->stream));
+        d_masks = D.masks.p;
+        if (in->rects) {
+            if ((rc = reserve(c, D.rects, (size_t)F * M * 16))) return rc;
+            LPF_HIP(c, hipMemcpyAsync(D.rects.p, in->rects, (size_t)F * M * 16, hipMemcpyHostToDevice, c->stream));
+            d_rects = (const int32_t *)D.rects.p;
+        }
+    }
+    // (the rectangles hold where lpf_set_mask_rects takes them: uint8, or float under binarize 0, without erosion)
+    const int4 *rects = (in->rects && in->erode_iters == 0 && (!in->f32 || in->binarize == 0)) ? (const int4 *)d_rects : nullptr;
+
+    // ---- pack (+ erosion) into LW planes --------------------------------------------------------------------------------------
+    if (M > 0) {
+        if ((rc = reserve(c, D.planes_a, (size_t)F * LW * hw * 4))) return rc;
+        uint32_t *cur = (uint32_t *)D.planes_a.p;
+        const dim3 grid((c->W + LPF_TW - 1) / LPF_TW, (c->H + LPF_TH - 1) / LPF_TH, (unsigned)(F * LW));
+        const int fuse = in->erode_iters > 0 ? 1 : 0;
+        if (!in->f32)
+            hipLaunchKernelGGL((lpf_wide_pack<uint8_t, 0>), grid, dim3(LPF_BLOCK), 0, c->stream, (const uint8_t *)d_masks, cur, M, LW, c->H, c->W, fuse, rects);
+        else if (in->binarize == 0)
+            hipLaunchKernelGGL((lpf_wide_pack<float, 1>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, c->H, c->W, fuse, rects);
+        else if (in->binarize == 1)
+            hipLaunchKernelGGL((lpf_wide_pack<float, 2>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, c->H, c->W, fuse, rects);
+        else
+            hipLaunchKernelGGL((lpf_wide_pack<float, 3>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, c->H, c->W, fuse, rects);
+        LPF_HIP(c, hipGetLastError());
+        if (in->erode_iters > 1) {                        // further iterations: the narrow path's own kernel, a plane per (frame, word)
+            if ((rc = reserve(c, D.planes_b, (size_t)F * LW * hw * 4))) return rc;
+            uint32_t *other = (uint32_t *)D.planes_b.p;
+            for (int it = 1; it < in->erode_iters; ++it) {
+                hipLaunchKernelGGL((lpf_erode_packed<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, c->H, c->W);
+                LPF_HIP(c, hipGetLastError());
+                std::swap(cur, other);
+            }
+        }
+        W.planes = cur;
+    }
+
+    // ---- buffers: the caller's device pointers, or staging for host callers ---------------------------------------------------
+    const size_t nF = (size_t)F, nFM = (size_t)F * M, nMB = (size_t)M * Btot, ncap = out->inst_cap > 0 ? (size_t)F * out->inst_cap : 0;
+    size_t off = 0;
+    auto carve = [&](const void *want, size_t bytes) -> size_t { if (!want || !host_io) return (size_t)-1; const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_uv = carve(out->uv, n * 8), o_dep = carve(out->depth, n * 8), o_uf = carve(out->u_f, n * 8), o_vf = carve(out->v_f, n * 8),
+                 o_vi = carve(out->valid_idx, n * 8), o_uvv = carve(out->uv_valid, n * 8), o_lw = carve(out->label_words, n * LW * 4),
+                 o_lvw = carve(out->label_valid_words, n * LW * 4), o_ii = carve(out->inst_idx, ncap * 8), o_cmb = carve(out->count_mb, nMB * 4),
+                 o_nv = carve(out->n_valid, nF * 8), o_nl = carve(out->n_labelled, nF * 8), o_ic = carve(out->inst_count, nFM * 8),
+                 o_io = carve(out->inst_off, (nFM + nF) * 8), o_bc = carve(out->best_cnt, nFM * 8), o_bb = carve(out->best_box, nFM * 4),
+                 o_of = carve(out->inst_overflow, nF * 4);
+    if (host_io && off && (rc = reserve(c, D.out, off))) return rc;
+    auto dst = [&](void *user, size_t o) -> void * { return !user ? nullptr : host_io ? (void *)((char *)D.out.p + o) : user; };
+    W.uv = (int2 *)dst(out->uv, o_uv);
+    if (!W.uv) { if ((rc = reserve(c, D.uv, n * 8))) return rc; W.uv = (int2 *)D.uv.p; }
+    W.depth = (double *)dst(out->depth, o_dep); W.uf = (double *)dst(out->u_f, o_uf); W.vf = (double *)dst(out->v_f, o_vf);
+    W.valid_idx = (long long *)dst(out->valid_idx, o_vi); W.uv_valid = (int2 *)dst(out->uv_valid, o_uvv);
+    W.label_words = (uint32_t *)dst(out->label_words, o_lw);
+    if (!W.label_words) { if ((rc = reserve(c, D.words, n * LW * 4))) return rc; W.label_words = (uint32_t *)D.words.p; }
+    W.label_valid = (uint32_t *)dst(out->label_valid_words, o_lvw);
+    W.inst_idx = (long long *)dst(out->inst_idx, o_ii); W.count_out = (int32_t *)dst(out->count_mb, o_cmb);
+    W.n_valid = (long long *)dst(out->n_valid, o_nv); W.n_labelled = (long long *)dst(out->n_labelled, o_nl);
+    W.inst_count = (long long *)dst(out->inst_count, o_ic); W.inst_off = (long long *)dst(out->inst_off, o_io);
+    W.best_cnt = (long long *)dst(out->best_cnt, o_bc); W.best_box = (int32_t *)dst(out->best_box, o_bb);
+    W.inst_overflow = (int32_t *)dst(out->inst_overflow, o_of);
+    if ((rc = reserve(c, D.flags, (size_t)std::max(nchunk, 1) * LPF_WIDE_CHUNK))) return rc;
+    if ((rc = reserve(c, D.ccnt, (size_t)std::max(nchunk, 1) * 8))) return rc;
+    if ((rc = reserve(c, D.cpre, (size_t)std::max(nchunk, 1) * 8))) return rc;
+    if ((rc = reserve(c, D.fcnt, nF * 8))) return rc;
+    if ((rc = reserve(c, D.midx, n * 4))) return rc;
+    if ((rc = reserve(c, D.mwords, n * LW * 4))) return rc;
+    if ((rc = reserve(c, D.mpts, n * 16))) return rc;
+    if ((rc = reserve(c, D.cnt, nMB * 4))) return rc;
+    W.flags = (uint32_t *)D.flags.p; W.chunk_cnt = (int2 *)D.ccnt.p; W.chunk_pre = (int2 *)D.cpre.p; W.fcnt = (int2 *)D.fcnt.p;
+    W.m_idx = (int *)D.midx.p; W.m_words = (uint32_t *)D.mwords.p; W.m_pts = (float4 *)D.mpts.p; W.cnt = (unsigned *)D.cnt.p;
+
+    // ---- the launch set ------------------------------------------------------------------------------------------------------
+    if (nchunk > 0) {
+        hipLaunchKernelGGL(lpf_wide_project, dim3((unsigned)nchunk), dim3(LPF_BLOCK), 0, c->stream, W);
+        LPF_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(lpf_wide_scan, dim3((unsigned)F), dim3(LPF_BLOCK), 0, c->stream, W);
+    LPF_HIP(c, hipGetLastError());
+    if (nchunk > 0) {
+        hipLaunchKernelGGL(lpf_wide_scatter, dim3((unsigned)nchunk), dim3(LPF_BLOCK), 0, c->stream, W);
+        LPF_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(lpf_wide_lists, dim3((unsigned)(F * std::max(LW, 1))), dim3(LPF_BLOCK), 0, c->stream, W);
+    LPF_HIP(c, hipGetLastError());
+    if (M > 0) {
+        if (nMB > 0) {
+            LPF_HIP(c, hipMemsetAsync(D.cnt.p, 0, nMB * 4, c->stream));
+            hipLaunchKernelGGL(lpf_wide_boxes, dim3((unsigned)(F * LW * W.nbw), LPF_WIDE_PARTS), dim3(LPF_BLOCK), 0, c->stream, W);
+            LPF_HIP(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(lpf_wide_best, dim3((unsigned)F), dim3(LPF_BLOCK), 0, c->stream, W);
+        LPF_HIP(c, hipGetLastError());
+    }
+
+    if (host_io) {
+        auto back = [&](void *user, size_t o, size_t bytes) -> hipError_t {
+            if (!user || !bytes) return hipSuccess;
+            return hipMemcpyAsync(user, (const char *)D.out.p + o, bytes, hipMemcpyDeviceToHost, c->stream);
+        };
+        LPF_HIP(c, back(out->uv, o_uv, n * 8));
+        LPF_HIP(c, back(out->depth, o_dep, n * 8));
+        LPF_HIP(c, back(out->u_f, o_uf, n * 8));
+        LPF_HIP(c, back(out->v_f, o_vf, n * 8));
+        LPF_HIP(c, back(out->valid_idx, o_vi, n * 8));
+        LPF_HIP(c, back(out->uv_valid, o_uvv, n * 8));
+        LPF_HIP(c, back(out->label_words, o_lw, n * LW * 4));
+        LPF_HIP(c, back(out->label_valid_words, o_lvw, n * LW * 4));
+        LPF_HIP(c, back(out->inst_idx, o_ii, ncap * 8));
+        LPF_HIP(c, back(out->count_mb, o_cmb, nMB * 4));
+        LPF_HIP(c, back(out->n_valid, o_nv, nF * 8));
+        LPF_HIP(c, back(out->n_labelled, o_nl, nF * 8));
+        LPF_HIP(c, back(out->inst_count, o_ic, nFM * 8));
+        LPF_HIP(c, back(out->inst_off, o_io, (nFM + nF) * 8));
+        LPF_HIP(c, back(out->best_cnt, o_bc, nFM * 8));
+        LPF_HIP(c, back(out->best_box, o_bb, nFM * 4));
+        LPF_HIP(c, back(out->inst_overflow, o_of, nF * 4));
+    }
+    if (host_io || (M > 0 && !in->on_device) || (n > 0 && !pts_on_device)) LPF_HIP(c, host_wait(c));   // host buffers may be reused
     return LPF_OK;
 }
 

@@ -17,7 +17,7 @@ from datetime import datetime
 import numpy as np
 
 from . import _native, kitti360
-from ._native import LpfContext, LPF_MAX_MASKS, Scan, ScanReader
+from ._native import LpfContext, LPF_MAX_MASKS, LPF_MAX_MASKS_WIDE, Scan, ScanReader
 
 _CONTEXTS = {}
 
@@ -248,11 +248,16 @@ def extract_car_points_by_mask(points_valid, u_valid, v_valid, masks, camera, de
     pix[:, 1] = np.asarray(v_valid)
     pix[:, 2] = 1.0
     ctx.clear_boxes()
-    for m0 in range(0, M, LPF_MAX_MASKS):
-        ctx.set_masks(stack[m0:m0 + LPF_MAX_MASKS])
+    if M <= LPF_MAX_MASKS:
+        ctx.set_masks(stack)
         r = ctx.run(pix, want_uv=False, want_label=False)
-        for lst in r["inst_lists"]:
-            sets.append(pv[lst] if len(lst) else np.array([]).reshape(0, 3))
+        lists = r["inst_lists"]
+    else:                                                    # more detections: the wide pass (groups of 256 beyond that)
+        lists = []
+        for m0 in range(0, M, LPF_MAX_MASKS_WIDE):
+            lists += ctx.run_wide([pix], stack[m0:m0 + LPF_MAX_MASKS_WIDE], want_uv=False)[0]["inst_lists"]
+    for lst in lists:
+        sets.append(pv[lst] if len(lst) else np.array([]).reshape(0, 3))
     return sets
 
 
@@ -941,12 +946,15 @@ def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_
     if chain_all:                                                        # the erosion has been done: the masks below are uint8 0 / 1 at camera size
         erode_iters, v3_pipeline = 0, False
     M = max(s.shape[0] for s in stacks)
-    if M > LPF_MAX_MASKS:
-        # The reference loops over every mask (V3:220), with no bound; a launch labels a point with one bit per mask in a
-        # 32-bit word.  More detections than that: the frames run once per group of 32 masks (same points, same boxes) and the
-        # per-detection results are put together -- everything per point (pixels, valid indices) is the same in every pass.
+    if M > LPF_MAX_MASKS_WIDE:
+        # The reference loops over every mask (V3:220), with no bound: beyond what one wide pass takes, the frames run once per group
+        # of 256 masks and the per-detection results are put together
         return _run_frames_in_mask_groups(frames, stacks, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters,
-                                          v3_pipeline, device, ctx)
+                                          v3_pipeline, device, ctx, group=LPF_MAX_MASKS_WIDE)
+    if M > LPF_MAX_MASKS:
+        # A launch of the narrow path labels a point with one bit per mask in a 32-bit word; more detections than that take the wide
+        # pass (lpf_run_wide: ceil(M / 32) label words per point), which projects and reads every point once
+        return _run_frames_wide(frames, stacks, camera, min_points, use_oriented, erode_iters, v3_pipeline, ctx, M, H, W, gather_scans)
     on_gpu = [_is_device_tensor(s) for s in stacks]
     if any(on_gpu):                                                      # YOLO's masks still on the GPU: no host round trip
         import torch
@@ -1006,13 +1014,74 @@ def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_
     return out
 
 
+def _run_frames_wide(frames, stacks, camera, min_points, use_oriented, erode_iters, v3_pipeline, ctx, M, H, W, gather_scans):
+    """run_frames for frames with 32 < M <= 256 detections: one native wide pass per batch (lpf_run_wide), the same results as the
+    per-group passes of _run_frames_in_mask_groups."""
+    if any(_is_device_tensor(s) for s in stacks):                      # the segmenter's masks still on the GPU
+        import torch
+        if not all(_is_device_tensor(s) for s in stacks) or any(s.shape[0] != M or s.dtype != stacks[0].dtype for s in stacks):
+            raise NotImplementedError("device masks: every frame of a batch needs the same detection count and dtype")
+        batch = stacks[0][None] if len(stacks) == 1 else torch.stack(stacks)
+    else:
+        dt = np.float32 if any(t.dtype == np.float32 for t in stacks if t.shape[0]) else np.uint8
+        if all(s.shape[0] == M and s.dtype == dt for s in stacks):
+            batch = stacks[0][None] if len(stacks) == 1 else np.stack(stacks)
+        else:                                                          # ragged detection counts: pad with empty masks
+            batch = np.zeros((len(frames), M, H, W), dt)
+            for i, s in enumerate(stacks):
+                if s.shape[0]:
+                    batch[i, :s.shape[0]] = s
+    corners, positions = [], []
+    for f in frames:
+        c, pos = _corners_velo(f.bboxes_3d)
+        corners.append(c)
+        positions.append(pos)
+    ctx.set_boxes(corners, oriented=use_oriented)
+    pts = [f.points for f in frames]
+    if len(pts) == 1 and isinstance(pts[0], Scan):
+        pts[0]._check_live()
+        host = np.asarray(_LiveScanPoints(pts[0])[:, :], np.float32)
+        pts = [host]
+    elif any(isinstance(p, Scan) for p in pts):
+        pts = [np.asarray(_LiveScanPoints(p)[:, :], np.float32) if isinstance(p, Scan) else p for p in pts]
+    if len(pts) > 1 and any(_is_device_tensor(p) for p in pts):
+        pts = [p.cpu().numpy() if _is_device_tensor(p) else p for p in pts]
+    res = ctx.run_wide(pts, batch, erode_iters=erode_iters, v3_pipeline=v3_pipeline, want_uv=False, want_valid_uv=True)
+    out = []
+    for f, r, s, pos in zip(frames, res, stacks, positions):
+        m = s.shape[0]
+        vi = r["valid_idx"].copy()
+        uvv = r["uv_valid"].copy()
+        labv = r["label_valid_words"].copy()
+        lists = [l.copy() for l in r["inst_lists"][:m]]
+        is_scan = isinstance(f.points, Scan)
+        host_pts = _LiveScanPoints(f.points) if is_scan else f.points
+        if _is_device_tensor(host_pts):
+            host_pts = _DevicePoints(host_pts)
+        stats = []
+        if f.bboxes_3d and m:
+            stats = stats_from_counts(r["inst_count"][:m], r["count_mb"][:m], f.colors, min_points, pos)
+            for d in stats:
+                d.pop("_best_col"), d.pop("_best_count")
+        lazy = dict(u_valid=lambda uvv=uvv: uvv[:, 0].astype(np.int64), v_valid=lambda uvv=uvv: uvv[:, 1].astype(np.int64),
+                    points_valid=lambda p=host_pts, vi=vi: p[vi, :3],
+                    car_point_sets=lambda p=host_pts, ls=lists: [p[l, :3] if len(l) else np.array([]).reshape(0, 3) for l in ls],
+                    bg_assigned=lambda labv=labv: (labv != 0).any(axis=1) if labv.ndim == 2 else labv != 0)
+        fr = FrameResult(dict(frame=f.frame, valid_indices=vi, count_mb=r["count_mb"][:m].copy(), car_statistics=stats, n_valid=r["n_valid"]), lazy)
+        if is_scan and gather_scans:
+            fr._all()
+        out.append(fr)
+    return out
+
+
 def _run_frames_in_mask_groups(frames, stacks, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline,
-                               device, ctx):
-    """run_frames for frames with more than LPF_MAX_MASKS detections: one pass per group of 32 masks, results merged."""
+                               device, ctx, group=LPF_MAX_MASKS):
+    """run_frames for frames with more masks than one pass takes: one pass per group of ``group`` masks, results merged.  (With the
+    default 32 every pass is the narrow path: the yardstick of the wide pass.)"""
     M = max(s.shape[0] for s in stacks)
     merged = None
-    for g0 in range(0, M, LPF_MAX_MASKS):
-        part = [FrameInputs(f.frame, f.points, s[g0:g0 + LPF_MAX_MASKS], f.bboxes_3d, f.colors[g0:g0 + LPF_MAX_MASKS], f.boxes_2d)
+    for g0 in range(0, M, group):
+        part = [FrameInputs(f.frame, f.points, s[g0:g0 + group], f.bboxes_3d, f.colors[g0:g0 + group], f.boxes_2d)
                 for f, s in zip(frames, stacks)]
         res = run_frames(part, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline, device, ctx)
         if merged is None:
