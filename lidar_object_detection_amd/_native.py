@@ -842,61 +842,104 @@ class LpfContext:
             ent = self._pin[name] = (p, cap, np.frombuffer((ctypes.c_uint8 * cap).from_address(p), dtype=np.uint8))
         return ent[2][:need].view(dtype).reshape(shape)
 
+    def _stage_points(self, frames):
+        """Where the library reads a run's points: (frame offsets int64 [F+1], pointer, on_device, what must stay alive until the run
+        returns).  ONE Scan of a ScanReader is read where it already is, in HBM; ONE float32 [N,4] GPU tensor too (ordered with
+        torch's current stream).  Several frames -- host arrays, Scans, GPU tensors -- each go to their place in ONE device tensor:
+        no concatenation of the batch on the host first (20 real frames are 37 MB: the copy cost as much as their kernels a hundred
+        times over).  Without torch's GPU support they are concatenated on the host."""
+        pts = []
+        for p in frames:
+            if isinstance(p, Scan):
+                p._check_live()
+            elif _is_torch(p):
+                if p.ndim != 2 or p.shape[1] != 4:
+                    raise ValueError("device points must be a float32 tensor [N,4]")
+            else:
+                p = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 4)
+            pts.append(p)
+        if not pts:
+            raise ValueError("no frames")
+        off = np.zeros(len(pts) + 1, np.int64)
+        off[1:] = np.cumsum([len(p.points) if isinstance(p, Scan) else int(p.shape[0]) for p in pts])
+        n = int(off[-1])
+        one = pts[0] if len(pts) == 1 else None
+        if isinstance(one, Scan):
+            return off, (one.dev_ptr if n else None), 1, one
+        if _is_torch(one):
+            import torch
+            self.wait_for_stream(torch.cuda.current_stream(one.device).cuda_stream)      # the tensor was produced on torch's stream
+            return off, (_dev_ptr(one, "float32") if n else None), 1, one
+        pts = [p.points if isinstance(p, Scan) else p for p in pts]
+        if len(pts) > 1 and n:
+            try:
+                import torch
+                if torch.cuda.is_available():
+                    batch = torch.empty((n, 4), dtype=torch.float32, device=torch.device("cuda", self.device))
+                    for f, p in enumerate(pts):
+                        if p.shape[0]:
+                            batch[int(off[f]):int(off[f + 1])].copy_(p if _is_torch(p) else torch.from_numpy(p))
+                    self.wait_for_stream(torch.cuda.current_stream(batch.device).cuda_stream)
+                    return off, batch.data_ptr(), 1, batch
+            except ImportError:
+                pass
+        host = np.concatenate([p.cpu().numpy() if _is_torch(p) else p for p in pts], axis=0) if len(pts) > 1 else pts[0]
+        return off, (host.ctypes.data if n else None), 0, host
+
+    @staticmethod
+    def _until_lists_fit(launch, inst_cap, off):
+        """launch(inst_cap) -> (outputs, 0 or the capacity the instance lists need when they did not fit): run again with the exact
+        capacity, once it is known"""
+        o = off.tolist()
+        cap = max(max(b - a for a, b in zip(o, o[1:])), 1) if inst_cap is None else inst_cap
+        while True:
+            out, need = launch(cap)
+            if not need:
+                return out
+            cap = need
+
+    def _frame_results(self, off, M, summ, per_point, per_valid, iidx, cmb):
+        """One dict per frame of a run's outputs: the frame's row of the summary columns ``summ`` (n_valid, n_labelled, inst_count,
+        inst_off, best_box, best_cnt), its rows of the ``per_point`` arrays [Ntot, ...], the first n_valid rows of its part of the
+        ``per_valid`` arrays, its instance lists out of ``iidx`` and its [M, B_f] block of the counts ``cmb``."""
+        nv, nl, ic, io, bb, bc = (summ[k] for k in ("n_valid", "n_labelled", "inst_count", "inst_off", "best_box", "best_cnt"))
+        res = []
+        for f in range(len(off) - 1):
+            a, b = int(off[f]), int(off[f + 1])
+            n_valid = int(nv[f])
+            r = dict(n_valid=n_valid, n_labelled=int(nl[f]), inst_count=ic[f, :M].copy(), best_box=bb[f, :M].copy(),
+                     best_cnt=bc[f, :M].copy())
+            for k, x in per_point.items():
+                r[k] = x[a:b]
+            for k, x in per_valid.items():
+                r[k] = x[a:a + n_valid]
+            if per_valid:                                                     # (want_lists)
+                o = io[f].tolist()
+                r["inst_lists"] = [iidx[f, o[m]:o[m + 1]] for m in range(M)] if iidx is not None else []
+            if self.box_off is not None:
+                b0, b1 = int(self.box_off[f]), int(self.box_off[f + 1])
+                r["count_mb"] = cmb[M * b0:M * b1].reshape(M, b1 - b0).astype(np.int64)
+            else:
+                r["count_mb"] = np.zeros((M, 0), np.int64)
+            res.append(r)
+        return res
+
     def run_batch(self, frames, want_uv=True, want_label=True, want_float=False, want_lists=True,
                   inst_cap=None, want_valid_uv=False, pinned=False):
-        """frames: list of f32[N_f,4] arrays.  Returns one dict per frame with
+        """frames: list of f32[N_f,4] arrays, Scans of a ScanReader or float32 [N_f,4] GPU tensors (see _stage_points).  Returns one
+        dict per frame with
         u, v (int32), label_bits, valid_idx, inst_lists, inst_count, count_mb, best_box, best_cnt,
         n_valid, n_labelled (+ depth, uf, vf with want_float; + u_valid, v_valid, label_valid with
         want_valid_uv: the values at the valid points only -- with want_uv/want_label off, a quarter of the read-back).
         pinned=True: the result arrays are views into page-locked buffers the context owns and reuses -- valid until the next
         run on this context (copy what must live longer); the frame loops use it."""
-        scan = frames[0] if (len(frames) == 1 and isinstance(frames[0], Scan)) else None
-        dev_pts = frames[0] if (len(frames) == 1 and _is_torch(frames[0])) else None
-        if scan is not None:                     # points already in HBM (ScanReader): no host staging
-            frames = [scan.points]
-        elif dev_pts is not None:                # ... or a float32 [N,4] torch tensor on the GPU (ordered with torch's current stream)
-            if dev_pts.ndim != 2 or dev_pts.shape[1] != 4:
-                raise ValueError("device points must be a float32 tensor [N,4]")
-            frames = [np.empty((int(dev_pts.shape[0]), 4), np.float32)]      # (only its shape is used below)
-        elif any(isinstance(p, Scan) or _is_torch(p) for p in frames):
-            raise ValueError("a Scan from a ScanReader / a GPU tensor of points is processed on its own (one frame per run)")
-        frames = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 4) for p in frames]
-        F = len(frames)
-        off = np.zeros(F + 1, np.int64)
-        off[1:] = np.cumsum([p.shape[0] for p in frames])
-        n = int(off[-1])
-        batch_dev = None
-        if F > 1 and n and scan is None and dev_pts is None:
-            # several host frames: each goes to its place in ONE device tensor -- no concatenation of the batch on the host first
-            # (20 real frames are 37 MB: the copy cost as much as their kernels a hundred times over)
-            try:
-                import torch
-                if torch.cuda.is_available():
-                    batch_dev = torch.empty((n, 4), dtype=torch.float32, device=torch.device("cuda", self.device))
-                    for f_, p_ in enumerate(frames):
-                        if p_.shape[0]:
-                            batch_dev[int(off[f_]):int(off[f_ + 1])].copy_(torch.from_numpy(p_))
-                    self.wait_for_stream(torch.cuda.current_stream(batch_dev.device).cuda_stream)
-            except ImportError:
-                batch_dev = None
-        if batch_dev is not None:
-            pts, pts_ptr, pts_dev = None, batch_dev.data_ptr(), 1
-        else:
-            pts = np.concatenate(frames, axis=0) if F > 1 else frames[0]
-            pts_ptr, pts_dev = (pts.ctypes.data if n else None), 0
-        if scan is not None:
-            scan._check_live()
-            pts_ptr, pts_dev = (scan.dev_ptr if n else None), 1
-        elif dev_pts is not None:
-            import torch
-            self.wait_for_stream(torch.cuda.current_stream(dev_pts.device).cuda_stream)      # the tensor was produced on torch's stream
-            pts_ptr, pts_dev = (_dev_ptr(dev_pts, "float32") if n else None), 1
+        off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the run returns)
+        F, n = len(off) - 1, int(off[-1])
         M = self.M if self.F_masks else 0
         Btot = int(self.box_off[-1]) if self.box_off is not None else 0
-        if inst_cap is None:
-            inst_cap = max(int(max(p.shape[0] for p in frames)), 1)
         new = (lambda name, shape, dt: self._pinned(name, shape, dt)) if pinned else (lambda name, shape, dt: np.empty(shape, dt))
-        while True:
+
+        def launch(inst_cap):
             o = Outputs()
             o.on_device = 0
             uv = new("uv", (n, 2), np.int32) if want_uv else None
@@ -918,43 +961,27 @@ class LpfContext:
                 setattr(o, name, arr.ctypes.data if arr is not None else None)
             o.inst_cap = inst_cap
             self._check(self._lib.lpf_run_batch(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(o)))
-            if iidx is not None and summ["inst_overflow"].any():
-                inst_cap = int(summ["inst_off"][:, 32].max())      # exact size now known: run again
-                continue
-            break
-        res = []
-        for f in range(F):
-            a, b = int(off[f]), int(off[f + 1])
-            s = summ[f]
-            r = dict(n_valid=int(s["n_valid"]), n_labelled=int(s["n_labelled"]),
-                     inst_count=s["inst_count"][:M].copy(), best_box=s["best_box"][:M].copy(),
-                     best_cnt=s["best_cnt"][:M].copy())
+            per_point = {}
             if want_uv:
-                r["u"], r["v"] = uv[a:b, 0], uv[a:b, 1]
+                per_point.update(u=uv[:, 0], v=uv[:, 1])
             if want_label:
-                r["label_bits"] = lab[a:b]
+                per_point.update(label_bits=lab)
             if want_float:
-                r["depth"], r["uf"], r["vf"] = dep[a:b], uf[a:b], vf[a:b]
-            if want_lists:
-                r["valid_idx"] = vidx[a:a + r["n_valid"]]
-                if uvv is not None:
-                    r["uv_valid"] = uvv[a:a + r["n_valid"]]                      # contiguous [n_valid, 2]; u / v are its columns
-                    r["u_valid"], r["v_valid"] = r["uv_valid"][:, 0], r["uv_valid"][:, 1]
-                    r["label_valid"] = labv[a:a + r["n_valid"]]
-                r["inst_lists"] = [iidx[f, int(s["inst_off"][m]):int(s["inst_off"][m + 1])] for m in range(M)] \
-                    if iidx is not None else []
-            if self.box_off is not None:
-                b0, b1 = int(self.box_off[f]), int(self.box_off[f + 1])
-                r["count_mb"] = cmb[M * b0:M * b1].reshape(M, b1 - b0).astype(np.int64)
-            else:
-                r["count_mb"] = np.zeros((M, 0), np.int64)
-            res.append(r)
-        return res
+                per_point.update(depth=dep, uf=uf, vf=vf)
+            per_valid = dict(valid_idx=vidx) if want_lists else {}
+            if uvv is not None:
+                per_valid.update(uv_valid=uvv, u_valid=uvv[:, 0], v_valid=uvv[:, 1], label_valid=labv)   # uv_valid: contiguous [n_valid, 2]
+            need = int(summ["inst_off"][:, 32].max()) if (iidx is not None and summ["inst_overflow"].any()) else 0
+            return (summ, per_point, per_valid, iidx, cmb), need
+
+        out = self._until_lists_fit(launch, inst_cap, off)
+        return self._frame_results(off, M, *out)
 
     def run_wide(self, frames, masks, erode_iters=0, binarize="astype", rects=None, v3_pipeline=False, want_uv=True, want_float=False,
                  want_lists=True, want_valid_uv=False, inst_cap=None):
         """Frames with up to 256 masks each in ONE native pass (lpf_run_wide): every point is projected and read once.
-        frames: list of f32[N_f,4] host arrays, or ONE float32 [N,4] GPU tensor.  masks: [M,H,W] or [F,M,H,W] (uint8 / bool, or
+        frames: as run_batch's -- f32[N_f,4] host arrays, Scans of a ScanReader (read in HBM where they are), float32 [N,4] GPU
+        tensors.  masks: [M,H,W] or [F,M,H,W] (uint8 / bool, or
         float32 under ``binarize`` as set_masks), host or GPU (lent until the call returns: it waits for its results).  rects: the
         optional [F,M,4] hint of set_mask_rects.  Boxes and camera are the ones in force; the masks, boxes and rectangles of the
         narrow calls are left as they are.  Returns one dict per frame with what run_batch returns -- inst_count, best_box,
@@ -962,31 +989,13 @@ class LpfContext:
         and with want_valid_uv label_valid_words [n_valid, LW]."""
         if v3_pipeline:
             binarize = "v3"
-        dev_pts = frames[0] if (len(frames) == 1 and _is_torch(frames[0])) else None
-        if dev_pts is not None:
-            if dev_pts.ndim != 2 or dev_pts.shape[1] != 4 or str(dev_pts.dtype) != "torch.float32":
-                raise ValueError("device points must be a float32 tensor [N,4]")
-            sizes = [int(dev_pts.shape[0])]
-        else:
-            if any(_is_torch(p) or isinstance(p, Scan) for p in frames):
-                raise ValueError("a GPU tensor of points is processed on its own (one frame per run)")
-            frames = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 4) for p in frames]
-            sizes = [p.shape[0] for p in frames]
-        F = len(sizes)
+        F = len(frames)
         if F == 0:
             raise ValueError("no frames")
         masks, M, is_f, mdev, rects = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
         LW = (M + 31) // 32
-        off = np.zeros(F + 1, np.int64)
-        off[1:] = np.cumsum(sizes)
+        off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the run returns)
         n = int(off[-1])
-        if dev_pts is not None:
-            import torch
-            self.wait_for_stream(torch.cuda.current_stream(dev_pts.device).cuda_stream)
-            pts_ptr, pts_dev, keep_pts = (_dev_ptr(dev_pts, "float32") if n else None), 1, dev_pts
-        else:
-            keep_pts = np.concatenate(frames, axis=0) if F > 1 else frames[0]
-            pts_ptr, pts_dev = (keep_pts.ctypes.data if n else None), 0
         if mdev:
             import torch
             self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
@@ -996,9 +1005,8 @@ class LpfContext:
         inp.M, inp.f32, inp.binarize, inp.erode_iters = M, int(is_f), self.BINARIZE[binarize], int(erode_iters)
         inp.on_device = 1 if mdev else 0
         Btot = int(self.box_off[-1]) if self.box_off is not None else 0
-        if inst_cap is None:
-            inst_cap = max(max(sizes), 1)
-        while True:
+
+        def launch(inst_cap):
             o = WideOutputs()
             o.on_device = 0
             uv = np.empty((n, 2), np.int32) if want_uv else None
@@ -1019,34 +1027,20 @@ class LpfContext:
                 setattr(o, name, arr.ctypes.data if (arr is not None and arr.size) else None)
             o.inst_cap = inst_cap
             self._check(self._lib.lpf_run_wide(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
-            if iidx is not None and ov.any():
-                inst_cap = int(io[:, M].max())                   # exact size now known: run again
-                continue
-            break
-        del keep_pts
-        res = []
-        for f in range(F):
-            a, b = int(off[f]), int(off[f + 1])
-            r = dict(n_valid=int(nv[f]), n_labelled=int(nl[f]), inst_count=ic[f].copy(), best_box=bb[f].copy(), best_cnt=bc[f].copy(),
-                     label_words=words[a:b])
+            summ = dict(n_valid=nv, n_labelled=nl, inst_count=ic, inst_off=io, best_box=bb, best_cnt=bc)
+            per_point = dict(label_words=words)
             if want_uv:
-                r["u"], r["v"] = uv[a:b, 0], uv[a:b, 1]
+                per_point.update(u=uv[:, 0], v=uv[:, 1])
             if want_float:
-                r["depth"], r["uf"], r["vf"] = dep[a:b], uf[a:b], vf[a:b]
-            if want_lists:
-                r["valid_idx"] = vidx[a:a + r["n_valid"]]
-                if uvv is not None:
-                    r["uv_valid"] = uvv[a:a + r["n_valid"]]
-                    r["u_valid"], r["v_valid"] = r["uv_valid"][:, 0], r["uv_valid"][:, 1]
-                    r["label_valid_words"] = lvw[a:a + r["n_valid"]]
-                r["inst_lists"] = [iidx[f, int(io[f, m]):int(io[f, m + 1])] for m in range(M)] if iidx is not None else []
-            if self.box_off is not None:
-                b0, b1 = int(self.box_off[f]), int(self.box_off[f + 1])
-                r["count_mb"] = cmb[M * b0:M * b1].reshape(M, b1 - b0).astype(np.int64)
-            else:
-                r["count_mb"] = np.zeros((M, 0), np.int64)
-            res.append(r)
-        return res
+                per_point.update(depth=dep, uf=uf, vf=vf)
+            per_valid = dict(valid_idx=vidx) if want_lists else {}
+            if uvv is not None:
+                per_valid.update(uv_valid=uvv, u_valid=uvv[:, 0], v_valid=uvv[:, 1], label_valid_words=lvw)
+            need = int(io[:, M].max()) if (iidx is not None and ov.any()) else 0
+            return (summ, per_point, per_valid, iidx, cmb), need
+
+        out = self._until_lists_fit(launch, inst_cap, off)
+        return self._frame_results(off, M, *out)
 
     # -- the hot path, device tensors (asynchronous) -------------------------------------
     def run_device(self, pts, frame_off, uv=None, label_bits=None, depth=None, u_f=None, v_f=None,

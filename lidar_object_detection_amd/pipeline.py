@@ -921,6 +921,45 @@ def _host_masks_to_device_batch(stacks, M, H, W, ctx):
     return t
 
 
+def _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline):
+    """(per-frame mask stacks at the camera's size, erode_iters, v3_pipeline still owed to the pass) of a batch: the one place that
+    decides how masks of another size than the camera's are treated.  They go through cv2.resize as V3:222 does it, on the GPU; with
+    the V3 erosion block in force they are eroded at their own size first, as V3:82-97 does before V3:222 (_mask_stack's chain), and
+    then so are the batch's other frames, by the same chain -- a batch is eroded either all in the pass or all here.  Which frames
+    took the chain is what _mask_stack reports, whatever form their masks came in."""
+    def stack(f, force_chain=False):
+        return _mask_stack(f.masks if f.masks is not None else [], camera, resize_ctx=ctx, erode_iters=erode_iters,
+                           v3_pipeline=v3_pipeline, force_chain=force_chain)
+    done = [stack(f) for f in frames]
+    if not any(eroded for _, eroded in done):
+        return [s for s, _ in done], erode_iters, v3_pipeline
+    return [s if eroded else stack(f, force_chain=True)[0] for f, (s, eroded) in zip(frames, done)], 0, False
+
+
+def _mask_batch(stacks, M, H, W, ctx):
+    """The frames' mask stacks as ONE [F,M,H,W] batch for a pass (frames with fewer detections padded with empty masks)."""
+    on_gpu = [_is_device_tensor(s) for s in stacks]
+    if any(on_gpu):                                                      # YOLO's masks still on the GPU: no host round trip
+        import torch
+        if not all(on_gpu) or any(s.shape[0] != M or s.dtype != stacks[0].dtype for s in stacks):
+            raise NotImplementedError("device masks: every frame of a batch needs the same detection count and dtype")
+        batch = stacks[0][None] if len(stacks) == 1 else torch.stack(stacks)
+        ctx.wait_for_stream(torch.cuda.current_stream(batch.device).cuda_stream)    # the masks were produced on torch's stream
+        return batch
+    if len(stacks) > 1 and (batch := _host_masks_to_device_batch(stacks, M, H, W, ctx)) is not None:
+        # several frames of host masks: each frame's masks go to their place in ONE device tensor -- no np.stack of the batch on the
+        # host first (32 frames of five float masks are 340 MB: the copy cost more than everything else in the call)
+        return batch
+    dt = np.float32 if any(s.dtype == np.float32 for s in stacks if s.shape[0]) else np.uint8
+    if all(s.shape[0] == M and s.dtype == dt for s in stacks):
+        return stacks[0][None] if len(stacks) == 1 else np.stack(stacks)     # the usual case: no padding, no extra copy
+    batch = np.zeros((len(stacks), M, H, W), dt)                         # ragged detection counts: pad with empty masks
+    for i, s in enumerate(stacks):
+        if s.shape[0]:
+            batch[i, :s.shape[0]] = s
+    return batch
+
+
 def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_oriented=True,
                erode_iters=0, v3_pipeline=False, device=0, ctx=None, gather_scans=True):
     """Projection + clip + mask lookup + box counting + best-box scan for a list of
@@ -935,143 +974,57 @@ def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_
     ctx = ctx or get_context(device)
     H, W = camera.height, camera.width
     ctx.set_camera(TrVeloToRect, camera.K, W, H, 0.0, float(depth_max))
-    # (masks of another size than the camera's: cv2.resize as V3:222, on the GPU; with the V3 erosion block in force such masks are
-    #  eroded at their own size first, as V3:82-97 does before V3:222 -- and then so are the batch's other frames, by the same chain)
-    def _off_size(mk):
-        shp = tuple(getattr(mk, "shape", ())) if mk is not None else ()
-        return len(shp) == 3 and shp[0] > 0 and shp[1:] != (H, W)
-    chain_all = bool(erode_iters or v3_pipeline) and any(_off_size(f.masks) for f in frames)
-    stacks = [_mask_stack(f.masks if f.masks is not None else [], camera, resize_ctx=ctx, erode_iters=erode_iters, v3_pipeline=v3_pipeline,
-                          force_chain=chain_all)[0] for f in frames]
-    if chain_all:                                                        # the erosion has been done: the masks below are uint8 0 / 1 at camera size
-        erode_iters, v3_pipeline = 0, False
-    M = max(s.shape[0] for s in stacks)
+    stacks, erode_iters, v3_pipeline = _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline)
+    counts = [s.shape[0] for s in stacks]
+    M = max(counts)
     if M > LPF_MAX_MASKS_WIDE:
         # The reference loops over every mask (V3:220), with no bound: beyond what one wide pass takes, the frames run once per group
         # of 256 masks and the per-detection results are put together
         return _run_frames_in_mask_groups(frames, stacks, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters,
                                           v3_pipeline, device, ctx, group=LPF_MAX_MASKS_WIDE)
-    if M > LPF_MAX_MASKS:
+    batch = _mask_batch(stacks, M, H, W, ctx)
+    corners, positions = zip(*(_corners_velo(f.bboxes_3d) for f in frames))
+    pts = [f.points for f in frames]
+    # only the valid points' pixels and labels are used below: fetch those (a quarter of the dense arrays on real frames)
+    if M <= LPF_MAX_MASKS:
+        ctx.set_masks(batch, erode_iters=erode_iters, v3_pipeline=v3_pipeline, lend=True)   # (the run follows in this call: GPU masks can be lent)
+        ctx.set_boxes(list(corners), oriented=use_oriented)
+        # (results arrive in page-locked buffers the context reuses: _frame_result copies out what is handed to the caller)
+        res = ctx.run_batch(pts, want_uv=False, want_label=False, want_valid_uv=True, pinned=True)
+    else:
         # A launch of the narrow path labels a point with one bit per mask in a 32-bit word; more detections than that take the wide
         # pass (lpf_run_wide: ceil(M / 32) label words per point), which projects and reads every point once
-        return _run_frames_wide(frames, stacks, camera, min_points, use_oriented, erode_iters, v3_pipeline, ctx, M, H, W, gather_scans)
-    on_gpu = [_is_device_tensor(s) for s in stacks]
-    if any(on_gpu):                                                      # YOLO's masks still on the GPU: no host round trip
-        import torch
-        if not all(on_gpu) or any(s.shape[0] != M or s.dtype != stacks[0].dtype for s in stacks):
-            raise NotImplementedError("device masks: every frame of a batch needs the same detection count and dtype")
-        batch = stacks[0][None] if len(stacks) == 1 else torch.stack(stacks)
-        ctx.wait_for_stream(torch.cuda.current_stream(batch.device).cuda_stream)    # the masks were produced on torch's stream
-        stacks = [np.empty((M, 0, 0), np.uint8)] * len(stacks)          # only their detection count is used below
-    elif len(stacks) > 1 and (batch := _host_masks_to_device_batch(stacks, M, H, W, ctx)) is not None:
-        # several frames of host masks: each frame's masks go to their place in ONE device tensor -- no np.stack of the batch on the
-        # host first (32 frames of five float masks are 340 MB: the copy cost more than everything else in the call)
-        stacks = [np.empty((s.shape[0], 0, 0), np.uint8) for s in stacks]
-    elif all(s.shape[0] == M and s.dtype == (np.float32 if any(t.dtype == np.float32 for t in stacks if t.shape[0]) else np.uint8) for s in stacks):
-        batch = stacks[0][None] if len(stacks) == 1 else np.stack(stacks)   # the usual case: no padding, no extra copy
-    else:                                                               # ragged detection counts: pad with empty masks
-        dt = np.float32 if any(t.dtype == np.float32 for t in stacks if t.shape[0]) else np.uint8
-        batch = np.zeros((len(frames), M, H, W), dt)
-        for i, s in enumerate(stacks):
-            if s.shape[0]:
-                batch[i, :s.shape[0]] = s
-    corners, positions = [], []
-    for f in frames:
-        c, pos = _corners_velo(f.bboxes_3d)
-        corners.append(c)
-        positions.append(pos)
-    ctx.set_masks(batch, erode_iters=erode_iters, v3_pipeline=v3_pipeline, lend=True)   # (the run follows in this call: GPU masks can be lent)
-    ctx.set_boxes(corners, oriented=use_oriented)
-    # only the valid points' pixels and labels are used below: fetch those (a quarter of the dense arrays on real frames)
-    # (results arrive in page-locked buffers the context reuses: what is handed to the caller is copied out of them below)
-    res = ctx.run_batch([f.points for f in frames], want_uv=False, want_label=False, want_valid_uv=True, pinned=True)
-    out = []
-    for f, r, s, pos in zip(frames, res, stacks, positions):
-        m = s.shape[0]
-        # (the result arrays live in page-locked buffers the context reuses: what outlives this call is copied out of them here -- the
-        #  compact lists, a few hundred KB -- and the gathers / casts of the reference's types are made from those copies when read)
-        vi = r["valid_idx"].copy()
-        uvv = r["uv_valid"].copy()                                       # int32 [n_valid, 2]: one contiguous copy
-        labv = r["label_valid"].copy()
-        lists = [l.copy() for l in r["inst_lists"][:m]]
-        is_scan = isinstance(f.points, Scan)
-        host_pts = _LiveScanPoints(f.points) if is_scan else f.points    # Scan: pinned copy of the file, while the reader has not moved on
-        if _is_device_tensor(host_pts):                                  # points that live on the GPU: the gathers run there when asked for
-            host_pts = _DevicePoints(host_pts)
-        stats = []
-        if f.bboxes_3d and m:
-            stats = stats_from_counts(r["inst_count"][:m], r["count_mb"][:m], f.colors, min_points, pos)
-            for d in stats:
-                d.pop("_best_col"), d.pop("_best_count")
-        lazy = dict(u_valid=lambda uvv=uvv: uvv[:, 0].astype(np.int64), v_valid=lambda uvv=uvv: uvv[:, 1].astype(np.int64),
-                    points_valid=lambda p=host_pts, vi=vi: p[vi, :3],
-                    car_point_sets=lambda p=host_pts, ls=lists: [p[l, :3] if len(l) else np.array([]).reshape(0, 3) for l in ls],
-                    bg_assigned=lambda labv=labv: labv != 0)
-        fr = FrameResult(dict(frame=f.frame, valid_indices=vi, count_mb=r["count_mb"][:m].copy(), car_statistics=stats, n_valid=r["n_valid"]), lazy)
-        if is_scan and gather_scans:
-            fr._all()                                        # (a Scan's pinned points are recycled when the reader moves on: gather now)
-        out.append(fr)
-    return out
+        ctx.set_boxes(list(corners), oriented=use_oriented)
+        res = ctx.run_wide(pts, batch, erode_iters=erode_iters, v3_pipeline=v3_pipeline, want_uv=False, want_valid_uv=True)
+    return [_frame_result(f, r, m, pos, min_points, gather_scans) for f, r, m, pos in zip(frames, res, counts, positions)]
 
 
-def _run_frames_wide(frames, stacks, camera, min_points, use_oriented, erode_iters, v3_pipeline, ctx, M, H, W, gather_scans):
-    """run_frames for frames with 32 < M <= 256 detections: one native wide pass per batch (lpf_run_wide), the same results as the
-    per-group passes of _run_frames_in_mask_groups."""
-    if any(_is_device_tensor(s) for s in stacks):                      # the segmenter's masks still on the GPU
-        import torch
-        if not all(_is_device_tensor(s) for s in stacks) or any(s.shape[0] != M or s.dtype != stacks[0].dtype for s in stacks):
-            raise NotImplementedError("device masks: every frame of a batch needs the same detection count and dtype")
-        batch = stacks[0][None] if len(stacks) == 1 else torch.stack(stacks)
-    else:
-        dt = np.float32 if any(t.dtype == np.float32 for t in stacks if t.shape[0]) else np.uint8
-        if all(s.shape[0] == M and s.dtype == dt for s in stacks):
-            batch = stacks[0][None] if len(stacks) == 1 else np.stack(stacks)
-        else:                                                          # ragged detection counts: pad with empty masks
-            batch = np.zeros((len(frames), M, H, W), dt)
-            for i, s in enumerate(stacks):
-                if s.shape[0]:
-                    batch[i, :s.shape[0]] = s
-    corners, positions = [], []
-    for f in frames:
-        c, pos = _corners_velo(f.bboxes_3d)
-        corners.append(c)
-        positions.append(pos)
-    ctx.set_boxes(corners, oriented=use_oriented)
-    pts = [f.points for f in frames]
-    if len(pts) == 1 and isinstance(pts[0], Scan):
-        pts[0]._check_live()
-        host = np.asarray(_LiveScanPoints(pts[0])[:, :], np.float32)
-        pts = [host]
-    elif any(isinstance(p, Scan) for p in pts):
-        pts = [np.asarray(_LiveScanPoints(p)[:, :], np.float32) if isinstance(p, Scan) else p for p in pts]
-    if len(pts) > 1 and any(_is_device_tensor(p) for p in pts):
-        pts = [p.cpu().numpy() if _is_device_tensor(p) else p for p in pts]
-    res = ctx.run_wide(pts, batch, erode_iters=erode_iters, v3_pipeline=v3_pipeline, want_uv=False, want_valid_uv=True)
-    out = []
-    for f, r, s, pos in zip(frames, res, stacks, positions):
-        m = s.shape[0]
-        vi = r["valid_idx"].copy()
-        uvv = r["uv_valid"].copy()
-        labv = r["label_valid_words"].copy()
-        lists = [l.copy() for l in r["inst_lists"][:m]]
-        is_scan = isinstance(f.points, Scan)
-        host_pts = _LiveScanPoints(f.points) if is_scan else f.points
-        if _is_device_tensor(host_pts):
-            host_pts = _DevicePoints(host_pts)
-        stats = []
-        if f.bboxes_3d and m:
-            stats = stats_from_counts(r["inst_count"][:m], r["count_mb"][:m], f.colors, min_points, pos)
-            for d in stats:
-                d.pop("_best_col"), d.pop("_best_count")
-        lazy = dict(u_valid=lambda uvv=uvv: uvv[:, 0].astype(np.int64), v_valid=lambda uvv=uvv: uvv[:, 1].astype(np.int64),
-                    points_valid=lambda p=host_pts, vi=vi: p[vi, :3],
-                    car_point_sets=lambda p=host_pts, ls=lists: [p[l, :3] if len(l) else np.array([]).reshape(0, 3) for l in ls],
-                    bg_assigned=lambda labv=labv: (labv != 0).any(axis=1) if labv.ndim == 2 else labv != 0)
-        fr = FrameResult(dict(frame=f.frame, valid_indices=vi, count_mb=r["count_mb"][:m].copy(), car_statistics=stats, n_valid=r["n_valid"]), lazy)
-        if is_scan and gather_scans:
-            fr._all()
-        out.append(fr)
-    return out
+def _frame_result(f, r, m, pos, min_points, gather_scans):
+    """The FrameResult of frame ``f`` (``m`` detections, boxes at ``pos`` of its list) from the pass's dict ``r``: run_batch's, whose
+    label_valid holds one word per valid point, or run_wide's, whose label_valid_words hold ceil(M / 32)."""
+    # (the result arrays may live in page-locked buffers the context reuses: what outlives this call is copied out of them here -- the
+    #  compact lists, a few hundred KB -- and the gathers / casts of the reference's types are made from those copies when read)
+    vi = r["valid_idx"].copy()
+    uvv = r["uv_valid"].copy()                                           # int32 [n_valid, 2]: one contiguous copy
+    labv = (r["label_valid"] if "label_valid" in r else r["label_valid_words"]).copy()
+    lists = [l.copy() for l in r["inst_lists"][:m]]
+    is_scan = isinstance(f.points, Scan)
+    host_pts = _LiveScanPoints(f.points) if is_scan else f.points        # Scan: pinned copy of the file, while the reader has not moved on
+    if _is_device_tensor(host_pts):                                      # points that live on the GPU: the gathers run there when asked for
+        host_pts = _DevicePoints(host_pts)
+    stats = []
+    if f.bboxes_3d and m:
+        stats = stats_from_counts(r["inst_count"][:m], r["count_mb"][:m], f.colors, min_points, pos)
+        for d in stats:
+            d.pop("_best_col"), d.pop("_best_count")
+    lazy = dict(u_valid=lambda uvv=uvv: uvv[:, 0].astype(np.int64), v_valid=lambda uvv=uvv: uvv[:, 1].astype(np.int64),
+                points_valid=lambda p=host_pts, vi=vi: p[vi, :3],
+                car_point_sets=lambda p=host_pts, ls=lists: [p[l, :3] if len(l) else np.array([]).reshape(0, 3) for l in ls],
+                bg_assigned=lambda labv=labv: labv != 0 if labv.ndim == 1 else (labv != 0).any(axis=1))
+    fr = FrameResult(dict(frame=f.frame, valid_indices=vi, count_mb=r["count_mb"][:m].copy(), car_statistics=stats, n_valid=r["n_valid"]), lazy)
+    if is_scan and gather_scans:
+        fr._all()                                            # (a Scan's pinned points are recycled when the reader moves on: gather now)
+    return fr
 
 
 def _run_frames_in_mask_groups(frames, stacks, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline,

@@ -262,8 +262,9 @@ def _same(a, b):
     assert a["car_statistics"] == b["car_statistics"]
 
 
-@pytest.mark.parametrize("M,erode,f32", [(40, 0, True), (100, 1, False), (300, 0, False)])
-def test_run_frames_wide_equals_mask_groups(cal, M, erode, f32):
+@pytest.mark.parametrize("M,erode,f32,scan", [(40, 0, True, False), (100, 1, False, False), (300, 0, False, False), (100, 1, False, True)],
+                         ids=["40-0-True", "100-1-False", "300-0-False", "100-1-False-scan"])
+def test_run_frames_wide_equals_mask_groups(cal, M, erode, f32, scan, tmp_path):
     calib = cal["calib"]
     cam = _camera(calib)
     frames = []
@@ -275,7 +276,15 @@ def test_run_frames_wide_equals_mask_groups(cal, M, erode, f32):
         colors = [(i, j % 255, 0) for j in range(M)]
         frames.append(pipeline.FrameInputs(i, sc["points"], mk, boxes, colors))
     ctx = pipeline.get_context(0)
-    r_wide = pipeline.run_frames(frames, calib["TrVeloToRect"], cam, 50.0, 10, True, erode_iters=erode)
+    if scan:                                     # the scans through the read-ahead reader: the wide pass reads each Scan where it is
+        paths = [tmp_path / ("%010d.bin" % f.frame) for f in frames]
+        for f, p in zip(frames, paths):
+            f.points.tofile(p)
+        inputs = lambda i, path: (frames[i].frame, frames[i].masks, frames[i].bboxes_3d, frames[i].colors)     # noqa: E731
+        r_wide = list(pipeline.stream_frames(paths, inputs, calib["TrVeloToRect"], cam, 50.0, 10, True, erode_iters=erode))
+    else:
+        r_wide = pipeline.run_frames(frames, calib["TrVeloToRect"], cam, 50.0, 10, True, erode_iters=erode)
+    assert len(r_wide) == len(frames)
     stacks = [pipeline._mask_stack(f.masks, cam, resize_ctx=ctx)[0] for f in frames]
     r_grp = pipeline._run_frames_in_mask_groups(frames, stacks, calib["TrVeloToRect"], cam, 50.0, 10, True, erode, False, 0, ctx)
     for a, b in zip(r_wide, r_grp):

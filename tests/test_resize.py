@@ -138,12 +138,12 @@ def test_erosion_kernel_equals_the_restatement(calib, where, iters):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("where", ["host", "device"])
+@pytest.mark.parametrize("where", ["host", "device", "list"])
 def test_v3_erosion_block_on_masks_of_another_size(calib, where):
     """V3's own order for detector masks that do not arrive at camera size: (mask * 255).astype(uint8) -> cv2.erode at the MASK's size
     -> / 255.0 (V3:82-97), then astype(uint8) + cv2.resize + > 0.5 in extract_car_points_by_mask (V3:222-225).  run_frames with
-    erode_iters=1, v3_pipeline=True on such masks == run_frames on the masks the restated chain produces (host and device masks; a batch
-    that mixes them with masks at camera size erodes those by the same chain)."""
+    erode_iters=1, v3_pipeline=True on such masks == run_frames on the masks the restated chain produces (host and device masks, and a
+    Python list of [h,w] host masks; a batch that mixes them with masks at camera size erodes those by the same chain)."""
     import torch
     from lidar_object_detection_amd import pipeline
     from lidar_object_detection_amd import synthetic as S
@@ -156,10 +156,10 @@ def test_v3_erosion_block_on_masks_of_another_size(calib, where):
     want_full = npp.v3_masks_at_camera_size(sc["masks"].astype(np.float32), W, H, 1)      # masks at camera size through the same statements
     assert not want_small[1].any() and want_small[0].any() and (want_small[0] != npp.cv2_resize_linear_u8(small[0].astype(np.uint8), W, H)).any()
     boxes3d = [{"corners_velo": c.tolist()} for c in sc["corners_velo"]]
-    to = (lambda a: torch.from_numpy(a).to(torch.device("cuda", 0))) if where == "device" else (lambda a: a)
+    to = {"host": lambda a: a, "device": lambda a: torch.from_numpy(a).to(torch.device("cuda", 0)), "list": list}[where]
     items = [pipeline.FrameInputs(1, sc["points"], to(small), boxes3d, pipeline.default_colors(5))]
     ref = [pipeline.FrameInputs(1, sc["points"], want_small, boxes3d, pipeline.default_colors(5))]
-    if where == "host":                                                                   # (a mixed batch: ragged device batches are refused elsewhere)
+    if where != "device":                                                                 # (a mixed batch: ragged device batches are refused elsewhere)
         items.append(pipeline.FrameInputs(2, sc["points"], sc["masks"].astype(np.float32), boxes3d, pipeline.default_colors(5)))
         ref.append(pipeline.FrameInputs(2, sc["points"], want_full, boxes3d, pipeline.default_colors(5)))
     a = pipeline.run_frames(items, T, cam, 50.0, 10, True, erode_iters=1, v3_pipeline=True)
