@@ -47,8 +47,10 @@ extern "C" {
                                       8: lpf_reader_submit_frame, lpf_reader_boxes, lpf_parse_boxes_json (added); lpf_resize_masks_u8 no longer
                                          refuses an exact halving (it is cv2.resize's INTER_AREA case)
                                       8 (continued): LPF_MAX_MASKS_WIDE, lpf_wide_input, lpf_wide_outputs, lpf_run_wide (added; nothing
-                                         else changed) */
+                                         else changed)
+                                      8 (continued): LPF_MAX_CAMS, lpf_cam_input, lpf_run_cams (added; nothing else changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
+#define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams pass */
 
 typedef enum lpf_status {
     LPF_OK = 0,
@@ -319,6 +321,37 @@ typedef struct lpf_wide_outputs {
 } lpf_wide_outputs;
 int lpf_run_wide(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
                  const lpf_wide_outputs *out);
+
+/* ---- one scan in several cameras -----------------------------------------------------------------------------------------------
+ * lpf_run_cams: a batch of F frames labelled in C cameras (1 <= C <= LPF_MAX_CAMS) in ONE pass: every point is read from memory once
+ * and projected, clipped and labelled in each camera's arithmetic; one streaming launch, one tail launch and one summary launch serve
+ * all C cameras (each camera's mask pack and box tables are launches of their own, ahead of them).  The reference runs a camera per
+ * process_frame*(seq, cam_id) call (V3:524-535, 572-573): a rig of two rectified cameras reads and projects the scan twice.
+ * out[c] is, field for field and bit for bit, what a fresh context gives for
+ *   lpf_set_camera(cams[c].T_velo_to_rect, K, W, H, depth_min_excl, depth_max_excl)
+ *   lpf_set_mask_rects(masks.rects, ...)                              if masks.rects
+ *   lpf_set_masks_u8 / lpf_set_masks_f32(masks: M, binarize, erode_iters)
+ *   lpf_set_boxes_ex(corners_velo, boxes_on_device, box_off, F, oriented)   if corners_velo (else no boxes)
+ *   lpf_run_batch(pts, frame_off, F, pts_on_device, &out[c])
+ * Each camera has its own image size, depth window, 0 <= M <= LPF_MAX_MASKS masks (lpf_wide_input: uint8, or float32 under `binarize`;
+ * masks.on_device 0 = host, copied by the call, else device memory lent until the call's work has completed), rectangles, erosion and
+ * boxes.  The context's camera, masks, rectangles and boxes in force are left as they were (the pass has box tables of its own).  Not
+ * capturable (LPF_ERR_STATE between lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it first launches what the
+ * pipeline owes (no host wait), then runs in order.  Outputs: each out[c] is in host or device memory per its own on_device; with
+ * device outputs the call only enqueues work (unless some input is in host memory), with host outputs it returns with them filled. */
+typedef struct lpf_cam_input {
+    double         T_velo_to_rect[16];     /* lpf_set_camera's arguments for this camera */
+    double         K[9];
+    int32_t        W, H;
+    double         depth_min_excl, depth_max_excl;
+    lpf_wide_input masks;                  /* [F][M][H][W] + optional rects [F][M][4], M <= LPF_MAX_MASKS */
+    const double  *corners_velo;           /* [Btot][8][3] velodyne-frame corners (lpf_set_boxes_ex), or NULL: no boxes */
+    const int32_t *box_off;                /* [F + 1], host memory (with corners_velo) */
+    int32_t        boxes_on_device;        /* 0 / 1 / 2 as lpf_set_boxes_ex's on_device */
+    int32_t        oriented;
+} lpf_cam_input;
+int lpf_run_cams(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_cam_input *cams, int C,
+                 const lpf_outputs *out /* [C] */);
 
 /* ---- box membership as a stand-alone operator -------------------------------------------
  * inside[b*k + i] = 1 if point i lies in box b, else 0: the boolean arrays the reference's

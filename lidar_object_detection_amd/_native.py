@@ -62,6 +62,16 @@ class WideOutputs(ctypes.Structure):
                 ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+LPF_MAX_CAMS = 4                        # lpf_run_cams: cameras of one pass
+
+
+class CamInput(ctypes.Structure):
+    """lpf_cam_input (include/lpf.h): one camera of an lpf_run_cams pass"""
+    _fields_ = [("T_velo_to_rect", ctypes.c_double * 16), ("K", ctypes.c_double * 9), ("W", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("depth_min_excl", ctypes.c_double), ("depth_max_excl", ctypes.c_double), ("masks", WideInput),
+                ("corners_velo", _P), ("box_off", _P), ("boxes_on_device", ctypes.c_int32), ("oriented", ctypes.c_int32)]
+
+
 def wide_mask_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", binarize_codes=None):
     """Checks the masks of a wide run before anything reaches the GPU: ``(masks [F,M,H,W], M, is_float, on_device, rects [F,M,4] or
     None)``.  masks: [M,H,W] (F = 1) or [F,M,H,W], uint8 / bool or float32, a NumPy array or a contiguous GPU tensor; M <= 256."""
@@ -206,6 +216,7 @@ def load(path=None):
     lib.lpf_run_batch.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_frame.argtypes = [_P, ctypes.POINTER(FrameJob)]
     lib.lpf_run_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(WideOutputs)]
+    lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
     lib.lpf_depth_image.argtypes = [_P, _P, _I64, ctypes.c_int, _P, _P]
     lib.lpf_prepare_boxes.argtypes = [_P, _P, ctypes.c_int, _P, _P, _P, _P, _P]
@@ -239,7 +250,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_points_in_boxes", "lpf_prepare_boxes", "lpf_depth_image", "lpf_resize_masks_u8", "lpf_erode_masks_u8", "lpf_get_stats", "lpf_profile_enable", "lpf_profile_read", "lpf_profile_overhead",
             "lpf_graph_begin", "lpf_graph_end", "lpf_graph_launch", "lpf_graph_destroy",
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
-            "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide")
+            "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -898,10 +909,15 @@ class LpfContext:
                 return out
             cap = need
 
-    def _frame_results(self, off, M, summ, per_point, per_valid, iidx, cmb):
+    _BOXES_IN_FORCE = object()
+
+    def _frame_results(self, off, M, summ, per_point, per_valid, iidx, cmb, box_off=_BOXES_IN_FORCE):
         """One dict per frame of a run's outputs: the frame's row of the summary columns ``summ`` (n_valid, n_labelled, inst_count,
         inst_off, best_box, best_cnt), its rows of the ``per_point`` arrays [Ntot, ...], the first n_valid rows of its part of the
-        ``per_valid`` arrays, its instance lists out of ``iidx`` and its [M, B_f] block of the counts ``cmb``."""
+        ``per_valid`` arrays, its instance lists out of ``iidx`` and its [M, B_f] block of the counts ``cmb`` (boxes: the ones in
+        force, or the run's own ``box_off``)."""
+        if box_off is self._BOXES_IN_FORCE:
+            box_off = self.box_off
         nv, nl, ic, io, bb, bc = (summ[k] for k in ("n_valid", "n_labelled", "inst_count", "inst_off", "best_box", "best_cnt"))
         res = []
         for f in range(len(off) - 1):
@@ -916,8 +932,8 @@ class LpfContext:
             if per_valid:                                                     # (want_lists)
                 o = io[f].tolist()
                 r["inst_lists"] = [iidx[f, o[m]:o[m + 1]] for m in range(M)] if iidx is not None else []
-            if self.box_off is not None:
-                b0, b1 = int(self.box_off[f]), int(self.box_off[f + 1])
+            if box_off is not None:
+                b0, b1 = int(box_off[f]), int(box_off[f + 1])
                 r["count_mb"] = cmb[M * b0:M * b1].reshape(M, b1 - b0).astype(np.int64)
             else:
                 r["count_mb"] = np.zeros((M, 0), np.int64)
@@ -937,30 +953,43 @@ class LpfContext:
         F, n = len(off) - 1, int(off[-1])
         M = self.M if self.F_masks else 0
         Btot = int(self.box_off[-1]) if self.box_off is not None else 0
-        new = (lambda name, shape, dt: self._pinned(name, shape, dt)) if pinned else (lambda name, shape, dt: np.empty(shape, dt))
+        wants = dict(want_uv=want_uv, want_label=want_label, want_float=want_float, want_lists=want_lists, want_valid_uv=want_valid_uv)
 
         def launch(inst_cap):
             o = Outputs()
-            o.on_device = 0
-            uv = new("uv", (n, 2), np.int32) if want_uv else None
-            lab = new("lab", (n,), np.uint32) if want_label else None
-            dep = new("dep", (n,), np.float64) if want_float else None
-            uf = new("uf", (n,), np.float64) if want_float else None
-            vf = new("vf", (n,), np.float64) if want_float else None
-            vidx = new("vidx", (n,), np.int64) if want_lists else None
-            uvv = new("uvv", (n, 2), np.int32) if (want_valid_uv and want_lists) else None     # only the first n_valid rows come back
-            labv = new("labv", (n,), np.uint32) if (want_valid_uv and want_lists) else None
-            iidx = new("iidx", (F, inst_cap), np.int64) if (want_lists and M) else None
-            cmb = new("cmb", (max(M * Btot, 1),), np.int32)
-            cmb[:] = 0
-            summ = new("summ", (F,), SUMMARY_DTYPE)
-            summ.view(np.uint8)[:] = 0
-            for name, arr in (("uv", uv), ("label_bits", lab), ("depth", dep), ("u_f", uf), ("v_f", vf),
-                              ("valid_idx", vidx), ("inst_idx", iidx), ("count_mb", cmb), ("summary", summ),
-                              ("uv_valid", uvv), ("label_valid", labv)):
-                setattr(o, name, arr.ctypes.data if arr is not None else None)
-            o.inst_cap = inst_cap
+            finish = self._host_outputs(o, "", pinned, n, F, M, Btot, inst_cap, **wants)
             self._check(self._lib.lpf_run_batch(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(o)))
+            return finish()
+
+        out = self._until_lists_fit(launch, inst_cap, off)
+        return self._frame_results(off, M, *out)
+
+    def _host_outputs(self, o, tag, pinned, n, F, M, Btot, inst_cap, want_uv, want_label, want_float, want_lists, want_valid_uv):
+        """Host result arrays of a run (Ntot = n points, F frames, M masks, Btot boxes), wired into the lpf_outputs ``o``.  Returns
+        finish() -> ((summary columns, per_point, per_valid, inst_idx, count_mb), 0 or the list capacity the run needed) for after the
+        call.  pinned: the context's page-locked buffers (names prefixed by ``tag``), reused by the next run."""
+        new = (lambda name, shape, dt: self._pinned(tag + name, shape, dt)) if pinned else (lambda name, shape, dt: np.empty(shape, dt))
+        o.on_device = 0
+        uv = new("uv", (n, 2), np.int32) if want_uv else None
+        lab = new("lab", (n,), np.uint32) if want_label else None
+        dep = new("dep", (n,), np.float64) if want_float else None
+        uf = new("uf", (n,), np.float64) if want_float else None
+        vf = new("vf", (n,), np.float64) if want_float else None
+        vidx = new("vidx", (n,), np.int64) if want_lists else None
+        uvv = new("uvv", (n, 2), np.int32) if (want_valid_uv and want_lists) else None     # only the first n_valid rows come back
+        labv = new("labv", (n,), np.uint32) if (want_valid_uv and want_lists) else None
+        iidx = new("iidx", (F, inst_cap), np.int64) if (want_lists and M) else None
+        cmb = new("cmb", (max(M * Btot, 1),), np.int32)
+        cmb[:] = 0
+        summ = new("summ", (F,), SUMMARY_DTYPE)
+        summ.view(np.uint8)[:] = 0
+        for name, arr in (("uv", uv), ("label_bits", lab), ("depth", dep), ("u_f", uf), ("v_f", vf),
+                          ("valid_idx", vidx), ("inst_idx", iidx), ("count_mb", cmb), ("summary", summ),
+                          ("uv_valid", uvv), ("label_valid", labv)):
+            setattr(o, name, arr.ctypes.data if arr is not None else None)
+        o.inst_cap = inst_cap
+
+        def finish():
             per_point = {}
             if want_uv:
                 per_point.update(u=uv[:, 0], v=uv[:, 1])
@@ -973,9 +1002,86 @@ class LpfContext:
                 per_valid.update(uv_valid=uvv, u_valid=uvv[:, 0], v_valid=uvv[:, 1], label_valid=labv)   # uv_valid: contiguous [n_valid, 2]
             need = int(summ["inst_off"][:, 32].max()) if (iidx is not None and summ["inst_overflow"].any()) else 0
             return (summ, per_point, per_valid, iidx, cmb), need
+        return finish
 
-        out = self._until_lists_fit(launch, inst_cap, off)
-        return self._frame_results(off, M, *out)
+    def run_cams(self, frames, cams, want_uv=True, want_label=True, want_float=False, want_lists=True, inst_cap=None,
+                 want_valid_uv=False, pinned=False):
+        """One batch of frames labelled in up to four cameras in ONE native pass (lpf_run_cams): the points are staged once (as
+        run_batch's ``frames``: host arrays, Scans of a ScanReader, float32 [N,4] GPU tensors) and read once by the GPU.
+        cams: one dict per camera --
+          T_velo_to_rect  4x4, K  (3x3 or larger), width, height, depth_min (0.0), depth_max (50.0)  -- set_camera's arguments
+          masks           [M,H,W] (one frame) or [F,M,H,W], uint8 / bool or float32, NumPy or a contiguous GPU tensor, M <= 32; or None
+          binarize        float masks: "astype" (default), "v3" or "gt0.5" (set_masks'); v3_pipeline=True means "v3"
+          erode_iters     (0), rects: the optional [F,M,4] hint of set_mask_rects (where the masks are)
+          boxes           one f64 [B_f,8,3] array of velodyne-frame corners per frame (set_boxes'), or None; oriented (True)
+        Returns one list per camera of what run_batch returns for that camera after set_camera / set_mask_rects / set_masks /
+        set_boxes with the same arguments -- equal, array for array.  The context's camera, masks and boxes are left as they were."""
+        C = len(cams)
+        if not 1 <= C <= LPF_MAX_CAMS:
+            raise ValueError("run_cams takes 1 to %d cameras, got %d" % (LPF_MAX_CAMS, C))
+        F = len(frames)
+        if F == 0:
+            raise ValueError("no frames")
+        cin = (CamInput * C)()
+        keep, Ms, box_offs = [], [], []
+        for k, cam in enumerate(cams):
+            W, H = int(cam["width"]), int(cam["height"])
+            T = np.ascontiguousarray(cam["T_velo_to_rect"], dtype=np.float64).reshape(-1)
+            K = np.asarray(cam["K"], dtype=np.float64)
+            if T.size != 16 or K.ndim != 2 or K.shape[0] < 3 or K.shape[1] < 3 or W <= 0 or H <= 0:
+                raise ValueError("camera %d: T_velo_to_rect must be 4x4, K at least 3x3, width and height positive" % k)
+            binarize = cam.get("binarize") or ("v3" if cam.get("v3_pipeline") else "astype")
+            masks = cam.get("masks")
+            if masks is None:
+                masks = np.zeros((F, 0, H, W), np.uint8)
+            erode = cam.get("erode_iters", 0)
+            masks, M, is_f, mdev, rects = wide_mask_batch(masks, F, H, W, cam.get("rects"), erode, binarize, self.BINARIZE)
+            if M > LPF_MAX_MASKS:
+                raise ValueError("camera %d has %d masks per frame: a multi-camera pass takes at most %d per camera (run_wide takes more)"
+                                 % (k, M, LPF_MAX_MASKS))
+            if mdev:
+                import torch
+                self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
+            ci = cin[k]
+            ci.T_velo_to_rect[:] = T.tolist()
+            ci.K[:] = np.ascontiguousarray(K[:3, :3]).reshape(9).tolist()
+            ci.W, ci.H = W, H
+            ci.depth_min_excl, ci.depth_max_excl = float(cam.get("depth_min", 0.0)), float(cam.get("depth_max", 50.0))
+            ci.masks.masks = (masks.data_ptr() if mdev else masks.ctypes.data) if M else None
+            ci.masks.rects = (rects.data_ptr() if mdev else rects.ctypes.data) if (rects is not None and M) else None
+            ci.masks.M, ci.masks.f32, ci.masks.binarize, ci.masks.erode_iters = M, int(is_f), self.BINARIZE[binarize], int(erode)
+            ci.masks.on_device = 1 if mdev else 0
+            boxes, box_off = cam.get("boxes"), None
+            if boxes is not None:
+                if isinstance(boxes, np.ndarray) and F == 1:
+                    boxes = [boxes]
+                if len(boxes) != F:
+                    raise ValueError("camera %d: boxes for %d frames, the batch has %d" % (k, len(boxes), F))
+                arrs = [np.asarray(b, dtype=np.float64).reshape(-1, 8, 3) for b in boxes]
+                box_off = np.zeros(F + 1, np.int32)
+                box_off[1:] = np.cumsum([a.shape[0] for a in arrs])
+                cat = np.ascontiguousarray(np.concatenate(arrs, axis=0))
+                ci.corners_velo = cat.ctypes.data if cat.size else None
+                ci.box_off = box_off.ctypes.data
+                ci.boxes_on_device, ci.oriented = 0, int(bool(cam.get("oriented", True)))
+                keep.append(cat)
+            keep += [masks, rects]
+            Ms.append(M)
+            box_offs.append(box_off)
+        off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the run returns)
+        n = int(off[-1])
+        wants = dict(want_uv=want_uv, want_label=want_label, want_float=want_float, want_lists=want_lists, want_valid_uv=want_valid_uv)
+
+        def launch(inst_cap):
+            outs = (Outputs * C)()
+            fins = [self._host_outputs(outs[k], "cam%d_" % k, pinned, n, F, Ms[k], int(box_offs[k][-1]) if box_offs[k] is not None else 0,
+                                       inst_cap, **wants) for k in range(C)]
+            self._check(self._lib.lpf_run_cams(self._h, pts_ptr, off.ctypes.data, F, pts_dev, cin, C, outs))
+            res = [fin() for fin in fins]
+            return [r for r, _ in res], max(need for _, need in res)
+
+        outs = self._until_lists_fit(launch, inst_cap, off)
+        return [self._frame_results(off, Ms[k], *outs[k], box_off=box_offs[k]) for k in range(C)]
 
     def run_wide(self, frames, masks, erode_iters=0, binarize="astype", rects=None, v3_pipeline=False, want_uv=True, want_float=False,
                  want_lists=True, want_valid_uv=False, inst_cap=None):

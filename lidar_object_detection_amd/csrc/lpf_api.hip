@@ -3,6 +3,7 @@
 // either launches HIP kernels or fails with an error code.
 #include "lpf_kernels.hip.h"
 #include "lpf_wide.hip.h"
+#include "lpf_cams.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -168,6 +169,9 @@ struct lpf_ctx {
 
     // lpf_run_wide: its own buffers (the narrow masks, label images and staging stay as they are)
     struct Wide { DevBuf tab, masks, rects, planes_a, planes_b, flags, ccnt, cpre, fcnt, midx, mwords, mpts, cnt, uv, words, pts, out; } wide;
+    // lpf_run_cams: camera c's box tables, label images, staged masks / rectangles and host-output staging (grow-only, allocated on
+    // first use); its counters and geometry tables are scratch set c's
+    struct Cams { BoxSet bx[LPF_NSETS]; DevBuf label_a[LPF_NSETS], label_b[LPF_NSETS], masks[LPF_NSETS], rects[LPF_NSETS], out[LPF_NSETS], pts; } cams;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -487,6 +491,8 @@ void box_params(const double *c, int oriented, double *o)
     }
 }
 
+int box_shape(lpf_ctx *c, lpf_ctx::BoxSet &B, const int32_t *box_off, int F, int oriented);
+
 // The box set a lpf_set_boxes* call writes: in the software-pipelined modes the next one of the ring once the current one has
 // been used by a run (its tables are still to be read by that run's tail), else the current one.  Then its shapes: per-frame
 // records, grid offsets, buffers.  Nothing here waits for the GPU unless a buffer has to grow.
@@ -510,6 +516,16 @@ int box_layout(lpf_ctx *c, const int32_t *box_off, int F, int oriented, const ch
         const int depth = c->defer ? 2 : 1;
         if (B->last_ref >= 0 && B->last_ref + depth >= c->run_seq && (rc = flush_pending(c))) return rc;
     }
+    if ((rc = box_shape(c, *B, box_off, F, oriented))) return rc;
+    *out = B;
+    return LPF_OK;
+}
+
+// a box set's shapes for F frames of box_off: per-frame records, grid offsets, buffers (the job that fills the tables comes later)
+int box_shape(lpf_ctx *c, lpf_ctx::BoxSet &BS, const int32_t *box_off, int F, int oriented)
+{
+    int rc;
+    lpf_ctx::BoxSet *B = &BS;
     B->used = false; B->last_ref = -1; B->job_valid = false; B->F = 0;
     B->h_bframes.resize((size_t)F);
     B->cand_off.assign((size_t)F, 0);
@@ -541,7 +557,6 @@ int box_layout(lpf_ctx *c, const int32_t *box_off, int F, int oriented, const ch
     B->cand_words = total;
     B->box_off.assign(box_off, box_off + F + 1);
     B->F = F; B->oriented = oriented ? 1 : 0;
-    *out = B;
     return LPF_OK;
 }
 
@@ -614,14 +629,15 @@ int set_boxes_impl(lpf_ctx *c, const double *corners, int on_device, const int32
     return LPF_OK;
 }
 
-// masks -> label image with element type LT, on stream ms, into S.label_a (S.label_b = erosion ping-pong)
+// masks [F][M][H][W] -> label image with element type LT, on stream ms, into la (lb_ = erosion ping-pong): the context's camera size
+// for the narrow calls (a scratch set's label_a / label_b), camera c's for lpf_run_cams
 template <typename T, typename LT>
-int pack_typed(lpf_ctx *c, lpf_ctx::Scratch &S, hipStream_t ms, const T *d_masks, int F, int M, int mode, int erode_iters, void **result,
-               const int4 *rects = nullptr)
+int pack_typed(lpf_ctx *c, DevBuf &la, DevBuf &lb_, const int W, const int H, hipStream_t ms, const T *d_masks, int F, int M, int mode,
+               int erode_iters, void **result, const int4 *rects = nullptr)
 {
-    const size_t hw = (size_t)c->H * c->W;
-    dim3 grid((c->W + LPF_TW - 1) / LPF_TW, (c->H + LPF_TH - 1) / LPF_TH, F);
-    LT *cur = (LT *)S.label_a.p;
+    const size_t hw = (size_t)H * W;
+    dim3 grid((W + LPF_TW - 1) / LPF_TW, (H + LPF_TH - 1) / LPF_TH, F);
+    LT *cur = (LT *)la.p;
     int rc;
     if (M == 0) {
         LPF_HIP(c, hipMemsetAsync(cur, 0, (size_t)F * hw * sizeof(LT), ms));
@@ -633,31 +649,31 @@ int pack_typed(lpf_ctx *c, lpf_ctx::Scratch &S, hipStream_t ms, const T *d_masks
             const unsigned nb = (unsigned)((total16 + LPF_BLOCK - 1) / LPF_BLOCK);
             // (rectangles: only where set_masks_impl accepted them -- uint8 rule 0 / float rule 1, no erosion)
             if (mode == 0)
-                hipLaunchKernelGGL((lpf_pack16<T, 0, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, rects, c->W);
+                hipLaunchKernelGGL((lpf_pack16<T, 0, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, rects, W);
             else if (mode == 1)
-                hipLaunchKernelGGL((lpf_pack16<T, 1, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, rects, c->W);
+                hipLaunchKernelGGL((lpf_pack16<T, 1, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, rects, W);
             else if (mode == 2)
-                hipLaunchKernelGGL((lpf_pack16<T, 2, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, (const int4 *)nullptr, c->W);
+                hipLaunchKernelGGL((lpf_pack16<T, 2, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, (const int4 *)nullptr, W);
             else
-                hipLaunchKernelGGL((lpf_pack16<T, 3, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, (const int4 *)nullptr, c->W);
+                hipLaunchKernelGGL((lpf_pack16<T, 3, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, (const int4 *)nullptr, W);
         } else {
             const int fuse = erode_iters > 0 ? 1 : 0;
             left -= fuse;
             if (mode == 0)
-                hipLaunchKernelGGL((lpf_pack_erode<T, 0, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, c->H, c->W, fuse, rects);
+                hipLaunchKernelGGL((lpf_pack_erode<T, 0, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, H, W, fuse, rects);
             else if (mode == 1)
-                hipLaunchKernelGGL((lpf_pack_erode<T, 1, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, c->H, c->W, fuse, rects);
+                hipLaunchKernelGGL((lpf_pack_erode<T, 1, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, H, W, fuse, rects);
             else if (mode == 2)
-                hipLaunchKernelGGL((lpf_pack_erode<T, 2, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, c->H, c->W, fuse, (const int4 *)nullptr);
+                hipLaunchKernelGGL((lpf_pack_erode<T, 2, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, H, W, fuse, (const int4 *)nullptr);
             else
-                hipLaunchKernelGGL((lpf_pack_erode<T, 3, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, c->H, c->W, fuse, (const int4 *)nullptr);
+                hipLaunchKernelGGL((lpf_pack_erode<T, 3, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, H, W, fuse, (const int4 *)nullptr);
         }
         LPF_HIP(c, hipGetLastError());
         if (left > 0) {
-            if ((rc = reserve(c, S.label_b, (size_t)F * hw * 4))) return rc;
-            LT *other = (LT *)S.label_b.p;
+            if ((rc = reserve(c, lb_, (size_t)F * hw * 4))) return rc;
+            LT *other = (LT *)lb_.p;
             for (int it = 0; it < left; ++it) {
-                hipLaunchKernelGGL((lpf_erode_packed<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, c->H, c->W);
+                hipLaunchKernelGGL((lpf_erode_packed<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, H, W);
                 LPF_HIP(c, hipGetLastError());
                 LT *t = cur; cur = other; other = t;
             }
@@ -724,9 +740,9 @@ int set_masks_impl(lpf_ctx *c, const T *masks, int F, int M, int mode, int erode
         return LPF_OK;
     }
     void *cur = nullptr;
-    if (lb == 1) rc = pack_typed<T, uint8_t>(c, S, ms, d_masks, F, M, mode, erode_iters, &cur, rects);
-    else if (lb == 2) rc = pack_typed<T, uint16_t>(c, S, ms, d_masks, F, M, mode, erode_iters, &cur, rects);
-    else rc = pack_typed<T, uint32_t>(c, S, ms, d_masks, F, M, mode, erode_iters, &cur, rects);
+    if (lb == 1) rc = pack_typed<T, uint8_t>(c, S.label_a, S.label_b, c->W, c->H, ms, d_masks, F, M, mode, erode_iters, &cur, rects);
+    else if (lb == 2) rc = pack_typed<T, uint16_t>(c, S.label_a, S.label_b, c->W, c->H, ms, d_masks, F, M, mode, erode_iters, &cur, rects);
+    else rc = pack_typed<T, uint32_t>(c, S.label_a, S.label_b, c->W, c->H, ms, d_masks, F, M, mode, erode_iters, &cur, rects);
     if (rc) return rc;
     S.label_bytes = lb;
     if (!on_device) LPF_HIP(c, host_wait(c));   // the host buffer may be reused by the caller
@@ -743,14 +759,14 @@ int pack_masks_now(lpf_ctx *c, lpf_ctx::Scratch &S, const void *masks, bool f32,
     int rc;
     if (f32) {
         const float *m = (const float *)masks;
-        if (lb == 1) rc = pack_typed<float, uint8_t>(c, S, c->stream, m, F, M, mode, 0, &cur, rects);
-        else if (lb == 2) rc = pack_typed<float, uint16_t>(c, S, c->stream, m, F, M, mode, 0, &cur, rects);
-        else rc = pack_typed<float, uint32_t>(c, S, c->stream, m, F, M, mode, 0, &cur, rects);
+        if (lb == 1) rc = pack_typed<float, uint8_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
+        else if (lb == 2) rc = pack_typed<float, uint16_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
+        else rc = pack_typed<float, uint32_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
     } else {
         const uint8_t *m = (const uint8_t *)masks;
-        if (lb == 1) rc = pack_typed<uint8_t, uint8_t>(c, S, c->stream, m, F, M, mode, 0, &cur, rects);
-        else if (lb == 2) rc = pack_typed<uint8_t, uint16_t>(c, S, c->stream, m, F, M, mode, 0, &cur, rects);
-        else rc = pack_typed<uint8_t, uint32_t>(c, S, c->stream, m, F, M, mode, 0, &cur, rects);
+        if (lb == 1) rc = pack_typed<uint8_t, uint8_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
+        else if (lb == 2) rc = pack_typed<uint8_t, uint16_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
+        else rc = pack_typed<uint8_t, uint32_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
     }
     if (rc) return rc;
     S.label_cur = cur;
@@ -832,10 +848,17 @@ void lpf_destroy(lpf_ctx *c)
         DevBuf *sb[] = {&S.vbal, &S.mbal, &S.seg_tab, &S.grp_tab, &S.frm_tab, &S.seg_pre, &S.cnt, &S.mlist, &S.label_a, &S.label_b, &S.tab, &S.rects, &S.rgrid};
         for (DevBuf *b : sb) release(*b);
     }
-    for (auto &B : c->bx) {
-        DevBuf *bb[] = {&B.boxp, &B.boxq, &B.cand, &B.corners, &B.enabled, &B.aux, &B.bframes, &B.stage};
-        for (DevBuf *b : bb) release(*b);
+    for (auto *ring : {c->bx, c->cams.bx})
+        for (int k = 0; k < LPF_NSETS; ++k) {
+            lpf_ctx::BoxSet &B = ring[k];
+            DevBuf *bb[] = {&B.boxp, &B.boxq, &B.cand, &B.corners, &B.enabled, &B.aux, &B.bframes, &B.stage};
+            for (DevBuf *b : bb) release(*b);
+        }
+    for (int k = 0; k < LPF_NSETS; ++k) {
+        DevBuf *cb[] = {&c->cams.label_a[k], &c->cams.label_b[k], &c->cams.masks[k], &c->cams.rects[k], &c->cams.out[k]};
+        for (DevBuf *b : cb) release(*b);
     }
+    release(c->cams.pts);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_uvv, &c->st_labv, &c->st_pts, &c->st_uv, &c->st_label,
                      &c->st_depth, &c->st_uf, &c->st_vf, &c->st_valid, &c->st_inst, &c->st_count, &c->st_summary};
     for (DevBuf *b : all) release(*b);
@@ -2096,6 +2119,364 @@ int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         LPF_HIP(c, back(out->inst_overflow, o_of, nF * 4));
     }
     if (host_io || (M > 0 && !in->on_device) || (n > 0 && !pts_on_device)) LPF_HIP(c, host_wait(c));   // host buffers may be reused
+    return LPF_OK;
+}
+
+// ---- lpf_run_cams (include/lpf.h): one scan in up to LPF_MAX_CAMS cameras, kernels in lpf_cams.hip.h ------------------------------
+// Camera c runs as the narrow in-order run would -- the same segments, counters, tables and tail -- in scratch set c, with its own box
+// tables (c->cams.bx[c]) and label images (c->cams.label_a[c]); the three launches after the packs and box jobs serve every camera.
+static_assert(LPF_MAX_CAMS == LPF_MAX_CAMS_DEV && LPF_MAX_CAMS <= LPF_NSETS, "a scratch set per camera");
+
+int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_cam_input *cams, int C,
+                 const lpf_outputs *out)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (use_device(c)) return LPF_ERR_HIP;
+    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_run_cams cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
+    if (C < 1 || C > LPF_MAX_CAMS) return fail(c, LPF_ERR_ARG, "run_cams: C=%d cameras, a pass takes 1 .. LPF_MAX_CAMS = %d", C, LPF_MAX_CAMS);
+    if (!cams || !out || !frame_off || F <= 0)
+        return fail(c, LPF_ERR_ARG, "run_cams: cams=%p out=%p frame_off=%p F=%d", (const void *)cams, (const void *)out, (const void *)frame_off, F);
+    if (frame_off[0] != 0) return fail(c, LPF_ERR_ARG, "run_cams: frame_off[0] must be 0");
+    for (int f = 0; f < F; ++f) {
+        const int64_t n = frame_off[f + 1] - frame_off[f];
+        if (n < 0 || n > 0x7fffffffll - LPF_SEG_QUANTUM) return fail(c, LPF_ERR_ARG, "run_cams: frame %d has %lld points", f, (long long)n);
+    }
+    const int64_t Ntot = frame_off[F];
+    if (Ntot > 0 && !pts) return fail(c, LPF_ERR_ARG, "run_cams: pts is NULL");
+    for (int k = 0; k < C; ++k) {
+        const lpf_cam_input &I = cams[k];
+        const lpf_wide_input &m = I.masks;
+        if (I.W <= 0 || I.H <= 0 || (long long)I.W * I.H > (1ll << 30))
+            return fail(c, LPF_ERR_ARG, "run_cams: camera %d is %d x %d", k, I.W, I.H);
+        if (m.M < 0 || m.M > LPF_MAX_MASKS)
+            return fail(c, LPF_ERR_ARG, "run_cams: camera %d has M=%d masks per frame, a pass takes 0 .. LPF_MAX_MASKS = %d per camera (more: "
+                                        "lpf_run_wide for that camera)", k, m.M, LPF_MAX_MASKS);
+        if (m.erode_iters < 0 || (m.f32 && (m.binarize < 0 || m.binarize > 2)) || (m.M > 0 && !m.masks))
+            return fail(c, LPF_ERR_ARG, "run_cams: camera %d: erode_iters=%d f32=%d binarize=%d masks=%p", k, m.erode_iters, m.f32, m.binarize, m.masks);
+        if (I.corners_velo) {
+            if (!I.box_off || I.box_off[0] != 0) return fail(c, LPF_ERR_ARG, "run_cams: camera %d: box_off must be given and start at 0", k);
+            for (int f = 0; f < F; ++f)
+                if (I.box_off[f + 1] < I.box_off[f]) return fail(c, LPF_ERR_ARG, "run_cams: camera %d: box_off not ascending at %d", k, f);
+            if (I.boxes_on_device < 0 || I.boxes_on_device > 2) return fail(c, LPF_ERR_ARG, "run_cams: camera %d: boxes_on_device=%d", k, I.boxes_on_device);
+        }
+        if (out[k].inst_idx && out[k].inst_cap <= 0) return fail(c, LPF_ERR_ARG, "run_cams: out[%d].inst_idx given with inst_cap=%lld", k, (long long)out[k].inst_cap);
+        if ((out[k].uv_valid || out[k].label_valid) && !out[k].valid_idx)
+            return fail(c, LPF_ERR_ARG, "run_cams: out[%d]: uv_valid / label_valid need valid_idx as well (they share its order)", k);
+    }
+    int rc;
+    // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+    const size_t n = (size_t)Ntot;
+    bool host_in = false;
+
+    // ---- points: read once by the streaming launch ----------------------------------------------------------------------------------
+    const float4 *d_pts = (const float4 *)pts;
+    if (!pts_on_device && n) {
+        if ((rc = reserve(c, c->cams.pts, n * 16))) return rc;
+        LPF_HIP(c, hipMemcpyAsync(c->cams.pts.p, pts, n * 16, hipMemcpyHostToDevice, c->stream));
+        d_pts = (const float4 *)c->cams.pts.p;
+        host_in = true;
+    }
+
+    // ---- per camera: box tables (the box job), masks -> label images (one element type for the pass) ------------------------------
+    int lb_all = 1;
+    for (int k = 0; k < C; ++k) { const int M = cams[k].masks.M; lb_all = std::max(lb_all, M <= 8 ? 1 : M <= 16 ? 2 : 4); }
+    const void *label_img[LPF_MAX_CAMS] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < C; ++k) {
+        const lpf_cam_input &I = cams[k];
+        lpf_ctx::BoxSet &B = c->cams.bx[k];
+        B.F = 0; B.box_off.clear(); B.job_valid = false;
+        if (I.corners_velo) {
+            if ((rc = box_shape(c, B, I.box_off, F, I.oriented))) return rc;
+            const size_t nb = (size_t)I.box_off[F];
+            if (nb > 0) {
+                const double *src = I.corners_velo;
+                if (I.boxes_on_device != 2) {                // not lent: the pass's own copy, in stream order
+                    if ((rc = reserve(c, B.stage, nb * 192))) return rc;
+                    if (I.boxes_on_device) LPF_HIP(c, hipMemcpyAsync(B.stage.p, src, nb * 192, hipMemcpyDeviceToDevice, c->stream));
+                    else if ((rc = upload(c, B.stage.p, src, nb * 192))) return rc;
+                    src = (const double *)B.stage.p;
+                }
+                B.have_enabled = false;
+                LpfBoxJob &J = B.job;
+                memset(&J, 0, sizeof J);
+                J.src = src; J.oriented = B.oriented; J.F = F; J.chunks = B.max_words;
+                J.bframes = (const LpfBoxFrame *)B.bframes.p; J.frame0 = B.h_bframes[0];
+                J.boxp = (double *)B.boxp.p; J.boxq = (float *)B.boxq.p; J.cand = (unsigned long long *)B.cand.p;
+                J.corners_keep = (double *)B.corners.p;
+                memcpy(J.K, I.K, sizeof J.K);
+                J.W = I.W; J.H = I.H;
+                ++c->stats[4];
+                hipLaunchKernelGGL(lpf_box_job_kernel, dim3((unsigned)box_job_blocks(B)), dim3(LPF_BLOCK), 0, c->stream, J);
+                LPF_HIP(c, hipGetLastError());
+            }
+        }
+        const lpf_wide_input &m = I.masks;
+        if (m.M == 0) continue;
+        const size_t hw = (size_t)I.W * I.H, esz = m.f32 ? 4 : 1;
+        const void *d_masks = m.masks;
+        const int32_t *d_rects = m.rects;
+        if (!m.on_device) {
+            const size_t bytes = (size_t)F * m.M * hw * esz;
+            if ((rc = reserve(c, c->cams.masks[k], bytes))) return rc;
+            LPF_HIP(c, hipMemcpyAsync(c->cams.masks[k].p, m.masks, bytes, hipMemcpyHostToDevice, c->stream));
+            d_masks = c->cams.masks[k].p;
+            if (m.rects) {
+                if ((rc = reserve(c, c->cams.rects[k], (size_t)F * m.M * 16))) return rc;
+                LPF_HIP(c, hipMemcpyAsync(c->cams.rects[k].p, m.rects, (size_t)F * m.M * 16, hipMemcpyHostToDevice, c->stream));
+                d_rects = (const int32_t *)c->cams.rects[k].p;
+            }
+            host_in = true;
+        }
+        // (the rectangles hold where lpf_set_masks_* takes them: uint8, or float32 under binarize 0, without erosion, W >= 16)
+        const int4 *rects = (m.rects && m.erode_iters == 0 && (!m.f32 || m.binarize == 0) && I.W >= 16) ? (const int4 *)d_rects : nullptr;
+        if ((rc = reserve(c, c->cams.label_a[k], (size_t)F * hw * 4))) return rc;
+        DevBuf &la = c->cams.label_a[k], &lb2 = c->cams.label_b[k];
+        void *cur = nullptr;
+        const int mode = m.f32 ? m.binarize + 1 : 0;
+#define LPF_CAMS_PACK(T) (lb_all == 1 ? pack_typed<T, uint8_t>(c, la, lb2, I.W, I.H, c->stream, (const T *)d_masks, F, m.M, mode, m.erode_iters, &cur, rects) : \
+                          lb_all == 2 ? pack_typed<T, uint16_t>(c, la, lb2, I.W, I.H, c->stream, (const T *)d_masks, F, m.M, mode, m.erode_iters, &cur, rects) : \
+                                        pack_typed<T, uint32_t>(c, la, lb2, I.W, I.H, c->stream, (const T *)d_masks, F, m.M, mode, m.erode_iters, &cur, rects))
+        rc = m.f32 ? LPF_CAMS_PACK(float) : LPF_CAMS_PACK(uint8_t);
+#undef LPF_CAMS_PACK
+        if (rc) return rc;
+        label_img[k] = cur;
+    }
+
+    // ---- segmentation: as lpf_run_batch's in-order run (it depends on the points only) ---------------------------------------------
+    const bool small = Ntot <= LPF_SMALL_LAUNCH;
+    const int64_t seg_pts = small ? LPF_SEG_SMALL : LPF_SEG_QUANTUM;
+    const int tile_pts = (small && Ntot <= 1792ll * 512) ? 512 : 1024;
+    LpfCamsArgs A;
+    memset(&A, 0, sizeof A);
+    A.C = C;
+    int nk1 = 0, max_tail = 0;
+    bool pre_scan = false;
+    std::vector<LpfFrame> fr((size_t)F);
+    for (int k = 0; k < C; ++k) {
+        const lpf_cam_input &I = cams[k];
+        const lpf_ctx::BoxSet &BX = c->cams.bx[k];
+        const lpf_outputs &o = out[k];
+        const int M = I.masks.M;
+        const int Btot = BX.F ? BX.box_off[F] : 0;
+        int nseg_total = 0, ngrp_total = 0, max_ngrp = 0;
+        for (int f = 0; f < F; ++f) {
+            LpfFrame &e = fr[f];
+            memset(&e, 0, sizeof e);
+            e.pt_off = frame_off[f];
+            e.N = (int)(frame_off[f + 1] - frame_off[f]);
+            e.seg_off = nseg_total;
+            e.shift = (int)(frame_off[f] & 63);
+            e.nseg = e.N ? (int)((e.N + e.shift + seg_pts - 1) / seg_pts) : 0;
+            nseg_total += e.nseg;
+            e.box_off = BX.F ? BX.box_off[f] : 0;
+            e.B = BX.F ? BX.box_off[f + 1] - BX.box_off[f] : 0;
+            e.inst_base = (long long)f * o.inst_cap;
+            e.pad = f;
+            e.cand_off = BX.F ? BX.cand_off[f] : 0;
+            e.cand_words = (e.B + 63) / 64;
+            e.grp_off = ngrp_total;
+            const int ngrp = (e.nseg + LPF_GROUP_SEGS - 1) / LPF_GROUP_SEGS;
+            ngrp_total += ngrp;
+            max_ngrp = std::max(max_ngrp, ngrp);
+        }
+        const int nseg_cap = nseg_total > 0 ? nseg_total : 1, ngrp_cap = ngrp_total > 0 ? ngrp_total : 1;
+        const bool count_boxes = M > 0 && Btot > 0;
+        int nblk = 0, ncblk = 0;
+        for (int f = 0; f < F; ++f) {
+            const int nbk = fr[f].nseg > 0 ? (fr[f].nseg + LPF_LISTS_WAVES - 1) / LPF_LISTS_WAVES : 1;
+            nblk += nbk;
+            ncblk += nbk * std::max(1, fr[f].cand_words);
+        }
+        const bool few = small && nblk <= LPF_FEW_BLOCKS;
+        const size_t rows = (size_t)nseg_cap * (size_t)(seg_pts / 64);
+        pre_scan = max_ngrp > 64;
+        lpf_ctx::Scratch &S = c->sc[k];
+        if ((rc = reserve(c, S.vbal, rows * 8))) return rc;
+        if ((rc = reserve(c, S.mbal, rows * 8))) return rc;
+        if ((rc = reserve(c, S.seg_tab, (size_t)LPF_TAB_GROUPS * nseg_cap * sizeof(uint4), true))) return rc;
+        if ((rc = reserve(c, S.grp_tab, (size_t)LPF_TAB_GROUPS * ngrp_cap * sizeof(uint4), true))) return rc;
+        if ((rc = reserve(c, S.frm_tab, (size_t)F * LPF_FRM_SHARDS * LPF_TAB_GROUPS * sizeof(uint4), true))) return rc;
+        if (pre_scan && (rc = reserve(c, S.seg_pre, (size_t)LPF_TAB_GROUPS * nseg_cap * sizeof(uint4)))) return rc;
+        if ((rc = reserve(c, S.cnt, (size_t)(M > 0 ? M : 1) * (Btot > 0 ? Btot : 1) * 4, true))) return rc;
+        if (M > 0 && (rc = reserve(c, S.mlist, n * 16))) return rc;
+        // geometry tables in scratch set k, the layout of lpf_run_batch's (count blocks in one part); the set's bookkeeping is cleared,
+        // so the next narrow run on it uploads its own
+        size_t o_segs = 0, o_blks = 0, o_cblks = 0;
+        if (F > 1) {
+            const size_t b_frames = (size_t)F * sizeof(LpfFrame), b_segs = (size_t)nseg_total * sizeof(LpfFrame), b_blks = (size_t)nblk * sizeof(int2),
+                         b_cblks = (size_t)ncblk * sizeof(int4);
+            S.tab_frames.clear();
+            if ((rc = reserve(c, S.tab, b_frames + b_segs + b_blks + b_cblks))) return rc;
+            c->h_tab.resize(b_frames + b_segs + b_blks + b_cblks);
+            memcpy(c->h_tab.data(), fr.data(), b_frames);
+            LpfFrame *hs = reinterpret_cast<LpfFrame *>(c->h_tab.data() + b_frames);
+            int2 *hb = reinterpret_cast<int2 *>(c->h_tab.data() + b_frames + b_segs);
+            int4 *hc = reinterpret_cast<int4 *>(c->h_tab.data() + b_frames + b_segs + b_blks);
+            for (int f = 0; f < F; ++f) {
+                const LpfFrame &e = fr[f];
+                const int wpg = std::max(1, e.cand_words);
+                for (int sg = 0; sg < e.nseg; ++sg) hs[(size_t)e.seg_off + sg] = e;
+                if (e.nseg == 0) {
+                    *hb++ = make_int2(e.seg_off, f << 3);
+                    for (int w = 0; w < wpg; ++w) *hc++ = make_int4(e.seg_off, f, w, 0);
+                }
+                for (int sg = 0; sg < e.nseg; sg += LPF_LISTS_WAVES) {
+                    const int nw = std::min(LPF_LISTS_WAVES, e.nseg - sg);
+                    *hb++ = make_int2(e.seg_off + sg, (f << 3) | nw);
+                    for (int w = 0; w < wpg; ++w) *hc++ = make_int4(e.seg_off + sg, f, w, nw);
+                }
+            }
+            if ((rc = upload(c, S.tab.p, c->h_tab.data(), c->h_tab.size()))) return rc;
+            o_segs = b_frames; o_blks = b_frames + b_segs; o_cblks = b_frames + b_segs + b_blks;
+            ++c->generation;                                   // graphs captured for narrow runs read this set's tables
+        }
+
+        LpfParams &P = A.P[k];
+        memcpy(P.T, I.T_velo_to_rect, sizeof P.T);             // rows 0..2 (as lpf_set_camera)
+        memcpy(P.K, I.K, sizeof P.K);
+        P.dmin = I.depth_min_excl; P.dmax = I.depth_max_excl; P.W = I.W; P.H = I.H;
+        P.F = F; P.M = M; P.seg_pts = (int)seg_pts; P.nseg_total = nseg_total; P.nseg_cap = nseg_cap; P.ngrp_cap = ngrp_cap;
+        P.oriented = BX.F ? BX.oriented : 1; P.inst_cap = o.inst_cap;
+        P.frame0 = fr[0];
+        if (F > 1) {
+            P.frames = (const LpfFrame *)S.tab.p;
+            P.segs = (const LpfFrame *)((const char *)S.tab.p + o_segs);
+            P.blks = (const int2 *)((const char *)S.tab.p + o_blks);
+            P.cblks = (const int4 *)((const char *)S.tab.p + o_cblks);
+        }
+        P.label_img = M > 0 ? label_img[k] : nullptr;
+        P.boxp = (const double *)BX.boxp.p; P.boxq = (const float *)BX.boxq.p; P.cand = (const unsigned long long *)BX.cand.p;
+        P.vbal = (unsigned long long *)S.vbal.p; P.mbal = (unsigned long long *)S.mbal.p;
+        P.seg_tab = (uint4 *)S.seg_tab.p; P.grp_tab = (uint4 *)S.grp_tab.p; P.frm_tab = (uint4 *)S.frm_tab.p;
+        P.seg_pre = pre_scan ? (uint4 *)S.seg_pre.p : nullptr;
+        P.cnt = (unsigned *)S.cnt.p;
+        P.mlist = M > 0 ? (float4 *)S.mlist.p : nullptr;
+        P.nblk = nblk; P.ncblk = ncblk; P.csplit = 1; P.lists_small = few ? 1 : 0; P.count_boxes = count_boxes ? 1 : 0;
+        P.count_lazy = small ? 0 : 1;
+        P.pts = d_pts;
+        P.tile_pts = tile_pts;
+        nk1 = nseg_total * (int)(seg_pts / tile_pts);
+
+        // outputs: the caller's device pointers, or staging carved out of one buffer (host callers; and what a device caller leaves out
+        // but the pass needs: the dense uv / labels behind the compact copies, the summaries)
+        const bool host_io = !o.on_device;
+        size_t off = 0;
+        auto carve = [&](bool want, size_t bytes) -> size_t { if (!want) return (size_t)-1; const size_t r = off; off += (bytes + 255) & ~(size_t)255; return r; };
+        const size_t nMB = (size_t)(M > 0 ? M : 1) * (Btot > 0 ? Btot : 1);
+        const size_t c_uv = carve((o.uv && host_io) || (!o.uv && o.uv_valid), n * 8),
+                     c_lab = carve((o.label_bits && host_io) || (!o.label_bits && o.label_valid), n * 4),
+                     c_uvv = carve(o.uv_valid && host_io, n * 8), c_labv = carve(o.label_valid && host_io, n * 4),
+                     c_dep = carve(o.depth && host_io, n * 8), c_uf = carve(o.u_f && host_io, n * 8), c_vf = carve(o.v_f && host_io, n * 8),
+                     c_vi = carve(o.valid_idx && host_io, n * 8), c_ii = carve(o.inst_idx && host_io, (size_t)F * (size_t)(o.inst_cap > 0 ? o.inst_cap : 0) * 8),
+                     c_cmb = carve(o.count_mb && host_io, nMB * 4), c_sum = carve(host_io || !o.summary, (size_t)F * sizeof(lpf_frame_summary));
+        if (off && (rc = reserve(c, c->cams.out[k], off))) return rc;
+        char *base = (char *)c->cams.out[k].p;
+        auto pick = [&](void *user, size_t o_) -> void * { return o_ != (size_t)-1 ? (void *)(base + o_) : user; };
+        P.uv = (int2 *)pick(o.uv, c_uv); P.label_bits = (uint32_t *)pick(o.label_bits, c_lab);
+        P.uv_valid = (int2 *)pick(o.uv_valid, c_uvv); P.label_valid = (uint32_t *)pick(o.label_valid, c_labv);
+        P.depth = (double *)pick(o.depth, c_dep); P.uf = (double *)pick(o.u_f, c_uf); P.vf = (double *)pick(o.v_f, c_vf);
+        P.valid_idx = (long long *)pick(o.valid_idx, c_vi); P.inst_idx = (long long *)pick(o.inst_idx, c_ii);
+        P.count_out = (int32_t *)pick(o.count_mb, c_cmb); P.summary = pick(o.summary, c_sum);
+        const bool want_lists = o.valid_idx || o.inst_idx;
+        A.ntail[k] = (count_boxes ? ncblk : 0) + (want_lists ? nblk : 0);
+        max_tail = std::max(max_tail, A.ntail[k]);
+    }
+
+    // ---- the launch set: streaming tiles of every camera, then every camera's tail, then every camera's summaries --------------------
+    if (nk1 > 0) {
+        const dim3 g1((unsigned)nk1);
+#define LPF_CAMS_STREAM(R) do { if (lb_all == 1) hipLaunchKernelGGL((lpf_cams_stream<R, uint8_t>), g1, dim3(LPF_BLOCK), 0, c->stream, A); \
+                                else if (lb_all == 2) hipLaunchKernelGGL((lpf_cams_stream<R, uint16_t>), g1, dim3(LPF_BLOCK), 0, c->stream, A); \
+                                else hipLaunchKernelGGL((lpf_cams_stream<R, uint32_t>), g1, dim3(LPF_BLOCK), 0, c->stream, A); } while (0)
+        if (tile_pts == 512) LPF_CAMS_STREAM(2); else LPF_CAMS_STREAM(4);
+#undef LPF_CAMS_STREAM
+        LPF_HIP(c, hipGetLastError());
+    }
+    if (pre_scan && nk1 > 0)                                   // frames beyond 64 groups (16.7 M points): their prefixes, per camera
+        for (int k = 0; k < C; ++k) {
+            hipLaunchKernelGGL(lpf_scan_segments, dim3((unsigned)F), dim3(LPF_BLOCK), 0, c->stream, A.P[k]);
+            LPF_HIP(c, hipGetLastError());
+        }
+    if (max_tail > 0) {
+        const dim3 gt((unsigned)max_tail, (unsigned)C);
+        if (pre_scan) hipLaunchKernelGGL((lpf_cams_tail<true>), gt, dim3(LPF_BLOCK), 0, c->stream, A);
+        else hipLaunchKernelGGL((lpf_cams_tail<false>), gt, dim3(LPF_BLOCK), 0, c->stream, A);
+        LPF_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(lpf_cams_finalize, dim3((unsigned)F, (unsigned)C), dim3(LPF_BLOCK), 0, c->stream, A);
+    LPF_HIP(c, hipGetLastError());
+
+    // ---- host outputs: the dense arrays; the compact ones and the summaries written into page-locked result buffers by
+    //      lpf_results_to_host (as lpf_run_batch does), or else -- once the summaries are here -- the filled part of each list -------
+    bool any_host = false, lists_later = false;
+    bool later[LPF_MAX_CAMS] = {false, false, false, false};
+    std::vector<lpf_frame_summary> hs((size_t)F * C);
+    for (int k = 0; k < C; ++k) {
+        const lpf_outputs &o = out[k];
+        const LpfParams &P = A.P[k];
+        if (o.on_device) continue;
+        any_host = true;
+        const int nMB = P.M * (c->cams.bx[k].F ? c->cams.bx[k].box_off[F] : 0);
+#define LPF_D2H(member, field, bytes) \
+    if (o.member && (bytes)) LPF_HIP(c, hipMemcpyAsync(o.member, P.field, (bytes), hipMemcpyDeviceToHost, c->stream));
+        LPF_D2H(uv, uv, n * 8)
+        LPF_D2H(label_bits, label_bits, n * 4)
+        LPF_D2H(depth, depth, n * 8)
+        LPF_D2H(u_f, uf, n * 8)
+        LPF_D2H(v_f, vf, n * 8)
+        LpfToHost D;
+        memset(&D, 0, sizeof D);
+        bool r2h = o.summary != nullptr && (o.valid_idx || o.inst_idx);
+        auto alias = [&](void *host, void **dev) {
+            *dev = host ? device_alias_of_pinned(host) : nullptr;
+            if (host && !*dev) r2h = false;
+        };
+        if (r2h) {
+            alias(o.summary, &D.summary);
+            alias(o.valid_idx, (void **)&D.valid_idx);
+            alias(o.uv_valid, (void **)&D.uv_valid);
+            alias(o.label_valid, (void **)&D.label_valid);
+            alias(o.inst_idx, (void **)&D.inst_idx);
+            alias(o.count_mb, (void **)&D.count_mb);
+        }
+        if (r2h) {
+            D.inst_cap = o.inst_cap;
+            D.n_count = o.count_mb ? nMB : 0;
+            hipLaunchKernelGGL(lpf_results_to_host, dim3((unsigned)F * LPF_R2H_BLOCKS), dim3(LPF_BLOCK), 0, c->stream, P, D);
+            LPF_HIP(c, hipGetLastError());
+            continue;
+        }
+        LPF_D2H(count_mb, count_out, (size_t)nMB * 4)
+#undef LPF_D2H
+        LPF_HIP(c, hipMemcpyAsync(hs.data() + (size_t)k * F, P.summary, (size_t)F * sizeof(lpf_frame_summary), hipMemcpyDeviceToHost, c->stream));
+        later[k] = lists_later = true;
+    }
+    if (lists_later) {
+        LPF_HIP(c, host_wait(c));
+        for (int k = 0; k < C; ++k) {
+            const lpf_outputs &o = out[k];
+            const LpfParams &P = A.P[k];
+            if (!later[k]) continue;
+            for (int f = 0; f < F; ++f) {
+                const lpf_frame_summary &h = hs[(size_t)k * F + f];
+                const size_t nv = (size_t)h.n_valid;
+                if (o.valid_idx && nv)
+                    LPF_HIP(c, hipMemcpyAsync(o.valid_idx + frame_off[f], P.valid_idx + frame_off[f], nv * 8, hipMemcpyDeviceToHost, c->stream));
+                if (o.uv_valid && nv)
+                    LPF_HIP(c, hipMemcpyAsync(o.uv_valid + 2 * frame_off[f], P.uv_valid + frame_off[f], nv * 8, hipMemcpyDeviceToHost, c->stream));
+                if (o.label_valid && nv)
+                    LPF_HIP(c, hipMemcpyAsync(o.label_valid + frame_off[f], P.label_valid + frame_off[f], nv * 4, hipMemcpyDeviceToHost, c->stream));
+                int64_t tot = h.inst_off[LPF_MAX_MASKS];
+                if (tot > o.inst_cap) tot = o.inst_cap;
+                if (o.inst_idx && tot > 0)
+                    LPF_HIP(c, hipMemcpyAsync(o.inst_idx + (size_t)f * o.inst_cap, P.inst_idx + (size_t)f * o.inst_cap, (size_t)tot * 8,
+                                              hipMemcpyDeviceToHost, c->stream));
+            }
+            if (o.summary) memcpy(o.summary, hs.data() + (size_t)k * F, (size_t)F * sizeof(lpf_frame_summary));
+        }
+    }
+    if (any_host || host_in) LPF_HIP(c, host_wait(c));         // host buffers are filled, or may be reused
     return LPF_OK;
 }
 

@@ -321,8 +321,11 @@ struct LpfLabelSrc<LpfDirectRect<T, MODE> > {                // masks [F][M][H][
 #define LPF_RG_CELL (1 << LPF_RG_SHIFT)
 __device__ __forceinline__ unsigned lpf_wave_or(unsigned x);
 
-template <int ROWS, unsigned FL, typename LT>
-__device__ __forceinline__ void lpf_k1_tile(const LpfParams &P, const int blk, unsigned *s_cnt)
+// p: the tile's points, one float4 per row and lane -- loaded here, or (PRELOADED) already loaded by an earlier call for the same tile
+// (the multi-camera pass, lpf_cams.hip.h: one load, then this tile's work in each camera's LpfParams; the tile geometry depends on the
+// points only)
+template <int ROWS, unsigned FL, typename LT, bool PRELOADED>
+__device__ __forceinline__ void lpf_k1_tile(const LpfParams &P, const int blk, unsigned *s_cnt, float4 (&p)[ROWS])
 {
     // one block = one tile of 256*ROWS points; seg_pts / tile tiles share a segment (= one list wave of the tail)
     constexpr int TILE = LPF_BLOCK * ROWS;
@@ -353,9 +356,9 @@ __device__ __forceinline__ void lpf_k1_tile(const LpfParams &P, const int blk, u
     // a wave owns ROWS consecutive rows of 64 points: its ballots form one contiguous run
     {
         const int wbase = c + wave * (ROWS * 64) + lane;
-        float4 p[ROWS];
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) {
+            if constexpr (PRELOADED) continue;
             // clamp instead of branching: the loads issue back to back, waits are counted
             const float4 *src = pts + min(wbase + r * 64, seg_end - 1);
             if (FL & LPF_F_NTLOAD) {
@@ -500,6 +503,13 @@ __device__ __forceinline__ void lpf_k1_tile(const LpfParams &P, const int blk, u
             }
         }
     }
+}
+
+template <int ROWS, unsigned FL, typename LT>
+__device__ __forceinline__ void lpf_k1_tile(const LpfParams &P, const int blk, unsigned *s_cnt)
+{
+    float4 p[ROWS];
+    lpf_k1_tile<ROWS, FL, LT, false>(P, blk, s_cnt, p);
 }
 
 template <int ROWS, unsigned FL, typename LT = uint32_t>   // LT: label-image element (uint8 for M <= 8, uint16 for M <= 16), or LpfDirect<T, MODE>

@@ -17,7 +17,7 @@ from datetime import datetime
 import numpy as np
 
 from . import _native, kitti360
-from ._native import LpfContext, LPF_MAX_MASKS, LPF_MAX_MASKS_WIDE, Scan, ScanReader
+from ._native import LpfContext, LPF_MAX_CAMS, LPF_MAX_MASKS, LPF_MAX_MASKS_WIDE, Scan, ScanReader
 
 _CONTEXTS = {}
 
@@ -1050,6 +1050,64 @@ def _run_frames_in_mask_groups(frames, stacks, TrVeloToRect, camera, depth_max, 
     return merged
 
 
+def _n_points(points):
+    return len(points.points) if isinstance(points, Scan) else int(points.shape[0])
+
+
+def run_frames_multicam(frames_per_cam, cams, depth_max=50.0, min_points=10, use_oriented=True, erode_iters=0, v3_pipeline=False,
+                        device=0, ctx=None, gather_scans=True):
+    """run_frames for the same frames seen by up to four cameras, in ONE native pass (LpfContext.run_cams): every scan is staged and
+    read once, however many cameras label it.  ``cams[c] = (TrVeloToRect, camera)``; ``frames_per_cam[c]`` is camera c's list of
+    FrameInputs -- frame i of every camera carries the same points (the same frame id and point count; anything else raises
+    ValueError), its own masks, colors and boxes (the boxes camera c sees).  Returns ``results[c][i]`` equal to
+    ``run_frames(frames_per_cam[c], *cams[c], ...)[i]``, car_statistics and the lazy keys included.  A camera with a frame of more than
+    32 masks goes through run_frames on its own (the pass takes a 32-bit label word per camera); the results are the same."""
+    C = len(cams)
+    if not 1 <= C <= LPF_MAX_CAMS:
+        raise ValueError("run_frames_multicam takes 1 to %d cameras, got %d" % (LPF_MAX_CAMS, C))
+    if len(frames_per_cam) != C:
+        raise ValueError("frames for %d cameras, %d cameras given" % (len(frames_per_cam), C))
+    F = len(frames_per_cam[0])
+    for c, fs in enumerate(frames_per_cam):
+        if len(fs) != F:
+            raise ValueError("camera %d has %d frames, camera 0 has %d" % (c, len(fs), F))
+        for i, (f, f0) in enumerate(zip(fs, frames_per_cam[0])):
+            if f.frame != f0.frame or _n_points(f.points) != _n_points(f0.points):
+                raise ValueError("frame %d of camera %d (frame %r, %d points) is not camera 0's (frame %r, %d points): every camera "
+                                 "labels the same scans" % (i, c, f.frame, _n_points(f.points), f0.frame, _n_points(f0.points)))
+    if F == 0:
+        return [[] for _ in range(C)]
+    ctx = ctx or get_context(device)
+    results = [None] * C
+    passes = []                                           # (camera, stacks, counts, M, erode_iters, v3_pipeline)
+    for c, (T, camera) in enumerate(cams):
+        # (masks of another size are resized -- and with the V3 block eroded -- at camera c's size: the context's camera for that)
+        ctx.set_camera(T, camera.K, camera.width, camera.height, 0.0, float(depth_max))
+        stacks, er, v3 = _frame_mask_stacks(frames_per_cam[c], camera, ctx, erode_iters, v3_pipeline)
+        counts = [s.shape[0] for s in stacks]
+        if max(counts) > LPF_MAX_MASKS:
+            results[c] = run_frames(frames_per_cam[c], T, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline, device,
+                                    ctx, gather_scans)
+            continue
+        passes.append((c, stacks, counts, max(counts), er, v3))
+    if not passes:
+        return results
+    specs, positions = [], []
+    for c, stacks, counts, M, er, v3 in passes:
+        T, camera = cams[c]
+        corners, pos = zip(*(_corners_velo(f.bboxes_3d) for f in frames_per_cam[c]))
+        positions.append(pos)
+        specs.append(dict(T_velo_to_rect=T, K=camera.K, width=camera.width, height=camera.height, depth_min=0.0, depth_max=float(depth_max),
+                          masks=_mask_batch(stacks, M, camera.height, camera.width, ctx), binarize="v3" if v3 else "astype",
+                          erode_iters=er, boxes=list(corners), oriented=use_oriented))
+    pts = [f.points for f in frames_per_cam[passes[0][0]]]
+    # (results arrive in page-locked buffers the context reuses, one set per camera: _frame_result copies out what it hands on)
+    res = ctx.run_cams(pts, specs, want_uv=False, want_label=False, want_valid_uv=True, pinned=True)
+    for (c, stacks, counts, M, er, v3), rc, pos in zip(passes, res, positions):
+        results[c] = [_frame_result(f, r, m, p, min_points, gather_scans) for f, r, m, p in zip(frames_per_cam[c], rc, counts, pos)]
+    return results
+
+
 def stream_frames(scan_paths, inputs_for, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_oriented=True,
                   erode_iters=0, v3_pipeline=False, device=0, n_buffers=3, max_points=None, box_paths=None, announce=None, gather=True):
     """The frame loop with read-ahead: scans are read and moved to HBM by the native reader
@@ -1217,6 +1275,69 @@ def process_frames(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_
             if r["car_statistics"]:
                 append_to_master_csv(r["car_statistics"], r["frame"], master_csv_path, timestamp)
     return analyze_master_csv(master_csv_path)
+
+
+def process_frames_multicam(seq=0, cam_ids=(0, 1), segmenter=None, image_loader=None, kitti360_path=None, master_csv_paths=None,
+                            frames=None, erode_iters=0, v3_pipeline=False, device=0, timestamp=None):
+    """process_frames for several perspective cameras of the rig at once: each scan is read once (the native read-ahead reader) and
+    each box file parsed once; per frame the segmenter runs on every camera's image and ONE pass (run_frames_multicam) labels the scan
+    in all of them.  Camera c's boxes are prepared with camera c's TrVeloToCam and visibility filter, as the reference does for
+    ``cam_id = c`` (V3:532-535, 561-562: the cam-0 corners go through the selected camera's transform).  Camera c's rows go to
+    ``master_csv_paths[c]`` (default ``results/master_car_statistics_cam<c>.csv``), byte for byte what
+    ``process_frames(seq, cam_id=c, ...)`` writes with the same arguments and timestamp.  Skip rules per the reference: a frame without
+    a box file (or with an empty one) is skipped for every camera -- the reference skips before it looks at an image; a missing image
+    or no detections skip only that camera's part of the frame.  Returns ``{cam_id: analyze_master_csv(path)}``."""
+    if segmenter is None:
+        raise ValueError("process_frames_multicam needs the segmentation callable (YOLO stays outside this package)")
+    cam_ids = [int(c) for c in cam_ids]
+    if not 1 <= len(cam_ids) <= LPF_MAX_CAMS or len(set(cam_ids)) != len(cam_ids) or any(c not in (0, 1) for c in cam_ids):
+        raise ValueError("cam_ids: 1 to %d distinct perspective cameras (0, 1), got %r" % (LPF_MAX_CAMS, cam_ids))
+    if master_csv_paths is None:
+        master_csv_paths = {c: "results/master_car_statistics_cam%d.csv" % c for c in cam_ids}
+    elif not isinstance(master_csv_paths, dict):
+        master_csv_paths = dict(zip(cam_ids, master_csv_paths))
+    root = kitti360_path or os.environ["KITTI360_DATASET"]
+    setups = {c: sequence_setup(root, seq, c) for c in cam_ids}
+    sequence, _, _, _, velo = setups[cam_ids[0]]
+    todo = velo.available_frames() if frames is None else list(frames)
+    print(f"Found {len(todo)} frames to process")
+    box_paths = [os.path.join(root, "bboxes_3D_cam0", f"BBoxes_{f}.json") for f in todo]
+    scan_paths = [os.path.join(velo.raw3DPcdPath, "%010d.bin" % f) for f in todo]
+    sizes = [os.path.getsize(p) // 16 for p in scan_paths if os.path.isfile(p)]
+    ctx = get_context(device)
+    with ScanReader(ctx, scan_paths, n_buffers=3, max_points=max(sizes + [1]), box_paths=box_paths) as reader:
+        for i, frame in enumerate(todo):
+            print(f"\nProcessing frame {frame}...")
+            try:
+                scan = next(reader)
+            except RuntimeError as e:
+                print(f"Failed to load frame {os.path.basename(scan_paths[i])}: {e}")
+                continue
+            parsed = (scan.boxes_state, scan.box_index, scan.boxes_cam0)
+            inputs, cams = {}, {}
+            for c in cam_ids:
+                _, camera, velo_to_cam, velo_to_rect, _ = setups[c]
+                boxes = _boxes_of_file(box_paths[i], camera, velo_to_cam, parsed=parsed)
+                if boxes is None:                        # (no box file: the same for every camera -- the frame is skipped)
+                    break
+                image_path = os.path.join(root, "data_2d_raw", sequence, f"image_{c:02d}", "data_rect", f"{frame:010d}.png")
+                if not os.path.isfile(image_path):
+                    continue
+                _, masks, colors, _, _ = segmenter(image_loader(image_path) if image_loader else image_path)
+                if masks is None or len(masks) == 0:
+                    continue
+                inputs[c] = FrameInputs(frame, scan, masks, boxes, colors)
+                cams[c] = (velo_to_rect, camera)
+            if not inputs:
+                continue
+            order = list(inputs)
+            res = run_frames_multicam([[inputs[c]] for c in order], [cams[c] for c in order], 50.0, 10, True, erode_iters, v3_pipeline,
+                                      device, ctx, gather_scans=False)
+            for c, r in zip(order, res):
+                r = r[0]
+                if r["n_valid"] and r["car_statistics"]:
+                    append_to_master_csv(r["car_statistics"], r["frame"], master_csv_paths[c], timestamp)
+    return {c: analyze_master_csv(master_csv_paths[c]) for c in cam_ids}
 
 
 def process_frame_with_statistics(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_path=None,
