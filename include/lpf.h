@@ -48,9 +48,10 @@ extern "C" {
                                          refuses an exact halving (it is cv2.resize's INTER_AREA case)
                                       8 (continued): LPF_MAX_MASKS_WIDE, lpf_wide_input, lpf_wide_outputs, lpf_run_wide (added; nothing
                                          else changed)
-                                      8 (continued): LPF_MAX_CAMS, lpf_cam_input, lpf_run_cams (added; nothing else changed) */
+                                      8 (continued): LPF_MAX_CAMS, lpf_cam_input, lpf_run_cams (added; nothing else changed)
+                                      8 (continued): lpf_run_cams_wide (added; nothing else changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
-#define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams pass */
+#define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
 typedef enum lpf_status {
     LPF_OK = 0,
@@ -344,7 +345,7 @@ typedef struct lpf_cam_input {
     double         K[9];
     int32_t        W, H;
     double         depth_min_excl, depth_max_excl;
-    lpf_wide_input masks;                  /* [F][M][H][W] + optional rects [F][M][4], M <= LPF_MAX_MASKS */
+    lpf_wide_input masks;                  /* [F][M][H][W] + optional rects [F][M][4], M <= LPF_MAX_MASKS (lpf_run_cams_wide: LPF_MAX_MASKS_WIDE) */
     const double  *corners_velo;           /* [Btot][8][3] velodyne-frame corners (lpf_set_boxes_ex), or NULL: no boxes */
     const int32_t *box_off;                /* [F + 1], host memory (with corners_velo) */
     int32_t        boxes_on_device;        /* 0 / 1 / 2 as lpf_set_boxes_ex's on_device */
@@ -352,6 +353,24 @@ typedef struct lpf_cam_input {
 } lpf_cam_input;
 int lpf_run_cams(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_cam_input *cams, int C,
                  const lpf_outputs *out /* [C] */);
+
+/* lpf_run_cams_wide: lpf_run_cams with up to LPF_MAX_MASKS_WIDE masks per camera -- a batch of F frames labelled in C cameras
+ * (1 <= C <= LPF_MAX_CAMS), camera c with 0 <= cams[c].masks.M <= LPF_MAX_MASKS_WIDE masks per frame, in ONE pass: every point is read
+ * from memory once and projected, clipped and labelled in each camera's arithmetic with LW_c = ceil(M_c / 32) label words; each later
+ * stage (compaction, instance lists, box counts, best boxes) is one launch for all C cameras (each camera's mask pack and box tables are
+ * launches of their own, ahead of them).  Cameras may differ in M, mask type, binarisation, erosion, rectangles, image size, depth window
+ * and boxes.  out[c] is, field for field and bit for bit, what a fresh context gives for
+ *   lpf_set_camera(cams[c].T_velo_to_rect, K, W, H, depth_min_excl, depth_max_excl)
+ *   lpf_set_boxes_ex(corners_velo, boxes_on_device, box_off, F, oriented)   if corners_velo (else no boxes)
+ *   lpf_run_wide(pts, frame_off, F, pts_on_device, &cams[c].masks, &out[c])
+ * LW_c sets the width of out[c].label_words and label_valid_words.  The checks are lpf_run_cams', with the mask limit raised to
+ * LPF_MAX_MASKS_WIDE.  The context's camera, masks, rectangles and boxes in force are left as they were, and so is what lpf_run_cams and
+ * lpf_run_wide keep between calls.  Not capturable (LPF_ERR_STATE between lpf_graph_begin and lpf_graph_end); with a software-pipelined
+ * mode on it first launches what the pipeline owes (no host wait), then runs in order.  Outputs: each out[c] is in host or device memory
+ * per its own on_device; with device outputs and device inputs the call only enqueues work, with host outputs it returns with them
+ * filled. */
+int lpf_run_cams_wide(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_cam_input *cams, int C,
+                      const lpf_wide_outputs *out /* [C] */);
 
 /* ---- box membership as a stand-alone operator -------------------------------------------
  * inside[b*k + i] = 1 if point i lies in box b, else 0: the boolean arrays the reference's

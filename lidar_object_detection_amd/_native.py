@@ -62,7 +62,7 @@ class WideOutputs(ctypes.Structure):
                 ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
-LPF_MAX_CAMS = 4                        # lpf_run_cams: cameras of one pass
+LPF_MAX_CAMS = 4                        # lpf_run_cams / lpf_run_cams_wide: cameras of one pass
 
 
 class CamInput(ctypes.Structure):
@@ -217,6 +217,7 @@ def load(path=None):
     lib.lpf_run_frame.argtypes = [_P, ctypes.POINTER(FrameJob)]
     lib.lpf_run_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(WideOutputs)]
     lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
+    lib.lpf_run_cams_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(WideOutputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
     lib.lpf_depth_image.argtypes = [_P, _P, _I64, ctypes.c_int, _P, _P]
     lib.lpf_prepare_boxes.argtypes = [_P, _P, ctypes.c_int, _P, _P, _P, _P, _P]
@@ -250,7 +251,8 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_points_in_boxes", "lpf_prepare_boxes", "lpf_depth_image", "lpf_resize_masks_u8", "lpf_erode_masks_u8", "lpf_get_stats", "lpf_profile_enable", "lpf_profile_read", "lpf_profile_overhead",
             "lpf_graph_begin", "lpf_graph_end", "lpf_graph_launch", "lpf_graph_destroy",
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
-            "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams")
+            "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
+            "lpf_run_cams_wide")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -1004,21 +1006,12 @@ class LpfContext:
             return (summ, per_point, per_valid, iidx, cmb), need
         return finish
 
-    def run_cams(self, frames, cams, want_uv=True, want_label=True, want_float=False, want_lists=True, inst_cap=None,
-                 want_valid_uv=False, pinned=False):
-        """One batch of frames labelled in up to four cameras in ONE native pass (lpf_run_cams): the points are staged once (as
-        run_batch's ``frames``: host arrays, Scans of a ScanReader, float32 [N,4] GPU tensors) and read once by the GPU.
-        cams: one dict per camera --
-          T_velo_to_rect  4x4, K  (3x3 or larger), width, height, depth_min (0.0), depth_max (50.0)  -- set_camera's arguments
-          masks           [M,H,W] (one frame) or [F,M,H,W], uint8 / bool or float32, NumPy or a contiguous GPU tensor, M <= 32; or None
-          binarize        float masks: "astype" (default), "v3" or "gt0.5" (set_masks'); v3_pipeline=True means "v3"
-          erode_iters     (0), rects: the optional [F,M,4] hint of set_mask_rects (where the masks are)
-          boxes           one f64 [B_f,8,3] array of velodyne-frame corners per frame (set_boxes'), or None; oriented (True)
-        Returns one list per camera of what run_batch returns for that camera after set_camera / set_mask_rects / set_masks /
-        set_boxes with the same arguments -- equal, array for array.  The context's camera, masks and boxes are left as they were."""
+    def _cam_inputs(self, frames, cams, max_masks, who):
+        """The lpf_cam_input array of a multi-camera pass over ``frames`` (run_cams' camera dicts), checked before anything reaches the
+        GPU: (CamInput [C], masks per camera, box offsets per camera or None, what must stay alive until the run returns)."""
         C = len(cams)
         if not 1 <= C <= LPF_MAX_CAMS:
-            raise ValueError("run_cams takes 1 to %d cameras, got %d" % (LPF_MAX_CAMS, C))
+            raise ValueError("%s takes 1 to %d cameras, got %d" % (who, LPF_MAX_CAMS, C))
         F = len(frames)
         if F == 0:
             raise ValueError("no frames")
@@ -1036,9 +1029,9 @@ class LpfContext:
                 masks = np.zeros((F, 0, H, W), np.uint8)
             erode = cam.get("erode_iters", 0)
             masks, M, is_f, mdev, rects = wide_mask_batch(masks, F, H, W, cam.get("rects"), erode, binarize, self.BINARIZE)
-            if M > LPF_MAX_MASKS:
+            if M > max_masks:
                 raise ValueError("camera %d has %d masks per frame: a multi-camera pass takes at most %d per camera (run_wide takes more)"
-                                 % (k, M, LPF_MAX_MASKS))
+                                 % (k, M, max_masks))
             if mdev:
                 import torch
                 self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
@@ -1068,6 +1061,22 @@ class LpfContext:
             keep += [masks, rects]
             Ms.append(M)
             box_offs.append(box_off)
+        return cin, Ms, box_offs, keep
+
+    def run_cams(self, frames, cams, want_uv=True, want_label=True, want_float=False, want_lists=True, inst_cap=None,
+                 want_valid_uv=False, pinned=False):
+        """One batch of frames labelled in up to four cameras in ONE native pass (lpf_run_cams): the points are staged once (as
+        run_batch's ``frames``: host arrays, Scans of a ScanReader, float32 [N,4] GPU tensors) and read once by the GPU.
+        cams: one dict per camera --
+          T_velo_to_rect  4x4, K  (3x3 or larger), width, height, depth_min (0.0), depth_max (50.0)  -- set_camera's arguments
+          masks           [M,H,W] (one frame) or [F,M,H,W], uint8 / bool or float32, NumPy or a contiguous GPU tensor, M <= 32; or None
+          binarize        float masks: "astype" (default), "v3" or "gt0.5" (set_masks'); v3_pipeline=True means "v3"
+          erode_iters     (0), rects: the optional [F,M,4] hint of set_mask_rects (where the masks are)
+          boxes           one f64 [B_f,8,3] array of velodyne-frame corners per frame (set_boxes'), or None; oriented (True)
+        Returns one list per camera of what run_batch returns for that camera after set_camera / set_mask_rects / set_masks /
+        set_boxes with the same arguments -- equal, array for array.  The context's camera, masks and boxes are left as they were."""
+        cin, Ms, box_offs, _keep_in = self._cam_inputs(frames, cams, LPF_MAX_MASKS, "run_cams")
+        C, F = len(cams), len(frames)
         off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the run returns)
         n = int(off[-1])
         wants = dict(want_uv=want_uv, want_label=want_label, want_float=want_float, want_lists=want_lists, want_valid_uv=want_valid_uv)
@@ -1082,6 +1091,55 @@ class LpfContext:
 
         outs = self._until_lists_fit(launch, inst_cap, off)
         return [self._frame_results(off, Ms[k], *outs[k], box_off=box_offs[k]) for k in range(C)]
+
+    def _wide_host_outputs(self, o, n, F, M, Btot, inst_cap, want_uv, want_float, want_lists, want_valid_uv, want_label=True, pinned=False,
+                           tag=""):
+        """Host result arrays of a wide run (Ntot = n points, F frames, M masks, Btot boxes), wired into the lpf_wide_outputs ``o``.
+        Returns finish() -> ((summary columns, per_point, per_valid, inst_idx, count_mb), 0 or the list capacity the run needed) for
+        after the call.  want_label=False: no dense label_words.  pinned: the context's page-locked buffers (names prefixed by ``tag``),
+        reused by the next run -- no allocation and no page faults per call, and the copies back are DMA transfers."""
+        LW = (M + 31) // 32
+        if pinned:
+            def new(name, shape, dt, fill=None):
+                a = self._pinned(tag + "w_" + name, shape, dt)
+                if fill is not None:
+                    a[...] = fill
+                return a
+        else:
+            def new(name, shape, dt, fill=None):
+                return np.empty(shape, dt) if fill is None else np.full(shape, fill, dt)
+        o.on_device = 0
+        uv = new("uv", (n, 2), np.int32) if want_uv else None
+        dep, uf, vf = [(new(k, (n,), np.float64) if want_float else None) for k in ("dep", "uf", "vf")]
+        words = new("words", (n, LW), np.uint32) if want_label else None
+        vidx = new("vidx", (n,), np.int64) if want_lists else None
+        uvv = new("uvv", (n, 2), np.int32) if (want_valid_uv and want_lists) else None
+        lvw = new("lvw", (n, LW), np.uint32) if (want_valid_uv and want_lists) else None
+        iidx = new("iidx", (F, inst_cap), np.int64) if (want_lists and M) else None
+        cmb = new("cmb", (max(M * Btot, 1),), np.int32, 0)
+        nv, nl = new("nv", (F,), np.int64, 0), new("nl", (F,), np.int64, 0)
+        ic, io = new("ic", (F, M), np.int64, 0), new("io", (F, M + 1), np.int64, 0)
+        bc, bb, ov = new("bc", (F, M), np.int64, 0), new("bb", (F, M), np.int32, -1), new("ov", (F,), np.int32, 0)
+        for name, arr in (("uv", uv), ("depth", dep), ("u_f", uf), ("v_f", vf), ("valid_idx", vidx), ("uv_valid", uvv),
+                          ("label_words", words), ("label_valid_words", lvw), ("inst_idx", iidx), ("count_mb", cmb),
+                          ("n_valid", nv), ("n_labelled", nl), ("inst_count", ic), ("inst_off", io), ("best_cnt", bc),
+                          ("best_box", bb), ("inst_overflow", ov)):
+            setattr(o, name, arr.ctypes.data if (arr is not None and arr.size) else None)
+        o.inst_cap = inst_cap
+
+        def finish():
+            summ = dict(n_valid=nv, n_labelled=nl, inst_count=ic, inst_off=io, best_box=bb, best_cnt=bc)
+            per_point = dict(label_words=words) if want_label else {}
+            if want_uv:
+                per_point.update(u=uv[:, 0], v=uv[:, 1])
+            if want_float:
+                per_point.update(depth=dep, uf=uf, vf=vf)
+            per_valid = dict(valid_idx=vidx) if want_lists else {}
+            if uvv is not None:
+                per_valid.update(uv_valid=uvv, u_valid=uvv[:, 0], v_valid=uvv[:, 1], label_valid_words=lvw)
+            need = int(io[:, M].max()) if (iidx is not None and ov.any()) else 0
+            return (summ, per_point, per_valid, iidx, cmb), need
+        return finish
 
     def run_wide(self, frames, masks, erode_iters=0, binarize="astype", rects=None, v3_pipeline=False, want_uv=True, want_float=False,
                  want_lists=True, want_valid_uv=False, inst_cap=None):
@@ -1099,7 +1157,6 @@ class LpfContext:
         if F == 0:
             raise ValueError("no frames")
         masks, M, is_f, mdev, rects = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
-        LW = (M + 31) // 32
         off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the run returns)
         n = int(off[-1])
         if mdev:
@@ -1111,42 +1168,42 @@ class LpfContext:
         inp.M, inp.f32, inp.binarize, inp.erode_iters = M, int(is_f), self.BINARIZE[binarize], int(erode_iters)
         inp.on_device = 1 if mdev else 0
         Btot = int(self.box_off[-1]) if self.box_off is not None else 0
+        wants = dict(want_uv=want_uv, want_float=want_float, want_lists=want_lists, want_valid_uv=want_valid_uv)
 
         def launch(inst_cap):
             o = WideOutputs()
-            o.on_device = 0
-            uv = np.empty((n, 2), np.int32) if want_uv else None
-            dep, uf, vf = [(np.empty(n, np.float64) if want_float else None) for _ in range(3)]
-            words = np.empty((n, LW), np.uint32)
-            vidx = np.empty(n, np.int64) if want_lists else None
-            uvv = np.empty((n, 2), np.int32) if (want_valid_uv and want_lists) else None
-            lvw = np.empty((n, LW), np.uint32) if (want_valid_uv and want_lists) else None
-            iidx = np.empty((F, inst_cap), np.int64) if (want_lists and M) else None
-            cmb = np.zeros(max(M * Btot, 1), np.int32)
-            nv, nl = np.zeros(F, np.int64), np.zeros(F, np.int64)
-            ic, io = np.zeros((F, M), np.int64), np.zeros((F, M + 1), np.int64)
-            bc, bb, ov = np.zeros((F, M), np.int64), np.full((F, M), -1, np.int32), np.zeros(F, np.int32)
-            for name, arr in (("uv", uv), ("depth", dep), ("u_f", uf), ("v_f", vf), ("valid_idx", vidx), ("uv_valid", uvv),
-                              ("label_words", words), ("label_valid_words", lvw), ("inst_idx", iidx), ("count_mb", cmb),
-                              ("n_valid", nv), ("n_labelled", nl), ("inst_count", ic), ("inst_off", io), ("best_cnt", bc),
-                              ("best_box", bb), ("inst_overflow", ov)):
-                setattr(o, name, arr.ctypes.data if (arr is not None and arr.size) else None)
-            o.inst_cap = inst_cap
+            finish = self._wide_host_outputs(o, n, F, M, Btot, inst_cap, **wants)
             self._check(self._lib.lpf_run_wide(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
-            summ = dict(n_valid=nv, n_labelled=nl, inst_count=ic, inst_off=io, best_box=bb, best_cnt=bc)
-            per_point = dict(label_words=words)
-            if want_uv:
-                per_point.update(u=uv[:, 0], v=uv[:, 1])
-            if want_float:
-                per_point.update(depth=dep, uf=uf, vf=vf)
-            per_valid = dict(valid_idx=vidx) if want_lists else {}
-            if uvv is not None:
-                per_valid.update(uv_valid=uvv, u_valid=uvv[:, 0], v_valid=uvv[:, 1], label_valid_words=lvw)
-            need = int(io[:, M].max()) if (iidx is not None and ov.any()) else 0
-            return (summ, per_point, per_valid, iidx, cmb), need
+            return finish()
 
         out = self._until_lists_fit(launch, inst_cap, off)
         return self._frame_results(off, M, *out)
+
+    def run_cams_wide(self, frames, cams, want_uv=True, want_float=False, want_lists=True, want_valid_uv=False, inst_cap=None,
+                      want_label=True, pinned=False):
+        """run_cams with up to 256 masks per camera, in ONE native pass (lpf_run_cams_wide): the points are staged once (as run_batch's
+        ``frames``) and read once by the GPU, every camera's masks give ceil(M / 32) label words per point.  cams: run_cams' camera
+        dicts, masks of up to 256 per frame.  Returns ``results[c][f]``: what run_wide returns for frame f after set_camera / set_boxes
+        with camera c's arguments -- equal, array for array.  The context's camera, masks and boxes are left as they were.
+        want_label=False leaves out the dense label_words (label_valid_words, with want_valid_uv, still come back).  pinned=True: the
+        result arrays are views into page-locked buffers the context owns and reuses -- valid until the next run on this context."""
+        cin, Ms, box_offs, _keep_in = self._cam_inputs(frames, cams, LPF_MAX_MASKS_WIDE, "run_cams_wide")
+        C, F = len(cams), len(frames)
+        off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the run returns)
+        n = int(off[-1])
+        wants = dict(want_uv=want_uv, want_float=want_float, want_lists=want_lists, want_valid_uv=want_valid_uv, want_label=want_label,
+                     pinned=pinned)
+
+        def launch(inst_cap):
+            outs = (WideOutputs * C)()
+            fins = [self._wide_host_outputs(outs[k], n, F, Ms[k], int(box_offs[k][-1]) if box_offs[k] is not None else 0, inst_cap,
+                                            tag="cam%d_" % k, **wants) for k in range(C)]
+            self._check(self._lib.lpf_run_cams_wide(self._h, pts_ptr, off.ctypes.data, F, pts_dev, cin, C, outs))
+            res = [fin() for fin in fins]
+            return [r for r, _ in res], max(need for _, need in res)
+
+        outs = self._until_lists_fit(launch, inst_cap, off)
+        return [self._frame_results(off, Ms[k], *outs[k], box_off=box_offs[k]) for k in range(C)]
 
     # -- the hot path, device tensors (asynchronous) -------------------------------------
     def run_device(self, pts, frame_off, uv=None, label_bits=None, depth=None, u_f=None, v_f=None,

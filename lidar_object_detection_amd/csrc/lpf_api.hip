@@ -4,6 +4,7 @@
 #include "lpf_kernels.hip.h"
 #include "lpf_wide.hip.h"
 #include "lpf_cams.hip.h"
+#include "lpf_cams_wide.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -172,6 +173,9 @@ struct lpf_ctx {
     // lpf_run_cams: camera c's box tables, label images, staged masks / rectangles and host-output staging (grow-only, allocated on
     // first use); its counters and geometry tables are scratch set c's
     struct Cams { BoxSet bx[LPF_NSETS]; DevBuf label_a[LPF_NSETS], label_b[LPF_NSETS], masks[LPF_NSETS], rects[LPF_NSETS], out[LPF_NSETS], pts; } cams;
+    // lpf_run_cams_wide: camera c's lpf_run_wide buffers (cam[c]: staged masks, planes, scratch, host-output staging), the pass's frame
+    // tables and staged points (grow-only, allocated on first use); its box tables are lpf_run_cams' (cams.bx[c])
+    struct CamsWide { Wide cam[LPF_NSETS]; DevBuf tab, pts; } camsw;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -859,6 +863,13 @@ void lpf_destroy(lpf_ctx *c)
         for (DevBuf *b : cb) release(*b);
     }
     release(c->cams.pts);
+    for (lpf_ctx::Wide *D : {&c->wide, &c->camsw.cam[0], &c->camsw.cam[1], &c->camsw.cam[2], &c->camsw.cam[3]}) {
+        DevBuf *wb[] = {&D->tab, &D->masks, &D->rects, &D->planes_a, &D->planes_b, &D->flags, &D->ccnt, &D->cpre, &D->fcnt, &D->midx, &D->mwords,
+                        &D->mpts, &D->cnt, &D->uv, &D->words, &D->pts, &D->out};
+        for (DevBuf *b : wb) release(*b);
+    }
+    release(c->camsw.tab);
+    release(c->camsw.pts);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_uvv, &c->st_labv, &c->st_pts, &c->st_uv, &c->st_label,
                      &c->st_depth, &c->st_uf, &c->st_vf, &c->st_valid, &c->st_inst, &c->st_count, &c->st_summary};
     for (DevBuf *b : all) release(*b);
@@ -1920,6 +1931,139 @@ int lpf_profile_read(lpf_ctx *c, double *k1_ms_sum, int64_t *k1_launches, int re
 }
 
 // ---- lpf_run_wide (include/lpf.h): frames of up to LPF_MAX_MASKS_WIDE masks, kernels in lpf_wide.hip.h ----------------------
+// The parts of a wide run that lpf_run_cams_wide repeats per camera, on that camera's buffers D:
+
+// masks (host masks are staged into D; device masks are lent) -> LW planes in D (+ erosion); W.planes = the result (NULL: no masks).
+// *host_in: the masks were read from host memory
+static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int F, int Wimg, int Himg, LpfWideParams &W, bool *host_in)
+{
+    int rc;
+    const int M = in->M, LW = (M + 31) / 32;
+    const size_t hw = (size_t)Wimg * Himg;
+    const size_t esz = in->f32 ? 4 : 1;
+    const void *d_masks = in->masks;
+    const int32_t *d_rects = in->rects;
+    W.planes = nullptr;
+    if (M > 0 && !in->on_device) {
+        const size_t bytes = (size_t)F * M * hw * esz;
+        if ((rc = reserve(c, D.masks, bytes))) return rc;
+        LPF_HIP(c, hipMemcpyAsync(D.masks.p, in->masks, bytes, hipMemcpyHostToDevice, c->stream));
+        d_masks = D.masks.p;
+        if (in->rects) {
+            if ((rc = reserve(c, D.rects, (size_t)F * M * 16))) return rc;
+            LPF_HIP(c, hipMemcpyAsync(D.rects.p, in->rects, (size_t)F * M * 16, hipMemcpyHostToDevice, c->stream));
+            d_rects = (const int32_t *)D.rects.p;
+        }
+        *host_in = true;
+    }
+    // (the rectangles hold where lpf_set_mask_rects takes them: uint8, or float under binarize 0, without erosion)
+    const int4 *rects = (in->rects && in->erode_iters == 0 && (!in->f32 || in->binarize == 0)) ? (const int4 *)d_rects : nullptr;
+
+    // ---- pack (+ erosion) into LW planes --------------------------------------------------------------------------------------
+    if (M > 0) {
+        if ((rc = reserve(c, D.planes_a, (size_t)F * LW * hw * 4))) return rc;
+        uint32_t *cur = (uint32_t *)D.planes_a.p;
+        const dim3 grid((Wimg + LPF_TW - 1) / LPF_TW, (Himg + LPF_TH - 1) / LPF_TH, (unsigned)(F * LW));
+        const int fuse = in->erode_iters > 0 ? 1 : 0;
+        if (!in->f32)
+            hipLaunchKernelGGL((lpf_wide_pack<uint8_t, 0>), grid, dim3(LPF_BLOCK), 0, c->stream, (const uint8_t *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
+        else if (in->binarize == 0)
+            hipLaunchKernelGGL((lpf_wide_pack<float, 1>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
+        else if (in->binarize == 1)
+            hipLaunchKernelGGL((lpf_wide_pack<float, 2>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
+        else
+            hipLaunchKernelGGL((lpf_wide_pack<float, 3>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
+        LPF_HIP(c, hipGetLastError());
+        if (in->erode_iters > 1) {                        // further iterations: the narrow path's own kernel, a plane per (frame, word)
+            if ((rc = reserve(c, D.planes_b, (size_t)F * LW * hw * 4))) return rc;
+            uint32_t *other = (uint32_t *)D.planes_b.p;
+            for (int it = 1; it < in->erode_iters; ++it) {
+                hipLaunchKernelGGL((lpf_erode_packed<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, Himg, Wimg);
+                LPF_HIP(c, hipGetLastError());
+                std::swap(cur, other);
+            }
+        }
+        W.planes = cur;
+    }
+    return LPF_OK;
+}
+
+// where a wide run's outputs go: the caller's device pointers, or staging carved out of D.out for host callers (offsets below)
+struct WideStage {
+    size_t uv, dep, uf, vf, vi, uvv, lw, lvw, ii, cmb, nv, nl, ic, io, bc, bb, of;
+};
+
+// outputs and scratch of a wide run of n points, F frames, W.M masks, Btot boxes, W.nchunk chunks, on buffers D -> W's pointers
+static int wide_bind(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_outputs *out, size_t n, int F, int Btot, LpfWideParams &W, WideStage &S)
+{
+    int rc;
+    const int M = W.M, LW = W.LW, nchunk = W.nchunk;
+    const bool host_io = !out->on_device;
+    const size_t nF = (size_t)F, nFM = (size_t)F * M, nMB = (size_t)M * Btot, ncap = out->inst_cap > 0 ? (size_t)F * out->inst_cap : 0;
+    size_t off = 0;
+    auto carve = [&](const void *want, size_t bytes) -> size_t { if (!want || !host_io) return (size_t)-1; const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    S.uv = carve(out->uv, n * 8); S.dep = carve(out->depth, n * 8); S.uf = carve(out->u_f, n * 8); S.vf = carve(out->v_f, n * 8);
+    S.vi = carve(out->valid_idx, n * 8); S.uvv = carve(out->uv_valid, n * 8); S.lw = carve(out->label_words, n * LW * 4);
+    S.lvw = carve(out->label_valid_words, n * LW * 4); S.ii = carve(out->inst_idx, ncap * 8); S.cmb = carve(out->count_mb, nMB * 4);
+    S.nv = carve(out->n_valid, nF * 8); S.nl = carve(out->n_labelled, nF * 8); S.ic = carve(out->inst_count, nFM * 8);
+    S.io = carve(out->inst_off, (nFM + nF) * 8); S.bc = carve(out->best_cnt, nFM * 8); S.bb = carve(out->best_box, nFM * 4);
+    S.of = carve(out->inst_overflow, nF * 4);
+    if (host_io && off && (rc = reserve(c, D.out, off))) return rc;
+    auto dst = [&](void *user, size_t o) -> void * { return !user ? nullptr : host_io ? (void *)((char *)D.out.p + o) : user; };
+    W.uv = (int2 *)dst(out->uv, S.uv);
+    if (!W.uv) { if ((rc = reserve(c, D.uv, n * 8))) return rc; W.uv = (int2 *)D.uv.p; }
+    W.depth = (double *)dst(out->depth, S.dep); W.uf = (double *)dst(out->u_f, S.uf); W.vf = (double *)dst(out->v_f, S.vf);
+    W.valid_idx = (long long *)dst(out->valid_idx, S.vi); W.uv_valid = (int2 *)dst(out->uv_valid, S.uvv);
+    W.label_words = (uint32_t *)dst(out->label_words, S.lw);
+    if (!W.label_words) { if ((rc = reserve(c, D.words, n * LW * 4))) return rc; W.label_words = (uint32_t *)D.words.p; }
+    W.label_valid = (uint32_t *)dst(out->label_valid_words, S.lvw);
+    W.inst_idx = (long long *)dst(out->inst_idx, S.ii); W.count_out = (int32_t *)dst(out->count_mb, S.cmb);
+    W.n_valid = (long long *)dst(out->n_valid, S.nv); W.n_labelled = (long long *)dst(out->n_labelled, S.nl);
+    W.inst_count = (long long *)dst(out->inst_count, S.ic); W.inst_off = (long long *)dst(out->inst_off, S.io);
+    W.best_cnt = (long long *)dst(out->best_cnt, S.bc); W.best_box = (int32_t *)dst(out->best_box, S.bb);
+    W.inst_overflow = (int32_t *)dst(out->inst_overflow, S.of);
+    if ((rc = reserve(c, D.flags, (size_t)std::max(nchunk, 1) * LPF_WIDE_CHUNK))) return rc;
+    if ((rc = reserve(c, D.ccnt, (size_t)std::max(nchunk, 1) * 8))) return rc;
+    if ((rc = reserve(c, D.cpre, (size_t)std::max(nchunk, 1) * 8))) return rc;
+    if ((rc = reserve(c, D.fcnt, nF * 8))) return rc;
+    if ((rc = reserve(c, D.midx, n * 4))) return rc;
+    if ((rc = reserve(c, D.mwords, n * LW * 4))) return rc;
+    if ((rc = reserve(c, D.mpts, n * 16))) return rc;
+    if ((rc = reserve(c, D.cnt, nMB * 4))) return rc;
+    W.flags = (uint32_t *)D.flags.p; W.chunk_cnt = (int2 *)D.ccnt.p; W.chunk_pre = (int2 *)D.cpre.p; W.fcnt = (int2 *)D.fcnt.p;
+    W.m_idx = (int *)D.midx.p; W.m_words = (uint32_t *)D.mwords.p; W.m_pts = (float4 *)D.mpts.p; W.cnt = (unsigned *)D.cnt.p;
+    return LPF_OK;
+}
+
+// host outputs of a wide run bound by wide_bind: the copies back, queued on the stream
+static int wide_back(lpf_ctx *c, const lpf_ctx::Wide &D, const lpf_wide_outputs *out, const WideStage &S, size_t n, int F, int M, int Btot)
+{
+    const int LW = (M + 31) / 32;
+    const size_t nF = (size_t)F, nFM = (size_t)F * M, nMB = (size_t)M * Btot, ncap = out->inst_cap > 0 ? (size_t)F * out->inst_cap : 0;
+    auto back = [&](void *user, size_t o, size_t bytes) -> hipError_t {
+        if (!user || !bytes) return hipSuccess;
+        return hipMemcpyAsync(user, (const char *)D.out.p + o, bytes, hipMemcpyDeviceToHost, c->stream);
+    };
+    LPF_HIP(c, back(out->uv, S.uv, n * 8));
+    LPF_HIP(c, back(out->depth, S.dep, n * 8));
+    LPF_HIP(c, back(out->u_f, S.uf, n * 8));
+    LPF_HIP(c, back(out->v_f, S.vf, n * 8));
+    LPF_HIP(c, back(out->valid_idx, S.vi, n * 8));
+    LPF_HIP(c, back(out->uv_valid, S.uvv, n * 8));
+    LPF_HIP(c, back(out->label_words, S.lw, n * LW * 4));
+    LPF_HIP(c, back(out->label_valid_words, S.lvw, n * LW * 4));
+    LPF_HIP(c, back(out->inst_idx, S.ii, ncap * 8));
+    LPF_HIP(c, back(out->count_mb, S.cmb, nMB * 4));
+    LPF_HIP(c, back(out->n_valid, S.nv, nF * 8));
+    LPF_HIP(c, back(out->n_labelled, S.nl, nF * 8));
+    LPF_HIP(c, back(out->inst_count, S.ic, nFM * 8));
+    LPF_HIP(c, back(out->inst_off, S.io, (nFM + nF) * 8));
+    LPF_HIP(c, back(out->best_cnt, S.bc, nFM * 8));
+    LPF_HIP(c, back(out->best_box, S.bb, nFM * 4));
+    LPF_HIP(c, back(out->inst_overflow, S.of, nF * 4));
+    return LPF_OK;
+}
+
 int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
                  const lpf_wide_outputs *out)
 {
@@ -1955,7 +2099,7 @@ int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
     const int LW = (M + 31) / 32;
     const int Btot = BX.F ? BX.box_off[F] : 0;
     const bool host_io = !out->on_device;
-    const size_t n = (size_t)Ntot, hw = (size_t)c->W * c->H;
+    const size_t n = (size_t)Ntot;
     lpf_ctx::Wide &D = c->wide;
 
     // frame table
@@ -1993,84 +2137,13 @@ int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         LPF_HIP(c, hipMemcpyAsync(D.pts.p, pts, n * 16, hipMemcpyHostToDevice, c->stream));
         W.pts = (const float4 *)D.pts.p;
     }
-    const size_t esz = in->f32 ? 4 : 1;
-    const void *d_masks = in->masks;
-    const int32_t *d_rects = in->rects;
-    if (M > 0 && !in->on_device) {
-        const size_t bytes = (size_t)F * M * hw * esz;
-        if ((rc = reserve(c, D.masks, bytes))) return rc;
-        LPF_HIP(c, hipMemcpyAsync(D.masks.p, in->masks, bytes, hipMemcpyHostToDevice, c->stream));
-        d_masks = D.masks.p;
-        if (in->rects) {
-            if ((rc = reserve(c, D.rects, (size_t)F * M * 16))) return rc;
-            LPF_HIP(c, hipMemcpyAsync(D.rects.p, in->rects, (size_t)F * M * 16, hipMemcpyHostToDevice, c->stream));
-            d_rects = (const int32_t *)D.rects.p;
-        }
-    }
-    // (the rectangles hold where lpf_set_mask_rects takes them: uint8, or float under binarize 0, without erosion)
-    const int4 *rects = (in->rects && in->erode_iters == 0 && (!in->f32 || in->binarize == 0)) ? (const int4 *)d_rects : nullptr;
-
-    // ---- pack (+ erosion) into LW planes --------------------------------------------------------------------------------------
-    if (M > 0) {
-        if ((rc = reserve(c, D.planes_a, (size_t)F * LW * hw * 4))) return rc;
-        uint32_t *cur = (uint32_t *)D.planes_a.p;
-        const dim3 grid((c->W + LPF_TW - 1) / LPF_TW, (c->H + LPF_TH - 1) / LPF_TH, (unsigned)(F * LW));
-        const int fuse = in->erode_iters > 0 ? 1 : 0;
-        if (!in->f32)
-            hipLaunchKernelGGL((lpf_wide_pack<uint8_t, 0>), grid, dim3(LPF_BLOCK), 0, c->stream, (const uint8_t *)d_masks, cur, M, LW, c->H, c->W, fuse, rects);
-        else if (in->binarize == 0)
-            hipLaunchKernelGGL((lpf_wide_pack<float, 1>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, c->H, c->W, fuse, rects);
-        else if (in->binarize == 1)
-            hipLaunchKernelGGL((lpf_wide_pack<float, 2>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, c->H, c->W, fuse, rects);
-        else
-            hipLaunchKernelGGL((lpf_wide_pack<float, 3>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, c->H, c->W, fuse, rects);
-        LPF_HIP(c, hipGetLastError());
-        if (in->erode_iters > 1) {                        // further iterations: the narrow path's own kernel, a plane per (frame, word)
-            if ((rc = reserve(c, D.planes_b, (size_t)F * LW * hw * 4))) return rc;
-            uint32_t *other = (uint32_t *)D.planes_b.p;
-            for (int it = 1; it < in->erode_iters; ++it) {
-                hipLaunchKernelGGL((lpf_erode_packed<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, c->H, c->W);
-                LPF_HIP(c, hipGetLastError());
-                std::swap(cur, other);
-            }
-        }
-        W.planes = cur;
-    }
+    bool masks_in = false;
+    if ((rc = wide_pack(c, D, in, F, c->W, c->H, W, &masks_in))) return rc;
 
     // ---- buffers: the caller's device pointers, or staging for host callers ---------------------------------------------------
-    const size_t nF = (size_t)F, nFM = (size_t)F * M, nMB = (size_t)M * Btot, ncap = out->inst_cap > 0 ? (size_t)F * out->inst_cap : 0;
-    size_t off = 0;
-    auto carve = [&](const void *want, size_t bytes) -> size_t { if (!want || !host_io) return (size_t)-1; const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_uv = carve(out->uv, n * 8), o_dep = carve(out->depth, n * 8), o_uf = carve(out->u_f, n * 8), o_vf = carve(out->v_f, n * 8),
-                 o_vi = carve(out->valid_idx, n * 8), o_uvv = carve(out->uv_valid, n * 8), o_lw = carve(out->label_words, n * LW * 4),
-                 o_lvw = carve(out->label_valid_words, n * LW * 4), o_ii = carve(out->inst_idx, ncap * 8), o_cmb = carve(out->count_mb, nMB * 4),
-                 o_nv = carve(out->n_valid, nF * 8), o_nl = carve(out->n_labelled, nF * 8), o_ic = carve(out->inst_count, nFM * 8),
-                 o_io = carve(out->inst_off, (nFM + nF) * 8), o_bc = carve(out->best_cnt, nFM * 8), o_bb = carve(out->best_box, nFM * 4),
-                 o_of = carve(out->inst_overflow, nF * 4);
-    if (host_io && off && (rc = reserve(c, D.out, off))) return rc;
-    auto dst = [&](void *user, size_t o) -> void * { return !user ? nullptr : host_io ? (void *)((char *)D.out.p + o) : user; };
-    W.uv = (int2 *)dst(out->uv, o_uv);
-    if (!W.uv) { if ((rc = reserve(c, D.uv, n * 8))) return rc; W.uv = (int2 *)D.uv.p; }
-    W.depth = (double *)dst(out->depth, o_dep); W.uf = (double *)dst(out->u_f, o_uf); W.vf = (double *)dst(out->v_f, o_vf);
-    W.valid_idx = (long long *)dst(out->valid_idx, o_vi); W.uv_valid = (int2 *)dst(out->uv_valid, o_uvv);
-    W.label_words = (uint32_t *)dst(out->label_words, o_lw);
-    if (!W.label_words) { if ((rc = reserve(c, D.words, n * LW * 4))) return rc; W.label_words = (uint32_t *)D.words.p; }
-    W.label_valid = (uint32_t *)dst(out->label_valid_words, o_lvw);
-    W.inst_idx = (long long *)dst(out->inst_idx, o_ii); W.count_out = (int32_t *)dst(out->count_mb, o_cmb);
-    W.n_valid = (long long *)dst(out->n_valid, o_nv); W.n_labelled = (long long *)dst(out->n_labelled, o_nl);
-    W.inst_count = (long long *)dst(out->inst_count, o_ic); W.inst_off = (long long *)dst(out->inst_off, o_io);
-    W.best_cnt = (long long *)dst(out->best_cnt, o_bc); W.best_box = (int32_t *)dst(out->best_box, o_bb);
-    W.inst_overflow = (int32_t *)dst(out->inst_overflow, o_of);
-    if ((rc = reserve(c, D.flags, (size_t)std::max(nchunk, 1) * LPF_WIDE_CHUNK))) return rc;
-    if ((rc = reserve(c, D.ccnt, (size_t)std::max(nchunk, 1) * 8))) return rc;
-    if ((rc = reserve(c, D.cpre, (size_t)std::max(nchunk, 1) * 8))) return rc;
-    if ((rc = reserve(c, D.fcnt, nF * 8))) return rc;
-    if ((rc = reserve(c, D.midx, n * 4))) return rc;
-    if ((rc = reserve(c, D.mwords, n * LW * 4))) return rc;
-    if ((rc = reserve(c, D.mpts, n * 16))) return rc;
-    if ((rc = reserve(c, D.cnt, nMB * 4))) return rc;
-    W.flags = (uint32_t *)D.flags.p; W.chunk_cnt = (int2 *)D.ccnt.p; W.chunk_pre = (int2 *)D.cpre.p; W.fcnt = (int2 *)D.fcnt.p;
-    W.m_idx = (int *)D.midx.p; W.m_words = (uint32_t *)D.mwords.p; W.m_pts = (float4 *)D.mpts.p; W.cnt = (unsigned *)D.cnt.p;
+    const size_t nMB = (size_t)M * Btot;
+    WideStage S;
+    if ((rc = wide_bind(c, D, out, n, F, Btot, W, S))) return rc;
 
     // ---- the launch set ------------------------------------------------------------------------------------------------------
     if (nchunk > 0) {
@@ -2095,34 +2168,81 @@ int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         LPF_HIP(c, hipGetLastError());
     }
 
-    if (host_io) {
-        auto back = [&](void *user, size_t o, size_t bytes) -> hipError_t {
-            if (!user || !bytes) return hipSuccess;
-            return hipMemcpyAsync(user, (const char *)D.out.p + o, bytes, hipMemcpyDeviceToHost, c->stream);
-        };
-        LPF_HIP(c, back(out->uv, o_uv, n * 8));
-        LPF_HIP(c, back(out->depth, o_dep, n * 8));
-        LPF_HIP(c, back(out->u_f, o_uf, n * 8));
-        LPF_HIP(c, back(out->v_f, o_vf, n * 8));
-        LPF_HIP(c, back(out->valid_idx, o_vi, n * 8));
-        LPF_HIP(c, back(out->uv_valid, o_uvv, n * 8));
-        LPF_HIP(c, back(out->label_words, o_lw, n * LW * 4));
-        LPF_HIP(c, back(out->label_valid_words, o_lvw, n * LW * 4));
-        LPF_HIP(c, back(out->inst_idx, o_ii, ncap * 8));
-        LPF_HIP(c, back(out->count_mb, o_cmb, nMB * 4));
-        LPF_HIP(c, back(out->n_valid, o_nv, nF * 8));
-        LPF_HIP(c, back(out->n_labelled, o_nl, nF * 8));
-        LPF_HIP(c, back(out->inst_count, o_ic, nFM * 8));
-        LPF_HIP(c, back(out->inst_off, o_io, (nFM + nF) * 8));
-        LPF_HIP(c, back(out->best_cnt, o_bc, nFM * 8));
-        LPF_HIP(c, back(out->best_box, o_bb, nFM * 4));
-        LPF_HIP(c, back(out->inst_overflow, o_of, nF * 4));
-    }
-    if (host_io || (M > 0 && !in->on_device) || (n > 0 && !pts_on_device)) LPF_HIP(c, host_wait(c));   // host buffers may be reused
+    if (host_io && (rc = wide_back(c, D, out, S, n, F, M, Btot))) return rc;
+    if (host_io || masks_in || (n > 0 && !pts_on_device)) LPF_HIP(c, host_wait(c));   // host buffers may be reused
     return LPF_OK;
 }
 
 // ---- lpf_run_cams (include/lpf.h): one scan in up to LPF_MAX_CAMS cameras, kernels in lpf_cams.hip.h ------------------------------
+// The checks lpf_run_cams and lpf_run_cams_wide share (who: the call's name; frames of up to 0x7fffffff - slack points; 0 .. max_M masks
+// per camera, max_name: the limit's name in the header, m_more: what the message adds for a camera with more).  Refuses graph capture.
+static int cams_check(lpf_ctx *c, const char *who, const float *pts, const int64_t *frame_off, int F, const lpf_cam_input *cams, int C,
+                      const void *out, int64_t slack, int max_M, const char *max_name, const char *m_more)
+{
+    const char *w = who + 4;                               // "run_cams..." in the messages
+    if (c->capturing) return fail(c, LPF_ERR_STATE, "%s cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)", who);
+    if (C < 1 || C > LPF_MAX_CAMS) return fail(c, LPF_ERR_ARG, "%s: C=%d cameras, a pass takes 1 .. LPF_MAX_CAMS = %d", w, C, LPF_MAX_CAMS);
+    if (!cams || !out || !frame_off || F <= 0)
+        return fail(c, LPF_ERR_ARG, "%s: cams=%p out=%p frame_off=%p F=%d", w, (const void *)cams, out, (const void *)frame_off, F);
+    if (frame_off[0] != 0) return fail(c, LPF_ERR_ARG, "%s: frame_off[0] must be 0", w);
+    for (int f = 0; f < F; ++f) {
+        const int64_t n = frame_off[f + 1] - frame_off[f];
+        if (n < 0 || n > 0x7fffffffll - slack) return fail(c, LPF_ERR_ARG, "%s: frame %d has %lld points", w, f, (long long)n);
+    }
+    if (frame_off[F] > 0 && !pts) return fail(c, LPF_ERR_ARG, "%s: pts is NULL", w);
+    for (int k = 0; k < C; ++k) {
+        const lpf_cam_input &I = cams[k];
+        const lpf_wide_input &m = I.masks;
+        if (I.W <= 0 || I.H <= 0 || (long long)I.W * I.H > (1ll << 30))
+            return fail(c, LPF_ERR_ARG, "%s: camera %d is %d x %d", w, k, I.W, I.H);
+        if (m.M < 0 || m.M > max_M)
+            return fail(c, LPF_ERR_ARG, "%s: camera %d has M=%d masks per frame, a pass takes 0 .. %s = %d per camera%s", w, k, m.M, max_name,
+                        max_M, m_more);
+        if (m.erode_iters < 0 || (m.f32 && (m.binarize < 0 || m.binarize > 2)) || (m.M > 0 && !m.masks))
+            return fail(c, LPF_ERR_ARG, "%s: camera %d: erode_iters=%d f32=%d binarize=%d masks=%p", w, k, m.erode_iters, m.f32, m.binarize, m.masks);
+        if (I.corners_velo) {
+            if (!I.box_off || I.box_off[0] != 0) return fail(c, LPF_ERR_ARG, "%s: camera %d: box_off must be given and start at 0", w, k);
+            for (int f = 0; f < F; ++f)
+                if (I.box_off[f + 1] < I.box_off[f]) return fail(c, LPF_ERR_ARG, "%s: camera %d: box_off not ascending at %d", w, k, f);
+            if (I.boxes_on_device < 0 || I.boxes_on_device > 2) return fail(c, LPF_ERR_ARG, "%s: camera %d: boxes_on_device=%d", w, k, I.boxes_on_device);
+        }
+    }
+    return LPF_OK;
+}
+
+// camera k's box tables of a multi-camera pass: lpf_run_cams' box set k, shaped for F frames and filled by a box job launched here
+// in camera k's K, W, H (lpf_set_boxes_ex's tables for that camera); no corners: no boxes
+static int cams_box_tables(lpf_ctx *c, const lpf_cam_input &I, int k, int F)
+{
+    int rc;
+    lpf_ctx::BoxSet &B = c->cams.bx[k];
+    B.F = 0; B.box_off.clear(); B.job_valid = false;
+    if (!I.corners_velo) return LPF_OK;
+    if ((rc = box_shape(c, B, I.box_off, F, I.oriented))) return rc;
+    const size_t nb = (size_t)I.box_off[F];
+    if (nb == 0) return LPF_OK;
+    const double *src = I.corners_velo;
+    if (I.boxes_on_device != 2) {                // not lent: the pass's own copy, in stream order
+        if ((rc = reserve(c, B.stage, nb * 192))) return rc;
+        if (I.boxes_on_device) LPF_HIP(c, hipMemcpyAsync(B.stage.p, src, nb * 192, hipMemcpyDeviceToDevice, c->stream));
+        else if ((rc = upload(c, B.stage.p, src, nb * 192))) return rc;
+        src = (const double *)B.stage.p;
+    }
+    B.have_enabled = false;
+    LpfBoxJob &J = B.job;
+    memset(&J, 0, sizeof J);
+    J.src = src; J.oriented = B.oriented; J.F = F; J.chunks = B.max_words;
+    J.bframes = (const LpfBoxFrame *)B.bframes.p; J.frame0 = B.h_bframes[0];
+    J.boxp = (double *)B.boxp.p; J.boxq = (float *)B.boxq.p; J.cand = (unsigned long long *)B.cand.p;
+    J.corners_keep = (double *)B.corners.p;
+    memcpy(J.K, I.K, sizeof J.K);
+    J.W = I.W; J.H = I.H;
+    ++c->stats[4];
+    hipLaunchKernelGGL(lpf_box_job_kernel, dim3((unsigned)box_job_blocks(B)), dim3(LPF_BLOCK), 0, c->stream, J);
+    LPF_HIP(c, hipGetLastError());
+    return LPF_OK;
+}
+
 // Camera c runs as the narrow in-order run would -- the same segments, counters, tables and tail -- in scratch set c, with its own box
 // tables (c->cams.bx[c]) and label images (c->cams.label_a[c]); the three launches after the packs and box jobs serve every camera.
 static_assert(LPF_MAX_CAMS == LPF_MAX_CAMS_DEV && LPF_MAX_CAMS <= LPF_NSETS, "a scratch set per camera");
@@ -2132,38 +2252,16 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
 {
     if (!c) return LPF_ERR_ARG;
     if (use_device(c)) return LPF_ERR_HIP;
-    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_run_cams cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
-    if (C < 1 || C > LPF_MAX_CAMS) return fail(c, LPF_ERR_ARG, "run_cams: C=%d cameras, a pass takes 1 .. LPF_MAX_CAMS = %d", C, LPF_MAX_CAMS);
-    if (!cams || !out || !frame_off || F <= 0)
-        return fail(c, LPF_ERR_ARG, "run_cams: cams=%p out=%p frame_off=%p F=%d", (const void *)cams, (const void *)out, (const void *)frame_off, F);
-    if (frame_off[0] != 0) return fail(c, LPF_ERR_ARG, "run_cams: frame_off[0] must be 0");
-    for (int f = 0; f < F; ++f) {
-        const int64_t n = frame_off[f + 1] - frame_off[f];
-        if (n < 0 || n > 0x7fffffffll - LPF_SEG_QUANTUM) return fail(c, LPF_ERR_ARG, "run_cams: frame %d has %lld points", f, (long long)n);
-    }
+    int rc;
+    if ((rc = cams_check(c, "lpf_run_cams", pts, frame_off, F, cams, C, out, LPF_SEG_QUANTUM, LPF_MAX_MASKS, "LPF_MAX_MASKS",
+                         " (more: lpf_run_wide for that camera)")))
+        return rc;
     const int64_t Ntot = frame_off[F];
-    if (Ntot > 0 && !pts) return fail(c, LPF_ERR_ARG, "run_cams: pts is NULL");
     for (int k = 0; k < C; ++k) {
-        const lpf_cam_input &I = cams[k];
-        const lpf_wide_input &m = I.masks;
-        if (I.W <= 0 || I.H <= 0 || (long long)I.W * I.H > (1ll << 30))
-            return fail(c, LPF_ERR_ARG, "run_cams: camera %d is %d x %d", k, I.W, I.H);
-        if (m.M < 0 || m.M > LPF_MAX_MASKS)
-            return fail(c, LPF_ERR_ARG, "run_cams: camera %d has M=%d masks per frame, a pass takes 0 .. LPF_MAX_MASKS = %d per camera (more: "
-                                        "lpf_run_wide for that camera)", k, m.M, LPF_MAX_MASKS);
-        if (m.erode_iters < 0 || (m.f32 && (m.binarize < 0 || m.binarize > 2)) || (m.M > 0 && !m.masks))
-            return fail(c, LPF_ERR_ARG, "run_cams: camera %d: erode_iters=%d f32=%d binarize=%d masks=%p", k, m.erode_iters, m.f32, m.binarize, m.masks);
-        if (I.corners_velo) {
-            if (!I.box_off || I.box_off[0] != 0) return fail(c, LPF_ERR_ARG, "run_cams: camera %d: box_off must be given and start at 0", k);
-            for (int f = 0; f < F; ++f)
-                if (I.box_off[f + 1] < I.box_off[f]) return fail(c, LPF_ERR_ARG, "run_cams: camera %d: box_off not ascending at %d", k, f);
-            if (I.boxes_on_device < 0 || I.boxes_on_device > 2) return fail(c, LPF_ERR_ARG, "run_cams: camera %d: boxes_on_device=%d", k, I.boxes_on_device);
-        }
         if (out[k].inst_idx && out[k].inst_cap <= 0) return fail(c, LPF_ERR_ARG, "run_cams: out[%d].inst_idx given with inst_cap=%lld", k, (long long)out[k].inst_cap);
         if ((out[k].uv_valid || out[k].label_valid) && !out[k].valid_idx)
             return fail(c, LPF_ERR_ARG, "run_cams: out[%d]: uv_valid / label_valid need valid_idx as well (they share its order)", k);
     }
-    int rc;
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
     const size_t n = (size_t)Ntot;
@@ -2184,33 +2282,7 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
     const void *label_img[LPF_MAX_CAMS] = {nullptr, nullptr, nullptr, nullptr};
     for (int k = 0; k < C; ++k) {
         const lpf_cam_input &I = cams[k];
-        lpf_ctx::BoxSet &B = c->cams.bx[k];
-        B.F = 0; B.box_off.clear(); B.job_valid = false;
-        if (I.corners_velo) {
-            if ((rc = box_shape(c, B, I.box_off, F, I.oriented))) return rc;
-            const size_t nb = (size_t)I.box_off[F];
-            if (nb > 0) {
-                const double *src = I.corners_velo;
-                if (I.boxes_on_device != 2) {                // not lent: the pass's own copy, in stream order
-                    if ((rc = reserve(c, B.stage, nb * 192))) return rc;
-                    if (I.boxes_on_device) LPF_HIP(c, hipMemcpyAsync(B.stage.p, src, nb * 192, hipMemcpyDeviceToDevice, c->stream));
-                    else if ((rc = upload(c, B.stage.p, src, nb * 192))) return rc;
-                    src = (const double *)B.stage.p;
-                }
-                B.have_enabled = false;
-                LpfBoxJob &J = B.job;
-                memset(&J, 0, sizeof J);
-                J.src = src; J.oriented = B.oriented; J.F = F; J.chunks = B.max_words;
-                J.bframes = (const LpfBoxFrame *)B.bframes.p; J.frame0 = B.h_bframes[0];
-                J.boxp = (double *)B.boxp.p; J.boxq = (float *)B.boxq.p; J.cand = (unsigned long long *)B.cand.p;
-                J.corners_keep = (double *)B.corners.p;
-                memcpy(J.K, I.K, sizeof J.K);
-                J.W = I.W; J.H = I.H;
-                ++c->stats[4];
-                hipLaunchKernelGGL(lpf_box_job_kernel, dim3((unsigned)box_job_blocks(B)), dim3(LPF_BLOCK), 0, c->stream, J);
-                LPF_HIP(c, hipGetLastError());
-            }
-        }
+        if ((rc = cams_box_tables(c, I, k, F))) return rc;
         const lpf_wide_input &m = I.masks;
         if (m.M == 0) continue;
         const size_t hw = (size_t)I.W * I.H, esz = m.f32 ? 4 : 1;
@@ -2477,6 +2549,123 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         }
     }
     if (any_host || host_in) LPF_HIP(c, host_wait(c));         // host buffers are filled, or may be reused
+    return LPF_OK;
+}
+
+// ---- lpf_run_cams_wide (include/lpf.h): one scan in up to LPF_MAX_CAMS cameras of up to LPF_MAX_MASKS_WIDE masks each, kernels in
+// lpf_cams_wide.hip.h.  Camera c runs lpf_run_wide's chain on buffers of its own (c->camsw.cam[c]) with lpf_run_cams' box tables
+// (c->cams.bx[c]); one projecting launch reads the points once for every camera, and each later stage is one launch for all of them.
+int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_cam_input *cams, int C,
+                      const lpf_wide_outputs *out)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (use_device(c)) return LPF_ERR_HIP;
+    int rc;
+    if ((rc = cams_check(c, "lpf_run_cams_wide", pts, frame_off, F, cams, C, out, LPF_WIDE_CHUNK, LPF_MAX_MASKS_WIDE, "LPF_MAX_MASKS_WIDE", "")))
+        return rc;
+    for (int k = 0; k < C; ++k)
+        if (out[k].inst_idx && out[k].inst_cap <= 0)
+            return fail(c, LPF_ERR_ARG, "run_cams_wide: out[%d].inst_idx given with inst_cap=%lld", k, (long long)out[k].inst_cap);
+    // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+    const size_t n = (size_t)frame_off[F];
+    bool host_in = false;
+
+    // ---- points: read once by the projecting launch ---------------------------------------------------------------------------------
+    const float4 *d_pts = (const float4 *)pts;
+    if (!pts_on_device && n) {
+        if ((rc = reserve(c, c->camsw.pts, n * 16))) return rc;
+        LPF_HIP(c, hipMemcpyAsync(c->camsw.pts.p, pts, n * 16, hipMemcpyHostToDevice, c->stream));
+        d_pts = (const float4 *)c->camsw.pts.p;
+        host_in = true;
+    }
+
+    // ---- frame tables, one per camera (the chunk fields depend on the points only, the box fields on the camera's boxes) -----------
+    std::vector<LpfWideFrame> fr((size_t)C * F);
+    int nchunk = 0, Btot[LPF_MAX_CAMS] = {0, 0, 0, 0}, nbw[LPF_MAX_CAMS] = {0, 0, 0, 0};
+    for (int k = 0; k < C; ++k) {
+        if ((rc = cams_box_tables(c, cams[k], k, F))) return rc;
+        const lpf_ctx::BoxSet &BX = c->cams.bx[k];
+        Btot[k] = BX.F ? BX.box_off[F] : 0;
+        int ch = 0, maxB = 0;
+        for (int f = 0; f < F; ++f) {
+            LpfWideFrame &e = fr[(size_t)k * F + f];
+            e.pt_off = frame_off[f];
+            e.N = (int)(frame_off[f + 1] - frame_off[f]);
+            e.chunk_off = ch;
+            e.nchunk = (e.N + LPF_WIDE_CHUNK - 1) / LPF_WIDE_CHUNK;
+            e.box_off = BX.F ? BX.box_off[f] : 0;
+            e.B = BX.F ? BX.box_off[f + 1] - BX.box_off[f] : 0;
+            e.pad = 0;
+            ch += e.nchunk;
+            maxB = std::max(maxB, e.B);
+        }
+        nchunk = ch;
+        nbw[k] = (maxB + 63) / 64;
+    }
+    if ((rc = reserve(c, c->camsw.tab, fr.size() * sizeof(LpfWideFrame)))) return rc;
+    if ((rc = upload(c, c->camsw.tab.p, fr.data(), fr.size() * sizeof(LpfWideFrame)))) return rc;
+
+    // ---- per camera: its lpf_run_wide parameters, masks -> planes, outputs and scratch ---------------------------------------------
+    LpfCamsWideArgs A;
+    memset(&A, 0, sizeof A);
+    A.C = C;
+    WideStage S[LPF_MAX_CAMS];
+    int max_lists = 0, max_boxes = 0;
+    bool any_boxes = false, any_host = false;
+    for (int k = 0; k < C; ++k) {
+        const lpf_cam_input &I = cams[k];
+        const lpf_ctx::BoxSet &BX = c->cams.bx[k];
+        lpf_ctx::Wide &D = c->camsw.cam[k];
+        LpfWideParams &W = A.P[k];
+        const int M = I.masks.M, LW = (M + 31) / 32;
+        memcpy(W.cam.T, I.T_velo_to_rect, sizeof W.cam.T);  // rows 0..2 (as lpf_set_camera)
+        memcpy(W.cam.K, I.K, sizeof W.cam.K);
+        W.cam.dmin = I.depth_min_excl; W.cam.dmax = I.depth_max_excl; W.cam.W = I.W; W.cam.H = I.H;
+        W.F = F; W.M = M; W.LW = LW; W.nchunk = nchunk; W.nbw = nbw[k];
+        W.oriented = BX.F ? BX.oriented : 1; W.inst_cap = out[k].inst_cap;
+        W.frames = (const LpfWideFrame *)c->camsw.tab.p + (size_t)k * F;
+        W.boxp = (const double *)BX.boxp.p; W.boxq = (const float *)BX.boxq.p;
+        W.pts = d_pts;
+        if ((rc = wide_pack(c, D, &I.masks, F, I.W, I.H, W, &host_in))) return rc;
+        if ((rc = wide_bind(c, D, &out[k], n, F, Btot[k], W, S[k]))) return rc;
+        max_lists = std::max(max_lists, F * std::max(LW, 1));
+        if (M > 0 && Btot[k] > 0) {
+            any_boxes = true;
+            max_boxes = std::max(max_boxes, F * LW * nbw[k]);
+        }
+        any_host |= !out[k].on_device;
+    }
+
+    // ---- the launch set: each stage once for every camera --------------------------------------------------------------------------
+    if (nchunk > 0) {
+        hipLaunchKernelGGL(lpf_cams_wide_project, dim3((unsigned)nchunk), dim3(LPF_BLOCK), 0, c->stream, A);
+        LPF_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(lpf_cams_wide_scan, dim3((unsigned)F, (unsigned)C), dim3(LPF_BLOCK), 0, c->stream, A);
+    LPF_HIP(c, hipGetLastError());
+    if (nchunk > 0) {
+        hipLaunchKernelGGL(lpf_cams_wide_scatter, dim3((unsigned)nchunk, (unsigned)C), dim3(LPF_BLOCK), 0, c->stream, A);
+        LPF_HIP(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(lpf_cams_wide_lists, dim3((unsigned)max_lists, (unsigned)C), dim3(LPF_BLOCK), 0, c->stream, A);
+    LPF_HIP(c, hipGetLastError());
+    if (any_boxes) {
+        for (int k = 0; k < C; ++k)
+            if (A.P[k].M > 0 && Btot[k] > 0) LPF_HIP(c, hipMemsetAsync(A.P[k].cnt, 0, (size_t)A.P[k].M * Btot[k] * 4, c->stream));
+        hipLaunchKernelGGL(lpf_cams_wide_boxes, dim3((unsigned)max_boxes, LPF_WIDE_PARTS, (unsigned)C), dim3(LPF_BLOCK), 0, c->stream, A);
+        LPF_HIP(c, hipGetLastError());
+    }
+    bool any_masks = false;
+    for (int k = 0; k < C; ++k) any_masks |= A.P[k].M > 0;
+    if (any_masks) {
+        hipLaunchKernelGGL(lpf_cams_wide_best, dim3((unsigned)F, (unsigned)C), dim3(LPF_BLOCK), 0, c->stream, A);
+        LPF_HIP(c, hipGetLastError());
+    }
+
+    for (int k = 0; k < C; ++k)
+        if (!out[k].on_device && (rc = wide_back(c, c->camsw.cam[k], &out[k], S[k], n, F, A.P[k].M, Btot[k]))) return rc;
+    if (any_host || host_in) LPF_HIP(c, host_wait(c));       // host buffers are filled, or may be reused
     return LPF_OK;
 }
 

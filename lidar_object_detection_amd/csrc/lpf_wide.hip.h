@@ -144,12 +144,12 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_pack(const T *__restrict__
 }
 
 // ---- project + label: 1024 points per block, 4 consecutive points per thread ----------------------------------------------------
-__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_project(const LpfWideParams W)
+// Chunk c of frame f (chunk_off and the points depend on the points only: every camera of lpf_cams_wide_project finds the same ones).
+// PRE: the thread's four points are in p[] already (lpf_cams_wide_project loads them once for every camera); else each is read here.
+template <bool PRE>
+__device__ __forceinline__ void lpf_wide_project_chunk(const LpfWideParams &W, const int c, const int f, const LpfWideFrame &fr,
+                                                       const float4 *p_pre, unsigned *s_tmp)
 {
-    __shared__ unsigned s_tmp[8];
-    const int c = blockIdx.x;
-    const int f = lpf_wide_frame_of_chunk(W, c);
-    const LpfWideFrame fr = W.frames[f];
     const int base = (c - fr.chunk_off) * LPF_WIDE_CHUNK;
     const size_t hw = (size_t)W.cam.W * (size_t)W.cam.H;
     const uint32_t *__restrict__ pl = W.planes ? W.planes + (size_t)f * W.LW * hw : nullptr;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_project(const LpfWideParam
         const int i = base + threadIdx.x * 4 + r;          // frame-relative point
         if (i >= fr.N) break;
         const size_t g = (size_t)fr.pt_off + i;
-        const float4 p = W.pts[g];
+        const float4 p = PRE ? p_pre[r] : W.pts[g];
         double uf, vf, d;
         lpf_project_point(W.cam, p.x, p.y, p.z, uf, vf, d);
         const double ru = rint(uf), rv = rint(vf);        // np.round: half to even
@@ -188,11 +188,18 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_project(const LpfWideParam
     if (threadIdx.x == 0) W.chunk_cnt[c] = make_int2((int)tv, (int)tm);
 }
 
-// ---- per frame: chunk prefixes and the frame's totals -------------------------------------------------------------------------
-__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_scan(const LpfWideParams W)
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_project(const LpfWideParams W)
 {
     __shared__ unsigned s_tmp[8];
-    const int f = blockIdx.x;
+    const int c = blockIdx.x;
+    const int f = lpf_wide_frame_of_chunk(W, c);
+    const LpfWideFrame fr = W.frames[f];
+    lpf_wide_project_chunk<false>(W, c, f, fr, nullptr, s_tmp);
+}
+
+// ---- per frame: chunk prefixes and the frame's totals -------------------------------------------------------------------------
+__device__ __forceinline__ void lpf_wide_scan_frame(const LpfWideParams &W, const int f, unsigned *s_tmp)
+{
     const LpfWideFrame fr = W.frames[f];
     unsigned cv = 0, cm = 0;
     for (int k0 = 0; k0 < fr.nchunk; k0 += LPF_BLOCK) {
@@ -211,11 +218,15 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_scan(const LpfWideParams W
     }
 }
 
-// ---- compact outputs and the masked list ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_scatter(const LpfWideParams W)
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_scan(const LpfWideParams W)
 {
     __shared__ unsigned s_tmp[8];
-    const int c = blockIdx.x;
+    lpf_wide_scan_frame(W, blockIdx.x, s_tmp);
+}
+
+// ---- compact outputs and the masked list ---------------------------------------------------------------------------------------
+__device__ __forceinline__ void lpf_wide_scatter_chunk(const LpfWideParams &W, const int c, unsigned *s_tmp)
+{
     const int f = lpf_wide_frame_of_chunk(W, c);
     const LpfWideFrame fr = W.frames[f];
     const int base = (c - fr.chunk_off) * LPF_WIDE_CHUNK;
@@ -249,13 +260,20 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_scatter(const LpfWideParam
     }
 }
 
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_scatter(const LpfWideParams W)
+{
+    __shared__ unsigned s_tmp[8];
+    lpf_wide_scatter_chunk(W, blockIdx.x, s_tmp);
+}
+
 // ---- instance counts, offsets and lists: block (frame, word) ---------------------------------------------------------------------
 // Offsets need the counts of every earlier mask of the frame: the block sums the popcounts of the earlier words of each masked entry
 // itself (a few thousand entries), so no block waits for another.
-__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_lists(const LpfWideParams W)
+// (blk: frame * max(LW, 1) + word; LDS: s_cnt[32], s_run[32], s_wc[4][32], s_before)
+__device__ __forceinline__ void lpf_wide_lists_block(const LpfWideParams &W, const int blk, unsigned *s_cnt, unsigned *s_run,
+                                                     unsigned (*s_wc)[32], unsigned &s_before)
 {
-    __shared__ unsigned s_cnt[32], s_run[32], s_wc[4][32], s_before;
-    const int f = blockIdx.x / max(W.LW, 1), wd = blockIdx.x - f * max(W.LW, 1);
+    const int f = blk / max(W.LW, 1), wd = blk - f * max(W.LW, 1);
     const int lane = lpf_lane(), wave = lpf_wave(), tid = threadIdx.x;
     const LpfWideFrame fr = W.frames[f];
     const int n = W.fcnt[f].y;
@@ -333,16 +351,21 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_lists(const LpfWideParams 
     }
 }
 
-// ---- box counts: block (frame, word, 64-box word, part); a lane per masked entry, the boxes from LDS ----------------------------
-__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_boxes(const LpfWideParams W)
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_lists(const LpfWideParams W)
 {
-    __shared__ double s_bp[64 * 16];
-    __shared__ float s_bq[64 * 6];
-    __shared__ unsigned s_c[32 * 64];
+    __shared__ unsigned s_cnt[32], s_run[32], s_wc[4][32], s_before;
+    lpf_wide_lists_block(W, blockIdx.x, s_cnt, s_run, s_wc, s_before);
+}
+
+// ---- box counts: block (frame, word, 64-box word, part); a lane per masked entry, the boxes from LDS ----------------------------
+// (blk: (frame * LW + word) * nbw + 64-box word; LDS: s_bp[64 * 16], s_bq[64 * 6], s_c[32 * 64])
+__device__ __forceinline__ void lpf_wide_boxes_block(const LpfWideParams &W, const int blk, const int part, double *s_bp, float *s_bq,
+                                                     unsigned *s_c)
+{
     const int per_f = W.LW * W.nbw;
-    const int f = blockIdx.x / per_f, rem = blockIdx.x - f * per_f;
+    const int f = blk / per_f, rem = blk - f * per_f;
     const int wd = rem / W.nbw, bw = rem - wd * W.nbw;
-    const int part = blockIdx.y, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const LpfWideFrame fr = W.frames[f];
     const int b0 = 64 * bw, nb = min(64, fr.B - b0);
     if (nb <= 0) return;
@@ -384,10 +407,18 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_boxes(const LpfWideParams 
     }
 }
 
-// ---- per frame: count_mb and the first strict maximum per mask (lpf_finalize_frame's rule) --------------------------------------
-__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_best(const LpfWideParams W)
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_boxes(const LpfWideParams W)
 {
-    const int f = blockIdx.x, lane = lpf_lane(), wave = lpf_wave();
+    __shared__ double s_bp[64 * 16];
+    __shared__ float s_bq[64 * 6];
+    __shared__ unsigned s_c[32 * 64];
+    lpf_wide_boxes_block(W, blockIdx.x, blockIdx.y, s_bp, s_bq, s_c);
+}
+
+// ---- per frame: count_mb and the first strict maximum per mask (lpf_finalize_frame's rule) --------------------------------------
+__device__ __forceinline__ void lpf_wide_best_frame(const LpfWideParams &W, const int f)
+{
+    const int lane = lpf_lane(), wave = lpf_wave();
     const LpfWideFrame fr = W.frames[f];
     const int B = fr.B, M = W.M;
     const unsigned *__restrict__ cnt = W.cnt + (size_t)M * fr.box_off;
@@ -412,3 +443,5 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_best(const LpfWideParams W
         }
     }
 }
+
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_best(const LpfWideParams W) { lpf_wide_best_frame(W, blockIdx.x); }

@@ -1061,7 +1061,8 @@ def run_frames_multicam(frames_per_cam, cams, depth_max=50.0, min_points=10, use
     FrameInputs -- frame i of every camera carries the same points (the same frame id and point count; anything else raises
     ValueError), its own masks, colors and boxes (the boxes camera c sees).  Returns ``results[c][i]`` equal to
     ``run_frames(frames_per_cam[c], *cams[c], ...)[i]``, car_statistics and the lazy keys included.  A camera with a frame of more than
-    32 masks goes through run_frames on its own (the pass takes a 32-bit label word per camera); the results are the same."""
+    32 masks goes through run_frames on its own (the pass takes a 32-bit label word per camera); the results are the same.  (Routing
+    such cameras through one LpfContext.run_cams_wide pass measured slower per frame than this)"""
     C = len(cams)
     if not 1 <= C <= LPF_MAX_CAMS:
         raise ValueError("run_frames_multicam takes 1 to %d cameras, got %d" % (LPF_MAX_CAMS, C))
