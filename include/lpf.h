@@ -49,7 +49,9 @@ extern "C" {
                                       8 (continued): LPF_MAX_MASKS_WIDE, lpf_wide_input, lpf_wide_outputs, lpf_run_wide (added; nothing
                                          else changed)
                                       8 (continued): LPF_MAX_CAMS, lpf_cam_input, lpf_run_cams (added; nothing else changed)
-                                      8 (continued): lpf_run_cams_wide (added; nothing else changed) */
+                                      8 (continued): lpf_run_cams_wide (added; nothing else changed)
+                                      8 (continued): lpf_frame_job_wide, lpf_run_frame_wide (added; lpf_get_stats gained slot [7];
+                                         nothing else changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -323,6 +325,33 @@ typedef struct lpf_wide_outputs {
 int lpf_run_wide(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
                  const lpf_wide_outputs *out);
 
+/* One frame of a stream with 0 .. LPF_MAX_MASKS_WIDE masks in ONE call: lpf_run_frame's job for frames with more than 32 masks (crowded
+ * frames of KITTI-360 have hundreds of annotated boxes; the reference applies every mask of a frame, V3:220).  Exactly the sequence
+ *   lpf_set_boxes_cam0(ctx, corners_cam0, 2, {0, n_boxes}, 1, T_cam_to_velo, filter_visible, oriented, 0, 0, 0, 0)   if corners_cam0
+ *   lpf_run_wide(ctx, pts, {0, n_points}, 1, 1, &{masks, mask_rects, n_masks, f32 0, binarize 0, erode_iters 0, on_device 2}, &out)
+ * with the same results, bit for bit, ownership and error behaviour: a NULL corners_cam0 leaves the boxes in force as they are; the
+ * masks, rectangles and label state of the narrow calls are left as they were.  Every pointer except T_cam_to_velo is device memory and
+ * lent until the frame's work has completed; out.on_device must be 1, and the call only enqueues work.  Not capturable (LPF_ERR_STATE
+ * between lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it first launches what the pipeline owes (no host wait),
+ * then runs in order.  LPF_ERR_ARG: a NULL job, n_masks < 0 or > LPF_MAX_MASKS_WIDE, masks NULL with n_masks > 0, n_boxes < 0,
+ * out.on_device != 1.
+ * A sparse frame (2 * n_points <= W * H: a real scan) with mask_rects (16-byte aligned) and 1 .. 48 masks reads its masks where its
+ * valid points fall, inside their rectangles, instead of packing them into ceil(n_masks / 32) full-image planes first (lpf_get_stats
+ * [7] counts such jobs); any other job runs lpf_run_wide's pack (with more masks the pack was measured faster).
+ * The results are the same either way. */
+typedef struct lpf_frame_job_wide {
+    const float   *pts;            /* [n_points][4] */
+    int64_t        n_points;
+    const uint8_t *masks;          /* [n_masks][H][W] uint8, nonzero = member, lent; NULL only with n_masks == 0 */
+    const int32_t *mask_rects;     /* [n_masks][4] {x0, y0, x1, y1}, lent, 16-byte aligned (lpf_set_mask_rects' contract); or NULL */
+    const double  *corners_cam0;   /* [n_boxes][8][3], lent; or NULL = the boxes in force stay */
+    const double  *T_cam_to_velo;  /* host memory, row-major 4x4 (with corners_cam0) */
+    int32_t        n_masks, n_boxes;   /* 0 <= n_masks <= LPF_MAX_MASKS_WIDE */
+    int32_t        filter_visible, oriented;
+    lpf_wide_outputs out;          /* LW = ceil(n_masks / 32) label words per point; out.on_device must be 1 */
+} lpf_frame_job_wide;
+int lpf_run_frame_wide(lpf_ctx *ctx, const lpf_frame_job_wide *job);
+
 /* ---- one scan in several cameras -----------------------------------------------------------------------------------------------
  * lpf_run_cams: a batch of F frames labelled in C cameras (1 <= C <= LPF_MAX_CAMS) in ONE pass: every point is read from memory once
  * and projected, clipped and labelled in each camera's arithmetic; one streaming launch, one tail launch and one summary launch serve
@@ -448,7 +477,8 @@ int lpf_profile_overhead(lpf_ctx *ctx, double *empty_bracket_ms);
 /* What the context has done so far (for tests and tuning: a software-pipelined stream must show no host wait and no drain):
  * out[0] host waits (the calling thread blocked on the GPU), [1] drains (owed work of the pipelined modes launched outside
  * a run), [2] table / corner uploads through the pinned ring (no wait), [3] step launches, [4] box jobs launched as a kernel
- * of their own, [5] box jobs that rode in a step launch, [6] uploads too large for the ring (they wait); n <= 8. */
+ * of their own, [5] box jobs that rode in a step launch, [6] uploads too large for the ring (they wait), [7] lpf_run_frame_wide jobs
+ * whose masks were read directly, with no pack; n <= 8. */
 int lpf_get_stats(lpf_ctx *ctx, int64_t *out, int n, int reset);
 
 /* ---- multi-GPU: the one exchange step ------------------------------------------------------------

@@ -125,6 +125,14 @@ class FrameJob(ctypes.Structure):
                 ("out", Outputs)]
 
 
+class FrameJobWide(ctypes.Structure):
+    """lpf_frame_job_wide (include/lpf.h): one frame of a stream with up to 256 masks -- scan, lent uint8 masks + rectangles, cam-0
+    box corners, wide outputs -- for lpf_run_frame_wide"""
+    _fields_ = [("pts", _P), ("n_points", _I64), ("masks", _P), ("mask_rects", _P), ("corners_cam0", _P), ("T_cam_to_velo", _P),
+                ("n_masks", ctypes.c_int32), ("n_boxes", ctypes.c_int32), ("filter_visible", ctypes.c_int32), ("oriented", ctypes.c_int32),
+                ("out", WideOutputs)]
+
+
 _libs = {}
 
 
@@ -215,6 +223,7 @@ def load(path=None):
     lib.lpf_run.argtypes = [_P, _P, _I64, ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_batch.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_frame.argtypes = [_P, ctypes.POINTER(FrameJob)]
+    lib.lpf_run_frame_wide.argtypes = [_P, ctypes.POINTER(FrameJobWide)]
     lib.lpf_run_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(WideOutputs)]
     lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_cams_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(WideOutputs)]
@@ -252,7 +261,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_graph_begin", "lpf_graph_end", "lpf_graph_launch", "lpf_graph_destroy",
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
-            "lpf_run_cams_wide")
+            "lpf_run_cams_wide", "lpf_run_frame_wide")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -535,7 +544,8 @@ class LpfContext:
     def graph_destroy(self, g):
         self._lib.lpf_graph_destroy(g)
 
-    STATS = ("host_waits", "drains", "uploads", "step_launches", "box_jobs_alone", "box_jobs_riding", "blocking_uploads")
+    STATS = ("host_waits", "drains", "uploads", "step_launches", "box_jobs_alone", "box_jobs_riding", "blocking_uploads",
+             "wide_direct_frames")
 
     def stats(self, reset=False):
         """dict of lpf_get_stats: what the context has done so far (host waits, drains, uploads, launches)."""
@@ -1266,6 +1276,73 @@ class LpfContext:
         o.summary = _dev_ptr(outs.get("summary"))
         o.uv_valid, o.label_valid = _dev_ptr(outs.get("uv_valid"), "int32"), _dev_ptr(outs.get("label_valid"))
         run, h, check, ref = self._lib.lpf_run_frame, self._h, self._check, ctypes.byref(j)
+
+        def fn(_keep=(j, keep)):
+            rc = run(h, ref)
+            if rc:
+                check(rc)
+        return fn
+
+    _WIDE_OUTS = {"uv": "int32", "depth": "float64", "u_f": "float64", "v_f": "float64", "valid_idx": "int64", "uv_valid": "int32",
+                  "label_words": None, "label_valid_words": None, "inst_idx": "int64", "count_mb": "int32", "n_valid": "int64",
+                  "n_labelled": "int64", "inst_count": "int64", "inst_off": "int64", "best_cnt": "int64", "best_box": "int32",
+                  "inst_overflow": "int32"}
+
+    def make_frame_step_wide(self, pts, masks_u8, mask_rects=None, boxes_cam0=None, T_cam_to_velo=None, filter_visible=True, oriented=True,
+                             **outs):
+        """make_frame_step for frames with up to 256 masks: pre-marshal ONE frame -- scan, lent uint8 masks [M,H,W] (+ their rectangles
+        [M,4]), lent cam-0 box corners [B,8,3] -- into an lpf_frame_job_wide and return a zero-argument callable that makes the one C
+        call (lpf_run_frame_wide).  outs: GPU tensors named after the lpf_wide_outputs fields (uv, depth, u_f, v_f, valid_idx, uv_valid,
+        label_words [N, ceil(M/32)], label_valid_words, inst_idx, count_mb, n_valid, n_labelled, inst_count, inst_off, best_cnt,
+        best_box, inst_overflow), plus inst_cap.  Lent tensors stay unchanged until the frame's results are complete."""
+        bad = set(outs) - set(self._WIDE_OUTS) - {"inst_cap"}
+        if bad:
+            raise ValueError("unknown outputs %s" % sorted(bad))
+        def tensor(t):
+            return _is_torch(t) and hasattr(t, "is_cuda")
+
+        # shapes and dtypes first, then where the tensors live: nothing reaches the native library before every check has passed
+        if not tensor(pts) or str(pts.dtype) != "torch.float32" or pts.dim() != 2 or pts.shape[1] != 4 or not pts.is_contiguous():
+            raise ValueError("pts must be a contiguous torch.float32 tensor [N,4]")
+        if not tensor(masks_u8) or str(masks_u8.dtype) != "torch.uint8" or masks_u8.dim() != 3 or not masks_u8.is_contiguous():
+            raise ValueError("masks_u8 must be a contiguous torch.uint8 tensor [M,H,W]")
+        M = int(masks_u8.shape[0])
+        if M > LPF_MAX_MASKS_WIDE:
+            raise ValueError("at most %d masks per frame, got %d" % (LPF_MAX_MASKS_WIDE, M))
+        if tuple(masks_u8.shape[1:]) != (self.H, self.W):
+            raise ValueError("masks_u8 must be [M,%d,%d] (the camera's size), got %s" % (self.H, self.W, tuple(masks_u8.shape)))
+        if mask_rects is not None and (not tensor(mask_rects) or str(mask_rects.dtype) != "torch.int32" or tuple(mask_rects.shape) != (M, 4)
+                                       or not mask_rects.is_contiguous()):
+            raise ValueError("mask_rects must be a contiguous torch.int32 tensor [M=%d,4]" % M)
+        if boxes_cam0 is not None and (not tensor(boxes_cam0) or str(boxes_cam0.dtype) != "torch.float64" or boxes_cam0.dim() != 3
+                                       or tuple(boxes_cam0.shape[1:]) != (8, 3) or not boxes_cam0.is_contiguous()):
+            raise ValueError("boxes_cam0 must be a contiguous torch.float64 tensor [B,8,3]")
+        if boxes_cam0 is not None and np.asarray(T_cam_to_velo, dtype=np.float64).size != 16:
+            raise ValueError("T_cam_to_velo must be a 4x4 matrix")
+        for k, t in outs.items():
+            if k != "inst_cap" and t is not None and (not tensor(t) or not t.is_contiguous()):
+                raise ValueError("output %s must be a contiguous tensor" % k)
+        for k, t in [("pts", pts), ("masks_u8", masks_u8), ("mask_rects", mask_rects), ("boxes_cam0", boxes_cam0)] + list(outs.items()):
+            if k != "inst_cap" and t is not None and not t.is_cuda:
+                raise ValueError("%s must be a GPU tensor: lpf_run_frame_wide takes device memory only" % k)
+        j = FrameJobWide()
+        j.pts, j.n_points = _dev_ptr(pts, "float32"), int(pts.shape[0])
+        j.masks, j.n_masks = (_dev_ptr(masks_u8) if M else None), M
+        j.mask_rects = _dev_ptr(mask_rects) if (mask_rects is not None and M) else None
+        keep = [pts, masks_u8, mask_rects, outs]
+        if boxes_cam0 is not None:
+            Tcv = np.ascontiguousarray(T_cam_to_velo, dtype=np.float64).reshape(16)
+            B = int(boxes_cam0.shape[0])
+            j.corners_cam0, j.n_boxes, j.T_cam_to_velo = _dev_ptr(boxes_cam0, "float64") if B else None, B, Tcv.ctypes.data
+            j.filter_visible, j.oriented = int(bool(filter_visible)), int(bool(oriented))
+            self.box_off = np.array([0, B], np.int32)
+            keep += [boxes_cam0, Tcv]
+        o = j.out
+        o.on_device = 1
+        for k, dt in self._WIDE_OUTS.items():
+            setattr(o, k, _dev_ptr(outs.get(k), dt))
+        o.inst_cap = int(outs.get("inst_cap", 0))
+        run, h, check, ref = self._lib.lpf_run_frame_wide, self._h, self._check, ctypes.byref(j)
 
         def fn(_keep=(j, keep)):
             rc = run(h, ref)
