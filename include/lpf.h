@@ -51,7 +51,8 @@ extern "C" {
                                       8 (continued): LPF_MAX_CAMS, lpf_cam_input, lpf_run_cams (added; nothing else changed)
                                       8 (continued): lpf_run_cams_wide (added; nothing else changed)
                                       8 (continued): lpf_frame_job_wide, lpf_run_frame_wide (added; lpf_get_stats gained slot [7];
-                                         nothing else changed) */
+                                         nothing else changed)
+                                      8 (continued): lpf_depth_maps_outputs, lpf_depth_maps (added; nothing else changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -416,6 +417,38 @@ int lpf_points_in_boxes(lpf_ctx *ctx, const float *pts, int64_t k, int stride, c
  * (0 where no valid point projects), winner: int32 [H][W] index of that point or -1 (may be NULL).
  * Uses lpf_set_camera's transform and depth window.  pts as in lpf_run; outputs follow on_device. */
 int lpf_depth_image(lpf_ctx *ctx, const float *pts, int64_t N, int on_device, double *depth_img, int32_t *winner);
+
+/* lpf_depth_maps: seg_with_pointcloud.py:160-170's per-car depth maps of a batch of F frames in ONE call, as sparse lists.  Let D_f be
+ * lpf_depth_image's last-writer image of frame f (points frame_off[f] .. frame_off[f + 1] of pts) and member_m mask m's membership
+ * under lpf_wide_input's rules (uint8 nonzero, float32 under binarize 0 / 1 / 2 -- 2 is the script's mask > 0.5 --, erode_iters,
+ * the rectangles a hint: zero outside them).  Car m of frame f is then, bit for bit,
+ *   pix = np.flatnonzero(np.where(member_m, D_f, 0)),  depth = D_f.ravel()[pix]
+ * in entries car_off[f][m] .. car_off[f][m + 1] of row f of pix / depth / point_idx (point_idx: the winning point of the pixel, an
+ * index within frame f).  in->M (0 .. LPF_MAX_MASKS_WIDE) is the same for every frame: frames with fewer masks pad with empty planes.
+ * Camera, transform, size and depth window are lpf_set_camera's (the script's window is (0, 30)).  Entries at or beyond cap are not
+ * written: need[f] is exact and overflow[f] says so.  The masks, rectangles, boxes and label state of the other calls are left as
+ * they were.  Not capturable (LPF_ERR_STATE between lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it first
+ * launches what the pipeline owes (no host wait), then runs in order.  With out->on_device (all outputs device memory) the call
+ * only enqueues work, unless some input is in host memory; with host outputs it returns with them filled, after one host wait.
+ * LPF_ERR_ARG: F < 0, M out of range, cap < 0, car_off or need NULL, pix NULL with cap > 0, bad frame offsets, binarize or
+ * erode_iters; LPF_ERR_STATE: no camera.
+ * Device memory: the frames go through in chunks whose scratch -- a u32 winner plane per frame (W * H rounded up to 1024 pixels),
+ * counters of 8 bytes per (mask, 1024 pixels), with erosion lpf_run_wide's label planes (4 * ceil(M / 32) bytes per pixel, twice
+ * with more than one iteration), staged host masks and points -- stays within 256 MiB, or one frame's worth when a single frame
+ * needs more; plus F * cap * 24 bytes of staging for host outputs.  A 146-frame batch never holds 146 image planes at once. */
+typedef struct lpf_depth_maps_outputs {
+    int64_t  *pix;        /* [F][cap] flat pixel v * W + u, ascending within each car (may be NULL only with cap == 0) */
+    double   *depth;      /* [F][cap] depth of that pixel's last valid point (may be NULL) */
+    int64_t  *point_idx;  /* [F][cap] index of that point within its frame (may be NULL) */
+    int64_t   cap;
+    int64_t  *car_off;    /* [F][M + 1] car m of frame f = entries car_off[f][m] .. car_off[f][m + 1] (required) */
+    int64_t  *need;       /* [F] entries frame f needs = car_off[f][M] (required) */
+    int32_t  *overflow;   /* [F] 1 if need[f] > cap: entries at or beyond cap are not written (may be NULL) */
+    int32_t   on_device;
+    int32_t   reserved;
+} lpf_depth_maps_outputs;
+int lpf_depth_maps(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
+                   const lpf_depth_maps_outputs *out);
 
 /* cv2.resize(mask.astype(np.uint8), (camera.width, camera.height)) (V3:222; INTER_LINEAR, the default) for masks that do not arrive at
  * the camera's size (the reference's scripts all pass retina_masks=True, so theirs do): n planes [h][w] of uint8 -> n planes [H][W]

@@ -62,6 +62,12 @@ class WideOutputs(ctypes.Structure):
                 ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class DepthMapsOutputs(ctypes.Structure):
+    """lpf_depth_maps_outputs (include/lpf.h): the per-car sparse depth maps of an lpf_depth_maps call"""
+    _fields_ = [("pix", _P), ("depth", _P), ("point_idx", _P), ("cap", _I64), ("car_off", _P), ("need", _P), ("overflow", _P),
+                ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 LPF_MAX_CAMS = 4                        # lpf_run_cams / lpf_run_cams_wide: cameras of one pass
 
 
@@ -225,6 +231,7 @@ def load(path=None):
     lib.lpf_run_frame.argtypes = [_P, ctypes.POINTER(FrameJob)]
     lib.lpf_run_frame_wide.argtypes = [_P, ctypes.POINTER(FrameJobWide)]
     lib.lpf_run_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(WideOutputs)]
+    lib.lpf_depth_maps.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(DepthMapsOutputs)]
     lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_cams_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(WideOutputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
@@ -261,7 +268,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_graph_begin", "lpf_graph_end", "lpf_graph_launch", "lpf_graph_destroy",
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
-            "lpf_run_cams_wide", "lpf_run_frame_wide")
+            "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -1188,6 +1195,55 @@ class LpfContext:
 
         out = self._until_lists_fit(launch, inst_cap, off)
         return self._frame_results(off, M, *out)
+
+    def depth_maps(self, frames, masks, binarize="gt0.5", rects=None, erode_iters=0, cap=None, want_point_idx=True):
+        """seg_with_pointcloud's per-car depth maps of a batch of frames in ONE native call (lpf_depth_maps) and one host wait.
+        frames: as run_wide's -- f32[N_f,4] host arrays, Scans of a ScanReader, float32 [N,4] GPU tensors.  masks: [M,H,W] or
+        [F,M,H,W] at the camera's size (uint8 / bool: nonzero, or float32 under ``binarize``; "gt0.5" is the script's mask > 0.5),
+        host or GPU; rects: the optional [F,M,4] hint of set_mask_rects; erode_iters: cv2.erode iterations.  The camera, transform
+        and depth window are set_camera's.  Returns, per frame, M tuples (pix int64, depth float64, point_idx int64 or None): car m
+        = np.flatnonzero(np.where(member_m, D, 0)) with D the frame's depth_image, its depths and the winning points.  cap: list
+        entries per frame of the first attempt (default from the point counts); a frame that needs more runs the call once more
+        with the exact capacity."""
+        F = len(frames)
+        if F == 0:
+            raise ValueError("no frames")
+        if cap is not None and (isinstance(cap, bool) or int(cap) != cap or cap < 0):
+            raise ValueError("cap must be a non-negative integer, got %r" % (cap,))
+        masks, M, is_f, mdev, rects = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
+        off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the call returns)
+        if mdev:
+            import torch
+            self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
+        inp = WideInput()
+        inp.masks = (masks.data_ptr() if mdev else masks.ctypes.data) if M else None
+        inp.rects = (rects.data_ptr() if mdev else rects.ctypes.data) if (rects is not None and M) else None
+        inp.M, inp.f32, inp.binarize, inp.erode_iters = M, int(is_f), self.BINARIZE[binarize], int(erode_iters)
+        inp.on_device = 1 if mdev else 0
+        if cap is None:                     # a quarter of the largest frame's points: frame 100's five cars are 8 k of its 109 k
+            cap = 0 if M == 0 else max(1024, min(int(np.diff(off).max()) // 4, self.W * self.H))
+
+        def launch(cap):
+            o = DepthMapsOutputs()
+            pix = self._pinned("dm_pix", (F, cap), np.int64)
+            dep = self._pinned("dm_dep", (F, cap), np.float64)
+            pid = self._pinned("dm_pid", (F, cap), np.int64) if want_point_idx else None
+            car_off, need, ovf = np.zeros((F, M + 1), np.int64), np.zeros(F, np.int64), np.zeros(F, np.int32)
+            o.pix, o.depth = (pix.ctypes.data, dep.ctypes.data) if cap else (None, None)
+            o.point_idx = pid.ctypes.data if (pid is not None and cap) else None
+            o.cap, o.car_off, o.need, o.overflow, o.on_device = cap, car_off.ctypes.data, need.ctypes.data, ovf.ctypes.data, 0
+            self._check(self._lib.lpf_depth_maps(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
+            return pix, dep, pid, car_off, need, ovf
+
+        pix, dep, pid, car_off, need, ovf = launch(int(cap))
+        if ovf.any():                       # once, with the exact capacity
+            pix, dep, pid, car_off, need, ovf = launch(int(need.max()))
+        out = []
+        for f in range(F):
+            o = car_off[f]
+            out.append([(pix[f, o[m]:o[m + 1]].copy(), dep[f, o[m]:o[m + 1]].copy(),
+                         pid[f, o[m]:o[m + 1]].copy() if pid is not None else None) for m in range(M)])
+        return out
 
     def run_cams_wide(self, frames, cams, want_uv=True, want_float=False, want_lists=True, want_valid_uv=False, inst_cap=None,
                       want_label=True, pinned=False):

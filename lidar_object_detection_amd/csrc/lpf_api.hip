@@ -6,6 +6,7 @@
 #include "lpf_cams.hip.h"
 #include "lpf_cams_wide.hip.h"
 #include "lpf_frame_wide.hip.h"
+#include "lpf_depth_maps.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -178,6 +179,9 @@ struct lpf_ctx {
     // lpf_run_cams_wide: camera c's lpf_run_wide buffers (cam[c]: staged masks, planes, scratch, host-output staging), the pass's frame
     // tables and staged points (grow-only, allocated on first use); its box tables are lpf_run_cams' (cams.bx[c])
     struct CamsWide { Wide cam[LPF_NSETS]; DevBuf tab, pts; } camsw;
+    // lpf_depth_maps: frame offsets, a chunk's winner planes, counters, staged masks / rectangles / points, host-output staging and
+    // (with erosion) lpf_run_wide's label planes in pack.planes_* (grow-only, allocated on first use)
+    struct DepthMaps { Wide pack; DevBuf foff, win, cnt, masks, rects, pts, out; } dmaps;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -872,6 +876,9 @@ void lpf_destroy(lpf_ctx *c)
     }
     release(c->camsw.tab);
     release(c->camsw.pts);
+    for (DevBuf *b : {&c->dmaps.pack.planes_a, &c->dmaps.pack.planes_b, &c->dmaps.foff, &c->dmaps.win, &c->dmaps.cnt, &c->dmaps.masks,
+                      &c->dmaps.rects, &c->dmaps.pts, &c->dmaps.out})
+        release(*b);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_uvv, &c->st_labv, &c->st_pts, &c->st_uv, &c->st_label,
                      &c->st_depth, &c->st_uf, &c->st_vf, &c->st_valid, &c->st_inst, &c->st_count, &c->st_summary};
     for (DevBuf *b : all) release(*b);
@@ -2189,6 +2196,185 @@ int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
                  const lpf_wide_outputs *out)
 {
     return run_wide_impl(c, pts, frame_off, F, pts_on_device, in, out, false);
+}
+
+// ---- lpf_depth_maps (include/lpf.h): per-car depth maps as sparse lists, kernels in lpf_depth_maps.hip.h ----------------------
+// Frames go through in chunks of Fc: Fc winner planes, counters, staged masks / points (and label planes with erosion) within
+// LPF_DM_BUDGET, or one frame when a single frame needs more.  Every buffer is reserved for the largest chunk before the first launch,
+// so no chunk waits for the one before it (reserve() only waits when it has to grow a buffer).
+#define LPF_DM_BUDGET (256ull << 20)
+
+// lpf_dm_raster for the masks' element type and rule: the count walk, or (scatter) the writing one
+#define LPF_DM_RASTER(S)                                                                                                              \
+    do {                                                                                                                              \
+        if (planes) hipLaunchKernelGGL((lpf_dm_raster<uint32_t, 0, true, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);                   \
+        else if (!in->f32) hipLaunchKernelGGL((lpf_dm_raster<uint8_t, 0, false, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);            \
+        else if (in->binarize == 0) hipLaunchKernelGGL((lpf_dm_raster<float, 1, false, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);     \
+        else if (in->binarize == 1) hipLaunchKernelGGL((lpf_dm_raster<float, 2, false, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);     \
+        else hipLaunchKernelGGL((lpf_dm_raster<float, 3, false, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);                            \
+    } while (0)
+static void dm_raster(lpf_ctx *c, const LpfDmParams &P, dim3 g, bool planes, const lpf_wide_input *in, bool scatter)
+{
+    if (scatter) LPF_DM_RASTER(true);
+    else LPF_DM_RASTER(false);
+}
+#undef LPF_DM_RASTER
+
+int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
+                   const lpf_depth_maps_outputs *out)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (use_device(c)) return LPF_ERR_HIP;
+    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_depth_maps cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
+    if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera has not been called");
+    if (!in || !out || F < 0 || (F > 0 && !frame_off))
+        return fail(c, LPF_ERR_ARG, "depth_maps: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
+    const int M = in->M;
+    if (M < 0 || M > LPF_MAX_MASKS_WIDE)
+        return fail(c, LPF_ERR_ARG, "depth_maps: M=%d masks per frame, lpf_depth_maps takes 0 .. LPF_MAX_MASKS_WIDE = %d", M, LPF_MAX_MASKS_WIDE);
+    if (in->erode_iters < 0 || (in->f32 && (in->binarize < 0 || in->binarize > 2)) || (M > 0 && !in->masks))
+        return fail(c, LPF_ERR_ARG, "depth_maps: erode_iters=%d f32=%d binarize=%d masks=%p", in->erode_iters, in->f32, in->binarize, in->masks);
+    if (out->cap < 0 || !out->car_off || !out->need || (out->cap > 0 && !out->pix))
+        return fail(c, LPF_ERR_ARG, "depth_maps: cap=%lld pix=%p car_off=%p need=%p (car_off and need are required, pix with cap > 0)",
+                    (long long)out->cap, (void *)out->pix, (void *)out->car_off, (void *)out->need);
+    if (F == 0) return LPF_OK;
+    if (frame_off[0] != 0) return fail(c, LPF_ERR_ARG, "depth_maps: frame_off[0] must be 0");
+    long long maxN = 0;
+    for (int f = 0; f < F; ++f) {
+        const int64_t n = frame_off[f + 1] - frame_off[f];
+        if (n < 0 || n > 0x7fffffffll - LPF_BLOCK) return fail(c, LPF_ERR_ARG, "depth_maps: frame %d has %lld points", f, (long long)n);
+        maxN = std::max(maxN, (long long)n);
+    }
+    const int64_t Ntot = frame_off[F];
+    if (Ntot > 0 && !pts) return fail(c, LPF_ERR_ARG, "depth_maps: pts is NULL");
+    int rc;
+    // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+
+    lpf_ctx::DepthMaps &D = c->dmaps;
+    const size_t hw = (size_t)c->W * c->H, esz = in->f32 ? 4 : 1;
+    const int ntile = (int)((hw + LPF_DM_TILE - 1) / LPF_DM_TILE), LW = (M + 31) / 32;
+    const size_t hwp = (size_t)ntile * LPF_DM_TILE;
+    const bool planes = M > 0 && in->erode_iters > 0;
+    const bool host_masks = M > 0 && !in->on_device, host_pts = Ntot > 0 && !pts_on_device, host_io = !out->on_device;
+    // (the rectangles hold where lpf_set_mask_rects takes them: uint8, or float under binarize 0, without erosion -- wide_pack's rule)
+    const bool use_rects = in->rects && M > 0 && in->erode_iters == 0 && (!in->f32 || in->binarize == 0);
+    const size_t per_frame = hwp * 4 + (size_t)M * ntile * 12 + (planes ? (size_t)LW * hw * 4 * (in->erode_iters > 1 ? 2 : 1) : 0) +
+                             (host_masks ? (size_t)M * (hw * esz + 16) : 0) + (host_pts ? (size_t)maxN * 16 : 0);
+    const int Fc = (int)std::max<size_t>(1, std::min<size_t>((size_t)F, LPF_DM_BUDGET / per_frame));
+
+    // ---- buffers, reserved for the largest chunk ------------------------------------------------------------------------------------
+    if ((rc = reserve(c, D.foff, (size_t)(F + 1) * 8))) return rc;
+    if ((rc = reserve(c, D.win, (size_t)Fc * hwp * 4))) return rc;
+    if (M > 0 && (rc = reserve(c, D.cnt, (size_t)Fc * M * (2 * ntile + 1) * 4))) return rc;
+    if (host_masks) {
+        if ((rc = reserve(c, D.masks, (size_t)Fc * M * hw * esz))) return rc;
+        if (in->rects && (rc = reserve(c, D.rects, (size_t)Fc * M * 16))) return rc;
+    }
+    if (host_pts) {
+        long long most = 0;                                   // points of the largest chunk
+        for (int f0 = 0; f0 < F; f0 += Fc) most = std::max(most, (long long)(frame_off[std::min(F, f0 + Fc)] - frame_off[f0]));
+        if ((rc = reserve(c, D.pts, (size_t)most * 16))) return rc;
+    }
+    const size_t cap = (size_t)out->cap, nF = (size_t)F;
+    size_t o_pix = 0, o_dep = 0, o_pid = 0, o_off = 0, o_need = 0, o_ovf = 0;
+    if (host_io) {
+        size_t off = 0;
+        auto carve = [&](bool want, size_t bytes) -> size_t { const size_t o = off; if (want) off += (bytes + 255) & ~(size_t)255; return o; };
+        o_pix = carve(cap > 0, nF * cap * 8); o_dep = carve(out->depth && cap > 0, nF * cap * 8); o_pid = carve(out->point_idx && cap > 0, nF * cap * 8);
+        o_off = carve(true, nF * (M + 1) * 8); o_need = carve(true, nF * 8); o_ovf = carve(out->overflow != nullptr, nF * 4);
+        if ((rc = reserve(c, D.out, off))) return rc;
+    }
+    if ((rc = upload(c, D.foff.p, frame_off, (size_t)(F + 1) * 8))) return rc;
+
+    LpfDmParams P;
+    memset(&P, 0, sizeof P);
+    memcpy(P.cam.T, c->T, sizeof P.cam.T);
+    memcpy(P.cam.K, c->K, sizeof P.cam.K);
+    P.cam.dmin = c->dmin; P.cam.dmax = c->dmax; P.cam.W = c->W; P.cam.H = c->H;
+    P.M = M; P.LW = LW; P.ntile = ntile; P.hwp = (long long)hwp; P.cap = out->cap;
+    P.foff = (const long long *)D.foff.p;
+    P.win = (unsigned *)D.win.p;
+    P.cnt = (unsigned *)D.cnt.p;
+    P.toff = P.cnt + (size_t)Fc * M * ntile;
+    P.tot = P.toff + (size_t)Fc * M * ntile;
+    char *st = (char *)D.out.p;
+    P.pix = (long long *)(host_io ? (cap ? st + o_pix : nullptr) : (void *)out->pix);
+    P.depth = (double *)(host_io ? (out->depth && cap ? st + o_dep : nullptr) : (void *)out->depth);
+    P.pidx = (long long *)(host_io ? (out->point_idx && cap ? st + o_pid : nullptr) : (void *)out->point_idx);
+    P.car_off = (long long *)(host_io ? st + o_off : (void *)out->car_off);
+    P.need = (long long *)(host_io ? st + o_need : (void *)out->need);
+    P.overflow = (int *)(host_io ? (out->overflow ? st + o_ovf : nullptr) : (void *)out->overflow);
+
+    // ---- the chunks ---------------------------------------------------------------------------------------------------------
+    for (int f0 = 0; f0 < F; f0 += Fc) {
+        const int fc = std::min(Fc, F - f0);
+        const long long a = frame_off[f0], nc = frame_off[f0 + fc] - a;
+        long long mc = 0;
+        for (int f = f0; f < f0 + fc; ++f) mc = std::max(mc, (long long)(frame_off[f + 1] - frame_off[f]));
+        P.f0 = f0; P.pt_base = a;
+        if (host_pts && nc > 0) {
+            LPF_HIP(c, hipMemcpyAsync(D.pts.p, pts + 4 * a, (size_t)nc * 16, hipMemcpyHostToDevice, c->stream));
+            P.cam.pts = (const float4 *)D.pts.p;
+        } else {
+            P.cam.pts = nc > 0 ? (const float4 *)(pts + 4 * a) : nullptr;
+        }
+        if (M > 0) {
+            const void *dm = (const char *)in->masks + (size_t)f0 * M * hw * esz;
+            const int32_t *dr = in->rects ? in->rects + (size_t)f0 * M * 4 : nullptr;
+            if (host_masks) {
+                LPF_HIP(c, hipMemcpyAsync(D.masks.p, dm, (size_t)fc * M * hw * esz, hipMemcpyHostToDevice, c->stream));
+                dm = D.masks.p;
+                if (dr) {
+                    LPF_HIP(c, hipMemcpyAsync(D.rects.p, dr, (size_t)fc * M * 16, hipMemcpyHostToDevice, c->stream));
+                    dr = (const int32_t *)D.rects.p;
+                }
+            }
+            P.masks = dm;
+            P.rects = use_rects ? (const int4 *)dr : nullptr;
+            if (planes) {                                   // erosion: lpf_run_wide's pack + erode into LW planes per frame
+                lpf_wide_input sub = *in;
+                sub.masks = dm; sub.rects = dr; sub.on_device = 1;
+                LpfWideParams Wp;
+                memset(&Wp, 0, sizeof Wp);
+                bool staged = false;
+                if ((rc = wide_pack(c, D.pack, &sub, fc, c->W, c->H, Wp, &staged))) return rc;
+                P.masks = Wp.planes;
+                P.rects = nullptr;
+            }
+            LPF_HIP(c, hipMemsetAsync(D.win.p, 0, (size_t)fc * hwp * 4, c->stream));
+            LPF_HIP(c, hipMemsetAsync(D.cnt.p, 0, (size_t)fc * M * ntile * 4, c->stream));
+            if (mc > 0) {
+                hipLaunchKernelGGL(lpf_dm_winner, dim3((unsigned)((mc + LPF_BLOCK - 1) / LPF_BLOCK), (unsigned)fc), dim3(LPF_BLOCK), 0, c->stream, P);
+                LPF_HIP(c, hipGetLastError());
+                dm_raster(c, P, dim3((unsigned)((ntile + 3) / 4), (unsigned)fc, (unsigned)((M + LPF_DM_MGROUP - 1) / LPF_DM_MGROUP)), planes, in, false);
+                LPF_HIP(c, hipGetLastError());
+            }
+            hipLaunchKernelGGL(lpf_dm_scan, dim3((unsigned)((M + 3) / 4), (unsigned)fc), dim3(LPF_BLOCK), 0, c->stream, P);
+            LPF_HIP(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(lpf_dm_frame, dim3((unsigned)fc), dim3(LPF_BLOCK), 0, c->stream, P);
+        LPF_HIP(c, hipGetLastError());
+        if (M > 0 && mc > 0 && cap > 0) {
+            dm_raster(c, P, dim3((unsigned)((ntile + 3) / 4), (unsigned)fc, (unsigned)((M + LPF_DM_MGROUP - 1) / LPF_DM_MGROUP)), planes, in, true);
+            LPF_HIP(c, hipGetLastError());
+        }
+    }
+
+    if (host_io) {
+        auto back = [&](void *user, size_t o, size_t bytes) -> hipError_t {
+            if (!user || !bytes) return hipSuccess;
+            return hipMemcpyAsync(user, st + o, bytes, hipMemcpyDeviceToHost, c->stream);
+        };
+        LPF_HIP(c, back(out->pix, o_pix, nF * cap * 8));
+        LPF_HIP(c, back(out->depth, o_dep, nF * cap * 8));
+        LPF_HIP(c, back(out->point_idx, o_pid, nF * cap * 8));
+        LPF_HIP(c, back(out->car_off, o_off, nF * (M + 1) * 8));
+        LPF_HIP(c, back(out->need, o_need, nF * 8));
+        LPF_HIP(c, back(out->overflow, o_ovf, nF * 4));
+    }
+    if (host_io || host_masks || host_pts) LPF_HIP(c, host_wait(c));   // host buffers may be reused
+    return LPF_OK;
 }
 
 // ---- lpf_run_cams (include/lpf.h): one scan in up to LPF_MAX_CAMS cameras, kernels in lpf_cams.hip.h ------------------------------

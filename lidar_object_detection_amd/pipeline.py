@@ -227,6 +227,28 @@ def per_car_depth_maps(points, TrVeloToRect, camera, masks, depth_max=30.0, devi
     return [(i + 1, np.where(np.asarray(m) > 0.5, D, 0.0)) for i, m in enumerate(masks)]
 
 
+class SparseDepthMap:
+    """One car's depth map of seg_with_pointcloud.py:160-170 as the list of its nonzero pixels: ``pixels`` = the flat indices
+    v * W + u in ascending order (``np.flatnonzero(depthMap)``), ``depth`` = ``depthMap.ravel()[pixels]``, ``point_idx`` = the
+    winning point of each pixel (index into the frame's scan, or None), ``shape`` = (H, W).  to_dense() is the script's depthMap."""
+    __slots__ = ("car_id", "pixels", "depth", "point_idx", "shape")
+
+    def __init__(self, car_id, pixels, depth, point_idx, shape):
+        self.car_id, self.pixels, self.depth, self.point_idx, self.shape = car_id, pixels, depth, point_idx, tuple(shape)
+
+    def to_dense(self):
+        """depthMap f64 [H,W]: depth at the listed pixels, 0 elsewhere"""
+        d = np.zeros(self.shape, np.float64)
+        d.ravel()[self.pixels] = self.depth
+        return d
+
+    def __len__(self):
+        return len(self.pixels)
+
+    def __repr__(self):
+        return "SparseDepthMap(car_id=%d, %d pixels, shape=%s)" % (self.car_id, len(self.pixels), self.shape)
+
+
 # ---------------------------------------------------------------------------------------
 # mask lookup (V3:211-233, cvs_erosion.py:148-162)
 # ---------------------------------------------------------------------------------------
@@ -1276,6 +1298,120 @@ def process_frames(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_
             if r["car_statistics"]:
                 append_to_master_csv(r["car_statistics"], r["frame"], master_csv_path, timestamp)
     return analyze_master_csv(master_csv_path)
+
+
+def _depth_map_masks(frames, H, W):
+    """The frames' masks as ONE [F,M,H,W] batch for lpf_depth_maps (M = the most masks of a frame; the others pad with empty
+    masks) and each frame's own count.  float masks are read as the script's ``mask > 0.5``, uint8 / bool ones as nonzero; a batch
+    that mixes them goes as float32 (a nonzero byte is >= 1).  GPU tensors stay on the GPU (the batch is made there).  Masks at
+    another size than the camera's raise ValueError: seg_with_pointcloud indexes them with the image's pixels."""
+    stacks = []
+    for f in frames:
+        m = f.masks if f.masks is not None else []
+        if _is_device_tensor(m):
+            if m.dim() != 3:
+                raise ValueError("frame %s: device masks must be [M,H,W], got %s" % (f.frame, tuple(m.shape)))
+        elif isinstance(m, np.ndarray):
+            if m.ndim != 3 and not (m.ndim == 1 and m.size == 0):
+                raise ValueError("frame %s: masks must be [M,H,W], got %s" % (f.frame, m.shape))
+        else:
+            m = [x if _is_device_tensor(x) else np.asarray(x) for x in m]
+            for x in m:
+                if x.ndim != 2:
+                    raise ValueError("frame %s: each mask must be [H,W], got %s" % (f.frame, tuple(x.shape)))
+            if m and any(_is_device_tensor(x) for x in m):
+                import torch
+                m = torch.stack([x if _is_device_tensor(x) else torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in m])
+            else:
+                m = np.stack(m) if m else np.zeros((0, H, W), np.uint8)
+        if m.shape[0] and tuple(m.shape[1:]) != (H, W):
+            raise ValueError("frame %s: masks must be at the camera's size [M,%d,%d], got %s" % (f.frame, H, W, tuple(m.shape)))
+        stacks.append(m)
+    Ms = [int(m.shape[0]) for m in stacks]
+    M = max(Ms) if Ms else 0
+
+    def is_float(m):
+        return (str(m.dtype) in ("torch.float16", "torch.float32", "torch.float64")) if _is_device_tensor(m) else m.dtype.kind == "f"
+    flt = any(is_float(m) for m in stacks if m.shape[0])
+    if any(_is_device_tensor(m) for m in stacks if m.shape[0]):
+        import torch
+        dev = next(m.device for m in stacks if _is_device_tensor(m) and m.shape[0])
+        batch = torch.zeros((len(stacks), M, H, W), dtype=torch.float32 if flt else torch.uint8, device=dev)
+        for i, m in enumerate(stacks):
+            if m.shape[0]:
+                t = m if _is_device_tensor(m) else torch.from_numpy(np.ascontiguousarray(m))
+                batch[i, :m.shape[0]].copy_(t.to(dev) if flt else (t.to(dev) != 0))
+        return batch, Ms, flt
+    batch = np.zeros((len(stacks), M, H, W), np.float32 if flt else np.uint8)
+    for i, m in enumerate(stacks):
+        if m.shape[0]:
+            batch[i, :m.shape[0]] = m if flt else (m != 0)
+    return batch, Ms, flt
+
+
+def depth_maps_frames(frames, TrVeloToRect, camera, depth_max=30.0, device=0, ctx=None):
+    """seg_with_pointcloud.py:160-170's per-car depth maps of a list of FrameInputs in one native call (lpf_depth_maps) per group
+    of up to 256 masks: per frame ``[(car_id, SparseDepthMap)]``, car_id = i + 1 over the frame's masks, each map equal to
+    ``per_car_depth_maps``' depthMap (``to_dense()``).  Points: host arrays, Scans of the read-ahead reader or GPU tensors; masks: a
+    list, an array or a GPU tensor [M,H,W] at the camera's size, float (> 0.5) or uint8 / bool (nonzero); frames may differ in
+    their mask counts.  The depth window is (0, depth_max)."""
+    frames = list(frames)
+    if not frames:
+        return []
+    ctx = ctx or get_context(device)
+    ctx.set_camera(TrVeloToRect, camera.K, camera.width, camera.height, 0.0, float(depth_max))
+    H, W = int(camera.height), int(camera.width)
+    batch, Ms, flt = _depth_map_masks(frames, H, W)
+    M = batch.shape[1]
+    out = [[] for _ in frames]
+    if M == 0:
+        return out
+    pts = [f.points for f in frames]
+    for g in range(0, M, LPF_MAX_MASKS_WIDE):                   # groups of 256 masks, concatenated
+        part = batch[:, g:g + LPF_MAX_MASKS_WIDE]
+        part = part.contiguous() if _is_device_tensor(part) else np.ascontiguousarray(part)
+        res = ctx.depth_maps(pts, part, binarize="gt0.5" if flt else "astype")
+        for f, cars in enumerate(res):
+            for j, (pix, dep, pid) in enumerate(cars):
+                i = g + j
+                if i < Ms[f]:
+                    out[f].append((i + 1, SparseDepthMap(i + 1, pix, dep, pid, (H, W))))
+    return out
+
+
+def process_frames_depth_maps(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_path=None, frames=None, depth_max=30.0,
+                              device=0):
+    """seg_with_pointcloud.projectVeloToImage's frame loop (seg_with_pointcloud.py:105-170) without the plotting: yields
+    ``(frame, [(car_id, SparseDepthMap)])`` per frame with detections.  Scans are read in order by the native read-ahead reader; the
+    image is data_rect/<frame>.png of the camera (a missing one raises the script's RuntimeError, :145-146);
+    ``segmenter(image) -> (img, masks, ...)`` is the segmentation stage (it stays outside this package), and a frame whose masks
+    are None or empty prints the script's ``[INFO]`` line and is skipped (:148-151).  cam_id: 0 or 1 (perspective cameras; the
+    script runs camera 0)."""
+    if segmenter is None:
+        raise ValueError("process_frames_depth_maps needs the segmentation callable (YOLO stays outside this package)")
+    if cam_id not in (0, 1):
+        raise ValueError("cam_id must be 0 or 1 (the perspective cameras), got %r" % (cam_id,))
+    root = kitti360_path or os.environ["KITTI360_DATASET"]
+    sequence, camera, velo_to_cam, velo_to_rect, velo = sequence_setup(root, seq, cam_id)
+    todo = velo.available_frames() if frames is None else list(frames)
+    paths = [os.path.join(velo.raw3DPcdPath, "%010d.bin" % f) for f in todo]
+    if not paths:
+        return
+    ctx = get_context(device)
+    sizes = [os.path.getsize(p) // 16 for p in paths if os.path.isfile(p)]
+    with ScanReader(ctx, paths, n_buffers=3, max_points=max(sizes + [1])) as reader:
+        for frame in todo:
+            scan = next(reader)
+            image_path = os.path.join(root, "data_2d_raw", sequence, "image_%02d" % cam_id,
+                                      "data_rect" if cam_id in [0, 1] else "data_rgb", "%010d.png" % frame)
+            if not os.path.isfile(image_path):
+                raise RuntimeError(f'Image file {image_path} does not exist!')
+            seg = segmenter(image_loader(image_path) if image_loader else image_path)
+            masks = seg[1] if seg is not None else None
+            if masks is None or len(masks) == 0:
+                print(f"[INFO] No cars detected in frame {frame}, skipping.")
+                continue
+            yield frame, depth_maps_frames([FrameInputs(frame, scan, masks)], velo_to_rect, camera, depth_max, device, ctx)[0]
 
 
 def process_frames_multicam(seq=0, cam_ids=(0, 1), segmenter=None, image_loader=None, kitti360_path=None, master_csv_paths=None,
