@@ -121,7 +121,8 @@ struct lpf_ctx {
         DevBuf rgrid;                 // candidate grid of the masks' rectangles (LpfDirectRect tiles), [F][cells] uint32
         DevBuf rects;                 // lpf_set_mask_rects from host memory: the copy this set's run reads (its tiles may run a launch later)
         DevBuf tab;                   // [frames | segs | blks]
-        std::vector<LpfFrame> tab_frames;         // the frame table `tab` holds (empty: none)
+        std::vector<LpfFrame> tab_frames;         // the frame records `tab` was built from (empty: none) ...
+        int tab_csplit = 0;                       // ... and its count blocks per (group, word): the key of the tables (narrow_tables)
         size_t o_segs = 0, o_blks = 0, o_cblks = 0;
     } sc[LPF_NSETS];
     int parity = 0;
@@ -168,7 +169,7 @@ struct lpf_ctx {
     DevBuf pib_box, pib_pts, pib_out, boxprep, dimg, coll;
     DevBuf st_uvv, st_labv;
     DevBuf st_pts, st_uv, st_label, st_depth, st_uf, st_vf, st_valid, st_inst, st_count, st_summary;
-    std::vector<LpfFrame> h_frames;   // table being built
+    std::vector<LpfFrame> h_frames;   // frame records being built (narrow_layout)
     std::vector<char> h_tab;          // [frames | segs | blks] being built
 
     // lpf_run_wide: its own buffers (the narrow masks, label images and staging stay as they are)
@@ -803,6 +804,318 @@ int ensure_packed(lpf_ctx *c)
     return LPF_OK;
 }
 
+// ---- setup the run paths share ---------------------------------------------------------------------------------------------------
+
+// frame_off[0..F] (not NULL, F > 0: the caller's checks) starts at 0 and has frames of 0 .. 0x7fffffff - slack points; pts is given if
+// there are points.  who: the messages' prefix
+int check_frames(lpf_ctx *c, const char *who, const float *pts, const int64_t *frame_off, int F, int64_t slack)
+{
+    if (frame_off[0] != 0) return fail(c, LPF_ERR_ARG, "%s: frame_off[0] must be 0", who);
+    for (int f = 0; f < F; ++f) {
+        const int64_t n = frame_off[f + 1] - frame_off[f];
+        if (n < 0 || n > 0x7fffffffll - slack) return fail(c, LPF_ERR_ARG, "%s: frame %d has %lld points", who, f, (long long)n);
+    }
+    if (frame_off[F] > 0 && !pts) return fail(c, LPF_ERR_ARG, "%s: pts is NULL", who);
+    return LPF_OK;
+}
+
+// a lpf_wide_input: 0 .. max_M masks per frame ("... M=<M> masks per frame, <takes> = <max_M><more>"), erosion, binarisation, masks
+// given if M > 0.  who: the messages' prefix; cam >= 0: the input of that camera of a multi-camera pass
+int check_wide_input(lpf_ctx *c, const char *who, int cam, const lpf_wide_input &m, int max_M, const char *takes, const char *more)
+{
+    if (m.M < 0 || m.M > max_M) {
+        if (cam < 0) return fail(c, LPF_ERR_ARG, "%s: M=%d masks per frame, %s = %d%s", who, m.M, takes, max_M, more);
+        return fail(c, LPF_ERR_ARG, "%s: camera %d has M=%d masks per frame, %s = %d%s", who, cam, m.M, takes, max_M, more);
+    }
+    if (m.erode_iters < 0 || (m.f32 && (m.binarize < 0 || m.binarize > 2)) || (m.M > 0 && !m.masks)) {
+        if (cam < 0) return fail(c, LPF_ERR_ARG, "%s: erode_iters=%d f32=%d binarize=%d masks=%p", who, m.erode_iters, m.f32, m.binarize, m.masks);
+        return fail(c, LPF_ERR_ARG, "%s: camera %d: erode_iters=%d f32=%d binarize=%d masks=%p", who, cam, m.erode_iters, m.f32, m.binarize, m.masks);
+    }
+    return LPF_OK;
+}
+
+// the rectangles of a lpf_wide_input hold where lpf_set_mask_rects takes them: uint8, or float under binarize 0, without erosion
+bool rects_hold(const lpf_wide_input &m) { return m.rects && m.erode_iters == 0 && (!m.f32 || m.binarize == 0); }
+
+// the masks of a lpf_wide_input (M > 0) for F frames of hw pixels: host masks and rectangles are staged into dm / dr in stream order
+// (*host_in is set), device ones are lent.  *rects: the rectangles where they hold (rects_hold), else NULL
+int stage_masks(lpf_ctx *c, const lpf_wide_input &m, int F, size_t hw, DevBuf &dm, DevBuf &dr, const void **masks, const int4 **rects,
+                bool *host_in)
+{
+    int rc;
+    const void *d_masks = m.masks;
+    const int32_t *d_rects = m.rects;
+    if (!m.on_device) {
+        const size_t bytes = (size_t)F * m.M * hw * (m.f32 ? 4 : 1);
+        if ((rc = reserve(c, dm, bytes))) return rc;
+        LPF_HIP(c, hipMemcpyAsync(dm.p, m.masks, bytes, hipMemcpyHostToDevice, c->stream));
+        d_masks = dm.p;
+        if (m.rects) {
+            if ((rc = reserve(c, dr, (size_t)F * m.M * 16))) return rc;
+            LPF_HIP(c, hipMemcpyAsync(dr.p, m.rects, (size_t)F * m.M * 16, hipMemcpyHostToDevice, c->stream));
+            d_rects = (const int32_t *)dr.p;
+        }
+        *host_in = true;
+    }
+    *masks = d_masks;
+    *rects = rects_hold(m) ? (const int4 *)d_rects : nullptr;
+    return LPF_OK;
+}
+
+// a camera as the kernels take it (LpfParams' T, K, dmin, dmax, W, H): the context's (lpf_set_camera) or a lpf_cam_input's
+struct Cam {
+    const double *T, *K;              // T: rows 0..2 are used (as lpf_set_camera)
+    double dmin, dmax;
+    int W, H;
+};
+Cam ctx_cam(const lpf_ctx *c) { return Cam{c->T, c->K, c->dmin, c->dmax, c->W, c->H}; }
+Cam input_cam(const lpf_cam_input &I) { return Cam{I.T_velo_to_rect, I.K, I.depth_min_excl, I.depth_max_excl, I.W, I.H}; }
+void set_cam(LpfParams &P, const Cam &k)
+{
+    memcpy(P.T, k.T, sizeof P.T);
+    memcpy(P.K, k.K, sizeof P.K);
+    P.dmin = k.dmin; P.dmax = k.dmax; P.W = k.W; P.H = k.H;
+}
+
+// The segmentation of a narrow run (lpf_run_batch, lpf_run_cams): segments of 4096 points (1024 for small launches), one list wave
+// each; K1 tiles subdivide them; groups of 64 segments are the second level of the counters.  Tail blocks: four consecutive segments
+// of one frame each (an empty frame still gets one, to write its summary) -- the list blocks, then, when boxes are counted, a box-count
+// block per list block, 64-box word of its frame and part (csplit parts: see lpf_tail_block).
+struct NarrowLayout {
+    int F = 0;
+    bool small = false;
+    int64_t seg_pts = 0;
+    int nseg_total = 0, ngrp_total = 0, max_ngrp = 0;
+    int nblk = 0;                     // list blocks
+    int nwblk = 0;                    // list blocks x 64-box words of their frame (at least one): box-count blocks per part
+    int csplit = 1, ncblk = 0;        // parts, box-count blocks
+    bool few = false;                 // a frame or two (see lpf_run_batch): the lists use the 16-row wave
+    bool pre_scan = false;            // segment prefixes from the scan kernel
+    int nseg_cap() const { return nseg_total > 0 ? nseg_total : 1; }
+    int ngrp_cap() const { return ngrp_total > 0 ? ngrp_total : 1; }
+    void split(int parts) { csplit = parts; ncblk = nwblk * parts; }
+};
+
+// the frame records of a narrow run (into c->h_frames) and its layout: F frames of frame_off, the boxes of BX, lists of inst_cap entries
+void narrow_layout(lpf_ctx *c, const int64_t *frame_off, int F, const lpf_ctx::BoxSet &BX, long long inst_cap, bool small, NarrowLayout &L)
+{
+    L = NarrowLayout();
+    L.F = F; L.small = small;
+    L.seg_pts = small ? LPF_SEG_SMALL : LPF_SEG_QUANTUM;
+    c->h_frames.resize(F);
+    for (int f = 0; f < F; ++f) {
+        LpfFrame &fr = c->h_frames[f];
+        fr.pt_off = frame_off[f];
+        fr.N = (int)(frame_off[f + 1] - frame_off[f]);
+        fr.seg_off = L.nseg_total;
+        fr.shift = (int)(frame_off[f] & 63);               // the frame's rows start at the 64-point boundary below its first point (LpfFrame)
+        fr.nseg = fr.N ? (int)((fr.N + fr.shift + L.seg_pts - 1) / L.seg_pts) : 0;
+        L.nseg_total += fr.nseg;
+        fr.box_off = BX.F ? BX.box_off[f] : 0;
+        fr.B = BX.F ? BX.box_off[f + 1] - BX.box_off[f] : 0;
+        fr.inst_base = (long long)f * inst_cap;
+        fr.pad = f;
+        fr.cand_off = BX.F ? BX.cand_off[f] : 0;
+        fr.cand_words = (fr.B + 63) / 64;
+        fr.grp_off = L.ngrp_total;
+        fr.pad4 = 0;
+        const int ngrp = (fr.nseg + LPF_GROUP_SEGS - 1) / LPF_GROUP_SEGS;
+        L.ngrp_total += ngrp;
+        L.max_ngrp = std::max(L.max_ngrp, ngrp);
+        const int nb = fr.nseg > 0 ? (fr.nseg + LPF_LISTS_WAVES - 1) / LPF_LISTS_WAVES : 1;
+        L.nblk += nb;
+        L.nwblk += nb * std::max(1, fr.cand_words);
+    }
+    L.few = small && L.nblk <= LPF_FEW_BLOCKS;
+    // a list wave sums one group's segments and the frame's groups, a lane each: frames of more than 64 groups (16.7 M points) take
+    // their prefixes from the scan kernel instead
+    L.pre_scan = L.max_ngrp > 64;
+    L.split(1);
+}
+
+// ballots and counters of a narrow run of layout L with M masks and Btot boxes in scratch set S
+int narrow_reserve(lpf_ctx *c, lpf_ctx::Scratch &S, const NarrowLayout &L, int M, int Btot)
+{
+    int rc;
+    const size_t rows = (size_t)L.nseg_cap() * (size_t)(L.seg_pts / 64);
+    if ((rc = reserve(c, S.vbal, rows * 8))) return rc;
+    if ((rc = reserve(c, S.mbal, rows * 8))) return rc;
+    if ((rc = reserve(c, S.seg_tab, (size_t)LPF_TAB_GROUPS * L.nseg_cap() * sizeof(uint4), true))) return rc;
+    if ((rc = reserve(c, S.grp_tab, (size_t)LPF_TAB_GROUPS * L.ngrp_cap() * sizeof(uint4), true))) return rc;
+    if ((rc = reserve(c, S.frm_tab, (size_t)L.F * LPF_FRM_SHARDS * LPF_TAB_GROUPS * sizeof(uint4), true))) return rc;
+    if (L.pre_scan && (rc = reserve(c, S.seg_pre, (size_t)LPF_TAB_GROUPS * L.nseg_cap() * sizeof(uint4)))) return rc;
+    if ((rc = reserve(c, S.cnt, (size_t)(M > 0 ? M : 1) * (Btot > 0 ? Btot : 1) * 4, true))) return rc;
+    return LPF_OK;
+}
+
+// The geometry tables of a narrow run of layout L in scratch set S: the frame records (c->h_frames), the owning frame's record per
+// segment, the list and box-count block tables.  A single frame needs none of them (record by value, block table computed).  They are
+// built from the frame records and csplit alone, which the set keeps as their key: only another key uploads them (unless `force`),
+// through the pinned ring -- no wait, no drain.
+int narrow_tables(lpf_ctx *c, lpf_ctx::Scratch &S, const NarrowLayout &L, bool force)
+{
+    const int F = L.F;
+    if (F <= 1) return LPF_OK;
+    const size_t b_frames = (size_t)F * sizeof(LpfFrame), b_segs = (size_t)L.nseg_total * sizeof(LpfFrame), b_blks = (size_t)L.nblk * sizeof(int2),
+                 b_cblks = (size_t)L.ncblk * sizeof(int4);
+    if (!force && S.tab_csplit == L.csplit && S.tab_frames.size() == (size_t)F && memcmp(S.tab_frames.data(), c->h_frames.data(), b_frames) == 0)
+        return LPF_OK;
+    int rc;
+    if ((rc = reserve(c, S.tab, b_frames + b_segs + b_blks + b_cblks))) return rc;
+    c->h_tab.resize(b_frames + b_segs + b_blks + b_cblks);
+    memcpy(c->h_tab.data(), c->h_frames.data(), b_frames);
+    LpfFrame *hs = reinterpret_cast<LpfFrame *>(c->h_tab.data() + b_frames);
+    int2 *hb = reinterpret_cast<int2 *>(c->h_tab.data() + b_frames + b_segs);
+    int4 *hc = reinterpret_cast<int4 *>(c->h_tab.data() + b_frames + b_segs + b_blks);
+    for (int f = 0; f < F; ++f) {
+        const LpfFrame &fr = c->h_frames[f];
+        const int wpg = std::max(1, fr.cand_words);
+        for (int sg = 0; sg < fr.nseg; ++sg) hs[(size_t)fr.seg_off + sg] = fr;
+        if (fr.nseg == 0) {
+            *hb++ = make_int2(fr.seg_off, f << 3);
+            for (int w = 0; w < wpg; ++w) for (int r = 0; r < L.csplit; ++r) *hc++ = make_int4(fr.seg_off, f, w, r << 3);
+        }
+        for (int sg = 0; sg < fr.nseg; sg += LPF_LISTS_WAVES) {
+            const int nw = std::min(LPF_LISTS_WAVES, fr.nseg - sg);
+            *hb++ = make_int2(fr.seg_off + sg, (f << 3) | nw);
+            for (int w = 0; w < wpg; ++w) for (int r = 0; r < L.csplit; ++r) *hc++ = make_int4(fr.seg_off + sg, f, w, (r << 3) | nw);
+        }
+    }
+    S.tab_frames.clear();                                  // (nothing valid if the upload fails half way)
+    if ((rc = upload(c, S.tab.p, c->h_tab.data(), c->h_tab.size()))) return rc;
+    S.tab_frames = c->h_frames;
+    S.tab_csplit = L.csplit;
+    S.o_segs = b_frames; S.o_blks = b_frames + b_segs; S.o_cblks = b_frames + b_segs + b_blks;
+    ++c->generation;                                       // graphs captured for another geometry read these tables
+    return LPF_OK;
+}
+
+// the parts of a narrow run's parameters that do not depend on its path: camera, shape, tables (narrow_tables), box tables, scratch
+// (narrow_reserve).  P is cleared first.
+void narrow_params(LpfParams &P, const lpf_ctx *c, const Cam &cam, const NarrowLayout &L, const lpf_ctx::Scratch &S, const lpf_ctx::BoxSet &BX,
+                   int M, long long inst_cap)
+{
+    memset(&P, 0, sizeof P);
+    set_cam(P, cam);
+    const int Btot = BX.F ? BX.box_off[L.F] : 0;
+    P.F = L.F; P.M = M; P.seg_pts = (int)L.seg_pts; P.nseg_total = L.nseg_total; P.nseg_cap = L.nseg_cap(); P.ngrp_cap = L.ngrp_cap();
+    P.oriented = BX.F ? BX.oriented : 1; P.inst_cap = inst_cap;
+    P.frame0 = c->h_frames[0];
+    if (L.F > 1) {
+        P.frames = (const LpfFrame *)S.tab.p;
+        P.segs = (const LpfFrame *)((const char *)S.tab.p + S.o_segs);
+        P.blks = (const int2 *)((const char *)S.tab.p + S.o_blks);
+        P.cblks = (const int4 *)((const char *)S.tab.p + S.o_cblks);
+    }
+    P.boxp = (const double *)BX.boxp.p; P.boxq = (const float *)BX.boxq.p;
+    P.cand = (const unsigned long long *)BX.cand.p;
+    P.vbal = (unsigned long long *)S.vbal.p; P.mbal = (unsigned long long *)S.mbal.p;
+    P.seg_tab = (uint4 *)S.seg_tab.p; P.grp_tab = (uint4 *)S.grp_tab.p; P.frm_tab = (uint4 *)S.frm_tab.p;
+    P.seg_pre = L.pre_scan ? (uint4 *)S.seg_pre.p : nullptr;
+    P.cnt = (unsigned *)S.cnt.p;
+    P.nblk = L.nblk; P.ncblk = L.ncblk; P.csplit = L.csplit; P.lists_small = L.few ? 1 : 0; P.count_boxes = (M > 0 && Btot > 0) ? 1 : 0;
+    P.count_lazy = L.small ? 0 : 1;
+}
+
+// Host outputs of a narrow run of n points, phase (a): the dense arrays are queued.  Then, with result buffers in page-locked memory
+// (lpf_host_alloc, hipHostMalloc), lpf_results_to_host writes the filled parts of the compact results and the summaries there, reading
+// the lengths from the summaries on the device -- one launch and ONE host wait, where the copy engine needs the summaries on the host
+// first (a wait), four copies per frame and a second wait.  Else the counts (nMB = M x Btot) are queued, and the summaries into hs[F]:
+// *lists says that the lists are still to be copied (phase b), once the caller has waited for hs.
+int narrow_back_a(lpf_ctx *c, const lpf_outputs &o, const LpfParams &P, size_t n, int nMB, lpf_frame_summary *hs, bool *lists)
+{
+#define LPF_D2H(member, field, bytes) \
+    if (o.member && (bytes)) LPF_HIP(c, hipMemcpyAsync(o.member, P.field, (bytes), hipMemcpyDeviceToHost, c->stream));
+    LPF_D2H(uv, uv, n * 8)
+    LPF_D2H(label_bits, label_bits, n * 4)
+    LPF_D2H(depth, depth, n * 8)
+    LPF_D2H(u_f, uf, n * 8)
+    LPF_D2H(v_f, vf, n * 8)
+    LpfToHost D;
+    memset(&D, 0, sizeof D);
+    bool r2h = o.summary != nullptr && (o.valid_idx || o.inst_idx);
+    auto alias = [&](void *host, void **dev) {
+        *dev = host ? device_alias_of_pinned(host) : nullptr;
+        if (host && !*dev) r2h = false;
+    };
+    if (r2h) {
+        alias(o.summary, &D.summary);
+        alias(o.valid_idx, (void **)&D.valid_idx);
+        alias(o.uv_valid, (void **)&D.uv_valid);
+        alias(o.label_valid, (void **)&D.label_valid);
+        alias(o.inst_idx, (void **)&D.inst_idx);
+        alias(o.count_mb, (void **)&D.count_mb);
+    }
+    if (r2h) {
+        D.inst_cap = o.inst_cap;
+        D.n_count = o.count_mb ? nMB : 0;
+        hipLaunchKernelGGL(lpf_results_to_host, dim3((unsigned)P.F * LPF_R2H_BLOCKS), dim3(LPF_BLOCK), 0, c->stream, P, D);
+        LPF_HIP(c, hipGetLastError());
+        *lists = false;
+        return LPF_OK;
+    }
+    LPF_D2H(count_mb, count_out, (size_t)nMB * 4)
+#undef LPF_D2H
+    LPF_HIP(c, hipMemcpyAsync(hs, P.summary, (size_t)P.F * sizeof(lpf_frame_summary), hipMemcpyDeviceToHost, c->stream));
+    *lists = true;
+    return LPF_OK;
+}
+
+// phase (b), after the caller's wait: the filled part of each frame's lists, by the summaries hs[F]; the summaries to the caller
+int narrow_back_b(lpf_ctx *c, const lpf_outputs &o, const LpfParams &P, const int64_t *frame_off, const lpf_frame_summary *hs)
+{
+    for (int f = 0; f < P.F; ++f) {
+        const size_t nv = (size_t)hs[f].n_valid;
+        if (o.valid_idx && nv)
+            LPF_HIP(c, hipMemcpyAsync(o.valid_idx + frame_off[f], P.valid_idx + frame_off[f], nv * 8, hipMemcpyDeviceToHost, c->stream));
+        if (o.uv_valid && nv)
+            LPF_HIP(c, hipMemcpyAsync(o.uv_valid + 2 * frame_off[f], P.uv_valid + frame_off[f], nv * 8, hipMemcpyDeviceToHost, c->stream));
+        if (o.label_valid && nv)
+            LPF_HIP(c, hipMemcpyAsync(o.label_valid + frame_off[f], P.label_valid + frame_off[f], nv * 4, hipMemcpyDeviceToHost, c->stream));
+        int64_t tot = hs[f].inst_off[LPF_MAX_MASKS];
+        if (tot > o.inst_cap) tot = o.inst_cap;
+        if (o.inst_idx && tot > 0)
+            LPF_HIP(c, hipMemcpyAsync(o.inst_idx + (size_t)f * o.inst_cap, P.inst_idx + (size_t)f * o.inst_cap, (size_t)tot * 8,
+                                      hipMemcpyDeviceToHost, c->stream));
+    }
+    if (o.summary) memcpy(o.summary, hs, (size_t)P.F * sizeof(lpf_frame_summary));
+    return LPF_OK;
+}
+
+// the frame table of a wide run into fr[F]: F frames of frame_off with the boxes of BX.  Returns the chunks; *nbw: the 64-box words of
+// the frame with the most boxes
+int wide_frames(const int64_t *frame_off, int F, const lpf_ctx::BoxSet &BX, LpfWideFrame *fr, int *nbw)
+{
+    int nchunk = 0, maxB = 0;
+    for (int f = 0; f < F; ++f) {
+        LpfWideFrame &e = fr[f];
+        e.pt_off = frame_off[f];
+        e.N = (int)(frame_off[f + 1] - frame_off[f]);
+        e.chunk_off = nchunk;
+        e.nchunk = (e.N + LPF_WIDE_CHUNK - 1) / LPF_WIDE_CHUNK;
+        e.box_off = BX.F ? BX.box_off[f] : 0;
+        e.B = BX.F ? BX.box_off[f + 1] - BX.box_off[f] : 0;
+        e.pad = 0;
+        nchunk += e.nchunk;
+        maxB = std::max(maxB, e.B);
+    }
+    *nbw = (maxB + 63) / 64;
+    return nchunk;
+}
+
+// the parts of a wide run's parameters that do not depend on its path: camera, shape, frame table (wide_frames), box tables.  W is
+// cleared first; the points, planes, outputs and scratch are the caller's (wide_pack, wide_bind)
+void wide_params(LpfWideParams &W, const Cam &cam, int F, int M, int nchunk, int nbw, const lpf_ctx::BoxSet &BX, long long inst_cap,
+                 const LpfWideFrame *frames)
+{
+    memset(&W, 0, sizeof W);
+    set_cam(W.cam, cam);
+    W.F = F; W.M = M; W.LW = (M + 31) / 32; W.nchunk = nchunk; W.nbw = nbw;
+    W.oriented = BX.F ? BX.oriented : 1; W.inst_cap = inst_cap;
+    W.frames = frames;
+    W.boxp = (const double *)BX.boxp.p; W.boxq = (const float *)BX.boxq.p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1147,13 +1460,9 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     if (use_device(c)) return LPF_ERR_HIP;
     if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera has not been called");
     if (!out || !frame_off || F <= 0) return fail(c, LPF_ERR_ARG, "run: out=%p frame_off=%p F=%d", (const void *)out, (const void *)frame_off, F);
-    if (frame_off[0] != 0) return fail(c, LPF_ERR_ARG, "run: frame_off[0] must be 0");
-    for (int f = 0; f < F; ++f) {
-        const int64_t n = frame_off[f + 1] - frame_off[f];
-        if (n < 0 || n > 0x7fffffffll - LPF_SEG_QUANTUM) return fail(c, LPF_ERR_ARG, "run: frame %d has %lld points", f, (long long)n);
-    }
+    int rc;
+    if ((rc = check_frames(c, "run", pts, frame_off, F, LPF_SEG_QUANTUM))) return rc;
     const int64_t Ntot = frame_off[F];
-    if (Ntot > 0 && !pts) return fail(c, LPF_ERR_ARG, "run: pts is NULL");
     lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
     if (c->mask_F != 0 && c->mask_F != F) return fail(c, LPF_ERR_STATE, "masks were set for %d frames, run has %d", c->mask_F, F);
     if (BX.F != 0 && BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, run has %d", BX.F, F);
@@ -1163,119 +1472,26 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     const int M = c->mask_F ? c->mask_M : 0;
     const int Btot = BX.F ? BX.box_off[F] : 0;
     const bool host_io = !out->on_device;
-    int rc;
 
-    // ---- segmentation: segments of 4096 points (1024 for small launches), one list wave each; K1 tiles subdivide them;
-    //      groups of 64 segments are the second level of the counters ------------------------------------------------
+    // ---- segmentation (NarrowLayout) ---------------------------------------------------------------------------------------------
     const bool small = c->geometry == 1 || c->geometry == 4 || c->geometry == 5 || (c->geometry == 0 && Ntot <= LPF_SMALL_LAUNCH);
-    const int64_t seg_pts = small ? LPF_SEG_SMALL : LPF_SEG_QUANTUM;
-    c->h_frames.resize(F);
-    int nseg_total = 0, ngrp_total = 0, max_ngrp = 0;
-    for (int f = 0; f < F; ++f) {
-        LpfFrame &fr = c->h_frames[f];
-        fr.pt_off = frame_off[f];
-        fr.N = (int)(frame_off[f + 1] - frame_off[f]);
-        fr.seg_off = nseg_total;
-        fr.shift = (int)(frame_off[f] & 63);               // the frame's rows start at the 64-point boundary below its first point (LpfFrame)
-        fr.nseg = fr.N ? (int)((fr.N + fr.shift + seg_pts - 1) / seg_pts) : 0;
-        nseg_total += fr.nseg;
-        fr.box_off = BX.F ? BX.box_off[f] : 0;
-        fr.B = BX.F ? BX.box_off[f + 1] - BX.box_off[f] : 0;
-        fr.inst_base = (long long)f * out->inst_cap;
-        fr.pad = f;
-        fr.cand_off = BX.F ? BX.cand_off[f] : 0;
-        fr.cand_words = (fr.B + 63) / 64;
-        fr.grp_off = ngrp_total;
-        fr.pad4 = 0;
-        const int ngrp = (fr.nseg + LPF_GROUP_SEGS - 1) / LPF_GROUP_SEGS;
-        ngrp_total += ngrp;
-        if (ngrp > max_ngrp) max_ngrp = ngrp;
-    }
-    const int nseg_cap = nseg_total > 0 ? nseg_total : 1, ngrp_cap = ngrp_total > 0 ? ngrp_total : 1;
-    // tail blocks: four consecutive segments of one frame each (an empty frame still gets one, to write its summary);
-    // the list blocks, then -- when boxes are to be counted -- as many box-count blocks
-    const bool count_boxes = M > 0 && Btot > 0;
-    // (fused is decided further down; the same condition here)
-    int nblk_early = 0;
-    for (int f = 0; f < F; ++f) nblk_early += c->h_frames[f].nseg > 0 ? (c->h_frames[f].nseg + LPF_LISTS_WAVES - 1) / LPF_LISTS_WAVES : 1;
+    NarrowLayout L;
+    narrow_layout(c, frame_off, F, BX, out->inst_cap, small, L);
+    // software-pipelined device runs rotate through the scratch sets (3 in mode 2, 4 in mode 4); everything else uses set 0 with
+    // nothing owed
+    const bool fused = c->fused && !host_io && pts_on_device && !c->capturing;   // one launch per run, the tail rides in the next
     // a frame or two of a real scan (up to 64 list blocks = 262 144 points): the launch is as long as its longest block, so the count
     // blocks are cut in four and the lists use the 16-row wave.  Beyond that both cost more than they save (same box, us per step in a
     // pipelined stream with / without: 20 real frames 29.8 / 25.5 with the cut, 25.2 / 25.5 with the list wave; one 2 M-point
     // synthetic cloud 25.7 / 21.3 and 22.9 / 21.3, in order 42.4 / 38.9 with the list wave).
-    const bool few = small && nblk_early <= LPF_FEW_BLOCKS;
-    const int csplit = (c->fused && !host_io && pts_on_device && !c->capturing && few) ? 4 : 1;     // count blocks per (group, word): see lpf_tail_block
-    int nblk = 0, ncblk = 0;                               // list blocks; box-count blocks: one per group of segments, 64-box word and part
-    for (int f = 0; f < F; ++f) {
-        const int nb = c->h_frames[f].nseg > 0 ? (c->h_frames[f].nseg + LPF_LISTS_WAVES - 1) / LPF_LISTS_WAVES : 1;
-        nblk += nb;
-        ncblk += nb * std::max(1, c->h_frames[f].cand_words) * csplit;
-    }
-    const size_t rows = (size_t)nseg_cap * (size_t)(seg_pts / 64);
-    // a list wave sums one group's segments and the frame's groups, a lane each: frames of more than 64 groups
-    // (16.7 M points) take their prefixes from the scan kernel instead
-    const bool pre_scan = max_ngrp > 64 || c->geometry == 3;
-
-    // software-pipelined device runs rotate through the scratch sets (3 in mode 2, 4 in mode 4); everything else uses set 0 with
-    // nothing owed
-    const bool fused = c->fused && !host_io && pts_on_device && !c->capturing;   // one launch per run, the tail rides in the next
+    L.split(fused && L.few ? 4 : 1);
+    if (c->geometry == 3) L.pre_scan = true;
     if (!fused && anything_owed(c) && (rc = sync_all(c))) return rc;
     lpf_ctx::Scratch &S = c->sc[fused ? c->parity : 0];
-    if ((rc = reserve(c, S.vbal, rows * 8))) return rc;
-    if ((rc = reserve(c, S.mbal, rows * 8))) return rc;
-    if ((rc = reserve(c, S.seg_tab, (size_t)LPF_TAB_GROUPS * nseg_cap * sizeof(uint4), true))) return rc;
-    if ((rc = reserve(c, S.grp_tab, (size_t)LPF_TAB_GROUPS * ngrp_cap * sizeof(uint4), true))) return rc;
-    if ((rc = reserve(c, S.frm_tab, (size_t)F * LPF_FRM_SHARDS * LPF_TAB_GROUPS * sizeof(uint4), true))) return rc;
-    if (pre_scan && (rc = reserve(c, S.seg_pre, (size_t)LPF_TAB_GROUPS * nseg_cap * sizeof(uint4)))) return rc;
-    if ((rc = reserve(c, S.cnt, (size_t)(M > 0 ? M : 1) * (Btot > 0 ? Btot : 1) * 4, true))) return rc;
-
-    // ---- geometry tables of the run, in its own scratch set: the frame records, the owning frame's record per segment, the
-    //      tail block table.  A single frame needs none of them (record by value, block table computed).  They only change
-    //      when the batch shape does, and then travel through the pinned ring: no wait, no drain ---------------------------
-    const bool have_tab = S.tab_frames.size() == (size_t)F && memcmp(S.tab_frames.data(), c->h_frames.data(), (size_t)F * sizeof(LpfFrame)) == 0;
-    if (F > 1 && !have_tab) {
-        const size_t b_frames = (size_t)F * sizeof(LpfFrame), b_segs = (size_t)nseg_total * sizeof(LpfFrame), b_blks = (size_t)nblk * sizeof(int2),
-                     b_cblks = (size_t)ncblk * sizeof(int4);
-        if ((rc = reserve(c, S.tab, b_frames + b_segs + b_blks + b_cblks))) return rc;
-        c->h_tab.resize(b_frames + b_segs + b_blks + b_cblks);
-        memcpy(c->h_tab.data(), c->h_frames.data(), b_frames);
-        LpfFrame *hs = reinterpret_cast<LpfFrame *>(c->h_tab.data() + b_frames);
-        int2 *hb = reinterpret_cast<int2 *>(c->h_tab.data() + b_frames + b_segs);
-        int4 *hc = reinterpret_cast<int4 *>(c->h_tab.data() + b_frames + b_segs + b_blks);
-        for (int f = 0; f < F; ++f) {
-            const LpfFrame &fr = c->h_frames[f];
-            const int wpg = std::max(1, fr.cand_words);
-            for (int sg = 0; sg < fr.nseg; ++sg) hs[(size_t)fr.seg_off + sg] = fr;
-            if (fr.nseg == 0) {
-                *hb++ = make_int2(fr.seg_off, f << 3);
-                for (int w = 0; w < wpg; ++w) for (int r = 0; r < csplit; ++r) *hc++ = make_int4(fr.seg_off, f, w, r << 3);
-            }
-            for (int sg = 0; sg < fr.nseg; sg += LPF_LISTS_WAVES) {
-                const int nw = std::min(LPF_LISTS_WAVES, fr.nseg - sg);
-                *hb++ = make_int2(fr.seg_off + sg, (f << 3) | nw);
-                for (int w = 0; w < wpg; ++w) for (int r = 0; r < csplit; ++r) *hc++ = make_int4(fr.seg_off + sg, f, w, (r << 3) | nw);
-            }
-        }
-        S.tab_frames.clear();                              // (nothing valid if the upload fails half way)
-        if ((rc = upload(c, S.tab.p, c->h_tab.data(), c->h_tab.size()))) return rc;
-        S.tab_frames = c->h_frames;
-        S.o_segs = b_frames; S.o_blks = b_frames + b_segs; S.o_cblks = b_frames + b_segs + b_blks;
-        ++c->generation;                  // graphs captured for another geometry read these tables
-    }
-
+    if ((rc = narrow_reserve(c, S, L, M, Btot))) return rc;
+    if ((rc = narrow_tables(c, S, L, false))) return rc;
     LpfParams P;
-    memset(&P, 0, sizeof P);
-    memcpy(P.T, c->T, sizeof P.T);
-    memcpy(P.K, c->K, sizeof P.K);
-    P.dmin = c->dmin; P.dmax = c->dmax; P.W = c->W; P.H = c->H;
-    P.F = F; P.M = M; P.seg_pts = (int)seg_pts; P.nseg_total = nseg_total; P.nseg_cap = nseg_cap; P.ngrp_cap = ngrp_cap;
-    P.oriented = BX.oriented; P.inst_cap = out->inst_cap;
-    P.frame0 = c->h_frames[0];
-    if (F > 1) {
-        P.frames = (const LpfFrame *)S.tab.p;
-        P.segs = (const LpfFrame *)((const char *)S.tab.p + S.o_segs);
-        P.blks = (const int2 *)((const char *)S.tab.p + S.o_blks);
-        P.cblks = (const int4 *)((const char *)S.tab.p + S.o_cblks);
-    }
+    narrow_params(P, c, ctx_cam(c), L, S, BX, M, out->inst_cap);
     // lent masks of a pipelined context (lpf_ctx::Ride): a small fused launch reads them directly, a large one in mode 4 carries
     // their pack, anything else (mode 2, float masks, a host-memory run) packs them now
     // (directly: M gathers per valid point against M reads per pixel for the pack -- it pays while a frame has fewer points than
@@ -1321,14 +1537,6 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
         P.rect_grid = RG.grid; P.rg_cw = RG.cw; P.rg_cells = RG.cells;
     }
     if (M > 0 && !P.label_img) return fail(c, LPF_ERR_STATE, "no masks for this run's scratch set: in the pipelined modes the label images rotate with the scratch sets -- call lpf_set_masks_* before every lpf_run* (and after switching modes)");
-    P.boxp = (const double *)BX.boxp.p; P.boxq = (const float *)BX.boxq.p;
-    P.cand = (const unsigned long long *)BX.cand.p;
-    P.vbal = (unsigned long long *)S.vbal.p; P.mbal = (unsigned long long *)S.mbal.p;
-    P.seg_tab = (uint4 *)S.seg_tab.p; P.grp_tab = (uint4 *)S.grp_tab.p; P.frm_tab = (uint4 *)S.frm_tab.p;
-    P.seg_pre = pre_scan ? (uint4 *)S.seg_pre.p : nullptr;
-    P.cnt = (unsigned *)S.cnt.p;
-    P.nblk = nblk; P.ncblk = ncblk; P.csplit = csplit; P.lists_small = few ? 1 : 0; P.count_boxes = count_boxes ? 1 : 0;
-    P.count_lazy = small ? 0 : 1;
 
     // ---- buffers: caller's HBM pointers, or internal staging for host callers -----------
     const size_t n = (size_t)Ntot;
@@ -1392,10 +1600,10 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     // the fused launch shares the chip with the previous run's tail blocks: 2048-point tiles keep twice the loads in flight
     // per wave, so the streaming work holds its bandwidth on fewer resident blocks (measured: 104.9 vs 108.8 us per step)
     if (fused && !small) P.tile_pts = direct_rect_fused ? LPF_RECT_FUSED_TILE : 2048;
-    const int nk1 = nseg_total * (int)(seg_pts / P.tile_pts);
+    const int nk1 = L.nseg_total * (int)(L.seg_pts / P.tile_pts);
     const int lb = (M > 0) ? SM.label_bytes : 4;
     const bool want_lists = out->valid_idx || out->inst_idx;
-    const int ntail = (count_boxes ? ncblk : 0) + (want_lists ? nblk : 0);        // no lists wanted and no boxes: no tail blocks at all
+    const int ntail = (P.count_boxes ? L.ncblk : 0) + (want_lists ? L.nblk : 0);        // no lists wanted and no boxes: no tail blocks at all
     hipEvent_t e0 = nullptr, e1 = nullptr;
     // mode 4: the mask pack and the tiles of one launch share the label element type -- else the pipeline is drained first
     if (fused && c->defer && c->pend_k1.valid && ride_pack && (c->pend_k1.direct || c->pend_k1.lb != lb) && (rc = flush_pending(c))) return rc;
@@ -1424,7 +1632,7 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
         //      Mode 2: the tiles are this run's.  Mode 4: this run's MASK PACK rides as well (lent uint8 masks), the tiles are
         //      the previous run's -- everything one launch later, nothing left on the stream between two steps.
         lpf_ctx::Pending cur;
-        cur.valid = true; cur.P = P; cur.pre = pre_scan; cur.ntail = ntail; cur.nk1 = nk1; cur.lb = lb; cur.small = small;
+        cur.valid = true; cur.P = P; cur.pre = L.pre_scan; cur.ntail = ntail; cur.nk1 = nk1; cur.lb = lb; cur.small = small;
         cur.direct = direct_fused; cur.dsel = direct_rect_fused ? (c->ride.f32 ? 5 : 4) : c->ride.f32 ? c->ride.mode : 0;
         const lpf_ctx::Pending KK = c->defer ? c->pend_k1 : cur, Q = c->pend_tail, R = c->pend_fin;
         if ((rc = launch_step(c, KK, Q, R, ride_pack, lb, &BX, e1, (rect_tiles && c->defer) ? &RG : nullptr))) return rc;
@@ -1465,16 +1673,16 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     }
     }
     // ---- the tail: lists and box counts in one launch (a wave per segment each, side by side), then the per-frame summaries ----
-    if (pre_scan && nseg_total > 0) {
+    if (L.pre_scan && L.nseg_total > 0) {
         hipLaunchKernelGGL(lpf_scan_segments, dim3(F), dim3(LPF_BLOCK), 0, c->stream, P);
         LPF_HIP(c, hipGetLastError());
     }
     if (ntail > 0) {
-        if (small && count_boxes && c->geometry != 4 && (nblk <= LPF_WIDE_BELOW || c->geometry == 1)) {   // a frame or a few, dense real segments: the box-count blocks share their chunks over 16 waves
-            if (pre_scan) hipLaunchKernelGGL((lpf_tail_wide_t<true>), dim3((unsigned)ntail), dim3(64 * LPF_WIDE_WAVES), 0, c->stream, P);
+        if (small && P.count_boxes && c->geometry != 4 && (L.nblk <= LPF_WIDE_BELOW || c->geometry == 1)) {   // a frame or a few, dense real segments: the box-count blocks share their chunks over 16 waves
+            if (L.pre_scan) hipLaunchKernelGGL((lpf_tail_wide_t<true>), dim3((unsigned)ntail), dim3(64 * LPF_WIDE_WAVES), 0, c->stream, P);
             else hipLaunchKernelGGL((lpf_tail_wide_t<false>), dim3((unsigned)ntail), dim3(64 * LPF_WIDE_WAVES), 0, c->stream, P);
         } else {
-            launch_tail(c->stream, P, ntail, pre_scan);
+            launch_tail(c->stream, P, ntail, L.pre_scan);
         }
         LPF_HIP(c, hipGetLastError());
     }
@@ -1482,66 +1690,14 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     LPF_HIP(c, hipGetLastError());
 
     if (host_io) {
-#define LPF_D2H(member, field, bytes) \
-    if (out->member && (bytes)) LPF_HIP(c, hipMemcpyAsync(out->member, P.field, (bytes), hipMemcpyDeviceToHost, c->stream));
-        LPF_D2H(uv, uv, n * 8)
-        LPF_D2H(label_bits, label_bits, n * 4)
-        LPF_D2H(depth, depth, n * 8)
-        LPF_D2H(u_f, uf, n * 8)
-        LPF_D2H(v_f, vf, n * 8)
-        // Result buffers in page-locked memory (lpf_host_alloc, hipHostMalloc): the filled parts of the compact results are written
-        // there by a kernel that reads the lengths from the summaries on the device -- one launch and ONE host wait, where the copy
-        // engine needs the summaries on the host first (a wait), four copies per frame and a second wait.
-        {
-            LpfToHost D;
-            memset(&D, 0, sizeof D);
-            bool r2h = out->summary != nullptr && (out->valid_idx || out->inst_idx);
-            auto alias = [&](void *host, void **dev) {
-                *dev = host ? device_alias_of_pinned(host) : nullptr;
-                if (host && !*dev) r2h = false;
-            };
-            if (r2h) {
-                alias(out->summary, &D.summary);
-                alias(out->valid_idx, (void **)&D.valid_idx);
-                alias(out->uv_valid, (void **)&D.uv_valid);
-                alias(out->label_valid, (void **)&D.label_valid);
-                alias(out->inst_idx, (void **)&D.inst_idx);
-                alias(out->count_mb, (void **)&D.count_mb);
-            }
-            if (r2h) {
-                D.inst_cap = out->inst_cap;
-                D.n_count = out->count_mb ? M * Btot : 0;
-                hipLaunchKernelGGL(lpf_results_to_host, dim3((unsigned)F * LPF_R2H_BLOCKS), dim3(LPF_BLOCK), 0, c->stream, P, D);
-                LPF_HIP(c, hipGetLastError());
-                LPF_HIP(c, host_wait(c));
-                return LPF_OK;
-            }
-        }
-        LPF_D2H(count_mb, count_out, (size_t)M * Btot * 4)
-        // lists: fetch the summary first, then only the filled part of each list
         std::vector<lpf_frame_summary> hs((size_t)F);
-        LPF_HIP(c, hipMemcpyAsync(hs.data(), P.summary, (size_t)F * sizeof(lpf_frame_summary), hipMemcpyDeviceToHost, c->stream));
+        bool lists = false;
+        if ((rc = narrow_back_a(c, *out, P, n, M * Btot, hs.data(), &lists))) return rc;
         LPF_HIP(c, host_wait(c));
-        for (int f = 0; f < F; ++f) {
-            const size_t nv = (size_t)hs[f].n_valid;
-            if (out->valid_idx && nv)
-                LPF_HIP(c, hipMemcpyAsync(out->valid_idx + frame_off[f], P.valid_idx + frame_off[f], nv * 8,
-                                          hipMemcpyDeviceToHost, c->stream));
-            if (out->uv_valid && nv)
-                LPF_HIP(c, hipMemcpyAsync(out->uv_valid + 2 * frame_off[f], P.uv_valid + frame_off[f], nv * 8,
-                                          hipMemcpyDeviceToHost, c->stream));
-            if (out->label_valid && nv)
-                LPF_HIP(c, hipMemcpyAsync(out->label_valid + frame_off[f], P.label_valid + frame_off[f], nv * 4,
-                                          hipMemcpyDeviceToHost, c->stream));
-            int64_t tot = hs[f].inst_off[LPF_MAX_MASKS];
-            if (tot > out->inst_cap) tot = out->inst_cap;
-            if (out->inst_idx && tot > 0)
-                LPF_HIP(c, hipMemcpyAsync(out->inst_idx + (size_t)f * out->inst_cap, P.inst_idx + (size_t)f * out->inst_cap,
-                                          (size_t)tot * 8, hipMemcpyDeviceToHost, c->stream));
+        if (lists) {
+            if ((rc = narrow_back_b(c, *out, P, frame_off, hs.data()))) return rc;
+            LPF_HIP(c, host_wait(c));
         }
-        if (out->summary) memcpy(out->summary, hs.data(), (size_t)F * sizeof(lpf_frame_summary));
-#undef LPF_D2H
-        LPF_HIP(c, host_wait(c));
     }
     return LPF_OK;
 }
@@ -1720,8 +1876,8 @@ int lpf_depth_image(lpf_ctx *c, const float *pts, int64_t N, int on_device, doub
     if (N > 0) {
         LpfParams P;
         memset(&P, 0, sizeof P);
-        memcpy(P.T, c->T, sizeof P.T); memcpy(P.K, c->K, sizeof P.K);
-        P.dmin = c->dmin; P.dmax = c->dmax; P.W = c->W; P.H = c->H; P.pts = (const float4 *)dP;
+        set_cam(P, ctx_cam(c));
+        P.pts = (const float4 *)dP;
         const dim3 g((unsigned)((N + LPF_BLOCK - 1) / LPF_BLOCK));
         hipLaunchKernelGGL((lpf_depth_image_kernel<0>), g, dim3(LPF_BLOCK), 0, c->stream, P, (int)N, dW, dD);
         hipLaunchKernelGGL((lpf_depth_image_kernel<1>), g, dim3(LPF_BLOCK), 0, c->stream, P, (int)N, dW, dD);
@@ -1949,27 +2105,12 @@ static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int
     int rc;
     const int M = in->M, LW = (M + 31) / 32;
     const size_t hw = (size_t)Wimg * Himg;
-    const size_t esz = in->f32 ? 4 : 1;
-    const void *d_masks = in->masks;
-    const int32_t *d_rects = in->rects;
     W.planes = nullptr;
-    if (M > 0 && !in->on_device) {
-        const size_t bytes = (size_t)F * M * hw * esz;
-        if ((rc = reserve(c, D.masks, bytes))) return rc;
-        LPF_HIP(c, hipMemcpyAsync(D.masks.p, in->masks, bytes, hipMemcpyHostToDevice, c->stream));
-        d_masks = D.masks.p;
-        if (in->rects) {
-            if ((rc = reserve(c, D.rects, (size_t)F * M * 16))) return rc;
-            LPF_HIP(c, hipMemcpyAsync(D.rects.p, in->rects, (size_t)F * M * 16, hipMemcpyHostToDevice, c->stream));
-            d_rects = (const int32_t *)D.rects.p;
-        }
-        *host_in = true;
-    }
-    // (the rectangles hold where lpf_set_mask_rects takes them: uint8, or float under binarize 0, without erosion)
-    const int4 *rects = (in->rects && in->erode_iters == 0 && (!in->f32 || in->binarize == 0)) ? (const int4 *)d_rects : nullptr;
-
-    // ---- pack (+ erosion) into LW planes --------------------------------------------------------------------------------------
     if (M > 0) {
+        const void *d_masks = nullptr;
+        const int4 *rects = nullptr;
+        if ((rc = stage_masks(c, *in, F, hw, D.masks, D.rects, &d_masks, &rects, host_in))) return rc;
+        // ---- pack (+ erosion) into LW planes ----------------------------------------------------------------------------------
         if ((rc = reserve(c, D.planes_a, (size_t)F * LW * hw * 4))) return rc;
         uint32_t *cur = (uint32_t *)D.planes_a.p;
         const dim3 grid((Wimg + LPF_TW - 1) / LPF_TW, (Himg + LPF_TH - 1) / LPF_TH, (unsigned)(F * LW));
@@ -2086,21 +2227,13 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera has not been called");
     if (!in || !out || !frame_off || F <= 0) return fail(c, LPF_ERR_ARG, "run_wide: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
     const int M = in->M;
-    if (M < 0 || M > LPF_MAX_MASKS_WIDE)
-        return fail(c, LPF_ERR_ARG, "run_wide: M=%d masks per frame, lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE = %d", M, LPF_MAX_MASKS_WIDE);
-    if (in->erode_iters < 0 || (in->f32 && (in->binarize < 0 || in->binarize > 2)) || (M > 0 && !in->masks))
-        return fail(c, LPF_ERR_ARG, "run_wide: erode_iters=%d f32=%d binarize=%d masks=%p", in->erode_iters, in->f32, in->binarize, in->masks);
-    if (frame_off[0] != 0) return fail(c, LPF_ERR_ARG, "run_wide: frame_off[0] must be 0");
-    for (int f = 0; f < F; ++f) {
-        const int64_t n = frame_off[f + 1] - frame_off[f];
-        if (n < 0 || n > 0x7fffffffll - LPF_WIDE_CHUNK) return fail(c, LPF_ERR_ARG, "run_wide: frame %d has %lld points", f, (long long)n);
-    }
+    int rc;
+    if ((rc = check_wide_input(c, "run_wide", -1, *in, LPF_MAX_MASKS_WIDE, "lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE", ""))) return rc;
+    if ((rc = check_frames(c, "run_wide", pts, frame_off, F, LPF_WIDE_CHUNK))) return rc;
     const int64_t Ntot = frame_off[F];
-    if (Ntot > 0 && !pts) return fail(c, LPF_ERR_ARG, "run_wide: pts is NULL");
     if (out->inst_idx && out->inst_cap <= 0) return fail(c, LPF_ERR_ARG, "run_wide: inst_idx given with inst_cap=%lld", (long long)out->inst_cap);
     lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
     if (BX.F != 0 && BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, run_wide has %d", BX.F, F);
-    int rc;
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
     if (BX.F && c->cand_dirty && !BX.job_valid) box_rebuild_job(BX);
@@ -2117,30 +2250,13 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
 
     // frame table
     std::vector<LpfWideFrame> fr((size_t)F);
-    int nchunk = 0, maxB = 0;
-    for (int f = 0; f < F; ++f) {
-        fr[f].pt_off = frame_off[f];
-        fr[f].N = (int)(frame_off[f + 1] - frame_off[f]);
-        fr[f].chunk_off = nchunk;
-        fr[f].nchunk = (fr[f].N + LPF_WIDE_CHUNK - 1) / LPF_WIDE_CHUNK;
-        fr[f].box_off = BX.F ? BX.box_off[f] : 0;
-        fr[f].B = BX.F ? BX.box_off[f + 1] - BX.box_off[f] : 0;
-        fr[f].pad = 0;
-        nchunk += fr[f].nchunk;
-        maxB = std::max(maxB, fr[f].B);
-    }
+    int nbw = 0;
+    const int nchunk = wide_frames(frame_off, F, BX, fr.data(), &nbw);
     if ((rc = reserve(c, D.tab, (size_t)F * sizeof(LpfWideFrame)))) return rc;
     if ((rc = upload(c, D.tab.p, fr.data(), (size_t)F * sizeof(LpfWideFrame)))) return rc;
 
     LpfWideParams W;
-    memset(&W, 0, sizeof W);
-    memcpy(W.cam.T, c->T, sizeof W.cam.T);
-    memcpy(W.cam.K, c->K, sizeof W.cam.K);
-    W.cam.dmin = c->dmin; W.cam.dmax = c->dmax; W.cam.W = c->W; W.cam.H = c->H;
-    W.F = F; W.M = M; W.LW = LW; W.nchunk = nchunk; W.nbw = (maxB + 63) / 64;
-    W.oriented = BX.oriented; W.inst_cap = out->inst_cap;
-    W.frames = (const LpfWideFrame *)D.tab.p;
-    W.boxp = (const double *)BX.boxp.p; W.boxq = (const float *)BX.boxq.p;
+    wide_params(W, ctx_cam(c), F, M, nchunk, nbw, BX, out->inst_cap, (const LpfWideFrame *)D.tab.p);
 
     // inputs: points, masks (host masks are staged; device masks are lent), rectangles
     if (pts_on_device || n == 0) {
@@ -2230,24 +2346,16 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     if (!in || !out || F < 0 || (F > 0 && !frame_off))
         return fail(c, LPF_ERR_ARG, "depth_maps: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
     const int M = in->M;
-    if (M < 0 || M > LPF_MAX_MASKS_WIDE)
-        return fail(c, LPF_ERR_ARG, "depth_maps: M=%d masks per frame, lpf_depth_maps takes 0 .. LPF_MAX_MASKS_WIDE = %d", M, LPF_MAX_MASKS_WIDE);
-    if (in->erode_iters < 0 || (in->f32 && (in->binarize < 0 || in->binarize > 2)) || (M > 0 && !in->masks))
-        return fail(c, LPF_ERR_ARG, "depth_maps: erode_iters=%d f32=%d binarize=%d masks=%p", in->erode_iters, in->f32, in->binarize, in->masks);
+    int rc;
+    if ((rc = check_wide_input(c, "depth_maps", -1, *in, LPF_MAX_MASKS_WIDE, "lpf_depth_maps takes 0 .. LPF_MAX_MASKS_WIDE", ""))) return rc;
     if (out->cap < 0 || !out->car_off || !out->need || (out->cap > 0 && !out->pix))
         return fail(c, LPF_ERR_ARG, "depth_maps: cap=%lld pix=%p car_off=%p need=%p (car_off and need are required, pix with cap > 0)",
                     (long long)out->cap, (void *)out->pix, (void *)out->car_off, (void *)out->need);
     if (F == 0) return LPF_OK;
-    if (frame_off[0] != 0) return fail(c, LPF_ERR_ARG, "depth_maps: frame_off[0] must be 0");
+    if ((rc = check_frames(c, "depth_maps", pts, frame_off, F, LPF_BLOCK))) return rc;
     long long maxN = 0;
-    for (int f = 0; f < F; ++f) {
-        const int64_t n = frame_off[f + 1] - frame_off[f];
-        if (n < 0 || n > 0x7fffffffll - LPF_BLOCK) return fail(c, LPF_ERR_ARG, "depth_maps: frame %d has %lld points", f, (long long)n);
-        maxN = std::max(maxN, (long long)n);
-    }
+    for (int f = 0; f < F; ++f) maxN = std::max(maxN, (long long)(frame_off[f + 1] - frame_off[f]));
     const int64_t Ntot = frame_off[F];
-    if (Ntot > 0 && !pts) return fail(c, LPF_ERR_ARG, "depth_maps: pts is NULL");
-    int rc;
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
 
@@ -2257,8 +2365,7 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     const size_t hwp = (size_t)ntile * LPF_DM_TILE;
     const bool planes = M > 0 && in->erode_iters > 0;
     const bool host_masks = M > 0 && !in->on_device, host_pts = Ntot > 0 && !pts_on_device, host_io = !out->on_device;
-    // (the rectangles hold where lpf_set_mask_rects takes them: uint8, or float under binarize 0, without erosion -- wide_pack's rule)
-    const bool use_rects = in->rects && M > 0 && in->erode_iters == 0 && (!in->f32 || in->binarize == 0);
+    const bool use_rects = M > 0 && rects_hold(*in);
     const size_t per_frame = hwp * 4 + (size_t)M * ntile * 12 + (planes ? (size_t)LW * hw * 4 * (in->erode_iters > 1 ? 2 : 1) : 0) +
                              (host_masks ? (size_t)M * (hw * esz + 16) : 0) + (host_pts ? (size_t)maxN * 16 : 0);
     const int Fc = (int)std::max<size_t>(1, std::min<size_t>((size_t)F, LPF_DM_BUDGET / per_frame));
@@ -2289,9 +2396,7 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
 
     LpfDmParams P;
     memset(&P, 0, sizeof P);
-    memcpy(P.cam.T, c->T, sizeof P.cam.T);
-    memcpy(P.cam.K, c->K, sizeof P.cam.K);
-    P.cam.dmin = c->dmin; P.cam.dmax = c->dmax; P.cam.W = c->W; P.cam.H = c->H;
+    set_cam(P.cam, ctx_cam(c));
     P.M = M; P.LW = LW; P.ntile = ntile; P.hwp = (long long)hwp; P.cap = out->cap;
     P.foff = (const long long *)D.foff.p;
     P.win = (unsigned *)D.win.p;
@@ -2379,31 +2484,22 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
 
 // ---- lpf_run_cams (include/lpf.h): one scan in up to LPF_MAX_CAMS cameras, kernels in lpf_cams.hip.h ------------------------------
 // The checks lpf_run_cams and lpf_run_cams_wide share (who: the call's name; frames of up to 0x7fffffff - slack points; 0 .. max_M masks
-// per camera, max_name: the limit's name in the header, m_more: what the message adds for a camera with more).  Refuses graph capture.
+// per camera, takes / more: what the message says about the limit, check_wide_input).  Refuses graph capture.
 static int cams_check(lpf_ctx *c, const char *who, const float *pts, const int64_t *frame_off, int F, const lpf_cam_input *cams, int C,
-                      const void *out, int64_t slack, int max_M, const char *max_name, const char *m_more)
+                      const void *out, int64_t slack, int max_M, const char *takes, const char *more)
 {
     const char *w = who + 4;                               // "run_cams..." in the messages
     if (c->capturing) return fail(c, LPF_ERR_STATE, "%s cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)", who);
     if (C < 1 || C > LPF_MAX_CAMS) return fail(c, LPF_ERR_ARG, "%s: C=%d cameras, a pass takes 1 .. LPF_MAX_CAMS = %d", w, C, LPF_MAX_CAMS);
     if (!cams || !out || !frame_off || F <= 0)
         return fail(c, LPF_ERR_ARG, "%s: cams=%p out=%p frame_off=%p F=%d", w, (const void *)cams, out, (const void *)frame_off, F);
-    if (frame_off[0] != 0) return fail(c, LPF_ERR_ARG, "%s: frame_off[0] must be 0", w);
-    for (int f = 0; f < F; ++f) {
-        const int64_t n = frame_off[f + 1] - frame_off[f];
-        if (n < 0 || n > 0x7fffffffll - slack) return fail(c, LPF_ERR_ARG, "%s: frame %d has %lld points", w, f, (long long)n);
-    }
-    if (frame_off[F] > 0 && !pts) return fail(c, LPF_ERR_ARG, "%s: pts is NULL", w);
+    int rc;
+    if ((rc = check_frames(c, w, pts, frame_off, F, slack))) return rc;
     for (int k = 0; k < C; ++k) {
         const lpf_cam_input &I = cams[k];
-        const lpf_wide_input &m = I.masks;
         if (I.W <= 0 || I.H <= 0 || (long long)I.W * I.H > (1ll << 30))
             return fail(c, LPF_ERR_ARG, "%s: camera %d is %d x %d", w, k, I.W, I.H);
-        if (m.M < 0 || m.M > max_M)
-            return fail(c, LPF_ERR_ARG, "%s: camera %d has M=%d masks per frame, a pass takes 0 .. %s = %d per camera%s", w, k, m.M, max_name,
-                        max_M, m_more);
-        if (m.erode_iters < 0 || (m.f32 && (m.binarize < 0 || m.binarize > 2)) || (m.M > 0 && !m.masks))
-            return fail(c, LPF_ERR_ARG, "%s: camera %d: erode_iters=%d f32=%d binarize=%d masks=%p", w, k, m.erode_iters, m.f32, m.binarize, m.masks);
+        if ((rc = check_wide_input(c, w, k, I.masks, max_M, takes, more))) return rc;
         if (I.corners_velo) {
             if (!I.box_off || I.box_off[0] != 0) return fail(c, LPF_ERR_ARG, "%s: camera %d: box_off must be given and start at 0", w, k);
             for (int f = 0; f < F; ++f)
@@ -2457,8 +2553,8 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
     if (!c) return LPF_ERR_ARG;
     if (use_device(c)) return LPF_ERR_HIP;
     int rc;
-    if ((rc = cams_check(c, "lpf_run_cams", pts, frame_off, F, cams, C, out, LPF_SEG_QUANTUM, LPF_MAX_MASKS, "LPF_MAX_MASKS",
-                         " (more: lpf_run_wide for that camera)")))
+    if ((rc = cams_check(c, "lpf_run_cams", pts, frame_off, F, cams, C, out, LPF_SEG_QUANTUM, LPF_MAX_MASKS, "a pass takes 0 .. LPF_MAX_MASKS",
+                         " per camera (more: lpf_run_wide for that camera)")))
         return rc;
     const int64_t Ntot = frame_off[F];
     for (int k = 0; k < C; ++k) {
@@ -2489,23 +2585,11 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         if ((rc = cams_box_tables(c, I, k, F))) return rc;
         const lpf_wide_input &m = I.masks;
         if (m.M == 0) continue;
-        const size_t hw = (size_t)I.W * I.H, esz = m.f32 ? 4 : 1;
-        const void *d_masks = m.masks;
-        const int32_t *d_rects = m.rects;
-        if (!m.on_device) {
-            const size_t bytes = (size_t)F * m.M * hw * esz;
-            if ((rc = reserve(c, c->cams.masks[k], bytes))) return rc;
-            LPF_HIP(c, hipMemcpyAsync(c->cams.masks[k].p, m.masks, bytes, hipMemcpyHostToDevice, c->stream));
-            d_masks = c->cams.masks[k].p;
-            if (m.rects) {
-                if ((rc = reserve(c, c->cams.rects[k], (size_t)F * m.M * 16))) return rc;
-                LPF_HIP(c, hipMemcpyAsync(c->cams.rects[k].p, m.rects, (size_t)F * m.M * 16, hipMemcpyHostToDevice, c->stream));
-                d_rects = (const int32_t *)c->cams.rects[k].p;
-            }
-            host_in = true;
-        }
-        // (the rectangles hold where lpf_set_masks_* takes them: uint8, or float32 under binarize 0, without erosion, W >= 16)
-        const int4 *rects = (m.rects && m.erode_iters == 0 && (!m.f32 || m.binarize == 0) && I.W >= 16) ? (const int4 *)d_rects : nullptr;
+        const size_t hw = (size_t)I.W * I.H;
+        const void *d_masks = nullptr;
+        const int4 *rects = nullptr;
+        if ((rc = stage_masks(c, m, F, hw, c->cams.masks[k], c->cams.rects[k], &d_masks, &rects, &host_in))) return rc;
+        if (I.W < 16) rects = nullptr;                     // (as lpf_set_masks_*: a group of 16 pixels of the pack spans at most two rows)
         if ((rc = reserve(c, c->cams.label_a[k], (size_t)F * hw * 4))) return rc;
         DevBuf &la = c->cams.label_a[k], &lb2 = c->cams.label_b[k];
         void *cur = nullptr;
@@ -2521,118 +2605,32 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
 
     // ---- segmentation: as lpf_run_batch's in-order run (it depends on the points only) ---------------------------------------------
     const bool small = Ntot <= LPF_SMALL_LAUNCH;
-    const int64_t seg_pts = small ? LPF_SEG_SMALL : LPF_SEG_QUANTUM;
     const int tile_pts = (small && Ntot <= 1792ll * 512) ? 512 : 1024;
     LpfCamsArgs A;
     memset(&A, 0, sizeof A);
     A.C = C;
     int nk1 = 0, max_tail = 0;
-    bool pre_scan = false;
-    std::vector<LpfFrame> fr((size_t)F);
+    NarrowLayout L;
     for (int k = 0; k < C; ++k) {
         const lpf_cam_input &I = cams[k];
         const lpf_ctx::BoxSet &BX = c->cams.bx[k];
         const lpf_outputs &o = out[k];
         const int M = I.masks.M;
         const int Btot = BX.F ? BX.box_off[F] : 0;
-        int nseg_total = 0, ngrp_total = 0, max_ngrp = 0;
-        for (int f = 0; f < F; ++f) {
-            LpfFrame &e = fr[f];
-            memset(&e, 0, sizeof e);
-            e.pt_off = frame_off[f];
-            e.N = (int)(frame_off[f + 1] - frame_off[f]);
-            e.seg_off = nseg_total;
-            e.shift = (int)(frame_off[f] & 63);
-            e.nseg = e.N ? (int)((e.N + e.shift + seg_pts - 1) / seg_pts) : 0;
-            nseg_total += e.nseg;
-            e.box_off = BX.F ? BX.box_off[f] : 0;
-            e.B = BX.F ? BX.box_off[f + 1] - BX.box_off[f] : 0;
-            e.inst_base = (long long)f * o.inst_cap;
-            e.pad = f;
-            e.cand_off = BX.F ? BX.cand_off[f] : 0;
-            e.cand_words = (e.B + 63) / 64;
-            e.grp_off = ngrp_total;
-            const int ngrp = (e.nseg + LPF_GROUP_SEGS - 1) / LPF_GROUP_SEGS;
-            ngrp_total += ngrp;
-            max_ngrp = std::max(max_ngrp, ngrp);
-        }
-        const int nseg_cap = nseg_total > 0 ? nseg_total : 1, ngrp_cap = ngrp_total > 0 ? ngrp_total : 1;
-        const bool count_boxes = M > 0 && Btot > 0;
-        int nblk = 0, ncblk = 0;
-        for (int f = 0; f < F; ++f) {
-            const int nbk = fr[f].nseg > 0 ? (fr[f].nseg + LPF_LISTS_WAVES - 1) / LPF_LISTS_WAVES : 1;
-            nblk += nbk;
-            ncblk += nbk * std::max(1, fr[f].cand_words);
-        }
-        const bool few = small && nblk <= LPF_FEW_BLOCKS;
-        const size_t rows = (size_t)nseg_cap * (size_t)(seg_pts / 64);
-        pre_scan = max_ngrp > 64;
+        narrow_layout(c, frame_off, F, BX, o.inst_cap, small, L);
         lpf_ctx::Scratch &S = c->sc[k];
-        if ((rc = reserve(c, S.vbal, rows * 8))) return rc;
-        if ((rc = reserve(c, S.mbal, rows * 8))) return rc;
-        if ((rc = reserve(c, S.seg_tab, (size_t)LPF_TAB_GROUPS * nseg_cap * sizeof(uint4), true))) return rc;
-        if ((rc = reserve(c, S.grp_tab, (size_t)LPF_TAB_GROUPS * ngrp_cap * sizeof(uint4), true))) return rc;
-        if ((rc = reserve(c, S.frm_tab, (size_t)F * LPF_FRM_SHARDS * LPF_TAB_GROUPS * sizeof(uint4), true))) return rc;
-        if (pre_scan && (rc = reserve(c, S.seg_pre, (size_t)LPF_TAB_GROUPS * nseg_cap * sizeof(uint4)))) return rc;
-        if ((rc = reserve(c, S.cnt, (size_t)(M > 0 ? M : 1) * (Btot > 0 ? Btot : 1) * 4, true))) return rc;
+        if ((rc = narrow_reserve(c, S, L, M, Btot))) return rc;
         if (M > 0 && (rc = reserve(c, S.mlist, n * 16))) return rc;
-        // geometry tables in scratch set k, the layout of lpf_run_batch's (count blocks in one part); the set's bookkeeping is cleared,
-        // so the next narrow run on it uploads its own
-        size_t o_segs = 0, o_blks = 0, o_cblks = 0;
-        if (F > 1) {
-            const size_t b_frames = (size_t)F * sizeof(LpfFrame), b_segs = (size_t)nseg_total * sizeof(LpfFrame), b_blks = (size_t)nblk * sizeof(int2),
-                         b_cblks = (size_t)ncblk * sizeof(int4);
-            S.tab_frames.clear();
-            if ((rc = reserve(c, S.tab, b_frames + b_segs + b_blks + b_cblks))) return rc;
-            c->h_tab.resize(b_frames + b_segs + b_blks + b_cblks);
-            memcpy(c->h_tab.data(), fr.data(), b_frames);
-            LpfFrame *hs = reinterpret_cast<LpfFrame *>(c->h_tab.data() + b_frames);
-            int2 *hb = reinterpret_cast<int2 *>(c->h_tab.data() + b_frames + b_segs);
-            int4 *hc = reinterpret_cast<int4 *>(c->h_tab.data() + b_frames + b_segs + b_blks);
-            for (int f = 0; f < F; ++f) {
-                const LpfFrame &e = fr[f];
-                const int wpg = std::max(1, e.cand_words);
-                for (int sg = 0; sg < e.nseg; ++sg) hs[(size_t)e.seg_off + sg] = e;
-                if (e.nseg == 0) {
-                    *hb++ = make_int2(e.seg_off, f << 3);
-                    for (int w = 0; w < wpg; ++w) *hc++ = make_int4(e.seg_off, f, w, 0);
-                }
-                for (int sg = 0; sg < e.nseg; sg += LPF_LISTS_WAVES) {
-                    const int nw = std::min(LPF_LISTS_WAVES, e.nseg - sg);
-                    *hb++ = make_int2(e.seg_off + sg, (f << 3) | nw);
-                    for (int w = 0; w < wpg; ++w) *hc++ = make_int4(e.seg_off + sg, f, w, nw);
-                }
-            }
-            if ((rc = upload(c, S.tab.p, c->h_tab.data(), c->h_tab.size()))) return rc;
-            o_segs = b_frames; o_blks = b_frames + b_segs; o_cblks = b_frames + b_segs + b_blks;
-            ++c->generation;                                   // graphs captured for narrow runs read this set's tables
-        }
+        // geometry tables in scratch set k (count blocks in one part), uploaded every pass
+        if ((rc = narrow_tables(c, S, L, true))) return rc;
 
         LpfParams &P = A.P[k];
-        memcpy(P.T, I.T_velo_to_rect, sizeof P.T);             // rows 0..2 (as lpf_set_camera)
-        memcpy(P.K, I.K, sizeof P.K);
-        P.dmin = I.depth_min_excl; P.dmax = I.depth_max_excl; P.W = I.W; P.H = I.H;
-        P.F = F; P.M = M; P.seg_pts = (int)seg_pts; P.nseg_total = nseg_total; P.nseg_cap = nseg_cap; P.ngrp_cap = ngrp_cap;
-        P.oriented = BX.F ? BX.oriented : 1; P.inst_cap = o.inst_cap;
-        P.frame0 = fr[0];
-        if (F > 1) {
-            P.frames = (const LpfFrame *)S.tab.p;
-            P.segs = (const LpfFrame *)((const char *)S.tab.p + o_segs);
-            P.blks = (const int2 *)((const char *)S.tab.p + o_blks);
-            P.cblks = (const int4 *)((const char *)S.tab.p + o_cblks);
-        }
+        narrow_params(P, c, input_cam(I), L, S, BX, M, o.inst_cap);
         P.label_img = M > 0 ? label_img[k] : nullptr;
-        P.boxp = (const double *)BX.boxp.p; P.boxq = (const float *)BX.boxq.p; P.cand = (const unsigned long long *)BX.cand.p;
-        P.vbal = (unsigned long long *)S.vbal.p; P.mbal = (unsigned long long *)S.mbal.p;
-        P.seg_tab = (uint4 *)S.seg_tab.p; P.grp_tab = (uint4 *)S.grp_tab.p; P.frm_tab = (uint4 *)S.frm_tab.p;
-        P.seg_pre = pre_scan ? (uint4 *)S.seg_pre.p : nullptr;
-        P.cnt = (unsigned *)S.cnt.p;
         P.mlist = M > 0 ? (float4 *)S.mlist.p : nullptr;
-        P.nblk = nblk; P.ncblk = ncblk; P.csplit = 1; P.lists_small = few ? 1 : 0; P.count_boxes = count_boxes ? 1 : 0;
-        P.count_lazy = small ? 0 : 1;
         P.pts = d_pts;
         P.tile_pts = tile_pts;
-        nk1 = nseg_total * (int)(seg_pts / tile_pts);
+        nk1 = L.nseg_total * (int)(L.seg_pts / tile_pts);      // (the same for every camera, as L.pre_scan)
 
         // outputs: the caller's device pointers, or staging carved out of one buffer (host callers; and what a device caller leaves out
         // but the pass needs: the dense uv / labels behind the compact copies, the summaries)
@@ -2655,7 +2653,7 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         P.valid_idx = (long long *)pick(o.valid_idx, c_vi); P.inst_idx = (long long *)pick(o.inst_idx, c_ii);
         P.count_out = (int32_t *)pick(o.count_mb, c_cmb); P.summary = pick(o.summary, c_sum);
         const bool want_lists = o.valid_idx || o.inst_idx;
-        A.ntail[k] = (count_boxes ? ncblk : 0) + (want_lists ? nblk : 0);
+        A.ntail[k] = (P.count_boxes ? L.ncblk : 0) + (want_lists ? L.nblk : 0);
         max_tail = std::max(max_tail, A.ntail[k]);
     }
 
@@ -2669,14 +2667,14 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
 #undef LPF_CAMS_STREAM
         LPF_HIP(c, hipGetLastError());
     }
-    if (pre_scan && nk1 > 0)                                   // frames beyond 64 groups (16.7 M points): their prefixes, per camera
+    if (L.pre_scan && nk1 > 0)                                 // frames beyond 64 groups (16.7 M points): their prefixes, per camera
         for (int k = 0; k < C; ++k) {
             hipLaunchKernelGGL(lpf_scan_segments, dim3((unsigned)F), dim3(LPF_BLOCK), 0, c->stream, A.P[k]);
             LPF_HIP(c, hipGetLastError());
         }
     if (max_tail > 0) {
         const dim3 gt((unsigned)max_tail, (unsigned)C);
-        if (pre_scan) hipLaunchKernelGGL((lpf_cams_tail<true>), gt, dim3(LPF_BLOCK), 0, c->stream, A);
+        if (L.pre_scan) hipLaunchKernelGGL((lpf_cams_tail<true>), gt, dim3(LPF_BLOCK), 0, c->stream, A);
         else hipLaunchKernelGGL((lpf_cams_tail<false>), gt, dim3(LPF_BLOCK), 0, c->stream, A);
         LPF_HIP(c, hipGetLastError());
     }
@@ -2694,63 +2692,13 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         if (o.on_device) continue;
         any_host = true;
         const int nMB = P.M * (c->cams.bx[k].F ? c->cams.bx[k].box_off[F] : 0);
-#define LPF_D2H(member, field, bytes) \
-    if (o.member && (bytes)) LPF_HIP(c, hipMemcpyAsync(o.member, P.field, (bytes), hipMemcpyDeviceToHost, c->stream));
-        LPF_D2H(uv, uv, n * 8)
-        LPF_D2H(label_bits, label_bits, n * 4)
-        LPF_D2H(depth, depth, n * 8)
-        LPF_D2H(u_f, uf, n * 8)
-        LPF_D2H(v_f, vf, n * 8)
-        LpfToHost D;
-        memset(&D, 0, sizeof D);
-        bool r2h = o.summary != nullptr && (o.valid_idx || o.inst_idx);
-        auto alias = [&](void *host, void **dev) {
-            *dev = host ? device_alias_of_pinned(host) : nullptr;
-            if (host && !*dev) r2h = false;
-        };
-        if (r2h) {
-            alias(o.summary, &D.summary);
-            alias(o.valid_idx, (void **)&D.valid_idx);
-            alias(o.uv_valid, (void **)&D.uv_valid);
-            alias(o.label_valid, (void **)&D.label_valid);
-            alias(o.inst_idx, (void **)&D.inst_idx);
-            alias(o.count_mb, (void **)&D.count_mb);
-        }
-        if (r2h) {
-            D.inst_cap = o.inst_cap;
-            D.n_count = o.count_mb ? nMB : 0;
-            hipLaunchKernelGGL(lpf_results_to_host, dim3((unsigned)F * LPF_R2H_BLOCKS), dim3(LPF_BLOCK), 0, c->stream, P, D);
-            LPF_HIP(c, hipGetLastError());
-            continue;
-        }
-        LPF_D2H(count_mb, count_out, (size_t)nMB * 4)
-#undef LPF_D2H
-        LPF_HIP(c, hipMemcpyAsync(hs.data() + (size_t)k * F, P.summary, (size_t)F * sizeof(lpf_frame_summary), hipMemcpyDeviceToHost, c->stream));
-        later[k] = lists_later = true;
+        if ((rc = narrow_back_a(c, o, P, n, nMB, hs.data() + (size_t)k * F, &later[k]))) return rc;
+        lists_later |= later[k];
     }
     if (lists_later) {
         LPF_HIP(c, host_wait(c));
-        for (int k = 0; k < C; ++k) {
-            const lpf_outputs &o = out[k];
-            const LpfParams &P = A.P[k];
-            if (!later[k]) continue;
-            for (int f = 0; f < F; ++f) {
-                const lpf_frame_summary &h = hs[(size_t)k * F + f];
-                const size_t nv = (size_t)h.n_valid;
-                if (o.valid_idx && nv)
-                    LPF_HIP(c, hipMemcpyAsync(o.valid_idx + frame_off[f], P.valid_idx + frame_off[f], nv * 8, hipMemcpyDeviceToHost, c->stream));
-                if (o.uv_valid && nv)
-                    LPF_HIP(c, hipMemcpyAsync(o.uv_valid + 2 * frame_off[f], P.uv_valid + frame_off[f], nv * 8, hipMemcpyDeviceToHost, c->stream));
-                if (o.label_valid && nv)
-                    LPF_HIP(c, hipMemcpyAsync(o.label_valid + frame_off[f], P.label_valid + frame_off[f], nv * 4, hipMemcpyDeviceToHost, c->stream));
-                int64_t tot = h.inst_off[LPF_MAX_MASKS];
-                if (tot > o.inst_cap) tot = o.inst_cap;
-                if (o.inst_idx && tot > 0)
-                    LPF_HIP(c, hipMemcpyAsync(o.inst_idx + (size_t)f * o.inst_cap, P.inst_idx + (size_t)f * o.inst_cap, (size_t)tot * 8,
-                                              hipMemcpyDeviceToHost, c->stream));
-            }
-            if (o.summary) memcpy(o.summary, hs.data() + (size_t)k * F, (size_t)F * sizeof(lpf_frame_summary));
-        }
+        for (int k = 0; k < C; ++k)
+            if (later[k] && (rc = narrow_back_b(c, out[k], A.P[k], frame_off, hs.data() + (size_t)k * F))) return rc;
     }
     if (any_host || host_in) LPF_HIP(c, host_wait(c));         // host buffers are filled, or may be reused
     return LPF_OK;
@@ -2765,7 +2713,8 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
     if (!c) return LPF_ERR_ARG;
     if (use_device(c)) return LPF_ERR_HIP;
     int rc;
-    if ((rc = cams_check(c, "lpf_run_cams_wide", pts, frame_off, F, cams, C, out, LPF_WIDE_CHUNK, LPF_MAX_MASKS_WIDE, "LPF_MAX_MASKS_WIDE", "")))
+    if ((rc = cams_check(c, "lpf_run_cams_wide", pts, frame_off, F, cams, C, out, LPF_WIDE_CHUNK, LPF_MAX_MASKS_WIDE,
+                         "a pass takes 0 .. LPF_MAX_MASKS_WIDE", " per camera")))
         return rc;
     for (int k = 0; k < C; ++k)
         if (out[k].inst_idx && out[k].inst_cap <= 0)
@@ -2791,21 +2740,7 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
         if ((rc = cams_box_tables(c, cams[k], k, F))) return rc;
         const lpf_ctx::BoxSet &BX = c->cams.bx[k];
         Btot[k] = BX.F ? BX.box_off[F] : 0;
-        int ch = 0, maxB = 0;
-        for (int f = 0; f < F; ++f) {
-            LpfWideFrame &e = fr[(size_t)k * F + f];
-            e.pt_off = frame_off[f];
-            e.N = (int)(frame_off[f + 1] - frame_off[f]);
-            e.chunk_off = ch;
-            e.nchunk = (e.N + LPF_WIDE_CHUNK - 1) / LPF_WIDE_CHUNK;
-            e.box_off = BX.F ? BX.box_off[f] : 0;
-            e.B = BX.F ? BX.box_off[f + 1] - BX.box_off[f] : 0;
-            e.pad = 0;
-            ch += e.nchunk;
-            maxB = std::max(maxB, e.B);
-        }
-        nchunk = ch;
-        nbw[k] = (maxB + 63) / 64;
+        nchunk = wide_frames(frame_off, F, BX, fr.data() + (size_t)k * F, &nbw[k]);
     }
     if ((rc = reserve(c, c->camsw.tab, fr.size() * sizeof(LpfWideFrame)))) return rc;
     if ((rc = upload(c, c->camsw.tab.p, fr.data(), fr.size() * sizeof(LpfWideFrame)))) return rc;
@@ -2823,13 +2758,7 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
         lpf_ctx::Wide &D = c->camsw.cam[k];
         LpfWideParams &W = A.P[k];
         const int M = I.masks.M, LW = (M + 31) / 32;
-        memcpy(W.cam.T, I.T_velo_to_rect, sizeof W.cam.T);  // rows 0..2 (as lpf_set_camera)
-        memcpy(W.cam.K, I.K, sizeof W.cam.K);
-        W.cam.dmin = I.depth_min_excl; W.cam.dmax = I.depth_max_excl; W.cam.W = I.W; W.cam.H = I.H;
-        W.F = F; W.M = M; W.LW = LW; W.nchunk = nchunk; W.nbw = nbw[k];
-        W.oriented = BX.F ? BX.oriented : 1; W.inst_cap = out[k].inst_cap;
-        W.frames = (const LpfWideFrame *)c->camsw.tab.p + (size_t)k * F;
-        W.boxp = (const double *)BX.boxp.p; W.boxq = (const float *)BX.boxq.p;
+        wide_params(W, input_cam(I), F, M, nchunk, nbw[k], BX, out[k].inst_cap, (const LpfWideFrame *)c->camsw.tab.p + (size_t)k * F);
         W.pts = d_pts;
         if ((rc = wide_pack(c, D, &I.masks, F, I.W, I.H, W, &host_in))) return rc;
         if ((rc = wide_bind(c, D, &out[k], n, F, Btot[k], W, S[k]))) return rc;

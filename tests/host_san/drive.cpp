@@ -1,9 +1,10 @@
 // drive.cpp -- drives the HOST side of liblpf (lpf_api.hip compiled --offload-host-only against fake_hip.cpp) under a sanitizer:
-// argument validation, host-memory runs, the software-pipelined modes with new masks / rectangles / boxes / batch shapes every
-// run (the pinned upload ring is lapped several times: > 40 000 small uploads and sizes that fill a quarter exactly), the box-set
-// and scratch-set rotation, the graph state machine, mask resize / erosion staging and the reader's worker threads.  Kernel
-// launches do nothing (fake_hip.cpp), so results are not checked here -- the GPU tests do that; what is checked is that every
-// call returns what it should and that the sanitizer stays silent.
+// argument validation, host-memory runs, the multi-camera, wide and depth-map entry points (host and device outputs, one and several
+// frames, their refused arguments and messages), the geometry tables' cache key, the software-pipelined modes with new masks /
+// rectangles / boxes / batch shapes every run (the pinned upload ring is lapped several times: > 40 000 small uploads and sizes that
+// fill a quarter exactly), the box-set and scratch-set rotation, the graph state machine, mask resize / erosion staging and the
+// reader's worker threads.  Kernel launches do nothing (fake_hip.cpp), so results are not checked here -- the GPU tests do that;
+// what is checked is that every call returns what it should and that the sanitizer stays silent.
 #include "../../include/lpf.h"
 
 #include <cstdio>
@@ -207,6 +208,228 @@ static void pipelined_streams(int mode, int runs, const int W, const int H)
     g_ctx = nullptr;
 }
 
+static void fill_wide_outputs(Dev &D, lpf_wide_outputs &o, int64_t n, int F, int M, int Btot, int64_t cap, int on_device)
+{
+    const int LW = M > 0 ? (M + 31) / 32 : 1;
+    memset(&o, 0, sizeof o);
+    o.uv = D.get<int32_t>(2 * n); o.depth = D.get<double>(n); o.u_f = D.get<double>(n); o.v_f = D.get<double>(n);
+    o.valid_idx = D.get<int64_t>(n); o.uv_valid = D.get<int32_t>(2 * n); o.label_words = D.get<uint32_t>(n * LW);
+    o.label_valid_words = D.get<uint32_t>(n * LW); o.inst_idx = D.get<int64_t>((size_t)F * cap); o.inst_cap = cap;
+    o.count_mb = D.get<int32_t>((size_t)(M ? M : 1) * (Btot ? Btot : 1)); o.n_valid = D.get<int64_t>(F); o.n_labelled = D.get<int64_t>(F);
+    o.inst_count = D.get<int64_t>((size_t)F * M + 1); o.inst_off = D.get<int64_t>((size_t)F * (M + 1)); o.best_cnt = D.get<int64_t>((size_t)F * M + 1);
+    o.best_box = D.get<int32_t>((size_t)F * M + 1); o.inst_overflow = D.get<int32_t>(F);
+    o.on_device = on_device;
+}
+
+static bool err_is(lpf_ctx *c, const char *text) { return strcmp(lpf_last_error(c), text) == 0; }
+
+// lpf_run_cams, lpf_run_cams_wide, lpf_run_wide, lpf_run_frame_wide and lpf_depth_maps: host and device outputs, one and several frames,
+// host and device masks (uint8 and float, with and without rectangles and erosion), and one of each refused argument
+static void wide_and_multicam_runs()
+{
+    lpf_ctx *c = nullptr;
+    CHECK(lpf_create(&c, 0) == LPF_OK);
+    g_ctx = c;
+    CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+    Dev D;
+    const int FMAX = 3, MW = 40;                               // (MW: more masks than a narrow run takes)
+    const int64_t offs[2][FMAX + 1] = {{0, 2500, 0, 0}, {0, 1000, 1000, 4321}};     // one frame; three with an empty one in the middle
+    const int64_t NMAX = offs[1][FMAX];
+    std::vector<float> hpts(4 * NMAX, 1.0f);
+    float *dpts = D.get<float>(4 * NMAX);
+    const size_t hw = (size_t)W * H;
+    std::vector<uint8_t> hmasks((size_t)FMAX * MW * hw, 1);
+    uint8_t *dmasks = D.get<uint8_t>((size_t)FMAX * MW * hw);
+    std::vector<float> hfmasks((size_t)FMAX * 5 * hw, 1.0f);
+    float *dfmasks = D.get<float>((size_t)FMAX * 5 * hw);
+    std::vector<int32_t> hrects((size_t)FMAX * MW * 4, 2);
+    int32_t *drects = D.get<int32_t>((size_t)FMAX * MW * 4);
+    std::vector<double> hcorners(24 * 9, 0.5);
+    double *dcorners = D.get<double>(24 * 9);
+    const int32_t boffs[2][FMAX + 1] = {{0, 4, 0, 0}, {0, 3, 3, 9}};
+    for (int shape = 0; shape < 2; ++shape) {
+        const int F = shape ? FMAX : 1;
+        const int64_t *off = offs[shape];
+        const int32_t *boff = boffs[shape];
+        const int64_t n = off[F];
+        for (int on_device = 0; on_device < 2; ++on_device) {
+            const float *pts = on_device ? dpts : hpts.data();
+            // three cameras: uint8 masks with rectangles and host boxes; float masks eroded, with device boxes; no masks, no boxes, 12 px wide
+            lpf_cam_input cams[3];
+            memset(cams, 0, sizeof cams);
+            for (int k = 0; k < 3; ++k) {
+                memcpy(cams[k].T_velo_to_rect, T16, sizeof T16);
+                memcpy(cams[k].K, K9, sizeof K9);
+                cams[k].W = k == 2 ? 12 : W; cams[k].H = H; cams[k].depth_min_excl = 0; cams[k].depth_max_excl = 50;
+            }
+            cams[0].masks.masks = on_device ? (const void *)dmasks : hmasks.data(); cams[0].masks.rects = on_device ? drects : hrects.data();
+            cams[0].masks.M = 5; cams[0].masks.on_device = on_device;
+            cams[0].corners_velo = hcorners.data(); cams[0].box_off = boff; cams[0].boxes_on_device = 0; cams[0].oriented = 1;
+            cams[1].masks.masks = on_device ? (const void *)dfmasks : hfmasks.data(); cams[1].masks.M = 5; cams[1].masks.f32 = 1;
+            cams[1].masks.binarize = 1; cams[1].masks.erode_iters = 2; cams[1].masks.on_device = on_device;
+            cams[1].corners_velo = dcorners; cams[1].box_off = boff; cams[1].boxes_on_device = 1 + on_device; cams[1].oriented = 0;
+            lpf_outputs o[3];
+            for (int k = 0; k < 3; ++k) fill_outputs(D, o[k], n, F, 5, boff[F], 3000, (on_device + k) & 1);   // (host and device outputs in one pass)
+            CHECK(lpf_run_cams(c, pts, off, F, on_device, cams, 3, o) == LPF_OK);
+            CHECK(lpf_run_cams(c, pts, off, F, on_device, cams, 1, o) == LPF_OK);
+            // the same cameras with up to MW masks each
+            cams[0].masks.M = MW;
+            lpf_wide_outputs ow[3];
+            for (int k = 0; k < 3; ++k) fill_wide_outputs(D, ow[k], n, F, cams[k].masks.M, boff[F], 3000, (on_device + k) & 1);
+            CHECK(lpf_run_cams_wide(c, pts, off, F, on_device, cams, 3, ow) == LPF_OK);
+            // one camera's worth through lpf_run_wide and lpf_depth_maps, with and without the context's boxes
+            CHECK(lpf_set_boxes_ex(c, hcorners.data(), 0, boff, F, 1) == LPF_OK);
+            for (int k = 0; k < 2; ++k) {
+                lpf_wide_outputs w1;
+                fill_wide_outputs(D, w1, n, F, cams[k].masks.M, boff[F], 3000, on_device);
+                CHECK(lpf_run_wide(c, pts, off, F, on_device, &cams[k].masks, &w1) == LPF_OK);
+                lpf_depth_maps_outputs dm;
+                memset(&dm, 0, sizeof dm);
+                dm.cap = 500; dm.pix = D.get<int64_t>((size_t)F * 500); dm.depth = D.get<double>((size_t)F * 500);
+                dm.point_idx = D.get<int64_t>((size_t)F * 500); dm.car_off = D.get<int64_t>((size_t)F * (cams[k].masks.M + 1));
+                dm.need = D.get<int64_t>(F); dm.overflow = D.get<int32_t>(F); dm.on_device = on_device;
+                CHECK(lpf_depth_maps(c, pts, off, F, on_device, &cams[k].masks, &dm) == LPF_OK);
+                CHECK(lpf_depth_maps(c, pts, off, 0, on_device, &cams[k].masks, &dm) == LPF_OK);      // no frames: nothing to do
+            }
+            CHECK(lpf_set_boxes_ex(c, nullptr, 0, nullptr, 0, 1) == LPF_OK);
+        }
+    }
+    // lpf_run_frame_wide: masks read directly (sparse frame, aligned rectangles) or packed; with and without boxes
+    for (int direct = 0; direct < 2; ++direct) {
+        lpf_frame_job_wide j;
+        memset(&j, 0, sizeof j);
+        j.pts = dpts; j.n_points = direct ? 1000 : 4000; j.masks = dmasks; j.mask_rects = direct ? drects : nullptr; j.n_masks = MW;
+        j.corners_cam0 = direct ? dcorners : nullptr; j.n_boxes = 9; j.T_cam_to_velo = T16; j.filter_visible = 1; j.oriented = 1;
+        fill_wide_outputs(D, j.out, j.n_points, 1, MW, 9, 3000, 1);
+        CHECK(lpf_run_frame_wide(c, &j) == LPF_OK);
+    }
+
+    // ---- refused arguments (the messages are part of the interface: the Python layer passes them on) ----------------------------------
+    const int64_t bad0[2] = {1, 5}, neg[3] = {0, 7, 3}, huge[2] = {0, 0x7fffffffll};
+    lpf_cam_input cam;
+    memset(&cam, 0, sizeof cam);
+    memcpy(cam.T_velo_to_rect, T16, sizeof T16); memcpy(cam.K, K9, sizeof K9); cam.W = W; cam.H = H; cam.depth_max_excl = 50;
+    lpf_outputs on;
+    fill_outputs(D, on, 1000, 1, 5, 1, 100, 1);
+    lpf_wide_outputs owd;
+    fill_wide_outputs(D, owd, 1000, 1, 5, 1, 100, 1);
+    const int64_t off1[2] = {0, 1000};
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 0, &on) == LPF_ERR_ARG && err_is(c, "run_cams: C=0 cameras, a pass takes 1 .. LPF_MAX_CAMS = 4"));
+    CHECK(lpf_run_cams(c, dpts, bad0, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: frame_off[0] must be 0"));
+    CHECK(lpf_run_cams_wide(c, dpts, neg, 2, 1, &cam, 1, &owd) == LPF_ERR_ARG && err_is(c, "run_cams_wide: frame 1 has -4 points"));
+    CHECK(lpf_run_cams(c, nullptr, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: pts is NULL"));
+    cam.W = 0;
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: camera 0 is 0 x 48"));
+    cam.W = W; cam.masks.M = 33;
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG &&
+          err_is(c, "run_cams: camera 0 has M=33 masks per frame, a pass takes 0 .. LPF_MAX_MASKS = 32 per camera (more: lpf_run_wide for that camera)"));
+    cam.masks.M = 257;
+    CHECK(lpf_run_cams_wide(c, dpts, off1, 1, 1, &cam, 1, &owd) == LPF_ERR_ARG &&
+          err_is(c, "run_cams_wide: camera 0 has M=257 masks per frame, a pass takes 0 .. LPF_MAX_MASKS_WIDE = 256 per camera"));
+    cam.masks.M = 2;
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG &&
+          err_is(c, "run_cams: camera 0: erode_iters=0 f32=0 binarize=0 masks=(nil)"));
+    cam.masks.masks = dmasks; cam.masks.f32 = 1; cam.masks.binarize = 3;
+    CHECK(lpf_run_cams_wide(c, dpts, off1, 1, 1, &cam, 1, &owd) == LPF_ERR_ARG);
+    cam.masks.f32 = 0; cam.masks.binarize = 0;
+    cam.corners_velo = dcorners; cam.box_off = boffs[1] + 1;                    // (starts at 3)
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: camera 0: box_off must be given and start at 0"));
+    const int32_t desc[3] = {0, 5, 2};
+    cam.box_off = desc;
+    CHECK(lpf_run_cams(c, dpts, neg, 2, 1, &cam, 1, &on) == LPF_ERR_ARG);      // (the frames are checked first)
+    const int64_t off2[3] = {0, 500, 1000};
+    CHECK(lpf_run_cams(c, dpts, off2, 2, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: camera 0: box_off not ascending at 1"));
+    cam.box_off = boffs[0]; cam.boxes_on_device = 3;
+    CHECK(lpf_run_cams_wide(c, dpts, off1, 1, 1, &cam, 1, &owd) == LPF_ERR_ARG && err_is(c, "run_cams_wide: camera 0: boxes_on_device=3"));
+    cam.boxes_on_device = 0;
+    on.inst_cap = 0;
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: out[0].inst_idx given with inst_cap=0"));
+    on.inst_cap = 100; on.valid_idx = nullptr;
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG);
+    owd.inst_cap = 0;
+    CHECK(lpf_run_cams_wide(c, dpts, off1, 1, 1, &cam, 1, &owd) == LPF_ERR_ARG && err_is(c, "run_cams_wide: out[0].inst_idx given with inst_cap=0"));
+    CHECK(lpf_run_wide(c, dpts, off1, 1, 1, &cam.masks, &owd) == LPF_ERR_ARG && err_is(c, "run_wide: inst_idx given with inst_cap=0"));
+    owd.inst_cap = 100;
+    CHECK(lpf_run_wide(c, dpts, off1, 1, 1, nullptr, &owd) == LPF_ERR_ARG);
+    lpf_wide_input wi = cam.masks;
+    wi.M = 300;
+    CHECK(lpf_run_wide(c, dpts, off1, 1, 1, &wi, &owd) == LPF_ERR_ARG &&
+          err_is(c, "run_wide: M=300 masks per frame, lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE = 256"));
+    wi.M = 2; wi.erode_iters = -1;
+    CHECK(lpf_run_wide(c, dpts, off1, 1, 1, &wi, &owd) == LPF_ERR_ARG && strncmp(lpf_last_error(c), "run_wide: erode_iters=-1 f32=0 binarize=0 masks=", 48) == 0);
+    wi.erode_iters = 0;
+    CHECK(lpf_run_wide(c, dpts, bad0, 1, 1, &wi, &owd) == LPF_ERR_ARG && err_is(c, "run_wide: frame_off[0] must be 0"));
+    CHECK(lpf_run_wide(c, dpts, huge, 1, 1, &wi, &owd) == LPF_ERR_ARG && err_is(c, "run_wide: frame 0 has 2147483647 points"));
+    CHECK(lpf_run_wide(c, nullptr, off1, 1, 1, &wi, &owd) == LPF_ERR_ARG && err_is(c, "run_wide: pts is NULL"));
+    lpf_depth_maps_outputs dm;
+    memset(&dm, 0, sizeof dm);
+    dm.car_off = D.get<int64_t>(8); dm.need = D.get<int64_t>(2); dm.on_device = 1;
+    wi.M = 300;
+    CHECK(lpf_depth_maps(c, dpts, off1, 1, 1, &wi, &dm) == LPF_ERR_ARG &&
+          err_is(c, "depth_maps: M=300 masks per frame, lpf_depth_maps takes 0 .. LPF_MAX_MASKS_WIDE = 256"));
+    wi.M = 2; wi.f32 = 1; wi.binarize = -1;
+    CHECK(lpf_depth_maps(c, dpts, off1, 1, 1, &wi, &dm) == LPF_ERR_ARG && strncmp(lpf_last_error(c), "depth_maps: erode_iters=0 f32=1 binarize=-1", 43) == 0);
+    wi.f32 = 0; wi.binarize = 0;
+    CHECK(lpf_depth_maps(c, dpts, bad0, 1, 1, &wi, &dm) == LPF_ERR_ARG && err_is(c, "depth_maps: frame_off[0] must be 0"));
+    CHECK(lpf_depth_maps(c, dpts, neg, 2, 1, &wi, &dm) == LPF_ERR_ARG && err_is(c, "depth_maps: frame 1 has -4 points"));
+    CHECK(lpf_depth_maps(c, nullptr, off1, 1, 1, &wi, &dm) == LPF_ERR_ARG && err_is(c, "depth_maps: pts is NULL"));
+    dm.car_off = nullptr;
+    CHECK(lpf_depth_maps(c, dpts, off1, 1, 1, &wi, &dm) == LPF_ERR_ARG);
+    lpf_frame_job_wide j;
+    memset(&j, 0, sizeof j);
+    j.pts = dpts; j.n_points = 10; j.n_masks = 300; j.out = owd;
+    CHECK(lpf_run_frame_wide(c, nullptr) == LPF_ERR_ARG);
+    CHECK(lpf_run_frame_wide(c, &j) == LPF_ERR_ARG);
+    j.n_masks = 3;
+    CHECK(lpf_run_frame_wide(c, &j) == LPF_ERR_ARG);                            // masks NULL
+    j.out.on_device = 0;
+    CHECK(lpf_run_frame_wide(c, &j) == LPF_ERR_ARG);
+    // every entry point but lpf_run_batch refuses a graph capture
+    CHECK(lpf_graph_begin(c) == LPF_OK);
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_STATE &&
+          err_is(c, "lpf_run_cams cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end) [the graph capture in progress was abandoned]"));
+    lpf_destroy(c);
+    g_ctx = nullptr;
+}
+
+// The geometry tables of a scratch set are keyed by the frame records AND the count blocks' parts: a fused run of a frame or two (count
+// blocks in four parts) and an in-order host-output run of the same shape and box counts (one part) share scratch set 0 -- the first
+// run after lpf_set_pipelined uses it, a host-output run always does -- and the second of them must upload its own tables.
+static void table_key()
+{
+    Dev D;
+    const int F = 3, M = 2;
+    const int64_t off[F + 1] = {0, 1000, 1000, 3000};
+    const int32_t boff[F + 1] = {0, 2, 2, 70};                   // (two 64-box words in frame 2)
+    float *dpts = D.get<float>(4 * off[F]);
+    std::vector<float> hpts(4 * off[F], 1.0f);
+    uint8_t *dmasks = D.get<uint8_t>((size_t)F * M * W * H);
+    std::vector<double> corners(24 * boff[F], 0.5);
+    lpf_outputs od, oh;
+    fill_outputs(D, od, off[F], F, M, boff[F], 500, 1);
+    fill_outputs(D, oh, off[F], F, M, boff[F], 500, 0);
+    for (int fused_first = 1; fused_first >= 0; --fused_first) {
+        lpf_ctx *c = nullptr;
+        CHECK(lpf_create(&c, 0) == LPF_OK);
+        g_ctx = c;
+        CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+        CHECK(lpf_set_pipelined(c, 2) == LPF_OK);
+        CHECK(lpf_set_boxes_ex(c, corners.data(), 0, boff, F, 1) == LPF_OK);
+        for (int r = 0; r < 2; ++r) {
+            const bool fused = (r == 0) == (fused_first == 1);
+            CHECK(lpf_set_masks_u8(c, dmasks, F, M, 0, 2) == LPF_OK);
+            int64_t st[8];
+            CHECK(lpf_get_stats(c, st, 8, 1) == LPF_OK);
+            CHECK(lpf_run_batch(c, fused ? dpts : hpts.data(), off, F, fused ? 1 : 0, fused ? &od : &oh) == LPF_OK);
+            CHECK(lpf_get_stats(c, st, 8, 0) == LPF_OK);
+            CHECK(st[2] == 1);                                   // the run's tables went up through the pinned ring
+        }
+        CHECK(lpf_sync(c) == LPF_OK);
+        lpf_destroy(c);
+        g_ctx = nullptr;
+    }
+}
+
 // the ring alone: 256-byte uploads by the ten thousand (the head reached the end of the buffer after 32768 of them)
 static void ring_of_small_uploads()
 {
@@ -398,6 +621,8 @@ int main(int argc, char **argv)
     const int runs = argc > 2 ? atoi(argv[2]) : 12000;
     argument_errors();
     host_memory_runs();
+    wide_and_multicam_runs();
+    table_key();
     ring_of_small_uploads();
     pipelined_streams(2, runs, W, H);
     pipelined_streams(4, runs, W, H);

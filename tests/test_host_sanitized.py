@@ -5,7 +5,8 @@ GPU box, where sanitizer runs are not available):
     golden-vector and mask tests against the sanitized library;
   * the HOST side of liblpf -- lpf_api.hip compiled `--offload-host-only` and linked against tests/host_san/fake_hip.cpp, a functional
     stand-in for the HIP runtime (device memory = heap blocks, copies = memcpy, launches = nothing) -- under ASan + UBSan and under
-    ThreadSanitizer, driven by tests/host_san/drive.cpp: argument validation, host-memory runs, > 24 000 software-pipelined runs with
+    ThreadSanitizer, driven by tests/host_san/drive.cpp: argument validation, host-memory runs, lpf_run_cams / lpf_run_cams_wide /
+    lpf_run_wide / lpf_run_frame_wide / lpf_depth_maps with host and device outputs, > 24 000 software-pipelined runs with
     new masks / rectangles / boxes / batch shapes (the pinned upload ring is lapped many times, with pieces that fill a quarter
     exactly: ADVICE round 3), the box-set and scratch-set rotation, the graph state machine, and the reader's worker threads.
 """
