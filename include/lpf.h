@@ -52,7 +52,9 @@ extern "C" {
                                       8 (continued): lpf_run_cams_wide (added; nothing else changed)
                                       8 (continued): lpf_frame_job_wide, lpf_run_frame_wide (added; lpf_get_stats gained slot [7];
                                          nothing else changed)
-                                      8 (continued): lpf_depth_maps_outputs, lpf_depth_maps (added; nothing else changed) */
+                                      8 (continued): lpf_depth_maps_outputs, lpf_depth_maps (added; nothing else changed)
+                                      8 (continued): lpf_depth_overlay_input, lpf_depth_overlay_outputs, lpf_depth_overlays (added;
+                                         nothing else changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -449,6 +451,43 @@ typedef struct lpf_depth_maps_outputs {
 } lpf_depth_maps_outputs;
 int lpf_depth_maps(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
                    const lpf_depth_maps_outputs *out);
+
+/* lpf_depth_overlays: seg_with_pointcloud.py:174-180's per-car overlay images of a batch of F frames in ONE call, from the sparse
+ * lists of lpf_depth_maps.  For car m of frame f (entries car_off[f][m] .. car_off[f][m + 1] of row f of pix / depth) image
+ * images[f][m] is, byte for byte, cv2.cvtColor(np.uint8(image_withseg * 255), cv2.COLOR_RGB2BGR) of the script:
+ *   a listed pixel p:   (lut[i][2], lut[i][1], lut[i][0]),  i = min(255, (int)(256.0 * (depth / mx))),  mx = np.max(depthMap)
+ *   any other pixel p:  (seg[f][p][2], seg[f][p][1], seg[f][p][0])
+ * with lut = (matplotlib jet's _lut[:256, :3] * 255).astype(np.uint8) and one IEEE fp64 division.  max_depth[f][m] = mx, the max of
+ * the car's depths, 0 for an empty car; an empty car's image is the reversed segmented image (the script skips that car: `continue`).
+ * W and H are lpf_set_camera's (LPF_ERR_STATE without a camera).  Not capturable (LPF_ERR_STATE between lpf_graph_begin and
+ * lpf_graph_end); with a software-pipelined mode on it first launches what the pipeline owes (no host wait).  The camera, masks,
+ * rectangles, boxes and label state of the other calls are left as they were.  With every pointer device memory the call only
+ * enqueues work; otherwise it returns after one host wait, with host outputs filled.
+ * Lists in host memory are checked (offsets non-decreasing within [0, cap], pixels strictly ascending within each car and inside
+ * the image, depths finite and > 0: LPF_ERR_ARG otherwise); lists in device memory are not, but are never read or written out of
+ * bounds: offsets are clamped to [0, cap] and non-decreasing, pixels outside [0, W * H) are skipped.
+ * LPF_ERR_ARG: F < 0, M out of range, cap < 0, car_off NULL, seg NULL with M > 0, pix or depth NULL with cap > 0, both outputs NULL
+ * with M > 0, bad host lists.
+ * Device memory: the (frame, car) images go through in chunks whose scratch -- staged segmented images and lists, images for host
+ * outputs -- stays within 256 MiB, or one image's worth when a single image needs more; plus F * M * 8 bytes for host max_depth. */
+typedef struct lpf_depth_overlay_input {
+    const int64_t *pix;        /* [F][cap] rows as lpf_depth_maps writes them: flat v * W + u, strictly ascending per car */
+    const double  *depth;      /* [F][cap] */
+    int64_t        cap;
+    const int64_t *car_off;    /* [F][M + 1] */
+    int32_t        M;          /* 0 .. LPF_MAX_MASKS_WIDE */
+    int32_t        lists_on_device;
+    const uint8_t *seg;        /* [F][H][W][3] 8-bit segmented images at the camera's size */
+    int32_t        seg_on_device;
+    int32_t        reserved;
+} lpf_depth_overlay_input;
+typedef struct lpf_depth_overlay_outputs {
+    uint8_t *images;           /* [F][M][H][W][3] (may be NULL) */
+    double  *max_depth;        /* [F][M] np.max(depthMap), 0 for an empty car (may be NULL) */
+    int32_t  on_device;
+    int32_t  reserved;
+} lpf_depth_overlay_outputs;
+int lpf_depth_overlays(lpf_ctx *ctx, int F, const lpf_depth_overlay_input *in, const lpf_depth_overlay_outputs *out);
 
 /* cv2.resize(mask.astype(np.uint8), (camera.width, camera.height)) (V3:222; INTER_LINEAR, the default) for masks that do not arrive at
  * the camera's size (the reference's scripts all pass retina_masks=True, so theirs do): n planes [h][w] of uint8 -> n planes [H][W]

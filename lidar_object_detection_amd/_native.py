@@ -68,6 +68,17 @@ class DepthMapsOutputs(ctypes.Structure):
                 ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class DepthOverlayInput(ctypes.Structure):
+    """lpf_depth_overlay_input (include/lpf.h): the sparse lists of lpf_depth_maps and the segmented images of an lpf_depth_overlays call"""
+    _fields_ = [("pix", _P), ("depth", _P), ("cap", _I64), ("car_off", _P), ("M", ctypes.c_int32), ("lists_on_device", ctypes.c_int32),
+                ("seg", _P), ("seg_on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class DepthOverlayOutputs(ctypes.Structure):
+    """lpf_depth_overlay_outputs (include/lpf.h): the per-car overlay images and np.max of each car's depth map"""
+    _fields_ = [("images", _P), ("max_depth", _P), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 LPF_MAX_CAMS = 4                        # lpf_run_cams / lpf_run_cams_wide: cameras of one pass
 
 
@@ -232,6 +243,7 @@ def load(path=None):
     lib.lpf_run_frame_wide.argtypes = [_P, ctypes.POINTER(FrameJobWide)]
     lib.lpf_run_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(WideOutputs)]
     lib.lpf_depth_maps.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(DepthMapsOutputs)]
+    lib.lpf_depth_overlays.argtypes = [_P, ctypes.c_int, ctypes.POINTER(DepthOverlayInput), ctypes.POINTER(DepthOverlayOutputs)]
     lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_cams_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(WideOutputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
@@ -268,7 +280,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_graph_begin", "lpf_graph_end", "lpf_graph_launch", "lpf_graph_destroy",
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
-            "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps")
+            "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -1244,6 +1256,85 @@ class LpfContext:
             out.append([(pix[f, o[m]:o[m + 1]].copy(), dep[f, o[m]:o[m + 1]].copy(),
                          pid[f, o[m]:o[m + 1]].copy() if pid is not None else None) for m in range(M)])
         return out
+
+    @staticmethod
+    def overlay_rows(maps, hw):
+        """depth_maps()' per-frame car lists -> the rows of lpf_depth_overlay_input: pix int64 [F,cap], depth float64 [F,cap], car_off
+        int64 [F,M+1] and M.  Every car must be a strictly ascending pixel list inside the image with finite depths > 0 (ValueError)."""
+        F = len(maps)
+        Ms = {len(cars) for cars in maps}
+        if len(Ms) > 1:
+            raise ValueError("every frame of depth maps must have the same number of cars, got %s" % sorted(Ms))
+        M = Ms.pop() if Ms else 0
+        if M > LPF_MAX_MASKS_WIDE:
+            raise ValueError("M=%d cars per frame, depth_overlays takes at most %d" % (M, LPF_MAX_MASKS_WIDE))
+        car_off = np.zeros((F, M + 1), np.int64)
+        cars = []
+        for f, fr in enumerate(maps):
+            for m, car in enumerate(fr):
+                pix, dep = np.asarray(car[0]), np.asarray(car[1])
+                if pix.ndim != 1 or dep.shape != pix.shape or pix.dtype.kind not in "iu" or dep.dtype.kind != "f":
+                    raise ValueError("frame %d car %d: pixels must be an integer list and depths a float list of the same length" % (f, m))
+                if len(pix) and (pix[0] < 0 or pix[-1] >= hw or (len(pix) > 1 and not (np.diff(pix) > 0).all())):
+                    raise ValueError("frame %d car %d: pixels must be strictly ascending inside the image [0, %d)" % (f, m, hw))
+                if len(dep) and not (np.isfinite(dep).all() and (dep > 0).all()):
+                    raise ValueError("frame %d car %d: depths must be finite and > 0" % (f, m))
+                car_off[f, m + 1] = car_off[f, m] + len(pix)
+                cars.append((f, m, pix, dep))
+        cap = int(car_off[:, -1].max()) if F else 0
+        pix_rows, dep_rows = np.zeros((F, cap), np.int64), np.zeros((F, cap), np.float64)
+        for f, m, pix, dep in cars:
+            pix_rows[f, car_off[f, m]:car_off[f, m + 1]] = pix
+            dep_rows[f, car_off[f, m]:car_off[f, m + 1]] = dep
+        return pix_rows, dep_rows, car_off, M
+
+    def depth_overlays(self, maps, seg_images):
+        """seg_with_pointcloud.py:174-180's per-car overlay images in ONE native call (lpf_depth_overlays): ``maps`` is what
+        depth_maps() returns (per frame, M tuples (pix, depth, ...)), ``seg_images`` the segmented images uint8 [F,H,W,3] at the
+        camera's size (set_camera), a NumPy array or a GPU tensor.  Returns (images uint8 [F,M,H,W,3], max_depth float64 [F,M]):
+        image (f, m) is the script's cvtColor(np.uint8(image_withseg * 255), COLOR_RGB2BGR) byte for byte, max_depth its
+        np.max(depthMap) (0 for an empty car, whose image is only the reversed segmented image: the script skips that car).  Host
+        images give NumPy outputs after one host wait; a GPU tensor gives torch tensors on its device, in torch's stream order
+        (the call only enqueues work)."""
+        dev = _is_torch(seg_images)
+        F = len(maps)
+        shape = (F, self.H, self.W, 3)
+        if tuple(seg_images.shape) != shape:
+            raise ValueError("segmented images must be uint8 [F,H,W,3] = %s at the camera's size, got %s" % (shape, tuple(seg_images.shape)))
+        if str(seg_images.dtype) not in ("torch.uint8", "uint8"):
+            raise ValueError("segmented images must be uint8, got %s" % (seg_images.dtype,))
+        pix, dep, car_off, M = self.overlay_rows(maps, self.W * self.H)
+        cap = pix.shape[1]
+        inp, o = DepthOverlayInput(), DepthOverlayOutputs()
+        inp.cap, inp.M = cap, M
+        if dev:
+            import torch
+            d = seg_images.device
+            seg = seg_images.contiguous()
+            lists = [torch.from_numpy(a).to(d) for a in (pix, dep, car_off)]
+            images = torch.empty((F, M, self.H, self.W, 3), dtype=torch.uint8, device=d)
+            mx = torch.zeros((F, M), dtype=torch.float64, device=d)
+            if F == 0 or M == 0:
+                return images, mx
+            inp.pix, inp.depth = (lists[0].data_ptr(), lists[1].data_ptr()) if cap else (None, None)
+            inp.car_off, inp.seg = lists[2].data_ptr(), seg.data_ptr()
+            inp.lists_on_device = inp.seg_on_device = o.on_device = 1
+            o.images, o.max_depth = images.data_ptr(), mx.data_ptr()
+            ts = torch.cuda.current_stream(d).cuda_stream
+            self.wait_for_stream(ts)                # the lists, the images and the outputs' memory belong to torch's stream
+            self._check(self._lib.lpf_depth_overlays(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
+            self.release_to_stream(ts)
+            return images, mx
+        seg = np.ascontiguousarray(seg_images)
+        images = np.empty((F, M, self.H, self.W, 3), np.uint8)
+        mx = np.zeros((F, M), np.float64)
+        if F == 0 or M == 0:
+            return images, mx
+        inp.pix, inp.depth = (pix.ctypes.data, dep.ctypes.data) if cap else (None, None)
+        inp.car_off, inp.seg = car_off.ctypes.data, seg.ctypes.data
+        o.images, o.max_depth = images.ctypes.data, mx.ctypes.data
+        self._check(self._lib.lpf_depth_overlays(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
+        return images, mx
 
     def run_cams_wide(self, frames, cams, want_uv=True, want_float=False, want_lists=True, want_valid_uv=False, inst_cap=None,
                       want_label=True, pinned=False):

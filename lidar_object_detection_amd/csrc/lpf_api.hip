@@ -7,6 +7,7 @@
 #include "lpf_cams_wide.hip.h"
 #include "lpf_frame_wide.hip.h"
 #include "lpf_depth_maps.hip.h"
+#include "lpf_depth_overlays.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -183,6 +184,9 @@ struct lpf_ctx {
     // lpf_depth_maps: frame offsets, a chunk's winner planes, counters, staged masks / rectangles / points, host-output staging and
     // (with erosion) lpf_run_wide's label planes in pack.planes_* (grow-only, allocated on first use)
     struct DepthMaps { Wide pack; DevBuf foff, win, cnt, masks, rects, pts, out; } dmaps;
+    // lpf_depth_overlays: a chunk's staged segmented images and lists, images for host outputs, max_depth for host outputs
+    // (grow-only, allocated on first use)
+    struct DepthOverlays { DevBuf seg, lists, img, mx; } dovl;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -1191,6 +1195,8 @@ void lpf_destroy(lpf_ctx *c)
     release(c->camsw.pts);
     for (DevBuf *b : {&c->dmaps.pack.planes_a, &c->dmaps.pack.planes_b, &c->dmaps.foff, &c->dmaps.win, &c->dmaps.cnt, &c->dmaps.masks,
                       &c->dmaps.rects, &c->dmaps.pts, &c->dmaps.out})
+        release(*b);
+    for (DevBuf *b : {&c->dovl.seg, &c->dovl.lists, &c->dovl.img, &c->dovl.mx})
         release(*b);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_uvv, &c->st_labv, &c->st_pts, &c->st_uv, &c->st_label,
                      &c->st_depth, &c->st_uf, &c->st_vf, &c->st_valid, &c->st_inst, &c->st_count, &c->st_summary};
@@ -2479,6 +2485,137 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
         LPF_HIP(c, back(out->overflow, o_ovf, nF * 4));
     }
     if (host_io || host_masks || host_pts) LPF_HIP(c, host_wait(c));   // host buffers may be reused
+    return LPF_OK;
+}
+
+// ---- lpf_depth_overlays (include/lpf.h): per-car overlay images, kernels in lpf_depth_overlays.hip.h -----------------------------
+// The F * M (frame, car) images go through in chunks of consecutive images: a chunk's scratch -- the segmented images and lists of
+// the frames it touches when they are in host memory, its images when the outputs are -- stays within LPF_DO_BUDGET, or one image
+// when a single image needs more.  The chunks are planned and every buffer reserved before the first launch, so no chunk waits for
+// the one before it.
+#define LPF_DO_BUDGET (256ull << 20)
+#define LPF_DO_MAX_IMAGES 65535ll           // images per chunk: the render's grid.y
+
+// host lists: offsets non-decreasing within [0, cap], pixels strictly ascending within each car and inside the image, depths finite
+// and > 0 (the device lists are clamped by the kernels instead)
+static int check_overlay_lists(lpf_ctx *c, int F, const lpf_depth_overlay_input *in, long long hw)
+{
+    const int M = in->M;
+    const long long cap = in->cap;
+    for (int f = 0; f < F; ++f) {
+        const int64_t *off = in->car_off + (size_t)f * (M + 1);
+        const int64_t *pix = in->pix ? in->pix + (size_t)f * cap : nullptr;
+        const double *dep = in->depth ? in->depth + (size_t)f * cap : nullptr;
+        if (off[0] < 0 || off[M] > cap)
+            return fail(c, LPF_ERR_ARG, "depth_overlays: frame %d: car_off %lld .. %lld outside [0, cap = %lld]", f, (long long)off[0], (long long)off[M], cap);
+        for (int m = 0; m < M; ++m) {
+            if (off[m + 1] < off[m])
+                return fail(c, LPF_ERR_ARG, "depth_overlays: frame %d: car_off decreases at car %d", f, m);
+            for (int64_t e = off[m]; e < off[m + 1]; ++e) {
+                if (pix[e] < 0 || pix[e] >= hw || (e > off[m] && pix[e] <= pix[e - 1]))
+                    return fail(c, LPF_ERR_ARG, "depth_overlays: frame %d car %d: pixel %lld at entry %lld is outside the image or not ascending",
+                                f, m, (long long)pix[e], (long long)e);
+                if (!(std::isfinite(dep[e]) && dep[e] > 0.0))
+                    return fail(c, LPF_ERR_ARG, "depth_overlays: frame %d car %d: depth %g at entry %lld is not finite and > 0", f, m, dep[e], (long long)e);
+            }
+        }
+    }
+    return LPF_OK;
+}
+
+int lpf_depth_overlays(lpf_ctx *c, int F, const lpf_depth_overlay_input *in, const lpf_depth_overlay_outputs *out)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (use_device(c)) return LPF_ERR_HIP;
+    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_depth_overlays cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
+    if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera has not been called");
+    if (!in || !out || F < 0) return fail(c, LPF_ERR_ARG, "depth_overlays: in=%p out=%p F=%d", (const void *)in, (const void *)out, F);
+    const int M = in->M;
+    if (M < 0 || M > LPF_MAX_MASKS_WIDE)
+        return fail(c, LPF_ERR_ARG, "depth_overlays: M=%d cars per frame, lpf_depth_overlays takes 0 .. LPF_MAX_MASKS_WIDE = %d", M, LPF_MAX_MASKS_WIDE);
+    if (in->cap < 0 || !in->car_off || (M > 0 && !in->seg) || (in->cap > 0 && (!in->pix || !in->depth)))
+        return fail(c, LPF_ERR_ARG, "depth_overlays: cap=%lld pix=%p depth=%p car_off=%p seg=%p (car_off is required, seg with M > 0, pix and depth with cap > 0)",
+                    (long long)in->cap, (const void *)in->pix, (const void *)in->depth, (const void *)in->car_off, (const void *)in->seg);
+    if (M > 0 && !out->images && !out->max_depth) return fail(c, LPF_ERR_ARG, "depth_overlays: images and max_depth are both NULL");
+    const long long hw = (long long)c->W * c->H, cap = in->cap;
+    int rc;
+    if (!in->lists_on_device && F > 0 && (rc = check_overlay_lists(c, F, in, hw))) return rc;
+    if (F == 0 || M == 0) return LPF_OK;
+    // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+
+    lpf_ctx::DepthOverlays &D = c->dovl;
+    const size_t img_b = (size_t)hw * 3, total = (size_t)F * M;
+    const bool host_seg = !in->seg_on_device, host_lists = !in->lists_on_device;
+    const bool want_img = out->images != nullptr, host_img = want_img && !out->on_device, host_mx = out->max_depth && !out->on_device;
+    const size_t pix_b = (size_t)cap * 8, off_b = (size_t)(M + 1) * 8;
+    auto a256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t per_image = host_img ? img_b : 0;
+    const size_t per_frame = (host_seg ? img_b : 0) + (host_lists ? 2 * pix_b + off_b : 0);
+
+    // ---- the chunks: [i0, i0 + n) of the F * M images, planned first ----------------------------------------------------------
+    std::vector<std::pair<size_t, size_t>> chunks;
+    size_t most_img = 0, most_fr = 0;
+    for (size_t i0 = 0; i0 < total;) {
+        size_t n = 1;
+        auto cost = [&](size_t k) { return k * per_image + ((i0 + k - 1) / M - i0 / M + 1) * per_frame; };
+        while (i0 + n < total && n < (size_t)LPF_DO_MAX_IMAGES && cost(n + 1) <= LPF_DO_BUDGET) ++n;
+        chunks.emplace_back(i0, n);
+        most_img = std::max(most_img, n);
+        most_fr = std::max(most_fr, (i0 + n - 1) / M - i0 / M + 1);
+        i0 += n;
+    }
+    const size_t o_dep = a256(most_fr * pix_b), o_off = o_dep + a256(most_fr * pix_b);
+    if (host_seg && (rc = reserve(c, D.seg, most_fr * img_b))) return rc;
+    if (host_lists && (rc = reserve(c, D.lists, o_off + most_fr * off_b))) return rc;
+    if (host_img && (rc = reserve(c, D.img, most_img * img_b))) return rc;
+    if (host_mx && (rc = reserve(c, D.mx, total * 8))) return rc;
+
+    LpfDoParams Q;
+    memset(&Q, 0, sizeof Q);
+    Q.hw = hw; Q.M = M; Q.cap = cap;
+    Q.mx = host_mx ? (double *)D.mx.p : out->max_depth;
+    const unsigned char *seg_k = host_seg ? (const unsigned char *)D.seg.p : in->seg;
+    unsigned char *img_k = host_img ? (unsigned char *)D.img.p : out->images;
+    // pixels per render thread: 16 (three dwordx4) or 4 (three dwords) when that divides W * H and the bases allow it, else 1
+    auto fits = [&](uintptr_t al) { return hw % (long long)al == 0 && ((uintptr_t)seg_k % al) == 0 && ((uintptr_t)img_k % al) == 0; };
+    const int P = fits(16) ? 16 : fits(4) ? 4 : 1;
+    const unsigned gx = (unsigned)(((hw + P - 1) / P + LPF_BLOCK - 1) / LPF_BLOCK);
+    for (const auto &ch : chunks) {
+        const size_t i0 = ch.first, n = ch.second, fa = i0 / M, nf = (i0 + n - 1) / M - fa + 1;
+        Q.i0 = (long long)i0; Q.n = (long long)n;
+        if (host_seg) {
+            LPF_HIP(c, hipMemcpyAsync(D.seg.p, in->seg + fa * img_b, nf * img_b, hipMemcpyHostToDevice, c->stream));
+            Q.seg = (const unsigned char *)D.seg.p; Q.seg_f0 = (long long)fa;
+        } else {
+            Q.seg = in->seg; Q.seg_f0 = 0;
+        }
+        if (host_lists) {
+            char *L = (char *)D.lists.p;
+            if (cap > 0) {
+                LPF_HIP(c, hipMemcpyAsync(L, in->pix + fa * cap, nf * pix_b, hipMemcpyHostToDevice, c->stream));
+                LPF_HIP(c, hipMemcpyAsync(L + o_dep, in->depth + fa * cap, nf * pix_b, hipMemcpyHostToDevice, c->stream));
+            }
+            LPF_HIP(c, hipMemcpyAsync(L + o_off, in->car_off + fa * (M + 1), nf * off_b, hipMemcpyHostToDevice, c->stream));
+            Q.pix = (const long long *)L; Q.depth = (const double *)(L + o_dep); Q.car_off = (const long long *)(L + o_off);
+            Q.list_f0 = (long long)fa;
+        } else {
+            Q.pix = (const long long *)in->pix; Q.depth = in->depth; Q.car_off = (const long long *)in->car_off; Q.list_f0 = 0;
+        }
+        Q.img = want_img ? (host_img ? img_k : img_k + i0 * img_b) : nullptr;
+        if (want_img) {
+            const dim3 g(gx, (unsigned)n);
+            if (P == 16) hipLaunchKernelGGL(lpf_do_render<16>, g, dim3(LPF_BLOCK), 0, c->stream, Q);
+            else if (P == 4) hipLaunchKernelGGL(lpf_do_render<4>, g, dim3(LPF_BLOCK), 0, c->stream, Q);
+            else hipLaunchKernelGGL(lpf_do_render<1>, g, dim3(LPF_BLOCK), 0, c->stream, Q);
+            LPF_HIP(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(lpf_do_paint, dim3((unsigned)((n + 3) / 4)), dim3(LPF_BLOCK), 0, c->stream, Q);
+        LPF_HIP(c, hipGetLastError());
+        if (host_img) LPF_HIP(c, hipMemcpyAsync(out->images + i0 * img_b, D.img.p, n * img_b, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (host_mx) LPF_HIP(c, hipMemcpyAsync(out->max_depth, D.mx.p, total * 8, hipMemcpyDeviceToHost, c->stream));
+    if (host_img || host_mx || host_seg || host_lists) LPF_HIP(c, host_wait(c));    // host buffers filled, or free to be reused
     return LPF_OK;
 }
 

@@ -1414,6 +1414,85 @@ def process_frames_depth_maps(seq=0, cam_id=0, segmenter=None, image_loader=None
             yield frame, depth_maps_frames([FrameInputs(frame, scan, masks)], velo_to_rect, camera, depth_max, device, ctx)[0]
 
 
+def _overlay_segs(seg_images, n, H, W):
+    """The segmented images of depth_overlays_frames as ONE [F,H,W,3] uint8 batch: a NumPy array, or a GPU tensor when any image is
+    one.  An image that is not uint8 [H,W,3] at the camera's size raises ValueError (seg_with_pointcloud.py:178 would fail)."""
+    segs = list(seg_images)
+    if len(segs) != n:
+        raise ValueError("one segmented image per frame: %d frames, %d images" % (n, len(segs)))
+    for i, s in enumerate(segs):
+        dt = str(s.dtype) if _is_device_tensor(s) else np.asarray(s).dtype.name
+        if tuple(s.shape) != (H, W, 3) or dt not in ("uint8", "torch.uint8"):
+            raise ValueError("segmented image %d must be uint8 [%d,%d,3] at the camera's size, got %s %s" % (i, H, W, dt, tuple(s.shape)))
+    if any(_is_device_tensor(s) for s in segs):
+        import torch
+        dev = next(s.device for s in segs if _is_device_tensor(s))
+        return torch.stack([s.to(dev) if _is_device_tensor(s) else torch.from_numpy(np.ascontiguousarray(s)).to(dev) for s in segs])
+    return np.stack([np.asarray(s) for s in segs]) if segs else np.zeros((0, H, W, 3), np.uint8)
+
+
+def depth_overlays_frames(frames, seg_images, TrVeloToRect, camera, depth_max=30.0, device=0, ctx=None):
+    """seg_with_pointcloud.py:160-180 for a list of FrameInputs: per frame ``[(car_id, SparseDepthMap, overlay)]`` for the cars with
+    at least one pixel, in the script's car order.  ``overlay`` is uint8 [H,W,3], the script's image_withseg after
+    cv2.cvtColor(RGB2BGR) byte for byte (a NumPy array, or a GPU tensor when the segmented images are on the GPU).  seg_images: one
+    uint8 [H,W,3] segmented image per frame (the segmenter's first result) at the camera's size.  The depth maps come from
+    depth_maps_frames (ragged mask counts, groups of 256 masks), the overlays from one lpf_depth_overlays call per group of up to
+    256 nonzero cars per frame.  The depth window is (0, depth_max)."""
+    frames = list(frames)
+    H, W = int(camera.height), int(camera.width)
+    segs = _overlay_segs(seg_images, len(frames), H, W)
+    if not frames:
+        return []
+    ctx = ctx or get_context(device)
+    maps = depth_maps_frames(frames, TrVeloToRect, camera, depth_max, device, ctx)
+    cars = [[(cid, sm) for cid, sm in fr if len(sm)] for fr in maps]      # the script's `if np.max(depthMap) == 0: continue`
+    out = [[] for _ in frames]
+    for g in range(0, max(len(c) for c in cars), LPF_MAX_MASKS_WIDE):
+        part = [c[g:g + LPF_MAX_MASKS_WIDE] for c in cars]
+        M = max(len(c) for c in part)
+        empty = (np.zeros(0, np.int64), np.zeros(0, np.float64))
+        lists = [[(sm.pixels, sm.depth) for _, sm in c] + [empty] * (M - len(c)) for c in part]
+        images, _ = ctx.depth_overlays(lists, segs)
+        for f, c in enumerate(part):
+            for j, (cid, sm) in enumerate(c):
+                out[f].append((cid, sm, images[f, j]))
+    return out
+
+
+def process_frames_depth_overlays(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_path=None, frames=None, depth_max=30.0,
+                                  device=0):
+    """process_frames_depth_maps' frame loop (seg_with_pointcloud.py:105-180) with the overlays: yields ``(frame, [(car_id,
+    SparseDepthMap, overlay)])`` per frame with detections, overlay = the image the script draws in its lower panel (:188), from the
+    segmenter's image ``seg[0]``.  Cars without a pixel are left out, as the script skips them (:174-175).  The figure and PNG writing
+    stay outside this package."""
+    if segmenter is None:
+        raise ValueError("process_frames_depth_overlays needs the segmentation callable (YOLO stays outside this package)")
+    if cam_id not in (0, 1):
+        raise ValueError("cam_id must be 0 or 1 (the perspective cameras), got %r" % (cam_id,))
+    root = kitti360_path or os.environ["KITTI360_DATASET"]
+    sequence, camera, velo_to_cam, velo_to_rect, velo = sequence_setup(root, seq, cam_id)
+    todo = velo.available_frames() if frames is None else list(frames)
+    paths = [os.path.join(velo.raw3DPcdPath, "%010d.bin" % f) for f in todo]
+    if not paths:
+        return
+    ctx = get_context(device)
+    sizes = [os.path.getsize(p) // 16 for p in paths if os.path.isfile(p)]
+    with ScanReader(ctx, paths, n_buffers=3, max_points=max(sizes + [1])) as reader:
+        for frame in todo:
+            scan = next(reader)
+            image_path = os.path.join(root, "data_2d_raw", sequence, "image_%02d" % cam_id,
+                                      "data_rect" if cam_id in [0, 1] else "data_rgb", "%010d.png" % frame)
+            if not os.path.isfile(image_path):
+                raise RuntimeError(f'Image file {image_path} does not exist!')
+            seg = segmenter(image_loader(image_path) if image_loader else image_path)
+            masks = seg[1] if seg is not None else None
+            if masks is None or len(masks) == 0:
+                print(f"[INFO] No cars detected in frame {frame}, skipping.")
+                continue
+            yield frame, depth_overlays_frames([FrameInputs(frame, scan, masks)], [seg[0]], velo_to_rect, camera, depth_max, device,
+                                               ctx)[0]
+
+
 def process_frames_multicam(seq=0, cam_ids=(0, 1), segmenter=None, image_loader=None, kitti360_path=None, master_csv_paths=None,
                             frames=None, erode_iters=0, v3_pipeline=False, device=0, timestamp=None):
     """process_frames for several perspective cameras of the rig at once: each scan is read once (the native read-ahead reader) and
