@@ -54,7 +54,8 @@ extern "C" {
                                          nothing else changed)
                                       8 (continued): lpf_depth_maps_outputs, lpf_depth_maps (added; nothing else changed)
                                       8 (continued): lpf_depth_overlay_input, lpf_depth_overlay_outputs, lpf_depth_overlays (added;
-                                         nothing else changed) */
+                                         nothing else changed)
+                                      8 (continued): lpf_match2d_input, lpf_match2d_outputs, lpf_match_2d (added; nothing else changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -488,6 +489,59 @@ typedef struct lpf_depth_overlay_outputs {
     int32_t  reserved;
 } lpf_depth_overlay_outputs;
 int lpf_depth_overlays(lpf_ctx *ctx, int F, const lpf_depth_overlay_input *in, const lpf_depth_overlay_outputs *out);
+
+/* lpf_match_2d: the pair stage of V4's and V5's detection-to-box matching for a batch of F frames in ONE call: every (detection,
+ * projected box) pair of every frame is scored as calculate_iou_2d (V4:118-137) and calculate_matching_score (V5:277-304) score it,
+ * and every detection gets match_detections_to_bboxes' choice (V4:170-178).  Frame f owns detections det_off[f] .. det_off[f + 1]
+ * (D_f of them) and boxes box_off[f] .. box_off[f + 1] (B_f); its matrices are the [D_f][B_f] block at pair_off[f] = sum_{g<f} D_g *
+ * B_g of the [P] outputs (64-bit arithmetic).  The boxes' rectangles are what lpf_prepare_boxes / lpf_set_boxes_cam0 write.
+ * The arithmetic is the reference's, type for type (NumPy 2 promotion of np.float32 detections against int64 / float64 boxes): with T
+ * the detections' type (float32, or float64 under dets_f64) and every operation separate,
+ *   xa = box x0 if box x0 > det x1 else det x1;  xb = box x1 if box x1 < det x2 else det x2;  same for y;  iou = 0 if xb <= xa or yb <= ya
+ *   xb - xa: a T subtraction when both ends are the detection's, else float64; the product of the two differences is a T
+ *   multiplication only when both are T;  area1 = (x2 - x1) * (y2 - y1) in T;  area2 in float64
+ *   union = area1 + area2 - inter in float64, left to right;  iou = inter / union if union > 0 else 0
+ *   detection centre (x1 + x2) / 2, (y1 + y2) / 2 in T, box centre in float64;  dist = sqrt(fma(dy, dy, dx * dx)) of the float64
+ *   differences (np.linalg.norm);  center_score = c if c > 0 else 0 with c = 1 - dist / 1000
+ *   size_score = min(area1, area2) / max(area1, area2) if both > 0 else 0
+ *   total_score = w_iou * iou + w_center * center_score + w_size * size_score, left to right;  cost = 1 - total_score
+ *   (equal areas: min and max both return area1, the ratio is a T 1.0 and w_size times it a T product: the size term is (T)w_size)
+ * best_box[d] is the first strict maximum of the IoU over the frame's boxes in list order among those with iou > min_iou (an index
+ * into the frame's boxes), -1 if there is none; best_iou[d] that IoU, 0 if none.  A box with front == 0 has no projection (V4:162-164
+ * skips it): its column is iou 0, scores 0, cost 1 and it never wins; V5 drops such columns before the assignment (V5:337-341).
+ * Degenerate detections (x2 < x1) follow the same statements; with non-finite coordinates the values are unspecified, but nothing
+ * is read or written out of bounds.  A frame may have no detections or no boxes (its detections get -1 / 0); F = 0 does nothing.
+ * Needs no camera, masks or boxes in force and leaves all of them as they were.  Not capturable (LPF_ERR_STATE between
+ * lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it first launches what the pipeline owes (no host wait).
+ * With every pointer device memory the call only enqueues work on the context's stream (the offsets go through the pinned upload
+ * ring); otherwise it returns after one host wait, with host outputs filled.
+ * LPF_ERR_ARG: NULL in / out, F < 0, NULL offsets, det_off[0] or box_off[0] < 0, decreasing offsets, dets NULL with detections,
+ * bbox2d or front NULL with boxes, non-finite min_iou or weights.
+ * Device memory: 24 bytes per frame; host inputs and outputs are staged frame range by frame range, each range within 256 MiB of
+ * scratch, or one frame when a single frame needs more. */
+typedef struct lpf_match2d_input {
+    const void    *dets;       /* [Dtot][4] {x1, y1, x2, y2}: float32 (the detector's boxes.xyxy, V4:64), or float64 under dets_f64 */
+    const int32_t *det_off;    /* [F + 1], host memory */
+    const double  *bbox2d;     /* [Btot][4] {min u, min v, max u, max v} */
+    const int32_t *front;      /* [Btot] corners with depth > 0; 0 = the box has no projection */
+    const int32_t *box_off;    /* [F + 1], host memory */
+    int32_t        dets_f64;
+    int32_t        on_device;  /* dets, bbox2d, front are device memory, lent until the call's work has completed */
+    double         min_iou;    /* V4: 0.25, firsttest.py: 0.1 */
+    double         w_iou, w_center, w_size;   /* V5: 0.5, 0.3, 0.2 */
+} lpf_match2d_input;
+typedef struct lpf_match2d_outputs {           /* any pointer may be NULL: only what is asked for is computed and stored */
+    int32_t *best_box;         /* [Dtot] */
+    double  *best_iou;         /* [Dtot] */
+    double  *iou;              /* [P] */
+    double  *center_score;     /* [P] */
+    double  *size_score;       /* [P] */
+    double  *total_score;      /* [P] */
+    double  *cost;             /* [P] the matrix V5:356 hands to linear_sum_assignment */
+    int32_t  on_device;
+    int32_t  reserved;
+} lpf_match2d_outputs;
+int lpf_match_2d(lpf_ctx *ctx, int F, const lpf_match2d_input *in, const lpf_match2d_outputs *out);
 
 /* cv2.resize(mask.astype(np.uint8), (camera.width, camera.height)) (V3:222; INTER_LINEAR, the default) for masks that do not arrive at
  * the camera's size (the reference's scripts all pass retina_masks=True, so theirs do): n planes [h][w] of uint8 -> n planes [H][W]

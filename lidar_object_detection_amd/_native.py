@@ -79,6 +79,19 @@ class DepthOverlayOutputs(ctypes.Structure):
     _fields_ = [("images", _P), ("max_depth", _P), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class Match2dInput(ctypes.Structure):
+    """lpf_match2d_input (include/lpf.h): the detections and projected boxes of a batch of frames for lpf_match_2d"""
+    _fields_ = [("dets", _P), ("det_off", _P), ("bbox2d", _P), ("front", _P), ("box_off", _P), ("dets_f64", ctypes.c_int32),
+                ("on_device", ctypes.c_int32), ("min_iou", ctypes.c_double), ("w_iou", ctypes.c_double), ("w_center", ctypes.c_double),
+                ("w_size", ctypes.c_double)]
+
+
+class Match2dOutputs(ctypes.Structure):
+    """lpf_match2d_outputs (include/lpf.h): V4's choice per detection and V5's score matrices per pair"""
+    _fields_ = [("best_box", _P), ("best_iou", _P), ("iou", _P), ("center_score", _P), ("size_score", _P), ("total_score", _P),
+                ("cost", _P), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 LPF_MAX_CAMS = 4                        # lpf_run_cams / lpf_run_cams_wide: cameras of one pass
 
 
@@ -244,6 +257,7 @@ def load(path=None):
     lib.lpf_run_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(WideOutputs)]
     lib.lpf_depth_maps.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(DepthMapsOutputs)]
     lib.lpf_depth_overlays.argtypes = [_P, ctypes.c_int, ctypes.POINTER(DepthOverlayInput), ctypes.POINTER(DepthOverlayOutputs)]
+    lib.lpf_match_2d.argtypes = [_P, ctypes.c_int, ctypes.POINTER(Match2dInput), ctypes.POINTER(Match2dOutputs)]
     lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_cams_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(WideOutputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
@@ -280,7 +294,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_graph_begin", "lpf_graph_end", "lpf_graph_launch", "lpf_graph_destroy",
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
-            "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays")
+            "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -1335,6 +1349,127 @@ class LpfContext:
         o.images, o.max_depth = images.ctypes.data, mx.ctypes.data
         self._check(self._lib.lpf_depth_overlays(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
         return images, mx
+
+    MATCH2D_WANT = ("best", "iou", "center", "size", "total", "cost")
+    _MATCH2D_FIELD = {"iou": "iou", "center": "center_score", "size": "size_score", "total": "total_score", "cost": "cost"}
+
+    @staticmethod
+    def match2d_batch(dets, bbox2d, front):
+        """The per-frame lists of match_2d checked and described: (on_device, dets dtype name, det_off int32 [F+1], box_off int32
+        [F+1]).  ValueError for frame counts that differ, detections that are not float32 / float64 [D,4] of one dtype, rectangles that
+        are not [B,4], front counts that are not [B], and host arrays mixed with GPU tensors."""
+        dets, bbox2d, front = list(dets), list(bbox2d), list(front)
+        if not (len(dets) == len(bbox2d) == len(front)):
+            raise ValueError("match_2d: one entry per frame in each list, got %d detections, %d bbox2d, %d front" % (len(dets), len(bbox2d), len(front)))
+        every = dets + bbox2d + front
+        n_dev = sum(1 for a in every if _is_torch(a) and a.is_cuda)
+        if n_dev not in (0, len(every)):
+            raise ValueError("match_2d: host arrays and GPU tensors are mixed (%d of %d inputs are on the GPU)" % (n_dev, len(every)))
+        dev = n_dev > 0
+        name = lambda a: str(a.dtype).replace("torch.", "")
+        dtypes = set()
+        det_off, box_off = np.zeros(len(dets) + 1, np.int64), np.zeros(len(dets) + 1, np.int64)
+        for f, (d, b, fr) in enumerate(zip(dets, bbox2d, front)):
+            if not dev:
+                d, b, fr = np.asarray(d), np.asarray(b), np.asarray(fr)
+            if len(d.shape) != 2 or d.shape[1] != 4:
+                raise ValueError("match_2d: frame %d: detections must be [D,4] (x1, y1, x2, y2), got %s" % (f, tuple(d.shape)))
+            if name(d) not in ("float32", "float64"):
+                raise ValueError("match_2d: frame %d: detections must be float32 or float64, got %s" % (f, name(d)))
+            dtypes.add(name(d))
+            if len(b.shape) != 2 or b.shape[1] != 4:
+                raise ValueError("match_2d: frame %d: bbox2d must be [B,4] (min u, min v, max u, max v), got %s" % (f, tuple(b.shape)))
+            if tuple(fr.shape) != (b.shape[0],):
+                raise ValueError("match_2d: frame %d: front must be [B] = [%d], got %s" % (f, b.shape[0], tuple(fr.shape)))
+            if dev and (name(b) != "float64" or name(fr) != "int32"):
+                raise ValueError("match_2d: frame %d: GPU bbox2d must be float64 and front int32, got %s and %s" % (f, name(b), name(fr)))
+            if not dev and (np.asarray(b).dtype.kind not in "fiu" or np.asarray(fr).dtype.kind not in "iub"):
+                raise ValueError("match_2d: frame %d: bbox2d must be numbers and front integers, got %s and %s" % (f, name(b), name(fr)))
+            det_off[f + 1] = det_off[f] + d.shape[0]
+            box_off[f + 1] = box_off[f] + b.shape[0]
+        if len(dtypes) > 1:
+            raise ValueError("match_2d: the detections of a call share one dtype, got %s" % sorted(dtypes))
+        if det_off[-1] > 0x7fffffff or box_off[-1] > 0x7fffffff:
+            raise ValueError("match_2d: %d detections and %d boxes, a call takes fewer than 2^31 of each" % (det_off[-1], box_off[-1]))
+        return dev, (dtypes.pop() if dtypes else "float32"), det_off.astype(np.int32), box_off.astype(np.int32)
+
+    def match_2d(self, dets, bbox2d, front, min_iou=0.25, weights=(0.5, 0.3, 0.2), want=("best",)):
+        """V4's and V5's detection-to-box scoring for a batch of frames in ONE native call (lpf_match_2d).  Per frame: ``dets`` [D,4]
+        float32 (the detector's boxes.xyxy) or float64, ``bbox2d`` float64 [B,4] and ``front`` int32 [B] as prepare_boxes returns them;
+        all host arrays or all GPU tensors.  ``want`` picks the outputs: "best" (V4: best_box int32 [D], the first strict maximum of the
+        IoU above min_iou into the frame's boxes or -1, and best_iou float64 [D]) and the [D,B] float64 matrices "iou", "center",
+        "size", "total", "cost" of V5 (cost = 1 - total: what V5 hands to linear_sum_assignment; a column of a box with front == 0 is
+        iou 0, scores 0, cost 1).  Returns a dict of per-frame lists, keys "best_box", "best_iou" and the matrices' names.  The
+        arithmetic is the reference's, type for type (include/lpf.h).  Host arrays: NumPy results after one host wait; GPU tensors:
+        torch tensors on their device in torch's stream order (the call only enqueues work)."""
+        want = tuple(want)
+        bad = [w for w in want if w not in self.MATCH2D_WANT]
+        if bad or not want:
+            raise ValueError("match_2d: want is a selection of %s, got %r" % (self.MATCH2D_WANT, want))
+        weights = tuple(float(w) for w in weights)
+        if len(weights) != 3 or not all(np.isfinite(weights)) or not np.isfinite(float(min_iou)):
+            raise ValueError("match_2d: min_iou and the three weights (iou, center, size) must be finite numbers")
+        dets, bbox2d, front = list(dets), list(bbox2d), list(front)
+        dev, dt, det_off, box_off = self.match2d_batch(dets, bbox2d, front)
+        F = len(dets)
+        Dtot, Btot = int(det_off[-1]), int(box_off[-1])
+        D, B = np.diff(det_off).astype(np.int64), np.diff(box_off).astype(np.int64)
+        pair_off = np.concatenate([[0], np.cumsum(D * B)]).astype(np.int64)
+        P = int(pair_off[-1])
+        inp, o = Match2dInput(), Match2dOutputs()
+        inp.det_off, inp.box_off = det_off.ctypes.data, box_off.ctypes.data
+        inp.dets_f64 = int(dt == "float64")
+        inp.min_iou, (inp.w_iou, inp.w_center, inp.w_size) = float(min_iou), weights
+        mats = [w for w in want if w != "best"]
+        res = {}
+        if dev:
+            import torch
+            d = (dets + bbox2d + front)[0].device
+            tdt = torch.float64 if dt == "float64" else torch.float32
+            dd = torch.cat([x.reshape(-1, 4) for x in dets]).contiguous() if Dtot else torch.zeros((0, 4), dtype=tdt, device=d)
+            bb = torch.cat([x.reshape(-1, 4) for x in bbox2d]).contiguous() if Btot else torch.zeros((0, 4), dtype=torch.float64, device=d)
+            ff = torch.cat(list(front)).contiguous() if Btot else torch.zeros(0, dtype=torch.int32, device=d)
+            flat = {}
+            if "best" in want:
+                flat["best_box"] = torch.full((Dtot,), -1, dtype=torch.int32, device=d)
+                flat["best_iou"] = torch.zeros(Dtot, dtype=torch.float64, device=d)
+            for w in mats:
+                flat[w] = torch.empty(P, dtype=torch.float64, device=d)
+            inp.dets, inp.bbox2d, inp.front = (dd.data_ptr() if Dtot else None), (bb.data_ptr() if Btot else None), (ff.data_ptr() if Btot else None)
+            inp.on_device = o.on_device = 1
+        else:
+            dd = np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in dets]), dtype=dt) if Dtot else np.zeros((0, 4), dt)
+            bb = (np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in bbox2d]), dtype=np.float64) if Btot
+                  else np.zeros((0, 4), np.float64))
+            ff = np.ascontiguousarray(np.concatenate([np.asarray(x) for x in front]), dtype=np.int32) if Btot else np.zeros(0, np.int32)
+            flat = {}
+            if "best" in want:
+                flat["best_box"] = np.full(Dtot, -1, np.int32)
+                flat["best_iou"] = np.zeros(Dtot, np.float64)
+            for w in mats:
+                flat[w] = np.empty(P, np.float64)
+            inp.dets, inp.bbox2d, inp.front = (dd.ctypes.data if Dtot else None), (bb.ctypes.data if Btot else None), (ff.ctypes.data if Btot else None)
+        ptr = (lambda a: a.data_ptr()) if dev else (lambda a: a.ctypes.data)
+        if "best" in want and Dtot:
+            o.best_box, o.best_iou = ptr(flat["best_box"]), ptr(flat["best_iou"])
+        for w in mats:
+            if P:
+                setattr(o, self._MATCH2D_FIELD[w], ptr(flat[w]))
+        if F and Dtot:
+            if dev:
+                import torch
+                ts = torch.cuda.current_stream(d).cuda_stream
+                self.wait_for_stream(ts)                # the inputs and the outputs' memory belong to torch's stream
+                self._check(self._lib.lpf_match_2d(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
+                self.release_to_stream(ts)
+            else:
+                self._check(self._lib.lpf_match_2d(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
+        for k in ("best_box", "best_iou"):
+            if k in flat:
+                res[k] = [flat[k][det_off[f]:det_off[f + 1]] for f in range(F)]
+        for w in mats:
+            res[w] = [flat[w][pair_off[f]:pair_off[f + 1]].reshape(int(D[f]), int(B[f])) for f in range(F)]
+        return res
 
     def run_cams_wide(self, frames, cams, want_uv=True, want_float=False, want_lists=True, want_valid_uv=False, inst_cap=None,
                       want_label=True, pinned=False):

@@ -8,6 +8,7 @@
 #include "lpf_frame_wide.hip.h"
 #include "lpf_depth_maps.hip.h"
 #include "lpf_depth_overlays.hip.h"
+#include "lpf_match2d.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -187,6 +188,8 @@ struct lpf_ctx {
     // lpf_depth_overlays: a chunk's staged segmented images and lists, images for host outputs, max_depth for host outputs
     // (grow-only, allocated on first use)
     struct DepthOverlays { DevBuf seg, lists, img, mx; } dovl;
+    // lpf_match_2d: the frame table, a frame range's staged detections and boxes, its staged outputs (grow-only, allocated on first use)
+    struct Match2d { DevBuf tab, in, out; } m2d;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -1197,6 +1200,8 @@ void lpf_destroy(lpf_ctx *c)
                       &c->dmaps.rects, &c->dmaps.pts, &c->dmaps.out})
         release(*b);
     for (DevBuf *b : {&c->dovl.seg, &c->dovl.lists, &c->dovl.img, &c->dovl.mx})
+        release(*b);
+    for (DevBuf *b : {&c->m2d.tab, &c->m2d.in, &c->m2d.out})
         release(*b);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_uvv, &c->st_labv, &c->st_pts, &c->st_uv, &c->st_label,
                      &c->st_depth, &c->st_uf, &c->st_vf, &c->st_valid, &c->st_inst, &c->st_count, &c->st_summary};
@@ -2616,6 +2621,149 @@ int lpf_depth_overlays(lpf_ctx *c, int F, const lpf_depth_overlay_input *in, con
     }
     if (host_mx) LPF_HIP(c, hipMemcpyAsync(out->max_depth, D.mx.p, total * 8, hipMemcpyDeviceToHost, c->stream));
     if (host_img || host_mx || host_seg || host_lists) LPF_HIP(c, host_wait(c));    // host buffers filled, or free to be reused
+    return LPF_OK;
+}
+
+// ---- lpf_match_2d (include/lpf.h): V4 / V5 pair scoring of a batch, kernel in lpf_match2d.hip.h ---------------------------------------
+// With every array in device memory the whole batch is one launch on the caller's arrays.  Host arrays go through in ranges of
+// consecutive frames: a range's scratch -- its staged detections, rectangles and front counts when the inputs are in host memory, its
+// best_box / best_iou rows and matrices when the outputs are -- stays within LPF_M2_BUDGET, or one frame when a single frame needs
+// more.  The ranges are planned and every buffer reserved before the first launch, so no range waits for the one before it.
+#define LPF_M2_BUDGET (256ull << 20)
+#define LPF_M2_MAX_FRAMES 65535             // frames per launch: the grid's y
+#define LPF_M2_TAB_PIECE 32768              // frames per upload of the frame table: under a quarter of the pinned ring, so it never waits
+
+int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match2d_outputs *out)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (use_device(c)) return LPF_ERR_HIP;
+    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_match_2d cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
+    if (!in || !out || F < 0) return fail(c, LPF_ERR_ARG, "match_2d: in=%p out=%p F=%d", (const void *)in, (const void *)out, F);
+    if (!in->det_off || !in->box_off)
+        return fail(c, LPF_ERR_ARG, "match_2d: det_off=%p box_off=%p (both are required, F + 1 entries each)", (const void *)in->det_off, (const void *)in->box_off);
+    if (in->det_off[0] < 0 || in->box_off[0] < 0)
+        return fail(c, LPF_ERR_ARG, "match_2d: det_off[0]=%d box_off[0]=%d (offsets start at 0 or above)", in->det_off[0], in->box_off[0]);
+    for (int f = 0; f < F; ++f) {
+        if (in->det_off[f + 1] < in->det_off[f]) return fail(c, LPF_ERR_ARG, "match_2d: det_off decreases at frame %d", f);
+        if (in->box_off[f + 1] < in->box_off[f]) return fail(c, LPF_ERR_ARG, "match_2d: box_off decreases at frame %d", f);
+    }
+    const int Dtot = in->det_off[F], Btot = in->box_off[F];
+    if ((Dtot > 0 && !in->dets) || (Btot > 0 && (!in->bbox2d || !in->front)))
+        return fail(c, LPF_ERR_ARG, "match_2d: dets=%p bbox2d=%p front=%p with %d detections and %d boxes (dets is required with detections, bbox2d and front with boxes)",
+                    in->dets, (const void *)in->bbox2d, (const void *)in->front, Dtot, Btot);
+    if (!std::isfinite(in->min_iou) || !std::isfinite(in->w_iou) || !std::isfinite(in->w_center) || !std::isfinite(in->w_size))
+        return fail(c, LPF_ERR_ARG, "match_2d: min_iou=%g weights=%g %g %g must be finite", in->min_iou, in->w_iou, in->w_center, in->w_size);
+    double *const mats_out[5] = {out->iou, out->center_score, out->size_score, out->total_score, out->cost};
+    int nmat = 0;
+    for (double *m : mats_out) nmat += m != nullptr;
+    const bool want_best = out->best_box || out->best_iou;
+    if (F == 0 || in->det_off[F] == in->det_off[0] || (!want_best && !nmat)) return LPF_OK;
+    int rc;
+    // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+
+    lpf_ctx::Match2d &D = c->m2d;
+    const bool host_in = !in->on_device, host_out = !out->on_device;
+    const size_t esz = in->dets_f64 ? 8 : 4;
+    auto a256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+
+    // ---- the frame table and the ranges [fa, fb), planned first ------------------------------------------------------------------
+    std::vector<LpfM2Frame> tab((size_t)F);
+    long long p = 0;
+    for (int f = 0; f < F; ++f) {
+        LpfM2Frame &t = tab[(size_t)f];
+        t.d0 = in->det_off[f]; t.D = in->det_off[f + 1] - t.d0;
+        t.b0 = in->box_off[f]; t.B = in->box_off[f + 1] - t.b0;
+        t.p0 = p;
+        p += (long long)t.D * t.B;
+    }
+    auto frame_cost = [&](const LpfM2Frame &t) {
+        size_t b = 0;
+        if (host_in) b += (size_t)t.D * 4 * esz + (size_t)t.B * 36;
+        if (host_out) b += (size_t)t.D * 12 + (size_t)nmat * 8 * (size_t)t.D * (size_t)t.B;
+        return b;
+    };
+    struct Range { int fa, fb; };
+    std::vector<Range> ranges;
+    size_t most_d = 0, most_b = 0, most_p = 0;
+    for (int fa = 0; fa < F;) {
+        int fb = fa + 1;
+        size_t cost = frame_cost(tab[(size_t)fa]);
+        if (host_in || host_out)
+            while (fb < F && fb - fa < LPF_M2_MAX_FRAMES && cost + frame_cost(tab[(size_t)fb]) <= LPF_M2_BUDGET) cost += frame_cost(tab[(size_t)fb++]);
+        else
+            fb = std::min(F, fa + LPF_M2_MAX_FRAMES);
+        ranges.push_back({fa, fb});
+        most_d = std::max(most_d, (size_t)(in->det_off[fb] - in->det_off[fa]));
+        most_b = std::max(most_b, (size_t)(in->box_off[fb] - in->box_off[fa]));
+        most_p = std::max(most_p, (size_t)((fb < F ? tab[(size_t)fb].p0 : p) - tab[(size_t)fa].p0));
+        fa = fb;
+    }
+    const size_t i_box = a256(most_d * 4 * esz), i_front = i_box + a256(most_b * 32);       // staged inputs: dets | bbox2d | front
+    const size_t o_iou = a256(most_d * 4), o_mat = o_iou + a256(most_d * 8);                 // staged outputs: best_box | best_iou | matrices
+    if ((rc = reserve(c, D.tab, (size_t)F * sizeof(LpfM2Frame)))) return rc;
+    if (host_in && (rc = reserve(c, D.in, i_front + most_b * 4))) return rc;
+    if (host_out && (rc = reserve(c, D.out, o_mat + (size_t)nmat * a256(most_p * 8)))) return rc;
+    for (int f = 0; f < F; f += LPF_M2_TAB_PIECE) {
+        const size_t n = (size_t)std::min(F - f, LPF_M2_TAB_PIECE);
+        if ((rc = upload(c, (LpfM2Frame *)D.tab.p + f, tab.data() + f, n * sizeof(LpfM2Frame)))) return rc;
+    }
+
+    LpfM2Params Q;
+    memset(&Q, 0, sizeof Q);
+    Q.min_iou = in->min_iou; Q.w_iou = in->w_iou; Q.w_center = in->w_center; Q.w_size = in->w_size;
+    const bool scores = out->center_score || out->size_score || out->total_score || out->cost;
+    for (const Range &r : ranges) {
+        const int fa = r.fa, fb = r.fb, d0 = in->det_off[fa], nd = in->det_off[fb] - d0, b0 = in->box_off[fa], nb = in->box_off[fb] - b0;
+        const long long p0 = tab[(size_t)fa].p0, np = (fb < F ? tab[(size_t)fb].p0 : p) - p0;
+        int most_rows = 0;
+        for (int f = fa; f < fb; ++f) most_rows = std::max(most_rows, tab[(size_t)f].D);
+        if (most_rows == 0) continue;                       // no detections in the range: nothing to write
+        Q.frames = (const LpfM2Frame *)D.tab.p + fa;
+        if (host_in) {
+            char *S = (char *)D.in.p;
+            LPF_HIP(c, hipMemcpyAsync(S, (const char *)in->dets + (size_t)d0 * 4 * esz, (size_t)nd * 4 * esz, hipMemcpyHostToDevice, c->stream));
+            if (nb > 0) {
+                LPF_HIP(c, hipMemcpyAsync(S + i_box, in->bbox2d + (size_t)b0 * 4, (size_t)nb * 32, hipMemcpyHostToDevice, c->stream));
+                LPF_HIP(c, hipMemcpyAsync(S + i_front, in->front + b0, (size_t)nb * 4, hipMemcpyHostToDevice, c->stream));
+            }
+            Q.dets = S; Q.bbox2d = (const double *)(S + i_box); Q.front = (const int *)(S + i_front);
+            Q.det_base = d0; Q.box_base = b0;
+        } else {
+            Q.dets = in->dets; Q.bbox2d = in->bbox2d; Q.front = in->front;
+            Q.det_base = 0; Q.box_base = 0;
+        }
+        double *mats_k[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (host_out) {
+            char *S = (char *)D.out.p;
+            Q.best_box = out->best_box ? (int *)S : nullptr;
+            Q.best_iou = out->best_iou ? (double *)(S + o_iou) : nullptr;
+            for (int m = 0, k = 0; m < 5; ++m)
+                if (mats_out[m]) mats_k[m] = (double *)(S + o_mat + (size_t)k++ * a256(most_p * 8));
+            Q.det_out_base = d0; Q.pair_base = p0;
+        } else {
+            Q.best_box = out->best_box; Q.best_iou = out->best_iou;
+            for (int m = 0; m < 5; ++m) mats_k[m] = mats_out[m];
+            Q.det_out_base = 0; Q.pair_base = 0;
+        }
+        Q.iou = mats_k[0]; Q.center = mats_k[1]; Q.size = mats_k[2]; Q.total = mats_k[3]; Q.cost = mats_k[4];
+        const dim3 g((unsigned)((most_rows + LPF_M2_ROWS - 1) / LPF_M2_ROWS), (unsigned)(fb - fa));
+        if (in->dets_f64) {
+            if (scores) hipLaunchKernelGGL((lpf_m2_pairs<double, true>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
+            else hipLaunchKernelGGL((lpf_m2_pairs<double, false>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
+        } else {
+            if (scores) hipLaunchKernelGGL((lpf_m2_pairs<float, true>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
+            else hipLaunchKernelGGL((lpf_m2_pairs<float, false>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
+        }
+        LPF_HIP(c, hipGetLastError());
+        if (host_out) {
+            if (out->best_box) LPF_HIP(c, hipMemcpyAsync(out->best_box + d0, Q.best_box, (size_t)nd * 4, hipMemcpyDeviceToHost, c->stream));
+            if (out->best_iou) LPF_HIP(c, hipMemcpyAsync(out->best_iou + d0, Q.best_iou, (size_t)nd * 8, hipMemcpyDeviceToHost, c->stream));
+            for (int m = 0; m < 5; ++m)
+                if (mats_out[m] && np > 0) LPF_HIP(c, hipMemcpyAsync(mats_out[m] + p0, mats_k[m], (size_t)np * 8, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    if (host_in || host_out) LPF_HIP(c, host_wait(c));       // host outputs filled, host inputs free to be reused
     return LPF_OK;
 }
 

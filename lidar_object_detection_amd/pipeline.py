@@ -412,7 +412,7 @@ def calculate_car_point_statistics(car_point_sets, bboxes_3d, colors, min_points
 
 
 # ---------------------------------------------------------------------------------------
-# 2D IoU matching of V4 (V4:118-183) -- D x B scalars on the host
+# 2D IoU matching of V4 (V4:118-183) and V5 (V5:277-416), one frame at a time in host scalars: the yardstick of the batched forms below
 # ---------------------------------------------------------------------------------------
 def calculate_iou_2d(box1, box2):
     x1a, y1a, x1b, y1b = box1
@@ -543,6 +543,169 @@ def improved_match_detections_to_bboxes(boxes_2d, bboxes_3d, mask_colors, camera
             matched.append((np.array(bbox["corners_velo"]), [0.7, 0.7, 0.7]))
             print(f"[INFO] Added unmatched 3D bbox {i} in default color")
     return matched
+
+
+# ---------------------------------------------------------------------------------------
+# the same two matchers for a list of frames: the pair stage on the GPU (lpf_match_2d), one call per batch
+# ---------------------------------------------------------------------------------------
+def _match2d_dets(boxes_2d):
+    """A frame's detections as a [D,4] array: float32 stays float32 (the detector's boxes.xyxy), anything else becomes float64."""
+    if boxes_2d is None:
+        return np.zeros((0, 4), np.float32)
+    if type(boxes_2d).__module__.startswith("torch"):
+        boxes_2d = boxes_2d.detach().cpu().numpy()
+    d = np.asarray(boxes_2d)
+    if d.size == 0:
+        return np.zeros((0, 4), np.float32)
+    if d.dtype != np.float32:
+        d = d.astype(np.float64)
+    if d.ndim != 2 or d.shape[1] != 4:
+        raise ValueError("detections must be [D,4] (x1, y1, x2, y2), got %s" % (d.shape,))
+    return d
+
+
+def _match2d_rects(bboxes_per_frame, camera, ctx):
+    """Per frame (bbox2d float64 [B,4], front int32 [B]) for EVERY dict of the frame's list, in order: prepare_boxes' '_bbox2d' /
+    '_front' where a dict carries them, else the projection of its 'corners_cam0' -- all such boxes of the batch in ONE
+    lpf_prepare_boxes call.  front = 0 (the matchers skip the box) for a dict without 'corners_cam0' or without a corner in front."""
+    rects, todo, corners = [], [], []
+    for f, boxes in enumerate(bboxes_per_frame):
+        bb, fr = np.zeros((len(boxes), 4), np.float64), np.zeros(len(boxes), np.int32)
+        for j, b in enumerate(boxes):
+            if "corners_cam0" not in b:
+                continue
+            if "_bbox2d" in b:
+                if b["_bbox2d"] is not None:
+                    bb[j] = b["_bbox2d"]
+                    fr[j] = b.get("_front", 8) or 8
+            else:
+                todo.append((f, j))
+                corners.append(b["corners_cam0"])
+        rects.append((bb, fr))
+    if todo:
+        ctx.ensure_intrinsics(camera.K, camera.width, camera.height)
+        _, _, bb_all, fr_all = ctx.prepare_boxes(np.array(corners, np.float64).reshape(-1, 8, 3), np.eye(4))
+        for (f, j), bb, fr in zip(todo, bb_all, fr_all):
+            if fr > 0:
+                rects[f][0][j], rects[f][1][j] = bb, fr
+    return rects
+
+
+def _match2d_call(dets, rects, ctx, want, min_iou=0.25):
+    """ctx.match_2d over the frames that have detections and boxes, one call per detection dtype: per frame the dict of that frame's
+    outputs, or None for a frame the matchers leave before they score anything."""
+    out = [None] * len(dets)
+    for dt in (np.float32, np.float64):
+        idx = [f for f, d in enumerate(dets) if d is not None and d.dtype == dt and len(d) and len(rects[f][0])]
+        if not idx:
+            continue
+        res = ctx.match_2d([dets[f] for f in idx], [rects[f][0] for f in idx], [rects[f][1] for f in idx], min_iou=min_iou, want=want)
+        for k, f in enumerate(idx):
+            out[f] = {name: vals[k] for name, vals in res.items()}
+    return out
+
+
+def match_detections_frames(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame, camera, min_iou=0.25, device=0, ctx=None):
+    """match_detections_to_bboxes (V4:140-183) for a list of frames: per frame exactly the list that function returns, with the
+    IoU of every (detection, box) pair and each detection's first strict maximum computed by ONE lpf_match_2d call for the batch.
+    Box dicts without '_bbox2d' are projected for the whole batch by one lpf_prepare_boxes call."""
+    boxes_2d_per_frame, bboxes_3d_per_frame = list(boxes_2d_per_frame), list(bboxes_3d_per_frame)
+    colors_per_frame = list(colors_per_frame)
+    if not (len(boxes_2d_per_frame) == len(bboxes_3d_per_frame) == len(colors_per_frame)):
+        raise ValueError("one entry per frame in each list")
+    live = [bool(b) and d is not None and len(d) > 0 for d, b in zip(boxes_2d_per_frame, bboxes_3d_per_frame)]
+    dets = [_match2d_dets(d) if ok else None for d, ok in zip(boxes_2d_per_frame, live)]
+    out = [[] for _ in live]
+    if not any(live):
+        return out
+    ctx = ctx or get_context(device)
+    rects = _match2d_rects([b if ok else [] for b, ok in zip(bboxes_3d_per_frame, live)], camera, ctx)
+    res = _match2d_call(dets, rects, ctx, ("best",), min_iou)
+    for f, r in enumerate(res):
+        if r is None:
+            continue
+        boxes, colors = bboxes_3d_per_frame[f], colors_per_frame[f]
+        for det_idx, best_idx in enumerate(r["best_box"].tolist()):
+            if best_idx >= 0 and "corners_velo" in boxes[best_idx]:
+                c = colors[det_idx]
+                out[f].append((np.array(boxes[best_idx]["corners_velo"]), np.array([c[2], c[1], c[0]]) / 255.0))
+    return out
+
+
+def _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device=0, ctx=None):
+    """The score matrices of improved_match_detections_frames for a list of frames (one lpf_match_2d call): per frame None (the
+    matcher leaves before it scores) or (valid_idx, dict of [D, len(valid_idx)] matrices) -- V5's columns, the boxes with a projection."""
+    live = [bool(b) and d is not None and len(d) > 0 for d, b in zip(boxes_2d_per_frame, bboxes_3d_per_frame)]
+    dets = [_match2d_dets(d) if ok else None for d, ok in zip(boxes_2d_per_frame, live)]
+    if not any(live):
+        return [None] * len(live)
+    ctx = ctx or get_context(device)
+    rects = _match2d_rects([b if ok else [] for b, ok in zip(bboxes_3d_per_frame, live)], camera, ctx)
+    res = _match2d_call(dets, rects, ctx, ("iou", "center", "size", "total", "cost"))
+    out = []
+    for f, r in enumerate(res):
+        if r is None:
+            out.append(None)
+            continue
+        valid = np.flatnonzero(rects[f][1] > 0)
+        out.append((valid.tolist(), {k: np.asarray(v)[:, valid] for k, v in r.items()}))
+    return out
+
+
+def _improved_assign(boxes_2d, bboxes_3d, mask_colors, scores, min_score_threshold=0.3, min_iou_threshold=0.15):
+    """improved_match_detections_to_bboxes from its cost matrix on: the assignment, the thresholds, the returned list and every
+    printed line, with the pair scores read from lpf_match_2d's matrices (``scores``: a frame's entry of _improved_scores)."""
+    from scipy.optimize import linear_sum_assignment
+    matched = []
+    if not bboxes_3d or boxes_2d is None or len(boxes_2d) == 0:
+        print("[INFO] No detections or 3D bounding boxes to match")
+        return matched
+    print(f"[INFO] Matching {len(boxes_2d)} 2D detections with {len(bboxes_3d)} 3D bboxes")
+    valid_idx, m = scores
+    if not valid_idx:
+        print("[WARN] No valid 3D bbox projections found")
+        return matched
+    rows, cols = linear_sum_assignment(m["cost"])
+    iou, center, size, total = m["iou"], m["center"], m["size"], m["total"]
+    used = set()
+    for i, j in zip(rows, cols):
+        if total[i, j] >= min_score_threshold and iou[i, j] >= min_iou_threshold:
+            orig = valid_idx[j]
+            used.add(orig)
+            bbox = bboxes_3d[orig]
+            if "corners_velo" in bbox:
+                if i < len(mask_colors):
+                    c = mask_colors[i]
+                    color = np.array([c[2], c[1], c[0]], dtype=float) / 255.0
+                else:
+                    color = np.array([1.0, 0.0, 0.0])
+                matched.append((np.array(bbox["corners_velo"]), color))
+                print(f"[INFO] Matched detection {i} with 3D bbox {orig}")
+                print(f"        Scores - IoU: {iou[i, j]:.3f}, Center: {center[i, j]:.3f}, "
+                      f"Size: {size[i, j]:.3f}, Total: {total[i, j]:.3f}")
+            else:
+                print(f"[WARN] No Velodyne corners found for bbox {orig}")
+        else:
+            print(f"[INFO] Rejected match det{i}-bbox{j}: score={total[i, j]:.3f}, IoU={iou[i, j]:.3f}")
+    for i, bbox in enumerate(bboxes_3d):
+        if i not in used and "corners_velo" in bbox:
+            matched.append((np.array(bbox["corners_velo"]), [0.7, 0.7, 0.7]))
+            print(f"[INFO] Added unmatched 3D bbox {i} in default color")
+    return matched
+
+
+def improved_match_detections_frames(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame, camera, min_score_threshold=0.3,
+                                     min_iou_threshold=0.15, device=0, ctx=None):
+    """improved_match_detections_to_bboxes (V5:307-416) for a list of frames: per frame exactly the list that function returns and
+    the same printed lines in the same order.  The score of every (detection, box) pair of the batch comes from ONE lpf_match_2d
+    call; the assignment stays scipy's linear_sum_assignment on the cost matrix of the boxes that have a projection."""
+    boxes_2d_per_frame, bboxes_3d_per_frame = list(boxes_2d_per_frame), list(bboxes_3d_per_frame)
+    colors_per_frame = list(colors_per_frame)
+    if not (len(boxes_2d_per_frame) == len(bboxes_3d_per_frame) == len(colors_per_frame)):
+        raise ValueError("one entry per frame in each list")
+    scores = _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device, ctx)
+    return [_improved_assign(d, b, c, s, min_score_threshold, min_iou_threshold)
+            for d, b, c, s in zip(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame, scores)]
 
 
 # ---------------------------------------------------------------------------------------
@@ -1588,11 +1751,14 @@ def process_frame(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_p
     _, camera, velo_to_cam, velo_to_rect, velo = sequence_setup(root, seq, cam_id)
     items = collect_frame_inputs(root, seq, cam_id, segmenter, image_loader, camera, velo_to_cam, velo, frames)
     results = []
-    for r, item in zip(run_frames(items, velo_to_rect, camera, 30.0, 10, True, 0, False, device), items):
+    # the 2D matching of every frame in one lpf_match_2d call (it reads the detections and the boxes' rectangles only)
+    pairs = match_detections_frames([i.boxes_2d for i in items], [i.bboxes_3d for i in items], [i.colors for i in items], camera,
+                                    device=device)
+    for r, item, matched in zip(run_frames(items, velo_to_rect, camera, 30.0, 10, True, 0, False, device), items, pairs):
         if r["n_valid"] == 0:
             continue
         r["remaining_points"] = r["points_valid"][~r["bg_assigned"]]
-        r["matched_pairs"] = match_detections_to_bboxes(item.boxes_2d, item.bboxes_3d, item.colors, camera)
+        r["matched_pairs"] = matched
         print(f"Visualizing frame {r['frame']} with {sum(len(s) > 0 for s in r['car_point_sets']) + 1 + len(r['matched_pairs'])} objects")
         if visualizer is not None:
             visualizer(r["frame"], r["car_point_sets"], item.colors, r["remaining_points"], r["matched_pairs"])
@@ -1612,13 +1778,15 @@ def projectVeloToImage(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti
     items = collect_frame_inputs(root, seq, cam_id, segmenter, image_loader, camera, velo_to_cam, velo, frames,
                                  keep_all_boxes=True)
     results = []
-    for r, item in zip(run_frames(items, velo_to_rect, camera, 30.0, 10, True, 0, False, device), items):
+    # the pair scores of every frame in one lpf_match_2d call; the assignment and its printed lines stay in the frame's turn
+    scores = _improved_scores([i.boxes_2d for i in items], [i.bboxes_3d for i in items], camera, device)
+    for r, item, sc in zip(run_frames(items, velo_to_rect, camera, 30.0, 10, True, 0, False, device), items, scores):
         print(f"[DEBUG] Frame {r['frame']}: {r['n_valid']} points passed validation filter")
         if r["n_valid"] == 0:
             print(f"[WARN] No valid LiDAR points in frame {r['frame']}")
             continue
         r["remaining_points"] = r["points_valid"][~r["bg_assigned"]]
-        r["matched_pairs"] = improved_match_detections_to_bboxes(item.boxes_2d, item.bboxes_3d, item.colors, camera)
+        r["matched_pairs"] = _improved_assign(item.boxes_2d, item.bboxes_3d, item.colors, sc)
         if visualizer is not None:
             visualizer(r["frame"], r["car_point_sets"], item.colors, r["remaining_points"], r["matched_pairs"])
         results.append(r)
