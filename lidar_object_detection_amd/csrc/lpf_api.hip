@@ -20,6 +20,7 @@
 #include <dlfcn.h>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 // Points per launch up to which a run uses the small geometry: 512-point K1 tiles and 1024-point segments (more,
@@ -52,6 +53,20 @@ struct DevBuf {                       // grow-only device buffer
     size_t cap = 0;
 };
 
+// Where the streaming tiles of a run get their label bits (plan_tile_source, once per lpf_run_batch): nowhere (no masks), from the
+// packed label image, from the unpacked masks themselves -- all M bytes of a valid point (LpfDirect) -- or from the masks inside their
+// rectangles, through the candidate grid (LpfDirectRect).
+struct TileSource {
+    enum Kind { NONE, PACKED, DIRECT, DIRECT_RECT } kind = NONE;
+    bool f32 = false;                 // DIRECT, DIRECT_RECT: the masks' element type (uint8 / float) ...
+    int rule = 0;                     // ... and membership rule: 0 (uint8) or 1..3 (float)
+    int label_bytes = 4;              // element size of the run's label image (4 without masks)
+    const void *img = nullptr;        // what the tiles read (LpfParams::label_img): the label image, or the masks
+    const int4 *rects = nullptr;      // the masks' rectangles (LpfParams::rects), DIRECT kinds only: they gate DIRECT tiles too
+    bool ride_pack = false;           // mode 4: the pack of the unpacked masks rides in the launch that queues this run
+    bool reads_masks() const { return kind == DIRECT || kind == DIRECT_RECT; }
+};
+
 }  // namespace
 
 struct lpf_graph {
@@ -80,9 +95,20 @@ struct lpf_ctx {
     int mask_F = 0, mask_M = 0;       // 0 frames = no masks set
     int mask_set = 0;                 // the scratch set whose label image holds them
     DevBuf mask_stage;
-    // Masks not packed yet (serial mode, no erosion, host masks in mask_stage or device masks the caller lends: on_device 2):
-    // a small launch reads them directly in K1 (LpfDirect), anything else packs them first (ensure_packed).
-    struct Lazy { bool valid = false; const void *p = nullptr; bool f32 = false; int mode = 0; const int4 *rects = nullptr; } lazy;
+    // Masks that are set but not packed (no erosion; the next lpf_run* decides, plan_tile_source).  Left by lpf_set_masks_* of a serial
+    // context -- host masks in mask_stage, or device masks the caller lends (on_device 2): a launch of sparse frames reads them directly,
+    // anything else packs them first -- or of a pipelined one (lent masks only): a fused launch of sparse frames reads them directly, a
+    // large one in mode 4 lets their pack ride in its launch (uint8, 16-byte aligned planes: can_ride), anything else packs now
+    // (pack_unpacked).  Never both: lpf_set_pipelined packs what it finds.
+    struct Unpacked {
+        bool valid = false;
+        bool pipelined = false;       // left by a pipelined context's lpf_set_masks_*
+        const void *masks = nullptr;
+        bool f32 = false, can_ride = false;
+        int rule = 0, F = 0, M = 0;
+        const int4 *rects = nullptr;
+        void *label = nullptr;        // the label image they are packed into (scratch set mask_set's label_a)
+    } unpacked;
 
     // Boxes.  A ring of box sets: in the software-pipelined modes the tail that counts into the boxes of run i executes one
     // or two launches after run i was queued, so a lpf_set_boxes* for the NEXT run must not touch the tables run i's tail is
@@ -137,19 +163,14 @@ struct lpf_ctx {
         LpfParams P;
         bool pre = false;                 // its prefixes come from the scan kernel
         int ntail = 0;                    // tail blocks
-        int nk1 = 0, lb = 4;              // (pend_k1) K1 tiles, label element size
+        int nk1 = 0;                      // (pend_k1) K1 tiles
         bool small = false;
-        bool direct = false;              // its tiles read the lent masks themselves (LpfDirect; small launches)
-        int dsel = 0;                     // ... under membership rule 0 (uint8) or 1..3 (float); 4 / 5: inside the masks' rectangles only
-                                          // (LpfDirectRect, launches of any size: uint8 rule 0 / float rule 1)
+        TileSource src;                   // where its tiles get their label bits
     } pend_k1, pend_tail, pend_fin;
     bool fused = false;               // pipelined: one launch per run (modes 2 / 4)
     // Mode 4: the mask pack rides as well -- the launch of run i carries the pack of run i's masks, the K1 tiles of run i-1
     // (pend_k1), the tail of run i-2 and the summaries of run i-3; four scratch sets.
     bool defer = false;
-    // Lent masks of a software-pipelined context that have not been packed: the next run decides -- a small launch reads them
-    // directly, a large one in mode 4 lets their pack ride in its launch (uint8, 16-byte aligned planes), anything else packs now.
-    struct Ride { bool valid = false; const void *masks = nullptr; bool f32 = false, can_ride = false; int mode = 0, F = 0, M = 0; void *label = nullptr; const int4 *rects = nullptr; } ride;
     // lpf_get_stats: [0] host waits, [1] drains (owed work launched outside a run), [2] uploads through the pinned ring, [3] step
     // launches, [4] box jobs launched as a kernel of their own, [5] box jobs that rode in a step launch, [6] blocking uploads,
     // [7] lpf_run_frame_wide jobs whose masks were read directly (lpf_wide_direct_project)
@@ -169,13 +190,13 @@ struct lpf_ctx {
 
     // host-io staging
     DevBuf pib_box, pib_pts, pib_out, boxprep, dimg, coll;
-    DevBuf st_uvv, st_labv;
-    DevBuf st_pts, st_uv, st_label, st_depth, st_uf, st_vf, st_valid, st_inst, st_count, st_summary;
+    DevBuf st_pts;                    // staged points of a host caller (lpf_run_batch, lpf_depth_image)
+    DevBuf out_stage;                 // lpf_run_batch: staged outputs of a host caller, and what a run needs though its caller left it out (narrow_bind)
     std::vector<LpfFrame> h_frames;   // frame records being built (narrow_layout)
     std::vector<char> h_tab;          // [frames | segs | blks] being built
 
     // lpf_run_wide: its own buffers (the narrow masks, label images and staging stay as they are)
-    struct Wide { DevBuf tab, masks, rects, planes_a, planes_b, flags, ccnt, cpre, fcnt, midx, mwords, mpts, cnt, uv, words, pts, out; } wide;
+    struct Wide { DevBuf tab, masks, rects, planes_a, planes_b, flags, ccnt, cpre, fcnt, midx, mwords, mpts, cnt, pts, out; } wide;
     // lpf_run_cams: camera c's box tables, label images, staged masks / rectangles and host-output staging (grow-only, allocated on
     // first use); its counters and geometry tables are scratch set c's
     struct Cams { BoxSet bx[LPF_NSETS]; DevBuf label_a[LPF_NSETS], label_b[LPF_NSETS], masks[LPF_NSETS], rects[LPF_NSETS], out[LPF_NSETS], pts; } cams;
@@ -226,6 +247,63 @@ int fail(lpf_ctx *c, int code, const char *fmt, ...)
                         __FILE__, __LINE__);                                                     \
     } while (0)
 
+// ---- one dispatcher per template axis of the kernels ----------------------------------------------------------------------------------
+// Each hands a tag to a generic lambda, which launches (or calls on) the instantiation the tag names; only what a helper names here is
+// instantiated, so the library carries no kernel that no call can select.
+template <typename T, int RULE> struct MaskKind { typedef T elem; static constexpr int rule = RULE; };
+template <typename T> struct TypeTag { typedef T type; };
+template <int N> using Rows = std::integral_constant<int, N>;
+template <bool B> using Flag = std::integral_constant<bool, B>;
+
+// the masks' element type and membership rule: uint8 under rule 0 (lpf_set_masks_u8), float under rules 1..3 (lpf_set_masks_f32's
+// binarize + 1) -- the four pairs the interface can ask for
+template <typename Fn> auto with_rule(bool f32, int rule, Fn &&fn)
+{
+    if (!f32) return fn(MaskKind<uint8_t, 0>());
+    if (rule == 1) return fn(MaskKind<float, 1>());
+    if (rule == 2) return fn(MaskKind<float, 2>());
+    return fn(MaskKind<float, 3>());
+}
+
+// the element type of a label image of `bytes` per pixel: 1 (M <= 8), 2 (M <= 16) or 4
+template <typename Fn> auto with_label(int bytes, Fn &&fn)
+{
+    if (bytes == 1) return fn(TypeTag<uint8_t>());
+    if (bytes == 2) return fn(TypeTag<uint16_t>());
+    return fn(TypeTag<uint32_t>());
+}
+
+template <typename Fn> auto with_flag(bool on, Fn &&fn)
+{
+    if (on) return fn(Flag<true>());
+    return fn(Flag<false>());
+}
+
+// The forms of a run's streaming tiles: fn(tile type, rows of 256 points, scan-kernel tail).  STEP: lpf_step_t's (tiles of 512 / 1024 /
+// 2048 points, the riding tail with or without the scan kernel's prefixes); else lpf_k1_project_t's (512 / 1024, no tail).  Packed
+// tiles come in every size; tiles that read all M mask bytes of a point (LpfDirect) in 512 points only; tiles that read the masks
+// inside their rectangles (LpfDirectRect) for uint8 rule 0 and float rule 1, in 1024 points -- they need a launch beyond the small
+// geometry, whose tiles are 1024 points in order and LPF_RECT_FUSED_TILE fused -- and never beside a scan-kernel tail (launch_step).
+static_assert(LPF_RECT_FUSED_TILE == 1024, "LpfDirectRect tiles are instantiated for 1024 points only");
+template <bool STEP, typename Fn> void with_tile_form(const TileSource &src, int rows, bool scan_tail, Fn &&fn)
+{
+    auto tail = [&](auto lt, auto rw) {
+        if (STEP && scan_tail) fn(lt, rw, Flag<STEP>()); else fn(lt, rw, Flag<false>());
+    };
+    if (src.kind == TileSource::DIRECT_RECT) {
+        if (!src.f32) fn(TypeTag<LpfDirectRect<uint8_t, 0>>(), Rows<4>(), Flag<false>());
+        else fn(TypeTag<LpfDirectRect<float, 1>>(), Rows<4>(), Flag<false>());
+    } else if (src.kind == TileSource::DIRECT) {
+        with_rule(src.f32, src.rule, [&](auto kind) { tail(TypeTag<LpfDirect<typename decltype(kind)::elem, decltype(kind)::rule>>(), Rows<2>()); });
+    } else {                                               // (packed tiles; without masks, those for 4-byte labels)
+        with_label(src.label_bytes, [&](auto lt) {
+            if (rows == 2) tail(lt, Rows<2>());
+            else if (STEP && rows == 8) tail(lt, Rows<STEP ? 8 : 4>());
+            else tail(lt, Rows<4>());
+        });
+    }
+}
+
 hipError_t host_wait(lpf_ctx *c)        // the host blocks until the context's stream is idle (counted: lpf_get_stats)
 {
     ++c->stats[0];
@@ -264,24 +342,30 @@ int launch_box_job(lpf_ctx *c, lpf_ctx::BoxSet &B)
 }
 
 // One launch of lpf_step_t: the streaming tiles of run K, the tail blocks of run Q dealt out among them, the summaries of
-// run R, the box job X of the run being queued (a block per frame, in front) and -- mode 4 -- the pack of the masks waiting
-// in c->ride behind the tiles (label elements of pack_lb bytes; K's when K is there: the host keeps the two equal).  Any of
-// the roles may be absent.  `after` is recorded behind the launch.
-int launch_step(lpf_ctx *c, const lpf_ctx::Pending &KK, const lpf_ctx::Pending &Q, const lpf_ctx::Pending &R, bool ride, int pack_lb,
+// run R, the box job X of the run being queued (a block per frame, in front) and -- mode 4 -- the pack of that run's masks, waiting
+// in c->unpacked, behind the tiles (cur: the source of the run being queued, NULL in a drain; its pack rides if it says so, with label
+// elements of its size -- K's when K is there: the host keeps the two equal).  Any of the roles may be absent.  `after` is recorded
+// behind the launch.
+int launch_step(lpf_ctx *c, const lpf_ctx::Pending &KK, const lpf_ctx::Pending &Q, const lpf_ctx::Pending &R, const TileSource *cur,
                 lpf_ctx::BoxSet *XB, hipEvent_t after, const LpfRectJob *RG = nullptr)
 {
     static const LpfParams none = {};                      // unused roles get a well-formed struct
     static const LpfBoxJob nojob = {};
-    if (KK.valid && KK.direct && KK.dsel >= 4 && Q.valid && Q.pre) {
+    if (KK.valid && KK.src.kind == TileSource::DIRECT_RECT && Q.valid && Q.pre) {
         // tiles that read the masks inside their rectangles exist without the scan-kernel form of the riding tail (frames of more than
         // 16.7 M points: rare): that tail and the summaries go in a launch of their own, ahead of the tiles
         static const lpf_ctx::Pending nobody = lpf_ctx::Pending();
-        int rc_ = launch_step(c, nobody, Q, R, false, pack_lb, nullptr, nullptr);
+        TileSource no_pack = cur ? *cur : TileSource();
+        no_pack.ride_pack = false;
+        int rc_ = launch_step(c, nobody, Q, R, cur ? &no_pack : nullptr, nullptr, nullptr);
         if (rc_) return rc_;
-        return launch_step(c, KK, nobody, nobody, ride, pack_lb, XB, after, RG);
+        return launch_step(c, KK, nobody, nobody, cur, XB, after, RG);
     }
+    const bool ride = cur && cur->ride_pack;
     const LpfParams &KP = KK.valid ? KK.P : none, &QP = Q.valid ? Q.P : none, &RP = R.valid ? R.P : none;
-    const int k_lb = KK.valid ? KK.lb : pack_lb;
+    // (a launch without tiles is instantiated as packed tiles with the label elements of the run being queued)
+    TileSource tiles = KK.src;
+    if (!KK.valid) { tiles = TileSource(); tiles.label_bytes = cur ? cur->label_bytes : 4; }
     LpfStepLayout Y;
     LpfPackJob J;
     memset(&J, 0, sizeof J);
@@ -304,9 +388,10 @@ int launch_step(lpf_ctx *c, const lpf_ctx::Pending &KK, const lpf_ctx::Pending &
     Y.nk1 = KK.valid ? KK.nk1 : 0;
     Y.npack = 0;
     if (ride) {
-        J.masks = (const uint8_t *)c->ride.masks; J.label = c->ride.label; J.M = c->ride.M; J.hw = (long long)c->H * c->W;
-        J.rects = c->ride.rects; J.W = c->W;
-        J.total16 = (long long)c->ride.F * (J.hw / 16);
+        const lpf_ctx::Unpacked &U = c->unpacked;
+        J.masks = (const uint8_t *)U.masks; J.label = U.label; J.M = U.M; J.hw = (long long)c->H * c->W;
+        J.rects = U.rects; J.W = c->W;
+        J.total16 = (long long)U.F * (J.hw / 16);
         Y.npack = (int)((J.total16 + LPF_BLOCK - 1) / LPF_BLOCK);
     }
     const int nk1_pad = (Y.nk1 + 7) & ~7;
@@ -326,28 +411,12 @@ int launch_step(lpf_ctx *c, const lpf_ctx::Pending &KK, const lpf_ctx::Pending &
         const dim3 gs((unsigned)grid);
         ++c->stats[3];
         if (boxes) ++c->stats[5];
-#define LPF_STEP_LAUNCH(RW, LT, PR) do { if (boxes) hipLaunchKernelGGL((lpf_step_t<RW, LPF_K1_FLAGS, LT, PR, true>), gs, dim3(LPF_BLOCK), 0, c->stream, KP, QP, RP, Y, J, XJ, GJ); \
-                                         else hipLaunchKernelGGL((lpf_step_t<RW, LPF_K1_FLAGS, LT, PR, false>), gs, dim3(LPF_BLOCK), 0, c->stream, KP, QP, RP, Y, J, XJ, GJ); } while (0)
-#define LPF_STEP_LT(RW, PR) do { if (k_lb == 1) LPF_STEP_LAUNCH(RW, uint8_t, PR); else if (k_lb == 2) LPF_STEP_LAUNCH(RW, uint16_t, PR); else LPF_STEP_LAUNCH(RW, uint32_t, PR); } while (0)
-        const bool qpre = Q.valid && Q.pre;
-        const int rows = KP.tile_pts >> 8;
-        if (KK.valid && KK.direct && KK.dsel >= 4) {       // tiles of any size that read the masks inside their rectangles (no pack, no label image)
-            typedef LpfDirectRect<uint8_t, 0> R0; typedef LpfDirectRect<float, 1> R1;
-#define LPF_STEP_RECT(RW) do { if (KK.dsel == 4) LPF_STEP_LAUNCH(RW, R0, false); else LPF_STEP_LAUNCH(RW, R1, false); } while (0)
-            if (rows == 2) LPF_STEP_RECT(2); else LPF_STEP_RECT(4);
-#undef LPF_STEP_RECT
-        } else
-        if (KK.valid && KK.direct) {                       // small launch whose tiles read the lent masks themselves (no pack role beside it)
-            typedef LpfDirect<uint8_t, 0> D0; typedef LpfDirect<float, 1> D1; typedef LpfDirect<float, 2> D2; typedef LpfDirect<float, 3> D3;
-#define LPF_STEP_DIRECT(D) do { if (qpre) LPF_STEP_LAUNCH(2, D, true); else LPF_STEP_LAUNCH(2, D, false); } while (0)
-            if (KK.dsel == 0) LPF_STEP_DIRECT(D0); else if (KK.dsel == 1) LPF_STEP_DIRECT(D1); else if (KK.dsel == 2) LPF_STEP_DIRECT(D2); else LPF_STEP_DIRECT(D3);
-#undef LPF_STEP_DIRECT
-        } else
-        if (rows == 2) { if (qpre) LPF_STEP_LT(2, true); else LPF_STEP_LT(2, false); }
-        else if (rows == 8) { if (qpre) LPF_STEP_LT(8, true); else LPF_STEP_LT(8, false); }
-        else       { if (qpre) LPF_STEP_LT(4, true); else LPF_STEP_LT(4, false); }
-#undef LPF_STEP_LT
-#undef LPF_STEP_LAUNCH
+        with_tile_form<true>(tiles, KP.tile_pts >> 8, Q.valid && Q.pre, [&](auto lt, auto rw, auto pr) {
+            with_flag(boxes, [&](auto bx) {
+                hipLaunchKernelGGL((lpf_step_t<decltype(rw)::value, LPF_K1_FLAGS, typename decltype(lt)::type, decltype(pr)::value, decltype(bx)::value>),
+                                   gs, dim3(LPF_BLOCK), 0, c->stream, KP, QP, RP, Y, J, XJ, GJ);
+            });
+        });
         LPF_HIP(c, hipGetLastError());
     }
     if (after) LPF_HIP(c, hipEventRecord(after, c->stream));
@@ -368,7 +437,7 @@ int flush_pending(lpf_ctx *c)
     if (anything_owed(c)) ++c->stats[1];
     while (anything_owed(c)) {
         const lpf_ctx::Pending K = c->pend_k1, Q = c->pend_tail, R = c->pend_fin;
-        int rc_ = launch_step(c, K, Q, R, false, 4, XB, nullptr);
+        int rc_ = launch_step(c, K, Q, R, nullptr, XB, nullptr);
         if (rc_) return rc_;
         c->pend_fin = Q;                   // its tail has just been launched: summaries next
         c->pend_tail = K;
@@ -416,6 +485,52 @@ void release(DevBuf &b)
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr; b.cap = 0;
 }
+
+// Where the output arrays of a run live.  add(): one line per array -- the field of the kernel-parameter struct that is to point at
+// it, the caller's pointer (NULL: not asked for), its bytes, and whether the run needs the array itself when the caller left it out.
+// commit(): an array of a device caller is the caller's; one of a host caller, and one the run needs though the caller left it out,
+// is a 256-byte aligned piece of ONE staging buffer, reserved here; anything else is NULL.  back(): the copies of the staged arrays
+// to a host caller, queued on the stream.  Fixed capacity, nothing on the heap: it sits on the per-step path of a pipelined stream.
+struct OutStage {
+    enum { CAP = 20 };
+    struct Item { void *field; void *user; size_t bytes, off; bool needed, staged; } item[CAP];
+    int n = 0;
+    char *base = nullptr;
+    template <typename T> void add(T *&field, void *user, size_t bytes, bool needed = false)
+    {
+        if (n < CAP) item[n] = Item{&field, user, bytes, 0, needed, false};
+        ++n;
+    }
+    int commit(lpf_ctx *c, DevBuf &buf, bool host_io)
+    {
+        if (n > CAP) return fail(c, LPF_ERR_STATE, "OutStage: %d arrays, room for %d", n, (int)CAP);
+        size_t total = 0;
+        bool any = false;
+        for (int i = 0; i < n; ++i) {
+            Item &t = item[i];
+            t.staged = t.user ? host_io : t.needed;
+            if (!t.staged) continue;
+            any = true;
+            t.off = total;
+            total += (t.bytes + 255) & ~(size_t)255;
+        }
+        int rc;
+        if (any && (rc = reserve(c, buf, total))) return rc;
+        base = (char *)buf.p;
+        for (int i = 0; i < n; ++i) {
+            void *p = item[i].staged ? (void *)(base + item[i].off) : item[i].user;
+            memcpy(item[i].field, &p, sizeof p);           // (the field is a pointer of some type: written as the bytes of one)
+        }
+        return LPF_OK;
+    }
+    int back(lpf_ctx *c) const
+    {
+        for (int i = 0; i < n; ++i)
+            if (item[i].staged && item[i].user && item[i].bytes)
+                LPF_HIP(c, hipMemcpyAsync(item[i].user, base + item[i].off, item[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        return LPF_OK;
+    }
+};
 
 int use_device(lpf_ctx *c)
 {
@@ -647,58 +762,54 @@ int set_boxes_impl(lpf_ctx *c, const double *corners, int on_device, const int32
     return LPF_OK;
 }
 
-// masks [F][M][H][W] -> label image with element type LT, on stream ms, into la (lb_ = erosion ping-pong): the context's camera size
-// for the narrow calls (a scratch set's label_a / label_b), camera c's for lpf_run_cams
-template <typename T, typename LT>
-int pack_typed(lpf_ctx *c, DevBuf &la, DevBuf &lb_, const int W, const int H, hipStream_t ms, const T *d_masks, int F, int M, int mode,
-               int erode_iters, void **result, const int4 *rects = nullptr)
+void forget_unpacked(lpf_ctx *c) { c->unpacked = lpf_ctx::Unpacked(); }
+
+// masks [F][M][H][W] (uint8 under rule 0, or float under rule 1..3) -> label image with elements of `label_bytes`, on stream ms, into la
+// (lb_ = erosion ping-pong): the context's camera size for the narrow calls (a scratch set's label_a / label_b), camera c's for
+// lpf_run_cams
+int pack_masks(lpf_ctx *c, DevBuf &la, DevBuf &lb_, const int W, const int H, hipStream_t ms, const void *masks, bool f32, int rule,
+               int label_bytes, int F, int M, int erode_iters, void **result, const int4 *rects = nullptr)
 {
-    const size_t hw = (size_t)H * W;
-    dim3 grid((W + LPF_TW - 1) / LPF_TW, (H + LPF_TH - 1) / LPF_TH, F);
-    LT *cur = (LT *)la.p;
-    int rc;
-    if (M == 0) {
-        LPF_HIP(c, hipMemsetAsync(cur, 0, (size_t)F * hw * sizeof(LT), ms));
-    } else {
-        int left = erode_iters;
-        if (hw % 16 == 0 && ((uintptr_t)d_masks & 15) == 0) {
-            // streaming pack, 16 pixels per lane; erosion (if any) then runs on the packed image
-            const long long total16 = (long long)F * (long long)(hw / 16);
-            const unsigned nb = (unsigned)((total16 + LPF_BLOCK - 1) / LPF_BLOCK);
-            // (rectangles: only where set_masks_impl accepted them -- uint8 rule 0 / float rule 1, no erosion)
-            if (mode == 0)
-                hipLaunchKernelGGL((lpf_pack16<T, 0, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, rects, W);
-            else if (mode == 1)
-                hipLaunchKernelGGL((lpf_pack16<T, 1, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, rects, W);
-            else if (mode == 2)
-                hipLaunchKernelGGL((lpf_pack16<T, 2, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, (const int4 *)nullptr, W);
-            else
-                hipLaunchKernelGGL((lpf_pack16<T, 3, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, (long long)hw, total16, (const int4 *)nullptr, W);
+    return with_label(label_bytes, [&](auto lt) -> int {
+        typedef typename decltype(lt)::type LT;
+        const size_t hw = (size_t)H * W;
+        dim3 grid((W + LPF_TW - 1) / LPF_TW, (H + LPF_TH - 1) / LPF_TH, F);
+        LT *cur = (LT *)la.p;
+        int rc;
+        if (M == 0) {
+            LPF_HIP(c, hipMemsetAsync(cur, 0, (size_t)F * hw * sizeof(LT), ms));
         } else {
-            const int fuse = erode_iters > 0 ? 1 : 0;
-            left -= fuse;
-            if (mode == 0)
-                hipLaunchKernelGGL((lpf_pack_erode<T, 0, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, H, W, fuse, rects);
-            else if (mode == 1)
-                hipLaunchKernelGGL((lpf_pack_erode<T, 1, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, H, W, fuse, rects);
-            else if (mode == 2)
-                hipLaunchKernelGGL((lpf_pack_erode<T, 2, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, H, W, fuse, (const int4 *)nullptr);
-            else
-                hipLaunchKernelGGL((lpf_pack_erode<T, 3, LT>), grid, dim3(LPF_BLOCK), 0, ms, d_masks, cur, M, H, W, fuse, (const int4 *)nullptr);
-        }
-        LPF_HIP(c, hipGetLastError());
-        if (left > 0) {
-            if ((rc = reserve(c, lb_, (size_t)F * hw * 4))) return rc;
-            LT *other = (LT *)lb_.p;
-            for (int it = 0; it < left; ++it) {
-                hipLaunchKernelGGL((lpf_erode_packed<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, H, W);
-                LPF_HIP(c, hipGetLastError());
-                LT *t = cur; cur = other; other = t;
+            int left = erode_iters;
+            const bool stream16 = hw % 16 == 0 && ((uintptr_t)masks & 15) == 0;
+            if (!stream16 && erode_iters > 0) --left;      // (the tiled pack does the first erosion itself)
+            with_rule(f32, rule, [&](auto kind) {
+                typedef typename decltype(kind)::elem T;
+                constexpr int RULE = decltype(kind)::rule;
+                // (rectangles: only where set_masks_impl accepted them -- uint8 rule 0 / float rule 1, no erosion)
+                const int4 *r = RULE <= 1 ? rects : nullptr;
+                if (stream16) {
+                    // streaming pack, 16 pixels per lane; erosion (if any) then runs on the packed image
+                    const long long total16 = (long long)F * (long long)(hw / 16);
+                    const unsigned nb = (unsigned)((total16 + LPF_BLOCK - 1) / LPF_BLOCK);
+                    hipLaunchKernelGGL((lpf_pack16<T, RULE, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, (const T *)masks, cur, M, (long long)hw, total16, r, W);
+                } else {
+                    hipLaunchKernelGGL((lpf_pack_erode<T, RULE, LT>), grid, dim3(LPF_BLOCK), 0, ms, (const T *)masks, cur, M, H, W, erode_iters > 0 ? 1 : 0, r);
+                }
+            });
+            LPF_HIP(c, hipGetLastError());
+            if (left > 0) {
+                if ((rc = reserve(c, lb_, (size_t)F * hw * 4))) return rc;
+                LT *other = (LT *)lb_.p;
+                for (int it = 0; it < left; ++it) {
+                    hipLaunchKernelGGL((lpf_erode_packed<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, H, W);
+                    LPF_HIP(c, hipGetLastError());
+                    LT *t = cur; cur = other; other = t;
+                }
             }
         }
-    }
-    *result = cur;
-    return LPF_OK;
+        *result = cur;
+        return LPF_OK;
+    });
 }
 
 template <typename T>
@@ -720,7 +831,10 @@ int set_masks_impl(lpf_ctx *c, const T *masks, int F, int M, int mode, int erode
     if (!per_set && anything_owed(c) && (rc = sync_all(c))) return rc;    // owed tiles read set 0's label image / the staging copy
     lpf_ctx::Scratch &S = c->sc[per_set ? c->parity : 0];
     hipStream_t ms = c->stream;
-    c->mask_F = 0; c->mask_M = 0; S.label_cur = nullptr; c->lazy.valid = false;
+    c->mask_F = 0; c->mask_M = 0; S.label_cur = nullptr;
+    // (masks a pipelined lpf_set_masks_* left unpacked stay on record until this call has its buffers -- so also when it is for no
+    //  frames: the next run packs them.  Kept as it was)
+    if (!c->unpacked.pipelined) forget_unpacked(c);
     c->mask_set = per_set ? c->parity : 0;
     if (F == 0) return LPF_OK;
     const size_t hw = (size_t)c->H * c->W;
@@ -737,31 +851,23 @@ int set_masks_impl(lpf_ctx *c, const T *masks, int F, int M, int mode, int erode
     const int4 *rects = (((sizeof(T) == 1 && mode == 0) || (sizeof(T) == 4 && mode == 1)) && erode_iters == 0 && c->rects_F == F && c->rects_M == M &&
                          c->W >= 16) ? c->rects_pending : nullptr;         // (W >= 16: a group of 16 pixels of the pack spans at most two rows)
     c->rects_pending = nullptr;
-    c->ride.valid = false;
-    if (c->fused && per_set && M > 0 && erode_iters == 0 && on_device == 2) {
-        // software-pipelined modes, lent masks: left to the next lpf_run* (see lpf_ctx::Ride)
-        c->ride.valid = true; c->ride.masks = d_masks; c->ride.F = F; c->ride.M = M; c->ride.label = S.label_a.p;
-        c->ride.f32 = sizeof(T) == 4; c->ride.mode = mode; c->ride.rects = rects;
-        c->ride.can_ride = c->defer && sizeof(T) == 1 && hw % 16 == 0 && ((uintptr_t)d_masks & 15) == 0;
+    forget_unpacked(c);
+    const bool lent_pipelined = c->fused && per_set && on_device == 2, kept_serial = !c->fused && on_device != 1;
+    if (M > 0 && erode_iters == 0 && (lent_pipelined || kept_serial)) {
+        // nothing to erode, and the masks stay where they are (lent by the caller, or -- serial mode -- our staging buffer): packing
+        // is left to the next lpf_run* (see lpf_ctx::Unpacked) -- a launch of sparse frames does without it
+        lpf_ctx::Unpacked &U = c->unpacked;
+        U.valid = true; U.pipelined = lent_pipelined; U.masks = d_masks; U.f32 = sizeof(T) == 4; U.rule = mode; U.F = F; U.M = M;
+        U.rects = rects; U.label = S.label_a.p;
+        U.can_ride = lent_pipelined && c->defer && sizeof(T) == 1 && hw % 16 == 0 && ((uintptr_t)d_masks & 15) == 0;
         S.label_bytes = lb;
-        S.label_cur = S.label_a.p;
-        c->mask_F = F; c->mask_M = M;
-        return LPF_OK;
-    }
-    if (M > 0 && erode_iters == 0 && !c->fused && on_device != 1) {
-        // serial mode, nothing to erode, and the masks stay where they are (our staging buffer, or lent by the caller):
-        // packing is left to the run -- a small launch does without it
-        c->lazy.valid = true; c->lazy.p = d_masks; c->lazy.f32 = sizeof(T) == 4; c->lazy.mode = mode; c->lazy.rects = rects;
-        S.label_bytes = lb;
-        if (!on_device) LPF_HIP(c, host_wait(c));
+        if (lent_pipelined) S.label_cur = S.label_a.p;
+        else if (!on_device) LPF_HIP(c, host_wait(c));
         c->mask_F = F; c->mask_M = M;
         return LPF_OK;
     }
     void *cur = nullptr;
-    if (lb == 1) rc = pack_typed<T, uint8_t>(c, S.label_a, S.label_b, c->W, c->H, ms, d_masks, F, M, mode, erode_iters, &cur, rects);
-    else if (lb == 2) rc = pack_typed<T, uint16_t>(c, S.label_a, S.label_b, c->W, c->H, ms, d_masks, F, M, mode, erode_iters, &cur, rects);
-    else rc = pack_typed<T, uint32_t>(c, S.label_a, S.label_b, c->W, c->H, ms, d_masks, F, M, mode, erode_iters, &cur, rects);
-    if (rc) return rc;
+    if ((rc = pack_masks(c, S.label_a, S.label_b, c->W, c->H, ms, d_masks, sizeof(T) == 4, mode, lb, F, M, erode_iters, &cur, rects))) return rc;
     S.label_bytes = lb;
     if (!on_device) LPF_HIP(c, host_wait(c));   // the host buffer may be reused by the caller
     S.label_cur = cur;
@@ -769,45 +875,67 @@ int set_masks_impl(lpf_ctx *c, const T *masks, int F, int M, int mode, int erode
     return LPF_OK;
 }
 
-// masks [F][M][H][W] (uint8 under rule 0, or float under rule mode) -> label image of scratch set S, by a launch of their own
-int pack_masks_now(lpf_ctx *c, lpf_ctx::Scratch &S, const void *masks, bool f32, int mode, int F, int M, const int4 *rects)
+// masks that are set but not packed (lpf_ctx::Unpacked) -> packed now, by a launch of their own, into the label image of their scratch
+// set (mask_set: set 0 in serial mode)
+int pack_unpacked(lpf_ctx *c)
 {
-    const int lb = S.label_bytes;
+    const lpf_ctx::Unpacked &U = c->unpacked;
+    if (!U.valid) return LPF_OK;
+    lpf_ctx::Scratch &S = c->sc[c->mask_set];
     void *cur = nullptr;
-    int rc;
-    if (f32) {
-        const float *m = (const float *)masks;
-        if (lb == 1) rc = pack_typed<float, uint8_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
-        else if (lb == 2) rc = pack_typed<float, uint16_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
-        else rc = pack_typed<float, uint32_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
-    } else {
-        const uint8_t *m = (const uint8_t *)masks;
-        if (lb == 1) rc = pack_typed<uint8_t, uint8_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
-        else if (lb == 2) rc = pack_typed<uint8_t, uint16_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
-        else rc = pack_typed<uint8_t, uint32_t>(c, S.label_a, S.label_b, c->W, c->H, c->stream, m, F, M, mode, 0, &cur, rects);
-    }
+    int rc = pack_masks(c, S.label_a, S.label_b, c->W, c->H, c->stream, U.masks, U.f32, U.rule, S.label_bytes, U.F, U.M, 0, &cur, U.rects);
     if (rc) return rc;
     S.label_cur = cur;
+    forget_unpacked(c);
     return LPF_OK;
 }
 
-// lent masks of a pipelined context still unpacked (lpf_ctx::Ride) -> packed now
-int pack_ride_now(lpf_ctx *c)
+// Where the tiles of a run of lpf_run_batch get their label bits: a run of M masks (0: none) on a context whose masks may still be
+// unpacked (lpf_ctx::Unpacked); fused: one launch per run, the tail rides in the next; small: the small geometry; sparse_frames: the
+// run has at most half as many points as its images have pixels.  Masks that this run neither reads directly nor lets ride are packed
+// here, now (same stream, ahead of the tiles).
+//   Unpacked masks are read directly only by the kind of run they were left for: those a pipelined lpf_set_masks_* lent, by a fused
+// run -- a host-memory run or one with host points packs them now; those a serial call left are never met by a fused run
+// (lpf_set_pipelined packs them on the switch).
+//   A small fused launch reads lent masks directly, a large one in mode 4 carries their pack, anything else (mode 2, float masks, a
+// host-memory run) packs them now
+// (directly: M gathers per valid point against M reads per pixel for the pack -- it pays while a frame has fewer points than
+//  half its image has pixels: a real scan, 110 k points on 530 k pixels, 29.9 -> 24.9 us per 20-frame batch in a pipelined
+//  stream; a synthetic 2 M-point cloud is better off with the pack riding, 21.8 vs 24.2 us)
+// ... and with the masks' rectangles (lpf_set_mask_rects) a launch of sparse frames of ANY size reads the masks inside them: no
+// pack, no label image (146 real frames per step: 176 -> 134 us).  Dense frames keep the pack: with 2 M points on 530 k pixels and
+// rectangles that cover a good part of the image every row meets a rectangle, and the exact test of such a row is a dependent round
+// trip (one 2 M-point cloud with 8 disk masks, tiles 18.5 -> 21 us, pipelined stream 21.4 -> 25.4 us per cloud).
+// Small launches stay with the tiles that read all M mask bytes of a valid point (LpfDirect) and gate them by the rectangles: the
+// candidate grid would be one more kernel in front of a launch that is as long as its chain (a single real frame in order 18.8 vs
+// 23.0 us; pipelined 11.1 vs 10.2, 4 frames 21.1 vs 21.4, 20 frames 35.0 vs 36.6).
+//   Masks left unpacked in serial mode: a small serial launch reads them directly, anything else packs them now.
+int plan_tile_source(lpf_ctx *c, bool fused, bool small, bool sparse_frames, int M, TileSource &src)
 {
-    if (!c->ride.valid) return LPF_OK;
-    int rc = pack_masks_now(c, c->sc[c->mask_set], c->ride.masks, c->ride.f32, c->ride.mode, c->ride.F, c->ride.M, c->ride.rects);
-    if (rc) return rc;
-    c->ride.valid = false;
-    return LPF_OK;
-}
-
-// masks left unpacked by lpf_set_masks_* in serial mode (lpf_ctx::Lazy) -> label image of scratch set 0
-int ensure_packed(lpf_ctx *c)
-{
-    if (!c->lazy.valid) return LPF_OK;
-    int rc = pack_masks_now(c, c->sc[0], c->lazy.p, c->lazy.f32, c->lazy.mode, c->mask_F, c->mask_M, c->lazy.rects);
-    if (rc) return rc;
-    c->lazy.valid = false;
+    src = TileSource();
+    int rc;
+    const lpf_ctx::Unpacked &U = c->unpacked;
+    const bool readable = U.valid && U.pipelined == fused && M > 0 && sparse_frames;
+    if (readable && !small && U.rects && ((!U.f32 && U.rule == 0) || (U.f32 && U.rule == 1))) src.kind = TileSource::DIRECT_RECT;
+    else if (readable && small) src.kind = TileSource::DIRECT;
+    else {
+        src.ride_pack = U.valid && U.pipelined && fused && U.can_ride && M > 0;
+        if (!src.ride_pack && (rc = pack_unpacked(c))) return rc;
+        if (M > 0) src.kind = TileSource::PACKED;
+    }
+    // The label image lives in the scratch set that was current when the masks were set.  A pipelined run must find it in its
+    // own set (the sets rotate: masks are set before every run); any other run has nothing owed and reads it where it is.
+    const lpf_ctx::Scratch &SM = c->sc[c->mask_set];
+    if (M > 0 && fused && c->mask_set != c->parity)
+        return fail(c, LPF_ERR_STATE, "the masks were set for another scratch set: in the pipelined modes the label images rotate with the scratch sets -- call lpf_set_masks_* before every lpf_run* (and after switching modes)");
+    if (src.reads_masks()) {
+        src.f32 = U.f32; src.rule = U.rule; src.img = U.masks;
+        src.rects = U.rects;                               // (the rectangles also gate the tiles that read all M mask bytes: small sparse launches)
+    } else if (M > 0) {
+        src.img = SM.label_cur;
+    }
+    if (M > 0 && !src.img) return fail(c, LPF_ERR_STATE, "no masks for this run's scratch set: in the pipelined modes the label images rotate with the scratch sets -- call lpf_set_masks_* before every lpf_run* (and after switching modes)");
+    src.label_bytes = (M > 0) ? SM.label_bytes : 4;
     return LPF_OK;
 }
 
@@ -1024,6 +1152,27 @@ void narrow_params(LpfParams &P, const lpf_ctx *c, const Cam &cam, const NarrowL
     P.count_lazy = L.small ? 0 : 1;
 }
 
+// The outputs of a narrow run of n points, F frames, M masks and Btot boxes -> P's pointers: the caller's device pointers, or pieces of
+// `buf` for a host caller (narrow_back_a / narrow_back_b copy them back) and for what the run needs though the caller left it out --
+// the dense uv / labels the compact copies are gathered from, and the summaries: always produced, host callers size the list copies by
+// them.  Every output field of lpf_outputs is bound here and nowhere else.
+int narrow_bind(lpf_ctx *c, DevBuf &buf, const lpf_outputs &o, size_t n, int F, int M, int Btot, LpfParams &P)
+{
+    OutStage S;
+    S.add(P.summary, o.summary, (size_t)F * sizeof(lpf_frame_summary), true);
+    S.add(P.uv, o.uv, n * 8, o.uv_valid != nullptr);
+    S.add(P.label_bits, o.label_bits, n * 4, o.label_valid != nullptr);
+    S.add(P.uv_valid, o.uv_valid, n * 8);
+    S.add(P.label_valid, o.label_valid, n * 4);
+    S.add(P.depth, o.depth, n * 8);
+    S.add(P.uf, o.u_f, n * 8);
+    S.add(P.vf, o.v_f, n * 8);
+    S.add(P.valid_idx, o.valid_idx, n * 8);
+    S.add(P.inst_idx, o.inst_idx, (size_t)F * (size_t)(o.inst_cap > 0 ? o.inst_cap : 0) * 8);
+    S.add(P.count_out, o.count_mb, (size_t)(M > 0 ? M : 1) * (Btot > 0 ? Btot : 1) * 4);
+    return S.commit(c, buf, !o.on_device);
+}
+
 // Host outputs of a narrow run of n points, phase (a): the dense arrays are queued.  Then, with result buffers in page-locked memory
 // (lpf_host_alloc, hipHostMalloc), lpf_results_to_host writes the filled parts of the compact results and the summaries there, reading
 // the lengths from the summaries on the device -- one launch and ONE host wait, where the copy engine needs the summaries on the host
@@ -1191,7 +1340,7 @@ void lpf_destroy(lpf_ctx *c)
     release(c->cams.pts);
     for (lpf_ctx::Wide *D : {&c->wide, &c->camsw.cam[0], &c->camsw.cam[1], &c->camsw.cam[2], &c->camsw.cam[3]}) {
         DevBuf *wb[] = {&D->tab, &D->masks, &D->rects, &D->planes_a, &D->planes_b, &D->flags, &D->ccnt, &D->cpre, &D->fcnt, &D->midx, &D->mwords,
-                        &D->mpts, &D->cnt, &D->uv, &D->words, &D->pts, &D->out};
+                        &D->mpts, &D->cnt, &D->pts, &D->out};
         for (DevBuf *b : wb) release(*b);
     }
     release(c->camsw.tab);
@@ -1203,8 +1352,7 @@ void lpf_destroy(lpf_ctx *c)
         release(*b);
     for (DevBuf *b : {&c->m2d.tab, &c->m2d.in, &c->m2d.out})
         release(*b);
-    DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_uvv, &c->st_labv, &c->st_pts, &c->st_uv, &c->st_label,
-                     &c->st_depth, &c->st_uf, &c->st_vf, &c->st_valid, &c->st_inst, &c->st_count, &c->st_summary};
+    DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
     for (DevBuf *b : all) release(*b);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ring.ev) if (e) (void)hipEventDestroy(e);
@@ -1354,8 +1502,7 @@ int lpf_set_pipelined(lpf_ctx *c, int on)
                                                                    "4 = 2 + the mask pack rides as well)", on);
     int rc = sync_all(c);
     if (rc) return rc;
-    if ((rc = ensure_packed(c))) return rc;
-    if ((rc = pack_ride_now(c))) return rc;                // lent masks that were waiting for a run: packed now, where the next run looks
+    if ((rc = pack_unpacked(c))) return rc;                // masks that were waiting for a run: packed now, where the next run looks
     c->fused = on != 0;
     c->defer = on == 4;
     c->parity = 0;
@@ -1376,7 +1523,7 @@ int lpf_set_camera(lpf_ctx *c, const double T[16], const double K[9], int W, int
         if (rc_) return rc_;
     }
     if (W != c->W || H != c->H) {            // label images (and the visibility filter of cam-0 boxes) are per W x H: set masks / boxes again
-        c->mask_F = 0; c->mask_M = 0; c->lazy.valid = false; c->ride.valid = false;
+        c->mask_F = 0; c->mask_M = 0; forget_unpacked(c);
         for (auto &B : c->bx) { B.F = 0; B.box_off.clear(); B.job_valid = false; }
     }
     memcpy(c->T, T, sizeof c->T);          // row 3 of the 4x4 is never used by the reference either (V3:567 [:, :3])
@@ -1408,7 +1555,9 @@ int lpf_set_label_image(lpf_ctx *c, const uint32_t *label, int F, int M, int on_
     int rc;
     if ((rc = sync_all(c))) return rc;
     lpf_ctx::Scratch &S = c->sc[c->fused ? c->parity : 0];
-    c->mask_F = 0; c->mask_M = 0; S.label_cur = nullptr; c->lazy.valid = false;
+    c->mask_F = 0; c->mask_M = 0; S.label_cur = nullptr;
+    // (masks a pipelined lpf_set_masks_* left unpacked stay on record, and the next fused run takes them, not this image.  Kept as it was)
+    if (!c->unpacked.pipelined) forget_unpacked(c);
     c->mask_set = c->fused ? c->parity : 0;
     if (F == 0) return LPF_OK;
     const size_t bytes = (size_t)F * c->H * c->W * 4;
@@ -1426,8 +1575,7 @@ int lpf_get_label_image(lpf_ctx *c, uint32_t *out, int on_device)
     if (!c || !out) return LPF_ERR_ARG;
     if (use_device(c)) return LPF_ERR_HIP;
     { int rc_ = sync_all(c); if (rc_) return rc_; }
-    { int rc_ = ensure_packed(c); if (rc_) return rc_; }
-    { int rc_ = pack_ride_now(c); if (rc_) return rc_; }
+    { int rc_ = pack_unpacked(c); if (rc_) return rc_; }
     lpf_ctx::Scratch &S = c->sc[c->mask_set];
     if (!S.label_cur || !c->mask_F) return fail(c, LPF_ERR_STATE, "no masks set");
     const size_t npix = (size_t)c->mask_F * c->H * c->W;
@@ -1503,42 +1651,17 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     if ((rc = narrow_tables(c, S, L, false))) return rc;
     LpfParams P;
     narrow_params(P, c, ctx_cam(c), L, S, BX, M, out->inst_cap);
-    // lent masks of a pipelined context (lpf_ctx::Ride): a small fused launch reads them directly, a large one in mode 4 carries
-    // their pack, anything else (mode 2, float masks, a host-memory run) packs them now
-    // (directly: M gathers per valid point against M reads per pixel for the pack -- it pays while a frame has fewer points than
-    //  half its image has pixels: a real scan, 110 k points on 530 k pixels, 29.9 -> 24.9 us per 20-frame batch in a pipelined
-    //  stream; a synthetic 2 M-point cloud is better off with the pack riding, 21.8 vs 24.2 us)
     const bool sparse_frames = Ntot * 2 <= (int64_t)F * c->W * c->H;
-    // ... and with the masks' rectangles (lpf_set_mask_rects) a launch of sparse frames of ANY size reads the masks inside them: no
-    // pack, no label image (146 real frames per step: 176 -> 134 us).  Dense frames keep the pack: with 2 M points on 530 k pixels and
-    // rectangles that cover a good part of the image every row meets a rectangle, and the exact test of such a row is a dependent round
-    // trip (one 2 M-point cloud with 8 disk masks, tiles 18.5 -> 21 us, pipelined stream 21.4 -> 25.4 us per cloud).
-    // Small launches stay with the tiles that read all M mask bytes of a valid point (LpfDirect) and gate them by the rectangles: the
-    // candidate grid would be one more kernel in front of a launch that is as long as its chain (a single real frame in order 18.8 vs
-    // 23.0 us; pipelined 11.1 vs 10.2, 4 frames 21.1 vs 21.4, 20 frames 35.0 vs 36.6).
-    const bool direct_rect_fused = c->ride.valid && fused && M > 0 && sparse_frames && !small && c->ride.rects &&
-                                   ((!c->ride.f32 && c->ride.mode == 0) || (c->ride.f32 && c->ride.mode == 1));
-    const bool direct_fused = direct_rect_fused || (c->ride.valid && fused && small && sparse_frames && M > 0);
-    const bool ride_pack = c->ride.valid && fused && !direct_fused && c->ride.can_ride && M > 0;
-    if (c->ride.valid && !direct_fused && !ride_pack && (rc = pack_ride_now(c))) return rc;
-    // masks left unpacked: a small serial launch reads them directly, anything else packs them now (same stream, ahead of K1)
-    const bool direct_rect = M > 0 && c->lazy.valid && !fused && sparse_frames && !small && c->lazy.rects &&
-                             ((!c->lazy.f32 && c->lazy.mode == 0) || (c->lazy.f32 && c->lazy.mode == 1));
-    const bool direct = direct_rect || (M > 0 && c->lazy.valid && small && sparse_frames && !fused);
-    if (M > 0 && c->lazy.valid && !direct && (rc = ensure_packed(c))) return rc;
-    // The label image lives in the scratch set that was current when the masks were set.  A pipelined run must find it in its
-    // own set (the sets rotate: masks are set before every run); any other run has nothing owed and reads it where it is.
-    const lpf_ctx::Scratch &SM = c->sc[c->mask_set];
-    if (M > 0 && fused && !direct && c->mask_set != c->parity)
-        return fail(c, LPF_ERR_STATE, "the masks were set for another scratch set: in the pipelined modes the label images rotate with the scratch sets -- call lpf_set_masks_* before every lpf_run* (and after switching modes)");
-    P.label_img = (M > 0) ? (direct ? c->lazy.p : direct_fused ? c->ride.masks : SM.label_cur) : nullptr;
-    // (the rectangles also gate the tiles that read all M mask bytes: small sparse launches)
-    P.rects = (direct && c->lazy.valid) ? c->lazy.rects : (direct_fused && c->ride.valid) ? c->ride.rects : nullptr;
-    // ... whose tiles look a point's candidates up in a coarse grid of the rectangles (a few KB per frame), built once per run: by
-    // blocks of this run's own launch where the tiles come a launch later (mode 4), else by a small kernel ahead of the tiles
+    TileSource src;
+    if ((rc = plan_tile_source(c, fused, small, sparse_frames, M, src))) return rc;
+    P.label_img = src.img;
+    P.rects = src.rects;
+    // tiles that read the masks inside their rectangles look a point's candidates up in a coarse grid of the rectangles (a few KB per
+    // frame), built once per run: by blocks of this run's own launch where the tiles come a launch later (mode 4), else by a small
+    // kernel ahead of the tiles
     LpfRectJob RG;
     memset(&RG, 0, sizeof RG);
-    const bool rect_tiles = direct_rect || direct_rect_fused;
+    const bool rect_tiles = src.kind == TileSource::DIRECT_RECT;
     if (rect_tiles) {
         RG.rects = P.rects; RG.F = F; RG.M = M;
         RG.cw = (c->W + LPF_RG_CELL - 1) / LPF_RG_CELL; RG.ch = (c->H + LPF_RG_CELL - 1) / LPF_RG_CELL;
@@ -1547,7 +1670,6 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
         RG.grid = (uint32_t *)S.rgrid.p;
         P.rect_grid = RG.grid; P.rg_cw = RG.cw; P.rg_cells = RG.cells;
     }
-    if (M > 0 && !P.label_img) return fail(c, LPF_ERR_STATE, "no masks for this run's scratch set: in the pipelined modes the label images rotate with the scratch sets -- call lpf_set_masks_* before every lpf_run* (and after switching modes)");
 
     // ---- buffers: caller's HBM pointers, or internal staging for host callers -----------
     const size_t n = (size_t)Ntot;
@@ -1558,36 +1680,7 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
         if (n) LPF_HIP(c, hipMemcpyAsync(c->st_pts.p, pts, n * 16, hipMemcpyHostToDevice, c->stream));
         P.pts = (const float4 *)c->st_pts.p;
     }
-#define LPF_OUTBUF(field, member, stage, bytes)                                   \
-    if (out->member) {                                                            \
-        if (host_io) {                                                            \
-            if ((rc = reserve(c, c->stage, (bytes)))) return rc;                  \
-            P.field = (decltype(P.field))c->stage.p;                              \
-        } else {                                                                  \
-            P.field = (decltype(P.field))out->member;                             \
-        }                                                                         \
-    }
-    LPF_OUTBUF(uv, uv, st_uv, n * 8)
-    LPF_OUTBUF(label_bits, label_bits, st_label, n * 4)
-    // the compact copies are gathered from the dense arrays: keep those in internal buffers when the caller skips them
-    if (out->uv_valid && !P.uv) { if ((rc = reserve(c, c->st_uv, n * 8))) return rc; P.uv = (decltype(P.uv))c->st_uv.p; }
-    if (out->label_valid && !P.label_bits) { if ((rc = reserve(c, c->st_label, n * 4))) return rc; P.label_bits = (decltype(P.label_bits))c->st_label.p; }
-    LPF_OUTBUF(uv_valid, uv_valid, st_uvv, n * 8)
-    LPF_OUTBUF(label_valid, label_valid, st_labv, n * 4)
-    LPF_OUTBUF(depth, depth, st_depth, n * 8)
-    LPF_OUTBUF(uf, u_f, st_uf, n * 8)
-    LPF_OUTBUF(vf, v_f, st_vf, n * 8)
-    LPF_OUTBUF(valid_idx, valid_idx, st_valid, n * 8)
-    LPF_OUTBUF(inst_idx, inst_idx, st_inst, (size_t)F * (size_t)out->inst_cap * 8)
-    LPF_OUTBUF(count_out, count_mb, st_count, (size_t)(M > 0 ? M : 1) * (Btot > 0 ? Btot : 1) * 4)
-    // the summary is always produced: host callers need it to size the list copies
-    if (host_io || !out->summary) {
-        if ((rc = reserve(c, c->st_summary, (size_t)F * sizeof(lpf_frame_summary)))) return rc;
-        P.summary = c->st_summary.p;
-    } else {
-        P.summary = out->summary;
-    }
-#undef LPF_OUTBUF
+    if ((rc = narrow_bind(c, c->out_stage, *out, n, F, M, Btot, P))) return rc;
     if (M > 0) {                         // K1 -> tail hand-off of the masked points (sparse writes into N slots)
         if ((rc = reserve(c, S.mlist, n * 16))) return rc;
         P.mlist = (float4 *)S.mlist.p;
@@ -1605,19 +1698,19 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     // tiles pays for a third, nearly empty round of blocks (one cloud per launch set, in order / pipelined, us: 1 M points 43.6 / 17.4
     // -> 38.7 / 14.7, 2 M 39.2 / 21.4 -> 37.6 / 20.5, 3 M 63.9 / 28.4 -> 45.5 / 26.8).  Not for tiles that read M mask values per
     // valid point (LpfDirect: 512-point form only; small sparse launches).  Lab geometry 5 forces the 1024-point form, 1 / 4 the other.
-    const bool plain_direct = (direct && !direct_rect) || (direct_fused && !direct_rect_fused);
-    const bool small_1024 = small && !plain_direct && (c->geometry == 5 || (c->geometry == 0 && Ntot > 1792ll * 512));
+    const bool small_1024 = small && src.kind != TileSource::DIRECT && (c->geometry == 5 || (c->geometry == 0 && Ntot > 1792ll * 512));
     P.tile_pts = small ? (small_1024 ? 1024 : 512) : 1024;
     // the fused launch shares the chip with the previous run's tail blocks: 2048-point tiles keep twice the loads in flight
     // per wave, so the streaming work holds its bandwidth on fewer resident blocks (measured: 104.9 vs 108.8 us per step)
-    if (fused && !small) P.tile_pts = direct_rect_fused ? LPF_RECT_FUSED_TILE : 2048;
+    if (fused && !small) P.tile_pts = rect_tiles ? LPF_RECT_FUSED_TILE : 2048;
     const int nk1 = L.nseg_total * (int)(L.seg_pts / P.tile_pts);
-    const int lb = (M > 0) ? SM.label_bytes : 4;
     const bool want_lists = out->valid_idx || out->inst_idx;
     const int ntail = (P.count_boxes ? L.ncblk : 0) + (want_lists ? L.nblk : 0);        // no lists wanted and no boxes: no tail blocks at all
     hipEvent_t e0 = nullptr, e1 = nullptr;
     // mode 4: the mask pack and the tiles of one launch share the label element type -- else the pipeline is drained first
-    if (fused && c->defer && c->pend_k1.valid && ride_pack && (c->pend_k1.direct || c->pend_k1.lb != lb) && (rc = flush_pending(c))) return rc;
+    if (fused && c->defer && c->pend_k1.valid && src.ride_pack && (c->pend_k1.src.reads_masks() || c->pend_k1.src.label_bytes != src.label_bytes) &&
+        (rc = flush_pending(c)))
+        return rc;
     // the candidate grid of the masks' rectangles: where this run's tiles are in this run's own launch(es) -- in order, mode 2 -- a
     // small kernel ahead of them; in mode 4 it rides in the launch below (the tiles come a launch later)
     if (rect_tiles && nk1 > 0 && !(fused && c->defer)) {
@@ -1643,14 +1736,13 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
         //      Mode 2: the tiles are this run's.  Mode 4: this run's MASK PACK rides as well (lent uint8 masks), the tiles are
         //      the previous run's -- everything one launch later, nothing left on the stream between two steps.
         lpf_ctx::Pending cur;
-        cur.valid = true; cur.P = P; cur.pre = L.pre_scan; cur.ntail = ntail; cur.nk1 = nk1; cur.lb = lb; cur.small = small;
-        cur.direct = direct_fused; cur.dsel = direct_rect_fused ? (c->ride.f32 ? 5 : 4) : c->ride.f32 ? c->ride.mode : 0;
+        cur.valid = true; cur.P = P; cur.pre = L.pre_scan; cur.ntail = ntail; cur.nk1 = nk1; cur.small = small; cur.src = src;
         const lpf_ctx::Pending KK = c->defer ? c->pend_k1 : cur, Q = c->pend_tail, R = c->pend_fin;
-        if ((rc = launch_step(c, KK, Q, R, ride_pack, lb, &BX, e1, (rect_tiles && c->defer) ? &RG : nullptr))) return rc;
+        if ((rc = launch_step(c, KK, Q, R, &src, &BX, e1, (rect_tiles && c->defer) ? &RG : nullptr))) return rc;
         c->pend_fin = Q;                                   // its tail has just been launched: summaries in a later launch
         c->pend_tail = KK;
         if (c->defer) c->pend_k1 = cur;
-        c->ride.valid = false;
+        forget_unpacked(c);
         c->parity = (c->parity + 1) % (c->defer ? 4 : 3);
         return LPF_OK;
     }
@@ -1658,27 +1750,15 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
         // in order, with a box job waiting: the tiles and the job share one launch (lpf_step_t with those two roles), the tail
         // that reads the tables follows in the next -- the same number of launches as with boxes that never change
         lpf_ctx::Pending cur, none;
-        cur.valid = true; cur.P = P; cur.pre = false; cur.ntail = 0; cur.nk1 = nk1; cur.lb = lb; cur.small = small;
-        cur.direct = direct; cur.dsel = direct_rect ? (c->lazy.f32 ? 5 : 4) : c->lazy.f32 ? c->lazy.mode : 0;
-        if ((rc = launch_step(c, cur, none, none, false, lb, &BX, e1))) return rc;
+        cur.valid = true; cur.P = P; cur.pre = false; cur.ntail = 0; cur.nk1 = nk1; cur.small = small; cur.src = src;
+        if ((rc = launch_step(c, cur, none, none, nullptr, &BX, e1))) return rc;
     } else {
     if ((rc = launch_box_job(c, BX))) return rc;           // (no tiles to ride with)
     if (nk1 > 0) {
         const dim3 g1((unsigned)nk1);
-#define LPF_K1_LAUNCH(R, LT) hipLaunchKernelGGL((lpf_k1_project_t<R, LPF_K1_FLAGS, LT>), g1, dim3(LPF_BLOCK), 0, c->stream, P)
-        if (direct_rect) {
-            typedef LpfDirectRect<uint8_t, 0> R0; typedef LpfDirectRect<float, 1> R1;
-            if (P.tile_pts == 512) { if (!c->lazy.f32) LPF_K1_LAUNCH(2, R0); else LPF_K1_LAUNCH(2, R1); }
-            else       { if (!c->lazy.f32) LPF_K1_LAUNCH(4, R0); else LPF_K1_LAUNCH(4, R1); }
-        } else if (direct) {
-            typedef LpfDirect<uint8_t, 0> D0; typedef LpfDirect<float, 1> D1; typedef LpfDirect<float, 2> D2; typedef LpfDirect<float, 3> D3;
-            if (!c->lazy.f32) LPF_K1_LAUNCH(2, D0);
-            else if (c->lazy.mode == 1) LPF_K1_LAUNCH(2, D1);
-            else if (c->lazy.mode == 2) LPF_K1_LAUNCH(2, D2);
-            else LPF_K1_LAUNCH(2, D3);
-        } else if (P.tile_pts == 512) { if (lb == 1) LPF_K1_LAUNCH(2, uint8_t); else if (lb == 2) LPF_K1_LAUNCH(2, uint16_t); else LPF_K1_LAUNCH(2, uint32_t); }
-        else       { if (lb == 1) LPF_K1_LAUNCH(4, uint8_t); else if (lb == 2) LPF_K1_LAUNCH(4, uint16_t); else LPF_K1_LAUNCH(4, uint32_t); }
-#undef LPF_K1_LAUNCH
+        with_tile_form<false>(src, P.tile_pts >> 8, false, [&](auto lt, auto rw, auto) {
+            hipLaunchKernelGGL((lpf_k1_project_t<decltype(rw)::value, LPF_K1_FLAGS, typename decltype(lt)::type>), g1, dim3(LPF_BLOCK), 0, c->stream, P);
+        });
         LPF_HIP(c, hipGetLastError());
         if (e1) LPF_HIP(c, hipEventRecord(e1, c->stream));
     }
@@ -2126,14 +2206,10 @@ static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int
         uint32_t *cur = (uint32_t *)D.planes_a.p;
         const dim3 grid((Wimg + LPF_TW - 1) / LPF_TW, (Himg + LPF_TH - 1) / LPF_TH, (unsigned)(F * LW));
         const int fuse = in->erode_iters > 0 ? 1 : 0;
-        if (!in->f32)
-            hipLaunchKernelGGL((lpf_wide_pack<uint8_t, 0>), grid, dim3(LPF_BLOCK), 0, c->stream, (const uint8_t *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
-        else if (in->binarize == 0)
-            hipLaunchKernelGGL((lpf_wide_pack<float, 1>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
-        else if (in->binarize == 1)
-            hipLaunchKernelGGL((lpf_wide_pack<float, 2>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
-        else
-            hipLaunchKernelGGL((lpf_wide_pack<float, 3>), grid, dim3(LPF_BLOCK), 0, c->stream, (const float *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
+        with_rule(in->f32 != 0, in->binarize + 1, [&](auto kind) {
+            typedef typename decltype(kind)::elem T;
+            hipLaunchKernelGGL((lpf_wide_pack<T, decltype(kind)::rule>), grid, dim3(LPF_BLOCK), 0, c->stream, (const T *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
+        });
         LPF_HIP(c, hipGetLastError());
         if (in->erode_iters > 1) {                        // further iterations: the narrow path's own kernel, a plane per (frame, word)
             if ((rc = reserve(c, D.planes_b, (size_t)F * LW * hw * 4))) return rc;
@@ -2149,40 +2225,32 @@ static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int
     return LPF_OK;
 }
 
-// where a wide run's outputs go: the caller's device pointers, or staging carved out of D.out for host callers (offsets below)
-struct WideStage {
-    size_t uv, dep, uf, vf, vi, uvv, lw, lvw, ii, cmb, nv, nl, ic, io, bc, bb, of;
-};
-
-// outputs and scratch of a wide run of n points, F frames, W.M masks, Btot boxes, W.nchunk chunks, on buffers D -> W's pointers
-static int wide_bind(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_outputs *out, size_t n, int F, int Btot, LpfWideParams &W, WideStage &S)
+// outputs and scratch of a wide run of n points, F frames, W.M masks, Btot boxes, W.nchunk chunks, on buffers D -> W's pointers: the
+// caller's device pointers, or pieces of D.out (OutStage; S.back(c) queues a host caller's copies)
+static int wide_bind(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_outputs *out, size_t n, int F, int Btot, LpfWideParams &W, OutStage &S)
 {
     int rc;
     const int M = W.M, LW = W.LW, nchunk = W.nchunk;
-    const bool host_io = !out->on_device;
     const size_t nF = (size_t)F, nFM = (size_t)F * M, nMB = (size_t)M * Btot, ncap = out->inst_cap > 0 ? (size_t)F * out->inst_cap : 0;
-    size_t off = 0;
-    auto carve = [&](const void *want, size_t bytes) -> size_t { if (!want || !host_io) return (size_t)-1; const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    S.uv = carve(out->uv, n * 8); S.dep = carve(out->depth, n * 8); S.uf = carve(out->u_f, n * 8); S.vf = carve(out->v_f, n * 8);
-    S.vi = carve(out->valid_idx, n * 8); S.uvv = carve(out->uv_valid, n * 8); S.lw = carve(out->label_words, n * LW * 4);
-    S.lvw = carve(out->label_valid_words, n * LW * 4); S.ii = carve(out->inst_idx, ncap * 8); S.cmb = carve(out->count_mb, nMB * 4);
-    S.nv = carve(out->n_valid, nF * 8); S.nl = carve(out->n_labelled, nF * 8); S.ic = carve(out->inst_count, nFM * 8);
-    S.io = carve(out->inst_off, (nFM + nF) * 8); S.bc = carve(out->best_cnt, nFM * 8); S.bb = carve(out->best_box, nFM * 4);
-    S.of = carve(out->inst_overflow, nF * 4);
-    if (host_io && off && (rc = reserve(c, D.out, off))) return rc;
-    auto dst = [&](void *user, size_t o) -> void * { return !user ? nullptr : host_io ? (void *)((char *)D.out.p + o) : user; };
-    W.uv = (int2 *)dst(out->uv, S.uv);
-    if (!W.uv) { if ((rc = reserve(c, D.uv, n * 8))) return rc; W.uv = (int2 *)D.uv.p; }
-    W.depth = (double *)dst(out->depth, S.dep); W.uf = (double *)dst(out->u_f, S.uf); W.vf = (double *)dst(out->v_f, S.vf);
-    W.valid_idx = (long long *)dst(out->valid_idx, S.vi); W.uv_valid = (int2 *)dst(out->uv_valid, S.uvv);
-    W.label_words = (uint32_t *)dst(out->label_words, S.lw);
-    if (!W.label_words) { if ((rc = reserve(c, D.words, n * LW * 4))) return rc; W.label_words = (uint32_t *)D.words.p; }
-    W.label_valid = (uint32_t *)dst(out->label_valid_words, S.lvw);
-    W.inst_idx = (long long *)dst(out->inst_idx, S.ii); W.count_out = (int32_t *)dst(out->count_mb, S.cmb);
-    W.n_valid = (long long *)dst(out->n_valid, S.nv); W.n_labelled = (long long *)dst(out->n_labelled, S.nl);
-    W.inst_count = (long long *)dst(out->inst_count, S.ic); W.inst_off = (long long *)dst(out->inst_off, S.io);
-    W.best_cnt = (long long *)dst(out->best_cnt, S.bc); W.best_box = (int32_t *)dst(out->best_box, S.bb);
-    W.inst_overflow = (int32_t *)dst(out->inst_overflow, S.of);
+    // every output field of lpf_wide_outputs is bound here and nowhere else (uv and the label words: the later stages read them)
+    S.add(W.uv, out->uv, n * 8, true);
+    S.add(W.depth, out->depth, n * 8);
+    S.add(W.uf, out->u_f, n * 8);
+    S.add(W.vf, out->v_f, n * 8);
+    S.add(W.valid_idx, out->valid_idx, n * 8);
+    S.add(W.uv_valid, out->uv_valid, n * 8);
+    S.add(W.label_words, out->label_words, n * LW * 4, true);
+    S.add(W.label_valid, out->label_valid_words, n * LW * 4);
+    S.add(W.inst_idx, out->inst_idx, ncap * 8);
+    S.add(W.count_out, out->count_mb, nMB * 4);
+    S.add(W.n_valid, out->n_valid, nF * 8);
+    S.add(W.n_labelled, out->n_labelled, nF * 8);
+    S.add(W.inst_count, out->inst_count, nFM * 8);
+    S.add(W.inst_off, out->inst_off, (nFM + nF) * 8);
+    S.add(W.best_cnt, out->best_cnt, nFM * 8);
+    S.add(W.best_box, out->best_box, nFM * 4);
+    S.add(W.inst_overflow, out->inst_overflow, nF * 4);
+    if ((rc = S.commit(c, D.out, !out->on_device))) return rc;
     if ((rc = reserve(c, D.flags, (size_t)std::max(nchunk, 1) * LPF_WIDE_CHUNK))) return rc;
     if ((rc = reserve(c, D.ccnt, (size_t)std::max(nchunk, 1) * 8))) return rc;
     if ((rc = reserve(c, D.cpre, (size_t)std::max(nchunk, 1) * 8))) return rc;
@@ -2193,35 +2261,6 @@ static int wide_bind(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_outputs *out, 
     if ((rc = reserve(c, D.cnt, nMB * 4))) return rc;
     W.flags = (uint32_t *)D.flags.p; W.chunk_cnt = (int2 *)D.ccnt.p; W.chunk_pre = (int2 *)D.cpre.p; W.fcnt = (int2 *)D.fcnt.p;
     W.m_idx = (int *)D.midx.p; W.m_words = (uint32_t *)D.mwords.p; W.m_pts = (float4 *)D.mpts.p; W.cnt = (unsigned *)D.cnt.p;
-    return LPF_OK;
-}
-
-// host outputs of a wide run bound by wide_bind: the copies back, queued on the stream
-static int wide_back(lpf_ctx *c, const lpf_ctx::Wide &D, const lpf_wide_outputs *out, const WideStage &S, size_t n, int F, int M, int Btot)
-{
-    const int LW = (M + 31) / 32;
-    const size_t nF = (size_t)F, nFM = (size_t)F * M, nMB = (size_t)M * Btot, ncap = out->inst_cap > 0 ? (size_t)F * out->inst_cap : 0;
-    auto back = [&](void *user, size_t o, size_t bytes) -> hipError_t {
-        if (!user || !bytes) return hipSuccess;
-        return hipMemcpyAsync(user, (const char *)D.out.p + o, bytes, hipMemcpyDeviceToHost, c->stream);
-    };
-    LPF_HIP(c, back(out->uv, S.uv, n * 8));
-    LPF_HIP(c, back(out->depth, S.dep, n * 8));
-    LPF_HIP(c, back(out->u_f, S.uf, n * 8));
-    LPF_HIP(c, back(out->v_f, S.vf, n * 8));
-    LPF_HIP(c, back(out->valid_idx, S.vi, n * 8));
-    LPF_HIP(c, back(out->uv_valid, S.uvv, n * 8));
-    LPF_HIP(c, back(out->label_words, S.lw, n * LW * 4));
-    LPF_HIP(c, back(out->label_valid_words, S.lvw, n * LW * 4));
-    LPF_HIP(c, back(out->inst_idx, S.ii, ncap * 8));
-    LPF_HIP(c, back(out->count_mb, S.cmb, nMB * 4));
-    LPF_HIP(c, back(out->n_valid, S.nv, nF * 8));
-    LPF_HIP(c, back(out->n_labelled, S.nl, nF * 8));
-    LPF_HIP(c, back(out->inst_count, S.ic, nFM * 8));
-    LPF_HIP(c, back(out->inst_off, S.io, (nFM + nF) * 8));
-    LPF_HIP(c, back(out->best_cnt, S.bc, nFM * 8));
-    LPF_HIP(c, back(out->best_box, S.bb, nFM * 4));
-    LPF_HIP(c, back(out->inst_overflow, S.of, nF * 4));
     return LPF_OK;
 }
 
@@ -2283,7 +2322,7 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
 
     // ---- buffers: the caller's device pointers, or staging for host callers ---------------------------------------------------
     const size_t nMB = (size_t)M * Btot;
-    WideStage S;
+    OutStage S;
     if ((rc = wide_bind(c, D, out, n, F, Btot, W, S))) return rc;
 
     // ---- the launch set ------------------------------------------------------------------------------------------------------
@@ -2313,7 +2352,7 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
         LPF_HIP(c, hipGetLastError());
     }
 
-    if (host_io && (rc = wide_back(c, D, out, S, n, F, M, Btot))) return rc;
+    if (host_io && (rc = S.back(c))) return rc;
     if (host_io || masks_in || (n > 0 && !pts_on_device)) LPF_HIP(c, host_wait(c));   // host buffers may be reused
     if (direct) ++c->stats[7];
     return LPF_OK;
@@ -2331,21 +2370,18 @@ int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
 // so no chunk waits for the one before it (reserve() only waits when it has to grow a buffer).
 #define LPF_DM_BUDGET (256ull << 20)
 
-// lpf_dm_raster for the masks' element type and rule: the count walk, or (scatter) the writing one
-#define LPF_DM_RASTER(S)                                                                                                              \
-    do {                                                                                                                              \
-        if (planes) hipLaunchKernelGGL((lpf_dm_raster<uint32_t, 0, true, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);                   \
-        else if (!in->f32) hipLaunchKernelGGL((lpf_dm_raster<uint8_t, 0, false, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);            \
-        else if (in->binarize == 0) hipLaunchKernelGGL((lpf_dm_raster<float, 1, false, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);     \
-        else if (in->binarize == 1) hipLaunchKernelGGL((lpf_dm_raster<float, 2, false, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);     \
-        else hipLaunchKernelGGL((lpf_dm_raster<float, 3, false, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);                            \
-    } while (0)
+// lpf_dm_raster for the masks' element type and rule (or, with erosion, the planes packed from them): the count walk, or (scatter) the
+// writing one
 static void dm_raster(lpf_ctx *c, const LpfDmParams &P, dim3 g, bool planes, const lpf_wide_input *in, bool scatter)
 {
-    if (scatter) LPF_DM_RASTER(true);
-    else LPF_DM_RASTER(false);
+    with_flag(scatter, [&](auto sc) {
+        constexpr bool S = decltype(sc)::value;
+        if (planes) hipLaunchKernelGGL((lpf_dm_raster<uint32_t, 0, true, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);
+        else with_rule(in->f32 != 0, in->binarize + 1, [&](auto kind) {
+            hipLaunchKernelGGL((lpf_dm_raster<typename decltype(kind)::elem, decltype(kind)::rule, false, S>), g, dim3(LPF_BLOCK), 0, c->stream, P);
+        });
+    });
 }
-#undef LPF_DM_RASTER
 
 int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
                    const lpf_depth_maps_outputs *out)
@@ -2395,14 +2431,6 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
         if ((rc = reserve(c, D.pts, (size_t)most * 16))) return rc;
     }
     const size_t cap = (size_t)out->cap, nF = (size_t)F;
-    size_t o_pix = 0, o_dep = 0, o_pid = 0, o_off = 0, o_need = 0, o_ovf = 0;
-    if (host_io) {
-        size_t off = 0;
-        auto carve = [&](bool want, size_t bytes) -> size_t { const size_t o = off; if (want) off += (bytes + 255) & ~(size_t)255; return o; };
-        o_pix = carve(cap > 0, nF * cap * 8); o_dep = carve(out->depth && cap > 0, nF * cap * 8); o_pid = carve(out->point_idx && cap > 0, nF * cap * 8);
-        o_off = carve(true, nF * (M + 1) * 8); o_need = carve(true, nF * 8); o_ovf = carve(out->overflow != nullptr, nF * 4);
-        if ((rc = reserve(c, D.out, off))) return rc;
-    }
     if ((rc = upload(c, D.foff.p, frame_off, (size_t)(F + 1) * 8))) return rc;
 
     LpfDmParams P;
@@ -2414,13 +2442,16 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     P.cnt = (unsigned *)D.cnt.p;
     P.toff = P.cnt + (size_t)Fc * M * ntile;
     P.tot = P.toff + (size_t)Fc * M * ntile;
-    char *st = (char *)D.out.p;
-    P.pix = (long long *)(host_io ? (cap ? st + o_pix : nullptr) : (void *)out->pix);
-    P.depth = (double *)(host_io ? (out->depth && cap ? st + o_dep : nullptr) : (void *)out->depth);
-    P.pidx = (long long *)(host_io ? (out->point_idx && cap ? st + o_pid : nullptr) : (void *)out->point_idx);
-    P.car_off = (long long *)(host_io ? st + o_off : (void *)out->car_off);
-    P.need = (long long *)(host_io ? st + o_need : (void *)out->need);
-    P.overflow = (int *)(host_io ? (out->overflow ? st + o_ovf : nullptr) : (void *)out->overflow);
+    // the whole batch's outputs (a host caller's lists only with room in them: cap > 0)
+    const bool lists = cap > 0 || !host_io;
+    OutStage S;
+    S.add(P.pix, lists ? out->pix : nullptr, nF * cap * 8);
+    S.add(P.depth, lists ? out->depth : nullptr, nF * cap * 8);
+    S.add(P.pidx, lists ? out->point_idx : nullptr, nF * cap * 8);
+    S.add(P.car_off, out->car_off, nF * (M + 1) * 8);
+    S.add(P.need, out->need, nF * 8);
+    S.add(P.overflow, out->overflow, nF * 4);
+    if ((rc = S.commit(c, D.out, host_io))) return rc;
 
     // ---- the chunks ---------------------------------------------------------------------------------------------------------
     for (int f0 = 0; f0 < F; f0 += Fc) {
@@ -2477,18 +2508,7 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
         }
     }
 
-    if (host_io) {
-        auto back = [&](void *user, size_t o, size_t bytes) -> hipError_t {
-            if (!user || !bytes) return hipSuccess;
-            return hipMemcpyAsync(user, st + o, bytes, hipMemcpyDeviceToHost, c->stream);
-        };
-        LPF_HIP(c, back(out->pix, o_pix, nF * cap * 8));
-        LPF_HIP(c, back(out->depth, o_dep, nF * cap * 8));
-        LPF_HIP(c, back(out->point_idx, o_pid, nF * cap * 8));
-        LPF_HIP(c, back(out->car_off, o_off, nF * (M + 1) * 8));
-        LPF_HIP(c, back(out->need, o_need, nF * 8));
-        LPF_HIP(c, back(out->overflow, o_ovf, nF * 4));
-    }
+    if (host_io && (rc = S.back(c))) return rc;
     if (host_io || host_masks || host_pts) LPF_HIP(c, host_wait(c));   // host buffers may be reused
     return LPF_OK;
 }
@@ -2879,11 +2899,7 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         DevBuf &la = c->cams.label_a[k], &lb2 = c->cams.label_b[k];
         void *cur = nullptr;
         const int mode = m.f32 ? m.binarize + 1 : 0;
-#define LPF_CAMS_PACK(T) (lb_all == 1 ? pack_typed<T, uint8_t>(c, la, lb2, I.W, I.H, c->stream, (const T *)d_masks, F, m.M, mode, m.erode_iters, &cur, rects) : \
-                          lb_all == 2 ? pack_typed<T, uint16_t>(c, la, lb2, I.W, I.H, c->stream, (const T *)d_masks, F, m.M, mode, m.erode_iters, &cur, rects) : \
-                                        pack_typed<T, uint32_t>(c, la, lb2, I.W, I.H, c->stream, (const T *)d_masks, F, m.M, mode, m.erode_iters, &cur, rects))
-        rc = m.f32 ? LPF_CAMS_PACK(float) : LPF_CAMS_PACK(uint8_t);
-#undef LPF_CAMS_PACK
+        rc = pack_masks(c, la, lb2, I.W, I.H, c->stream, d_masks, m.f32 != 0, mode, lb_all, F, m.M, m.erode_iters, &cur, rects);
         if (rc) return rc;
         label_img[k] = cur;
     }
@@ -2917,26 +2933,7 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         P.tile_pts = tile_pts;
         nk1 = L.nseg_total * (int)(L.seg_pts / tile_pts);      // (the same for every camera, as L.pre_scan)
 
-        // outputs: the caller's device pointers, or staging carved out of one buffer (host callers; and what a device caller leaves out
-        // but the pass needs: the dense uv / labels behind the compact copies, the summaries)
-        const bool host_io = !o.on_device;
-        size_t off = 0;
-        auto carve = [&](bool want, size_t bytes) -> size_t { if (!want) return (size_t)-1; const size_t r = off; off += (bytes + 255) & ~(size_t)255; return r; };
-        const size_t nMB = (size_t)(M > 0 ? M : 1) * (Btot > 0 ? Btot : 1);
-        const size_t c_uv = carve((o.uv && host_io) || (!o.uv && o.uv_valid), n * 8),
-                     c_lab = carve((o.label_bits && host_io) || (!o.label_bits && o.label_valid), n * 4),
-                     c_uvv = carve(o.uv_valid && host_io, n * 8), c_labv = carve(o.label_valid && host_io, n * 4),
-                     c_dep = carve(o.depth && host_io, n * 8), c_uf = carve(o.u_f && host_io, n * 8), c_vf = carve(o.v_f && host_io, n * 8),
-                     c_vi = carve(o.valid_idx && host_io, n * 8), c_ii = carve(o.inst_idx && host_io, (size_t)F * (size_t)(o.inst_cap > 0 ? o.inst_cap : 0) * 8),
-                     c_cmb = carve(o.count_mb && host_io, nMB * 4), c_sum = carve(host_io || !o.summary, (size_t)F * sizeof(lpf_frame_summary));
-        if (off && (rc = reserve(c, c->cams.out[k], off))) return rc;
-        char *base = (char *)c->cams.out[k].p;
-        auto pick = [&](void *user, size_t o_) -> void * { return o_ != (size_t)-1 ? (void *)(base + o_) : user; };
-        P.uv = (int2 *)pick(o.uv, c_uv); P.label_bits = (uint32_t *)pick(o.label_bits, c_lab);
-        P.uv_valid = (int2 *)pick(o.uv_valid, c_uvv); P.label_valid = (uint32_t *)pick(o.label_valid, c_labv);
-        P.depth = (double *)pick(o.depth, c_dep); P.uf = (double *)pick(o.u_f, c_uf); P.vf = (double *)pick(o.v_f, c_vf);
-        P.valid_idx = (long long *)pick(o.valid_idx, c_vi); P.inst_idx = (long long *)pick(o.inst_idx, c_ii);
-        P.count_out = (int32_t *)pick(o.count_mb, c_cmb); P.summary = pick(o.summary, c_sum);
+        if ((rc = narrow_bind(c, c->cams.out[k], o, n, F, M, Btot, P))) return rc;
         const bool want_lists = o.valid_idx || o.inst_idx;
         A.ntail[k] = (P.count_boxes ? L.ncblk : 0) + (want_lists ? L.nblk : 0);
         max_tail = std::max(max_tail, A.ntail[k]);
@@ -2945,11 +2942,11 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
     // ---- the launch set: streaming tiles of every camera, then every camera's tail, then every camera's summaries --------------------
     if (nk1 > 0) {
         const dim3 g1((unsigned)nk1);
-#define LPF_CAMS_STREAM(R) do { if (lb_all == 1) hipLaunchKernelGGL((lpf_cams_stream<R, uint8_t>), g1, dim3(LPF_BLOCK), 0, c->stream, A); \
-                                else if (lb_all == 2) hipLaunchKernelGGL((lpf_cams_stream<R, uint16_t>), g1, dim3(LPF_BLOCK), 0, c->stream, A); \
-                                else hipLaunchKernelGGL((lpf_cams_stream<R, uint32_t>), g1, dim3(LPF_BLOCK), 0, c->stream, A); } while (0)
-        if (tile_pts == 512) LPF_CAMS_STREAM(2); else LPF_CAMS_STREAM(4);
-#undef LPF_CAMS_STREAM
+        with_label(lb_all, [&](auto lt) {
+            typedef typename decltype(lt)::type LT;
+            if (tile_pts == 512) hipLaunchKernelGGL((lpf_cams_stream<2, LT>), g1, dim3(LPF_BLOCK), 0, c->stream, A);
+            else hipLaunchKernelGGL((lpf_cams_stream<4, LT>), g1, dim3(LPF_BLOCK), 0, c->stream, A);
+        });
         LPF_HIP(c, hipGetLastError());
     }
     if (L.pre_scan && nk1 > 0)                                 // frames beyond 64 groups (16.7 M points): their prefixes, per camera
@@ -3034,7 +3031,7 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
     LpfCamsWideArgs A;
     memset(&A, 0, sizeof A);
     A.C = C;
-    WideStage S[LPF_MAX_CAMS];
+    OutStage S[LPF_MAX_CAMS];
     int max_lists = 0, max_boxes = 0;
     bool any_boxes = false, any_host = false;
     for (int k = 0; k < C; ++k) {
@@ -3082,7 +3079,7 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
     }
 
     for (int k = 0; k < C; ++k)
-        if (!out[k].on_device && (rc = wide_back(c, c->camsw.cam[k], &out[k], S[k], n, F, A.P[k].M, Btot[k]))) return rc;
+        if (!out[k].on_device && (rc = S[k].back(c))) return rc;
     if (any_host || host_in) LPF_HIP(c, host_wait(c));       // host buffers are filled, or may be reused
     return LPF_OK;
 }

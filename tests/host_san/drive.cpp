@@ -3,10 +3,14 @@
 // frames, their refused arguments and messages), the geometry tables' cache key, the software-pipelined modes with new masks /
 // rectangles / boxes / batch shapes every run (the pinned upload ring is lapped several times: > 40 000 small uploads and sizes that
 // fill a quarter exactly), the box-set and scratch-set rotation, the graph state machine, mask resize / erosion staging and the
-// reader's worker threads.  Kernel launches do nothing (fake_hip.cpp), so results are not checked here -- the GPU tests do that;
-// what is checked is that every call returns what it should and that the sanitizer stays silent.
+// reader's worker threads; then every source a run's tiles can take their label bits from (mask_sources, mask_transitions) and every
+// mask rule / label width of the multi-camera, wide and depth-map packs (pack_forms).  Kernel launches do nothing (fake_hip.cpp), so
+// results are not checked here -- the GPU tests do that; what is checked is that every call returns what it should and that the
+// sanitizer stays silent.  Which kernels are launched, with which grids, is recorded by fake_hip.cpp: count and hash are printed after
+// each section, and FAKE_HIP_TRACE=<file> keeps the lines -- two versions of the host code can be compared launch by launch.
 #include "../../include/lpf.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +18,8 @@
 #include <vector>
 
 extern "C" long long fake_hip_launches(void);
+extern "C" unsigned long long fake_hip_trace_hash(void);
+extern "C" void fake_hip_trace_flush(void);
 
 static int g_fail = 0;
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, ctx_err()); ++g_fail; } } while (0)
@@ -148,8 +154,10 @@ static void host_memory_runs()
 // the software-pipelined modes with everything new every run, long enough to lap the 8 MiB pinned ring several times
 static void pipelined_streams(int mode, int runs, const int W, const int H)
 {
-    // (W x H = 128 x 48: the frames are dense -- masks are packed, the pack rides in mode 4; 1408 x 376: sparse -- with rectangles the
-    //  tiles read the masks themselves, small launches gated, and large ones through the candidate grid, which rides in mode 4)
+    // (W x H = 128 x 48: the frames are dense -- masks are packed, the pack rides in mode 4; 1408 x 376: launches of sparse frames are
+    //  small here -- at most 6 frames hold 1.6 M points sparsely, the large geometry starts above 3.67 M -- and their tiles read all M
+    //  mask bytes of a point, gated by the rectangles; the large launches are dense and packed.  Large sparse launches, whose tiles go
+    //  through the rectangles' candidate grid, take 14 frames or more: mask_sources)
     lpf_ctx *c = nullptr;
     CHECK(lpf_create(&c, 0) == LPF_OK);
     g_ctx = c;
@@ -615,23 +623,267 @@ static void box_files(const char *tmpdir)
     CHECK(lpf_parse_boxes_json(p.c_str(), cs, ix, 4, &nb, &st) == LPF_OK && st == LPF_BOXES_ABSENT);
 }
 
+// ---- where a run's tiles get their label bits -------------------------------------------------------------------------------------
+// lpf_run_batch on one context per mode and image size, for every kind of masks (uint8; float under each of the three rules), from host
+// memory, device memory that is copied (on_device 1) or lent (2), 16-byte aligned or not, M = 0 / 5 / 12 / 32 (no label image; label
+// elements of 1, 2 and 4 bytes), with and without rectangles, with and without erosion -- each in launches of every shape the run tells
+// apart: small sparse (the tiles read the masks themselves), small dense in 512- and 1024-point tiles, large dense, and on the large
+// image large sparse (14 frames or more: with rectangles the tiles read the masks inside them, through the candidate grid).  Every
+// combination runs once with new boxes (the box job rides with the tiles) and once without; every fifth goes through host memory
+// (points and outputs), which a pipelined context runs in order after packing what was lent.
+static void mask_sources(int mode, const int W, const int H)
+{
+    const bool big = W > 1000;
+    lpf_ctx *c = nullptr;
+    CHECK(lpf_create(&c, 0) == LPF_OK);
+    g_ctx = c;
+    CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+    if (mode) CHECK(lpf_set_pipelined(c, mode) == LPF_OK);
+    Dev D;
+    struct Shape { int F; int64_t n; };
+    const Shape small_shapes[4] = {{3, 1700}, {2, 30000}, {1, 1000000}, {2, 4000000}};
+    const Shape big_shapes[2] = {{1, 100000}, {16, 3800000}};      // (3.8 M points: beyond LPF_SMALL_LAUNCH, and 2 N <= 16 W H)
+    const Shape *shapes = big ? big_shapes : small_shapes;
+    const int nshape = big ? 2 : 4, FMAX = big ? 16 : 3;
+    const int64_t NMAX = 4000000, NHOST = 30000;
+    const size_t hw = (size_t)W * H;
+    float *pts = D.get<float>(4 * NMAX);
+    std::vector<float> hpts(4 * NHOST, 1.0f);
+    // (the large image: float masks up to M = 12, uint8 up to 32 -- pages nobody touches)
+    const size_t mask_bytes = big ? std::max((size_t)FMAX * 32 * hw, (size_t)FMAX * 12 * hw * 4) + 64 : (size_t)FMAX * 32 * hw * 4 + 64;
+    char *dmasks = D.get<char>(mask_bytes);
+    std::vector<char> hmasks(big ? 1 : mask_bytes, 1);
+    int32_t *drects = D.get<int32_t>((size_t)FMAX * 32 * 4);
+    std::vector<int32_t> hrects((size_t)FMAX * 32 * 4, 3);
+    double *dcorners = D.get<double>(24 * 2 * FMAX);
+    lpf_outputs od, oh;
+    fill_outputs(D, od, NMAX, FMAX, 32, 2 * FMAX, 1000, 1);
+    fill_outputs(D, oh, NHOST, FMAX, 32, 2 * FMAX, 1000, 0);
+    static const int Ms[4] = {0, 5, 12, 32}, devs[5] = {0, 1, 2, 1, 2};
+    // (the host-memory runs' staging at its largest first: a buffer that has to grow drains the pipeline, box job and all, and when that
+    //  happens depends on how the staging is cut into buffers -- not on what this section is about)
+    for (int sh = 0; sh < 2 && !big; ++sh) {
+        const int64_t off[4] = {0, shapes[sh].n / 2, shapes[sh].n, shapes[sh].n};
+        const int32_t boff[4] = {0, 2, 4, 6};
+        CHECK(lpf_set_masks_u8(c, (const uint8_t *)hmasks.data(), shapes[sh].F, 32, 1, 0) == LPF_OK);
+        CHECK(lpf_set_boxes_ex(c, dcorners, 2, boff, shapes[sh].F, 1) == LPF_OK);
+        CHECK(lpf_run_batch(c, hpts.data(), off, shapes[sh].F, 0, &oh) == LPF_OK);
+    }
+    int combo = 0;
+    for (int kind = 0; kind < 4; ++kind)                     // uint8, float under binarize 0 / 1 / 2
+    for (int dv = big ? 1 : 0; dv < 5; ++dv)                 // host, copied, lent, copied and lent off the 16-byte boundary
+    for (int with_rects = 0; with_rects < 2; ++with_rects)
+    for (int erode = 0; erode < 2; ++erode)
+    for (int sh = 0; sh < nshape; ++sh)
+    for (int mi = 0; mi < 4; ++mi)
+    for (int new_boxes = 1; new_boxes >= 0; --new_boxes) {
+        const int M = Ms[mi], on_device = devs[dv], F = shapes[sh].F;
+        const size_t esz = kind ? 4 : 1;
+        if (big && kind && M > 12) continue;
+        int64_t off[17];
+        int32_t boff[17];
+        off[0] = 0; boff[0] = 0;
+        for (int f = 0; f < F; ++f) {
+            off[f + 1] = (F == 3 && f == 1) ? off[f] : f == F - 1 ? shapes[sh].n : off[f] + shapes[sh].n / F;     // (an empty frame among three)
+            boff[f + 1] = boff[f] + 2;
+        }
+        // (host masks go into scratch set 0, where only an in-order run looks for them)
+        if (mode && !on_device && sh >= 2) continue;
+        const bool host_run = !big && sh < 2 && (combo % 5 == 0 || (mode && !on_device));
+        ++combo;
+        if (with_rects && M > 0) CHECK(lpf_set_mask_rects(c, on_device ? drects : hrects.data(), on_device ? 1 : 0, F, M) == LPF_OK);
+        const char *m = (on_device ? dmasks : hmasks.data()) + (dv >= 3 ? esz : 0);
+        if (kind == 0) CHECK(lpf_set_masks_u8(c, (const uint8_t *)m, F, M, erode, on_device) == LPF_OK);
+        else CHECK(lpf_set_masks_f32(c, (const float *)m, F, M, kind - 1, erode, on_device) == LPF_OK);
+        if (new_boxes) CHECK(lpf_set_boxes_ex(c, dcorners, 2, boff, F, 1) == LPF_OK);
+        if (host_run) CHECK(lpf_run_batch(c, hpts.data(), off, F, 0, &oh) == LPF_OK);
+        else CHECK(lpf_run_batch(c, pts, off, F, 1, &od) == LPF_OK);
+    }
+    int64_t st[8];
+    CHECK(lpf_get_stats(c, st, 8, 0) == LPF_OK);
+    fprintf(stderr, "  mask sources, mode %d, %d x %d: %d runs, drains %lld, step launches %lld, box jobs alone %lld / riding %lld\n", mode, W, H, combo,
+            (long long)st[1], (long long)st[3], (long long)st[4], (long long)st[5]);
+    CHECK(lpf_sync(c) == LPF_OK);
+    lpf_destroy(c);
+    g_ctx = nullptr;
+}
+
+// Masks that are set but not packed when something else happens to the context: a mode switch, a camera of another size, a read or a
+// replacement of the label image, masks set for no frames, a graph capture, a run that cannot be fused; and, in mode 4, tiles and a
+// riding pack that do not go together in one launch (tiles that read masks themselves, or label elements of another size).
+static void mask_transitions()
+{
+    lpf_ctx *c = nullptr;
+    CHECK(lpf_create(&c, 0) == LPF_OK);
+    g_ctx = c;
+    CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+    Dev D;
+    const int F = 2, M = 5;
+    const size_t hw = (size_t)W * H;
+    const int64_t sparse[F + 1] = {0, 900, 1800}, dense[F + 1] = {0, 20000, 40000};
+    float *pts = D.get<float>(4 * 40000);
+    std::vector<float> hpts(4 * 40000, 1.0f);
+    uint8_t *masks = D.get<uint8_t>((size_t)F * 32 * hw);
+    float *fmasks = D.get<float>((size_t)F * 32 * hw);
+    int32_t *drects = D.get<int32_t>((size_t)F * 32 * 4);
+    std::vector<uint32_t> img((size_t)F * hw);
+    lpf_outputs od, oh;
+    fill_outputs(D, od, 40000, F, 32, 1, 1000, 1);
+    fill_outputs(D, oh, 40000, F, 32, 1, 1000, 0);
+    for (int mode = 2; mode <= 4; mode += 2) {
+        // serial masks left unpacked, then the switch: packed on the switch, read by the first pipelined run
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_set_pipelined(c, mode) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, sparse, F, 1, &od) == LPF_OK);
+        // lent masks of the pipelined context: read back (packed for it), then a run
+        CHECK(lpf_set_masks_f32(c, fmasks, F, M, 1, 0, 2) == LPF_OK);
+        CHECK(lpf_get_label_image(c, img.data(), 0) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, sparse, F, 1, &od) == LPF_OK);
+        // ... a run through host memory: packed now, in order
+        CHECK(lpf_set_mask_rects(c, drects, 1, F, M) == LPF_OK);
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_run_batch(c, hpts.data(), sparse, F, 0, &oh) == LPF_OK);
+        // ... tiles that read the masks themselves, then a dense run whose pack would ride beside them (mode 4: drained first), then
+        //     dense runs with label elements of 1, 2, 4 and 1 bytes
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, sparse, F, 1, &od) == LPF_OK);
+        static const int Ms[4] = {5, 12, 32, 5};
+        for (int k = 0; k < 4; ++k) {
+            CHECK(lpf_set_masks_u8(c, masks, F, Ms[k], 0, 2) == LPF_OK);
+            CHECK(lpf_run_batch(c, pts, dense, F, 1, &od) == LPF_OK);
+        }
+        // ... a label image in their place: the lent masks stay on record and the next run still takes them (as it is today)
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_get_label_image(c, img.data(), 0) == LPF_OK);
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_set_label_image(c, img.data(), F, M, 0) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, sparse, F, 1, &od) == LPF_OK);
+        // ... masks for no frames: the run has no masks, the lent ones stay on record and are packed by it (as it is today)
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_set_masks_u8(c, nullptr, 0, 0, 0, 2) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, sparse, F, 1, &od) == LPF_OK);
+        // ... a camera of another size forgets them: a run without masks, then back
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_set_camera(c, T16, K9, W / 2, H, 0, 50) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, sparse, F, 1, &od) == LPF_OK);
+        CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+        // ... and the switch back with lent masks waiting: packed on the switch, read by the serial run
+        CHECK(lpf_set_masks_f32(c, fmasks, F, M, 2, 0, 2) == LPF_OK);
+        CHECK(lpf_set_pipelined(c, 0) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, sparse, F, 1, &od) == LPF_OK);
+        // serial masks left unpacked: read back, replaced by a label image, forgotten with the camera's size
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_get_label_image(c, img.data(), 0) == LPF_OK);
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_set_label_image(c, img.data(), F, M, 0) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, sparse, F, 1, &od) == LPF_OK);
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_set_masks_u8(c, nullptr, 0, 0, 0, 2) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, sparse, F, 1, &od) == LPF_OK);
+        CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+        CHECK(lpf_set_camera(c, T16, K9, W / 2, H, 0, 50) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, sparse, F, 1, &od) == LPF_OK);
+        CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+        // ... and captured into a graph: the tiles of the captured run read the lent masks themselves
+        for (int k = 0; k < 2; ++k) {                      // (single frames: no tables to upload inside the capture)
+            if (k) CHECK(lpf_graph_begin(c) == LPF_OK);
+            CHECK(lpf_set_masks_u8(c, masks, 1, M, 0, 2) == LPF_OK);
+            CHECK(lpf_run(c, pts, 900, 1, &od) == LPF_OK);
+            CHECK(lpf_set_masks_u8(c, masks, 1, M, 0, 2) == LPF_OK);
+            CHECK(lpf_run(c, pts, 20000, 1, &od) == LPF_OK);
+        }
+        lpf_graph *g = nullptr;
+        CHECK(lpf_graph_end(c, &g) == LPF_OK && g);
+        CHECK(lpf_graph_launch(c, g) == LPF_OK);
+        lpf_graph_destroy(g);
+    }
+    lpf_destroy(c);
+    g_ctx = nullptr;
+}
+
+// the packs of lpf_run_cams, lpf_run_wide and lpf_depth_maps for every mask rule and label width: uint8 and float masks under each of
+// the three rules, with and without erosion, 5 / 12 / 32 masks per camera (one label element type per pass), passes of few points
+// (512-point tiles) and of more than 917 504 (1024-point tiles)
+static void pack_forms()
+{
+    lpf_ctx *c = nullptr;
+    CHECK(lpf_create(&c, 0) == LPF_OK);
+    g_ctx = c;
+    CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+    Dev D;
+    const size_t hw = (size_t)W * H;
+    const int64_t NMAX = 1000000;
+    float *pts = D.get<float>(4 * NMAX);
+    char *dmasks = D.get<char>(32 * hw * 4 + 64);
+    int32_t *drects = D.get<int32_t>(32 * 4);
+    static const int Ms[3] = {5, 12, 32};
+    for (int kind = 0; kind < 4; ++kind)
+    for (int erode = 0; erode < 3; ++erode)
+    for (int mi = 0; mi < 3; ++mi)
+    for (int shape = 0; shape < 2; ++shape)
+    for (int unaligned = 0; unaligned < 2; ++unaligned) {
+        const int64_t off[2] = {0, shape ? NMAX : 3000};
+        lpf_cam_input cam;
+        memset(&cam, 0, sizeof cam);
+        memcpy(cam.T_velo_to_rect, T16, sizeof T16); memcpy(cam.K, K9, sizeof K9); cam.W = W; cam.H = H; cam.depth_max_excl = 50;
+        cam.masks.masks = dmasks + (unaligned ? (kind ? 4 : 1) : 0); cam.masks.rects = erode ? nullptr : drects; cam.masks.M = Ms[mi];
+        cam.masks.f32 = kind != 0; cam.masks.binarize = kind ? kind - 1 : 0; cam.masks.erode_iters = erode; cam.masks.on_device = 1;
+        lpf_outputs o;
+        fill_outputs(D, o, 1, 1, 1, 1, 100, 1);
+        o.uv = nullptr; o.label_bits = nullptr; o.valid_idx = nullptr; o.uv_valid = nullptr; o.label_valid = nullptr;      // (summaries and lists' counts only)
+        o.inst_idx = nullptr; o.count_mb = nullptr;
+        CHECK(lpf_run_cams(c, pts, off, 1, 1, &cam, 1, &o) == LPF_OK);
+        if (shape || unaligned) continue;
+        lpf_wide_outputs w1;
+        memset(&w1, 0, sizeof w1);
+        w1.n_valid = D.get<int64_t>(1); w1.on_device = 1;
+        CHECK(lpf_run_wide(c, pts, off, 1, 1, &cam.masks, &w1) == LPF_OK);
+        lpf_depth_maps_outputs dm;
+        memset(&dm, 0, sizeof dm);
+        dm.cap = 100; dm.pix = D.get<int64_t>(100); dm.car_off = D.get<int64_t>(Ms[mi] + 1); dm.need = D.get<int64_t>(1); dm.on_device = 1;
+        CHECK(lpf_depth_maps(c, pts, off, 1, 1, &cam.masks, &dm) == LPF_OK);
+    }
+    lpf_destroy(c);
+    g_ctx = nullptr;
+}
+
+static void section(const char *name)
+{
+    fprintf(stderr, "  trace after %-24s %lld launches, hash %016llx\n", name, fake_hip_launches(), fake_hip_trace_hash());
+}
+
 int main(int argc, char **argv)
 {
     const char *tmp = argc > 1 ? argv[1] : "/tmp";
     const int runs = argc > 2 ? atoi(argv[2]) : 12000;
     argument_errors();
     host_memory_runs();
+    section("host_memory_runs");
     wide_and_multicam_runs();
+    section("wide_and_multicam_runs");
     table_key();
     ring_of_small_uploads();
+    section("table_key, ring");
     pipelined_streams(2, runs, W, H);
     pipelined_streams(4, runs, W, H);
     pipelined_streams(2, runs / 8, 1408, 376);
     pipelined_streams(4, runs / 8, 1408, 376);
-    pipelined_streams(0, runs / 8, 1408, 376);               // in order: the candidate grid goes ahead of the tiles as a kernel
+    pipelined_streams(0, runs / 8, 1408, 376);               // in order
+    section("pipelined_streams");
     graphs();
+    section("graphs");
     reader(tmp);
     box_files(tmp);
-    fprintf(stderr, "drive: %d failed checks, %lld fake launches\n", g_fail, fake_hip_launches());
+    for (int mode = 0; mode <= 4; mode += 2) {
+        mask_sources(mode, W, H);
+        mask_sources(mode, 1408, 376);                       // (large sparse launches: the rectangles' candidate grid ahead of the tiles, riding in mode 4)
+    }
+    section("mask_sources");
+    mask_transitions();
+    section("mask_transitions");
+    pack_forms();
+    section("pack_forms");
+    fake_hip_trace_flush();
+    fprintf(stderr, "drive: %d failed checks, %lld fake launches, trace hash %016llx\n", g_fail, fake_hip_launches(), fake_hip_trace_hash());
     return g_fail ? 1 : 0;
 }

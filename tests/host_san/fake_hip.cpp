@@ -5,11 +5,18 @@
 // objects.  What runs under ASan / UBSan / TSan is therefore everything the host code does around the launches: argument
 // validation, the pinned upload ring, the rotation of scratch sets and box sets, the table builders, the graph state machine and
 // the reader's worker threads -- with every "device" and "pinned" buffer a heap block whose bounds the sanitizer knows.
+// Which kernels the host code launches, and with which grids, is recorded: every launch is a line "<kernel> gx gy gz bx by bz" (the
+// kernel's mangled name as the code object lists it; no pointer-valued arguments -- they differ from run to run), folded into a running
+// hash (fake_hip_trace_hash) and written to the file FAKE_HIP_TRACE names, if it is set.  Two builds of the host code that launch the
+// same kernels in the same order have the same hash and the same file.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <map>
+#include <mutex>
+#include <string>
 
 extern "C" {
 
@@ -23,6 +30,35 @@ struct dim3_ { unsigned x, y, z; };
 static std::atomic<long long> g_launches{0}, g_copies{0};
 long long fake_hip_launches(void) { return g_launches.load(); }
 long long fake_hip_copies(void) { return g_copies.load(); }
+
+// The launch trace.  Its state is a function-local static: hipcc's registration constructors (__hipRegisterFunction) run before this
+// file's own static objects would be constructed.
+namespace {
+struct Trace {
+    std::mutex mu;
+    std::map<const void *, std::string> names;            // host stub -> kernel name
+    unsigned long long hash = 1469598103934665603ull;     // FNV-1a over the lines
+    FILE *file = nullptr;
+    bool opened = false;
+};
+Trace &trace() { static Trace *t = new Trace; return *t; }
+void trace_launch(const char *name, dim3_ g, dim3_ b)
+{
+    char line[640];
+    const int n = snprintf(line, sizeof line, "%s %u %u %u %u %u %u\n", name, g.x, g.y, g.z, b.x, b.y, b.z);
+    Trace &t = trace();
+    std::lock_guard<std::mutex> lock(t.mu);
+    for (int i = 0; i < n && i < (int)sizeof line - 1; ++i) t.hash = (t.hash ^ (unsigned char)line[i]) * 1099511628211ull;
+    if (!t.opened) {
+        t.opened = true;
+        const char *path = getenv("FAKE_HIP_TRACE");
+        if (path && *path) t.file = fopen(path, "w");
+    }
+    if (t.file) fputs(line, t.file);
+}
+}  // namespace
+unsigned long long fake_hip_trace_hash(void) { Trace &t = trace(); std::lock_guard<std::mutex> lock(t.mu); return t.hash; }
+void fake_hip_trace_flush(void) { Trace &t = trace(); std::lock_guard<std::mutex> lock(t.mu); if (t.file) fflush(t.file); }
 
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return 0; }
 hipError_t hipSetDevice(int) { return 0; }
@@ -54,7 +90,7 @@ hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.001f; return 0; }
 
 hipError_t hipGraphInstantiate(hipGraphExec_t *x, hipGraph_t, void *, void *, size_t) { *x = new fake_exec{1}; return 0; }
-hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { ++g_launches; return 0; }
+hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { ++g_launches; trace_launch("hipGraphLaunch", dim3_{0, 0, 0}, dim3_{0, 0, 0}); return 0; }
 hipError_t hipGraphDestroy(hipGraph_t g) { delete g; return 0; }
 hipError_t hipGraphExecDestroy(hipGraphExec_t x) { delete x; return 0; }
 
@@ -62,14 +98,27 @@ hipError_t hipGraphExecDestroy(hipGraphExec_t x) { delete x; return 0; }
 static thread_local struct { dim3_ g, b; size_t shm; hipStream_t s; } t_cfg;
 hipError_t __hipPushCallConfiguration(dim3_ g, dim3_ b, size_t shm, hipStream_t s) { t_cfg.g = g; t_cfg.b = b; t_cfg.shm = shm; t_cfg.s = s; return 0; }
 hipError_t __hipPopCallConfiguration(dim3_ *g, dim3_ *b, size_t *shm, hipStream_t *s) { *g = t_cfg.g; *b = t_cfg.b; *shm = t_cfg.shm; *s = t_cfg.s; return 0; }
-hipError_t hipLaunchKernel(const void *, dim3_ g, dim3_ b, void **, size_t, hipStream_t)
+hipError_t hipLaunchKernel(const void *fn, dim3_ g, dim3_ b, void **, size_t, hipStream_t)
 {
     if (g.x == 0 || b.x == 0 || b.x > 1024) { fprintf(stderr, "fake_hip: launch with grid %u block %u\n", g.x, b.x); abort(); }
     ++g_launches;
+    const char *name = "?";
+    {
+        Trace &t = trace();
+        std::lock_guard<std::mutex> lock(t.mu);
+        auto it = t.names.find(fn);
+        if (it != t.names.end()) name = it->second.c_str();     // (entries are never removed: the pointer stays good)
+    }
+    trace_launch(name, g, b);
     return 0;
 }
 void **__hipRegisterFatBinary(const void *) { static void *h; return &h; }
-void __hipRegisterFunction(void **, const void *, char *, const char *, unsigned, void *, void *, void *, void *, int *) {}
+void __hipRegisterFunction(void **, const void *host_fn, char *, const char *device_name, unsigned, void *, void *, void *, void *, int *)
+{
+    Trace &t = trace();
+    std::lock_guard<std::mutex> lock(t.mu);
+    t.names[host_fn] = device_name;
+}
 void __hipRegisterVar(void **, void *, char *, const char *, int, size_t, int, int) {}
 void __hipUnregisterFatBinary(void **) {}
 

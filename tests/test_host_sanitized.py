@@ -8,7 +8,14 @@ GPU box, where sanitizer runs are not available):
     ThreadSanitizer, driven by tests/host_san/drive.cpp: argument validation, host-memory runs, lpf_run_cams / lpf_run_cams_wide /
     lpf_run_wide / lpf_run_frame_wide / lpf_depth_maps with host and device outputs, > 24 000 software-pipelined runs with
     new masks / rectangles / boxes / batch shapes (the pinned upload ring is lapped many times, with pieces that fill a quarter
-    exactly: ADVICE round 3), the box-set and scratch-set rotation, the graph state machine, and the reader's worker threads.
+    exactly: ADVICE round 3), the box-set and scratch-set rotation, the graph state machine, and the reader's worker threads; then
+    every source a run's tiles take their label bits from -- uint8 masks and float masks under each rule, from host memory, copied and
+    lent device memory, aligned or not, M = 0 / 5 / 12 / 32, with and without rectangles and erosion, serial, mode 2 and mode 4, in
+    small sparse, small dense, large dense and (14 frames and more of 1408 x 376) large sparse launches, with and without a box job,
+    through device and host memory; a mode switch, a camera of another size, a label image read or set, masks for no frames and a
+    graph capture with unpacked masks pending; mode-4 launches whose pack and tiles do not go together; and the packs of
+    lpf_run_cams / lpf_run_wide / lpf_depth_maps for every rule and label width.  fake_hip.cpp records every launch (kernel name,
+    grid, block): the driver prints count and hash per section, and FAKE_HIP_TRACE=<file> keeps the lines.
 """
 import os
 import shutil
