@@ -55,7 +55,8 @@ extern "C" {
                                       8 (continued): lpf_depth_maps_outputs, lpf_depth_maps (added; nothing else changed)
                                       8 (continued): lpf_depth_overlay_input, lpf_depth_overlay_outputs, lpf_depth_overlays (added;
                                          nothing else changed)
-                                      8 (continued): lpf_match2d_input, lpf_match2d_outputs, lpf_match_2d (added; nothing else changed) */
+                                      8 (continued): lpf_match2d_input, lpf_match2d_outputs, lpf_match_2d (added; nothing else changed)
+                                      8 (continued): lpf_inside_input, lpf_inside_outputs, lpf_inside_masks (added; nothing else changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -542,6 +543,61 @@ typedef struct lpf_match2d_outputs {           /* any pointer may be NULL: only 
     int32_t  reserved;
 } lpf_match2d_outputs;
 int lpf_match_2d(lpf_ctx *ctx, int F, const lpf_match2d_input *in, const lpf_match2d_outputs *out);
+
+/* lpf_inside_masks: V3's per-car inside / outside split for a batch of F frames in ONE call, from what a run leaves behind.  V3's
+ * statistics dicts carry, next to the counts, inside_mask = oriented_point_in_bbox(car_points, best box) for a car that found its box
+ * (V3:386-398) and None for one that did not (V3:413-425); create_colored_point_cloud_with_bbox_analysis (V3:471-515) and the geometry
+ * list of V3:606-621 show car_points[inside_mask] and car_points[~inside_mask].  The inputs are a run's outputs -- lpf_run_batch's
+ * inst_idx and summary columns, or lpf_run_wide's inst_idx / inst_off / best_box / best_cnt as they are -- the points are the run's
+ * points, and the boxes and the `oriented` flag are the ones in force (lpf_set_boxes*): the packed parameters the run counted with.
+ * Car m of frame f is MATCHED when best_box[f][m] >= 0 and best_cnt[f][m] >= min_points (V3:379).  With list m = entries
+ * inst_off[f][m] .. inst_off[f][m + 1] of row f of inst_idx (k of them), and each entry of it tested against that ONE box:
+ *   inside     parallel to inst_idx: 1 where the entry's point lies in the car's best box, else 0; all 0 for an unmatched or empty car.
+ *              The test is the counting kernels' own, so a matched car's bytes sum to best_cnt[f][m] bit for bit.
+ *   part_idx   the stable partition of the list, in the car's own entries: the inside entries first, then the outside ones, each in the
+ *              list's (ascending) order; the outside part starts at inst_off[f][m] + n_inside[f][m].  An unmatched car's entries are
+ *              its list unchanged.  These are point indices within the frame.
+ *   part_xyz   the float32 x, y, z of the points of part_idx, in that order: car_points[inside_mask] followed by
+ *              car_points[~inside_mask] (V3:488, V3:498), or car_points itself (V3:481).
+ *   n_inside   bytes set for the car (0 for an unmatched one);  matched: 0 / 1.
+ * Entries at or beyond inst_off[f][M] of a row are NOT WRITTEN, and no entry of the rows of a frame whose lists did not fit
+ * (inst_overflow: inst_off[f][M] > inst_cap) is: such a frame's n_inside is 0, its matched is as above.  M (0 .. LPF_MAX_MASKS_WIDE) is
+ * the width of the per-car arrays, as lpf_run_wide's; lpf_frame_summary's columns are 32 wide and go in as their first M + 1 / M entries.
+ * The masks, boxes, rectangles and label state of the other calls are left as they were.  Not capturable (LPF_ERR_STATE between
+ * lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it first launches what the pipeline owes (no host wait), then
+ * runs in order.  pts (pts_on_device), the lists (in->on_device) and the outputs (out->on_device) are each in host or device memory;
+ * frame_off is host memory.  With device outputs the call only enqueues work (unless some input is in host memory); with host outputs it
+ * returns with them filled, after one host wait -- two when the lists are in device memory, whose offsets it has to read first.
+ * Lists in host memory are checked; lists in device memory are not, but nothing is read or written out of bounds whatever they hold: a
+ * car whose offsets do not ascend within [0, inst_cap] is skipped, an index outside the frame's points counts as outside (coordinates
+ * 0), a best box outside the frame's boxes as none.
+ * LPF_ERR_ARG: NULL in / out, F < 0, M out of range, inst_cap < 0, min_points < 0, frame_off NULL or bad, pts NULL with points, inst_off
+ * NULL, best_box or best_cnt NULL with M > 0, inst_idx NULL with inst_cap > 0 and M > 0; host lists: offsets that are negative or
+ * decrease, a best_box at or beyond the frame's box count, a negative best_cnt.  LPF_ERR_STATE: no boxes in force, or boxes for
+ * another number of frames.
+ * Device memory: 24 bytes per frame; 16 bytes per point for host points; F * (8 inst_cap + 20 M + 8) bytes for host lists and
+ * F * (21 inst_cap + 12 M) for host outputs (grow-only, allocated on first use). */
+typedef struct lpf_inside_input {
+    const int64_t *inst_idx;   /* [F][inst_cap]  as lpf_wide_outputs / lpf_run_batch write it */
+    int64_t        inst_cap;
+    const int64_t *inst_off;   /* [F][M + 1] */
+    const int32_t *best_box;   /* [F][M] */
+    const int64_t *best_cnt;   /* [F][M] */
+    int32_t        M, min_points;
+    int32_t        on_device;  /* the four arrays are device memory, lent until the call's work has completed */
+    int32_t        reserved;
+} lpf_inside_input;
+typedef struct lpf_inside_outputs {      /* any pointer may be NULL: not wanted */
+    uint8_t *inside;           /* [F][inst_cap]  parallel to inst_idx */
+    int64_t *part_idx;         /* [F][inst_cap]  per car: inside entries first, then outside */
+    float   *part_xyz;         /* [F][inst_cap][3] */
+    int64_t *n_inside;         /* [F][M]  0 for an unmatched car */
+    int32_t *matched;          /* [F][M]  0 / 1 */
+    int32_t  on_device;
+    int32_t  reserved;
+} lpf_inside_outputs;
+int lpf_inside_masks(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_inside_input *in,
+                     const lpf_inside_outputs *out);
 
 /* cv2.resize(mask.astype(np.uint8), (camera.width, camera.height)) (V3:222; INTER_LINEAR, the default) for masks that do not arrive at
  * the camera's size (the reference's scripts all pass retina_masks=True, so theirs do): n planes [h][w] of uint8 -> n planes [H][W]

@@ -92,6 +92,18 @@ class Match2dOutputs(ctypes.Structure):
                 ("cost", _P), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class InsideInput(ctypes.Structure):
+    """lpf_inside_input (include/lpf.h): a run's instance lists and best boxes, for lpf_inside_masks"""
+    _fields_ = [("inst_idx", _P), ("inst_cap", _I64), ("inst_off", _P), ("best_box", _P), ("best_cnt", _P), ("M", ctypes.c_int32),
+                ("min_points", ctypes.c_int32), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class InsideOutputs(ctypes.Structure):
+    """lpf_inside_outputs (include/lpf.h): per list entry the inside byte and the inside-first partition, per car the counts"""
+    _fields_ = [("inside", _P), ("part_idx", _P), ("part_xyz", _P), ("n_inside", _P), ("matched", _P), ("on_device", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 LPF_MAX_CAMS = 4                        # lpf_run_cams / lpf_run_cams_wide: cameras of one pass
 
 
@@ -258,6 +270,7 @@ def load(path=None):
     lib.lpf_depth_maps.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(DepthMapsOutputs)]
     lib.lpf_depth_overlays.argtypes = [_P, ctypes.c_int, ctypes.POINTER(DepthOverlayInput), ctypes.POINTER(DepthOverlayOutputs)]
     lib.lpf_match_2d.argtypes = [_P, ctypes.c_int, ctypes.POINTER(Match2dInput), ctypes.POINTER(Match2dOutputs)]
+    lib.lpf_inside_masks.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(InsideInput), ctypes.POINTER(InsideOutputs)]
     lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_cams_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(WideOutputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
@@ -294,7 +307,8 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_graph_begin", "lpf_graph_end", "lpf_graph_launch", "lpf_graph_destroy",
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
-            "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d")
+            "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d",
+            "lpf_inside_masks")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -985,16 +999,21 @@ class LpfContext:
             res.append(r)
         return res
 
+    def stage_points(self, frames):
+        """The points of a batch put where the library reads them, once, for several calls on the same frames (``staged=`` of
+        run_batch, run_wide and inside_masks): what _stage_points returns.  Keep it until the last of those calls has returned."""
+        return self._stage_points(frames)
+
     def run_batch(self, frames, want_uv=True, want_label=True, want_float=False, want_lists=True,
-                  inst_cap=None, want_valid_uv=False, pinned=False):
+                  inst_cap=None, want_valid_uv=False, pinned=False, staged=None):
         """frames: list of f32[N_f,4] arrays, Scans of a ScanReader or float32 [N_f,4] GPU tensors (see _stage_points).  Returns one
         dict per frame with
         u, v (int32), label_bits, valid_idx, inst_lists, inst_count, count_mb, best_box, best_cnt,
         n_valid, n_labelled (+ depth, uf, vf with want_float; + u_valid, v_valid, label_valid with
         want_valid_uv: the values at the valid points only -- with want_uv/want_label off, a quarter of the read-back).
         pinned=True: the result arrays are views into page-locked buffers the context owns and reuses -- valid until the next
-        run on this context (copy what must live longer); the frame loops use it."""
-        off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the run returns)
+        run on this context (copy what must live longer); the frame loops use it.  staged: stage_points(frames), made by the caller."""
+        off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the run returns)
         F, n = len(off) - 1, int(off[-1])
         M = self.M if self.F_masks else 0
         Btot = int(self.box_off[-1]) if self.box_off is not None else 0
@@ -1185,7 +1204,7 @@ class LpfContext:
         return finish
 
     def run_wide(self, frames, masks, erode_iters=0, binarize="astype", rects=None, v3_pipeline=False, want_uv=True, want_float=False,
-                 want_lists=True, want_valid_uv=False, inst_cap=None):
+                 want_lists=True, want_valid_uv=False, inst_cap=None, staged=None):
         """Frames with up to 256 masks each in ONE native pass (lpf_run_wide): every point is projected and read once.
         frames: as run_batch's -- f32[N_f,4] host arrays, Scans of a ScanReader (read in HBM where they are), float32 [N,4] GPU
         tensors.  masks: [M,H,W] or [F,M,H,W] (uint8 / bool, or
@@ -1193,14 +1212,14 @@ class LpfContext:
         optional [F,M,4] hint of set_mask_rects.  Boxes and camera are the ones in force; the masks, boxes and rectangles of the
         narrow calls are left as they are.  Returns one dict per frame with what run_batch returns -- inst_count, best_box,
         best_cnt of length M, count_mb [M, B_f] -- plus label_words [N_f, LW] (bit b of word w = mask 32 w + b; LW = ceil(M / 32)),
-        and with want_valid_uv label_valid_words [n_valid, LW]."""
+        and with want_valid_uv label_valid_words [n_valid, LW].  staged: stage_points(frames), made by the caller."""
         if v3_pipeline:
             binarize = "v3"
         F = len(frames)
         if F == 0:
             raise ValueError("no frames")
         masks, M, is_f, mdev, rects = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
-        off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the run returns)
+        off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the run returns)
         n = int(off[-1])
         if mdev:
             import torch
@@ -1469,6 +1488,86 @@ class LpfContext:
                 res[k] = [flat[k][det_off[f]:det_off[f + 1]] for f in range(F)]
         for w in mats:
             res[w] = [flat[w][pair_off[f]:pair_off[f + 1]].reshape(int(D[f]), int(B[f])) for f in range(F)]
+        return res
+
+    INSIDE_WANT = ("inside", "part_idx", "part_xyz", "n_inside", "matched")
+    _INSIDE_DTYPE = {"inside": "uint8", "part_idx": "int64", "part_xyz": "float32", "n_inside": "int64", "matched": "int32"}
+
+    @staticmethod
+    def inside_batch(inst_idx, inst_off, best_box, best_cnt):
+        """The four list arrays of inside_masks checked and described: (on_device, F, M, inst_cap).  ValueError for host arrays mixed
+        with GPU tensors, GPU tensors of another dtype than int64 / int64 / int32 / int64, and shapes that are not [F, inst_cap],
+        [F, M + 1], [F, M], [F, M] with 0 <= M <= 256."""
+        every = (inst_idx, inst_off, best_box, best_cnt)
+        n_dev = sum(1 for a in every if _is_torch(a) and a.is_cuda)
+        if n_dev not in (0, 4):
+            raise ValueError("inside_masks: host arrays and GPU tensors are mixed (%d of 4 list arrays are on the GPU)" % n_dev)
+        shp = [tuple(a.shape) for a in every]
+        if any(len(t) != 2 for t in shp) or len({t[0] for t in shp}) != 1:
+            raise ValueError("inside_masks: inst_idx [F, inst_cap], inst_off [F, M + 1], best_box [F, M], best_cnt [F, M], got %s" % (shp,))
+        F, M = shp[0][0], shp[2][1]
+        if shp[1][1] != M + 1 or shp[3][1] != M or not 0 <= M <= LPF_MAX_MASKS_WIDE:
+            raise ValueError("inside_masks: inst_off [F, M + 1], best_box [F, M], best_cnt [F, M] with 0 <= M <= %d, got %s"
+                             % (LPF_MAX_MASKS_WIDE, shp[1:]))
+        if n_dev:
+            names = [str(a.dtype).replace("torch.", "") for a in every]
+            if names != ["int64", "int64", "int32", "int64"]:
+                raise ValueError("inside_masks: GPU list arrays must be int64, int64, int32, int64, got %s" % names)
+        return n_dev > 0, F, M, shp[0][1]
+
+    def inside_masks(self, frames, inst_idx, inst_off, best_box, best_cnt, min_points=10, want=INSIDE_WANT, out=None, staged=None):
+        """V3's per-car inside / outside split of a batch of frames in ONE native call (lpf_inside_masks), from what a run on the same
+        frames and boxes returned: ``inst_idx`` int64 [F, inst_cap], ``inst_off`` int64 [F, M + 1], ``best_box`` int32 [F, M],
+        ``best_cnt`` int64 [F, M] -- all host arrays or all GPU tensors.  frames: as run_batch's (or ``staged=stage_points(frames)``).
+        The boxes are the ones in force.  ``want`` picks the outputs (INSIDE_WANT): "inside" uint8 [F, inst_cap] parallel to inst_idx,
+        "part_idx" int64 [F, inst_cap] and "part_xyz" float32 [F, inst_cap, 3] (per car: the inside entries first, then the outside
+        ones), "n_inside" int64 [F, M], "matched" int32 [F, M].  Returns a dict of them: NumPy arrays after one host wait, or GPU
+        tensors in torch's stream order (the call only enqueues work).  Entries the call does not write (beyond a frame's lists, rows
+        of a frame whose lists did not fit) are zero, or what ``out`` -- a dict of the caller's own arrays under the same names -- held."""
+        want = tuple(want)
+        bad = [w for w in want if w not in self.INSIDE_WANT]
+        if bad or not want:
+            raise ValueError("inside_masks: want is a selection of %s, got %r" % (self.INSIDE_WANT, want))
+        if int(min_points) < 0:
+            raise ValueError("inside_masks: min_points must not be negative")
+        dev, F, M, cap = self.inside_batch(inst_idx, inst_off, best_box, best_cnt)
+        off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the call returns)
+        if len(off) - 1 != F:
+            raise ValueError("inside_masks: lists of %d frames, points of %d" % (F, len(off) - 1))
+        shape = {"inside": (F, cap), "part_idx": (F, cap), "part_xyz": (F, cap, 3), "n_inside": (F, M), "matched": (F, M)}
+        inp, o = InsideInput(), InsideOutputs()
+        inp.inst_cap, inp.M, inp.min_points = cap, M, int(min_points)
+        res = {}
+        if dev:
+            import torch
+            d = inst_idx.device
+            arrs = [a.contiguous() for a in (inst_idx, inst_off, best_box, best_cnt)]
+            for w in want:
+                res[w] = out[w] if out is not None and w in out else torch.zeros(shape[w], dtype=getattr(torch, self._INSIDE_DTYPE[w]), device=d)
+                if tuple(res[w].shape) != shape[w]:
+                    raise ValueError("inside_masks: out[%r] must be %s, got %s" % (w, shape[w], tuple(res[w].shape)))
+            ptr = lambda a: _dev_ptr(a) if a.numel() else None
+            for w in want:
+                _dev_ptr(res[w], self._INSIDE_DTYPE[w])
+            inp.on_device = o.on_device = 1
+        else:
+            arrs = [np.ascontiguousarray(a, dtype=t) for a, t in zip((inst_idx, inst_off, best_box, best_cnt), (np.int64, np.int64, np.int32, np.int64))]
+            for w in want:
+                res[w] = out[w] if out is not None and w in out else np.zeros(shape[w], self._INSIDE_DTYPE[w])
+                if res[w].shape != shape[w] or res[w].dtype != np.dtype(self._INSIDE_DTYPE[w]) or not res[w].flags.c_contiguous:
+                    raise ValueError("inside_masks: out[%r] must be a contiguous %s array %s" % (w, self._INSIDE_DTYPE[w], shape[w]))
+            ptr = lambda a: a.ctypes.data if a.size else None
+        inp.inst_idx, inp.inst_off, inp.best_box, inp.best_cnt = (ptr(a) for a in arrs)
+        for w in want:
+            setattr(o, w, ptr(res[w]))
+        if F:
+            if dev:
+                ts = torch.cuda.current_stream(d).cuda_stream
+                self.wait_for_stream(ts)                    # the lists and the outputs' memory belong to torch's stream
+                self._check(self._lib.lpf_inside_masks(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
+                self.release_to_stream(ts)
+            else:
+                self._check(self._lib.lpf_inside_masks(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
         return res
 
     def run_cams_wide(self, frames, cams, want_uv=True, want_float=False, want_lists=True, want_valid_uv=False, inst_cap=None,

@@ -9,6 +9,7 @@
 #include "lpf_depth_maps.hip.h"
 #include "lpf_depth_overlays.hip.h"
 #include "lpf_match2d.hip.h"
+#include "lpf_inside.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -211,6 +212,8 @@ struct lpf_ctx {
     struct DepthOverlays { DevBuf seg, lists, img, mx; } dovl;
     // lpf_match_2d: the frame table, a frame range's staged detections and boxes, its staged outputs (grow-only, allocated on first use)
     struct Match2d { DevBuf tab, in, out; } m2d;
+    // lpf_inside_masks: the frame table, staged host points, staged host lists, staged host outputs (grow-only, allocated on first use)
+    struct Inside { DevBuf tab, pts, in, out; } insd;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -1351,6 +1354,8 @@ void lpf_destroy(lpf_ctx *c)
     for (DevBuf *b : {&c->dovl.seg, &c->dovl.lists, &c->dovl.img, &c->dovl.mx})
         release(*b);
     for (DevBuf *b : {&c->m2d.tab, &c->m2d.in, &c->m2d.out})
+        release(*b);
+    for (DevBuf *b : {&c->insd.tab, &c->insd.pts, &c->insd.in, &c->insd.out})
         release(*b);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
     for (DevBuf *b : all) release(*b);
@@ -2784,6 +2789,148 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
         }
     }
     if (host_in || host_out) LPF_HIP(c, host_wait(c));       // host outputs filled, host inputs free to be reused
+    return LPF_OK;
+}
+
+// ---- lpf_inside_masks (include/lpf.h): V3's inside / outside split of every car of a batch, kernel in lpf_inside.hip.h -----------------
+// One launch per 65535 frames on the box parameters in force.  Host arrays are staged whole: the points, the four list arrays in one
+// buffer, the five outputs in another; of the staged [F][inst_cap] outputs only what the kernel wrote -- the first inst_off[f][M] entries
+// of a frame whose lists fitted -- goes back to the caller, so the rest of the caller's rows stays as it was.
+#define LPF_IN_MAX_FRAMES 65535             // frames per launch: the grid's y
+#define LPF_IN_TAB_PIECE 32768              // frames per upload of the frame table: under a quarter of the pinned ring, so it never waits
+
+int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_inside_input *in,
+                     const lpf_inside_outputs *out)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (use_device(c)) return LPF_ERR_HIP;
+    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_inside_masks cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
+    if (!in || !out || F < 0 || !frame_off)
+        return fail(c, LPF_ERR_ARG, "inside_masks: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
+    const int M = in->M;
+    if (M < 0 || M > LPF_MAX_MASKS_WIDE)
+        return fail(c, LPF_ERR_ARG, "inside_masks: M=%d cars per frame, lpf_inside_masks takes 0 .. LPF_MAX_MASKS_WIDE = %d", M, LPF_MAX_MASKS_WIDE);
+    if (in->inst_cap < 0 || in->min_points < 0)
+        return fail(c, LPF_ERR_ARG, "inside_masks: inst_cap=%lld min_points=%d (neither may be negative)", (long long)in->inst_cap, in->min_points);
+    if (F == 0) return LPF_OK;
+    const long long cap = in->inst_cap;
+    if (!in->inst_off || (M > 0 && (!in->best_box || !in->best_cnt || (cap > 0 && !in->inst_idx))))
+        return fail(c, LPF_ERR_ARG, "inside_masks: inst_idx=%p inst_off=%p best_box=%p best_cnt=%p (inst_off is required, best_box and best_cnt with M > 0, inst_idx with inst_cap > 0)",
+                    (const void *)in->inst_idx, (const void *)in->inst_off, (const void *)in->best_box, (const void *)in->best_cnt);
+    int rc;
+    if ((rc = check_frames(c, "inside_masks", pts, frame_off, F, 0))) return rc;
+    lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
+    if (BX.F == 0) return fail(c, LPF_ERR_STATE, "inside_masks: no boxes in force (lpf_set_boxes* comes first)");
+    if (BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, inside_masks has %d", BX.F, F);
+    const bool host_in = !in->on_device, host_out = !out->on_device;
+    const size_t M1 = (size_t)M + 1;
+    if (host_in) {
+        for (int f = 0; f < F; ++f) {
+            const int64_t *off = in->inst_off + (size_t)f * M1;
+            if (off[0] < 0) return fail(c, LPF_ERR_ARG, "inside_masks: frame %d: inst_off[0]=%lld is negative", f, (long long)off[0]);
+            const int B = BX.box_off[f + 1] - BX.box_off[f];
+            for (int m = 0; m < M; ++m) {
+                if (off[m + 1] < off[m]) return fail(c, LPF_ERR_ARG, "inside_masks: frame %d: inst_off decreases at car %d", f, m);
+                const int32_t bb = in->best_box[(size_t)f * M + m];
+                if (bb >= B) return fail(c, LPF_ERR_ARG, "inside_masks: frame %d car %d: best_box=%d, the frame has %d boxes", f, m, bb, B);
+                if (in->best_cnt[(size_t)f * M + m] < 0)
+                    return fail(c, LPF_ERR_ARG, "inside_masks: frame %d car %d: best_cnt=%lld is negative", f, m, (long long)in->best_cnt[(size_t)f * M + m]);
+            }
+        }
+    }
+    if (M == 0) return LPF_OK;
+    // a software-pipelined context launches what it owes first (no host wait) -- the box tables of the set in force among it: everything
+    // below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+
+    lpf_ctx::Inside &D = c->insd;
+    auto a256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t fc = (size_t)F * (size_t)cap, fm = (size_t)F * M, Ntot = (size_t)frame_off[F];
+    // the offsets on the host: the copies back to a host caller are sized by them
+    std::vector<int64_t> fetched;
+    const int64_t *off_h = host_in ? in->inst_off : nullptr;
+    const bool lists_back = host_out && cap > 0 && (out->inside || out->part_idx || out->part_xyz);
+    if (!host_in && lists_back) {
+        fetched.resize((size_t)F * M1);
+        LPF_HIP(c, hipMemcpyAsync(fetched.data(), in->inst_off, fetched.size() * 8, hipMemcpyDeviceToHost, c->stream));
+        LPF_HIP(c, host_wait(c));
+        off_h = fetched.data();
+    }
+
+    std::vector<LpfInFrame> tab((size_t)F);
+    for (int f = 0; f < F; ++f) {
+        LpfInFrame &t = tab[(size_t)f];
+        t.pt_off = (long long)frame_off[f]; t.N = (int)(frame_off[f + 1] - frame_off[f]);
+        t.box_off = BX.box_off[f]; t.B = BX.box_off[f + 1] - BX.box_off[f]; t.pad = 0;
+    }
+    const size_t i_off = a256(fc * 8), i_cnt = i_off + a256((size_t)F * M1 * 8), i_box = i_cnt + a256(fm * 8);       // idx | off | best_cnt | best_box
+    const size_t o_idx = a256(fc), o_xyz = o_idx + a256(fc * 8), o_n = o_xyz + a256(fc * 12), o_mt = o_n + a256(fm * 8);   // inside | part_idx | part_xyz | n_inside | matched
+    if ((rc = reserve(c, D.tab, (size_t)F * sizeof(LpfInFrame)))) return rc;
+    if (!pts_on_device && Ntot && (rc = reserve(c, D.pts, Ntot * 16))) return rc;
+    if (host_in && (rc = reserve(c, D.in, i_box + fm * 4))) return rc;
+    if (host_out && (rc = reserve(c, D.out, o_mt + fm * 4))) return rc;
+    for (int f = 0; f < F; f += LPF_IN_TAB_PIECE) {
+        const size_t n = (size_t)std::min(F - f, LPF_IN_TAB_PIECE);
+        if ((rc = upload(c, (LpfInFrame *)D.tab.p + f, tab.data() + f, n * sizeof(LpfInFrame)))) return rc;
+    }
+
+    LpfInParams Q;
+    memset(&Q, 0, sizeof Q);
+    Q.frames = (const LpfInFrame *)D.tab.p;
+    Q.pts = (const float4 *)pts;
+    if (!pts_on_device && Ntot) {
+        LPF_HIP(c, hipMemcpyAsync(D.pts.p, pts, Ntot * 16, hipMemcpyHostToDevice, c->stream));
+        Q.pts = (const float4 *)D.pts.p;
+    }
+    if (host_in) {
+        char *S = (char *)D.in.p;
+        if (fc) LPF_HIP(c, hipMemcpyAsync(S, in->inst_idx, fc * 8, hipMemcpyHostToDevice, c->stream));
+        LPF_HIP(c, hipMemcpyAsync(S + i_off, in->inst_off, (size_t)F * M1 * 8, hipMemcpyHostToDevice, c->stream));
+        LPF_HIP(c, hipMemcpyAsync(S + i_cnt, in->best_cnt, fm * 8, hipMemcpyHostToDevice, c->stream));
+        LPF_HIP(c, hipMemcpyAsync(S + i_box, in->best_box, fm * 4, hipMemcpyHostToDevice, c->stream));
+        Q.inst_idx = (const long long *)S; Q.inst_off = (const long long *)(S + i_off);
+        Q.best_cnt = (const long long *)(S + i_cnt); Q.best_box = (const int *)(S + i_box);
+    } else {
+        Q.inst_idx = (const long long *)in->inst_idx; Q.inst_off = (const long long *)in->inst_off;
+        Q.best_cnt = (const long long *)in->best_cnt; Q.best_box = in->best_box;
+    }
+    Q.inst_cap = cap; Q.M = M; Q.min_points = in->min_points;
+    Q.boxp = (const double *)BX.boxp.p;
+    if (host_out) {
+        char *S = (char *)D.out.p;
+        Q.inside = out->inside ? (unsigned char *)S : nullptr;
+        Q.part_idx = out->part_idx ? (long long *)(S + o_idx) : nullptr;
+        Q.part_xyz = out->part_xyz ? (float *)(S + o_xyz) : nullptr;
+        Q.n_inside = out->n_inside ? (long long *)(S + o_n) : nullptr;
+        Q.matched = out->matched ? (int *)(S + o_mt) : nullptr;
+    } else {
+        Q.inside = out->inside; Q.part_idx = (long long *)out->part_idx; Q.part_xyz = out->part_xyz;
+        Q.n_inside = (long long *)out->n_inside; Q.matched = out->matched;
+    }
+    if (Q.inside || Q.part_idx || Q.part_xyz || Q.n_inside || Q.matched) {
+        for (int f0 = 0; f0 < F; f0 += LPF_IN_MAX_FRAMES) {
+            Q.f0 = f0;
+            const dim3 g((unsigned)M, (unsigned)std::min(F - f0, LPF_IN_MAX_FRAMES));
+            with_flag(BX.oriented != 0, [&](auto oriented) {
+                hipLaunchKernelGGL((lpf_inside_cars<decltype(oriented)::value>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
+            });
+            LPF_HIP(c, hipGetLastError());
+        }
+    }
+    if (host_out) {
+        if (Q.n_inside) LPF_HIP(c, hipMemcpyAsync(out->n_inside, Q.n_inside, fm * 8, hipMemcpyDeviceToHost, c->stream));
+        if (Q.matched) LPF_HIP(c, hipMemcpyAsync(out->matched, Q.matched, fm * 4, hipMemcpyDeviceToHost, c->stream));
+        for (int f = 0; lists_back && f < F; ++f) {
+            const int64_t *off = off_h + (size_t)f * M1;
+            const long long n = off[M];
+            if (n <= 0 || n > cap) continue;                              // nothing listed, or lists that did not fit: the row is left alone
+            const size_t r = (size_t)f * (size_t)cap;
+            if (Q.inside) LPF_HIP(c, hipMemcpyAsync(out->inside + r, Q.inside + r, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+            if (Q.part_idx) LPF_HIP(c, hipMemcpyAsync(out->part_idx + r, Q.part_idx + r, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+            if (Q.part_xyz) LPF_HIP(c, hipMemcpyAsync(out->part_xyz + r * 3, Q.part_xyz + r * 3, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    if (host_out || host_in || (!pts_on_device && Ntot)) LPF_HIP(c, host_wait(c));    // host outputs filled, host inputs free to be reused
     return LPF_OK;
 }
 

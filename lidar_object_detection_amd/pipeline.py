@@ -1167,7 +1167,14 @@ def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_
         # of 256 masks and the per-detection results are put together
         return _run_frames_in_mask_groups(frames, stacks, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters,
                                           v3_pipeline, device, ctx, group=LPF_MAX_MASKS_WIDE)
-    batch = _mask_batch(stacks, M, H, W, ctx)
+    res, positions = _frames_pass(frames, stacks, M, camera, use_oriented, erode_iters, v3_pipeline, ctx)
+    return [_frame_result(f, r, m, pos, min_points, gather_scans) for f, r, m, pos in zip(frames, res, counts, positions)]
+
+
+def _frames_pass(frames, stacks, M, camera, use_oriented, erode_iters, v3_pipeline, ctx, staged=None):
+    """ONE native pass over frames of up to 256 masks each (``stacks`` at the camera's size, the camera set): (the pass's dict per
+    frame, each frame's box positions).  It leaves the frames' boxes in force.  staged: the frames' points as ctx.stage_points put them."""
+    batch = _mask_batch(stacks, M, camera.height, camera.width, ctx)
     corners, positions = zip(*(_corners_velo(f.bboxes_3d) for f in frames))
     pts = [f.points for f in frames]
     # only the valid points' pixels and labels are used below: fetch those (a quarter of the dense arrays on real frames)
@@ -1175,13 +1182,13 @@ def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_
         ctx.set_masks(batch, erode_iters=erode_iters, v3_pipeline=v3_pipeline, lend=True)   # (the run follows in this call: GPU masks can be lent)
         ctx.set_boxes(list(corners), oriented=use_oriented)
         # (results arrive in page-locked buffers the context reuses: _frame_result copies out what is handed to the caller)
-        res = ctx.run_batch(pts, want_uv=False, want_label=False, want_valid_uv=True, pinned=True)
+        res = ctx.run_batch(pts, want_uv=False, want_label=False, want_valid_uv=True, pinned=True, staged=staged)
     else:
         # A launch of the narrow path labels a point with one bit per mask in a 32-bit word; more detections than that take the wide
         # pass (lpf_run_wide: ceil(M / 32) label words per point), which projects and reads every point once
         ctx.set_boxes(list(corners), oriented=use_oriented)
-        res = ctx.run_wide(pts, batch, erode_iters=erode_iters, v3_pipeline=v3_pipeline, want_uv=False, want_valid_uv=True)
-    return [_frame_result(f, r, m, pos, min_points, gather_scans) for f, r, m, pos in zip(frames, res, counts, positions)]
+        res = ctx.run_wide(pts, batch, erode_iters=erode_iters, v3_pipeline=v3_pipeline, want_uv=False, want_valid_uv=True, staged=staged)
+    return res, positions
 
 
 def _frame_result(f, r, m, pos, min_points, gather_scans):
@@ -1233,6 +1240,127 @@ def _run_frames_in_mask_groups(frames, stacks, TrVeloToRect, camera, depth_max, 
                 d["car_id"] += g0                            # car ids count the detections of the whole frame (V3:330)
             acc["car_statistics"] += r["car_statistics"]
     return merged
+
+
+# ---------------------------------------------------------------------------------------
+# V3's key set for a batch: corners_velo, inside_mask, car_points (V3:386-398, V3:413-425) and the cloud of V3:606-621
+# ---------------------------------------------------------------------------------------
+def inside_list_arrays(res, M):
+    """The instance lists of a pass (run_batch's / run_wide's dicts, M masks wide) as lpf_inside_masks takes them: inst_idx int64
+    [F, inst_cap], inst_off int64 [F, M + 1], best_box int32 [F, M], best_cnt int64 [F, M]."""
+    F = len(res)
+    inst_off = np.zeros((F, M + 1), np.int64)
+    best_box, best_cnt = np.full((F, M), -1, np.int32), np.zeros((F, M), np.int64)
+    for f, r in enumerate(res):
+        inst_off[f, 1:] = np.cumsum(r["inst_count"][:M])
+        best_box[f], best_cnt[f] = r["best_box"][:M], r["best_cnt"][:M]
+    inst_idx = np.zeros((F, max(int(inst_off[:, M].max()) if F else 0, 1)), np.int64)
+    for f, r in enumerate(res):
+        if inst_off[f, M]:
+            inst_idx[f, :inst_off[f, M]] = np.concatenate(r["inst_lists"][:M])
+    return inst_idx, inst_off, best_box, best_cnt
+
+
+def merge_inside_parts(a, b):
+    """The ``inside_parts`` of one frame over two groups of masks, group ``a``'s cars first (frames with more masks than one pass takes)."""
+    return dict(part_idx=np.concatenate([a["part_idx"], b["part_idx"]]), part_xyz=np.concatenate([a["part_xyz"], b["part_xyz"]]),
+                off=np.concatenate([a["off"], b["off"][1:] + a["off"][-1]]), n_inside=np.concatenate([a["n_inside"], b["n_inside"]]),
+                matched=np.concatenate([a["matched"], b["matched"]]))
+
+
+def car_statistics_v3_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_oriented=True, erode_iters=0,
+                             v3_pipeline=False, device=0, ctx=None):
+    """run_frames whose ``car_statistics`` carry V3's key set (V3:386-398, V3:413-425): next to the counts ``corners_velo`` (f64 [8,3]
+    or None), ``inside_mask`` (bool [k], None for a car without a box) and ``car_points`` -- what calculate_car_point_statistics
+    (style 'v3') returns for each frame, from run_frames' pass plus ONE lpf_inside_masks call for the whole batch: each list entry is
+    tested against its car's best box on the GPU, instead of every car point against every box of the frame in a blocking call per
+    frame.  The points are staged once for both.  Each frame's dict also has ``inside_parts`` -- part_idx int64 [sum k], part_xyz
+    float32 [sum k, 3] (per car: the points inside its box first, then the others), off int64 [m + 1], n_inside int64 [m], matched
+    bool [m] -- which inside_outside_cloud_frames turns into V3's cloud.  Frames with more than 256 masks run once per group of 256."""
+    if not frames:
+        return []
+    ctx = ctx or get_context(device)
+    ctx.set_camera(TrVeloToRect, camera.K, camera.width, camera.height, 0.0, float(depth_max))
+    stacks, erode_iters, v3_pipeline = _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline)
+    counts = [s.shape[0] for s in stacks]
+    M = max(counts)
+    if M > LPF_MAX_MASKS_WIDE:
+        merged = None
+        for g0 in range(0, M, LPF_MAX_MASKS_WIDE):
+            part = [FrameInputs(f.frame, f.points, s[g0:g0 + LPF_MAX_MASKS_WIDE], f.bboxes_3d, f.colors[g0:g0 + LPF_MAX_MASKS_WIDE], f.boxes_2d)
+                    for f, s in zip(frames, stacks)]
+            res = car_statistics_v3_frames(part, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline, device, ctx)
+            if merged is None:
+                merged = res
+                continue
+            for acc, r in zip(merged, res):
+                acc["car_point_sets"] += r["car_point_sets"]
+                acc["bg_assigned"] = acc["bg_assigned"] | r["bg_assigned"]
+                acc["count_mb"] = np.concatenate([acc["count_mb"], r["count_mb"]], axis=0)
+                for d in r["car_statistics"]:
+                    d["car_id"] += g0                        # car ids count the detections of the whole frame (V3:330)
+                acc["car_statistics"] += r["car_statistics"]
+                acc["inside_parts"] = merge_inside_parts(acc["inside_parts"], r["inside_parts"])
+        return merged
+    staged = ctx.stage_points([f.points for f in frames])    # one copy of the batch's points for the pass and the split
+    res, positions = _frames_pass(frames, stacks, M, camera, use_oriented, erode_iters, v3_pipeline, ctx, staged=staged)
+    inst_idx, inst_off, best_box, best_cnt = inside_list_arrays(res, M)
+    # (_frame_result copies what it keeps out of the pass's page-locked buffers; the list arrays above are copies already)
+    out = [_frame_result(f, r, m, pos, min_points, True) for f, r, m, pos in zip(frames, res, counts, positions)]
+    split = ctx.inside_masks(None, inst_idx, inst_off, best_box, best_cnt, min_points=min_points, staged=staged)
+    for i, (f, fr, m) in enumerate(zip(frames, out, counts)):
+        off = inst_off[i, :m + 1].copy()
+        tot = int(off[m])
+        fr["inside_parts"] = dict(part_idx=split["part_idx"][i, :tot].copy(), part_xyz=split["part_xyz"][i, :tot].copy(), off=off,
+                                  n_inside=split["n_inside"][i, :m].copy(), matched=split["matched"][i, :m] != 0)
+        if not fr["car_statistics"]:
+            continue
+        sets = fr["car_point_sets"]
+        for d in fr["car_statistics"]:
+            car = d["car_id"]
+            if d["matched_bbox_id"] >= 0:
+                d["corners_velo"] = np.array(f.bboxes_3d[d["matched_bbox_id"]]["corners_velo"])
+                d["inside_mask"] = split["inside"][i, off[car]:off[car + 1]] != 0
+            else:
+                d["corners_velo"] = None
+                d["inside_mask"] = None
+            d["car_points"] = sets[car]
+    return out
+
+
+def inside_outside_cloud_frames(results, background=(0.5, 0.5, 0.5)):
+    """The geometry list of V3:606-621 as arrays, for each dict of car_statistics_v3_frames: ``points`` float32 [n,3], ``colors``
+    float64 [n,3] and ``parts`` int32 [n,2] = (car id, code) with code 0 an unmatched car's point, 1 inside its car's box, 2 outside
+    it, 3 background (car id -1).  The order is the reference's: per statistics dict an unmatched car's points (V3:481-487), a matched
+    car's inside points and then its outside points (V3:493-507), and the points of no car last (V3:618-621:
+    points_valid[~bg_assigned]).  A car's colour is color[::-1] / 255.0 for all of its points -- the reference computes the same
+    colour for the outside points (V3:504); ``parts`` is what lets a caller tint them apart.  The cars' points are slices of the
+    GPU's inside-first partition (``inside_parts``), not boolean gathers per car."""
+    clouds = []
+    bg_color = np.asarray(background, np.float64).reshape(1, 3)
+    for r in results:
+        ip = r["inside_parts"]
+        off, xyz = ip["off"], ip["part_xyz"]
+        pts, cols, parts = [], [], []
+        for d in r["car_statistics"]:
+            car = d["car_id"]
+            a, b = int(off[car]), int(off[car + 1])
+            col = d["color"]
+            pts.append(xyz[a:b])
+            cols.append(np.tile(np.array([col[2], col[1], col[0]]) / 255.0, (b - a, 1)))
+            code = np.zeros((b - a, 2), np.int32)
+            code[:, 0] = car
+            if d["matched_bbox_id"] >= 0:
+                code[:, 1] = 2
+                code[:int(ip["n_inside"][car]), 1] = 1
+            parts.append(code)
+        rest = np.asarray(r["points_valid"])[~np.asarray(r["bg_assigned"])]
+        pts.append(rest.astype(np.float32, copy=False).reshape(-1, 3))
+        cols.append(np.tile(bg_color, (len(rest), 1)))
+        parts.append(np.tile(np.array([[-1, 3]], np.int32), (len(rest), 1)))
+        clouds.append(dict(frame=r["frame"], points=np.concatenate(pts).astype(np.float32, copy=False),
+                           colors=np.concatenate(cols).astype(np.float64, copy=False).reshape(-1, 3), parts=np.concatenate(parts)))
+    return clouds
 
 
 def _n_points(points):
@@ -1720,17 +1848,20 @@ def process_frames_multicam(seq=0, cam_ids=(0, 1), segmenter=None, image_loader=
 
 
 def process_frame_with_statistics(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_path=None,
-                                  visualizer=None, frames=None, erode_iters=0, v3_pipeline=False, device=0):
+                                  visualizer=None, frames=None, erode_iters=0, v3_pipeline=False, device=0, v3_keys=False):
     """V3's entry point (V3:516-641) without the blocking Open3D window: per frame it prints the
     statistics table and hands (frame, car_statistics, points_valid, bg_assigned) to
-    ``visualizer`` when one is given.  bg_assigned is V4's vectorised form of V3:609-616."""
+    ``visualizer`` when one is given.  bg_assigned is V4's vectorised form of V3:609-616.  ``v3_keys=True``: the statistics carry
+    V3's own key set -- corners_velo, inside_mask, car_points (car_statistics_v3_frames) -- and each result ``inside_parts``, from
+    which inside_outside_cloud_frames builds V3's cloud; the default leaves them out, as cvs_erosion's dicts do."""
     if segmenter is None:
         raise ValueError("process_frame_with_statistics needs the segmentation callable")
     root = kitti360_path or os.environ["KITTI360_DATASET"]
     _, camera, velo_to_cam, velo_to_rect, velo = sequence_setup(root, seq, cam_id)
     items = collect_frame_inputs(root, seq, cam_id, segmenter, image_loader, camera, velo_to_cam, velo, frames)
     results = []
-    for r, item in zip(run_frames(items, velo_to_rect, camera, 50.0, 10, True, erode_iters, v3_pipeline, device), items):
+    run = car_statistics_v3_frames if v3_keys else run_frames
+    for r, item in zip(run(items, velo_to_rect, camera, 50.0, 10, True, erode_iters, v3_pipeline, device), items):
         if r["n_valid"] == 0:
             continue
         print_summary_statistics(r["car_statistics"])
