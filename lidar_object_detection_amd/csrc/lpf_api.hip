@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -204,12 +205,12 @@ struct lpf_ctx {
     // lpf_run_cams_wide: camera c's lpf_run_wide buffers (cam[c]: staged masks, planes, scratch, host-output staging), the pass's frame
     // tables and staged points (grow-only, allocated on first use); its box tables are lpf_run_cams' (cams.bx[c])
     struct CamsWide { Wide cam[LPF_NSETS]; DevBuf tab, pts; } camsw;
-    // lpf_depth_maps: frame offsets, a chunk's winner planes, counters, staged masks / rectangles / points, host-output staging and
-    // (with erosion) lpf_run_wide's label planes in pack.planes_* (grow-only, allocated on first use)
-    struct DepthMaps { Wide pack; DevBuf foff, win, cnt, masks, rects, pts, out; } dmaps;
-    // lpf_depth_overlays: a chunk's staged segmented images and lists, images for host outputs, max_depth for host outputs
+    // lpf_depth_maps: frame offsets, a chunk's winner planes, counters, staged masks and rectangles, staged points, host-output staging
+    // and (with erosion) lpf_run_wide's label planes in pack.planes_* (grow-only, allocated on first use)
+    struct DepthMaps { Wide pack; DevBuf foff, win, cnt, in, pts, out; } dmaps;
+    // lpf_depth_overlays: a chunk's staged segmented images and lists; a chunk's images and the batch's max_depth for host outputs
     // (grow-only, allocated on first use)
-    struct DepthOverlays { DevBuf seg, lists, img, mx; } dovl;
+    struct DepthOverlays { DevBuf in, out; } dovl;
     // lpf_match_2d: the frame table, a frame range's staged detections and boxes, its staged outputs (grow-only, allocated on first use)
     struct Match2d { DevBuf tab, in, out; } m2d;
     // lpf_inside_masks: the frame table, staged host points, staged host lists, staged host outputs (grow-only, allocated on first use)
@@ -489,33 +490,41 @@ void release(DevBuf &b)
     b.p = nullptr; b.cap = 0;
 }
 
-// Where the output arrays of a run live.  add(): one line per array -- the field of the kernel-parameter struct that is to point at
-// it, the caller's pointer (NULL: not asked for), its bytes, and whether the run needs the array itself when the caller left it out.
-// commit(): an array of a device caller is the caller's; one of a host caller, and one the run needs though the caller left it out,
-// is a 256-byte aligned piece of ONE staging buffer, reserved here; anything else is NULL.  back(): the copies of the staged arrays
-// to a host caller, queued on the stream.  Fixed capacity, nothing on the heap: it sits on the per-step path of a pipelined stream.
-struct OutStage {
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Where the arrays of a call live: the caller's device memory, or ONE staging buffer.  add(): one line per array -- the field of the
+// kernel-parameter struct (or a local pointer) that is to point at it, the caller's pointer (NULL: not given / not asked for), the bytes
+// of an element, the elements of the largest range the call will stage at once (of the whole batch, for a call that does not cut it),
+// and whether the call needs the array itself when the caller left it out.  `host` says where the arrays declared next are: a call
+// whose arrays come from both sides sets it between add()s.  commit(): a device caller's array is lent -- the field gets the caller's
+// pointer; a host caller's, and one the call needs though the caller left it out, is a 256-byte aligned piece of the buffer, reserved
+// here; anything else is NULL.  in() / back(): the copies of the staged arrays from / to the host caller, queued on the stream -- all of
+// every array, or per array the elements [first, first + count) of the caller's, which lie at the start of the staged piece.  Fixed
+// capacity, nothing on the heap: it sits on the per-step path of a pipelined stream.
+struct Span { size_t first, count; };
+struct Stage {
     enum { CAP = 20 };
-    struct Item { void *field; void *user; size_t bytes, off; bool needed, staged; } item[CAP];
+    struct Item { void *field; void *user; size_t esz, most, off; bool staged; } item[CAP];
     int n = 0;
+    bool host;
     char *base = nullptr;
-    template <typename T> void add(T *&field, void *user, size_t bytes, bool needed = false)
+    explicit Stage(bool host_ = false) : host(host_) {}
+    template <typename T> void add(T *&field, const void *user, size_t esz, size_t most, bool needed = false)
     {
-        if (n < CAP) item[n] = Item{&field, user, bytes, 0, needed, false};
+        if (n < CAP) item[n] = Item{&field, const_cast<void *>(user), esz, most, 0, user ? host : needed};
         ++n;
     }
-    int commit(lpf_ctx *c, DevBuf &buf, bool host_io)
+    int commit(lpf_ctx *c, DevBuf &buf)
     {
-        if (n > CAP) return fail(c, LPF_ERR_STATE, "OutStage: %d arrays, room for %d", n, (int)CAP);
+        if (n > CAP) return fail(c, LPF_ERR_STATE, "Stage: %d arrays, room for %d", n, (int)CAP);
         size_t total = 0;
         bool any = false;
         for (int i = 0; i < n; ++i) {
             Item &t = item[i];
-            t.staged = t.user ? host_io : t.needed;
             if (!t.staged) continue;
             any = true;
             t.off = total;
-            total += (t.bytes + 255) & ~(size_t)255;
+            total += align256(t.esz * t.most);
         }
         int rc;
         if (any && (rc = reserve(c, buf, total))) return rc;
@@ -526,11 +535,23 @@ struct OutStage {
         }
         return LPF_OK;
     }
-    int back(lpf_ctx *c) const
+    int in(lpf_ctx *c, std::initializer_list<Span> spans = {}) const { return copies(c, spans, true); }
+    int back(lpf_ctx *c, std::initializer_list<Span> spans = {}) const { return copies(c, spans, false); }
+
+private:
+    int copies(lpf_ctx *c, std::initializer_list<Span> spans, bool up) const
     {
-        for (int i = 0; i < n; ++i)
-            if (item[i].staged && item[i].user && item[i].bytes)
-                LPF_HIP(c, hipMemcpyAsync(item[i].user, base + item[i].off, item[i].bytes, hipMemcpyDeviceToHost, c->stream));
+        if (spans.size() && (int)spans.size() != n) return fail(c, LPF_ERR_STATE, "Stage: %d spans for %d arrays", (int)spans.size(), n);
+        for (int i = 0; i < n; ++i) {
+            const Item &t = item[i];
+            const Span r = spans.size() ? spans.begin()[i] : Span{0, t.most};
+            const size_t bytes = r.count * t.esz;
+            if (!t.staged || !t.user || !bytes) continue;
+            if (r.count > t.most) return fail(c, LPF_ERR_STATE, "Stage: array %d: %zu elements, staged for %zu", i, r.count, t.most);
+            char *u = (char *)t.user + r.first * t.esz, *d = base + t.off;
+            if (up) LPF_HIP(c, hipMemcpyAsync(d, u, bytes, hipMemcpyHostToDevice, c->stream));
+            else LPF_HIP(c, hipMemcpyAsync(u, d, bytes, hipMemcpyDeviceToHost, c->stream));
+        }
         return LPF_OK;
     }
 };
@@ -555,7 +576,7 @@ int upload(lpf_ctx *c, void *dst, const void *src, size_t bytes)
         R.cap = LPF_RING_BYTES; R.head = 0;
         for (hipEvent_t &e : R.ev) LPF_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    const size_t q = R.cap / 4, need = (bytes + 255) & ~(size_t)255;
+    const size_t q = R.cap / 4, need = align256(bytes);
     if (need >= q) {
         int rc_ = sync_all(c);
         if (rc_) return rc_;
@@ -582,6 +603,69 @@ int upload(lpf_ctx *c, void *dst, const void *src, size_t bytes)
     memcpy(h, src, bytes);
     ++c->stats[2];
     LPF_HIP(c, hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, c->stream));
+    return LPF_OK;
+}
+
+// A table of n records -> buf, reserved here, through the pinned ring in pieces of LPF_TABLE_PIECE records: each under a quarter of the
+// ring, so none takes upload()'s blocking route, whatever n is
+#define LPF_TABLE_PIECE 32768
+template <typename T> int upload_table(lpf_ctx *c, DevBuf &buf, const T *tab, size_t n)
+{
+    static_assert(sizeof(T) * LPF_TABLE_PIECE + 256 < LPF_RING_BYTES / 4, "a piece must stay under a quarter of the ring");
+    int rc;
+    if ((rc = reserve(c, buf, n * sizeof(T)))) return rc;
+    for (size_t i = 0; i < n; i += LPF_TABLE_PIECE)
+        if ((rc = upload(c, (T *)buf.p + i, tab + i, std::min(n - i, (size_t)LPF_TABLE_PIECE) * sizeof(T)))) return rc;
+    return LPF_OK;
+}
+
+// How a batched call cuts its items (frames, images) into ranges of consecutive items: a range grows while it has fewer than
+// most_items items -- what one launch takes -- and cost(first, count), the bytes it would stage, stays within LPF_STAGE_BUDGET; an item
+// that needs more by itself is a range of its own.  The ranges are planned, and every buffer reserved for the largest of them
+// (largest()), before the first launch, so no range waits for the one before it.
+#define LPF_STAGE_BUDGET (256ull << 20)
+template <typename Cost> std::vector<Span> plan_ranges(size_t items, size_t most_items, Cost &&cost)
+{
+    std::vector<Span> ranges;
+    for (size_t i0 = 0; i0 < items;) {
+        size_t n = 1;
+        while (i0 + n < items && n < most_items && cost(i0, n + 1) <= LPF_STAGE_BUDGET) ++n;
+        ranges.push_back({i0, n});
+        i0 += n;
+    }
+    return ranges;
+}
+template <typename Qty> size_t largest(const std::vector<Span> &ranges, Qty &&qty)
+{
+    size_t most = 0;
+    for (const Span &r : ranges) most = std::max(most, (size_t)qty(r.first, r.count));
+    return most;
+}
+
+// What a batched call begins with: a context, its device, no graph capture in progress (who: the call's name, as the refusal says it)
+// and, where the call projects, a camera.
+int enter(lpf_ctx *c, const char *who, bool need_camera)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (use_device(c)) return LPF_ERR_HIP;
+    if (c->capturing) return fail(c, LPF_ERR_STATE, "%s cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)", who);
+    if (need_camera && !c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera has not been called");
+    return LPF_OK;
+}
+
+// The points [first, first + count) of a caller -> *dev: a device caller's, and no points, are lent; a host caller's are copied in stream
+// order into buf -- reserved for `most` points, the largest range the call will ask for -- and *wait_owed is set: the call has to end
+// with a host_wait, so that the caller may reuse its memory.
+int host_points(lpf_ctx *c, DevBuf &buf, const float *pts, bool on_device, size_t first, size_t count, size_t most, const float4 **dev,
+                bool *wait_owed)
+{
+    *dev = (const float4 *)pts + first;
+    if (on_device || count == 0) return LPF_OK;
+    int rc;
+    if ((rc = reserve(c, buf, most * 16))) return rc;
+    LPF_HIP(c, hipMemcpyAsync(buf.p, pts + 4 * first, count * 16, hipMemcpyHostToDevice, c->stream));
+    *dev = (const float4 *)buf.p;
+    *wait_owed = true;
     return LPF_OK;
 }
 
@@ -1161,19 +1245,19 @@ void narrow_params(LpfParams &P, const lpf_ctx *c, const Cam &cam, const NarrowL
 // them.  Every output field of lpf_outputs is bound here and nowhere else.
 int narrow_bind(lpf_ctx *c, DevBuf &buf, const lpf_outputs &o, size_t n, int F, int M, int Btot, LpfParams &P)
 {
-    OutStage S;
-    S.add(P.summary, o.summary, (size_t)F * sizeof(lpf_frame_summary), true);
-    S.add(P.uv, o.uv, n * 8, o.uv_valid != nullptr);
-    S.add(P.label_bits, o.label_bits, n * 4, o.label_valid != nullptr);
-    S.add(P.uv_valid, o.uv_valid, n * 8);
-    S.add(P.label_valid, o.label_valid, n * 4);
-    S.add(P.depth, o.depth, n * 8);
-    S.add(P.uf, o.u_f, n * 8);
-    S.add(P.vf, o.v_f, n * 8);
-    S.add(P.valid_idx, o.valid_idx, n * 8);
-    S.add(P.inst_idx, o.inst_idx, (size_t)F * (size_t)(o.inst_cap > 0 ? o.inst_cap : 0) * 8);
-    S.add(P.count_out, o.count_mb, (size_t)(M > 0 ? M : 1) * (Btot > 0 ? Btot : 1) * 4);
-    return S.commit(c, buf, !o.on_device);
+    Stage S(!o.on_device);
+    S.add(P.summary, o.summary, sizeof(lpf_frame_summary), (size_t)F, true);
+    S.add(P.uv, o.uv, 8, n, o.uv_valid != nullptr);
+    S.add(P.label_bits, o.label_bits, 4, n, o.label_valid != nullptr);
+    S.add(P.uv_valid, o.uv_valid, 8, n);
+    S.add(P.label_valid, o.label_valid, 4, n);
+    S.add(P.depth, o.depth, 8, n);
+    S.add(P.uf, o.u_f, 8, n);
+    S.add(P.vf, o.v_f, 8, n);
+    S.add(P.valid_idx, o.valid_idx, 8, n);
+    S.add(P.inst_idx, o.inst_idx, 8, (size_t)F * (size_t)(o.inst_cap > 0 ? o.inst_cap : 0));
+    S.add(P.count_out, o.count_mb, 4, (size_t)(M > 0 ? M : 1) * (Btot > 0 ? Btot : 1));
+    return S.commit(c, buf);
 }
 
 // Host outputs of a narrow run of n points, phase (a): the dense arrays are queued.  Then, with result buffers in page-locked memory
@@ -1348,12 +1432,10 @@ void lpf_destroy(lpf_ctx *c)
     }
     release(c->camsw.tab);
     release(c->camsw.pts);
-    for (DevBuf *b : {&c->dmaps.pack.planes_a, &c->dmaps.pack.planes_b, &c->dmaps.foff, &c->dmaps.win, &c->dmaps.cnt, &c->dmaps.masks,
-                      &c->dmaps.rects, &c->dmaps.pts, &c->dmaps.out})
+    for (DevBuf *b : {&c->dmaps.pack.planes_a, &c->dmaps.pack.planes_b, &c->dmaps.foff, &c->dmaps.win, &c->dmaps.cnt, &c->dmaps.in,
+                      &c->dmaps.pts, &c->dmaps.out})
         release(*b);
-    for (DevBuf *b : {&c->dovl.seg, &c->dovl.lists, &c->dovl.img, &c->dovl.mx})
-        release(*b);
-    for (DevBuf *b : {&c->m2d.tab, &c->m2d.in, &c->m2d.out})
+    for (DevBuf *b : {&c->dovl.in, &c->dovl.out, &c->m2d.tab, &c->m2d.in, &c->m2d.out})
         release(*b);
     for (DevBuf *b : {&c->insd.tab, &c->insd.pts, &c->insd.in, &c->insd.out})
         release(*b);
@@ -2231,31 +2313,32 @@ static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int
 }
 
 // outputs and scratch of a wide run of n points, F frames, W.M masks, Btot boxes, W.nchunk chunks, on buffers D -> W's pointers: the
-// caller's device pointers, or pieces of D.out (OutStage; S.back(c) queues a host caller's copies)
-static int wide_bind(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_outputs *out, size_t n, int F, int Btot, LpfWideParams &W, OutStage &S)
+// caller's device pointers, or pieces of D.out (Stage; S.back(c) queues a host caller's copies)
+static int wide_bind(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_outputs *out, size_t n, int F, int Btot, LpfWideParams &W, Stage &S)
 {
     int rc;
     const int M = W.M, LW = W.LW, nchunk = W.nchunk;
     const size_t nF = (size_t)F, nFM = (size_t)F * M, nMB = (size_t)M * Btot, ncap = out->inst_cap > 0 ? (size_t)F * out->inst_cap : 0;
     // every output field of lpf_wide_outputs is bound here and nowhere else (uv and the label words: the later stages read them)
-    S.add(W.uv, out->uv, n * 8, true);
-    S.add(W.depth, out->depth, n * 8);
-    S.add(W.uf, out->u_f, n * 8);
-    S.add(W.vf, out->v_f, n * 8);
-    S.add(W.valid_idx, out->valid_idx, n * 8);
-    S.add(W.uv_valid, out->uv_valid, n * 8);
-    S.add(W.label_words, out->label_words, n * LW * 4, true);
-    S.add(W.label_valid, out->label_valid_words, n * LW * 4);
-    S.add(W.inst_idx, out->inst_idx, ncap * 8);
-    S.add(W.count_out, out->count_mb, nMB * 4);
-    S.add(W.n_valid, out->n_valid, nF * 8);
-    S.add(W.n_labelled, out->n_labelled, nF * 8);
-    S.add(W.inst_count, out->inst_count, nFM * 8);
-    S.add(W.inst_off, out->inst_off, (nFM + nF) * 8);
-    S.add(W.best_cnt, out->best_cnt, nFM * 8);
-    S.add(W.best_box, out->best_box, nFM * 4);
-    S.add(W.inst_overflow, out->inst_overflow, nF * 4);
-    if ((rc = S.commit(c, D.out, !out->on_device))) return rc;
+    S.host = !out->on_device;
+    S.add(W.uv, out->uv, 8, n, true);
+    S.add(W.depth, out->depth, 8, n);
+    S.add(W.uf, out->u_f, 8, n);
+    S.add(W.vf, out->v_f, 8, n);
+    S.add(W.valid_idx, out->valid_idx, 8, n);
+    S.add(W.uv_valid, out->uv_valid, 8, n);
+    S.add(W.label_words, out->label_words, 4, n * LW, true);
+    S.add(W.label_valid, out->label_valid_words, 4, n * LW);
+    S.add(W.inst_idx, out->inst_idx, 8, ncap);
+    S.add(W.count_out, out->count_mb, 4, nMB);
+    S.add(W.n_valid, out->n_valid, 8, nF);
+    S.add(W.n_labelled, out->n_labelled, 8, nF);
+    S.add(W.inst_count, out->inst_count, 8, nFM);
+    S.add(W.inst_off, out->inst_off, 8, nFM + nF);
+    S.add(W.best_cnt, out->best_cnt, 8, nFM);
+    S.add(W.best_box, out->best_box, 4, nFM);
+    S.add(W.inst_overflow, out->inst_overflow, 4, nF);
+    if ((rc = S.commit(c, D.out))) return rc;
     if ((rc = reserve(c, D.flags, (size_t)std::max(nchunk, 1) * LPF_WIDE_CHUNK))) return rc;
     if ((rc = reserve(c, D.ccnt, (size_t)std::max(nchunk, 1) * 8))) return rc;
     if ((rc = reserve(c, D.cpre, (size_t)std::max(nchunk, 1) * 8))) return rc;
@@ -2276,13 +2359,10 @@ static int wide_bind(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_outputs *out, 
 static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
                          const lpf_wide_outputs *out, bool direct)
 {
-    if (!c) return LPF_ERR_ARG;
-    if (use_device(c)) return LPF_ERR_HIP;
-    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_run_wide cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
-    if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera has not been called");
+    int rc;
+    if ((rc = enter(c, "lpf_run_wide", true))) return rc;
     if (!in || !out || !frame_off || F <= 0) return fail(c, LPF_ERR_ARG, "run_wide: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
     const int M = in->M;
-    int rc;
     if ((rc = check_wide_input(c, "run_wide", -1, *in, LPF_MAX_MASKS_WIDE, "lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE", ""))) return rc;
     if ((rc = check_frames(c, "run_wide", pts, frame_off, F, LPF_WIDE_CHUNK))) return rc;
     const int64_t Ntot = frame_off[F];
@@ -2314,20 +2394,14 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     wide_params(W, ctx_cam(c), F, M, nchunk, nbw, BX, out->inst_cap, (const LpfWideFrame *)D.tab.p);
 
     // inputs: points, masks (host masks are staged; device masks are lent), rectangles
-    if (pts_on_device || n == 0) {
-        W.pts = (const float4 *)pts;
-    } else {
-        if ((rc = reserve(c, D.pts, n * 16))) return rc;
-        LPF_HIP(c, hipMemcpyAsync(D.pts.p, pts, n * 16, hipMemcpyHostToDevice, c->stream));
-        W.pts = (const float4 *)D.pts.p;
-    }
-    bool masks_in = false;
+    bool pts_in = false, masks_in = false;
+    if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, 0, n, n, &W.pts, &pts_in))) return rc;
     if (direct) W.planes = nullptr;
     else if ((rc = wide_pack(c, D, in, F, c->W, c->H, W, &masks_in))) return rc;
 
     // ---- buffers: the caller's device pointers, or staging for host callers ---------------------------------------------------
     const size_t nMB = (size_t)M * Btot;
-    OutStage S;
+    Stage S;
     if ((rc = wide_bind(c, D, out, n, F, Btot, W, S))) return rc;
 
     // ---- the launch set ------------------------------------------------------------------------------------------------------
@@ -2358,7 +2432,7 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     }
 
     if (host_io && (rc = S.back(c))) return rc;
-    if (host_io || masks_in || (n > 0 && !pts_on_device)) LPF_HIP(c, host_wait(c));   // host buffers may be reused
+    if (host_io || masks_in || pts_in) LPF_HIP(c, host_wait(c));   // host buffers may be reused
     if (direct) ++c->stats[7];
     return LPF_OK;
 }
@@ -2370,10 +2444,8 @@ int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
 }
 
 // ---- lpf_depth_maps (include/lpf.h): per-car depth maps as sparse lists, kernels in lpf_depth_maps.hip.h ----------------------
-// Frames go through in chunks of Fc: Fc winner planes, counters, staged masks / points (and label planes with erosion) within
-// LPF_DM_BUDGET, or one frame when a single frame needs more.  Every buffer is reserved for the largest chunk before the first launch,
-// so no chunk waits for the one before it (reserve() only waits when it has to grow a buffer).
-#define LPF_DM_BUDGET (256ull << 20)
+// Frames go through in chunks of Fc (plan_ranges, the same cost for every frame): Fc winner planes, counters, staged masks / points
+// (and label planes with erosion).
 
 // lpf_dm_raster for the masks' element type and rule (or, with erosion, the planes packed from them): the count walk, or (scatter) the
 // writing one
@@ -2391,14 +2463,11 @@ static void dm_raster(lpf_ctx *c, const LpfDmParams &P, dim3 g, bool planes, con
 int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
                    const lpf_depth_maps_outputs *out)
 {
-    if (!c) return LPF_ERR_ARG;
-    if (use_device(c)) return LPF_ERR_HIP;
-    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_depth_maps cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
-    if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera has not been called");
+    int rc;
+    if ((rc = enter(c, "lpf_depth_maps", true))) return rc;
     if (!in || !out || F < 0 || (F > 0 && !frame_off))
         return fail(c, LPF_ERR_ARG, "depth_maps: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
     const int M = in->M;
-    int rc;
     if ((rc = check_wide_input(c, "depth_maps", -1, *in, LPF_MAX_MASKS_WIDE, "lpf_depth_maps takes 0 .. LPF_MAX_MASKS_WIDE", ""))) return rc;
     if (out->cap < 0 || !out->car_off || !out->need || (out->cap > 0 && !out->pix))
         return fail(c, LPF_ERR_ARG, "depth_maps: cap=%lld pix=%p car_off=%p need=%p (car_off and need are required, pix with cap > 0)",
@@ -2420,21 +2489,21 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     const bool use_rects = M > 0 && rects_hold(*in);
     const size_t per_frame = hwp * 4 + (size_t)M * ntile * 12 + (planes ? (size_t)LW * hw * 4 * (in->erode_iters > 1 ? 2 : 1) : 0) +
                              (host_masks ? (size_t)M * (hw * esz + 16) : 0) + (host_pts ? (size_t)maxN * 16 : 0);
-    const int Fc = (int)std::max<size_t>(1, std::min<size_t>((size_t)F, LPF_DM_BUDGET / per_frame));
+    const std::vector<Span> chunks = plan_ranges((size_t)F, (size_t)F, [&](size_t, size_t n) { return n * per_frame; });
+    const size_t Fc = chunks[0].count;
+    const size_t most_pts = largest(chunks, [&](size_t f0, size_t n) { return frame_off[f0 + n] - frame_off[f0]; });
 
     // ---- buffers, reserved for the largest chunk ------------------------------------------------------------------------------------
     if ((rc = reserve(c, D.foff, (size_t)(F + 1) * 8))) return rc;
-    if ((rc = reserve(c, D.win, (size_t)Fc * hwp * 4))) return rc;
-    if (M > 0 && (rc = reserve(c, D.cnt, (size_t)Fc * M * (2 * ntile + 1) * 4))) return rc;
-    if (host_masks) {
-        if ((rc = reserve(c, D.masks, (size_t)Fc * M * hw * esz))) return rc;
-        if (in->rects && (rc = reserve(c, D.rects, (size_t)Fc * M * 16))) return rc;
-    }
-    if (host_pts) {
-        long long most = 0;                                   // points of the largest chunk
-        for (int f0 = 0; f0 < F; f0 += Fc) most = std::max(most, (long long)(frame_off[std::min(F, f0 + Fc)] - frame_off[f0]));
-        if ((rc = reserve(c, D.pts, (size_t)most * 16))) return rc;
-    }
+    if ((rc = reserve(c, D.win, Fc * hwp * 4))) return rc;
+    if (M > 0 && (rc = reserve(c, D.cnt, Fc * M * (2 * ntile + 1) * 4))) return rc;
+    if (host_pts && (rc = reserve(c, D.pts, most_pts * 16))) return rc;      // (here, not by the first chunk with points: no chunk waits)
+    const void *masks_k = nullptr;                            // a chunk's staged masks and rectangles, or the caller's
+    const int32_t *rects_k = nullptr;
+    Stage I(host_masks);
+    I.add(masks_k, M > 0 ? in->masks : nullptr, (size_t)M * hw * esz, Fc);
+    I.add(rects_k, M > 0 ? in->rects : nullptr, (size_t)M * 16, Fc);
+    if ((rc = I.commit(c, D.in))) return rc;
     const size_t cap = (size_t)out->cap, nF = (size_t)F;
     if ((rc = upload(c, D.foff.p, frame_off, (size_t)(F + 1) * 8))) return rc;
 
@@ -2445,43 +2514,33 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     P.foff = (const long long *)D.foff.p;
     P.win = (unsigned *)D.win.p;
     P.cnt = (unsigned *)D.cnt.p;
-    P.toff = P.cnt + (size_t)Fc * M * ntile;
-    P.tot = P.toff + (size_t)Fc * M * ntile;
+    P.toff = P.cnt + Fc * M * ntile;
+    P.tot = P.toff + Fc * M * ntile;
     // the whole batch's outputs (a host caller's lists only with room in them: cap > 0)
     const bool lists = cap > 0 || !host_io;
-    OutStage S;
-    S.add(P.pix, lists ? out->pix : nullptr, nF * cap * 8);
-    S.add(P.depth, lists ? out->depth : nullptr, nF * cap * 8);
-    S.add(P.pidx, lists ? out->point_idx : nullptr, nF * cap * 8);
-    S.add(P.car_off, out->car_off, nF * (M + 1) * 8);
-    S.add(P.need, out->need, nF * 8);
-    S.add(P.overflow, out->overflow, nF * 4);
-    if ((rc = S.commit(c, D.out, host_io))) return rc;
+    Stage S(host_io);
+    S.add(P.pix, lists ? out->pix : nullptr, 8, nF * cap);
+    S.add(P.depth, lists ? out->depth : nullptr, 8, nF * cap);
+    S.add(P.pidx, lists ? out->point_idx : nullptr, 8, nF * cap);
+    S.add(P.car_off, out->car_off, 8, nF * (M + 1));
+    S.add(P.need, out->need, 8, nF);
+    S.add(P.overflow, out->overflow, 4, nF);
+    if ((rc = S.commit(c, D.out))) return rc;
 
     // ---- the chunks ---------------------------------------------------------------------------------------------------------
-    for (int f0 = 0; f0 < F; f0 += Fc) {
-        const int fc = std::min(Fc, F - f0);
+    bool pts_in = false;
+    for (const Span &ch : chunks) {
+        const int f0 = (int)ch.first, fc = (int)ch.count;
         const long long a = frame_off[f0], nc = frame_off[f0 + fc] - a;
         long long mc = 0;
         for (int f = f0; f < f0 + fc; ++f) mc = std::max(mc, (long long)(frame_off[f + 1] - frame_off[f]));
         P.f0 = f0; P.pt_base = a;
-        if (host_pts && nc > 0) {
-            LPF_HIP(c, hipMemcpyAsync(D.pts.p, pts + 4 * a, (size_t)nc * 16, hipMemcpyHostToDevice, c->stream));
-            P.cam.pts = (const float4 *)D.pts.p;
-        } else {
-            P.cam.pts = nc > 0 ? (const float4 *)(pts + 4 * a) : nullptr;
-        }
+        if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, (size_t)a, (size_t)nc, most_pts, &P.cam.pts, &pts_in))) return rc;
+        if (nc == 0) P.cam.pts = nullptr;
         if (M > 0) {
-            const void *dm = (const char *)in->masks + (size_t)f0 * M * hw * esz;
-            const int32_t *dr = in->rects ? in->rects + (size_t)f0 * M * 4 : nullptr;
-            if (host_masks) {
-                LPF_HIP(c, hipMemcpyAsync(D.masks.p, dm, (size_t)fc * M * hw * esz, hipMemcpyHostToDevice, c->stream));
-                dm = D.masks.p;
-                if (dr) {
-                    LPF_HIP(c, hipMemcpyAsync(D.rects.p, dr, (size_t)fc * M * 16, hipMemcpyHostToDevice, c->stream));
-                    dr = (const int32_t *)D.rects.p;
-                }
-            }
+            if ((rc = I.in(c, {{ch.first, ch.count}, {ch.first, ch.count}}))) return rc;             // masks | rects
+            const void *dm = host_masks ? masks_k : (const char *)masks_k + ch.first * M * hw * esz;
+            const int32_t *dr = host_masks || !rects_k ? rects_k : rects_k + ch.first * M * 4;
             P.masks = dm;
             P.rects = use_rects ? (const int4 *)dr : nullptr;
             if (planes) {                                   // erosion: lpf_run_wide's pack + erode into LW planes per frame
@@ -2514,17 +2573,14 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     }
 
     if (host_io && (rc = S.back(c))) return rc;
-    if (host_io || host_masks || host_pts) LPF_HIP(c, host_wait(c));   // host buffers may be reused
+    if (host_io || host_masks || pts_in) LPF_HIP(c, host_wait(c));   // host buffers may be reused
     return LPF_OK;
 }
 
 // ---- lpf_depth_overlays (include/lpf.h): per-car overlay images, kernels in lpf_depth_overlays.hip.h -----------------------------
-// The F * M (frame, car) images go through in chunks of consecutive images: a chunk's scratch -- the segmented images and lists of
-// the frames it touches when they are in host memory, its images when the outputs are -- stays within LPF_DO_BUDGET, or one image
-// when a single image needs more.  The chunks are planned and every buffer reserved before the first launch, so no chunk waits for
-// the one before it.
-#define LPF_DO_BUDGET (256ull << 20)
-#define LPF_DO_MAX_IMAGES 65535ll           // images per chunk: the render's grid.y
+// The F * M (frame, car) images go through in chunks of consecutive images (plan_ranges): a chunk stages the segmented images and lists
+// of the frames it touches when they are in host memory, its images when the outputs are.
+#define LPF_DO_MAX_IMAGES 65535             // images per chunk: the render's grid.y
 
 // host lists: offsets non-decreasing within [0, cap], pixels strictly ascending within each car and inside the image, depths finite
 // and > 0 (the device lists are clamped by the kernels instead)
@@ -2555,10 +2611,8 @@ static int check_overlay_lists(lpf_ctx *c, int F, const lpf_depth_overlay_input 
 
 int lpf_depth_overlays(lpf_ctx *c, int F, const lpf_depth_overlay_input *in, const lpf_depth_overlay_outputs *out)
 {
-    if (!c) return LPF_ERR_ARG;
-    if (use_device(c)) return LPF_ERR_HIP;
-    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_depth_overlays cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
-    if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera has not been called");
+    int rc;
+    if ((rc = enter(c, "lpf_depth_overlays", true))) return rc;
     if (!in || !out || F < 0) return fail(c, LPF_ERR_ARG, "depth_overlays: in=%p out=%p F=%d", (const void *)in, (const void *)out, F);
     const int M = in->M;
     if (M < 0 || M > LPF_MAX_MASKS_WIDE)
@@ -2568,7 +2622,6 @@ int lpf_depth_overlays(lpf_ctx *c, int F, const lpf_depth_overlay_input *in, con
                     (long long)in->cap, (const void *)in->pix, (const void *)in->depth, (const void *)in->car_off, (const void *)in->seg);
     if (M > 0 && !out->images && !out->max_depth) return fail(c, LPF_ERR_ARG, "depth_overlays: images and max_depth are both NULL");
     const long long hw = (long long)c->W * c->H, cap = in->cap;
-    int rc;
     if (!in->lists_on_device && F > 0 && (rc = check_overlay_lists(c, F, in, hw))) return rc;
     if (F == 0 || M == 0) return LPF_OK;
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
@@ -2576,62 +2629,42 @@ int lpf_depth_overlays(lpf_ctx *c, int F, const lpf_depth_overlay_input *in, con
 
     lpf_ctx::DepthOverlays &D = c->dovl;
     const size_t img_b = (size_t)hw * 3, total = (size_t)F * M;
-    const bool host_seg = !in->seg_on_device, host_lists = !in->lists_on_device;
-    const bool want_img = out->images != nullptr, host_img = want_img && !out->on_device, host_mx = out->max_depth && !out->on_device;
+    const bool host_seg = !in->seg_on_device, host_lists = !in->lists_on_device, host_out = !out->on_device;
+    const bool want_img = out->images != nullptr, host_img = want_img && host_out, host_mx = out->max_depth && host_out;
     const size_t pix_b = (size_t)cap * 8, off_b = (size_t)(M + 1) * 8;
-    auto a256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t per_image = host_img ? img_b : 0;
     const size_t per_frame = (host_seg ? img_b : 0) + (host_lists ? 2 * pix_b + off_b : 0);
 
-    // ---- the chunks: [i0, i0 + n) of the F * M images, planned first ----------------------------------------------------------
-    std::vector<std::pair<size_t, size_t>> chunks;
-    size_t most_img = 0, most_fr = 0;
-    for (size_t i0 = 0; i0 < total;) {
-        size_t n = 1;
-        auto cost = [&](size_t k) { return k * per_image + ((i0 + k - 1) / M - i0 / M + 1) * per_frame; };
-        while (i0 + n < total && n < (size_t)LPF_DO_MAX_IMAGES && cost(n + 1) <= LPF_DO_BUDGET) ++n;
-        chunks.emplace_back(i0, n);
-        most_img = std::max(most_img, n);
-        most_fr = std::max(most_fr, (i0 + n - 1) / M - i0 / M + 1);
-        i0 += n;
-    }
-    const size_t o_dep = a256(most_fr * pix_b), o_off = o_dep + a256(most_fr * pix_b);
-    if (host_seg && (rc = reserve(c, D.seg, most_fr * img_b))) return rc;
-    if (host_lists && (rc = reserve(c, D.lists, o_off + most_fr * off_b))) return rc;
-    if (host_img && (rc = reserve(c, D.img, most_img * img_b))) return rc;
-    if (host_mx && (rc = reserve(c, D.mx, total * 8))) return rc;
+    // ---- the chunks: [i0, i0 + n) of the F * M images, of frames [fa, fa + nf) ----------------------------------------------------
+    auto frames_of = [&](size_t i0, size_t n) { return (i0 + n - 1) / M - i0 / M + 1; };
+    const std::vector<Span> chunks = plan_ranges(total, LPF_DO_MAX_IMAGES, [&](size_t i0, size_t n) { return n * per_image + frames_of(i0, n) * per_frame; });
+    const size_t most_img = largest(chunks, [](size_t, size_t n) { return n; }), most_fr = largest(chunks, frames_of);
 
     LpfDoParams Q;
     memset(&Q, 0, sizeof Q);
     Q.hw = hw; Q.M = M; Q.cap = cap;
-    Q.mx = host_mx ? (double *)D.mx.p : out->max_depth;
-    const unsigned char *seg_k = host_seg ? (const unsigned char *)D.seg.p : in->seg;
-    unsigned char *img_k = host_img ? (unsigned char *)D.img.p : out->images;
+    Stage I(host_seg);                                        // per frame: the segmented image; pixels, depths and offsets of the lists
+    I.add(Q.seg, in->seg, img_b, most_fr);
+    I.host = host_lists;
+    I.add(Q.pix, in->pix, pix_b, most_fr);
+    I.add(Q.depth, in->depth, pix_b, most_fr);
+    I.add(Q.car_off, in->car_off, off_b, most_fr);
+    if ((rc = I.commit(c, D.in))) return rc;
+    unsigned char *img_k = nullptr;
+    Stage O(host_out);                                        // a chunk's images; the batch's max_depth
+    O.add(img_k, out->images, img_b, most_img);
+    O.add(Q.mx, out->max_depth, 8, total);
+    if ((rc = O.commit(c, D.out))) return rc;
     // pixels per render thread: 16 (three dwordx4) or 4 (three dwords) when that divides W * H and the bases allow it, else 1
-    auto fits = [&](uintptr_t al) { return hw % (long long)al == 0 && ((uintptr_t)seg_k % al) == 0 && ((uintptr_t)img_k % al) == 0; };
+    auto fits = [&](uintptr_t al) { return hw % (long long)al == 0 && ((uintptr_t)Q.seg % al) == 0 && ((uintptr_t)img_k % al) == 0; };
     const int P = fits(16) ? 16 : fits(4) ? 4 : 1;
     const unsigned gx = (unsigned)(((hw + P - 1) / P + LPF_BLOCK - 1) / LPF_BLOCK);
-    for (const auto &ch : chunks) {
-        const size_t i0 = ch.first, n = ch.second, fa = i0 / M, nf = (i0 + n - 1) / M - fa + 1;
+    for (const Span &ch : chunks) {
+        const size_t i0 = ch.first, n = ch.count, fa = i0 / M, nf = frames_of(i0, n);
         Q.i0 = (long long)i0; Q.n = (long long)n;
-        if (host_seg) {
-            LPF_HIP(c, hipMemcpyAsync(D.seg.p, in->seg + fa * img_b, nf * img_b, hipMemcpyHostToDevice, c->stream));
-            Q.seg = (const unsigned char *)D.seg.p; Q.seg_f0 = (long long)fa;
-        } else {
-            Q.seg = in->seg; Q.seg_f0 = 0;
-        }
-        if (host_lists) {
-            char *L = (char *)D.lists.p;
-            if (cap > 0) {
-                LPF_HIP(c, hipMemcpyAsync(L, in->pix + fa * cap, nf * pix_b, hipMemcpyHostToDevice, c->stream));
-                LPF_HIP(c, hipMemcpyAsync(L + o_dep, in->depth + fa * cap, nf * pix_b, hipMemcpyHostToDevice, c->stream));
-            }
-            LPF_HIP(c, hipMemcpyAsync(L + o_off, in->car_off + fa * (M + 1), nf * off_b, hipMemcpyHostToDevice, c->stream));
-            Q.pix = (const long long *)L; Q.depth = (const double *)(L + o_dep); Q.car_off = (const long long *)(L + o_off);
-            Q.list_f0 = (long long)fa;
-        } else {
-            Q.pix = (const long long *)in->pix; Q.depth = in->depth; Q.car_off = (const long long *)in->car_off; Q.list_f0 = 0;
-        }
+        if ((rc = I.in(c, {{fa, nf}, {fa, nf}, {fa, nf}, {fa, nf}}))) return rc;                     // seg | pix | depth | car_off
+        Q.seg_f0 = host_seg ? (long long)fa : 0;              // the staged arrays begin at the chunk's first frame
+        Q.list_f0 = host_lists ? (long long)fa : 0;
         Q.img = want_img ? (host_img ? img_k : img_k + i0 * img_b) : nullptr;
         if (want_img) {
             const dim3 g(gx, (unsigned)n);
@@ -2642,27 +2675,23 @@ int lpf_depth_overlays(lpf_ctx *c, int F, const lpf_depth_overlay_input *in, con
         }
         hipLaunchKernelGGL(lpf_do_paint, dim3((unsigned)((n + 3) / 4)), dim3(LPF_BLOCK), 0, c->stream, Q);
         LPF_HIP(c, hipGetLastError());
-        if (host_img) LPF_HIP(c, hipMemcpyAsync(out->images + i0 * img_b, D.img.p, n * img_b, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = O.back(c, {{i0, n}, {0, 0}}))) return rc;                                       // images | max_depth
     }
-    if (host_mx) LPF_HIP(c, hipMemcpyAsync(out->max_depth, D.mx.p, total * 8, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = O.back(c, {{0, 0}, {0, total}}))) return rc;                                        // images | max_depth
     if (host_img || host_mx || host_seg || host_lists) LPF_HIP(c, host_wait(c));    // host buffers filled, or free to be reused
     return LPF_OK;
 }
 
 // ---- lpf_match_2d (include/lpf.h): V4 / V5 pair scoring of a batch, kernel in lpf_match2d.hip.h ---------------------------------------
-// With every array in device memory the whole batch is one launch on the caller's arrays.  Host arrays go through in ranges of
-// consecutive frames: a range's scratch -- its staged detections, rectangles and front counts when the inputs are in host memory, its
-// best_box / best_iou rows and matrices when the outputs are -- stays within LPF_M2_BUDGET, or one frame when a single frame needs
-// more.  The ranges are planned and every buffer reserved before the first launch, so no range waits for the one before it.
-#define LPF_M2_BUDGET (256ull << 20)
+// With every array in device memory the whole batch is one launch per 65535 frames on the caller's arrays.  Host arrays go through in
+// ranges of consecutive frames (plan_ranges): a range stages its detections, rectangles and front counts when the inputs are in host
+// memory, its best_box / best_iou rows and matrices when the outputs are.
 #define LPF_M2_MAX_FRAMES 65535             // frames per launch: the grid's y
-#define LPF_M2_TAB_PIECE 32768              // frames per upload of the frame table: under a quarter of the pinned ring, so it never waits
 
 int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match2d_outputs *out)
 {
-    if (!c) return LPF_ERR_ARG;
-    if (use_device(c)) return LPF_ERR_HIP;
-    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_match_2d cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
+    int rc;
+    if ((rc = enter(c, "lpf_match_2d", false))) return rc;
     if (!in || !out || F < 0) return fail(c, LPF_ERR_ARG, "match_2d: in=%p out=%p F=%d", (const void *)in, (const void *)out, F);
     if (!in->det_off || !in->box_off)
         return fail(c, LPF_ERR_ARG, "match_2d: det_off=%p box_off=%p (both are required, F + 1 entries each)", (const void *)in->det_off, (const void *)in->box_off);
@@ -2683,17 +2712,16 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
     for (double *m : mats_out) nmat += m != nullptr;
     const bool want_best = out->best_box || out->best_iou;
     if (F == 0 || in->det_off[F] == in->det_off[0] || (!want_best && !nmat)) return LPF_OK;
-    int rc;
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
 
     lpf_ctx::Match2d &D = c->m2d;
     const bool host_in = !in->on_device, host_out = !out->on_device;
     const size_t esz = in->dets_f64 ? 8 : 4;
-    auto a256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
 
-    // ---- the frame table and the ranges [fa, fb), planned first ------------------------------------------------------------------
-    std::vector<LpfM2Frame> tab((size_t)F);
+    // ---- the frame table and the ranges of frames; cost[f]: the bytes staged for the frames before f ---------------------------------
+    std::vector<LpfM2Frame> tab((size_t)F + 1);               // (one past the end: where the pairs end)
+    std::vector<size_t> cost((size_t)F + 1, 0);
     long long p = 0;
     for (int f = 0; f < F; ++f) {
         LpfM2Frame &t = tab[(size_t)f];
@@ -2701,78 +2729,46 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
         t.b0 = in->box_off[f]; t.B = in->box_off[f + 1] - t.b0;
         t.p0 = p;
         p += (long long)t.D * t.B;
+        cost[(size_t)f + 1] = cost[(size_t)f] + (host_in ? (size_t)t.D * 4 * esz + (size_t)t.B * 36 : 0) +
+                              (host_out ? (size_t)t.D * 12 + (size_t)nmat * 8 * (size_t)t.D * (size_t)t.B : 0);
     }
-    auto frame_cost = [&](const LpfM2Frame &t) {
-        size_t b = 0;
-        if (host_in) b += (size_t)t.D * 4 * esz + (size_t)t.B * 36;
-        if (host_out) b += (size_t)t.D * 12 + (size_t)nmat * 8 * (size_t)t.D * (size_t)t.B;
-        return b;
-    };
-    struct Range { int fa, fb; };
-    std::vector<Range> ranges;
-    size_t most_d = 0, most_b = 0, most_p = 0;
-    for (int fa = 0; fa < F;) {
-        int fb = fa + 1;
-        size_t cost = frame_cost(tab[(size_t)fa]);
-        if (host_in || host_out)
-            while (fb < F && fb - fa < LPF_M2_MAX_FRAMES && cost + frame_cost(tab[(size_t)fb]) <= LPF_M2_BUDGET) cost += frame_cost(tab[(size_t)fb++]);
-        else
-            fb = std::min(F, fa + LPF_M2_MAX_FRAMES);
-        ranges.push_back({fa, fb});
-        most_d = std::max(most_d, (size_t)(in->det_off[fb] - in->det_off[fa]));
-        most_b = std::max(most_b, (size_t)(in->box_off[fb] - in->box_off[fa]));
-        most_p = std::max(most_p, (size_t)((fb < F ? tab[(size_t)fb].p0 : p) - tab[(size_t)fa].p0));
-        fa = fb;
-    }
-    const size_t i_box = a256(most_d * 4 * esz), i_front = i_box + a256(most_b * 32);       // staged inputs: dets | bbox2d | front
-    const size_t o_iou = a256(most_d * 4), o_mat = o_iou + a256(most_d * 8);                 // staged outputs: best_box | best_iou | matrices
-    if ((rc = reserve(c, D.tab, (size_t)F * sizeof(LpfM2Frame)))) return rc;
-    if (host_in && (rc = reserve(c, D.in, i_front + most_b * 4))) return rc;
-    if (host_out && (rc = reserve(c, D.out, o_mat + (size_t)nmat * a256(most_p * 8)))) return rc;
-    for (int f = 0; f < F; f += LPF_M2_TAB_PIECE) {
-        const size_t n = (size_t)std::min(F - f, LPF_M2_TAB_PIECE);
-        if ((rc = upload(c, (LpfM2Frame *)D.tab.p + f, tab.data() + f, n * sizeof(LpfM2Frame)))) return rc;
-    }
+    tab[(size_t)F].p0 = p;
+    const std::vector<Span> ranges = plan_ranges((size_t)F, LPF_M2_MAX_FRAMES, [&](size_t f, size_t n) { return cost[f + n] - cost[f]; });
+    const size_t most_d = largest(ranges, [&](size_t f, size_t n) { return in->det_off[f + n] - in->det_off[f]; });
+    const size_t most_b = largest(ranges, [&](size_t f, size_t n) { return in->box_off[f + n] - in->box_off[f]; });
+    const size_t most_p = largest(ranges, [&](size_t f, size_t n) { return tab[f + n].p0 - tab[f].p0; });
+    if ((rc = upload_table(c, D.tab, tab.data(), (size_t)F))) return rc;
 
     LpfM2Params Q;
     memset(&Q, 0, sizeof Q);
     Q.min_iou = in->min_iou; Q.w_iou = in->w_iou; Q.w_center = in->w_center; Q.w_size = in->w_size;
+    Stage I(host_in), O(host_out);
+    I.add(Q.dets, in->dets, 4 * esz, most_d);
+    I.add(Q.bbox2d, in->bbox2d, 32, most_b);
+    I.add(Q.front, in->front, 4, most_b);
+    if ((rc = I.commit(c, D.in))) return rc;
+    O.add(Q.best_box, out->best_box, 4, most_d);
+    O.add(Q.best_iou, out->best_iou, 8, most_d);
+    O.add(Q.iou, out->iou, 8, most_p);
+    O.add(Q.center, out->center_score, 8, most_p);
+    O.add(Q.size, out->size_score, 8, most_p);
+    O.add(Q.total, out->total_score, 8, most_p);
+    O.add(Q.cost, out->cost, 8, most_p);
+    if ((rc = O.commit(c, D.out))) return rc;
     const bool scores = out->center_score || out->size_score || out->total_score || out->cost;
-    for (const Range &r : ranges) {
-        const int fa = r.fa, fb = r.fb, d0 = in->det_off[fa], nd = in->det_off[fb] - d0, b0 = in->box_off[fa], nb = in->box_off[fb] - b0;
-        const long long p0 = tab[(size_t)fa].p0, np = (fb < F ? tab[(size_t)fb].p0 : p) - p0;
+    for (const Span &r : ranges) {
+        const size_t fa = r.first, fb = fa + r.count;
+        const size_t d0 = (size_t)in->det_off[fa], nd = (size_t)in->det_off[fb] - d0, b0 = (size_t)in->box_off[fa], nb = (size_t)in->box_off[fb] - b0;
+        const size_t p0 = (size_t)tab[fa].p0, np = (size_t)tab[fb].p0 - p0;
         int most_rows = 0;
-        for (int f = fa; f < fb; ++f) most_rows = std::max(most_rows, tab[(size_t)f].D);
+        for (size_t f = fa; f < fb; ++f) most_rows = std::max(most_rows, tab[f].D);
         if (most_rows == 0) continue;                       // no detections in the range: nothing to write
         Q.frames = (const LpfM2Frame *)D.tab.p + fa;
-        if (host_in) {
-            char *S = (char *)D.in.p;
-            LPF_HIP(c, hipMemcpyAsync(S, (const char *)in->dets + (size_t)d0 * 4 * esz, (size_t)nd * 4 * esz, hipMemcpyHostToDevice, c->stream));
-            if (nb > 0) {
-                LPF_HIP(c, hipMemcpyAsync(S + i_box, in->bbox2d + (size_t)b0 * 4, (size_t)nb * 32, hipMemcpyHostToDevice, c->stream));
-                LPF_HIP(c, hipMemcpyAsync(S + i_front, in->front + b0, (size_t)nb * 4, hipMemcpyHostToDevice, c->stream));
-            }
-            Q.dets = S; Q.bbox2d = (const double *)(S + i_box); Q.front = (const int *)(S + i_front);
-            Q.det_base = d0; Q.box_base = b0;
-        } else {
-            Q.dets = in->dets; Q.bbox2d = in->bbox2d; Q.front = in->front;
-            Q.det_base = 0; Q.box_base = 0;
-        }
-        double *mats_k[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (host_out) {
-            char *S = (char *)D.out.p;
-            Q.best_box = out->best_box ? (int *)S : nullptr;
-            Q.best_iou = out->best_iou ? (double *)(S + o_iou) : nullptr;
-            for (int m = 0, k = 0; m < 5; ++m)
-                if (mats_out[m]) mats_k[m] = (double *)(S + o_mat + (size_t)k++ * a256(most_p * 8));
-            Q.det_out_base = d0; Q.pair_base = p0;
-        } else {
-            Q.best_box = out->best_box; Q.best_iou = out->best_iou;
-            for (int m = 0; m < 5; ++m) mats_k[m] = mats_out[m];
-            Q.det_out_base = 0; Q.pair_base = 0;
-        }
-        Q.iou = mats_k[0]; Q.center = mats_k[1]; Q.size = mats_k[2]; Q.total = mats_k[3]; Q.cost = mats_k[4];
-        const dim3 g((unsigned)((most_rows + LPF_M2_ROWS - 1) / LPF_M2_ROWS), (unsigned)(fb - fa));
+        if ((rc = I.in(c, {{d0, nd}, {b0, nb}, {b0, nb}}))) return rc;                               // dets | bbox2d | front
+        // staged arrays begin at the range's first detection, box and pair; the caller's own at the batch's
+        Q.det_base = host_in ? (int)d0 : 0; Q.box_base = host_in ? (int)b0 : 0;
+        Q.det_out_base = host_out ? (int)d0 : 0; Q.pair_base = host_out ? (long long)p0 : 0;
+        const dim3 g((unsigned)((most_rows + LPF_M2_ROWS - 1) / LPF_M2_ROWS), (unsigned)r.count);
         if (in->dets_f64) {
             if (scores) hipLaunchKernelGGL((lpf_m2_pairs<double, true>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
             else hipLaunchKernelGGL((lpf_m2_pairs<double, false>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
@@ -2781,12 +2777,8 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
             else hipLaunchKernelGGL((lpf_m2_pairs<float, false>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
         }
         LPF_HIP(c, hipGetLastError());
-        if (host_out) {
-            if (out->best_box) LPF_HIP(c, hipMemcpyAsync(out->best_box + d0, Q.best_box, (size_t)nd * 4, hipMemcpyDeviceToHost, c->stream));
-            if (out->best_iou) LPF_HIP(c, hipMemcpyAsync(out->best_iou + d0, Q.best_iou, (size_t)nd * 8, hipMemcpyDeviceToHost, c->stream));
-            for (int m = 0; m < 5; ++m)
-                if (mats_out[m] && np > 0) LPF_HIP(c, hipMemcpyAsync(mats_out[m] + p0, mats_k[m], (size_t)np * 8, hipMemcpyDeviceToHost, c->stream));
-        }
+        // best_box | best_iou | iou | center | size | total | cost
+        if ((rc = O.back(c, {{d0, nd}, {d0, nd}, {p0, np}, {p0, np}, {p0, np}, {p0, np}, {p0, np}}))) return rc;
     }
     if (host_in || host_out) LPF_HIP(c, host_wait(c));       // host outputs filled, host inputs free to be reused
     return LPF_OK;
@@ -2797,14 +2789,12 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
 // buffer, the five outputs in another; of the staged [F][inst_cap] outputs only what the kernel wrote -- the first inst_off[f][M] entries
 // of a frame whose lists fitted -- goes back to the caller, so the rest of the caller's rows stays as it was.
 #define LPF_IN_MAX_FRAMES 65535             // frames per launch: the grid's y
-#define LPF_IN_TAB_PIECE 32768              // frames per upload of the frame table: under a quarter of the pinned ring, so it never waits
 
 int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_inside_input *in,
                      const lpf_inside_outputs *out)
 {
-    if (!c) return LPF_ERR_ARG;
-    if (use_device(c)) return LPF_ERR_HIP;
-    if (c->capturing) return fail(c, LPF_ERR_STATE, "lpf_inside_masks cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)");
+    int rc;
+    if ((rc = enter(c, "lpf_inside_masks", false))) return rc;
     if (!in || !out || F < 0 || !frame_off)
         return fail(c, LPF_ERR_ARG, "inside_masks: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
     const int M = in->M;
@@ -2817,7 +2807,6 @@ int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
     if (!in->inst_off || (M > 0 && (!in->best_box || !in->best_cnt || (cap > 0 && !in->inst_idx))))
         return fail(c, LPF_ERR_ARG, "inside_masks: inst_idx=%p inst_off=%p best_box=%p best_cnt=%p (inst_off is required, best_box and best_cnt with M > 0, inst_idx with inst_cap > 0)",
                     (const void *)in->inst_idx, (const void *)in->inst_off, (const void *)in->best_box, (const void *)in->best_cnt);
-    int rc;
     if ((rc = check_frames(c, "inside_masks", pts, frame_off, F, 0))) return rc;
     lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
     if (BX.F == 0) return fail(c, LPF_ERR_STATE, "inside_masks: no boxes in force (lpf_set_boxes* comes first)");
@@ -2844,7 +2833,6 @@ int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
     if ((rc = flush_pending(c))) return rc;
 
     lpf_ctx::Inside &D = c->insd;
-    auto a256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t fc = (size_t)F * (size_t)cap, fm = (size_t)F * M, Ntot = (size_t)frame_off[F];
     // the offsets on the host: the copies back to a host caller are sized by them
     std::vector<int64_t> fetched;
@@ -2863,50 +2851,27 @@ int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
         t.pt_off = (long long)frame_off[f]; t.N = (int)(frame_off[f + 1] - frame_off[f]);
         t.box_off = BX.box_off[f]; t.B = BX.box_off[f + 1] - BX.box_off[f]; t.pad = 0;
     }
-    const size_t i_off = a256(fc * 8), i_cnt = i_off + a256((size_t)F * M1 * 8), i_box = i_cnt + a256(fm * 8);       // idx | off | best_cnt | best_box
-    const size_t o_idx = a256(fc), o_xyz = o_idx + a256(fc * 8), o_n = o_xyz + a256(fc * 12), o_mt = o_n + a256(fm * 8);   // inside | part_idx | part_xyz | n_inside | matched
-    if ((rc = reserve(c, D.tab, (size_t)F * sizeof(LpfInFrame)))) return rc;
-    if (!pts_on_device && Ntot && (rc = reserve(c, D.pts, Ntot * 16))) return rc;
-    if (host_in && (rc = reserve(c, D.in, i_box + fm * 4))) return rc;
-    if (host_out && (rc = reserve(c, D.out, o_mt + fm * 4))) return rc;
-    for (int f = 0; f < F; f += LPF_IN_TAB_PIECE) {
-        const size_t n = (size_t)std::min(F - f, LPF_IN_TAB_PIECE);
-        if ((rc = upload(c, (LpfInFrame *)D.tab.p + f, tab.data() + f, n * sizeof(LpfInFrame)))) return rc;
-    }
+    if ((rc = upload_table(c, D.tab, tab.data(), (size_t)F))) return rc;
 
     LpfInParams Q;
     memset(&Q, 0, sizeof Q);
     Q.frames = (const LpfInFrame *)D.tab.p;
-    Q.pts = (const float4 *)pts;
-    if (!pts_on_device && Ntot) {
-        LPF_HIP(c, hipMemcpyAsync(D.pts.p, pts, Ntot * 16, hipMemcpyHostToDevice, c->stream));
-        Q.pts = (const float4 *)D.pts.p;
-    }
-    if (host_in) {
-        char *S = (char *)D.in.p;
-        if (fc) LPF_HIP(c, hipMemcpyAsync(S, in->inst_idx, fc * 8, hipMemcpyHostToDevice, c->stream));
-        LPF_HIP(c, hipMemcpyAsync(S + i_off, in->inst_off, (size_t)F * M1 * 8, hipMemcpyHostToDevice, c->stream));
-        LPF_HIP(c, hipMemcpyAsync(S + i_cnt, in->best_cnt, fm * 8, hipMemcpyHostToDevice, c->stream));
-        LPF_HIP(c, hipMemcpyAsync(S + i_box, in->best_box, fm * 4, hipMemcpyHostToDevice, c->stream));
-        Q.inst_idx = (const long long *)S; Q.inst_off = (const long long *)(S + i_off);
-        Q.best_cnt = (const long long *)(S + i_cnt); Q.best_box = (const int *)(S + i_box);
-    } else {
-        Q.inst_idx = (const long long *)in->inst_idx; Q.inst_off = (const long long *)in->inst_off;
-        Q.best_cnt = (const long long *)in->best_cnt; Q.best_box = in->best_box;
-    }
     Q.inst_cap = cap; Q.M = M; Q.min_points = in->min_points;
     Q.boxp = (const double *)BX.boxp.p;
-    if (host_out) {
-        char *S = (char *)D.out.p;
-        Q.inside = out->inside ? (unsigned char *)S : nullptr;
-        Q.part_idx = out->part_idx ? (long long *)(S + o_idx) : nullptr;
-        Q.part_xyz = out->part_xyz ? (float *)(S + o_xyz) : nullptr;
-        Q.n_inside = out->n_inside ? (long long *)(S + o_n) : nullptr;
-        Q.matched = out->matched ? (int *)(S + o_mt) : nullptr;
-    } else {
-        Q.inside = out->inside; Q.part_idx = (long long *)out->part_idx; Q.part_xyz = out->part_xyz;
-        Q.n_inside = (long long *)out->n_inside; Q.matched = out->matched;
-    }
+    bool pts_in = false;
+    if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, 0, Ntot, Ntot, &Q.pts, &pts_in))) return rc;
+    Stage I(host_in), O(host_out);
+    I.add(Q.inst_idx, in->inst_idx, 8, fc);
+    I.add(Q.inst_off, in->inst_off, 8, (size_t)F * M1);
+    I.add(Q.best_cnt, in->best_cnt, 8, fm);
+    I.add(Q.best_box, in->best_box, 4, fm);
+    if ((rc = I.commit(c, D.in)) || (rc = I.in(c))) return rc;
+    O.add(Q.inside, out->inside, 1, fc);
+    O.add(Q.part_idx, out->part_idx, 8, fc);
+    O.add(Q.part_xyz, out->part_xyz, 12, fc);
+    O.add(Q.n_inside, out->n_inside, 8, fm);
+    O.add(Q.matched, out->matched, 4, fm);
+    if ((rc = O.commit(c, D.out))) return rc;
     if (Q.inside || Q.part_idx || Q.part_xyz || Q.n_inside || Q.matched) {
         for (int f0 = 0; f0 < F; f0 += LPF_IN_MAX_FRAMES) {
             Q.f0 = f0;
@@ -2918,8 +2883,8 @@ int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
         }
     }
     if (host_out) {
-        if (Q.n_inside) LPF_HIP(c, hipMemcpyAsync(out->n_inside, Q.n_inside, fm * 8, hipMemcpyDeviceToHost, c->stream));
-        if (Q.matched) LPF_HIP(c, hipMemcpyAsync(out->matched, Q.matched, fm * 4, hipMemcpyDeviceToHost, c->stream));
+        // the summaries whole; of the staged [F][inst_cap] rows only what the kernel wrote
+        if ((rc = O.back(c, {{0, 0}, {0, 0}, {0, 0}, {0, fm}, {0, fm}}))) return rc;             // inside | part_idx | part_xyz | n_inside | matched
         for (int f = 0; lists_back && f < F; ++f) {
             const int64_t *off = off_h + (size_t)f * M1;
             const long long n = off[M];
@@ -2930,22 +2895,22 @@ int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
             if (Q.part_xyz) LPF_HIP(c, hipMemcpyAsync(out->part_xyz + r * 3, Q.part_xyz + r * 3, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
         }
     }
-    if (host_out || host_in || (!pts_on_device && Ntot)) LPF_HIP(c, host_wait(c));    // host outputs filled, host inputs free to be reused
+    if (host_out || host_in || pts_in) LPF_HIP(c, host_wait(c));    // host outputs filled, host inputs free to be reused
     return LPF_OK;
 }
 
 // ---- lpf_run_cams (include/lpf.h): one scan in up to LPF_MAX_CAMS cameras, kernels in lpf_cams.hip.h ------------------------------
 // The checks lpf_run_cams and lpf_run_cams_wide share (who: the call's name; frames of up to 0x7fffffff - slack points; 0 .. max_M masks
-// per camera, takes / more: what the message says about the limit, check_wide_input).  Refuses graph capture.
+// per camera, takes / more: what the message says about the limit, check_wide_input), after what every batched call begins with (enter).
 static int cams_check(lpf_ctx *c, const char *who, const float *pts, const int64_t *frame_off, int F, const lpf_cam_input *cams, int C,
                       const void *out, int64_t slack, int max_M, const char *takes, const char *more)
 {
     const char *w = who + 4;                               // "run_cams..." in the messages
-    if (c->capturing) return fail(c, LPF_ERR_STATE, "%s cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)", who);
+    int rc;
+    if ((rc = enter(c, who, false))) return rc;
     if (C < 1 || C > LPF_MAX_CAMS) return fail(c, LPF_ERR_ARG, "%s: C=%d cameras, a pass takes 1 .. LPF_MAX_CAMS = %d", w, C, LPF_MAX_CAMS);
     if (!cams || !out || !frame_off || F <= 0)
         return fail(c, LPF_ERR_ARG, "%s: cams=%p out=%p frame_off=%p F=%d", w, (const void *)cams, out, (const void *)frame_off, F);
-    int rc;
     if ((rc = check_frames(c, w, pts, frame_off, F, slack))) return rc;
     for (int k = 0; k < C; ++k) {
         const lpf_cam_input &I = cams[k];
@@ -3002,8 +2967,6 @@ static_assert(LPF_MAX_CAMS == LPF_MAX_CAMS_DEV && LPF_MAX_CAMS <= LPF_NSETS, "a 
 int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_cam_input *cams, int C,
                  const lpf_outputs *out)
 {
-    if (!c) return LPF_ERR_ARG;
-    if (use_device(c)) return LPF_ERR_HIP;
     int rc;
     if ((rc = cams_check(c, "lpf_run_cams", pts, frame_off, F, cams, C, out, LPF_SEG_QUANTUM, LPF_MAX_MASKS, "a pass takes 0 .. LPF_MAX_MASKS",
                          " per camera (more: lpf_run_wide for that camera)")))
@@ -3139,8 +3102,6 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
 int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_cam_input *cams, int C,
                       const lpf_wide_outputs *out)
 {
-    if (!c) return LPF_ERR_ARG;
-    if (use_device(c)) return LPF_ERR_HIP;
     int rc;
     if ((rc = cams_check(c, "lpf_run_cams_wide", pts, frame_off, F, cams, C, out, LPF_WIDE_CHUNK, LPF_MAX_MASKS_WIDE,
                          "a pass takes 0 .. LPF_MAX_MASKS_WIDE", " per camera")))
@@ -3178,7 +3139,7 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
     LpfCamsWideArgs A;
     memset(&A, 0, sizeof A);
     A.C = C;
-    OutStage S[LPF_MAX_CAMS];
+    Stage S[LPF_MAX_CAMS];
     int max_lists = 0, max_boxes = 0;
     bool any_boxes = false, any_host = false;
     for (int k = 0; k < C; ++k) {

@@ -19,6 +19,7 @@
 
 extern "C" long long fake_hip_launches(void);
 extern "C" unsigned long long fake_hip_trace_hash(void);
+extern "C" unsigned long long fake_hip_copy_hash(int restart);
 extern "C" void fake_hip_trace_flush(void);
 
 static int g_fail = 0;
@@ -847,9 +848,11 @@ static void pack_forms()
     g_ctx = nullptr;
 }
 
+// the launches so far and their hash; the hash of the copies and memsets since the section before (the reader's worker threads copy in
+// an order of their own, so the hash of "reader, box_files" differs from run to run -- every other section's is a constant)
 static void section(const char *name)
 {
-    fprintf(stderr, "  trace after %-24s %lld launches, hash %016llx\n", name, fake_hip_launches(), fake_hip_trace_hash());
+    fprintf(stderr, "  trace after %-24s %lld launches, hash %016llx, its copies %016llx\n", name, fake_hip_launches(), fake_hip_trace_hash(), fake_hip_copy_hash(1));
 }
 
 int main(int argc, char **argv)
@@ -874,6 +877,7 @@ int main(int argc, char **argv)
     section("graphs");
     reader(tmp);
     box_files(tmp);
+    section("reader, box_files");
     for (int mode = 0; mode <= 4; mode += 2) {
         mask_sources(mode, W, H);
         mask_sources(mode, 1408, 376);                       // (large sparse launches: the rectangles' candidate grid ahead of the tiles, riding in mode 4)

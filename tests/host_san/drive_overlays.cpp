@@ -13,6 +13,9 @@
 
 extern "C" long long fake_hip_launches(void);
 extern "C" long long fake_hip_copies(void);
+extern "C" unsigned long long fake_hip_trace_hash(void);
+extern "C" unsigned long long fake_hip_copy_hash(int restart);
+extern "C" void fake_hip_trace_flush(void);
 
 static int g_fail = 0;
 static lpf_ctx *g_ctx = nullptr;
@@ -171,6 +174,8 @@ int main()
     runs(c);
     lpf_destroy(c);
     g_ctx = nullptr;
-    fprintf(stderr, "drive_overlays: %d failed checks, %lld fake launches\n", g_fail, fake_hip_launches());
+    fake_hip_trace_flush();
+    fprintf(stderr, "drive_overlays: %d failed checks, %lld fake launches, trace hash %016llx, %lld copies, copy hash %016llx\n", g_fail, fake_hip_launches(),
+            fake_hip_trace_hash(), fake_hip_copies(), fake_hip_copy_hash(0));
     return g_fail ? 1 : 0;
 }

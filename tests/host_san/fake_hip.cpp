@@ -8,7 +8,11 @@
 // Which kernels the host code launches, and with which grids, is recorded: every launch is a line "<kernel> gx gy gz bx by bz" (the
 // kernel's mangled name as the code object lists it; no pointer-valued arguments -- they differ from run to run), folded into a running
 // hash (fake_hip_trace_hash) and written to the file FAKE_HIP_TRACE names, if it is set.  Two builds of the host code that launch the
-// same kernels in the same order have the same hash and the same file.
+// same kernels in the same order have the same hash and the same launch lines.  Copies and memsets are recorded beside them, as
+// "copy <kind> <bytes>" (hipMemcpyKind's number: 1 up, 2 down, 3 device to device) and "memset <bytes>" -- no pointers either -- in the
+// same file, where they stand between the launches they were queued between, and folded into a hash of their own
+// (fake_hip_copy_hash, which a driver may restart per section: threads that copy, the reader's workers, make the order of one
+// section's lines differ from run to run), so that the launch hash means what it always did.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -37,18 +41,17 @@ namespace {
 struct Trace {
     std::mutex mu;
     std::map<const void *, std::string> names;            // host stub -> kernel name
-    unsigned long long hash = 1469598103934665603ull;     // FNV-1a over the lines
+    unsigned long long hash = 1469598103934665603ull;     // FNV-1a over the launch lines ...
+    unsigned long long copy_hash = 1469598103934665603ull;    // ... and over the copy / memset lines
     FILE *file = nullptr;
     bool opened = false;
 };
 Trace &trace() { static Trace *t = new Trace; return *t; }
-void trace_launch(const char *name, dim3_ g, dim3_ b)
+void trace_line(const char *line, int n, unsigned long long Trace::*hash)
 {
-    char line[640];
-    const int n = snprintf(line, sizeof line, "%s %u %u %u %u %u %u\n", name, g.x, g.y, g.z, b.x, b.y, b.z);
     Trace &t = trace();
     std::lock_guard<std::mutex> lock(t.mu);
-    for (int i = 0; i < n && i < (int)sizeof line - 1; ++i) t.hash = (t.hash ^ (unsigned char)line[i]) * 1099511628211ull;
+    for (int i = 0; i < n; ++i) t.*hash = (t.*hash ^ (unsigned char)line[i]) * 1099511628211ull;
     if (!t.opened) {
         t.opened = true;
         const char *path = getenv("FAKE_HIP_TRACE");
@@ -56,8 +59,28 @@ void trace_launch(const char *name, dim3_ g, dim3_ b)
     }
     if (t.file) fputs(line, t.file);
 }
+void trace_launch(const char *name, dim3_ g, dim3_ b)
+{
+    char line[640];
+    const int n = snprintf(line, sizeof line, "%s %u %u %u %u %u %u\n", name, g.x, g.y, g.z, b.x, b.y, b.z);
+    trace_line(line, n < (int)sizeof line ? n : (int)sizeof line - 1, &Trace::hash);
+}
+void trace_copy(int kind, size_t bytes)                   // kind < 0: a memset
+{
+    char line[64];
+    const int n = kind < 0 ? snprintf(line, sizeof line, "memset %zu\n", bytes) : snprintf(line, sizeof line, "copy %d %zu\n", kind, bytes);
+    trace_line(line, n, &Trace::copy_hash);
+}
 }  // namespace
 unsigned long long fake_hip_trace_hash(void) { Trace &t = trace(); std::lock_guard<std::mutex> lock(t.mu); return t.hash; }
+unsigned long long fake_hip_copy_hash(int restart)        // restart: the next call's hash covers what is copied from here on
+{
+    Trace &t = trace();
+    std::lock_guard<std::mutex> lock(t.mu);
+    const unsigned long long h = t.copy_hash;
+    if (restart) t.copy_hash = 1469598103934665603ull;
+    return h;
+}
 void fake_hip_trace_flush(void) { Trace &t = trace(); std::lock_guard<std::mutex> lock(t.mu); if (t.file) fflush(t.file); }
 
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return 0; }
@@ -70,9 +93,9 @@ hipError_t hipFree(void *p) { free(p); return 0; }
 hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? 0 : 2; }
 hipError_t hipHostFree(void *p) { free(p); return 0; }
 hipError_t hipPointerGetAttributes(void *, const void *) { return 1; }      // (nothing is GPU-mapped here: host results take the copy path)
-hipError_t hipMemcpy(void *d, const void *s, size_t n, int) { ++g_copies; memmove(d, s, n); return 0; }
-hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, int, hipStream_t) { ++g_copies; memmove(d, s, n); return 0; }
-hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { memset(d, v, n); return 0; }
+hipError_t hipMemcpy(void *d, const void *s, size_t n, int kind) { ++g_copies; trace_copy(kind, n); memmove(d, s, n); return 0; }
+hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, int kind, hipStream_t) { ++g_copies; trace_copy(kind, n); memmove(d, s, n); return 0; }
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { trace_copy(-1, n); memset(d, v, n); return 0; }
 
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = new fake_stream{0}; return 0; }
 hipError_t hipStreamDestroy(hipStream_t s) { delete s; return 0; }

@@ -217,6 +217,29 @@ def test_mask_counts_and_rectangles(ctx, cal, gold, M, tiled):
             _same(ctx.depth_maps([pts], _dev(masks), binarize="astype", rects=_dev(_rects(masks, pad, W, H)))[0], base, ("dev rects", M, pad))
 
 
+def test_host_masks_of_more_than_one_chunk(ctx, cal, gold):
+    """Eight sample frames with 64 host uint8 masks and their rectangles each, just over what one chunk stages: a frame costs
+    4 hwp + 12 M ntile + M (W H + 16) + 16 max N bytes of scratch (lpf_depth_maps), 38 MB here, so seven frames fit the 256 MiB of a
+    chunk and the eighth is a chunk of its own -- its points, masks and rectangles are staged from an offset, its lists land behind
+    the first chunk's.  Every list against the definition, bit for bit.  The split itself is not observed at run time: the assert
+    below restates the host's cost formula and has to follow it (a kernel trace of this case shows lpf_dm_frame once per chunk)."""
+    W, H, M = cal["W"], cal["H"], 64
+    keys = sorted(k for k in gold if not isinstance(k, tuple))[:8]
+    pts = [gold[k]["pts"] for k in keys]
+    ntile = (W * H + 1023) // 1024
+    per_frame = 4 * ntile * 1024 + 12 * M * ntile + M * (W * H + 16) + 16 * max(len(p) for p in pts)
+    assert 7 * per_frame <= (256 << 20) < 8 * per_frame
+    base = _mask_set(gold, M, 0, W, H, True)
+    masks = np.stack([np.roll(base, 29 * f, axis=2) for f in range(len(keys))])     # another set per frame
+    rects = np.stack([_rects(m) for m in masks])
+    res = ctx.depth_maps(pts, masks, binarize="astype", rects=rects)
+    assert len(res) == len(keys)
+    for f, k in enumerate(keys):
+        D, win = _oracle(cal, pts[f])
+        _same(res[f], _expect(D, win, masks[f] != 0), ("chunks", k))
+    assert sum(len(c[0]) for c in res[7]) > 1000                # the second chunk found its points
+
+
 @pytest.mark.parametrize("rule", ["u8", "astype", "v3", "gt0.5"])
 @pytest.mark.parametrize("erode", [0, 1])
 @pytest.mark.parametrize("M", [5, 40])

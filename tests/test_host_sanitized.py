@@ -15,7 +15,8 @@ GPU box, where sanitizer runs are not available):
     through device and host memory; a mode switch, a camera of another size, a label image read or set, masks for no frames and a
     graph capture with unpacked masks pending; mode-4 launches whose pack and tiles do not go together; and the packs of
     lpf_run_cams / lpf_run_wide / lpf_depth_maps for every rule and label width.  fake_hip.cpp records every launch (kernel name,
-    grid, block): the driver prints count and hash per section, and FAKE_HIP_TRACE=<file> keeps the lines.
+    grid, block) and every copy and memset (kind, bytes): the driver prints the launch count and hash and the hash of the copies per
+    section, and FAKE_HIP_TRACE=<file> keeps the lines.
 """
 import os
 import shutil
@@ -47,8 +48,8 @@ def test_oracle_under_asan_and_ubsan():
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not installed")
 @pytest.mark.parametrize("san", ["asan", "tsan"])
-def test_host_side_of_the_library_under_sanitizers(tmp_path, san):
-    out = str(tmp_path / "build")
+def test_host_side_of_the_library_under_sanitizers(tmp_path, tmp_path_factory, san):
+    out = str(tmp_path_factory.getbasetemp() / "host_san")         # (shared with the other drivers' tests: one lpf_api object per sanitizer)
     b = subprocess.run(["make", "-C", os.path.join(REPO, "tests", "host_san"), san, "OUT=" + out, "HIPCC=" + HIPCC], capture_output=True, text=True, timeout=900)
     assert b.returncode == 0, (b.stdout + b.stderr)[-3000:]
     scans = tmp_path / "scans"
