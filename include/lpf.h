@@ -56,7 +56,8 @@ extern "C" {
                                       8 (continued): lpf_depth_overlay_input, lpf_depth_overlay_outputs, lpf_depth_overlays (added;
                                          nothing else changed)
                                       8 (continued): lpf_match2d_input, lpf_match2d_outputs, lpf_match_2d (added; nothing else changed)
-                                      8 (continued): lpf_inside_input, lpf_inside_outputs, lpf_inside_masks (added; nothing else changed) */
+                                      8 (continued): lpf_inside_input, lpf_inside_outputs, lpf_inside_masks (added; nothing else changed)
+                                      8 (continued): lpf_set_erosion_element (added; nothing else changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -190,7 +191,8 @@ int lpf_set_camera(lpf_ctx *ctx, const double T_velo_to_rect[16], const double K
  *   binarize = 1 : (mask*255).astype(uint8) -> erode -> /255.0 -> astype(uint8) != 0   (V3:82-97 then V3:222)
  *   binarize = 2 : member <=> mask > 0.5 on the raw float mask   (Same_color.py:125, vis.py:185,
  *                  seg_with_pointcloud.py:167: the scripts that index the YOLO mask without astype)
- * erode_iters: iterations of cv2.erode with the 3x3 MORPH_ELLIPSE (cross) element (V3:83-90).
+ * erode_iters: iterations of cv2.erode with the context's erosion element: the 3x3 MORPH_ELLIPSE (the cross, V3:83-90) unless
+ *   lpf_set_erosion_element has set another size.
  * The packed result is a label image [F][H][W], bit m = mask m, kept in HBM.
  * on_device: 0 = host memory (copied before the call returns); 1 = device memory, packed in stream order by this call (the
  *   buffer may be rewritten, in stream order, as soon as the call has returned); 2 = device memory LENT to the context: it
@@ -217,6 +219,24 @@ int lpf_set_masks_u8(lpf_ctx *ctx, const uint8_t *masks, int F, int M, int erode
  * 0 = host memory, copied now without a wait; otherwise device memory (16-byte aligned) that stays unchanged until the runs that use
  * these masks have completed, like lent masks.  rects = NULL clears a pending hint.  The hint is consumed by the next lpf_set_masks_*. */
 int lpf_set_mask_rects(lpf_ctx *ctx, const int32_t *rects, int on_device, int F, int M);
+/* The erosion element of the context: cv2.getStructuringElement(cv2.MORPH_ELLIPSE, (ksize, ksize)), the reference's
+ * `erosion_kernel_size` (V3:55-97, cvs_erosion.py:77-106: image_segmentation_with_erosion(image, erosion_kernel_size=3,
+ * erosion_iterations=1) builds this element and hands it to cv2.erode(mask_uint8, kernel, iterations=erosion_iterations)).
+ * ksize is odd, 1 .. 15; a new context has 3.  The element, restated from OpenCV for odd k and pinned by construction only, like the
+ * 3x3 erosion and the resize (OpenCV is no dependency of this project): with r = ksize / 2, row i (dy = i - r) is ones from column
+ * r - dx to r + dx inclusive, dx = round_half_even(r * sqrt((r*r - dy*dy) * (1.0 / (r*r)))) in double (ksize = 1: dx = 0).  Half-widths
+ * per row, shipped as a table (no quotient lies within 0.02 of a tie):
+ *    3: 0 1 0  (the cross)        5: 0 2 2 2 0        7: 0 2 3 3 3 2 0        9: 0 3 3 4 4 4 3 3 0
+ *   11: 0 3 4 5 5 5 5 5 4 3 0    13: 0 3 4 5 6 6 6 6 6 5 4 3 0    15: 0 4 5 6 6 7 7 7 7 7 6 6 5 4 0
+ * An erosion is the minimum (on packed masks: the AND) over the element, pixels outside the image left out; several iterations repeat
+ * one iteration (cv2.erode merges rectangular elements only).  ksize = 1 makes any number of iterations the identity.
+ * Context state, host side only: the call enqueues nothing and waits for nothing.  From then on every erosion of the context uses it:
+ * the erode_iters of lpf_set_masks_u8 / lpf_set_masks_f32 (every binarize rule), the erode_iters of a lpf_wide_input (lpf_run_wide,
+ * lpf_run_cams, lpf_run_cams_wide, lpf_depth_maps) and lpf_erode_masks_u8.  Masks already packed keep the element they were packed
+ * with, a captured graph the one it was captured with; lpf_set_mask_rects' contract is unchanged (no erosion).  With ksize = 3 the
+ * launches are the ones of a context that never called this.  LPF_ERR_ARG (the message names the value, the element stays as it
+ * was): an even size, ksize < 1, ksize > 15. */
+int lpf_set_erosion_element(lpf_ctx *ctx, int ksize);
 int lpf_set_masks_f32(lpf_ctx *ctx, const float *masks, int F, int M, int binarize,
                       int erode_iters, int on_device);
 /* Pre-packed label images [F][H][W] (bit m = mask m). */
@@ -299,7 +319,7 @@ typedef struct lpf_wide_input {
     int32_t  M;
     int32_t  f32;                  /* 0: uint8 masks, 1: float32 */
     int32_t  binarize;             /* float32 masks: 0 / 1 / 2 as lpf_set_masks_f32 */
-    int32_t  erode_iters;          /* cv2.erode iterations with the cross element, >= 0 */
+    int32_t  erode_iters;          /* cv2.erode iterations with the context's element (lpf_set_erosion_element; the cross by default), >= 0 */
     int32_t  on_device;            /* 0: masks (and rects) in host memory, copied by the call; else device memory lent until the
                                       run has completed (as on_device = 2 of lpf_set_masks_*) */
     int32_t  reserved;
@@ -609,8 +629,9 @@ int lpf_inside_masks(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, i
  * callers: in stream order.  Not capturable. */
 int lpf_resize_masks_u8(lpf_ctx *ctx, const uint8_t *src, int n, int h, int w, uint8_t *dst, int on_device);
 
-/* cv2.erode(plane, cv2.getStructuringElement(cv2.MORPH_ELLIPSE, (3, 3)), iterations=iters) on n planes [h][w] of 8-bit VALUES, at the
- * planes' own size (V3:83-90): the minimum over the plus-shaped neighbourhood, the image border left out.  For masks that do not
+/* cv2.erode(plane, cv2.getStructuringElement(cv2.MORPH_ELLIPSE, (k, k)), iterations=iters) on n planes [h][w] of 8-bit VALUES, at the
+ * planes' own size (V3:83-90), k = the context's element (lpf_set_erosion_element; 3 by default, the plus-shaped neighbourhood): the
+ * minimum over the element, the image border left out.  For masks that do not
  * arrive at camera size the reference erodes first and resizes afterwards (V3:82-97, then V3:222): this call, then
  * lpf_resize_masks_u8.  (Masks at camera size are eroded inside lpf_set_masks_*, on the packed label image.)  src != dst; host or
  * device pointers per on_device, device callers in stream order.  Pinned by construction only, like lpf_set_masks_*'s erosion. */

@@ -254,6 +254,7 @@ def load(path=None):
     lib.lpf_set_camera.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double]
     lib.lpf_set_masks_u8.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.lpf_set_mask_rects.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.lpf_set_erosion_element.argtypes = [_P, ctypes.c_int]
     lib.lpf_resize_masks_u8.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
     lib.lpf_erode_masks_u8.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
     lib.lpf_set_masks_f32.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -308,7 +309,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
             "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d",
-            "lpf_inside_masks")
+            "lpf_inside_masks", "lpf_set_erosion_element")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -471,6 +472,7 @@ class LpfContext:
         self.F_masks = 0
         self.box_off = None
         self._depth = 1
+        self.erosion_kernel_size = 3            # the element in force (set_erosion_element)
         self._pin = {}                          # persistent page-locked host buffers (run_batch(pinned=True))
         # lent tensors (masks, box corners) of the runs that may still read them: in the pipelined modes a run's inputs are read
         # up to two launches after it was queued, so the references of the last few runs are kept (torch's caching allocator is
@@ -666,10 +668,18 @@ class LpfContext:
         self._check(self._lib.lpf_resize_masks_u8(self._h, a.ctypes.data if n else None, n, shape[-2], shape[-1], out.ctypes.data if n else None, 0))
         return out
 
+    def set_erosion_element(self, k):
+        """The element of every erosion this context performs from now on: cv2.getStructuringElement(cv2.MORPH_ELLIPSE, (k, k)), the
+        reference's ``erosion_kernel_size`` (V3:55-97; include/lpf.h: lpf_set_erosion_element) -- k odd, 1 .. 15, 3 (the cross) in a
+        new context.  It holds for set_masks' / run_wide's / run_cams' / depth_maps' ``erode_iters`` and for erode_masks; masks that are
+        packed already keep theirs.  Host state only: nothing is queued.  A refused size raises LpfError and changes nothing."""
+        self._check(self._lib.lpf_set_erosion_element(self._h, int(k)))
+        self.erosion_kernel_size = int(k)
+
     def erode_masks(self, masks, iterations=1):
-        """cv2.erode(plane, MORPH_ELLIPSE 3x3, iterations) on uint8 VALUES [..., h, w] at the planes' own size (V3:83-90, for masks that
-        are eroded before they are resized): NumPy in -> NumPy out, uint8 torch GPU tensor in -> tensor out (ordered with torch's
-        current stream on both sides)."""
+        """cv2.erode(plane, MORPH_ELLIPSE k x k, iterations) on uint8 VALUES [..., h, w] at the planes' own size (V3:83-90, for masks that
+        are eroded before they are resized), k = the context's element (set_erosion_element; 3 by default): NumPy in -> NumPy out,
+        uint8 torch GPU tensor in -> tensor out (ordered with torch's current stream on both sides)."""
         if _is_torch(masks):
             import torch
             if str(masks.dtype) != "torch.uint8" or not masks.is_contiguous():

@@ -93,6 +93,11 @@ struct lpf_ctx {
     double T[12], K[9], dmin = 0, dmax = 0;
     int W = 0, H = 0;
 
+    // the erosion element (lpf_set_erosion_element): the k x k MORPH_ELLIPSE, its radius and its rows' half-widths as the kernels take
+    // them (nibble j = row |dy| = j).  k = 3 is the cross of lpf_pack_erode / lpf_erode_packed / lpf_erode_u8_kernel themselves
+    int erode_k = 3, erode_r = 1;
+    uint32_t erode_spans = 0x01u;
+
     // masks -> label images
     int mask_F = 0, mask_M = 0;       // 0 frames = no masks set
     int mask_set = 0;                 // the scratch set whose label image holds them
@@ -866,8 +871,13 @@ int pack_masks(lpf_ctx *c, DevBuf &la, DevBuf &lb_, const int W, const int H, hi
         if (M == 0) {
             LPF_HIP(c, hipMemsetAsync(cur, 0, (size_t)F * hw * sizeof(LT), ms));
         } else {
+            if (c->erode_k == 1) erode_iters = 0;          // (the 1 x 1 element: any number of iterations is the identity)
+            // the k x k element of lpf_set_erosion_element: its own pack (first erosion fused, whatever the shape) and erosion kernel
+            const bool element = erode_iters > 0 && c->erode_k != 3;
+            const int er = c->erode_r;
+            const uint32_t spans = c->erode_spans;
             int left = erode_iters;
-            const bool stream16 = hw % 16 == 0 && ((uintptr_t)masks & 15) == 0;
+            const bool stream16 = !element && hw % 16 == 0 && ((uintptr_t)masks & 15) == 0;
             if (!stream16 && erode_iters > 0) --left;      // (the tiled pack does the first erosion itself)
             with_rule(f32, rule, [&](auto kind) {
                 typedef typename decltype(kind)::elem T;
@@ -879,6 +889,8 @@ int pack_masks(lpf_ctx *c, DevBuf &la, DevBuf &lb_, const int W, const int H, hi
                     const long long total16 = (long long)F * (long long)(hw / 16);
                     const unsigned nb = (unsigned)((total16 + LPF_BLOCK - 1) / LPF_BLOCK);
                     hipLaunchKernelGGL((lpf_pack16<T, RULE, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, (const T *)masks, cur, M, (long long)hw, total16, r, W);
+                } else if (element) {
+                    hipLaunchKernelGGL((lpf_pack_erode_k<T, RULE, LT>), grid, dim3(LPF_BLOCK), 0, ms, (const T *)masks, cur, M, H, W, er, spans);
                 } else {
                     hipLaunchKernelGGL((lpf_pack_erode<T, RULE, LT>), grid, dim3(LPF_BLOCK), 0, ms, (const T *)masks, cur, M, H, W, erode_iters > 0 ? 1 : 0, r);
                 }
@@ -888,7 +900,8 @@ int pack_masks(lpf_ctx *c, DevBuf &la, DevBuf &lb_, const int W, const int H, hi
                 if ((rc = reserve(c, lb_, (size_t)F * hw * 4))) return rc;
                 LT *other = (LT *)lb_.p;
                 for (int it = 0; it < left; ++it) {
-                    hipLaunchKernelGGL((lpf_erode_packed<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, H, W);
+                    if (element) hipLaunchKernelGGL((lpf_erode_packed_k<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, H, W, er, spans);
+                    else hipLaunchKernelGGL((lpf_erode_packed<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, H, W);
                     LPF_HIP(c, hipGetLastError());
                     LT *t = cur; cur = other; other = t;
                 }
@@ -1578,6 +1591,25 @@ int lpf_set_mask_rects(lpf_ctx *c, const int32_t *rects, int on_device, int F, i
     return LPF_OK;
 }
 
+// The erosion element of every erosion the context performs from now on: cv2.getStructuringElement(MORPH_ELLIPSE, (ksize, ksize)), see
+// include/lpf.h.  Row |dy| of the element with radius r holds the columns -dx .. dx, dx = LPF_ELLIPSE_DX[r][|dy|]:
+// round(r * sqrt((r*r - dy*dy) / (r*r))), shipped as a table (no quotient lies near a tie, so it does not depend on the rounding rule).
+// Host state only: nothing is enqueued; masks already packed and a captured graph keep the element they were made with (it is a kernel
+// argument).
+static const uint8_t LPF_ELLIPSE_DX[8][8] = {{0}, {1, 0}, {2, 2, 0}, {3, 3, 2, 0}, {4, 4, 3, 3, 0}, {5, 5, 5, 4, 3, 0}, {6, 6, 6, 5, 4, 3, 0},
+                                             {7, 7, 7, 6, 6, 5, 4, 0}};
+int lpf_set_erosion_element(lpf_ctx *c, int ksize)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (ksize < 1 || ksize > 15 || ksize % 2 == 0)
+        return fail(c, LPF_ERR_ARG, "lpf_set_erosion_element: ksize=%d (the k x k MORPH_ELLIPSE for odd k, 1 .. 15)", ksize);
+    const int r = ksize / 2;
+    uint32_t spans = 0;
+    for (int j = 0; j <= r; ++j) spans |= (uint32_t)LPF_ELLIPSE_DX[r][j] << (4 * j);
+    c->erode_k = ksize; c->erode_r = r; c->erode_spans = spans;
+    return LPF_OK;
+}
+
 int lpf_set_pipelined(lpf_ctx *c, int on)
 {
     if (!c) return LPF_ERR_ARG;
@@ -1993,7 +2025,7 @@ int lpf_resize_masks_u8(lpf_ctx *c, const uint8_t *src, int n, int h, int w, uin
     return LPF_OK;
 }
 
-// n planes [h][w] of uint8 values, eroded `iters` times with the 3x3 cross at their own size (V3:83-90): see include/lpf.h
+// n planes [h][w] of uint8 values, eroded `iters` times with the context's element (the 3x3 cross unless lpf_set_erosion_element says otherwise) at their own size (V3:83-90): see include/lpf.h
 int lpf_erode_masks_u8(lpf_ctx *c, const uint8_t *src, int n, int h, int w, int iters, uint8_t *dst, int on_device)
 {
     if (!c) return LPF_ERR_ARG;
@@ -2017,9 +2049,11 @@ int lpf_erode_masks_u8(lpf_ctx *c, const uint8_t *src, int n, int h, int w, int 
     const long long total = (long long)bytes;
     const dim3 g((unsigned)((total + LPF_BLOCK - 1) / LPF_BLOCK));
     // the last iteration must land in `a` (dst for device callers): with an even count the first one goes to b
+    if (c->erode_k == 1) iters = 0;                        // (the 1 x 1 element of lpf_set_erosion_element: the identity)
     uint8_t *out = (iters % 2 == 1) ? a : b;
     for (int it = 0; it < iters; ++it) {
-        hipLaunchKernelGGL(lpf_erode_u8_kernel, g, dim3(LPF_BLOCK), 0, c->stream, cur, out, w, h, total);
+        if (c->erode_k != 3) hipLaunchKernelGGL(lpf_erode_u8_k_kernel, g, dim3(LPF_BLOCK), 0, c->stream, cur, out, w, h, total, c->erode_r, c->erode_spans);
+        else hipLaunchKernelGGL(lpf_erode_u8_kernel, g, dim3(LPF_BLOCK), 0, c->stream, cur, out, w, h, total);
         LPF_HIP(c, hipGetLastError());
         cur = out;
         out = (out == a) ? b : a;
@@ -2292,17 +2326,25 @@ static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int
         if ((rc = reserve(c, D.planes_a, (size_t)F * LW * hw * 4))) return rc;
         uint32_t *cur = (uint32_t *)D.planes_a.p;
         const dim3 grid((Wimg + LPF_TW - 1) / LPF_TW, (Himg + LPF_TH - 1) / LPF_TH, (unsigned)(F * LW));
-        const int fuse = in->erode_iters > 0 ? 1 : 0;
+        const int iters = c->erode_k == 1 ? 0 : in->erode_iters;      // (the 1 x 1 element: the identity)
+        const int fuse = iters > 0 ? 1 : 0;
+        const bool element = fuse && c->erode_k != 3;     // the k x k element of lpf_set_erosion_element: its own kernels
+        const int er = c->erode_r;
+        const uint32_t spans = c->erode_spans;
         with_rule(in->f32 != 0, in->binarize + 1, [&](auto kind) {
             typedef typename decltype(kind)::elem T;
-            hipLaunchKernelGGL((lpf_wide_pack<T, decltype(kind)::rule>), grid, dim3(LPF_BLOCK), 0, c->stream, (const T *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
+            if (element)
+                hipLaunchKernelGGL((lpf_wide_pack_k<T, decltype(kind)::rule>), grid, dim3(LPF_BLOCK), 0, c->stream, (const T *)d_masks, cur, M, LW, Himg, Wimg, er, spans);
+            else
+                hipLaunchKernelGGL((lpf_wide_pack<T, decltype(kind)::rule>), grid, dim3(LPF_BLOCK), 0, c->stream, (const T *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
         });
         LPF_HIP(c, hipGetLastError());
-        if (in->erode_iters > 1) {                        // further iterations: the narrow path's own kernel, a plane per (frame, word)
+        if (iters > 1) {                                  // further iterations: the narrow path's own kernel, a plane per (frame, word)
             if ((rc = reserve(c, D.planes_b, (size_t)F * LW * hw * 4))) return rc;
             uint32_t *other = (uint32_t *)D.planes_b.p;
-            for (int it = 1; it < in->erode_iters; ++it) {
-                hipLaunchKernelGGL((lpf_erode_packed<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, Himg, Wimg);
+            for (int it = 1; it < iters; ++it) {
+                if (element) hipLaunchKernelGGL((lpf_erode_packed_k<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, Himg, Wimg, er, spans);
+                else hipLaunchKernelGGL((lpf_erode_packed<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, Himg, Wimg);
                 LPF_HIP(c, hipGetLastError());
                 std::swap(cur, other);
             }

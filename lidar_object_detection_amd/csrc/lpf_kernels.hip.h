@@ -4,6 +4,8 @@
 // Kernel map (reference statements: /root/reference/Coding_testes, see include/lpf.h)
 //   lpf_pack16 / lpf_pack_erode / lpf_erode_packed
 //                      masks -> label image (bit m = mask m); 3x3-cross erosion
+//   lpf_pack_erode_k / lpf_erode_packed_k / lpf_erode_u8_k_kernel
+//                      the same with the k x k MORPH_ELLIPSE element, k = 5 .. 15 (lpf_set_erosion_element)
 //                      on an LDS-staged tile of packed bits                             (V3:82-97, V3:222)
 //   lpf_k1_project     float4 stream: 4x4 transform, cam2image, clip, label gather,
 //                      per-row wave ballots + three levels of counters                  (V3:565-569, 584, 225)
@@ -1762,6 +1764,29 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_erode_u8_kernel(const uint8_t *
     dst[i] = (uint8_t)v;
 }
 
+// The same with the k x k MORPH_ELLIPSE element of lpf_set_erosion_element, k = 5 .. 15 (r = k / 2; row dy holds the columns -dx .. dx,
+// dx = nibble |dy| of `spans`: see the packed kernels below): the minimum over the element's pixels that exist.  A thread per pixel;
+// the planes are small (masks at the detector's size) and a row span is contiguous bytes, so the reads come from the cache.
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_erode_u8_k_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const int w, const int h,
+                                                                   const long long total, const int r, const uint32_t spans)
+{
+    const long long i = (long long)blockIdx.x * LPF_BLOCK + threadIdx.x;
+    if (i >= total) return;
+    const long long hw = (long long)w * h;
+    const long long rem = i % hw;
+    const int y = (int)(rem / w), x = (int)(rem - (long long)y * w);
+    const uint8_t *__restrict__ plane = src + (i - rem);
+    unsigned v = 255u;                                            // (the centre belongs to every element)
+    for (int dy = -r; dy <= r; ++dy) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= h) continue;
+        const int dx = (int)((spans >> (4 * (dy < 0 ? -dy : dy))) & 15u);
+        const uint8_t *__restrict__ row = plane + (long long)yy * w;
+        for (int xx = max(x - dx, 0); xx <= min(x + dx, w - 1); ++xx) v = min(v, (unsigned)row[xx]);
+    }
+    dst[i] = (uint8_t)v;
+}
+
 // ------------------------------------------------------------------------------------
 // Standalone K6: inside[b][i] for k points x B boxes -- the drop-in for
 // oriented_point_in_bbox / point_in_bbox (V3:143-208), which return the per-point mask.
@@ -2323,5 +2348,88 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_erode_packed(const LT *__restri
         if (y < H && x < W)
             out[(size_t)f * hw + (size_t)y * W + x] = (LT)(s_tile[ty + 1][tx + 1] & s_tile[ty][tx + 1] & s_tile[ty + 2][tx + 1] &
                                                             s_tile[ty + 1][tx] & s_tile[ty + 1][tx + 2]);
+    }
+}
+
+// ---- k x k MORPH_ELLIPSE erosion, k = 5 .. 15 (lpf_set_erosion_element; k = 3 is the cross of the kernels above) --------------------
+// The element is cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)) as include/lpf.h restates it, r = k / 2: row dy = -r .. r holds the
+// columns -dx .. dx, dx = nibble |dy| of `spans` (the host's table: the rows are symmetric, r + 1 <= 8 nibbles fit one word).  The same
+// 64x16 output tile as above with a halo of r on each side, (16 + 2r) x (64 + 2r) words of the LDS tile in use (declared for r = 7:
+// 30 x 79 words, 9.3 KB; the + 1 keeps the rows off a power-of-two stride); pixels outside the image read as all-ones (OpenCV's
+// erode border).  The AND runs straight over the element's row spans: 17 / 33 / 169 LDS reads per pixel at k = 5 / 7 / 15, lanes of a
+// wave on consecutive words of a row (no bank conflict).  One iteration per launch: cv2.erode never merges a non-rectangular element.
+#define LPF_ER_MAX 7
+#define LPF_EK_LD (LPF_TW + 2 * LPF_ER_MAX + 1)
+#define LPF_EK_ROWS (LPF_TH + 2 * LPF_ER_MAX)
+
+__device__ __forceinline__ uint32_t lpf_element_and(const uint32_t (*s_tile)[LPF_EK_LD], const int ty, const int tx, const int r, const uint32_t spans)
+{
+    uint32_t v = 0xFFFFFFFFu;
+    for (int dy = -r; dy <= r; ++dy) {
+        const int dx = (int)((spans >> (4 * (dy < 0 ? -dy : dy))) & 15u);
+        const uint32_t *row = &s_tile[ty + r + dy][tx + r];
+        for (int d = -dx; d <= dx; ++d) v &= row[d];
+    }
+    return v;
+}
+
+// membership bits of masks mf[0 .. mw) (planes of hw pixels, mw <= 32) -> the halo tile of the block at (x0, y0)
+template <typename T, int MODE>
+__device__ __forceinline__ void lpf_element_stage_masks(uint32_t (*s_tile)[LPF_EK_LD], const T *__restrict__ mf, const int mw, const size_t hw,
+                                                        const int H, const int W, const int x0, const int y0, const int r)
+{
+    const int tw = LPF_TW + 2 * r, n = (LPF_TH + 2 * r) * tw;
+    for (int p = threadIdx.x; p < n; p += LPF_BLOCK) {
+        const int ty = p / tw, tx = p - ty * tw;
+        const int y = y0 + ty - r, x = x0 + tx - r;
+        uint32_t bits = 0xFFFFFFFFu;
+        if (y >= 0 && y < H && x >= 0 && x < W) {
+            bits = 0;
+            const size_t o = (size_t)y * W + x;
+            for (int m = 0; m < mw; ++m)
+                if (lpf_member<T, MODE>(mf[m * hw + o])) bits |= 1u << m;
+        }
+        s_tile[ty][tx] = bits;
+    }
+}
+
+// lpf_pack_erode's role for the k x k element: masks -> membership bits in the halo tile -> the first erosion -> label image (the
+// masks are read once, nothing is packed un-eroded first).  No rectangles: lpf_set_mask_rects holds without erosion only.
+template <typename T, int MODE, typename LT>
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_pack_erode_k(const T *__restrict__ masks, LT *__restrict__ label, int M, int H, int W,
+                                                              int r, uint32_t spans)
+{
+    __shared__ uint32_t s_tile[LPF_EK_ROWS][LPF_EK_LD];
+    const int f = blockIdx.z;
+    const int x0 = blockIdx.x * LPF_TW, y0 = blockIdx.y * LPF_TH;
+    const size_t hw = (size_t)H * W;
+    lpf_element_stage_masks<T, MODE>(s_tile, masks + (size_t)f * M * hw, M, hw, H, W, x0, y0, r);
+    __syncthreads();
+    const int tx = threadIdx.x & (LPF_TW - 1);
+    for (int ty = threadIdx.x >> 6; ty < LPF_TH; ty += LPF_BLOCK / LPF_TW) {
+        const int y = y0 + ty, x = x0 + tx;
+        if (y < H && x < W) label[(size_t)f * hw + (size_t)y * W + x] = (LT)lpf_element_and(s_tile, ty, tx, r, spans);
+    }
+}
+
+// lpf_erode_packed's role for the k x k element: one iteration on the packed image (the wide paths: a plane per (frame, word))
+template <typename LT>
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_erode_packed_k(const LT *__restrict__ in, LT *__restrict__ out, int H, int W, int r, uint32_t spans)
+{
+    __shared__ uint32_t s_tile[LPF_EK_ROWS][LPF_EK_LD];
+    const int f = blockIdx.z;
+    const int x0 = blockIdx.x * LPF_TW, y0 = blockIdx.y * LPF_TH;
+    const size_t hw = (size_t)H * W;
+    const int tw = LPF_TW + 2 * r, n = (LPF_TH + 2 * r) * tw;
+    for (int p = threadIdx.x; p < n; p += LPF_BLOCK) {
+        const int ty = p / tw, tx = p - ty * tw;
+        const int y = y0 + ty - r, x = x0 + tx - r;
+        s_tile[ty][tx] = (y >= 0 && y < H && x >= 0 && x < W) ? (uint32_t)in[(size_t)f * hw + (size_t)y * W + x] : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    const int tx = threadIdx.x & (LPF_TW - 1);
+    for (int ty = threadIdx.x >> 6; ty < LPF_TH; ty += LPF_BLOCK / LPF_TW) {
+        const int y = y0 + ty, x = x0 + tx;
+        if (y < H && x < W) out[(size_t)f * hw + (size_t)y * W + x] = (LT)lpf_element_and(s_tile, ty, tx, r, spans);
     }
 }

@@ -143,6 +143,27 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_pack(const T *__restrict__
     }
 }
 
+// The same with the first erosion by the k x k MORPH_ELLIPSE element of lpf_set_erosion_element, k = 5 .. 15 (lpf_pack_erode_k's tile
+// and AND, a plane per (frame, word)).  No rectangles: they hold without erosion only (rects_hold).
+template <typename T, int MODE>
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_pack_k(const T *__restrict__ masks, uint32_t *__restrict__ planes, int M, int LW,
+                                                             int H, int W, int r, uint32_t spans)
+{
+    __shared__ uint32_t s_tile[LPF_EK_ROWS][LPF_EK_LD];
+    const int f = blockIdx.z / LW, wd = blockIdx.z - f * LW;
+    const int m0 = 32 * wd, mw = min(32, M - m0);
+    const int x0 = blockIdx.x * LPF_TW, y0 = blockIdx.y * LPF_TH;
+    const size_t hw = (size_t)H * W;
+    lpf_element_stage_masks<T, MODE>(s_tile, masks + ((size_t)f * M + m0) * hw, mw, hw, H, W, x0, y0, r);
+    __syncthreads();
+    const int tx = threadIdx.x & (LPF_TW - 1);
+    uint32_t *__restrict__ dst = planes + ((size_t)f * LW + wd) * hw;
+    for (int ty = threadIdx.x >> 6; ty < LPF_TH; ty += LPF_BLOCK / LPF_TW) {
+        const int y = y0 + ty, x = x0 + tx;
+        if (y < H && x < W) dst[(size_t)y * W + x] = lpf_element_and(s_tile, ty, tx, r, spans);
+    }
+}
+
 // ---- project + label: 1024 points per block, 4 consecutive points per thread ----------------------------------------------------
 // Chunk c of frame f (chunk_off and the points depend on the points only: every camera of lpf_cams_wide_project finds the same ones).
 // PRE: the thread's four points are in p[] already (lpf_cams_wide_project loads them once for every camera); else each is read here.

@@ -167,16 +167,18 @@ def run_sharded(frame_items, process_local, device="cpu", group=None):
 
 def process_frames_distributed(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_path=None,
                                master_csv_path="results/master_car_statistics.csv", frames=None,
-                               erode_iters=0, v3_pipeline=False, timestamp=None, batch_frames=32):
+                               erode_iters=0, v3_pipeline=False, timestamp=None, batch_frames=32, erosion_kernel_size=3):
     """cvs_erosion.process_frames over all ranks of an initialised process group: rank r processes
     frames r, r+W, ... on GPU LOCAL_RANK in batches of ``batch_frames``; rank 0 writes the CSV (same rows, same
     order as one process would) and then, like the reference (cvs_erosion.py:379), prints analyze_master_csv of that
     file -- which covers earlier runs too when the file already existed; the all-reduced aggregates of THIS run are
-    returned (format_overall_analysis prints them in the same layout)."""
+    returned (format_overall_analysis prints them in the same layout).  ``erosion_kernel_size``: as in pipeline.run_frames."""
     import os
     import torch
     import torch.distributed as dist
     from . import pipeline
+
+    erosion_kernel_size = pipeline._erosion_kernel_size(erosion_kernel_size)
 
     root = kitti360_path or os.environ["KITTI360_DATASET"]
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -194,7 +196,8 @@ def process_frames_distributed(seq=0, cam_id=0, segmenter=None, image_loader=Non
                                            boxes_as_arrays=True)                  # (only the statistics leave this function)
         out = {}
         for batch in pipeline._batches(items, batch_frames):                        # one batch of the shard in memory at a time
-            res = pipeline.run_frames(batch, velo_to_rect, camera, 50.0, 10, True, erode_iters, v3_pipeline, local_rank)
+            res = pipeline.run_frames(batch, velo_to_rect, camera, 50.0, 10, True, erode_iters, v3_pipeline, local_rank,
+                                      erosion_kernel_size=erosion_kernel_size)
             out.update({r["frame"]: r["car_statistics"] for r in res if r["n_valid"] > 0})
         return out
 

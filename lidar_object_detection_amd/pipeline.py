@@ -30,6 +30,14 @@ def get_context(device=0):
     return ctx
 
 
+def _erosion_kernel_size(k):
+    """``erosion_kernel_size`` (V3:55, cvs_erosion.py:77: the side of the MORPH_ELLIPSE element) as the library takes it: an odd
+    integer 1 .. 15 (lpf_set_erosion_element), anything else raises ValueError -- before any GPU work."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 15 or k % 2 == 0:
+        raise ValueError("erosion_kernel_size must be an odd integer from 1 to 15 (the k x k MORPH_ELLIPSE element), got %r" % (k,))
+    return int(k)
+
+
 def _f32_points(points, what="points"):
     """float32 view of caller points; refuses values a float32 cannot hold (the kernels
     take the velodyne float32 format, V3:28, and there is no float64 point path)."""
@@ -46,7 +54,7 @@ def _is_device_tensor(x):
     return type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)
 
 
-def _mask_stack(masks, camera, resize_ctx=None, erode_iters=0, v3_pipeline=False, force_chain=False):
+def _mask_stack(masks, camera, resize_ctx=None, erode_iters=0, v3_pipeline=False, force_chain=False, erosion_kernel_size=3):
     """([M,H,W] float32/uint8 array from the reference's mask list, eroded_already).  A torch tensor that is already on the GPU --
     ``result.masks.data`` before the reference's ``.cpu().numpy()`` (V3:72) -- is passed through: the kernels read it where it is.
     Masks that do not arrive at the camera's size (the reference's scripts pass retina_masks=True, V3:64, so theirs do) go through
@@ -55,13 +63,17 @@ def _mask_stack(masks, camera, resize_ctx=None, erode_iters=0, v3_pipeline=False
     in force (``v3_pipeline`` / ``erode_iters``) such masks take V3's own order: ``(mask * 255).astype(uint8)`` -> ``cv2.erode`` AT THE
     MASKS' OWN SIZE -> ``/ 255.0`` (V3:82-97), and only then ``astype(uint8)`` + resize (V3:222) -- all on the GPU
     (LpfContext.erode_masks, then resize_masks); the second value tells the caller that the erosion has been done.  ``force_chain``:
-    masks at camera size take the same explicit chain (a batch is eroded either all inside lpf_set_masks_* or all here)."""
+    masks at camera size take the same explicit chain (a batch is eroded either all inside lpf_set_masks_* or all here).
+    ``erosion_kernel_size``: the side of the erosion's MORPH_ELLIPSE element (V3:55), set on ``resize_ctx`` before it erodes."""
+    erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
+
     def chain(m):
         """off-size masks -> uint8 [M,H,W] at camera size (device tensor in -> device tensor out)"""
         if resize_ctx is None:
             raise NotImplementedError("masks must already be %dx%d (retina_masks=True, V3:64) in this call" % (camera.height, camera.width))
         if not (erode_iters or v3_pipeline):
             return resize_ctx.resize_masks(m), False
+        resize_ctx.set_erosion_element(erosion_kernel_size)
         dev = _is_device_tensor(m)
         if dev:
             import torch
@@ -1106,7 +1118,7 @@ def _host_masks_to_device_batch(stacks, M, H, W, ctx):
     return t
 
 
-def _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline):
+def _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline, erosion_kernel_size=3):
     """(per-frame mask stacks at the camera's size, erode_iters, v3_pipeline still owed to the pass) of a batch: the one place that
     decides how masks of another size than the camera's are treated.  They go through cv2.resize as V3:222 does it, on the GPU; with
     the V3 erosion block in force they are eroded at their own size first, as V3:82-97 does before V3:222 (_mask_stack's chain), and
@@ -1114,7 +1126,7 @@ def _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline):
     took the chain is what _mask_stack reports, whatever form their masks came in."""
     def stack(f, force_chain=False):
         return _mask_stack(f.masks if f.masks is not None else [], camera, resize_ctx=ctx, erode_iters=erode_iters,
-                           v3_pipeline=v3_pipeline, force_chain=force_chain)
+                           v3_pipeline=v3_pipeline, force_chain=force_chain, erosion_kernel_size=erosion_kernel_size)
     done = [stack(f) for f in frames]
     if not any(eroded for _, eroded in done):
         return [s for s, _ in done], erode_iters, v3_pipeline
@@ -1146,27 +1158,31 @@ def _mask_batch(stacks, M, H, W, ctx):
 
 
 def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_oriented=True,
-               erode_iters=0, v3_pipeline=False, device=0, ctx=None, gather_scans=True):
+               erode_iters=0, v3_pipeline=False, device=0, ctx=None, gather_scans=True, erosion_kernel_size=3):
     """Projection + clip + mask lookup + box counting + best-box scan for a list of
     FrameInputs in ONE batched call (frames are independent units).  Returns one dict per
     frame: valid_indices, u_valid, v_valid, points_valid, car_point_sets, bg_assigned,
     count_mb, car_statistics (cvs_erosion key set) -- the integers are the kernels' output,
     the dicts are assembled here.  Frames whose points are a read-ahead reader's ``Scan`` have their gathers (``points_valid``,
     ``car_point_sets``) made before the call returns, because the reader recycles the scan's buffers when it moves on;
-    ``gather_scans=False`` leaves them lazy like everyone else's -- reading them after the reader has moved on raises."""
+    ``gather_scans=False`` leaves them lazy like everyone else's -- reading them after the reader has moved on raises.
+    ``erosion_kernel_size``: the reference's knob of that name (V3:55, cvs_erosion.py:77) -- ``erode_iters`` iterations erode with the
+    k x k MORPH_ELLIPSE element (odd, 1 .. 15; 3 is the cross).  It is set on the context by every call, the default included."""
+    erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     if not frames:
         return []
     ctx = ctx or get_context(device)
+    ctx.set_erosion_element(erosion_kernel_size)
     H, W = camera.height, camera.width
     ctx.set_camera(TrVeloToRect, camera.K, W, H, 0.0, float(depth_max))
-    stacks, erode_iters, v3_pipeline = _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline)
+    stacks, erode_iters, v3_pipeline = _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline, erosion_kernel_size)
     counts = [s.shape[0] for s in stacks]
     M = max(counts)
     if M > LPF_MAX_MASKS_WIDE:
         # The reference loops over every mask (V3:220), with no bound: beyond what one wide pass takes, the frames run once per group
         # of 256 masks and the per-detection results are put together
         return _run_frames_in_mask_groups(frames, stacks, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters,
-                                          v3_pipeline, device, ctx, group=LPF_MAX_MASKS_WIDE)
+                                          v3_pipeline, device, ctx, group=LPF_MAX_MASKS_WIDE, erosion_kernel_size=erosion_kernel_size)
     res, positions = _frames_pass(frames, stacks, M, camera, use_oriented, erode_iters, v3_pipeline, ctx)
     return [_frame_result(f, r, m, pos, min_points, gather_scans) for f, r, m, pos in zip(frames, res, counts, positions)]
 
@@ -1220,7 +1236,7 @@ def _frame_result(f, r, m, pos, min_points, gather_scans):
 
 
 def _run_frames_in_mask_groups(frames, stacks, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline,
-                               device, ctx, group=LPF_MAX_MASKS):
+                               device, ctx, group=LPF_MAX_MASKS, erosion_kernel_size=3):
     """run_frames for frames with more masks than one pass takes: one pass per group of ``group`` masks, results merged.  (With the
     default 32 every pass is the narrow path: the yardstick of the wide pass.)"""
     M = max(s.shape[0] for s in stacks)
@@ -1228,7 +1244,8 @@ def _run_frames_in_mask_groups(frames, stacks, TrVeloToRect, camera, depth_max, 
     for g0 in range(0, M, group):
         part = [FrameInputs(f.frame, f.points, s[g0:g0 + group], f.bboxes_3d, f.colors[g0:g0 + group], f.boxes_2d)
                 for f, s in zip(frames, stacks)]
-        res = run_frames(part, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline, device, ctx)
+        res = run_frames(part, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline, device, ctx,
+                         erosion_kernel_size=erosion_kernel_size)
         if merged is None:
             merged = res
             continue
@@ -1269,19 +1286,22 @@ def merge_inside_parts(a, b):
 
 
 def car_statistics_v3_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_oriented=True, erode_iters=0,
-                             v3_pipeline=False, device=0, ctx=None):
+                             v3_pipeline=False, device=0, ctx=None, erosion_kernel_size=3):
     """run_frames whose ``car_statistics`` carry V3's key set (V3:386-398, V3:413-425): next to the counts ``corners_velo`` (f64 [8,3]
     or None), ``inside_mask`` (bool [k], None for a car without a box) and ``car_points`` -- what calculate_car_point_statistics
     (style 'v3') returns for each frame, from run_frames' pass plus ONE lpf_inside_masks call for the whole batch: each list entry is
     tested against its car's best box on the GPU, instead of every car point against every box of the frame in a blocking call per
     frame.  The points are staged once for both.  Each frame's dict also has ``inside_parts`` -- part_idx int64 [sum k], part_xyz
     float32 [sum k, 3] (per car: the points inside its box first, then the others), off int64 [m + 1], n_inside int64 [m], matched
-    bool [m] -- which inside_outside_cloud_frames turns into V3's cloud.  Frames with more than 256 masks run once per group of 256."""
+    bool [m] -- which inside_outside_cloud_frames turns into V3's cloud.  Frames with more than 256 masks run once per group of 256.
+    ``erosion_kernel_size``: as in run_frames."""
+    erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     if not frames:
         return []
     ctx = ctx or get_context(device)
+    ctx.set_erosion_element(erosion_kernel_size)
     ctx.set_camera(TrVeloToRect, camera.K, camera.width, camera.height, 0.0, float(depth_max))
-    stacks, erode_iters, v3_pipeline = _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline)
+    stacks, erode_iters, v3_pipeline = _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline, erosion_kernel_size)
     counts = [s.shape[0] for s in stacks]
     M = max(counts)
     if M > LPF_MAX_MASKS_WIDE:
@@ -1289,7 +1309,8 @@ def car_statistics_v3_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_p
         for g0 in range(0, M, LPF_MAX_MASKS_WIDE):
             part = [FrameInputs(f.frame, f.points, s[g0:g0 + LPF_MAX_MASKS_WIDE], f.bboxes_3d, f.colors[g0:g0 + LPF_MAX_MASKS_WIDE], f.boxes_2d)
                     for f, s in zip(frames, stacks)]
-            res = car_statistics_v3_frames(part, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline, device, ctx)
+            res = car_statistics_v3_frames(part, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline, device, ctx,
+                                           erosion_kernel_size)
             if merged is None:
                 merged = res
                 continue
@@ -1368,14 +1389,16 @@ def _n_points(points):
 
 
 def run_frames_multicam(frames_per_cam, cams, depth_max=50.0, min_points=10, use_oriented=True, erode_iters=0, v3_pipeline=False,
-                        device=0, ctx=None, gather_scans=True):
+                        device=0, ctx=None, gather_scans=True, erosion_kernel_size=3):
     """run_frames for the same frames seen by up to four cameras, in ONE native pass (LpfContext.run_cams): every scan is staged and
     read once, however many cameras label it.  ``cams[c] = (TrVeloToRect, camera)``; ``frames_per_cam[c]`` is camera c's list of
     FrameInputs -- frame i of every camera carries the same points (the same frame id and point count; anything else raises
     ValueError), its own masks, colors and boxes (the boxes camera c sees).  Returns ``results[c][i]`` equal to
     ``run_frames(frames_per_cam[c], *cams[c], ...)[i]``, car_statistics and the lazy keys included.  A camera with a frame of more than
     32 masks goes through run_frames on its own (the pass takes a 32-bit label word per camera); the results are the same.  (Routing
-    such cameras through one LpfContext.run_cams_wide pass measured slower per frame than this)"""
+    such cameras through one LpfContext.run_cams_wide pass measured slower per frame than this)
+    ``erosion_kernel_size``: as in run_frames, for every camera."""
+    erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     C = len(cams)
     if not 1 <= C <= LPF_MAX_CAMS:
         raise ValueError("run_frames_multicam takes 1 to %d cameras, got %d" % (LPF_MAX_CAMS, C))
@@ -1392,16 +1415,17 @@ def run_frames_multicam(frames_per_cam, cams, depth_max=50.0, min_points=10, use
     if F == 0:
         return [[] for _ in range(C)]
     ctx = ctx or get_context(device)
+    ctx.set_erosion_element(erosion_kernel_size)
     results = [None] * C
     passes = []                                           # (camera, stacks, counts, M, erode_iters, v3_pipeline)
     for c, (T, camera) in enumerate(cams):
         # (masks of another size are resized -- and with the V3 block eroded -- at camera c's size: the context's camera for that)
         ctx.set_camera(T, camera.K, camera.width, camera.height, 0.0, float(depth_max))
-        stacks, er, v3 = _frame_mask_stacks(frames_per_cam[c], camera, ctx, erode_iters, v3_pipeline)
+        stacks, er, v3 = _frame_mask_stacks(frames_per_cam[c], camera, ctx, erode_iters, v3_pipeline, erosion_kernel_size)
         counts = [s.shape[0] for s in stacks]
         if max(counts) > LPF_MAX_MASKS:
             results[c] = run_frames(frames_per_cam[c], T, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline, device,
-                                    ctx, gather_scans)
+                                    ctx, gather_scans, erosion_kernel_size)
             continue
         passes.append((c, stacks, counts, max(counts), er, v3))
     if not passes:
@@ -1423,7 +1447,8 @@ def run_frames_multicam(frames_per_cam, cams, depth_max=50.0, min_points=10, use
 
 
 def stream_frames(scan_paths, inputs_for, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_oriented=True,
-                  erode_iters=0, v3_pipeline=False, device=0, n_buffers=3, max_points=None, box_paths=None, announce=None, gather=True):
+                  erode_iters=0, v3_pipeline=False, device=0, n_buffers=3, max_points=None, box_paths=None, announce=None, gather=True,
+                  erosion_kernel_size=3):
     """The frame loop with read-ahead: scans are read and moved to HBM by the native reader
     (lpf_reader_*) while earlier frames are processed; yields run_frames' dict per frame.
     ``inputs_for(i, path)`` returns ``(frame_id, masks, bboxes_3d, colors)`` or None to skip the
@@ -1434,7 +1459,9 @@ def stream_frames(scan_paths, inputs_for, TrVeloToRect, camera, depth_max=50.0, 
     ``scan.box_index`` / ``scan.boxes_cam0`` holding the result; the scans and box files of the NEXT frames are being fetched
     meanwhile.  ``announce(i, path)`` runs before the scan is waited for (the reference's "Processing frame" line).
     ``gather=False``: the consumer only reads the statistics (process_frames writes the CSV): ``points_valid`` / ``car_point_sets``
-    are not gathered from the scan before the reader recycles it (run_frames' ``gather_scans``)."""
+    are not gathered from the scan before the reader recycles it (run_frames' ``gather_scans``).  ``erosion_kernel_size``: as in
+    run_frames."""
+    erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     scan_paths = [os.fspath(p) for p in scan_paths]
     if max_points is None:
         sizes = [os.path.getsize(p) // 16 for p in scan_paths if os.path.isfile(p)]
@@ -1456,7 +1483,8 @@ def stream_frames(scan_paths, inputs_for, TrVeloToRect, camera, depth_max=50.0, 
                 continue
             frame_id, masks, boxes, colors = inputs
             yield run_frames([FrameInputs(frame_id, scan, masks, boxes, colors)], TrVeloToRect, camera, depth_max,
-                             min_points, use_oriented, erode_iters, v3_pipeline, device, ctx, gather_scans=gather)[0]
+                             min_points, use_oriented, erode_iters, v3_pipeline, device, ctx, gather_scans=gather,
+                             erosion_kernel_size=erosion_kernel_size)[0]
 
 
 # ---------------------------------------------------------------------------------------
@@ -1542,14 +1570,16 @@ def iter_frame_inputs(kitti360_path, seq, cam_id, segmenter, image_loader, camer
 
 def process_frames(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_path=None,
                    master_csv_path="results/master_car_statistics.csv", frames=None, batch_frames=32,
-                   erode_iters=0, v3_pipeline=False, device=0, timestamp=None, read_ahead=True):
+                   erode_iters=0, v3_pipeline=False, device=0, timestamp=None, read_ahead=True, erosion_kernel_size=3):
     """cvs_erosion.process_frames (cvs_erosion.py:298-379): writes the master CSV and prints the
     overall analysis.  ``segmenter(image) -> (img, masks, colors, boxes, confidences)`` is the
     YOLO stage (unchanged subsystem); pass masks it already eroded, or raw masks plus
     ``erode_iters=1, v3_pipeline=True`` to erode on the GPU.  ``read_ahead=True`` (the default) processes frame
     by frame, as the reference's loop does -- each frame's rows are appended before the next frame is looked at -- with the native
     reader fetching the next scans and parsing the next box files meanwhile; ``read_ahead=False`` reads ``batch_frames`` frames with
-    NumPy and runs them as one launch (same CSV; its lines are printed batch by batch)."""
+    NumPy and runs them as one launch (same CSV; its lines are printed batch by batch).  ``erosion_kernel_size``: the reference's
+    knob (cvs_erosion.py:77), as in run_frames -- 5 or 7 is the next experiment after the study's with / without erosion."""
+    erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     if segmenter is None:
         raise ValueError("process_frames needs the segmentation callable (YOLO stays outside this package)")
     root = kitti360_path or os.environ["KITTI360_DATASET"]
@@ -1577,13 +1607,15 @@ def process_frames(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_
 
         paths = [os.path.join(velo.raw3DPcdPath, "%010d.bin" % f) for f in todo]
         for r in stream_frames(paths, inputs_for, velo_to_rect, camera, 50.0, 10, True, erode_iters, v3_pipeline, device,
-                               box_paths=box_paths, announce=lambda i, path: print(f"\nProcessing frame {todo[i]}..."), gather=False):
+                               box_paths=box_paths, announce=lambda i, path: print(f"\nProcessing frame {todo[i]}..."), gather=False,
+                               erosion_kernel_size=erosion_kernel_size):
             if r["n_valid"] and r["car_statistics"]:
                 append_to_master_csv(r["car_statistics"], r["frame"], master_csv_path, timestamp)
         return analyze_master_csv(master_csv_path)
     items = iter_frame_inputs(root, seq, cam_id, segmenter, image_loader, camera, velo_to_cam, velo, frames, boxes_as_arrays=True)
     for batch in _batches(items, batch_frames):              # (one batch of scans and masks in memory at a time)
-        for r in run_frames(batch, velo_to_rect, camera, 50.0, 10, True, erode_iters, v3_pipeline, device):
+        for r in run_frames(batch, velo_to_rect, camera, 50.0, 10, True, erode_iters, v3_pipeline, device,
+                            erosion_kernel_size=erosion_kernel_size):
             if r["n_valid"] == 0:
                 continue
             if r["car_statistics"]:
@@ -1785,7 +1817,7 @@ def process_frames_depth_overlays(seq=0, cam_id=0, segmenter=None, image_loader=
 
 
 def process_frames_multicam(seq=0, cam_ids=(0, 1), segmenter=None, image_loader=None, kitti360_path=None, master_csv_paths=None,
-                            frames=None, erode_iters=0, v3_pipeline=False, device=0, timestamp=None):
+                            frames=None, erode_iters=0, v3_pipeline=False, device=0, timestamp=None, erosion_kernel_size=3):
     """process_frames for several perspective cameras of the rig at once: each scan is read once (the native read-ahead reader) and
     each box file parsed once; per frame the segmenter runs on every camera's image and ONE pass (run_frames_multicam) labels the scan
     in all of them.  Camera c's boxes are prepared with camera c's TrVeloToCam and visibility filter, as the reference does for
@@ -1793,7 +1825,9 @@ def process_frames_multicam(seq=0, cam_ids=(0, 1), segmenter=None, image_loader=
     ``master_csv_paths[c]`` (default ``results/master_car_statistics_cam<c>.csv``), byte for byte what
     ``process_frames(seq, cam_id=c, ...)`` writes with the same arguments and timestamp.  Skip rules per the reference: a frame without
     a box file (or with an empty one) is skipped for every camera -- the reference skips before it looks at an image; a missing image
-    or no detections skip only that camera's part of the frame.  Returns ``{cam_id: analyze_master_csv(path)}``."""
+    or no detections skip only that camera's part of the frame.  Returns ``{cam_id: analyze_master_csv(path)}``.
+    ``erosion_kernel_size``: as in run_frames."""
+    erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     if segmenter is None:
         raise ValueError("process_frames_multicam needs the segmentation callable (YOLO stays outside this package)")
     cam_ids = [int(c) for c in cam_ids]
@@ -1839,7 +1873,7 @@ def process_frames_multicam(seq=0, cam_ids=(0, 1), segmenter=None, image_loader=
                 continue
             order = list(inputs)
             res = run_frames_multicam([[inputs[c]] for c in order], [cams[c] for c in order], 50.0, 10, True, erode_iters, v3_pipeline,
-                                      device, ctx, gather_scans=False)
+                                      device, ctx, gather_scans=False, erosion_kernel_size=erosion_kernel_size)
             for c, r in zip(order, res):
                 r = r[0]
                 if r["n_valid"] and r["car_statistics"]:
@@ -1848,12 +1882,15 @@ def process_frames_multicam(seq=0, cam_ids=(0, 1), segmenter=None, image_loader=
 
 
 def process_frame_with_statistics(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_path=None,
-                                  visualizer=None, frames=None, erode_iters=0, v3_pipeline=False, device=0, v3_keys=False):
+                                  visualizer=None, frames=None, erode_iters=0, v3_pipeline=False, device=0, v3_keys=False,
+                                  erosion_kernel_size=3):
     """V3's entry point (V3:516-641) without the blocking Open3D window: per frame it prints the
     statistics table and hands (frame, car_statistics, points_valid, bg_assigned) to
     ``visualizer`` when one is given.  bg_assigned is V4's vectorised form of V3:609-616.  ``v3_keys=True``: the statistics carry
     V3's own key set -- corners_velo, inside_mask, car_points (car_statistics_v3_frames) -- and each result ``inside_parts``, from
-    which inside_outside_cloud_frames builds V3's cloud; the default leaves them out, as cvs_erosion's dicts do."""
+    which inside_outside_cloud_frames builds V3's cloud; the default leaves them out, as cvs_erosion's dicts do.
+    ``erosion_kernel_size``: as in run_frames (V3:55)."""
+    erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     if segmenter is None:
         raise ValueError("process_frame_with_statistics needs the segmentation callable")
     root = kitti360_path or os.environ["KITTI360_DATASET"]
@@ -1861,7 +1898,8 @@ def process_frame_with_statistics(seq=0, cam_id=0, segmenter=None, image_loader=
     items = collect_frame_inputs(root, seq, cam_id, segmenter, image_loader, camera, velo_to_cam, velo, frames)
     results = []
     run = car_statistics_v3_frames if v3_keys else run_frames
-    for r, item in zip(run(items, velo_to_rect, camera, 50.0, 10, True, erode_iters, v3_pipeline, device), items):
+    for r, item in zip(run(items, velo_to_rect, camera, 50.0, 10, True, erode_iters, v3_pipeline, device,
+                           erosion_kernel_size=erosion_kernel_size), items):
         if r["n_valid"] == 0:
             continue
         print_summary_statistics(r["car_statistics"])
