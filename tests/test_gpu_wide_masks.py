@@ -46,8 +46,8 @@ def _boxes(B, seed, calib):
     return S.synthetic_boxes(B, seed, np.asarray(calib["TrVeloToCam"]))[1]
 
 
-def _check(cal, res, pts_list, member, erode, corners, oriented, inst_full=True):
-    """res: run_wide's list; member: per frame uint8 [M,H,W] (the binarised masks, before erosion)."""
+def _check(cal, res, pts_list, member, erode, corners, oriented, inst_full=True, dmin=0.0, dmax=50.0):
+    """res: run_wide's list; member: per frame uint8 [M,H,W] (the binarised masks, before erosion); dmin, dmax: the camera's depth window."""
     W, H = cal["W"], cal["H"]
     for f, (r, pts, mem, cor) in enumerate(zip(res, pts_list, member, corners)):
         M = mem.shape[0]
@@ -61,7 +61,7 @@ def _check(cal, res, pts_list, member, erode, corners, oriented, inst_full=True)
         anyw = np.zeros(len(pts), bool)
         for w in range(LW):
             grp = mem[32 * w:32 * w + 32]
-            o = orc.run(pts, cal["T"], cal["K"], W, H, 0.0, 50.0, label_img=orc.pack_masks(grp, erode, H, W), M=len(grp),
+            o = orc.run(pts, cal["T"], cal["K"], W, H, dmin, dmax, label_img=orc.pack_masks(grp, erode, H, W), M=len(grp),
                         corners=cor, oriented=oriented, want_float=False)
             assert np.array_equal(r["label_words"][:, w], o["label_bits"]), "word %d" % w
             assert np.array_equal(r["u"], o["u"]) and np.array_equal(r["v"], o["v"])
