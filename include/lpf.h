@@ -57,7 +57,9 @@ extern "C" {
                                          nothing else changed)
                                       8 (continued): lpf_match2d_input, lpf_match2d_outputs, lpf_match_2d (added; nothing else changed)
                                       8 (continued): lpf_inside_input, lpf_inside_outputs, lpf_inside_masks (added; nothing else changed)
-                                      8 (continued): lpf_set_erosion_element (added; nothing else changed) */
+                                      8 (continued): lpf_set_erosion_element (added; nothing else changed)
+                                      8 (continued): lpf_box_points_input, lpf_box_points_outputs, lpf_box_points (added; nothing else
+                                         changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -618,6 +620,55 @@ typedef struct lpf_inside_outputs {      /* any pointer may be NULL: not wanted 
 } lpf_inside_outputs;
 int lpf_inside_masks(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_inside_input *in,
                      const lpf_inside_outputs *out);
+
+/* lpf_box_points: per-box LiDAR point counts, the ground-truth box of every valid point and the point-level confusion counts of a
+ * batch of F frames in ONE call, from what a run leaves behind.  count_mb[m][b] counts the points of mask m in box b; what no run
+ * returns is how many valid points box b holds at all -- the denominator of a recall.  This is the reference's box test,
+ * oriented_point_in_bbox (V3:167-208) or point_in_bbox (V3:143-164), on ALL of points_valid = points[valid_indices, :3] (V3:590-592)
+ * instead of on a car's points only.  The inputs are a run's compact outputs -- lpf_outputs' valid_idx / label_valid (LW = 1) or
+ * lpf_wide_outputs' valid_idx / label_valid_words -- the points are the run's points, and the boxes and the `oriented` flag are the ones
+ * in force (lpf_set_boxes*): the packed parameters the run counted with.  With the frame's valid points tested against each of its boxes:
+ *   box_points    per box: the valid points of the box's frame inside it.
+ *   box_labelled  per box: of those, the points with at least one label bit.  The test is the counting kernels' own (the float-bounds
+ *                 reject, then the fp64 slab test), so count_mb[m][b] <= box_labelled[b] <= box_points[b] bit for bit.
+ *   first_box     per valid point, parallel to valid_idx: the lowest index, within the frame's boxes, of a box that holds it, -1 if
+ *                 none: point-level ground truth.  Entries at or beyond n_valid[f] of a frame are NOT WRITTEN.
+ *   frame_counts  per frame {valid, in >= 1 box, labelled, labelled and in >= 1 box}: with "labelled" as the prediction and "in a box"
+ *                 as the truth, tp = [3], fp = [2] - [3], fn = [1] - [3], tn = [0] - [1] - [2] + [3].
+ * A box that filter_visible_bboxes dropped (lpf_set_boxes_cam0: its bounds are empty) keeps its position, counts 0 and is never a
+ * first_box.  A frame without boxes or without valid points is legal; F = 0 does nothing.  All counts are integer sums: the same bytes
+ * on every run.  The masks, boxes, rectangles, label state and camera of the other calls are left as they were.  Not capturable
+ * (LPF_ERR_STATE between lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it first launches what the pipeline owes
+ * (no host wait), then runs in order.  pts (pts_on_device), the lists (in->on_device) and the outputs (out->on_device) are each in host
+ * or device memory; frame_off is host memory.  With everything in device memory the call only enqueues work; with any host pointer it
+ * returns after one host wait, host outputs filled.
+ * Lists in host memory are checked; lists in device memory are not, but nothing is read or written out of bounds whatever they hold:
+ * n_valid[f] is clamped to [0, N_f]; an entry whose index is outside the frame's points counts in no box, has first_box -1 and is left
+ * out of frame_counts[f][1..3].
+ * LPF_ERR_ARG: NULL in / out, F < 0, frame_off NULL or bad, LW out of range, valid_idx or n_valid NULL with F > 0, pts NULL with points;
+ * host lists: n_valid[f] outside [0, N_f], an index outside [0, N_f), indices that do not strictly ascend (the message names frame and
+ * entry).  LPF_ERR_STATE: no boxes in force, or boxes for another number of frames.
+ * Device memory: 24 bytes per frame; 16 bytes per point for host points; (8 + 4 LW) Ntot + 8 F bytes for host lists and
+ * 8 Btot + 4 Ntot + 32 F for host outputs (grow-only, allocated on first use).  Device outputs are summed in place: no scratch. */
+typedef struct lpf_box_points_input {
+    const int64_t  *valid_idx;          /* [Ntot] as lpf_outputs / lpf_wide_outputs write it: frame f's at valid_idx[frame_off[f] ...],
+                                           n_valid[f] entries, indices within the frame, ascending */
+    const int64_t  *n_valid;            /* [F] */
+    const uint32_t *label_valid_words;  /* [Ntot][LW] compact, frame f's rows from row frame_off[f], in valid_idx order: lpf_wide_outputs'
+                                           label_valid_words, or lpf_outputs' label_valid with LW = 1; NULL or LW = 0: nothing is labelled */
+    int32_t LW;                         /* 0 .. LPF_MAX_MASKS_WIDE / 32 */
+    int32_t on_device;                  /* the three arrays are device memory, lent until the call's work has completed */
+} lpf_box_points_input;
+typedef struct lpf_box_points_outputs { /* any pointer may be NULL: not wanted */
+    int32_t *box_points;                /* [Btot] valid points of the box's frame inside the box */
+    int32_t *box_labelled;              /* [Btot] of those, points with at least one label bit */
+    int32_t *first_box;                 /* [Ntot] compact, parallel to valid_idx: lowest index, within the frame's given boxes, of a box
+                                           that holds the point; -1 if none.  Entries at or beyond n_valid[f] of a frame are not written */
+    int64_t *frame_counts;              /* [F][4] {valid, in >= 1 box, labelled, labelled and in >= 1 box} */
+    int32_t  on_device, reserved;
+} lpf_box_points_outputs;
+int lpf_box_points(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
+                   const lpf_box_points_input *in, const lpf_box_points_outputs *out);
 
 /* cv2.resize(mask.astype(np.uint8), (camera.width, camera.height)) (V3:222; INTER_LINEAR, the default) for masks that do not arrive at
  * the camera's size (the reference's scripts all pass retina_masks=True, so theirs do): n planes [h][w] of uint8 -> n planes [H][W]

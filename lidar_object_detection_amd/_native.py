@@ -104,6 +104,17 @@ class InsideOutputs(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class BoxPointsInput(ctypes.Structure):
+    """lpf_box_points_input (include/lpf.h): a run's compact valid indices and label words, for lpf_box_points"""
+    _fields_ = [("valid_idx", _P), ("n_valid", _P), ("label_valid_words", _P), ("LW", ctypes.c_int32), ("on_device", ctypes.c_int32)]
+
+
+class BoxPointsOutputs(ctypes.Structure):
+    """lpf_box_points_outputs (include/lpf.h): per box the valid points it holds, per valid point its first box, per frame four counts"""
+    _fields_ = [("box_points", _P), ("box_labelled", _P), ("first_box", _P), ("frame_counts", _P), ("on_device", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 LPF_MAX_CAMS = 4                        # lpf_run_cams / lpf_run_cams_wide: cameras of one pass
 
 
@@ -272,6 +283,7 @@ def load(path=None):
     lib.lpf_depth_overlays.argtypes = [_P, ctypes.c_int, ctypes.POINTER(DepthOverlayInput), ctypes.POINTER(DepthOverlayOutputs)]
     lib.lpf_match_2d.argtypes = [_P, ctypes.c_int, ctypes.POINTER(Match2dInput), ctypes.POINTER(Match2dOutputs)]
     lib.lpf_inside_masks.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(InsideInput), ctypes.POINTER(InsideOutputs)]
+    lib.lpf_box_points.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(BoxPointsInput), ctypes.POINTER(BoxPointsOutputs)]
     lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_cams_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(WideOutputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
@@ -309,7 +321,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
             "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d",
-            "lpf_inside_masks", "lpf_set_erosion_element")
+            "lpf_inside_masks", "lpf_set_erosion_element", "lpf_box_points")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -1578,6 +1590,105 @@ class LpfContext:
                 self.release_to_stream(ts)
             else:
                 self._check(self._lib.lpf_inside_masks(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
+        return res
+
+    BOX_POINTS_WANT = ("box_points", "box_labelled", "first_box", "frame_counts")
+    _BOX_POINTS_DTYPE = {"box_points": "int32", "box_labelled": "int32", "first_box": "int32", "frame_counts": "int64"}
+
+    @staticmethod
+    def box_points_batch(valid_idx, n_valid, label_valid, Ntot, F):
+        """The list arrays of box_points checked against a batch of F frames and Ntot points: (on_device, LW).  ValueError for host
+        arrays mixed with GPU tensors, shapes that are not [Ntot], [F] and [Ntot] or [Ntot, LW] with 1 <= LW <= 8, and GPU tensors
+        of another dtype than int64, int64 and int32 / uint32."""
+        every = [a for a in (valid_idx, n_valid, label_valid) if a is not None]
+        n_dev = sum(1 for a in every if _is_torch(a) and a.is_cuda)
+        if n_dev not in (0, len(every)):
+            raise ValueError("box_points: host arrays and GPU tensors are mixed (%d of %d list arrays are on the GPU)" % (n_dev, len(every)))
+        shp = [tuple(a.shape) for a in (valid_idx, n_valid)]
+        if shp[0] != (Ntot,) or shp[1] != (F,):
+            raise ValueError("box_points: valid_idx [Ntot] and n_valid [F] of %d points in %d frames, got %s" % (Ntot, F, shp))
+        LW = 0
+        if label_valid is not None:
+            ls = tuple(label_valid.shape)
+            LW = 1 if len(ls) == 1 else (ls[1] if len(ls) == 2 else -1)
+            if ls[:1] != (Ntot,) or not 1 <= LW <= LPF_MAX_MASKS_WIDE // 32:
+                raise ValueError("box_points: label_valid [Ntot] or [Ntot, LW] with 1 <= LW <= %d for %d points, got %s"
+                                 % (LPF_MAX_MASKS_WIDE // 32, Ntot, ls))
+        if n_dev:
+            names = [str(a.dtype).replace("torch.", "") for a in every]
+            if names[:2] != ["int64", "int64"] or (len(names) == 3 and names[2] not in ("int32", "uint32")):
+                raise ValueError("box_points: GPU list arrays must be int64, int64 and int32 / uint32, got %s" % names)
+        return n_dev > 0, LW
+
+    def box_points(self, frames, valid_idx, n_valid, label_valid=None, want=BOX_POINTS_WANT, out=None, staged=None):
+        """Per-box LiDAR point counts, the first box of every valid point and the point-level confusion counts of a batch of frames
+        in ONE native call (lpf_box_points), from what a run on the same frames returned: ``valid_idx`` int64 [Ntot] (frame f's
+        entries from the frame's first point on, as the runs write it), ``n_valid`` int64 [F] and ``label_valid`` uint32 [Ntot]
+        (run_batch) or [Ntot, LW] (run_wide), or None: nothing is labelled -- all host arrays or all GPU tensors.  frames: as
+        run_batch's (or ``staged=stage_points(frames)``).  The boxes are the ones in force.  ``want`` picks the outputs
+        (BOX_POINTS_WANT): "box_points" and "box_labelled" int32 [Btot], "first_box" int32 [Ntot] parallel to valid_idx (-1: in no
+        box), "frame_counts" int64 [F, 4] = {valid, in a box, labelled, labelled and in a box}.  Returns a dict of them: NumPy arrays
+        after one host wait, or GPU tensors in torch's stream order (the call only enqueues work).  Entries of first_box the call
+        does not write (beyond a frame's n_valid) are -1, or what ``out`` -- a dict of the caller's own arrays under the same names
+        -- held."""
+        want = tuple(want)
+        bad = [w for w in want if w not in self.BOX_POINTS_WANT]
+        if bad or not want:
+            raise ValueError("box_points: want is a selection of %s, got %r" % (self.BOX_POINTS_WANT, want))
+        off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the call returns)
+        F, Ntot = len(off) - 1, int(off[-1])
+        dev, LW = self.box_points_batch(valid_idx, n_valid, label_valid, Ntot, F)
+        if self.box_off is None or len(self.box_off) - 1 != F:
+            raise ValueError("box_points: boxes in force for %s frames, points of %d (set_boxes* comes first)"
+                             % ("no" if self.box_off is None else len(self.box_off) - 1, F))
+        Btot = int(self.box_off[-1])
+        shape = {"box_points": (Btot,), "box_labelled": (Btot,), "first_box": (Ntot,), "frame_counts": (F, 4)}
+        inp, o = BoxPointsInput(), BoxPointsOutputs()
+        inp.LW = LW
+        res = {}
+        lists = [valid_idx, n_valid] + ([label_valid] if label_valid is not None else [])
+        if dev:
+            import torch
+            d = valid_idx.device
+            arrs = [a.contiguous() for a in lists]
+            for w in want:
+                if out is not None and w in out:
+                    res[w] = out[w]
+                elif w == "first_box":
+                    res[w] = torch.full(shape[w], -1, dtype=torch.int32, device=d)
+                else:
+                    res[w] = torch.zeros(shape[w], dtype=getattr(torch, self._BOX_POINTS_DTYPE[w]), device=d)
+                if tuple(res[w].shape) != shape[w]:
+                    raise ValueError("box_points: out[%r] must be %s, got %s" % (w, shape[w], tuple(res[w].shape)))
+                _dev_ptr(res[w], self._BOX_POINTS_DTYPE[w])
+            if Ntot == 0:                                  # (an empty tensor has no address, and the call wants one)
+                arrs[0] = torch.zeros(1, dtype=torch.int64, device=d)
+            ptr = lambda a: a.data_ptr() if a.numel() else None
+            inp.on_device = o.on_device = 1
+        else:
+            arrs = [np.ascontiguousarray(a, dtype=t) for a, t in zip(lists, (np.int64, np.int64, np.uint32))]
+            for w in want:
+                if out is not None and w in out:
+                    res[w] = out[w]
+                else:
+                    res[w] = np.full(shape[w], -1, np.int32) if w == "first_box" else np.zeros(shape[w], self._BOX_POINTS_DTYPE[w])
+                if res[w].shape != shape[w] or res[w].dtype != np.dtype(self._BOX_POINTS_DTYPE[w]) or not res[w].flags.c_contiguous:
+                    raise ValueError("box_points: out[%r] must be a contiguous %s array %s" % (w, self._BOX_POINTS_DTYPE[w], shape[w]))
+            if Ntot == 0:
+                arrs[0] = np.zeros(1, np.int64)
+            ptr = lambda a: a.ctypes.data if a.size else None
+        inp.valid_idx, inp.n_valid = ptr(arrs[0]), ptr(arrs[1])
+        inp.label_valid_words = ptr(arrs[2]) if len(arrs) == 3 else None
+        for w in want:
+            setattr(o, w, ptr(res[w]))
+        if F:
+            if dev:
+                ts = torch.cuda.current_stream(d).cuda_stream
+                self.wait_for_stream(ts)                    # the lists and the outputs' memory belong to torch's stream
+                self._check(self._lib.lpf_box_points(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
+                self.release_to_stream(ts)
+            else:
+                self._check(self._lib.lpf_box_points(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
         return res
 
     def run_cams_wide(self, frames, cams, want_uv=True, want_float=False, want_lists=True, want_valid_uv=False, inst_cap=None,

@@ -10,6 +10,7 @@
 #include "lpf_depth_overlays.hip.h"
 #include "lpf_match2d.hip.h"
 #include "lpf_inside.hip.h"
+#include "lpf_box_points.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -220,6 +221,8 @@ struct lpf_ctx {
     struct Match2d { DevBuf tab, in, out; } m2d;
     // lpf_inside_masks: the frame table, staged host points, staged host lists, staged host outputs (grow-only, allocated on first use)
     struct Inside { DevBuf tab, pts, in, out; } insd;
+    // lpf_box_points: the frame table, staged host points, staged host lists, staged host outputs (grow-only, allocated on first use)
+    struct BoxPoints { DevBuf tab, pts, in, out; } bpts;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -1450,7 +1453,7 @@ void lpf_destroy(lpf_ctx *c)
         release(*b);
     for (DevBuf *b : {&c->dovl.in, &c->dovl.out, &c->m2d.tab, &c->m2d.in, &c->m2d.out})
         release(*b);
-    for (DevBuf *b : {&c->insd.tab, &c->insd.pts, &c->insd.in, &c->insd.out})
+    for (DevBuf *b : {&c->insd.tab, &c->insd.pts, &c->insd.in, &c->insd.out, &c->bpts.tab, &c->bpts.pts, &c->bpts.in, &c->bpts.out})
         release(*b);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
     for (DevBuf *b : all) release(*b);
@@ -2935,6 +2938,108 @@ int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
             if (Q.inside) LPF_HIP(c, hipMemcpyAsync(out->inside + r, Q.inside + r, (size_t)n, hipMemcpyDeviceToHost, c->stream));
             if (Q.part_idx) LPF_HIP(c, hipMemcpyAsync(out->part_idx + r, Q.part_idx + r, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
             if (Q.part_xyz) LPF_HIP(c, hipMemcpyAsync(out->part_xyz + r * 3, Q.part_xyz + r * 3, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    if (host_out || host_in || pts_in) LPF_HIP(c, host_wait(c));    // host outputs filled, host inputs free to be reused
+    return LPF_OK;
+}
+
+// ---- lpf_box_points (include/lpf.h): per-box point counts, first boxes and point-level confusion counts, kernel in lpf_box_points.hip.h --
+// One launch per 65535 frames on the box tables in force, into outputs zeroed in stream order.  Host arrays are staged whole: the points,
+// the three list arrays in one buffer, the four outputs in another; of a staged first_box only the first n_valid[f] entries of a frame
+// go back to a host caller, so the rest of the caller's array stays as it was (with lists in device memory the host does not know
+// n_valid: the caller's first_box goes up first and comes back whole).
+#define LPF_BP_MAX_FRAMES 65535             // frames per launch: the grid's y
+
+int lpf_box_points(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_box_points_input *in,
+                   const lpf_box_points_outputs *out)
+{
+    int rc;
+    if ((rc = enter(c, "lpf_box_points", false))) return rc;
+    if (!in || !out || F < 0 || !frame_off)
+        return fail(c, LPF_ERR_ARG, "box_points: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
+    const int LW = in->LW;
+    if (LW < 0 || LW > LPF_MAX_MASKS_WIDE / 32)
+        return fail(c, LPF_ERR_ARG, "box_points: LW=%d label words per point, lpf_box_points takes 0 .. LPF_MAX_MASKS_WIDE / 32 = %d", LW,
+                    LPF_MAX_MASKS_WIDE / 32);
+    if (F == 0) return LPF_OK;
+    if (!in->valid_idx || !in->n_valid)
+        return fail(c, LPF_ERR_ARG, "box_points: valid_idx=%p n_valid=%p (both are required)", (const void *)in->valid_idx, (const void *)in->n_valid);
+    if ((rc = check_frames(c, "box_points", pts, frame_off, F, 0))) return rc;
+    lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
+    if (BX.F == 0) return fail(c, LPF_ERR_STATE, "box_points: no boxes in force (lpf_set_boxes* comes first)");
+    if (BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, box_points has %d", BX.F, F);
+    const bool host_in = !in->on_device, host_out = !out->on_device;
+    int64_t most = 0;                                       // entries of the frame with the most: the grid's x
+    for (int f = 0; f < F; ++f) {
+        const int64_t N = frame_off[f + 1] - frame_off[f];
+        if (!host_in) { most = std::max(most, N); continue; }    // (lists in device memory: not known here; the kernel clamps n_valid to N)
+        const int64_t n = in->n_valid[f];
+        if (n < 0 || n > N) return fail(c, LPF_ERR_ARG, "box_points: frame %d: n_valid=%lld, the frame has %lld points", f, (long long)n, (long long)N);
+        const int64_t *v = in->valid_idx + frame_off[f];
+        for (int64_t e = 0; e < n; ++e) {
+            if (v[e] < 0 || v[e] >= N)
+                return fail(c, LPF_ERR_ARG, "box_points: frame %d entry %lld: index %lld, the frame has %lld points", f, (long long)e, (long long)v[e], (long long)N);
+            if (e > 0 && v[e] <= v[e - 1])
+                return fail(c, LPF_ERR_ARG, "box_points: frame %d entry %lld: index %lld does not ascend (the entry before is %lld)", f, (long long)e,
+                            (long long)v[e], (long long)v[e - 1]);
+        }
+        most = std::max(most, n);
+    }
+    if (!out->box_points && !out->box_labelled && !out->first_box && !out->frame_counts) return LPF_OK;     // nothing is wanted
+    // a software-pipelined context launches what it owes first (no host wait) -- the box tables of the set in force among it: everything
+    // below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+
+    lpf_ctx::BoxPoints &D = c->bpts;
+    const size_t Ntot = (size_t)frame_off[F], Btot = (size_t)BX.box_off[F];
+    std::vector<LpfBpFrame> tab((size_t)F);
+    for (int f = 0; f < F; ++f) {
+        LpfBpFrame &t = tab[(size_t)f];
+        t.pt_off = (long long)frame_off[f]; t.N = (int)(frame_off[f + 1] - frame_off[f]);
+        t.box_off = BX.box_off[f]; t.B = BX.box_off[f + 1] - BX.box_off[f]; t.pad = 0;
+    }
+    if ((rc = upload_table(c, D.tab, tab.data(), (size_t)F))) return rc;
+
+    LpfBpParams Q;
+    memset(&Q, 0, sizeof Q);
+    Q.frames = (const LpfBpFrame *)D.tab.p;
+    Q.boxp = (const double *)BX.boxp.p; Q.boxq = (const float *)BX.boxq.p;
+    const bool labels = in->label_valid_words && LW > 0;
+    Q.LW = labels ? LW : 0;
+    bool pts_in = false;
+    if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, 0, Ntot, Ntot, &Q.pts, &pts_in))) return rc;
+    Stage I(host_in), O(host_out);
+    I.add(Q.valid_idx, in->valid_idx, 8, Ntot);
+    I.add(Q.n_valid, in->n_valid, 8, (size_t)F);
+    I.add(Q.labels, labels ? in->label_valid_words : nullptr, 4, Ntot * (size_t)LW);
+    if ((rc = I.commit(c, D.in)) || (rc = I.in(c))) return rc;
+    O.add(Q.box_points, out->box_points, 4, Btot);
+    O.add(Q.box_labelled, out->box_labelled, 4, Btot);
+    O.add(Q.first_box, out->first_box, 4, Ntot);
+    O.add(Q.frame_counts, out->frame_counts, 32, (size_t)F);
+    if ((rc = O.commit(c, D.out))) return rc;
+    // the sums are added into zeroed outputs; a staged first_box whose written part the host cannot size starts as the caller's
+    if (Q.box_points && Btot) LPF_HIP(c, hipMemsetAsync(Q.box_points, 0, Btot * 4, c->stream));
+    if (Q.box_labelled && Btot) LPF_HIP(c, hipMemsetAsync(Q.box_labelled, 0, Btot * 4, c->stream));
+    if (Q.frame_counts) LPF_HIP(c, hipMemsetAsync(Q.frame_counts, 0, (size_t)F * 32, c->stream));
+    const bool first_whole = host_out && !host_in && out->first_box && Ntot;
+    if (first_whole) LPF_HIP(c, hipMemcpyAsync(Q.first_box, out->first_box, Ntot * 4, hipMemcpyHostToDevice, c->stream));
+    const unsigned gx = (unsigned)std::max<int64_t>((most + LPF_BP_CHUNK - 1) / LPF_BP_CHUNK, 1);     // (a block per frame writes frame_counts[f][0])
+    for (int f0 = 0; f0 < F; f0 += LPF_BP_MAX_FRAMES) {
+        Q.f0 = f0;
+        const dim3 g(gx, (unsigned)std::min(F - f0, LPF_BP_MAX_FRAMES));
+        with_flag(BX.oriented != 0, [&](auto oriented) {
+            hipLaunchKernelGGL((lpf_box_points_kernel<decltype(oriented)::value>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
+        });
+        LPF_HIP(c, hipGetLastError());
+    }
+    if (host_out) {
+        // box_points | box_labelled | first_box | frame_counts
+        if ((rc = O.back(c, {{0, Btot}, {0, Btot}, {0, first_whole ? Ntot : 0}, {0, (size_t)F}}))) return rc;
+        for (int f = 0; host_in && out->first_box && f < F; ++f) {
+            const size_t n = (size_t)in->n_valid[f], r = (size_t)frame_off[f];
+            if (n) LPF_HIP(c, hipMemcpyAsync(out->first_box + r, Q.first_box + r, n * 4, hipMemcpyDeviceToHost, c->stream));
         }
     }
     if (host_out || host_in || pts_in) LPF_HIP(c, host_wait(c));    // host outputs filled, host inputs free to be reused

@@ -1384,6 +1384,101 @@ def inside_outside_cloud_frames(results, background=(0.5, 0.5, 0.5)):
     return clouds
 
 
+# ---------------------------------------------------------------------------------------
+# point-level recall: how many of the LiDAR points in a car's annotated box does its mask still cover?
+# ---------------------------------------------------------------------------------------
+RECALL_COLUMNS = CSV_COLUMNS + ("bbox_lidar_points", "recall_percentage")
+
+
+def point_recall_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_oriented=True, erode_iters=0,
+                        v3_pipeline=False, device=0, erosion_kernel_size=3, ctx=None):
+    """run_frames plus the recall side of its statistics, from run_frames' pass and ONE lpf_box_points call for the whole batch (the
+    points are staged once for both): the box test on ALL valid points of a frame, not only on the masked ones.  Each frame's dict
+    is run_frames' plus
+      ``box_points`` / ``box_labelled``  int32, one entry per box of the frame's list, at the positions ``matched_bbox_id`` refers
+                           to: the valid points inside the box, and those of them some mask covers (0 for a list entry without corners);
+      ``first_box``        int32, parallel to ``valid_indices``: the first box of the list that holds the point, -1 if none;
+      ``point_confusion``  {"tp", "fp", "fn", "tn"} of "car vs. not car" per valid point: tp labelled and in a box, fp labelled and in
+                           no box, fn unlabelled and in a box, tn neither;
+    and in every ``car_statistics`` dict ``bbox_lidar_points`` (box_points of the matched box, 0 for an unmatched car) and
+    ``recall_percentage`` (points_inside_bbox / bbox_lidar_points * 100, 0.0 for an unmatched car).  Frames with more than 256 masks
+    run once per group of 256; a point counts as labelled when any group labels it.  ``erosion_kernel_size``: as in run_frames."""
+    erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
+    if not frames:
+        return []
+    ctx = ctx or get_context(device)
+    ctx.set_erosion_element(erosion_kernel_size)
+    ctx.set_camera(TrVeloToRect, camera.K, camera.width, camera.height, 0.0, float(depth_max))
+    stacks, erode_iters, v3_pipeline = _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline, erosion_kernel_size)
+    M = max(s.shape[0] for s in stacks)
+    staged = ctx.stage_points([f.points for f in frames])    # one copy of the batch's points for the passes and the box test
+    off = staged[0]
+    valid, n_valid, labels, out = np.zeros(int(off[-1]), np.int64), np.zeros(len(frames), np.int64), None, None
+    G = LPF_MAX_MASKS_WIDE
+    for g0 in range(0, max(M, 1), G):
+        part = frames if M <= G else [FrameInputs(f.frame, f.points, None, f.bboxes_3d, f.colors[g0:g0 + G], f.boxes_2d) for f in frames]
+        pstacks = stacks if M <= G else [s[g0:g0 + G] for s in stacks]
+        counts = [s.shape[0] for s in pstacks]
+        res, positions = _frames_pass(part, pstacks, max(counts), camera, use_oriented, erode_iters, v3_pipeline, ctx, staged=staged)
+        # the compact lists of the pass as the box test takes them (copies: the pass's arrays may live in buffers the context reuses)
+        for i, r in enumerate(res):
+            a, n = int(off[i]), int(r["n_valid"])
+            lab = r["label_valid"] if "label_valid" in r else r["label_valid_words"]
+            if M > G:                                        # several groups: one word per point, non-zero where any group labels it
+                lab = (lab != 0) if lab.ndim == 1 else (lab != 0).any(axis=1)
+            if labels is None:
+                labels = np.zeros((len(valid),) + tuple(np.shape(lab)[1:]), np.uint32)
+            if g0 == 0:
+                valid[a:a + n], n_valid[i] = r["valid_idx"], n
+                labels[a:a + n] = lab
+            else:
+                labels[a:a + n] |= lab.astype(np.uint32)
+        got = [_frame_result(f, r, m, pos, min_points, True) for f, r, m, pos in zip(part, res, counts, positions)]
+        if out is None:
+            out = got
+            continue
+        for acc, r in zip(out, got):
+            acc["car_point_sets"] += r["car_point_sets"]
+            acc["bg_assigned"] = acc["bg_assigned"] | r["bg_assigned"]
+            acc["count_mb"] = np.concatenate([acc["count_mb"], r["count_mb"]], axis=0)
+            for d in r["car_statistics"]:
+                d["car_id"] += g0                            # car ids count the detections of the whole frame (V3:330)
+            acc["car_statistics"] += r["car_statistics"]
+    bp = ctx.box_points(None, valid, n_valid, labels, staged=staged)
+    box_off = ctx.box_off
+    for i, (f, fr, pos) in enumerate(zip(frames, out, positions)):
+        b0, b1, a, n = int(box_off[i]), int(box_off[i + 1]), int(off[i]), int(n_valid[i])
+        pos = np.asarray(pos, np.int64)
+        per_box = {}
+        for k in ("box_points", "box_labelled"):
+            per_box[k] = np.zeros(len(f.bboxes_3d), np.int32)
+            per_box[k][pos] = bp[k][b0:b1]
+            fr[k] = per_box[k]
+        first = bp["first_box"][a:a + n]
+        fr["first_box"] = np.where(first >= 0, pos[np.maximum(first, 0)] if len(pos) else -1, -1).astype(np.int32)
+        valid_n, boxed, lab, both = (int(x) for x in bp["frame_counts"][i])
+        fr["point_confusion"] = {"tp": both, "fp": lab - both, "fn": boxed - both, "tn": valid_n - boxed - lab + both}
+        for d in fr["car_statistics"]:
+            if d["matched_bbox_id"] >= 0:
+                d["bbox_lidar_points"] = int(per_box["box_points"][d["matched_bbox_id"]])
+                d["recall_percentage"] = d["points_inside_bbox"] / d["bbox_lidar_points"] * 100
+            else:
+                d["bbox_lidar_points"], d["recall_percentage"] = 0, 0.0
+    return out
+
+
+def recall_rows(results, timestamp=None):
+    """One row per car of point_recall_frames' results: csv_rows' columns plus ``bbox_lidar_points`` and ``recall_percentage``
+    (RECALL_COLUMNS; the percentage rounded to two places like the others).  csv_rows and the master CSV's schema stay as they are."""
+    rows = []
+    for r in results:
+        for row, s in zip(csv_rows(r["car_statistics"], r["frame"], timestamp), r["car_statistics"]):
+            row["bbox_lidar_points"] = s["bbox_lidar_points"]
+            row["recall_percentage"] = round(s["recall_percentage"], 2)
+            rows.append(row)
+    return rows
+
+
 def _n_points(points):
     return len(points.points) if isinstance(points, Scan) else int(points.shape[0])
 
