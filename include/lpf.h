@@ -59,6 +59,8 @@ extern "C" {
                                       8 (continued): lpf_inside_input, lpf_inside_outputs, lpf_inside_masks (added; nothing else changed)
                                       8 (continued): lpf_set_erosion_element (added; nothing else changed)
                                       8 (continued): lpf_box_points_input, lpf_box_points_outputs, lpf_box_points (added; nothing else
+                                         changed)
+                                      8 (continued): lpf_box_views_input, lpf_box_views_outputs, lpf_box_views (added; nothing else
                                          changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
@@ -669,6 +671,61 @@ typedef struct lpf_box_points_outputs { /* any pointer may be NULL: not wanted *
 } lpf_box_points_outputs;
 int lpf_box_points(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
                    const lpf_box_points_input *in, const lpf_box_points_outputs *out);
+
+/* lpf_box_views: secondtest.py's camera-view filter (is_bbox_in_camera_view / filter_bboxes_in_camera_view, secondtest.py:277-419) and
+ * V5's detailed box projection (project_3d_bbox_to_2d, V5:215-252) for every box of a batch of F frames in ONE call.  Frame f owns
+ * boxes box_off[f] .. box_off[f + 1] of the [Btot] arrays.  K, W and H are lpf_set_camera's (LPF_ERR_STATE without one).  The
+ * arithmetic is the reference's, statement for statement, every operation separate:
+ *   cam2image on the raw cam-0 corners as lpf_prepare_boxes does it: k-ordered fma chains over K, d == 0 -> -1e-6,
+ *   u = rint(qx / |d|), v = rint(qy / |d|) (half to even)
+ *   near = depth_lo <= d <= depth_hi (closed);  corners_near = its count;  corners_in_view = near corners with 0 <= u < W, 0 <= v < H
+ *   reason, in the reference's order: corners_near == 0 -> 2 (all_behind_camera);  corners_in_view < min_points_in_view and the near
+ *   corners' pixel box misses the image (x1 < 0 or x0 >= W or y1 < 0 or y0 >= H) -> 3 (no_intersection);  corners_near >= 2 and
+ *   (umax - umin) * (vmax - vmin) < min_area -> 4 (too_small);  else 0 (valid).  keep = (reason == 0).  Codes 1 (no_corners) and 5
+ *   (error) are the host's: such boxes are not part of the call
+ *   avg_depth = np.mean of the near depths in corner order, in NumPy's summation order (fewer than 8 values: left to right from 0.0;
+ *   exactly 8: ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7))), then one division by the count; 0 when there is none
+ *   near_bbox2d = {min u, min v, max u, max v} of the near corners;  front / bbox2d / front_avg_depth: the same over the corners with
+ *   d > 0 -- front and bbox2d bit-identical to lpf_prepare_boxes' (an empty set leaves the sentinels {1e300, 1e300, -1e300, -1e300} in
+ *   either pixel box).  V5's center, size and area are exact integer arithmetic on bbox2d: the host derives them
+ *   kept_pos[b] = the rank of box b among the kept boxes of its frame, in list order (the index space in which secondtest's matcher
+ *   reports boxes), -1 for a dropped box;  frame_counts[f][r] = boxes of frame f with reason r ([0]: kept; [1] and [5] are 0)
+ *   corners_velo = transform_bboxes_to_velodyne's (T_cam_to_velo . [c 1])[:3] as lpf_prepare_boxes has it; needs T_cam_to_velo
+ * Device corners are not validated: nothing is read or written out of bounds whatever they hold; with non-finite corners the values
+ * are unspecified.  A frame may have no boxes (its frame_counts are zeros); F = 0 does nothing.  Leaves camera, masks and boxes in
+ * force as they were.  Not capturable (LPF_ERR_STATE between lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it
+ * first launches what the pipeline owes (no host wait).  With every pointer device memory the call only enqueues work on the
+ * context's stream (the frame table goes through the pinned upload ring): no host wait, and no allocation after the first call of a
+ * shape; otherwise it returns after one host wait, with host outputs filled.
+ * LPF_ERR_ARG: NULL in / out, F < 0, NULL box_off, box_off[0] < 0, a decreasing box_off, NULL corners_cam0 with boxes, corners_velo
+ * without T_cam_to_velo, non-finite depth_lo / depth_hi / min_area, min_points_in_view outside 0 .. 8.
+ * Device memory: 8 bytes per frame; host inputs and outputs are staged frame range by frame range, each range within 256 MiB of
+ * scratch, or one frame when a single frame needs more. */
+typedef struct lpf_box_views_input {
+    const double  *corners_cam0;        /* [Btot][8][3] */
+    const int32_t *box_off;             /* [F + 1], host memory */
+    const double  *T_cam_to_velo;       /* [16] row-major, host memory; may be NULL unless corners_velo is asked for */
+    int32_t        on_device;           /* corners_cam0 is device memory, lent until the call's work has completed */
+    int32_t        min_points_in_view;  /* secondtest.py: 4 */
+    double         depth_lo, depth_hi;  /* secondtest.py: 0.1, 100 */
+    double         min_area;            /* secondtest.py: 100 */
+} lpf_box_views_input;
+typedef struct lpf_box_views_outputs {  /* any pointer may be NULL: only what is asked for is computed and stored */
+    uint8_t *keep;                      /* [Btot] */
+    int32_t *reason;                    /* [Btot] 0 valid, 2 all_behind_camera, 3 no_intersection, 4 too_small */
+    int32_t *corners_in_view;           /* [Btot] */
+    int32_t *corners_near;              /* [Btot] the reference's corners_with_valid_depth */
+    double  *avg_depth;                 /* [Btot] */
+    double  *near_bbox2d;               /* [Btot][4] */
+    int32_t *front;                     /* [Btot] */
+    double  *bbox2d;                    /* [Btot][4] */
+    double  *front_avg_depth;           /* [Btot] */
+    int32_t *kept_pos;                  /* [Btot] */
+    int32_t *frame_counts;              /* [F][6] */
+    double  *corners_velo;              /* [Btot][8][3] */
+    int32_t  on_device, reserved;
+} lpf_box_views_outputs;
+int lpf_box_views(lpf_ctx *ctx, int F, const lpf_box_views_input *in, const lpf_box_views_outputs *out);
 
 /* cv2.resize(mask.astype(np.uint8), (camera.width, camera.height)) (V3:222; INTER_LINEAR, the default) for masks that do not arrive at
  * the camera's size (the reference's scripts all pass retina_masks=True, so theirs do): n planes [h][w] of uint8 -> n planes [H][W]

@@ -115,6 +115,20 @@ class BoxPointsOutputs(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class BoxViewsInput(ctypes.Structure):
+    """lpf_box_views_input (include/lpf.h): the cam-0 corners of a batch of frames' boxes and the filter's thresholds"""
+    _fields_ = [("corners_cam0", _P), ("box_off", _P), ("T_cam_to_velo", _P), ("on_device", ctypes.c_int32),
+                ("min_points_in_view", ctypes.c_int32), ("depth_lo", ctypes.c_double), ("depth_hi", ctypes.c_double),
+                ("min_area", ctypes.c_double)]
+
+
+class BoxViewsOutputs(ctypes.Structure):
+    """lpf_box_views_outputs (include/lpf.h): per box the filter's verdict and V5's projection, per frame the counts per reason"""
+    _fields_ = [("keep", _P), ("reason", _P), ("corners_in_view", _P), ("corners_near", _P), ("avg_depth", _P), ("near_bbox2d", _P),
+                ("front", _P), ("bbox2d", _P), ("front_avg_depth", _P), ("kept_pos", _P), ("frame_counts", _P), ("corners_velo", _P),
+                ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 LPF_MAX_CAMS = 4                        # lpf_run_cams / lpf_run_cams_wide: cameras of one pass
 
 
@@ -284,6 +298,7 @@ def load(path=None):
     lib.lpf_match_2d.argtypes = [_P, ctypes.c_int, ctypes.POINTER(Match2dInput), ctypes.POINTER(Match2dOutputs)]
     lib.lpf_inside_masks.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(InsideInput), ctypes.POINTER(InsideOutputs)]
     lib.lpf_box_points.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(BoxPointsInput), ctypes.POINTER(BoxPointsOutputs)]
+    lib.lpf_box_views.argtypes = [_P, ctypes.c_int, ctypes.POINTER(BoxViewsInput), ctypes.POINTER(BoxViewsOutputs)]
     lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_cams_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(WideOutputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
@@ -321,7 +336,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
             "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d",
-            "lpf_inside_masks", "lpf_set_erosion_element", "lpf_box_points")
+            "lpf_inside_masks", "lpf_set_erosion_element", "lpf_box_points", "lpf_box_views")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -1689,6 +1704,107 @@ class LpfContext:
                 self.release_to_stream(ts)
             else:
                 self._check(self._lib.lpf_box_points(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
+        return res
+
+    BOX_VIEWS_WANT = ("keep", "reason", "corners_in_view", "corners_near", "avg_depth", "near_bbox2d", "front", "bbox2d",
+                      "front_avg_depth", "kept_pos", "frame_counts", "corners_velo")
+    _BOX_VIEWS_DTYPE = {"keep": "uint8", "reason": "int32", "corners_in_view": "int32", "corners_near": "int32", "avg_depth": "float64",
+                        "near_bbox2d": "float64", "front": "int32", "bbox2d": "float64", "front_avg_depth": "float64",
+                        "kept_pos": "int32", "frame_counts": "int32", "corners_velo": "float64"}
+    BOX_VIEW_REASONS = ("valid", "no_corners", "all_behind_camera", "no_intersection", "too_small", "error")
+
+    @classmethod
+    def box_views_batch(cls, corners, box_off, T_cam_to_velo=None, min_points_in_view=4, depth_range=(0.1, 100), min_area=100,
+                        want=("keep", "reason")):
+        """The arguments of box_views checked and described: (on_device, box_off int32 [F+1], want tuple).  ValueError for corners
+        that are not float64 [Btot,8,3] (any numbers for host arrays), a box_off that is not [F+1] from 0 to Btot without a decrease,
+        an unknown or empty ``want``, "corners_velo" without T_cam_to_velo, thresholds that are not finite and min_points_in_view
+        outside 0..8."""
+        want = tuple(want)
+        bad = [w for w in want if w not in cls.BOX_VIEWS_WANT]
+        if bad or not want:
+            raise ValueError("box_views: want is a selection of %s, got %r" % (cls.BOX_VIEWS_WANT, want))
+        dev = _is_torch(corners) and bool(corners.is_cuda)
+        if _is_torch(corners) and not dev:
+            corners = corners.numpy()
+        if not dev:
+            corners = np.asarray(corners)
+            if corners.dtype.kind not in "fiu":
+                raise ValueError("box_views: corners must be numbers, got %s" % corners.dtype)
+        elif str(corners.dtype) != "torch.float64":
+            raise ValueError("box_views: GPU corners must be float64, got %s" % corners.dtype)
+        shape = tuple(corners.shape)
+        if len(shape) != 3 or shape[1:] != (8, 3):
+            raise ValueError("box_views: corners must be [Btot,8,3] (cam-0 corners), got %s" % (shape,))
+        off = np.asarray(box_off)
+        if off.ndim != 1 or len(off) < 1 or off.dtype.kind not in "iu":
+            raise ValueError("box_views: box_off must be integers [F+1], got %s %s" % (off.dtype, off.shape))
+        off = off.astype(np.int64)
+        if off[0] != 0 or off[-1] != shape[0] or (np.diff(off) < 0).any():
+            raise ValueError("box_views: box_off must rise from 0 to the %d boxes without a decrease, got %s .. %s"
+                             % (shape[0], off[0], off[-1]))
+        if shape[0] > 0x7fffffff:
+            raise ValueError("box_views: %d boxes, a call takes fewer than 2^31" % shape[0])
+        if "corners_velo" in want and T_cam_to_velo is None:
+            raise ValueError("box_views: \"corners_velo\" needs T_cam_to_velo")
+        if T_cam_to_velo is not None and np.asarray(T_cam_to_velo).size != 16:
+            raise ValueError("box_views: T_cam_to_velo must be 4 x 4, got %s" % (np.asarray(T_cam_to_velo).shape,))
+        try:
+            lo, hi = (float(v) for v in depth_range)
+            nums = (lo, hi, float(min_area))
+        except (TypeError, ValueError):
+            raise ValueError("box_views: depth_range is (lo, hi) and min_area a number") from None
+        if not all(np.isfinite(nums)):
+            raise ValueError("box_views: depth_range and min_area must be finite numbers, got %s" % (nums,))
+        if int(min_points_in_view) != min_points_in_view or not 0 <= int(min_points_in_view) <= 8:
+            raise ValueError("box_views: min_points_in_view must be an integer in 0..8, got %r" % (min_points_in_view,))
+        return dev, off.astype(np.int32), want
+
+    def box_views(self, corners, box_off, T_cam_to_velo=None, min_points_in_view=4, depth_range=(0.1, 100), min_area=100,
+                  want=("keep", "reason")):
+        """secondtest.py's camera-view filter (is_bbox_in_camera_view) and V5's detailed box projection (project_3d_bbox_to_2d) for
+        every box of a batch of frames in ONE native call (lpf_box_views; needs set_camera / ensure_intrinsics first).  ``corners``:
+        float64 [Btot,8,3] cam-0 corners, a NumPy array or a GPU tensor; ``box_off`` int [F+1]: frame f owns boxes box_off[f] ..
+        box_off[f+1].  ``want`` picks the outputs (BOX_VIEWS_WANT): "keep" uint8, "reason" int32 (an index into BOX_VIEW_REASONS),
+        "corners_in_view", "corners_near", "front", "kept_pos" int32 [Btot], "avg_depth", "front_avg_depth" float64 [Btot],
+        "near_bbox2d", "bbox2d" float64 [Btot,4] ({min u, min v, max u, max v}; bbox2d / front as prepare_boxes returns them),
+        "frame_counts" int32 [F,6] (boxes per reason, [0] = kept), "corners_velo" float64 [Btot,8,3] (needs T_cam_to_velo).  Returns a
+        dict of them: NumPy arrays after one host wait, or GPU tensors on the corners' device in torch's stream order (the call only
+        enqueues work).  The arithmetic is the reference's, statement for statement (include/lpf.h)."""
+        dev, off, want = self.box_views_batch(corners, box_off, T_cam_to_velo, min_points_in_view, depth_range, min_area, want)
+        F, Btot = len(off) - 1, int(off[-1])
+        shape = {w: (Btot,) for w in self.BOX_VIEWS_WANT}
+        shape.update(near_bbox2d=(Btot, 4), bbox2d=(Btot, 4), frame_counts=(F, 6), corners_velo=(Btot, 8, 3))
+        inp, o = BoxViewsInput(), BoxViewsOutputs()
+        inp.box_off = off.ctypes.data
+        T = None
+        if T_cam_to_velo is not None:
+            T = np.ascontiguousarray(T_cam_to_velo, dtype=np.float64).reshape(16)
+            inp.T_cam_to_velo = T.ctypes.data
+        inp.min_points_in_view = int(min_points_in_view)
+        inp.depth_lo, inp.depth_hi, inp.min_area = float(depth_range[0]), float(depth_range[1]), float(min_area)
+        if dev:
+            import torch
+            d = corners.device
+            cc = corners.contiguous()
+            res = {w: torch.zeros(shape[w], dtype=getattr(torch, self._BOX_VIEWS_DTYPE[w]), device=d) for w in want}
+            ptr = lambda a: a.data_ptr() if a.numel() else None
+            inp.on_device = o.on_device = 1
+        else:
+            cc = np.ascontiguousarray(corners.numpy() if _is_torch(corners) else corners, dtype=np.float64)
+            res = {w: np.zeros(shape[w], self._BOX_VIEWS_DTYPE[w]) for w in want}
+            ptr = lambda a: a.ctypes.data if a.size else None
+        inp.corners_cam0 = ptr(cc)
+        for w in want:
+            setattr(o, w, ptr(res[w]))
+        if F:
+            if dev:
+                ts = torch.cuda.current_stream(d).cuda_stream
+                self.wait_for_stream(ts)                    # the corners and the outputs' memory belong to torch's stream
+                self._check(self._lib.lpf_box_views(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
+                self.release_to_stream(ts)
+            else:
+                self._check(self._lib.lpf_box_views(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
         return res
 
     def run_cams_wide(self, frames, cams, want_uv=True, want_float=False, want_lists=True, want_valid_uv=False, inst_cap=None,

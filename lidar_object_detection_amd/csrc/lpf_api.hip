@@ -11,6 +11,7 @@
 #include "lpf_match2d.hip.h"
 #include "lpf_inside.hip.h"
 #include "lpf_box_points.hip.h"
+#include "lpf_box_views.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -223,6 +224,8 @@ struct lpf_ctx {
     struct Inside { DevBuf tab, pts, in, out; } insd;
     // lpf_box_points: the frame table, staged host points, staged host lists, staged host outputs (grow-only, allocated on first use)
     struct BoxPoints { DevBuf tab, pts, in, out; } bpts;
+    // lpf_box_views: the frame table, a frame range's staged corners, its staged outputs (grow-only, allocated on first use)
+    struct BoxViews { DevBuf tab, in, out; } bviews;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -1453,7 +1456,8 @@ void lpf_destroy(lpf_ctx *c)
         release(*b);
     for (DevBuf *b : {&c->dovl.in, &c->dovl.out, &c->m2d.tab, &c->m2d.in, &c->m2d.out})
         release(*b);
-    for (DevBuf *b : {&c->insd.tab, &c->insd.pts, &c->insd.in, &c->insd.out, &c->bpts.tab, &c->bpts.pts, &c->bpts.in, &c->bpts.out})
+    for (DevBuf *b : {&c->insd.tab, &c->insd.pts, &c->insd.in, &c->insd.out, &c->bpts.tab, &c->bpts.pts, &c->bpts.in, &c->bpts.out,
+                      &c->bviews.tab, &c->bviews.in, &c->bviews.out})
         release(*b);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
     for (DevBuf *b : all) release(*b);
@@ -3043,6 +3047,97 @@ int lpf_box_points(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
         }
     }
     if (host_out || host_in || pts_in) LPF_HIP(c, host_wait(c));    // host outputs filled, host inputs free to be reused
+    return LPF_OK;
+}
+
+// ---- lpf_box_views (include/lpf.h): secondtest's view filter and V5's box projection of a batch, kernel in lpf_box_views.hip.h ----------
+// With every array in device memory the whole batch is one launch on the caller's arrays, a block per frame.  Host arrays go through
+// in ranges of consecutive frames (plan_ranges): a range stages its corners when the input is in host memory, its per-box outputs and
+// frame counts when the outputs are.
+int lpf_box_views(lpf_ctx *c, int F, const lpf_box_views_input *in, const lpf_box_views_outputs *out)
+{
+    int rc;
+    if ((rc = enter(c, "lpf_box_views", true))) return rc;
+    if (!in || !out || F < 0) return fail(c, LPF_ERR_ARG, "box_views: in=%p out=%p F=%d", (const void *)in, (const void *)out, F);
+    if (!in->box_off) return fail(c, LPF_ERR_ARG, "box_views: box_off=%p (required, F + 1 entries)", (const void *)in->box_off);
+    if (in->box_off[0] < 0) return fail(c, LPF_ERR_ARG, "box_views: box_off[0]=%d (offsets start at 0 or above)", in->box_off[0]);
+    for (int f = 0; f < F; ++f)
+        if (in->box_off[f + 1] < in->box_off[f]) return fail(c, LPF_ERR_ARG, "box_views: box_off decreases at frame %d", f);
+    if (in->box_off[F] > in->box_off[0] && !in->corners_cam0)
+        return fail(c, LPF_ERR_ARG, "box_views: corners_cam0=%p with %d boxes (required with boxes)", (const void *)in->corners_cam0,
+                    in->box_off[F] - in->box_off[0]);
+    if (out->corners_velo && !in->T_cam_to_velo)
+        return fail(c, LPF_ERR_ARG, "box_views: T_cam_to_velo=%p with corners_velo asked for (required for corners_velo)", (const void *)in->T_cam_to_velo);
+    if (!std::isfinite(in->depth_lo) || !std::isfinite(in->depth_hi) || !std::isfinite(in->min_area))
+        return fail(c, LPF_ERR_ARG, "box_views: depth_lo=%g depth_hi=%g min_area=%g must be finite", in->depth_lo, in->depth_hi, in->min_area);
+    if (in->min_points_in_view < 0 || in->min_points_in_view > 8)
+        return fail(c, LPF_ERR_ARG, "box_views: min_points_in_view=%d (0 .. 8: a box has 8 corners)", in->min_points_in_view);
+    const void *const per_box[] = {out->keep, out->reason, out->corners_in_view, out->corners_near, out->avg_depth, out->near_bbox2d,
+                                   out->front, out->bbox2d, out->front_avg_depth, out->kept_pos, out->corners_velo};
+    const size_t per_box_esz[] = {1, 4, 4, 4, 8, 32, 4, 32, 8, 4, 192};
+    size_t out_bytes = 0;                                    // of a box's wanted outputs
+    bool any_box_out = false;
+    for (int i = 0; i < 11; ++i)
+        if (per_box[i]) { out_bytes += per_box_esz[i]; any_box_out = true; }
+    if (F == 0 || (!any_box_out && !out->frame_counts)) return LPF_OK;
+    // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+
+    lpf_ctx::BoxViews &D = c->bviews;
+    const bool host_in = !in->on_device, host_out = !out->on_device;
+
+    // ---- the frame table and the ranges of frames; cost[f]: the bytes staged for the frames before f ---------------------------------
+    std::vector<LpfBvFrame> tab((size_t)F);
+    std::vector<size_t> cost((size_t)F + 1, 0);
+    for (int f = 0; f < F; ++f) {
+        LpfBvFrame &t = tab[(size_t)f];
+        t.b0 = in->box_off[f]; t.B = in->box_off[f + 1] - t.b0;
+        cost[(size_t)f + 1] = cost[(size_t)f] + (host_in ? (size_t)t.B * 192 : 0) + (host_out ? (size_t)t.B * out_bytes + 24 : 0);
+    }
+    const std::vector<Span> ranges = plan_ranges((size_t)F, (size_t)F, [&](size_t f, size_t n) { return cost[f + n] - cost[f]; });
+    const size_t most_b = largest(ranges, [&](size_t f, size_t n) { return in->box_off[f + n] - in->box_off[f]; });
+    const size_t most_f = largest(ranges, [](size_t, size_t n) { return n; });
+    if ((rc = upload_table(c, D.tab, tab.data(), (size_t)F))) return rc;
+
+    LpfBvParams Q;
+    memset(&Q, 0, sizeof Q);
+    memcpy(Q.K, c->K, sizeof Q.K);
+    if (in->T_cam_to_velo) memcpy(Q.Tcv, in->T_cam_to_velo, sizeof Q.Tcv);
+    Q.W = c->W; Q.H = c->H; Q.min_in_view = in->min_points_in_view;
+    Q.depth_lo = in->depth_lo; Q.depth_hi = in->depth_hi; Q.min_area = in->min_area;
+    int *counts = nullptr;                                   // frame_counts of the range's first frame (staged) or of frame 0 (the caller's)
+    Stage I(host_in), O(host_out);
+    I.add(Q.corners, in->corners_cam0, 192, most_b);
+    if ((rc = I.commit(c, D.in))) return rc;
+    O.add(Q.keep, out->keep, 1, most_b);
+    O.add(Q.reason, out->reason, 4, most_b);
+    O.add(Q.in_view, out->corners_in_view, 4, most_b);
+    O.add(Q.n_near, out->corners_near, 4, most_b);
+    O.add(Q.avg_depth, out->avg_depth, 8, most_b);
+    O.add(Q.near_bbox2d, out->near_bbox2d, 32, most_b);
+    O.add(Q.front, out->front, 4, most_b);
+    O.add(Q.bbox2d, out->bbox2d, 32, most_b);
+    O.add(Q.front_avg_depth, out->front_avg_depth, 8, most_b);
+    O.add(Q.kept_pos, out->kept_pos, 4, most_b);
+    O.add(counts, out->frame_counts, 24, most_f);
+    O.add(Q.corners_velo, out->corners_velo, 192, most_b);
+    if ((rc = O.commit(c, D.out))) return rc;
+    for (const Span &r : ranges) {
+        const size_t fa = r.first, fb = fa + r.count;
+        const size_t b0 = (size_t)in->box_off[fa], nb = (size_t)in->box_off[fb] - b0;
+        if (nb == 0 && !counts) continue;                    // no boxes in the range and no counts to zero: nothing to write
+        Q.frames = (const LpfBvFrame *)D.tab.p + fa;
+        if ((rc = I.in(c, {{b0, nb}}))) return rc;
+        // staged arrays begin at the range's first box and frame; the caller's own at the batch's
+        Q.in_base = host_in ? (int)b0 : 0; Q.out_base = host_out ? (int)b0 : 0;
+        Q.frame_counts = counts ? counts + (host_out ? 0 : fa * 6) : nullptr;
+        hipLaunchKernelGGL(lpf_box_views_kernel, dim3((unsigned)r.count), dim3(LPF_BV_BLOCK), 0, c->stream, Q);
+        LPF_HIP(c, hipGetLastError());
+        // keep | reason | in_view | near | avg_depth | near_bbox2d | front | bbox2d | front_avg_depth | kept_pos | frame_counts | corners_velo
+        if ((rc = O.back(c, {{b0, nb}, {b0, nb}, {b0, nb}, {b0, nb}, {b0, nb}, {b0, nb}, {b0, nb}, {b0, nb}, {b0, nb}, {b0, nb},
+                             {fa, r.count}, {b0, nb}}))) return rc;
+    }
+    if (host_in || host_out) LPF_HIP(c, host_wait(c));       // host outputs filled, host inputs free to be reused
     return LPF_OK;
 }
 

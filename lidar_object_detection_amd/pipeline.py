@@ -11,7 +11,10 @@ there is no CPU path for them: without the GPU library these functions raise.
 YOLO segmentation and Open3D stay outside (reference: unchanged subsystems); the entry
 points take them as callables.
 """
+import contextlib
+import io
 import os
+import sys
 from datetime import datetime
 
 import numpy as np
@@ -644,15 +647,19 @@ def match_detections_frames(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_
     return out
 
 
-def _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device=0, ctx=None):
+def _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device=0, ctx=None, rects=None):
     """The score matrices of improved_match_detections_frames for a list of frames (one lpf_match_2d call): per frame None (the
-    matcher leaves before it scores) or (valid_idx, dict of [D, len(valid_idx)] matrices) -- V5's columns, the boxes with a projection."""
+    matcher leaves before it scores) or (valid_idx, dict of [D, len(valid_idx)] matrices) -- V5's columns, the boxes with a projection.
+    ``rects``: per frame the (bbox2d, front) of every dict of its list where the caller has them already (lpf_box_views')."""
     live = [bool(b) and d is not None and len(d) > 0 for d, b in zip(boxes_2d_per_frame, bboxes_3d_per_frame)]
     dets = [_match2d_dets(d) if ok else None for d, ok in zip(boxes_2d_per_frame, live)]
     if not any(live):
         return [None] * len(live)
     ctx = ctx or get_context(device)
-    rects = _match2d_rects([b if ok else [] for b, ok in zip(bboxes_3d_per_frame, live)], camera, ctx)
+    if rects is None:
+        rects = _match2d_rects([b if ok else [] for b, ok in zip(bboxes_3d_per_frame, live)], camera, ctx)
+    else:
+        rects = [r if ok else (np.zeros((0, 4), np.float64), np.zeros(0, np.int32)) for r, ok in zip(rects, live)]
     res = _match2d_call(dets, rects, ctx, ("iou", "center", "size", "total", "cost"))
     out = []
     for f, r in enumerate(res):
@@ -824,6 +831,215 @@ def filter_bboxes_in_camera_view(bboxes_3d, camera, verbose=True):
         print(f"        Filtered: {stats['filtered']}")
         print(f"        Filter reasons: {stats['filter_reasons']}")
     return kept, stats
+
+
+# ---------------------------------------------------------------------------------------
+# the same box-view helpers for a list of frames: every box of the batch in ONE lpf_box_views call
+# ---------------------------------------------------------------------------------------
+_VIEW_REASONS = ("valid", "no_corners", "all_behind_camera", "no_intersection", "too_small", "error")
+_NO_CORNERS, _SCALAR = -1, -2
+
+
+def _view_batch(bboxes_per_frame):
+    """The boxes of a batch as lpf_box_views takes them: (slots, corners float64 [Btot,8,3], box_off int64 [F+1]).  slots[f][i] is
+    the position of frame f's dict i among the call's boxes, _NO_CORNERS for a dict without 'corners_cam0' (the host's no_corners),
+    or _SCALAR for one whose corners are not 8 x 3 numbers: the scalar function decides about it, as it always has."""
+    slots, parts, off = [], [], [0]
+    for boxes in bboxes_per_frame:
+        have = [i for i, b in enumerate(boxes) if "corners_cam0" in b]
+        slot = [_NO_CORNERS] * len(boxes)
+        arr = None
+        try:
+            arr = np.array([boxes[i]["corners_cam0"] for i in have]) if have else np.zeros((0, 8, 3))
+        except ValueError:                                  # ragged
+            pass
+        if arr is not None and arr.shape == (len(have), 8, 3) and arr.dtype.kind in "fiu":
+            for k, i in enumerate(have):
+                slot[i] = off[-1] + k
+            parts.append(arr.astype(np.float64, copy=False))
+            n = len(have)
+        else:                                               # some dict of the frame is odd: look at each
+            n = 0
+            for i in have:
+                try:
+                    c = np.array(boxes[i]["corners_cam0"])
+                except ValueError:
+                    c = None
+                if c is not None and c.shape == (8, 3) and c.dtype.kind in "fiu":
+                    slot[i] = off[-1] + n
+                    parts.append(c.astype(np.float64).reshape(1, 8, 3))
+                    n += 1
+                else:
+                    slot[i] = _SCALAR
+        slots.append(slot)
+        off.append(off[-1] + n)
+    corners = np.concatenate(parts) if parts else np.zeros((0, 8, 3), np.float64)
+    return slots, np.ascontiguousarray(corners.reshape(-1, 8, 3)), np.array(off, np.int64)
+
+
+def _view_call(bboxes_per_frame, camera, want, device=0, ctx=None, T_cam_to_velo=None):
+    """(slots, corners, results) of ONE lpf_box_views call over every box of the batch that has 8 x 3 corners; results are host lists
+    (``tolist()`` once per array: per box it would cost more than the kernel), None when the batch has no such box."""
+    slots, corners, off = _view_batch(bboxes_per_frame)
+    if not len(corners):
+        return slots, corners, None
+    ctx = ctx or get_context(device)
+    ctx.ensure_intrinsics(camera.K, camera.width, camera.height)
+    res = ctx.box_views(corners, off, T_cam_to_velo=T_cam_to_velo, want=want)
+    return slots, corners, res
+
+
+def _filter_frame(boxes, slot, res, depth, camera, verbose, kept_slots=None):
+    """filter_bboxes_in_camera_view for one frame from the batch's results: its (kept, stats) and printed lines (kept_slots: a list
+    that receives the kept boxes' slots)"""
+    if not boxes:
+        return [], {"total": 0, "kept": 0, "filtered": 0, "filter_reasons": {}}
+    kept, reasons = [], {}
+    for i, bbox in enumerate(boxes):
+        j = slot[i]
+        if j == _SCALAR:
+            ok, info = is_bbox_in_camera_view(bbox, camera)
+            why = info["reason"]
+        elif j == _NO_CORNERS:
+            ok, info, why = False, None, "no_corners"
+        else:
+            ok, info, why = bool(res["keep"][j]), None, _VIEW_REASONS[res["reason"][j]]
+        if ok:
+            kept.append(bbox)
+            if kept_slots is not None:
+                kept_slots.append(j)
+            if verbose:
+                n, avg = (info["corners_in_view"], info.get("avg_depth", 0)) if info else (res["corners_in_view"][j], res["avg_depth"][j])
+                print(f"[INFO] Kept bbox {i}: {n} corners in view, avg depth: {avg:.2f}m")
+            continue
+        reasons[why] = reasons.get(why, 0) + 1
+        if verbose:
+            print(f"[INFO] Filtered bbox {i}: {why}")
+            if why == "all_behind_camera":
+                d = info["depths"] if info else depth[j]
+                if d:
+                    print(f"        Depths: min={min(d):.2f}, max={max(d):.2f}")
+            elif why == "no_intersection":
+                bb = info.get("bbox_2d", []) if info else [np.int64(x) for x in res["near_bbox2d"][j]]
+                print(f"        2D bbox: {bb}")
+            elif why == "too_small":
+                if info:
+                    area = info.get("projected_area", 0)
+                else:
+                    x0, y0, x1, y1 = (np.int64(x) for x in res["near_bbox2d"][j])
+                    area = (x1 - x0) * (y1 - y0)
+                print(f"        Projected area: {area:.1f} pixels")
+    stats = {"total": len(boxes), "kept": len(kept), "filtered": len(boxes) - len(kept), "filter_reasons": reasons}
+    if verbose:
+        print(f"\n[STATS] BBox Filtering Results:")
+        print(f"        Total: {stats['total']}")
+        print(f"        Kept: {stats['kept']}")
+        print(f"        Filtered: {stats['filtered']}")
+        print(f"        Filter reasons: {stats['filter_reasons']}")
+    return kept, stats
+
+
+def _filter_setup(bboxes_per_frame, camera, verbose, device, ctx, extra=(), T_cam_to_velo=None):
+    """The one lpf_box_views call of the batched filter: (slots, results as host lists or None, the depths of the boxes behind the
+    camera -- what the verbose lines print of them -- by position, raw results)"""
+    want = ("keep", "reason") + (("corners_in_view", "avg_depth", "near_bbox2d") if verbose else ()) + tuple(extra)
+    slots, corners, raw = _view_call(bboxes_per_frame, camera, want, device, ctx, T_cam_to_velo)
+    if raw is None:
+        return slots, None, {}, None
+    res = {k: np.asarray(raw[k]).tolist() for k in want if k not in extra}
+    depth = {}
+    if verbose:
+        behind = np.flatnonzero(np.asarray(raw["reason"]) == 2)
+        if len(behind):
+            d = camera.cam2image(corners[behind].transpose(0, 2, 1))[2].tolist()
+            depth = dict(zip(behind.tolist(), d))
+    return slots, res, depth, raw
+
+
+def filter_bboxes_in_camera_view_frames(bboxes_per_frame, camera, verbose=True, device=0, ctx=None):
+    """filter_bboxes_in_camera_view (secondtest.py:362-419) for a list of frames: per frame exactly the (kept, stats) that function
+    returns -- ``kept`` holds the same dict objects, the ``filter_reasons`` keys come in first-seen order -- and the same printed
+    lines in the same order, frame by frame.  Every box of the batch is judged by ONE lpf_box_views call; a dict without
+    'corners_cam0' is 'no_corners' on the host and is left out of the call."""
+    bboxes_per_frame = [list(b) if b else [] for b in bboxes_per_frame]
+    slots, res, depth, _ = _filter_setup(bboxes_per_frame, camera, verbose, device, ctx)
+    return [_filter_frame(boxes, slot, res, depth, camera, verbose) for boxes, slot in zip(bboxes_per_frame, slots)]
+
+
+def project_3d_bboxes_to_2d_frames(bboxes_per_frame, camera, detailed=True, device=0, ctx=None):
+    """project_3d_bbox_to_2d (V5:215-252; detailed=False: firsttest.py:172-193) for a list of frames: per frame the list of
+    (info, corners) that function returns per box, with the same value types (np.int64 pixels, float centre, np.float64 avg_depth).
+    Every box of the batch is projected by ONE lpf_box_views call."""
+    bboxes_per_frame = [list(b) if b else [] for b in bboxes_per_frame]
+    want = ("front", "bbox2d") + (("front_avg_depth",) if detailed else ())
+    slots, corners, res = _view_call(bboxes_per_frame, camera, want, device, ctx)
+    if res is not None:
+        front = np.asarray(res["front"]).tolist()
+        bb = np.where(np.asarray(res["front"])[:, None] > 0, np.asarray(res["bbox2d"]), 0.0).astype(np.int64)
+        avg = np.asarray(res["front_avg_depth"]) if detailed else None
+    out = []
+    for boxes, slot in zip(bboxes_per_frame, slots):
+        rows = []
+        for bbox, j in zip(boxes, slot):
+            if j < 0:                                       # no corners, or odd ones: the scalar function's answer and printed line
+                rows.append(project_3d_bbox_to_2d(bbox, camera, detailed))
+            elif front[j] == 0:
+                rows.append((None, None))
+            else:
+                x0, y0, x1, y1 = bb[j]
+                c = np.array(bbox["corners_cam0"])
+                if not detailed:
+                    rows.append(([x0, y0, x1, y1], c))
+                else:
+                    rows.append(({"bbox": [x0, y0, x1, y1], "center": [(x0 + x1) / 2, (y0 + y1) / 2], "size": [x1 - x0, y1 - y0],
+                                  "area": (x1 - x0) * (y1 - y0), "avg_depth": avg[j]}, c))
+        out.append(rows)
+    return out
+
+
+def secondtest_match_frames(boxes_2d_per_frame, bboxes_raw_per_frame, colors_per_frame, camera, TrVeloToCam, verbose=True,
+                            min_score_threshold=0.3, min_iou_threshold=0.15, device=0, ctx=None):
+    """secondtest.py:599-611 and :703 for a list of frames: filter_bboxes_in_camera_view, then transform_bboxes_to_velodyne on the
+    kept boxes, then improved_match_detections_to_bboxes.  Per frame (matched_pairs, filter_stats, bboxes_3d); the results and the
+    printed lines equal the scalar composition of the package's three functions, and -- as there -- the kept dicts gain
+    'corners_velo' in place and nothing else.  Two native calls per batch: lpf_box_views, whose front bbox2d / front of the kept
+    boxes and whose corners_velo feed the matcher, and lpf_match_2d."""
+    boxes_2d_per_frame, colors_per_frame = list(boxes_2d_per_frame), list(colors_per_frame)
+    bboxes_raw_per_frame = [list(b) if b else [] for b in bboxes_raw_per_frame]
+    if not (len(boxes_2d_per_frame) == len(bboxes_raw_per_frame) == len(colors_per_frame)):
+        raise ValueError("one entry per frame in each list")
+    slots, res, depth, raw = _filter_setup(bboxes_raw_per_frame, camera, verbose, device, ctx, ("front", "bbox2d", "corners_velo"),
+                                           np.linalg.inv(TrVeloToCam))
+    filtered, lines, rects = [], [], []
+    for boxes, slot in zip(bboxes_raw_per_frame, slots):
+        idx = []
+        with contextlib.redirect_stdout(io.StringIO()) as buf:                 # (a frame's lines are printed below, before its matcher's)
+            kept, stats = _filter_frame(boxes, slot, res, depth, camera, verbose, idx)
+        filtered.append((kept, stats))
+        lines.append(buf.getvalue())
+        bb, fr = np.zeros((len(kept), 4), np.float64), np.zeros(len(kept), np.int32)
+        odd = [k for k, j in enumerate(idx) if j < 0]
+        if odd:                                             # kept by the scalar function: transformed and projected as it always was
+            transform_bboxes_to_velodyne([kept[k] for k in odd], TrVeloToCam)
+        for k, j in enumerate(idx):
+            if j >= 0:
+                kept[k]["corners_velo"] = raw["corners_velo"][j].tolist()
+                fr[k] = raw["front"][j]
+                if fr[k] > 0:
+                    bb[k] = raw["bbox2d"][j]
+            else:
+                info = _projected_box_info({"corners_cam0": kept[k]["corners_cam0"]}, camera)
+                if info is not None:
+                    bb[k], fr[k] = info["bbox"], 8
+        rects.append((bb, fr))
+    kept_per_frame = [k for k, _ in filtered]
+    scores = _improved_scores(boxes_2d_per_frame, kept_per_frame, camera, device, ctx, rects=rects)
+    out = []
+    for f, (kept, stats) in enumerate(filtered):
+        sys.stdout.write(lines[f])
+        matched = _improved_assign(boxes_2d_per_frame[f], kept, colors_per_frame[f], scores[f], min_score_threshold, min_iou_threshold)
+        out.append((matched, stats, kept))
+    return out
 
 
 # ---------------------------------------------------------------------------------------
