@@ -378,6 +378,15 @@ def _dev_ptr(t, dtype_name=None):
     return t.data_ptr()
 
 
+def _ptr(a):
+    """What the library is given for a NumPy array or a contiguous GPU tensor: its address, NULL for None and for an empty one."""
+    if a is None:
+        return None
+    if _is_torch(a):
+        return _dev_ptr(a) if a.numel() else None
+    return a.ctypes.data if a.size else None
+
+
 class Scan:
     """One velodyne scan handed out by ScanReader: ``points`` is a float32 [N,4] NumPy view of the
     pinned host copy (what loadVelodyneData returns, V3:24-28), ``dev_ptr`` its copy in HBM.  Both
@@ -551,6 +560,19 @@ class LpfContext:
         """Device-side edge the other way: ``stream_ptr`` waits for everything this context has queued."""
         self._check(self._lib.lpf_release_to_stream(self._h, _P(int(stream_ptr))))
 
+    def _call_in_order(self, device, fn, *args):
+        """One native call ``fn(handle, *args)``.  device None (host arrays): plainly.  A torch device (GPU tensors): in torch's stream
+        order (include/lpf.h, "Ordering contract") -- the inputs, and the memory torch's caching allocator handed out for the outputs,
+        belong to torch's current stream, the kernels run on the context's: an edge in, an edge out (no-ops when the two are one)."""
+        if device is None:
+            self._check(fn(self._h, *args))
+            return
+        import torch
+        ts = torch.cuda.current_stream(device).cuda_stream
+        self.wait_for_stream(ts)
+        self._check(fn(self._h, *args))
+        self.release_to_stream(ts)
+
     def sync(self):
         self._check(self._lib.lpf_sync(self._h))
         self._lent.clear()
@@ -679,13 +701,8 @@ class LpfContext:
             shape = tuple(masks.shape)
             out = torch.empty(shape[:-2] + (self.H, self.W), dtype=torch.uint8, device=masks.device)
             n = int(np.prod(shape[:-2], dtype=np.int64)) if len(shape) > 2 else 1
-            # Ordering (include/lpf.h, "Ordering contract"): the masks -- and the cast above, and the memory torch's caching allocator
-            # just handed out for `out` -- belong to torch's current stream; the kernel runs on the context's.  An edge in, an edge
-            # out: the caller may use `out` on torch's stream at once (a no-op when the context shares that stream).
-            ts = torch.cuda.current_stream(masks.device).cuda_stream
-            self.wait_for_stream(ts)
-            self._check(self._lib.lpf_resize_masks_u8(self._h, _dev_ptr(masks) if n else None, n, shape[-2], shape[-1], _dev_ptr(out) if n else None, 1))
-            self.release_to_stream(ts)
+            self._call_in_order(masks.device, self._lib.lpf_resize_masks_u8, _dev_ptr(masks) if n else None, n, shape[-2], shape[-1],
+                                _dev_ptr(out) if n else None, 1)           # the caller may use `out` on torch's stream at once
             return out
         a = np.asarray(masks)
         a = np.ascontiguousarray(a.astype(np.uint8))
@@ -714,10 +731,8 @@ class LpfContext:
             shape = tuple(masks.shape)
             out = torch.empty_like(masks)
             n = int(np.prod(shape[:-2], dtype=np.int64)) if len(shape) > 2 else 1
-            ts = torch.cuda.current_stream(masks.device).cuda_stream
-            self.wait_for_stream(ts)
-            self._check(self._lib.lpf_erode_masks_u8(self._h, _dev_ptr(masks) if n else None, n, shape[-2], shape[-1], int(iterations), _dev_ptr(out) if n else None, 1))
-            self.release_to_stream(ts)
+            self._call_in_order(masks.device, self._lib.lpf_erode_masks_u8, _dev_ptr(masks) if n else None, n, shape[-2], shape[-1],
+                                int(iterations), _dev_ptr(out) if n else None, 1)
             return out
         a = np.ascontiguousarray(np.asarray(masks), dtype=np.uint8)
         out = np.empty_like(a)
@@ -1065,45 +1080,61 @@ class LpfContext:
         out = self._until_lists_fit(launch, inst_cap, off)
         return self._frame_results(off, M, *out)
 
+    _PER_POINT = {"uv": None, "label_bits": "label_bits", "label_words": "label_words", "depth": "depth", "u_f": "uf", "v_f": "vf"}
+    _PER_VALID = ("valid_idx", "uv_valid", "label_valid", "label_valid_words")
+
+    def _run_outputs(self, o, table, pinned, tag, inst_cap, null_if_empty):
+        """Host result arrays of a run, wired into its outputs struct ``o`` (lpf_outputs or lpf_wide_outputs).  table: per field of
+        ``o`` (field, shape, dtype, fill or None, wanted), in the order the result dicts list them.  pinned: the context's page-locked
+        buffers (named tag + field), reused by the next run -- no allocation and no page faults per call, and the copies back are DMA
+        transfers.  null_if_empty: an empty array is handed over as NULL (lpf_wide_outputs); lpf_outputs is given its address, as it
+        always was -- the library reads NULL as "not wanted", so run_batch(inst_cap=0), which it refuses today ("inst_idx given with
+        inst_cap=0"), would run without lists instead.  Returns finish(summary columns, last inst_off column, overflow flags) ->
+        ((summary columns, per_point, per_valid, inst_idx, count_mb), 0 or the list capacity the run needed) for after the call."""
+        a = {}
+        for field, shape, dt, fill, wanted in table:
+            if not wanted:
+                arr = None
+            elif pinned:
+                arr = self._pinned(tag + field, shape, dt)
+                if fill is not None:
+                    arr[...] = fill
+            else:
+                arr = np.empty(shape, dt) if fill is None else np.full(shape, fill, dt)
+            a[field] = arr
+            setattr(o, field, arr.ctypes.data if (arr is not None and (arr.size or not null_if_empty)) else None)
+        o.on_device, o.inst_cap = 0, inst_cap
+
+        def finish(summ, last_off, overflow):
+            per_point, per_valid = {}, {}
+            for field, arr in a.items():
+                if arr is None:
+                    continue
+                if field == "uv":
+                    per_point.update(u=arr[:, 0], v=arr[:, 1])
+                elif field == "uv_valid":
+                    per_valid.update(uv_valid=arr, u_valid=arr[:, 0], v_valid=arr[:, 1])      # uv_valid: contiguous [n_valid, 2]
+                elif field in self._PER_POINT:
+                    per_point[self._PER_POINT[field]] = arr
+                elif field in self._PER_VALID:
+                    per_valid[field] = arr
+            need = int(last_off.max()) if (a["inst_idx"] is not None and overflow.any()) else 0
+            return (summ, per_point, per_valid, a["inst_idx"], a["count_mb"]), need
+        return a, finish
+
     def _host_outputs(self, o, tag, pinned, n, F, M, Btot, inst_cap, want_uv, want_label, want_float, want_lists, want_valid_uv):
         """Host result arrays of a run (Ntot = n points, F frames, M masks, Btot boxes), wired into the lpf_outputs ``o``.  Returns
-        finish() -> ((summary columns, per_point, per_valid, inst_idx, count_mb), 0 or the list capacity the run needed) for after the
-        call.  pinned: the context's page-locked buffers (names prefixed by ``tag``), reused by the next run."""
-        new = (lambda name, shape, dt: self._pinned(tag + name, shape, dt)) if pinned else (lambda name, shape, dt: np.empty(shape, dt))
-        o.on_device = 0
-        uv = new("uv", (n, 2), np.int32) if want_uv else None
-        lab = new("lab", (n,), np.uint32) if want_label else None
-        dep = new("dep", (n,), np.float64) if want_float else None
-        uf = new("uf", (n,), np.float64) if want_float else None
-        vf = new("vf", (n,), np.float64) if want_float else None
-        vidx = new("vidx", (n,), np.int64) if want_lists else None
-        uvv = new("uvv", (n, 2), np.int32) if (want_valid_uv and want_lists) else None     # only the first n_valid rows come back
-        labv = new("labv", (n,), np.uint32) if (want_valid_uv and want_lists) else None
-        iidx = new("iidx", (F, inst_cap), np.int64) if (want_lists and M) else None
-        cmb = new("cmb", (max(M * Btot, 1),), np.int32)
-        cmb[:] = 0
-        summ = new("summ", (F,), SUMMARY_DTYPE)
-        summ.view(np.uint8)[:] = 0
-        for name, arr in (("uv", uv), ("label_bits", lab), ("depth", dep), ("u_f", uf), ("v_f", vf),
-                          ("valid_idx", vidx), ("inst_idx", iidx), ("count_mb", cmb), ("summary", summ),
-                          ("uv_valid", uvv), ("label_valid", labv)):
-            setattr(o, name, arr.ctypes.data if arr is not None else None)
-        o.inst_cap = inst_cap
-
-        def finish():
-            per_point = {}
-            if want_uv:
-                per_point.update(u=uv[:, 0], v=uv[:, 1])
-            if want_label:
-                per_point.update(label_bits=lab)
-            if want_float:
-                per_point.update(depth=dep, uf=uf, vf=vf)
-            per_valid = dict(valid_idx=vidx) if want_lists else {}
-            if uvv is not None:
-                per_valid.update(uv_valid=uvv, u_valid=uvv[:, 0], v_valid=uvv[:, 1], label_valid=labv)   # uv_valid: contiguous [n_valid, 2]
-            need = int(summ["inst_off"][:, 32].max()) if (iidx is not None and summ["inst_overflow"].any()) else 0
-            return (summ, per_point, per_valid, iidx, cmb), need
-        return finish
+        finish() of _run_outputs, for after the call."""
+        vu = want_valid_uv and want_lists                                     # only the first n_valid rows come back
+        a, finish = self._run_outputs(o, (
+            ("uv", (n, 2), np.int32, None, want_uv), ("label_bits", (n,), np.uint32, None, want_label),
+            ("depth", (n,), np.float64, None, want_float), ("u_f", (n,), np.float64, None, want_float),
+            ("v_f", (n,), np.float64, None, want_float), ("valid_idx", (n,), np.int64, None, want_lists),
+            ("uv_valid", (n, 2), np.int32, None, vu), ("label_valid", (n,), np.uint32, None, vu),
+            ("inst_idx", (F, inst_cap), np.int64, None, want_lists and M), ("count_mb", (max(M * Btot, 1),), np.int32, 0, True),
+            ("summary", (F,), SUMMARY_DTYPE, 0, True)), pinned, tag, inst_cap, False)
+        summ = a["summary"]
+        return lambda: finish(summ, summ["inst_off"][:, 32], summ["inst_overflow"])
 
     def _cam_inputs(self, frames, cams, max_masks, who):
         """The lpf_cam_input array of a multi-camera pass over ``frames`` (run_cams' camera dicts), checked before anything reaches the
@@ -1127,22 +1158,17 @@ class LpfContext:
             if masks is None:
                 masks = np.zeros((F, 0, H, W), np.uint8)
             erode = cam.get("erode_iters", 0)
-            masks, M, is_f, mdev, rects = wide_mask_batch(masks, F, H, W, cam.get("rects"), erode, binarize, self.BINARIZE)
+            batch = wide_mask_batch(masks, F, H, W, cam.get("rects"), erode, binarize, self.BINARIZE)
+            masks, M, rects = batch[0], batch[1], batch[4]
             if M > max_masks:
                 raise ValueError("camera %d has %d masks per frame: a multi-camera pass takes at most %d per camera (run_wide takes more)"
                                  % (k, M, max_masks))
-            if mdev:
-                import torch
-                self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
             ci = cin[k]
             ci.T_velo_to_rect[:] = T.tolist()
             ci.K[:] = np.ascontiguousarray(K[:3, :3]).reshape(9).tolist()
             ci.W, ci.H = W, H
             ci.depth_min_excl, ci.depth_max_excl = float(cam.get("depth_min", 0.0)), float(cam.get("depth_max", 50.0))
-            ci.masks.masks = (masks.data_ptr() if mdev else masks.ctypes.data) if M else None
-            ci.masks.rects = (rects.data_ptr() if mdev else rects.ctypes.data) if (rects is not None and M) else None
-            ci.masks.M, ci.masks.f32, ci.masks.binarize, ci.masks.erode_iters = M, int(is_f), self.BINARIZE[binarize], int(erode)
-            ci.masks.on_device = 1 if mdev else 0
+            self._wide_input(ci.masks, batch, binarize, erode)
             boxes, box_off = cam.get("boxes"), None
             if boxes is not None:
                 if isinstance(boxes, np.ndarray) and F == 1:
@@ -1194,51 +1220,32 @@ class LpfContext:
     def _wide_host_outputs(self, o, n, F, M, Btot, inst_cap, want_uv, want_float, want_lists, want_valid_uv, want_label=True, pinned=False,
                            tag=""):
         """Host result arrays of a wide run (Ntot = n points, F frames, M masks, Btot boxes), wired into the lpf_wide_outputs ``o``.
-        Returns finish() -> ((summary columns, per_point, per_valid, inst_idx, count_mb), 0 or the list capacity the run needed) for
-        after the call.  want_label=False: no dense label_words.  pinned: the context's page-locked buffers (names prefixed by ``tag``),
-        reused by the next run -- no allocation and no page faults per call, and the copies back are DMA transfers."""
+        Returns finish() of _run_outputs, for after the call.  want_label=False: no dense label_words."""
         LW = (M + 31) // 32
-        if pinned:
-            def new(name, shape, dt, fill=None):
-                a = self._pinned(tag + "w_" + name, shape, dt)
-                if fill is not None:
-                    a[...] = fill
-                return a
-        else:
-            def new(name, shape, dt, fill=None):
-                return np.empty(shape, dt) if fill is None else np.full(shape, fill, dt)
-        o.on_device = 0
-        uv = new("uv", (n, 2), np.int32) if want_uv else None
-        dep, uf, vf = [(new(k, (n,), np.float64) if want_float else None) for k in ("dep", "uf", "vf")]
-        words = new("words", (n, LW), np.uint32) if want_label else None
-        vidx = new("vidx", (n,), np.int64) if want_lists else None
-        uvv = new("uvv", (n, 2), np.int32) if (want_valid_uv and want_lists) else None
-        lvw = new("lvw", (n, LW), np.uint32) if (want_valid_uv and want_lists) else None
-        iidx = new("iidx", (F, inst_cap), np.int64) if (want_lists and M) else None
-        cmb = new("cmb", (max(M * Btot, 1),), np.int32, 0)
-        nv, nl = new("nv", (F,), np.int64, 0), new("nl", (F,), np.int64, 0)
-        ic, io = new("ic", (F, M), np.int64, 0), new("io", (F, M + 1), np.int64, 0)
-        bc, bb, ov = new("bc", (F, M), np.int64, 0), new("bb", (F, M), np.int32, -1), new("ov", (F,), np.int32, 0)
-        for name, arr in (("uv", uv), ("depth", dep), ("u_f", uf), ("v_f", vf), ("valid_idx", vidx), ("uv_valid", uvv),
-                          ("label_words", words), ("label_valid_words", lvw), ("inst_idx", iidx), ("count_mb", cmb),
-                          ("n_valid", nv), ("n_labelled", nl), ("inst_count", ic), ("inst_off", io), ("best_cnt", bc),
-                          ("best_box", bb), ("inst_overflow", ov)):
-            setattr(o, name, arr.ctypes.data if (arr is not None and arr.size) else None)
-        o.inst_cap = inst_cap
+        vu = want_valid_uv and want_lists
+        a, finish = self._run_outputs(o, (
+            ("label_words", (n, LW), np.uint32, None, want_label), ("uv", (n, 2), np.int32, None, want_uv),
+            ("depth", (n,), np.float64, None, want_float), ("u_f", (n,), np.float64, None, want_float),
+            ("v_f", (n,), np.float64, None, want_float), ("valid_idx", (n,), np.int64, None, want_lists),
+            ("uv_valid", (n, 2), np.int32, None, vu), ("label_valid_words", (n, LW), np.uint32, None, vu),
+            ("inst_idx", (F, inst_cap), np.int64, None, want_lists and M), ("count_mb", (max(M * Btot, 1),), np.int32, 0, True),
+            ("n_valid", (F,), np.int64, 0, True), ("n_labelled", (F,), np.int64, 0, True), ("inst_count", (F, M), np.int64, 0, True),
+            ("inst_off", (F, M + 1), np.int64, 0, True), ("best_cnt", (F, M), np.int64, 0, True), ("best_box", (F, M), np.int32, -1, True),
+            ("inst_overflow", (F,), np.int32, 0, True)), pinned, tag + "w_", inst_cap, True)
+        summ = {k: a[k] for k in ("n_valid", "n_labelled", "inst_count", "inst_off", "best_box", "best_cnt")}
+        return lambda: finish(summ, a["inst_off"][:, M], a["inst_overflow"])
 
-        def finish():
-            summ = dict(n_valid=nv, n_labelled=nl, inst_count=ic, inst_off=io, best_box=bb, best_cnt=bc)
-            per_point = dict(label_words=words) if want_label else {}
-            if want_uv:
-                per_point.update(u=uv[:, 0], v=uv[:, 1])
-            if want_float:
-                per_point.update(depth=dep, uf=uf, vf=vf)
-            per_valid = dict(valid_idx=vidx) if want_lists else {}
-            if uvv is not None:
-                per_valid.update(uv_valid=uvv, u_valid=uvv[:, 0], v_valid=uvv[:, 1], label_valid_words=lvw)
-            need = int(io[:, M].max()) if (iidx is not None and ov.any()) else 0
-            return (summ, per_point, per_valid, iidx, cmb), need
-        return finish
+    def _wide_input(self, inp, batch, binarize, erode_iters):
+        """Fills the lpf_wide_input ``inp`` from what wide_mask_batch returned (``batch``, which must stay alive until the call has
+        returned); masks on the GPU were produced on torch's stream, so the call is ordered after it."""
+        masks, M, is_f, mdev, rects = batch
+        if mdev:
+            import torch
+            self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
+        inp.masks = _ptr(masks) if M else None
+        inp.rects = _ptr(rects) if M else None
+        inp.M, inp.f32, inp.binarize, inp.erode_iters = M, int(is_f), self.BINARIZE[binarize], int(erode_iters)
+        inp.on_device = 1 if mdev else 0
 
     def run_wide(self, frames, masks, erode_iters=0, binarize="astype", rects=None, v3_pipeline=False, want_uv=True, want_float=False,
                  want_lists=True, want_valid_uv=False, inst_cap=None, staged=None):
@@ -1255,17 +1262,12 @@ class LpfContext:
         F = len(frames)
         if F == 0:
             raise ValueError("no frames")
-        masks, M, is_f, mdev, rects = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
+        batch = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
+        M = batch[1]
         off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the run returns)
         n = int(off[-1])
-        if mdev:
-            import torch
-            self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
         inp = WideInput()
-        inp.masks = (masks.data_ptr() if mdev else masks.ctypes.data) if M else None
-        inp.rects = (rects.data_ptr() if mdev else rects.ctypes.data) if (rects is not None and M) else None
-        inp.M, inp.f32, inp.binarize, inp.erode_iters = M, int(is_f), self.BINARIZE[binarize], int(erode_iters)
-        inp.on_device = 1 if mdev else 0
+        self._wide_input(inp, batch, binarize, erode_iters)
         Btot = int(self.box_off[-1]) if self.box_off is not None else 0
         wants = dict(want_uv=want_uv, want_float=want_float, want_lists=want_lists, want_valid_uv=want_valid_uv)
 
@@ -1292,16 +1294,11 @@ class LpfContext:
             raise ValueError("no frames")
         if cap is not None and (isinstance(cap, bool) or int(cap) != cap or cap < 0):
             raise ValueError("cap must be a non-negative integer, got %r" % (cap,))
-        masks, M, is_f, mdev, rects = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
+        batch = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
+        M = batch[1]
         off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the call returns)
-        if mdev:
-            import torch
-            self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
         inp = WideInput()
-        inp.masks = (masks.data_ptr() if mdev else masks.ctypes.data) if M else None
-        inp.rects = (rects.data_ptr() if mdev else rects.ctypes.data) if (rects is not None and M) else None
-        inp.M, inp.f32, inp.binarize, inp.erode_iters = M, int(is_f), self.BINARIZE[binarize], int(erode_iters)
-        inp.on_device = 1 if mdev else 0
+        self._wide_input(inp, batch, binarize, erode_iters)
         if cap is None:                     # a quarter of the largest frame's points: frame 100's five cars are 8 k of its 109 k
             cap = 0 if M == 0 else max(1024, min(int(np.diff(off).max()) // 4, self.W * self.H))
 
@@ -1358,6 +1355,53 @@ class LpfContext:
             dep_rows[f, car_off[f, m]:car_off[f, m + 1]] = dep
         return pix_rows, dep_rows, car_off, M
 
+    @staticmethod
+    def _want(who, want, known):
+        """the selection ``want`` of an analysis call's outputs ``known``, as a tuple"""
+        want = tuple(want)
+        if not want or any(w not in known for w in want):
+            raise ValueError("%s: want is a selection of %s, got %r" % (who, known, want))
+        return want
+
+    @staticmethod
+    def _on_gpu(who, arrays, noun):
+        """True when every one of an analysis call's ``arrays`` is a GPU tensor, False when none is"""
+        n_dev = sum(1 for a in arrays if _is_torch(a) and a.is_cuda)
+        if n_dev not in (0, len(arrays)):
+            raise ValueError("%s: host arrays and GPU tensors are mixed (%d of %d %s are on the GPU)" % (who, n_dev, len(arrays), noun))
+        return n_dev > 0
+
+    @staticmethod
+    def _outputs(who, o, names, table, dims, device, out=None, fields=None):
+        """The outputs ``names`` of an analysis call, wired into its outputs struct ``o`` (field fields[name], or name): GPU tensors on
+        ``device``, NumPy arrays for device None.  table: name -> (dtype, shape with the sizes of ``dims`` by name, fill; None: left
+        as allocated).  out: the caller's own arrays under the same names, taken as they are when they fit the table."""
+        dev = device is not None
+        if dev:
+            import torch
+        mod = torch if dev else np
+        res = {}
+        for w in names:
+            dt, shape, fill = table[w]
+            shape = tuple(map(dims.get, shape, shape))          # (a size by its name, a number as it is)
+            a = out.get(w) if out else None
+            if a is None:                                   # (fresh and contiguous: nothing to check)
+                make = mod.empty if fill is None else mod.zeros if fill == 0 else mod.full
+                args = (shape,) if fill is None or fill == 0 else (shape, fill)
+                a = make(*args, dtype=getattr(torch, dt), device=device) if dev else make(*args, dt)
+            elif dev:
+                if tuple(a.shape) != shape:
+                    raise ValueError("%s: out[%r] must be %s, got %s" % (who, w, shape, tuple(a.shape)))
+                _dev_ptr(a, dt)
+            elif a.shape != shape or a.dtype != np.dtype(dt) or not a.flags.c_contiguous:
+                raise ValueError("%s: out[%r] must be a contiguous %s array %s" % (who, w, dt, shape))
+            res[w] = a
+            setattr(o, fields.get(w, w) if fields else w, _ptr(a))
+        o.on_device = int(dev)
+        return res
+
+    _OVERLAY_OUT = {"images": ("uint8", ("F", "M", "H", "W", 3), None), "max_depth": ("float64", ("F", "M"), 0)}
+
     def depth_overlays(self, maps, seg_images):
         """seg_with_pointcloud.py:174-180's per-car overlay images in ONE native call (lpf_depth_overlays): ``maps`` is what
         depth_maps() returns (per frame, M tuples (pix, depth, ...)), ``seg_images`` the segmented images uint8 [F,H,W,3] at the
@@ -1373,41 +1417,31 @@ class LpfContext:
             raise ValueError("segmented images must be uint8 [F,H,W,3] = %s at the camera's size, got %s" % (shape, tuple(seg_images.shape)))
         if str(seg_images.dtype) not in ("torch.uint8", "uint8"):
             raise ValueError("segmented images must be uint8, got %s" % (seg_images.dtype,))
-        pix, dep, car_off, M = self.overlay_rows(maps, self.W * self.H)
-        cap = pix.shape[1]
-        inp, o = DepthOverlayInput(), DepthOverlayOutputs()
-        inp.cap, inp.M = cap, M
+        lists = self.overlay_rows(maps, self.W * self.H)
+        M = lists[3]
         if dev:
             import torch
-            d = seg_images.device
+            device = seg_images.device
             seg = seg_images.contiguous()
-            lists = [torch.from_numpy(a).to(d) for a in (pix, dep, car_off)]
-            images = torch.empty((F, M, self.H, self.W, 3), dtype=torch.uint8, device=d)
-            mx = torch.zeros((F, M), dtype=torch.float64, device=d)
-            if F == 0 or M == 0:
-                return images, mx
-            inp.pix, inp.depth = (lists[0].data_ptr(), lists[1].data_ptr()) if cap else (None, None)
-            inp.car_off, inp.seg = lists[2].data_ptr(), seg.data_ptr()
-            inp.lists_on_device = inp.seg_on_device = o.on_device = 1
-            o.images, o.max_depth = images.data_ptr(), mx.data_ptr()
-            ts = torch.cuda.current_stream(d).cuda_stream
-            self.wait_for_stream(ts)                # the lists, the images and the outputs' memory belong to torch's stream
-            self._check(self._lib.lpf_depth_overlays(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
-            self.release_to_stream(ts)
-            return images, mx
-        seg = np.ascontiguousarray(seg_images)
-        images = np.empty((F, M, self.H, self.W, 3), np.uint8)
-        mx = np.zeros((F, M), np.float64)
-        if F == 0 or M == 0:
-            return images, mx
-        inp.pix, inp.depth = (pix.ctypes.data, dep.ctypes.data) if cap else (None, None)
-        inp.car_off, inp.seg = car_off.ctypes.data, seg.ctypes.data
-        o.images, o.max_depth = images.ctypes.data, mx.ctypes.data
-        self._check(self._lib.lpf_depth_overlays(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
-        return images, mx
+            pix, dep, car_off = (torch.from_numpy(a).to(device) for a in lists[:3])
+        else:
+            device = None
+            seg = np.ascontiguousarray(seg_images)
+            pix, dep, car_off = lists[:3]
+        inp, o = DepthOverlayInput(), DepthOverlayOutputs()
+        res = self._outputs("depth_overlays", o, ("images", "max_depth"), self._OVERLAY_OUT, dict(F=F, M=M, H=self.H, W=self.W), device)
+        if F and M:
+            inp.cap, inp.M = pix.shape[1], M
+            inp.pix, inp.depth, inp.car_off, inp.seg = _ptr(pix), _ptr(dep), _ptr(car_off), _ptr(seg)
+            inp.lists_on_device = inp.seg_on_device = o.on_device
+            self._call_in_order(device, self._lib.lpf_depth_overlays, F, ctypes.byref(inp), ctypes.byref(o))
+        return res["images"], res["max_depth"]
 
     MATCH2D_WANT = ("best", "iou", "center", "size", "total", "cost")
-    _MATCH2D_FIELD = {"iou": "iou", "center": "center_score", "size": "size_score", "total": "total_score", "cost": "cost"}
+    _MATCH2D_FIELD = {"center": "center_score", "size": "size_score", "total": "total_score"}
+    _MATCH2D_OUT = {"best_box": ("int32", ("D",), -1), "best_iou": ("float64", ("D",), 0), "iou": ("float64", ("P",), None),
+                    "center": ("float64", ("P",), None), "size": ("float64", ("P",), None), "total": ("float64", ("P",), None),
+                    "cost": ("float64", ("P",), None)}
 
     @staticmethod
     def match2d_batch(dets, bbox2d, front):
@@ -1417,11 +1451,7 @@ class LpfContext:
         dets, bbox2d, front = list(dets), list(bbox2d), list(front)
         if not (len(dets) == len(bbox2d) == len(front)):
             raise ValueError("match_2d: one entry per frame in each list, got %d detections, %d bbox2d, %d front" % (len(dets), len(bbox2d), len(front)))
-        every = dets + bbox2d + front
-        n_dev = sum(1 for a in every if _is_torch(a) and a.is_cuda)
-        if n_dev not in (0, len(every)):
-            raise ValueError("match_2d: host arrays and GPU tensors are mixed (%d of %d inputs are on the GPU)" % (n_dev, len(every)))
-        dev = n_dev > 0
+        dev = LpfContext._on_gpu("match_2d", dets + bbox2d + front, "inputs")
         name = lambda a: str(a.dtype).replace("torch.", "")
         dtypes = set()
         det_off, box_off = np.zeros(len(dets) + 1, np.int64), np.zeros(len(dets) + 1, np.int64)
@@ -1458,10 +1488,7 @@ class LpfContext:
         iou 0, scores 0, cost 1).  Returns a dict of per-frame lists, keys "best_box", "best_iou" and the matrices' names.  The
         arithmetic is the reference's, type for type (include/lpf.h).  Host arrays: NumPy results after one host wait; GPU tensors:
         torch tensors on their device in torch's stream order (the call only enqueues work)."""
-        want = tuple(want)
-        bad = [w for w in want if w not in self.MATCH2D_WANT]
-        if bad or not want:
-            raise ValueError("match_2d: want is a selection of %s, got %r" % (self.MATCH2D_WANT, want))
+        want = self._want("match_2d", want, self.MATCH2D_WANT)
         weights = tuple(float(w) for w in weights)
         if len(weights) != 3 or not all(np.isfinite(weights)) or not np.isfinite(float(min_iou)):
             raise ValueError("match_2d: min_iou and the three weights (iou, center, size) must be finite numbers")
@@ -1471,64 +1498,37 @@ class LpfContext:
         Dtot, Btot = int(det_off[-1]), int(box_off[-1])
         D, B = np.diff(det_off).astype(np.int64), np.diff(box_off).astype(np.int64)
         pair_off = np.concatenate([[0], np.cumsum(D * B)]).astype(np.int64)
-        P = int(pair_off[-1])
-        inp, o = Match2dInput(), Match2dOutputs()
-        inp.det_off, inp.box_off = det_off.ctypes.data, box_off.ctypes.data
-        inp.dets_f64 = int(dt == "float64")
-        inp.min_iou, (inp.w_iou, inp.w_center, inp.w_size) = float(min_iou), weights
-        mats = [w for w in want if w != "best"]
-        res = {}
+        device = dd = bb = ff = None
         if dev:
             import torch
-            d = (dets + bbox2d + front)[0].device
-            tdt = torch.float64 if dt == "float64" else torch.float32
-            dd = torch.cat([x.reshape(-1, 4) for x in dets]).contiguous() if Dtot else torch.zeros((0, 4), dtype=tdt, device=d)
-            bb = torch.cat([x.reshape(-1, 4) for x in bbox2d]).contiguous() if Btot else torch.zeros((0, 4), dtype=torch.float64, device=d)
-            ff = torch.cat(list(front)).contiguous() if Btot else torch.zeros(0, dtype=torch.int32, device=d)
-            flat = {}
-            if "best" in want:
-                flat["best_box"] = torch.full((Dtot,), -1, dtype=torch.int32, device=d)
-                flat["best_iou"] = torch.zeros(Dtot, dtype=torch.float64, device=d)
-            for w in mats:
-                flat[w] = torch.empty(P, dtype=torch.float64, device=d)
-            inp.dets, inp.bbox2d, inp.front = (dd.data_ptr() if Dtot else None), (bb.data_ptr() if Btot else None), (ff.data_ptr() if Btot else None)
-            inp.on_device = o.on_device = 1
+            device = dets[0].device
+            if Dtot:
+                dd = torch.cat([x.reshape(-1, 4) for x in dets]).contiguous()
+            if Btot:
+                bb, ff = torch.cat([x.reshape(-1, 4) for x in bbox2d]).contiguous(), torch.cat(front).contiguous()
         else:
-            dd = np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in dets]), dtype=dt) if Dtot else np.zeros((0, 4), dt)
-            bb = (np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in bbox2d]), dtype=np.float64) if Btot
-                  else np.zeros((0, 4), np.float64))
-            ff = np.ascontiguousarray(np.concatenate([np.asarray(x) for x in front]), dtype=np.int32) if Btot else np.zeros(0, np.int32)
-            flat = {}
-            if "best" in want:
-                flat["best_box"] = np.full(Dtot, -1, np.int32)
-                flat["best_iou"] = np.zeros(Dtot, np.float64)
-            for w in mats:
-                flat[w] = np.empty(P, np.float64)
-            inp.dets, inp.bbox2d, inp.front = (dd.ctypes.data if Dtot else None), (bb.ctypes.data if Btot else None), (ff.ctypes.data if Btot else None)
-        ptr = (lambda a: a.data_ptr()) if dev else (lambda a: a.ctypes.data)
-        if "best" in want and Dtot:
-            o.best_box, o.best_iou = ptr(flat["best_box"]), ptr(flat["best_iou"])
-        for w in mats:
-            if P:
-                setattr(o, self._MATCH2D_FIELD[w], ptr(flat[w]))
+            if Dtot:
+                dd = np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in dets]), dtype=dt)
+            if Btot:
+                bb = np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in bbox2d]), dtype=np.float64)
+                ff = np.ascontiguousarray(np.concatenate([np.asarray(x) for x in front]), dtype=np.int32)
+        mats = [w for w in want if w != "best"]
+        inp, o = Match2dInput(), Match2dOutputs()
+        flat = self._outputs("match_2d", o, (["best_box", "best_iou"] if "best" in want else []) + mats, self._MATCH2D_OUT,
+                             dict(D=Dtot, P=int(pair_off[-1])), device, fields=self._MATCH2D_FIELD)
+        inp.dets, inp.bbox2d, inp.front, inp.det_off, inp.box_off = _ptr(dd), _ptr(bb), _ptr(ff), det_off.ctypes.data, box_off.ctypes.data
+        inp.dets_f64, inp.on_device = int(dt == "float64"), o.on_device
+        inp.min_iou, (inp.w_iou, inp.w_center, inp.w_size) = float(min_iou), weights
         if F and Dtot:
-            if dev:
-                import torch
-                ts = torch.cuda.current_stream(d).cuda_stream
-                self.wait_for_stream(ts)                # the inputs and the outputs' memory belong to torch's stream
-                self._check(self._lib.lpf_match_2d(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
-                self.release_to_stream(ts)
-            else:
-                self._check(self._lib.lpf_match_2d(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
-        for k in ("best_box", "best_iou"):
-            if k in flat:
-                res[k] = [flat[k][det_off[f]:det_off[f + 1]] for f in range(F)]
+            self._call_in_order(device, self._lib.lpf_match_2d, F, ctypes.byref(inp), ctypes.byref(o))
+        res = {k: [flat[k][det_off[f]:det_off[f + 1]] for f in range(F)] for k in ("best_box", "best_iou") if k in flat}
         for w in mats:
             res[w] = [flat[w][pair_off[f]:pair_off[f + 1]].reshape(int(D[f]), int(B[f])) for f in range(F)]
         return res
 
     INSIDE_WANT = ("inside", "part_idx", "part_xyz", "n_inside", "matched")
-    _INSIDE_DTYPE = {"inside": "uint8", "part_idx": "int64", "part_xyz": "float32", "n_inside": "int64", "matched": "int32"}
+    _INSIDE_OUT = {"inside": ("uint8", ("F", "cap"), 0), "part_idx": ("int64", ("F", "cap"), 0), "part_xyz": ("float32", ("F", "cap", 3), 0),
+                   "n_inside": ("int64", ("F", "M"), 0), "matched": ("int32", ("F", "M"), 0)}
 
     @staticmethod
     def inside_batch(inst_idx, inst_off, best_box, best_cnt):
@@ -1536,9 +1536,7 @@ class LpfContext:
         with GPU tensors, GPU tensors of another dtype than int64 / int64 / int32 / int64, and shapes that are not [F, inst_cap],
         [F, M + 1], [F, M], [F, M] with 0 <= M <= 256."""
         every = (inst_idx, inst_off, best_box, best_cnt)
-        n_dev = sum(1 for a in every if _is_torch(a) and a.is_cuda)
-        if n_dev not in (0, 4):
-            raise ValueError("inside_masks: host arrays and GPU tensors are mixed (%d of 4 list arrays are on the GPU)" % n_dev)
+        dev = LpfContext._on_gpu("inside_masks", every, "list arrays")
         shp = [tuple(a.shape) for a in every]
         if any(len(t) != 2 for t in shp) or len({t[0] for t in shp}) != 1:
             raise ValueError("inside_masks: inst_idx [F, inst_cap], inst_off [F, M + 1], best_box [F, M], best_cnt [F, M], got %s" % (shp,))
@@ -1546,11 +1544,11 @@ class LpfContext:
         if shp[1][1] != M + 1 or shp[3][1] != M or not 0 <= M <= LPF_MAX_MASKS_WIDE:
             raise ValueError("inside_masks: inst_off [F, M + 1], best_box [F, M], best_cnt [F, M] with 0 <= M <= %d, got %s"
                              % (LPF_MAX_MASKS_WIDE, shp[1:]))
-        if n_dev:
+        if dev:
             names = [str(a.dtype).replace("torch.", "") for a in every]
             if names != ["int64", "int64", "int32", "int64"]:
                 raise ValueError("inside_masks: GPU list arrays must be int64, int64, int32, int64, got %s" % names)
-        return n_dev > 0, F, M, shp[0][1]
+        return dev, F, M, shp[0][1]
 
     def inside_masks(self, frames, inst_idx, inst_off, best_box, best_cnt, min_points=10, want=INSIDE_WANT, out=None, staged=None):
         """V3's per-car inside / outside split of a batch of frames in ONE native call (lpf_inside_masks), from what a run on the same
@@ -1561,54 +1559,28 @@ class LpfContext:
         ones), "n_inside" int64 [F, M], "matched" int32 [F, M].  Returns a dict of them: NumPy arrays after one host wait, or GPU
         tensors in torch's stream order (the call only enqueues work).  Entries the call does not write (beyond a frame's lists, rows
         of a frame whose lists did not fit) are zero, or what ``out`` -- a dict of the caller's own arrays under the same names -- held."""
-        want = tuple(want)
-        bad = [w for w in want if w not in self.INSIDE_WANT]
-        if bad or not want:
-            raise ValueError("inside_masks: want is a selection of %s, got %r" % (self.INSIDE_WANT, want))
+        want = self._want("inside_masks", want, self.INSIDE_WANT)
         if int(min_points) < 0:
             raise ValueError("inside_masks: min_points must not be negative")
         dev, F, M, cap = self.inside_batch(inst_idx, inst_off, best_box, best_cnt)
         off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the call returns)
         if len(off) - 1 != F:
             raise ValueError("inside_masks: lists of %d frames, points of %d" % (F, len(off) - 1))
-        shape = {"inside": (F, cap), "part_idx": (F, cap), "part_xyz": (F, cap, 3), "n_inside": (F, M), "matched": (F, M)}
+        lists = (inst_idx, inst_off, best_box, best_cnt)
+        arrs = ([a.contiguous() for a in lists] if dev else
+                [np.ascontiguousarray(a, dtype=t) for a, t in zip(lists, (np.int64, np.int64, np.int32, np.int64))])
+        device = inst_idx.device if dev else None
         inp, o = InsideInput(), InsideOutputs()
-        inp.inst_cap, inp.M, inp.min_points = cap, M, int(min_points)
-        res = {}
-        if dev:
-            import torch
-            d = inst_idx.device
-            arrs = [a.contiguous() for a in (inst_idx, inst_off, best_box, best_cnt)]
-            for w in want:
-                res[w] = out[w] if out is not None and w in out else torch.zeros(shape[w], dtype=getattr(torch, self._INSIDE_DTYPE[w]), device=d)
-                if tuple(res[w].shape) != shape[w]:
-                    raise ValueError("inside_masks: out[%r] must be %s, got %s" % (w, shape[w], tuple(res[w].shape)))
-            ptr = lambda a: _dev_ptr(a) if a.numel() else None
-            for w in want:
-                _dev_ptr(res[w], self._INSIDE_DTYPE[w])
-            inp.on_device = o.on_device = 1
-        else:
-            arrs = [np.ascontiguousarray(a, dtype=t) for a, t in zip((inst_idx, inst_off, best_box, best_cnt), (np.int64, np.int64, np.int32, np.int64))]
-            for w in want:
-                res[w] = out[w] if out is not None and w in out else np.zeros(shape[w], self._INSIDE_DTYPE[w])
-                if res[w].shape != shape[w] or res[w].dtype != np.dtype(self._INSIDE_DTYPE[w]) or not res[w].flags.c_contiguous:
-                    raise ValueError("inside_masks: out[%r] must be a contiguous %s array %s" % (w, self._INSIDE_DTYPE[w], shape[w]))
-            ptr = lambda a: a.ctypes.data if a.size else None
-        inp.inst_idx, inp.inst_off, inp.best_box, inp.best_cnt = (ptr(a) for a in arrs)
-        for w in want:
-            setattr(o, w, ptr(res[w]))
+        res = self._outputs("inside_masks", o, want, self._INSIDE_OUT, dict(F=F, cap=cap, M=M), device, out)
+        inp.inst_idx, inp.inst_off, inp.best_box, inp.best_cnt = (_ptr(a) for a in arrs)
+        inp.inst_cap, inp.M, inp.min_points, inp.on_device = cap, M, int(min_points), o.on_device
         if F:
-            if dev:
-                ts = torch.cuda.current_stream(d).cuda_stream
-                self.wait_for_stream(ts)                    # the lists and the outputs' memory belong to torch's stream
-                self._check(self._lib.lpf_inside_masks(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
-                self.release_to_stream(ts)
-            else:
-                self._check(self._lib.lpf_inside_masks(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
+            self._call_in_order(device, self._lib.lpf_inside_masks, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o))
         return res
 
     BOX_POINTS_WANT = ("box_points", "box_labelled", "first_box", "frame_counts")
-    _BOX_POINTS_DTYPE = {"box_points": "int32", "box_labelled": "int32", "first_box": "int32", "frame_counts": "int64"}
+    _BOX_POINTS_OUT = {"box_points": ("int32", ("B",), 0), "box_labelled": ("int32", ("B",), 0), "first_box": ("int32", ("N",), -1),
+                       "frame_counts": ("int64", ("F", 4), 0)}
 
     @staticmethod
     def box_points_batch(valid_idx, n_valid, label_valid, Ntot, F):
@@ -1616,9 +1588,7 @@ class LpfContext:
         arrays mixed with GPU tensors, shapes that are not [Ntot], [F] and [Ntot] or [Ntot, LW] with 1 <= LW <= 8, and GPU tensors
         of another dtype than int64, int64 and int32 / uint32."""
         every = [a for a in (valid_idx, n_valid, label_valid) if a is not None]
-        n_dev = sum(1 for a in every if _is_torch(a) and a.is_cuda)
-        if n_dev not in (0, len(every)):
-            raise ValueError("box_points: host arrays and GPU tensors are mixed (%d of %d list arrays are on the GPU)" % (n_dev, len(every)))
+        dev = LpfContext._on_gpu("box_points", every, "list arrays")
         shp = [tuple(a.shape) for a in (valid_idx, n_valid)]
         if shp[0] != (Ntot,) or shp[1] != (F,):
             raise ValueError("box_points: valid_idx [Ntot] and n_valid [F] of %d points in %d frames, got %s" % (Ntot, F, shp))
@@ -1629,11 +1599,11 @@ class LpfContext:
             if ls[:1] != (Ntot,) or not 1 <= LW <= LPF_MAX_MASKS_WIDE // 32:
                 raise ValueError("box_points: label_valid [Ntot] or [Ntot, LW] with 1 <= LW <= %d for %d points, got %s"
                                  % (LPF_MAX_MASKS_WIDE // 32, Ntot, ls))
-        if n_dev:
+        if dev:
             names = [str(a.dtype).replace("torch.", "") for a in every]
             if names[:2] != ["int64", "int64"] or (len(names) == 3 and names[2] not in ("int32", "uint32")):
                 raise ValueError("box_points: GPU list arrays must be int64, int64 and int32 / uint32, got %s" % names)
-        return n_dev > 0, LW
+        return dev, LW
 
     def box_points(self, frames, valid_idx, n_valid, label_valid=None, want=BOX_POINTS_WANT, out=None, staged=None):
         """Per-box LiDAR point counts, the first box of every valid point and the point-level confusion counts of a batch of frames
@@ -1646,71 +1616,35 @@ class LpfContext:
         after one host wait, or GPU tensors in torch's stream order (the call only enqueues work).  Entries of first_box the call
         does not write (beyond a frame's n_valid) are -1, or what ``out`` -- a dict of the caller's own arrays under the same names
         -- held."""
-        want = tuple(want)
-        bad = [w for w in want if w not in self.BOX_POINTS_WANT]
-        if bad or not want:
-            raise ValueError("box_points: want is a selection of %s, got %r" % (self.BOX_POINTS_WANT, want))
+        want = self._want("box_points", want, self.BOX_POINTS_WANT)
         off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the call returns)
         F, Ntot = len(off) - 1, int(off[-1])
         dev, LW = self.box_points_batch(valid_idx, n_valid, label_valid, Ntot, F)
         if self.box_off is None or len(self.box_off) - 1 != F:
             raise ValueError("box_points: boxes in force for %s frames, points of %d (set_boxes* comes first)"
                              % ("no" if self.box_off is None else len(self.box_off) - 1, F))
-        Btot = int(self.box_off[-1])
-        shape = {"box_points": (Btot,), "box_labelled": (Btot,), "first_box": (Ntot,), "frame_counts": (F, 4)}
-        inp, o = BoxPointsInput(), BoxPointsOutputs()
-        inp.LW = LW
-        res = {}
-        lists = [valid_idx, n_valid] + ([label_valid] if label_valid is not None else [])
+        device = valid_idx.device if dev else None
         if dev:
             import torch
-            d = valid_idx.device
-            arrs = [a.contiguous() for a in lists]
-            for w in want:
-                if out is not None and w in out:
-                    res[w] = out[w]
-                elif w == "first_box":
-                    res[w] = torch.full(shape[w], -1, dtype=torch.int32, device=d)
-                else:
-                    res[w] = torch.zeros(shape[w], dtype=getattr(torch, self._BOX_POINTS_DTYPE[w]), device=d)
-                if tuple(res[w].shape) != shape[w]:
-                    raise ValueError("box_points: out[%r] must be %s, got %s" % (w, shape[w], tuple(res[w].shape)))
-                _dev_ptr(res[w], self._BOX_POINTS_DTYPE[w])
-            if Ntot == 0:                                  # (an empty tensor has no address, and the call wants one)
-                arrs[0] = torch.zeros(1, dtype=torch.int64, device=d)
-            ptr = lambda a: a.data_ptr() if a.numel() else None
-            inp.on_device = o.on_device = 1
+            arrs = [None if a is None else a.contiguous() for a in (valid_idx, n_valid, label_valid)]
         else:
-            arrs = [np.ascontiguousarray(a, dtype=t) for a, t in zip(lists, (np.int64, np.int64, np.uint32))]
-            for w in want:
-                if out is not None and w in out:
-                    res[w] = out[w]
-                else:
-                    res[w] = np.full(shape[w], -1, np.int32) if w == "first_box" else np.zeros(shape[w], self._BOX_POINTS_DTYPE[w])
-                if res[w].shape != shape[w] or res[w].dtype != np.dtype(self._BOX_POINTS_DTYPE[w]) or not res[w].flags.c_contiguous:
-                    raise ValueError("box_points: out[%r] must be a contiguous %s array %s" % (w, self._BOX_POINTS_DTYPE[w], shape[w]))
-            if Ntot == 0:
-                arrs[0] = np.zeros(1, np.int64)
-            ptr = lambda a: a.ctypes.data if a.size else None
-        inp.valid_idx, inp.n_valid = ptr(arrs[0]), ptr(arrs[1])
-        inp.label_valid_words = ptr(arrs[2]) if len(arrs) == 3 else None
-        for w in want:
-            setattr(o, w, ptr(res[w]))
+            arrs = [None if a is None else np.ascontiguousarray(a, dtype=t)
+                    for a, t in zip((valid_idx, n_valid, label_valid), (np.int64, np.int64, np.uint32))]
+        if Ntot == 0:                                      # (an empty array has no address, and the call wants one)
+            arrs[0] = torch.zeros(1, dtype=torch.int64, device=device) if dev else np.zeros(1, np.int64)
+        inp, o = BoxPointsInput(), BoxPointsOutputs()
+        res = self._outputs("box_points", o, want, self._BOX_POINTS_OUT, dict(B=int(self.box_off[-1]), N=Ntot, F=F), device, out)
+        inp.valid_idx, inp.n_valid, inp.label_valid_words = (_ptr(a) for a in arrs)
+        inp.LW, inp.on_device = LW, o.on_device
         if F:
-            if dev:
-                ts = torch.cuda.current_stream(d).cuda_stream
-                self.wait_for_stream(ts)                    # the lists and the outputs' memory belong to torch's stream
-                self._check(self._lib.lpf_box_points(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
-                self.release_to_stream(ts)
-            else:
-                self._check(self._lib.lpf_box_points(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
+            self._call_in_order(device, self._lib.lpf_box_points, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o))
         return res
 
-    BOX_VIEWS_WANT = ("keep", "reason", "corners_in_view", "corners_near", "avg_depth", "near_bbox2d", "front", "bbox2d",
-                      "front_avg_depth", "kept_pos", "frame_counts", "corners_velo")
-    _BOX_VIEWS_DTYPE = {"keep": "uint8", "reason": "int32", "corners_in_view": "int32", "corners_near": "int32", "avg_depth": "float64",
-                        "near_bbox2d": "float64", "front": "int32", "bbox2d": "float64", "front_avg_depth": "float64",
-                        "kept_pos": "int32", "frame_counts": "int32", "corners_velo": "float64"}
+    _BOX_VIEWS_OUT = {"keep": ("uint8", ("B",), 0), "reason": ("int32", ("B",), 0), "corners_in_view": ("int32", ("B",), 0),
+                      "corners_near": ("int32", ("B",), 0), "avg_depth": ("float64", ("B",), 0), "near_bbox2d": ("float64", ("B", 4), 0),
+                      "front": ("int32", ("B",), 0), "bbox2d": ("float64", ("B", 4), 0), "front_avg_depth": ("float64", ("B",), 0),
+                      "kept_pos": ("int32", ("B",), 0), "frame_counts": ("int32", ("F", 6), 0), "corners_velo": ("float64", ("B", 8, 3), 0)}
+    BOX_VIEWS_WANT = tuple(_BOX_VIEWS_OUT)
     BOX_VIEW_REASONS = ("valid", "no_corners", "all_behind_camera", "no_intersection", "too_small", "error")
 
     @classmethod
@@ -1720,10 +1654,7 @@ class LpfContext:
         that are not float64 [Btot,8,3] (any numbers for host arrays), a box_off that is not [F+1] from 0 to Btot without a decrease,
         an unknown or empty ``want``, "corners_velo" without T_cam_to_velo, thresholds that are not finite and min_points_in_view
         outside 0..8."""
-        want = tuple(want)
-        bad = [w for w in want if w not in cls.BOX_VIEWS_WANT]
-        if bad or not want:
-            raise ValueError("box_views: want is a selection of %s, got %r" % (cls.BOX_VIEWS_WANT, want))
+        want = cls._want("box_views", want, cls.BOX_VIEWS_WANT)
         dev = _is_torch(corners) and bool(corners.is_cuda)
         if _is_torch(corners) and not dev:
             corners = corners.numpy()
@@ -1773,38 +1704,16 @@ class LpfContext:
         enqueues work).  The arithmetic is the reference's, statement for statement (include/lpf.h)."""
         dev, off, want = self.box_views_batch(corners, box_off, T_cam_to_velo, min_points_in_view, depth_range, min_area, want)
         F, Btot = len(off) - 1, int(off[-1])
-        shape = {w: (Btot,) for w in self.BOX_VIEWS_WANT}
-        shape.update(near_bbox2d=(Btot, 4), bbox2d=(Btot, 4), frame_counts=(F, 6), corners_velo=(Btot, 8, 3))
+        device = corners.device if dev else None
+        cc = corners.contiguous() if dev else np.ascontiguousarray(corners.numpy() if _is_torch(corners) else corners, dtype=np.float64)
         inp, o = BoxViewsInput(), BoxViewsOutputs()
-        inp.box_off = off.ctypes.data
-        T = None
-        if T_cam_to_velo is not None:
-            T = np.ascontiguousarray(T_cam_to_velo, dtype=np.float64).reshape(16)
-            inp.T_cam_to_velo = T.ctypes.data
+        res = self._outputs("box_views", o, want, self._BOX_VIEWS_OUT, dict(B=Btot, F=F), device)
+        T = None if T_cam_to_velo is None else np.ascontiguousarray(T_cam_to_velo, dtype=np.float64).reshape(16)
+        inp.corners_cam0, inp.box_off, inp.T_cam_to_velo, inp.on_device = _ptr(cc), off.ctypes.data, _ptr(T), o.on_device
         inp.min_points_in_view = int(min_points_in_view)
         inp.depth_lo, inp.depth_hi, inp.min_area = float(depth_range[0]), float(depth_range[1]), float(min_area)
-        if dev:
-            import torch
-            d = corners.device
-            cc = corners.contiguous()
-            res = {w: torch.zeros(shape[w], dtype=getattr(torch, self._BOX_VIEWS_DTYPE[w]), device=d) for w in want}
-            ptr = lambda a: a.data_ptr() if a.numel() else None
-            inp.on_device = o.on_device = 1
-        else:
-            cc = np.ascontiguousarray(corners.numpy() if _is_torch(corners) else corners, dtype=np.float64)
-            res = {w: np.zeros(shape[w], self._BOX_VIEWS_DTYPE[w]) for w in want}
-            ptr = lambda a: a.ctypes.data if a.size else None
-        inp.corners_cam0 = ptr(cc)
-        for w in want:
-            setattr(o, w, ptr(res[w]))
         if F:
-            if dev:
-                ts = torch.cuda.current_stream(d).cuda_stream
-                self.wait_for_stream(ts)                    # the corners and the outputs' memory belong to torch's stream
-                self._check(self._lib.lpf_box_views(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
-                self.release_to_stream(ts)
-            else:
-                self._check(self._lib.lpf_box_views(self._h, F, ctypes.byref(inp), ctypes.byref(o)))
+            self._call_in_order(device, self._lib.lpf_box_views, F, ctypes.byref(inp), ctypes.byref(o))
         return res
 
     def run_cams_wide(self, frames, cams, want_uv=True, want_float=False, want_lists=True, want_valid_uv=False, inst_cap=None,

@@ -215,17 +215,9 @@ struct lpf_ctx {
     // lpf_depth_maps: frame offsets, a chunk's winner planes, counters, staged masks and rectangles, staged points, host-output staging
     // and (with erosion) lpf_run_wide's label planes in pack.planes_* (grow-only, allocated on first use)
     struct DepthMaps { Wide pack; DevBuf foff, win, cnt, in, pts, out; } dmaps;
-    // lpf_depth_overlays: a chunk's staged segmented images and lists; a chunk's images and the batch's max_depth for host outputs
-    // (grow-only, allocated on first use)
-    struct DepthOverlays { DevBuf in, out; } dovl;
-    // lpf_match_2d: the frame table, a frame range's staged detections and boxes, its staged outputs (grow-only, allocated on first use)
-    struct Match2d { DevBuf tab, in, out; } m2d;
-    // lpf_inside_masks: the frame table, staged host points, staged host lists, staged host outputs (grow-only, allocated on first use)
-    struct Inside { DevBuf tab, pts, in, out; } insd;
-    // lpf_box_points: the frame table, staged host points, staged host lists, staged host outputs (grow-only, allocated on first use)
-    struct BoxPoints { DevBuf tab, pts, in, out; } bpts;
-    // lpf_box_views: the frame table, a frame range's staged corners, its staged outputs (grow-only, allocated on first use)
-    struct BoxViews { DevBuf tab, in, out; } bviews;
+    // the analysis calls, each its own: the frame table, staged host points, staged host inputs (lists, detections, corners, segmented
+    // images), staged host outputs (grow-only, allocated on first use; a call leaves empty what it does not stage)
+    struct CallBufs { DevBuf tab, pts, in, out; } dovl, m2d, insd, bpts, bviews;       // lpf_depth_overlays, lpf_match_2d, lpf_inside_masks, lpf_box_points, lpf_box_views
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -678,6 +670,36 @@ int host_points(lpf_ctx *c, DevBuf &buf, const float *pts, bool on_device, size_
     *dev = (const float4 *)buf.p;
     *wait_owed = true;
     return LPF_OK;
+}
+
+// Offsets `name` [F + 1] of a call `who`: they start at 0 or above and do not decrease.
+int check_offsets(lpf_ctx *c, const char *who, const char *name, const int32_t *off, int F)
+{
+    if (off[0] < 0) return fail(c, LPF_ERR_ARG, "%s: %s[0]=%d (offsets start at 0 or above)", who, name, off[0]);
+    for (int f = 0; f < F; ++f)
+        if (off[f + 1] < off[f]) return fail(c, LPF_ERR_ARG, "%s: %s decreases at frame %d", who, name, f);
+    return LPF_OK;
+}
+
+// The box set in force, for a call `who` that tests the points of F frames against it: there must be one, set for F frames.
+int boxes_in_force(lpf_ctx *c, const char *who, int F, lpf_ctx::BoxSet **BX)
+{
+    *BX = &c->bx[c->box_cur];
+    if ((*BX)->F == 0) return fail(c, LPF_ERR_STATE, "%s: no boxes in force (lpf_set_boxes* comes first)", who);
+    if ((*BX)->F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, %s has %d", (*BX)->F, who, F);
+    return LPF_OK;
+}
+
+// The frame table of such a call in HBM (buf): per frame its points and its boxes in BX.
+int upload_batch_frames(lpf_ctx *c, DevBuf &buf, const int64_t *frame_off, int F, const lpf_ctx::BoxSet &BX)
+{
+    std::vector<LpfBatchFrame> tab((size_t)F);
+    for (int f = 0; f < F; ++f) {
+        LpfBatchFrame &t = tab[(size_t)f];
+        t.pt_off = (long long)frame_off[f]; t.N = (int)(frame_off[f + 1] - frame_off[f]);
+        t.box_off = BX.box_off[f]; t.B = BX.box_off[f + 1] - BX.box_off[f]; t.pad = 0;
+    }
+    return upload_table(c, buf, tab.data(), (size_t)F);
 }
 
 // The address a kernel may write for a host pointer that lies in page-locked, GPU-mapped memory (hipHostMalloc / lpf_host_alloc,
@@ -1454,11 +1476,8 @@ void lpf_destroy(lpf_ctx *c)
     for (DevBuf *b : {&c->dmaps.pack.planes_a, &c->dmaps.pack.planes_b, &c->dmaps.foff, &c->dmaps.win, &c->dmaps.cnt, &c->dmaps.in,
                       &c->dmaps.pts, &c->dmaps.out})
         release(*b);
-    for (DevBuf *b : {&c->dovl.in, &c->dovl.out, &c->m2d.tab, &c->m2d.in, &c->m2d.out})
-        release(*b);
-    for (DevBuf *b : {&c->insd.tab, &c->insd.pts, &c->insd.in, &c->insd.out, &c->bpts.tab, &c->bpts.pts, &c->bpts.in, &c->bpts.out,
-                      &c->bviews.tab, &c->bviews.in, &c->bviews.out})
-        release(*b);
+    for (lpf_ctx::CallBufs *D : {&c->dovl, &c->m2d, &c->insd, &c->bpts, &c->bviews})
+        for (DevBuf *b : {&D->tab, &D->pts, &D->in, &D->out}) release(*b);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
     for (DevBuf *b : all) release(*b);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
@@ -2676,7 +2695,7 @@ int lpf_depth_overlays(lpf_ctx *c, int F, const lpf_depth_overlay_input *in, con
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
 
-    lpf_ctx::DepthOverlays &D = c->dovl;
+    lpf_ctx::CallBufs &D = c->dovl;
     const size_t img_b = (size_t)hw * 3, total = (size_t)F * M;
     const bool host_seg = !in->seg_on_device, host_lists = !in->lists_on_device, host_out = !out->on_device;
     const bool want_img = out->images != nullptr, host_img = want_img && host_out, host_mx = out->max_depth && host_out;
@@ -2746,10 +2765,7 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
         return fail(c, LPF_ERR_ARG, "match_2d: det_off=%p box_off=%p (both are required, F + 1 entries each)", (const void *)in->det_off, (const void *)in->box_off);
     if (in->det_off[0] < 0 || in->box_off[0] < 0)
         return fail(c, LPF_ERR_ARG, "match_2d: det_off[0]=%d box_off[0]=%d (offsets start at 0 or above)", in->det_off[0], in->box_off[0]);
-    for (int f = 0; f < F; ++f) {
-        if (in->det_off[f + 1] < in->det_off[f]) return fail(c, LPF_ERR_ARG, "match_2d: det_off decreases at frame %d", f);
-        if (in->box_off[f + 1] < in->box_off[f]) return fail(c, LPF_ERR_ARG, "match_2d: box_off decreases at frame %d", f);
-    }
+    if ((rc = check_offsets(c, "match_2d", "det_off", in->det_off, F)) || (rc = check_offsets(c, "match_2d", "box_off", in->box_off, F))) return rc;
     const int Dtot = in->det_off[F], Btot = in->box_off[F];
     if ((Dtot > 0 && !in->dets) || (Btot > 0 && (!in->bbox2d || !in->front)))
         return fail(c, LPF_ERR_ARG, "match_2d: dets=%p bbox2d=%p front=%p with %d detections and %d boxes (dets is required with detections, bbox2d and front with boxes)",
@@ -2764,7 +2780,7 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
 
-    lpf_ctx::Match2d &D = c->m2d;
+    lpf_ctx::CallBufs &D = c->m2d;
     const bool host_in = !in->on_device, host_out = !out->on_device;
     const size_t esz = in->dets_f64 ? 8 : 4;
 
@@ -2857,9 +2873,9 @@ int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
         return fail(c, LPF_ERR_ARG, "inside_masks: inst_idx=%p inst_off=%p best_box=%p best_cnt=%p (inst_off is required, best_box and best_cnt with M > 0, inst_idx with inst_cap > 0)",
                     (const void *)in->inst_idx, (const void *)in->inst_off, (const void *)in->best_box, (const void *)in->best_cnt);
     if ((rc = check_frames(c, "inside_masks", pts, frame_off, F, 0))) return rc;
-    lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
-    if (BX.F == 0) return fail(c, LPF_ERR_STATE, "inside_masks: no boxes in force (lpf_set_boxes* comes first)");
-    if (BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, inside_masks has %d", BX.F, F);
+    lpf_ctx::BoxSet *in_force;
+    if ((rc = boxes_in_force(c, "inside_masks", F, &in_force))) return rc;
+    const lpf_ctx::BoxSet &BX = *in_force;
     const bool host_in = !in->on_device, host_out = !out->on_device;
     const size_t M1 = (size_t)M + 1;
     if (host_in) {
@@ -2881,7 +2897,7 @@ int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
     // below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
 
-    lpf_ctx::Inside &D = c->insd;
+    lpf_ctx::CallBufs &D = c->insd;
     const size_t fc = (size_t)F * (size_t)cap, fm = (size_t)F * M, Ntot = (size_t)frame_off[F];
     // the offsets on the host: the copies back to a host caller are sized by them
     std::vector<int64_t> fetched;
@@ -2894,17 +2910,11 @@ int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
         off_h = fetched.data();
     }
 
-    std::vector<LpfInFrame> tab((size_t)F);
-    for (int f = 0; f < F; ++f) {
-        LpfInFrame &t = tab[(size_t)f];
-        t.pt_off = (long long)frame_off[f]; t.N = (int)(frame_off[f + 1] - frame_off[f]);
-        t.box_off = BX.box_off[f]; t.B = BX.box_off[f + 1] - BX.box_off[f]; t.pad = 0;
-    }
-    if ((rc = upload_table(c, D.tab, tab.data(), (size_t)F))) return rc;
+    if ((rc = upload_batch_frames(c, D.tab, frame_off, F, BX))) return rc;
 
     LpfInParams Q;
     memset(&Q, 0, sizeof Q);
-    Q.frames = (const LpfInFrame *)D.tab.p;
+    Q.frames = (const LpfBatchFrame *)D.tab.p;
     Q.inst_cap = cap; Q.M = M; Q.min_points = in->min_points;
     Q.boxp = (const double *)BX.boxp.p;
     bool pts_in = false;
@@ -2970,9 +2980,9 @@ int lpf_box_points(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     if (!in->valid_idx || !in->n_valid)
         return fail(c, LPF_ERR_ARG, "box_points: valid_idx=%p n_valid=%p (both are required)", (const void *)in->valid_idx, (const void *)in->n_valid);
     if ((rc = check_frames(c, "box_points", pts, frame_off, F, 0))) return rc;
-    lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
-    if (BX.F == 0) return fail(c, LPF_ERR_STATE, "box_points: no boxes in force (lpf_set_boxes* comes first)");
-    if (BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, box_points has %d", BX.F, F);
+    lpf_ctx::BoxSet *in_force;
+    if ((rc = boxes_in_force(c, "box_points", F, &in_force))) return rc;
+    const lpf_ctx::BoxSet &BX = *in_force;
     const bool host_in = !in->on_device, host_out = !out->on_device;
     int64_t most = 0;                                       // entries of the frame with the most: the grid's x
     for (int f = 0; f < F; ++f) {
@@ -2995,19 +3005,13 @@ int lpf_box_points(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     // below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
 
-    lpf_ctx::BoxPoints &D = c->bpts;
+    lpf_ctx::CallBufs &D = c->bpts;
     const size_t Ntot = (size_t)frame_off[F], Btot = (size_t)BX.box_off[F];
-    std::vector<LpfBpFrame> tab((size_t)F);
-    for (int f = 0; f < F; ++f) {
-        LpfBpFrame &t = tab[(size_t)f];
-        t.pt_off = (long long)frame_off[f]; t.N = (int)(frame_off[f + 1] - frame_off[f]);
-        t.box_off = BX.box_off[f]; t.B = BX.box_off[f + 1] - BX.box_off[f]; t.pad = 0;
-    }
-    if ((rc = upload_table(c, D.tab, tab.data(), (size_t)F))) return rc;
+    if ((rc = upload_batch_frames(c, D.tab, frame_off, F, BX))) return rc;
 
     LpfBpParams Q;
     memset(&Q, 0, sizeof Q);
-    Q.frames = (const LpfBpFrame *)D.tab.p;
+    Q.frames = (const LpfBatchFrame *)D.tab.p;
     Q.boxp = (const double *)BX.boxp.p; Q.boxq = (const float *)BX.boxq.p;
     const bool labels = in->label_valid_words && LW > 0;
     Q.LW = labels ? LW : 0;
@@ -3060,9 +3064,7 @@ int lpf_box_views(lpf_ctx *c, int F, const lpf_box_views_input *in, const lpf_bo
     if ((rc = enter(c, "lpf_box_views", true))) return rc;
     if (!in || !out || F < 0) return fail(c, LPF_ERR_ARG, "box_views: in=%p out=%p F=%d", (const void *)in, (const void *)out, F);
     if (!in->box_off) return fail(c, LPF_ERR_ARG, "box_views: box_off=%p (required, F + 1 entries)", (const void *)in->box_off);
-    if (in->box_off[0] < 0) return fail(c, LPF_ERR_ARG, "box_views: box_off[0]=%d (offsets start at 0 or above)", in->box_off[0]);
-    for (int f = 0; f < F; ++f)
-        if (in->box_off[f + 1] < in->box_off[f]) return fail(c, LPF_ERR_ARG, "box_views: box_off decreases at frame %d", f);
+    if ((rc = check_offsets(c, "box_views", "box_off", in->box_off, F))) return rc;
     if (in->box_off[F] > in->box_off[0] && !in->corners_cam0)
         return fail(c, LPF_ERR_ARG, "box_views: corners_cam0=%p with %d boxes (required with boxes)", (const void *)in->corners_cam0,
                     in->box_off[F] - in->box_off[0]);
@@ -3083,7 +3085,7 @@ int lpf_box_views(lpf_ctx *c, int F, const lpf_box_views_input *in, const lpf_bo
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
 
-    lpf_ctx::BoxViews &D = c->bviews;
+    lpf_ctx::CallBufs &D = c->bviews;
     const bool host_in = !in->on_device, host_out = !out->on_device;
 
     // ---- the frame table and the ranges of frames; cost[f]: the bytes staged for the frames before f ---------------------------------
@@ -3225,13 +3227,8 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
     bool host_in = false;
 
     // ---- points: read once by the streaming launch ----------------------------------------------------------------------------------
-    const float4 *d_pts = (const float4 *)pts;
-    if (!pts_on_device && n) {
-        if ((rc = reserve(c, c->cams.pts, n * 16))) return rc;
-        LPF_HIP(c, hipMemcpyAsync(c->cams.pts.p, pts, n * 16, hipMemcpyHostToDevice, c->stream));
-        d_pts = (const float4 *)c->cams.pts.p;
-        host_in = true;
-    }
+    const float4 *d_pts;
+    if ((rc = host_points(c, c->cams.pts, pts, pts_on_device != 0, 0, n, n, &d_pts, &host_in))) return rc;
 
     // ---- per camera: box tables (the box job), masks -> label images (one element type for the pass) ------------------------------
     int lb_all = 1;
@@ -3357,13 +3354,8 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
     bool host_in = false;
 
     // ---- points: read once by the projecting launch ---------------------------------------------------------------------------------
-    const float4 *d_pts = (const float4 *)pts;
-    if (!pts_on_device && n) {
-        if ((rc = reserve(c, c->camsw.pts, n * 16))) return rc;
-        LPF_HIP(c, hipMemcpyAsync(c->camsw.pts.p, pts, n * 16, hipMemcpyHostToDevice, c->stream));
-        d_pts = (const float4 *)c->camsw.pts.p;
-        host_in = true;
-    }
+    const float4 *d_pts;
+    if ((rc = host_points(c, c->camsw.pts, pts, pts_on_device != 0, 0, n, n, &d_pts, &host_in))) return rc;
 
     // ---- frame tables, one per camera (the chunk fields depend on the points only, the box fields on the camera's boxes) -----------
     std::vector<LpfWideFrame> fr((size_t)C * F);

@@ -29,15 +29,8 @@
 #define LPF_BP_CHUNK (LPF_BP_PER * LPF_BLOCK)     // entries per block
 #define LPF_BP_TILE 64                            // boxes per LDS tile: one per lane of a wave
 
-struct LpfBpFrame {               // one frame of the batch
-    long long pt_off;             // its first point in pts = its first row in the compact arrays
-    int N;                        // points
-    int box_off, B;               // its boxes in the tables in force
-    int pad;
-};
-
 struct LpfBpParams {
-    const LpfBpFrame *frames;     // frame f0 + blockIdx.y
+    const LpfBatchFrame *frames;    // frame f0 + blockIdx.y
     const float4 *pts;
     const long long *valid_idx;   // [Ntot] compact
     const long long *n_valid;     // [F]
@@ -60,7 +53,7 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_box_points_kernel(const LpfBpPa
     __shared__ unsigned s_fc[3][4];                    // [in a box | labelled | both][wave]
     const int f = Q.f0 + (int)blockIdx.y;
     const int tid = threadIdx.x, lane = lpf_lane(), wave = lpf_wave();
-    const LpfBpFrame fr = Q.frames[f];
+    const LpfBatchFrame fr = Q.frames[f];
     const long long nv = Q.n_valid[f];
     const int n = nv < 0 ? 0 : (nv > (long long)fr.N ? fr.N : (int)nv);
     if (blockIdx.x == 0 && tid == 0 && Q.frame_counts) Q.frame_counts[(size_t)f * 4] = n;

@@ -27,15 +27,8 @@
 #define LPF_IN_PER 4                              // entries per thread and step
 #define LPF_IN_STEP (LPF_IN_PER * LPF_BLOCK)      // entries per block and step
 
-struct LpfInFrame {               // one frame of the batch
-    long long pt_off;             // its first point in pts
-    int N;                        // points
-    int box_off, B;               // its boxes in the tables in force
-    int pad;
-};
-
 struct LpfInParams {
-    const LpfInFrame *frames;     // frame f0 + blockIdx.y
+    const LpfBatchFrame *frames;    // frame f0 + blockIdx.y
     const float4 *pts;
     const long long *inst_idx;    // [F][inst_cap]
     long long inst_cap;
@@ -58,7 +51,7 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_inside_cars(const LpfInParams Q
     __shared__ unsigned s_wc[2][LPF_IN_PER * 4];
     const int m = blockIdx.x, f = Q.f0 + (int)blockIdx.y;
     const int tid = threadIdx.x, lane = lpf_lane(), wave = lpf_wave();
-    const LpfInFrame fr = Q.frames[f];
+    const LpfBatchFrame fr = Q.frames[f];
     const size_t car = (size_t)f * Q.M + m;
     const long long *__restrict__ off = Q.inst_off + (size_t)f * (Q.M + 1);
     const long long o0 = off[m], o1 = off[m + 1], tot = off[Q.M];

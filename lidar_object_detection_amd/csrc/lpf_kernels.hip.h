@@ -1540,6 +1540,12 @@ struct LpfBoxFrame {             // per frame, host-built from the box counts
     int box_off, B;
     long long cand_off;          // first word of the frame's grid
 };
+struct LpfBatchFrame {           // one frame of a batch whose points are tested against the box tables in force (lpf_inside.hip.h, lpf_box_points.hip.h)
+    long long pt_off;            // its first point in pts (and its first row in arrays parallel to them)
+    int N;                       // points
+    int box_off, B;              // its boxes in the tables in force
+    int pad;
+};
 struct LpfBoxJob {               // one box preparation / table set-up (lpf_box_frame_block): a block per frame
     const double *src;           // [Btot][8][3] corners, cam-0 frame (cam0 = 1) or velodyne frame
     const uint8_t *enabled_in;   // velodyne-frame input: [Btot] 0 = dropped earlier by filter_visible_bboxes, or null

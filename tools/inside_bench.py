@@ -137,7 +137,7 @@ def kernel_only(which, calib, calls):
     res, _ = pipeline._frames_pass(items, stacks, M, cam, True, 0, False, ctx, staged=staged)
     arrs = [torch.from_numpy(a).cuda() for a in pipeline.inside_list_arrays(res, M)]
     entries = int(arrs[1][:, M].sum())
-    out = {k: torch.zeros(s, dtype=getattr(torch, ctx._INSIDE_DTYPE[k]), device="cuda")
+    out = {k: torch.zeros(s, dtype=getattr(torch, ctx._INSIDE_OUT[k][0]), device="cuda")
            for k, s in (("inside", tuple(arrs[0].shape)), ("part_idx", tuple(arrs[0].shape)), ("part_xyz", tuple(arrs[0].shape) + (3,)),
                         ("n_inside", (FRAMES, M)), ("matched", (FRAMES, M)))}
     torch.cuda.synchronize()
