@@ -753,6 +753,11 @@ int lpf_erode_masks_u8(lpf_ctx *ctx, const uint8_t *src, int n, int h, int w, in
  *                     T_cam_to_velo = inv(TrVeloToCam), row-major 4x4
  *   bbox2d[b][4]    = {min u, min v, max u, max v} of the projected corners with depth > 0 and
  *   front[b]        = how many corners those are (V4:157-168; 0 -> the box is skipped by the IoU match)
+ *                     u and v are the rounded pixels as float64 (not saturated).  A box with no corner in front (front[b] = 0) leaves
+ *                     the sentinels {1e300, 1e300, -1e300, -1e300}.  The reference's pixels are integers, which have one zero; a
+ *                     rounded float64 pixel may be -0.0 (a quotient in [-0.5, -0]), and the minimum / maximum order the zeros as
+ *                     IEEE 754-2019 does (-0 < +0): a minimum of zeros is -0.0 if one of them is, a maximum +0.0 if one of them is.
+ *                     lpf_set_boxes_cam0 and lpf_box_views (bbox2d and near_bbox2d) give the same bits.
  * Any output may be NULL.  Host pointers. */
 int lpf_prepare_boxes(lpf_ctx *ctx, const double *corners_cam0, int nbox, const double T_cam_to_velo[16],
                       uint8_t *visible, double *corners_velo, double *bbox2d, int32_t *front);

@@ -43,9 +43,18 @@ def mean_in_numpy_order(d, m):
 
 
 def pixel_box(u, v, m):
-    """{min u, min v, max u, max v} over the corners of m, float64 [B,4]; the sentinels where m has none"""
-    lo = lambda a: np.where(m, a, BIG).min(axis=1)
-    hi = lambda a: np.where(m, a, -BIG).max(axis=1)
+    """{min u, min v, max u, max v} over the corners of m, float64 [B,4]; the sentinels where m has none.  The reference's pixels are
+    integers; as float64 a rounded pixel may be -0.0, and the zeros are ordered as include/lpf.h states it (-0 < +0: IEEE 754-2019's
+    minimum and maximum, where NumPy's min / max keep whichever zero they meet first)."""
+    def lo(a):
+        w = np.where(m, a, BIG)
+        r = w.min(axis=1)
+        return np.where(r == 0, np.where(((w == 0) & np.signbit(w)).any(axis=1), -0.0, 0.0), r)
+
+    def hi(a):
+        w = np.where(m, a, -BIG)
+        r = w.max(axis=1)
+        return np.where(r == 0, np.where(((w == 0) & ~np.signbit(w)).any(axis=1), 0.0, -0.0), r)
     return np.stack([lo(u), lo(v), hi(u), hi(v)], axis=1)
 
 
