@@ -61,7 +61,9 @@ extern "C" {
                                       8 (continued): lpf_box_points_input, lpf_box_points_outputs, lpf_box_points (added; nothing else
                                          changed)
                                       8 (continued): lpf_box_views_input, lpf_box_views_outputs, lpf_box_views (added; nothing else
-                                         changed) */
+                                         changed)
+                                      8 (continued): LPF_ASSIGN_MAX, lpf_assign_input, lpf_assign_outputs, lpf_assign_costs,
+                                         lpf_assign2d_params, lpf_assign2d_outputs, lpf_assign_2d (added; nothing else changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -567,6 +569,74 @@ typedef struct lpf_match2d_outputs {           /* any pointer may be NULL: only 
     int32_t  reserved;
 } lpf_match2d_outputs;
 int lpf_match_2d(lpf_ctx *ctx, int F, const lpf_match2d_input *in, const lpf_match2d_outputs *out);
+
+/* lpf_assign_costs: scipy.optimize.linear_sum_assignment for a batch of F cost matrices in ONE call -- the assignment stage of V5's
+ * matcher (improved_match_detections_to_bboxes, V5:307-416), on the GPU.  Frame f owns rows det_off[f] .. det_off[f + 1] (D_f) and
+ * columns box_off[f] .. box_off[f + 1] (B_f); its matrix is the [D_f][B_f] block at pair_off[f] = sum_{g<f} D_g * B_g of cost (64-bit
+ * arithmetic): lpf_match_2d's layout.  A column whose front is <= 0 (a box without a projection, lpf_match_2d's rule) is dropped
+ * before the assignment (V5:337-341); front == NULL: every column is live.  The result is SciPy's, not merely an optimal one: the
+ * rectangular assignment by shortest augmenting paths with duals, on the transpose when the matrix of live columns is tall, with
+ * SciPy's choice among equal path costs (the last position of its `remaining` list whose column is free, else the first; the list
+ * filled descending and a chosen position overwritten with the last) and its float64 operations in its order.
+ * col_of_row[d]: the column assigned to row d, an index into the frame's own columns in ORIGINAL numbering, or -1.  SciPy's (rows,
+ * cols) are the rows with a column in ascending order; with more rows than live columns, D_f - live rows stay -1.
+ * status[f]: 0 solved; 1 the live entries hold a NaN or -inf (SciPy: "matrix contains invalid numeric entries"), the frame is not
+ * solved; 2 infeasible (+inf entries are legal and can leave a row without a finite column; SciPy: "cost matrix is infeasible").
+ * With a status != 0 the frame's col_of_row is all -1.  A frame without rows or without live columns has status 0 and nothing
+ * assigned; F = 0 does nothing.  Either output may be NULL.
+ * A frame takes at most LPF_ASSIGN_MAX rows and LPF_ASSIGN_MAX live columns (the solver's state lives in LDS); live columns are
+ * counted where front is host memory, with front in device memory (or NULL) every column counts.
+ * Needs no camera, masks or boxes in force and leaves all of them as they were.  Not capturable (LPF_ERR_STATE between
+ * lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it first launches what the pipeline owes (no host wait).
+ * With every pointer device memory the call only enqueues work on the context's stream (the offsets go through the pinned upload
+ * ring) and allocates nothing after the first call of a shape; otherwise it returns after one host wait, with host outputs filled.
+ * No input spins the solver or makes it touch memory outside the frame: a path search is at most B_f steps, there are at most D_f
+ * paths, every index is checked; the worst case is status 2.
+ * LPF_ERR_ARG: NULL in / out, F < 0, NULL offsets, det_off[0] or box_off[0] < 0, decreasing offsets, cost NULL with pairs, a frame
+ * beyond LPF_ASSIGN_MAX (the message names the frame, its size and the cap).
+ * Device memory: 24 bytes per frame, and per range of frames the matrices of live columns (8 bytes per pair), 4 bytes per column and
+ * frame; frames go through in ranges of consecutive frames, each within 256 MiB of scratch and staging. */
+#define LPF_ASSIGN_MAX 1024
+typedef struct lpf_assign_input {
+    const double  *cost;       /* [P] */
+    const int32_t *det_off;    /* [F + 1], host memory */
+    const int32_t *box_off;    /* [F + 1], host memory */
+    const int32_t *front;      /* [Btot] or NULL */
+    int32_t        on_device;  /* cost and front are device memory, lent until the call's work has completed */
+    int32_t        reserved;
+} lpf_assign_input;
+typedef struct lpf_assign_outputs {
+    int32_t *col_of_row;       /* [Dtot] */
+    int32_t *status;           /* [F] */
+    int32_t  on_device;
+    int32_t  reserved;
+} lpf_assign_outputs;
+int lpf_assign_costs(lpf_ctx *ctx, int F, const lpf_assign_input *in, const lpf_assign_outputs *out);
+
+/* lpf_assign_2d: V5's matcher from detections and rectangles to accepted pairs for a batch of F frames in ONE call, with nothing
+ * [P]-sized crossing this interface: every (detection, live box) pair is scored as lpf_match_2d scores it (the same device function;
+ * in->min_iou is not used) into a scratch cost matrix in device memory, the matrix is assigned as lpf_assign_costs assigns it, and
+ * each assigned pair is scored once more, so that iou / center_score / size_score / total_score [Dtot] are lpf_match_2d's matrix
+ * entries at (d, box_of_det[d]) bit for bit, and 0 where nothing is assigned.  box_of_det[d]: an index into the frame's boxes, or
+ * -1.  accepted[d] = total_score >= min_score_threshold && iou >= min_iou_threshold (V5:368; V5's values 0.3 and 0.15).  status[f]
+ * as lpf_assign_costs'.  Any output may be NULL.  Everything else -- the cap, the ranges, ordering, capture, the pipeline -- is
+ * lpf_assign_costs'; LPF_ERR_ARG also for what lpf_match_2d refuses and for thresholds that are NaN. */
+typedef struct lpf_assign2d_params {
+    double min_score_threshold;
+    double min_iou_threshold;
+} lpf_assign2d_params;
+typedef struct lpf_assign2d_outputs {
+    int32_t *box_of_det;       /* [Dtot] */
+    double  *iou;              /* [Dtot] */
+    double  *center_score;     /* [Dtot] */
+    double  *size_score;       /* [Dtot] */
+    double  *total_score;      /* [Dtot] */
+    int32_t *accepted;         /* [Dtot] */
+    int32_t *status;           /* [F] */
+    int32_t  on_device;
+    int32_t  reserved;
+} lpf_assign2d_outputs;
+int lpf_assign_2d(lpf_ctx *ctx, int F, const lpf_match2d_input *in, const lpf_assign2d_params *p, const lpf_assign2d_outputs *out);
 
 /* lpf_inside_masks: V3's per-car inside / outside split for a batch of F frames in ONE call, from what a run leaves behind.  V3's
  * statistics dicts carry, next to the counts, inside_mask = oriented_point_in_bbox(car_points, best box) for a car that found its box

@@ -15,6 +15,7 @@ import numpy as np
 from . import _build
 
 LPF_MAX_MASKS = 32
+LPF_ASSIGN_MAX = 1024             # rows and live columns of a frame of lpf_assign_costs / lpf_assign_2d
 LPF_MAX_MASKS_WIDE = 256                # lpf_run_wide: masks per frame in one pass
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -90,6 +91,27 @@ class Match2dOutputs(ctypes.Structure):
     """lpf_match2d_outputs (include/lpf.h): V4's choice per detection and V5's score matrices per pair"""
     _fields_ = [("best_box", _P), ("best_iou", _P), ("iou", _P), ("center_score", _P), ("size_score", _P), ("total_score", _P),
                 ("cost", _P), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AssignInput(ctypes.Structure):
+    """lpf_assign_input (include/lpf.h): the cost matrices of a batch of frames for lpf_assign_costs"""
+    _fields_ = [("cost", _P), ("det_off", _P), ("box_off", _P), ("front", _P), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class AssignOutputs(ctypes.Structure):
+    """lpf_assign_outputs (include/lpf.h): the column of every row and the status of every frame"""
+    _fields_ = [("col_of_row", _P), ("status", _P), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class Assign2dParams(ctypes.Structure):
+    """lpf_assign2d_params (include/lpf.h): V5's two acceptance thresholds"""
+    _fields_ = [("min_score_threshold", ctypes.c_double), ("min_iou_threshold", ctypes.c_double)]
+
+
+class Assign2dOutputs(ctypes.Structure):
+    """lpf_assign2d_outputs (include/lpf.h): per detection its box, the four scores of that pair and accepted or not"""
+    _fields_ = [("box_of_det", _P), ("iou", _P), ("center_score", _P), ("size_score", _P), ("total_score", _P), ("accepted", _P),
+                ("status", _P), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class InsideInput(ctypes.Structure):
@@ -296,6 +318,8 @@ def load(path=None):
     lib.lpf_depth_maps.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(WideInput), ctypes.POINTER(DepthMapsOutputs)]
     lib.lpf_depth_overlays.argtypes = [_P, ctypes.c_int, ctypes.POINTER(DepthOverlayInput), ctypes.POINTER(DepthOverlayOutputs)]
     lib.lpf_match_2d.argtypes = [_P, ctypes.c_int, ctypes.POINTER(Match2dInput), ctypes.POINTER(Match2dOutputs)]
+    lib.lpf_assign_costs.argtypes = [_P, ctypes.c_int, ctypes.POINTER(AssignInput), ctypes.POINTER(AssignOutputs)]
+    lib.lpf_assign_2d.argtypes = [_P, ctypes.c_int, ctypes.POINTER(Match2dInput), ctypes.POINTER(Assign2dParams), ctypes.POINTER(Assign2dOutputs)]
     lib.lpf_inside_masks.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(InsideInput), ctypes.POINTER(InsideOutputs)]
     lib.lpf_box_points.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(BoxPointsInput), ctypes.POINTER(BoxPointsOutputs)]
     lib.lpf_box_views.argtypes = [_P, ctypes.c_int, ctypes.POINTER(BoxViewsInput), ctypes.POINTER(BoxViewsOutputs)]
@@ -336,7 +360,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
             "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d",
-            "lpf_inside_masks", "lpf_set_erosion_element", "lpf_box_points", "lpf_box_views")
+            "lpf_inside_masks", "lpf_set_erosion_element", "lpf_box_points", "lpf_box_views", "lpf_assign_costs", "lpf_assign_2d")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -1524,6 +1548,128 @@ class LpfContext:
         res = {k: [flat[k][det_off[f]:det_off[f + 1]] for f in range(F)] for k in ("best_box", "best_iou") if k in flat}
         for w in mats:
             res[w] = [flat[w][pair_off[f]:pair_off[f + 1]].reshape(int(D[f]), int(B[f])) for f in range(F)]
+        return res
+
+    ASSIGN_MESSAGES = {1: "matrix contains invalid numeric entries", 2: "cost matrix is infeasible"}     # SciPy's two
+    _ASSIGN_OUT = {"col_of_row": ("int32", ("D",), -1), "status": ("int32", ("F",), 0)}
+
+    def assign_costs(self, costs, front=None, raw=False):
+        """scipy.optimize.linear_sum_assignment for a batch of cost matrices in ONE native call (lpf_assign_costs): ``costs`` is a
+        list of per-frame [D,B] float64 arrays, or of GPU tensors; ``front`` None or a list of per-frame [B] integers -- a column
+        with front <= 0 is dropped before the assignment (V5:337-341), the returned columns stay in original numbering.  Returns per
+        frame ``(rows, cols)`` as int64 NumPy arrays, exactly linear_sum_assignment's return (SciPy's tie-breaking, not merely an
+        optimal assignment).  ValueError with SciPy's message and the frame for a frame whose live entries hold a NaN or -inf
+        ("matrix contains invalid numeric entries") or that has no complete assignment ("cost matrix is infeasible"); LpfError
+        (LPF_ERR_ARG, naming the frame) for a frame beyond LPF_ASSIGN_MAX rows or live columns.  raw=True: the dict {"col_of_row": int32 [Dtot], "status": int32 [F]} as the
+        call wrote it -- with GPU tensors the call only enqueues work, in torch's stream order, and nothing is waited for."""
+        costs = list(costs)
+        F = len(costs)
+        fronts = None if front is None else list(front)
+        if fronts is not None and len(fronts) != F:
+            raise ValueError("assign_costs: one entry per frame in each list, got %d costs and %d front" % (F, len(fronts)))
+        dev = self._on_gpu("assign_costs", costs + (fronts or []), "inputs")
+        name = lambda a: str(a.dtype).replace("torch.", "")
+        det_off, box_off = np.zeros(F + 1, np.int64), np.zeros(F + 1, np.int64)
+        if not dev:
+            costs = [np.asarray(m) for m in costs]
+            fronts = None if fronts is None else [np.asarray(a) for a in fronts]
+        for f, m in enumerate(costs):
+            if len(m.shape) != 2:
+                raise ValueError("assign_costs: frame %d: a cost matrix is [D,B], got %s" % (f, tuple(m.shape)))
+            if dev and name(m) != "float64":
+                raise ValueError("assign_costs: frame %d: GPU costs must be float64, got %s" % (f, name(m)))
+            if not dev and m.dtype.kind not in "fiub":
+                raise ValueError("assign_costs: frame %d: costs must be numbers, got %s" % (f, m.dtype))
+            if fronts is not None:
+                fr = fronts[f]
+                if tuple(fr.shape) != (m.shape[1],):
+                    raise ValueError("assign_costs: frame %d: front must be [B] = [%d], got %s" % (f, m.shape[1], tuple(fr.shape)))
+                if (dev and name(fr) != "int32") or (not dev and fr.dtype.kind not in "iub"):
+                    raise ValueError("assign_costs: frame %d: front must be integers (int32 on the GPU), got %s" % (f, name(fr)))
+            det_off[f + 1] = det_off[f] + m.shape[0]
+            box_off[f + 1] = box_off[f] + m.shape[1]
+        if det_off[-1] > 0x7fffffff or box_off[-1] > 0x7fffffff:
+            raise ValueError("assign_costs: %d rows and %d columns, a call takes fewer than 2^31 of each" % (det_off[-1], box_off[-1]))
+        det_off, box_off = det_off.astype(np.int32), box_off.astype(np.int32)
+        Dtot, Btot = int(det_off[-1]), int(box_off[-1])
+        device = cc = ff = None
+        if dev:
+            import torch
+            device = costs[0].device
+            cc = torch.cat([m.reshape(-1) for m in costs]).contiguous()
+            if fronts is not None and Btot:
+                ff = torch.cat(fronts).contiguous()
+        else:
+            if F:
+                cc = np.ascontiguousarray(np.concatenate([m.reshape(-1) for m in costs]), dtype=np.float64)
+            if fronts is not None and Btot:
+                ff = np.ascontiguousarray(np.concatenate(fronts), dtype=np.int32)
+        inp, o = AssignInput(), AssignOutputs()
+        res = self._outputs("assign_costs", o, ("col_of_row", "status"), self._ASSIGN_OUT, dict(D=Dtot, F=F), device)
+        inp.cost, inp.front, inp.det_off, inp.box_off, inp.on_device = _ptr(cc), _ptr(ff), det_off.ctypes.data, box_off.ctypes.data, o.on_device
+        if F:
+            self._call_in_order(device, self._lib.lpf_assign_costs, F, ctypes.byref(inp), ctypes.byref(o))
+        if raw:
+            return res
+        col, status = (a.cpu().numpy() if dev else a for a in (res["col_of_row"], res["status"]))
+        out = []
+        for f in range(F):
+            if status[f]:
+                raise ValueError("assign_costs: frame %d: %s" % (f, self.ASSIGN_MESSAGES.get(int(status[f]), "status %d" % status[f])))
+            c = col[det_off[f]:det_off[f + 1]]
+            rows = np.flatnonzero(c >= 0)
+            out.append((rows.astype(np.int64), c[rows].astype(np.int64)))
+        return out
+
+    ASSIGN2D_WANT = ("box_of_det", "iou", "center", "size", "total", "accepted", "status")
+    _ASSIGN2D_OUT = {"box_of_det": ("int32", ("D",), -1), "iou": ("float64", ("D",), 0), "center": ("float64", ("D",), 0),
+                     "size": ("float64", ("D",), 0), "total": ("float64", ("D",), 0), "accepted": ("int32", ("D",), 0),
+                     "status": ("int32", ("F",), 0)}
+
+    def assign_2d(self, dets, bbox2d, front, weights=(0.5, 0.3, 0.2), min_score_threshold=0.3, min_iou_threshold=0.15, want=ASSIGN2D_WANT):
+        """V5's matcher from detections and rectangles to accepted pairs for a batch of frames in ONE native call (lpf_assign_2d):
+        the pair scores of match_2d, SciPy's linear_sum_assignment on the cost matrix of the boxes with front > 0 and the thresholds,
+        all on the GPU -- no [D,B] matrix leaves it.  The inputs are match_2d's.  ``want`` picks the outputs (ASSIGN2D_WANT): per
+        detection "box_of_det" int32 (an index into the frame's boxes, -1: none), the scores "iou", "center", "size", "total" float64
+        of the assigned pair (match_2d's matrix entries bit for bit, 0 where none) and "accepted" int32 (total >=
+        min_score_threshold and iou >= min_iou_threshold, V5:368); per frame "status" int32 (0 solved, 1 invalid entries, 2
+        infeasible: nothing assigned).  Returns a dict: per-frame lists, and "status" as one [F] array.  Host arrays: NumPy results
+        after one host wait; GPU tensors: torch tensors on their device in torch's stream order (the call only enqueues work).
+        LpfError (LPF_ERR_ARG, naming the frame) for a frame beyond LPF_ASSIGN_MAX detections or boxes (live boxes, for host
+        arrays)."""
+        want = self._want("assign_2d", want, self.ASSIGN2D_WANT)
+        weights = tuple(float(w) for w in weights)
+        thr = (float(min_score_threshold), float(min_iou_threshold))
+        if len(weights) != 3 or not all(np.isfinite(weights)) or any(np.isnan(thr)):
+            raise ValueError("assign_2d: the three weights (iou, center, size) must be finite and the two thresholds numbers")
+        dets, bbox2d, front = list(dets), list(bbox2d), list(front)
+        dev, dt, det_off, box_off = self.match2d_batch(dets, bbox2d, front)
+        F = len(dets)
+        Dtot, Btot = int(det_off[-1]), int(box_off[-1])
+        device = dd = bb = ff = None
+        if dev:
+            import torch
+            device = dets[0].device
+            if Dtot:
+                dd = torch.cat([x.reshape(-1, 4) for x in dets]).contiguous()
+            if Btot:
+                bb, ff = torch.cat([x.reshape(-1, 4) for x in bbox2d]).contiguous(), torch.cat(front).contiguous()
+        else:
+            if Dtot:
+                dd = np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in dets]), dtype=dt)
+            if Btot:
+                bb = np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in bbox2d]), dtype=np.float64)
+                ff = np.ascontiguousarray(np.concatenate([np.asarray(x) for x in front]), dtype=np.int32)
+        inp, prm, o = Match2dInput(), Assign2dParams(*thr), Assign2dOutputs()
+        flat = self._outputs("assign_2d", o, want, self._ASSIGN2D_OUT, dict(D=Dtot, F=F), device, fields=self._MATCH2D_FIELD)
+        inp.dets, inp.bbox2d, inp.front, inp.det_off, inp.box_off = _ptr(dd), _ptr(bb), _ptr(ff), det_off.ctypes.data, box_off.ctypes.data
+        inp.dets_f64, inp.on_device = int(dt == "float64"), o.on_device
+        inp.min_iou, (inp.w_iou, inp.w_center, inp.w_size) = 0.0, weights
+        if F:
+            self._call_in_order(device, self._lib.lpf_assign_2d, F, ctypes.byref(inp), ctypes.byref(prm), ctypes.byref(o))
+        res = {k: [flat[k][det_off[f]:det_off[f + 1]] for f in range(F)] for k in want if k != "status"}
+        if "status" in want:
+            res["status"] = flat["status"]
         return res
 
     INSIDE_WANT = ("inside", "part_idx", "part_xyz", "n_inside", "matched")

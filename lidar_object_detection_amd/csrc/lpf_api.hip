@@ -9,6 +9,7 @@
 #include "lpf_depth_maps.hip.h"
 #include "lpf_depth_overlays.hip.h"
 #include "lpf_match2d.hip.h"
+#include "lpf_assign.hip.h"
 #include "lpf_inside.hip.h"
 #include "lpf_box_points.hip.h"
 #include "lpf_box_views.hip.h"
@@ -218,6 +219,7 @@ struct lpf_ctx {
     // the analysis calls, each its own: the frame table, staged host points, staged host inputs (lists, detections, corners, segmented
     // images), staged host outputs (grow-only, allocated on first use; a call leaves empty what it does not stage)
     struct CallBufs { DevBuf tab, pts, in, out; } dovl, m2d, insd, bpts, bviews;       // lpf_depth_overlays, lpf_match_2d, lpf_inside_masks, lpf_box_points, lpf_box_views
+    CallBufs asgn;                    // lpf_assign_costs / lpf_assign_2d (pts: the scratch matrices, live-column maps and counts of a range)
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -1476,7 +1478,7 @@ void lpf_destroy(lpf_ctx *c)
     for (DevBuf *b : {&c->dmaps.pack.planes_a, &c->dmaps.pack.planes_b, &c->dmaps.foff, &c->dmaps.win, &c->dmaps.cnt, &c->dmaps.in,
                       &c->dmaps.pts, &c->dmaps.out})
         release(*b);
-    for (lpf_ctx::CallBufs *D : {&c->dovl, &c->m2d, &c->insd, &c->bpts, &c->bviews})
+    for (lpf_ctx::CallBufs *D : {&c->dovl, &c->m2d, &c->insd, &c->bpts, &c->bviews, &c->asgn})
         for (DevBuf *b : {&D->tab, &D->pts, &D->in, &D->out}) release(*b);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
     for (DevBuf *b : all) release(*b);
@@ -2847,6 +2849,147 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
     }
     if (host_in || host_out) LPF_HIP(c, host_wait(c));       // host outputs filled, host inputs free to be reused
     return LPF_OK;
+}
+
+// ---- lpf_assign_costs / lpf_assign_2d (include/lpf.h): V5's Hungarian assignment of a batch, kernels in lpf_assign.hip.h ----------------
+// Both calls are one routine: frames go through in ranges of consecutive frames (plan_ranges) whose scratch -- the matrices of live
+// columns, the live-column maps -- and staged host arrays stay within the budget; a range is three launches (pack, solve, and for
+// lpf_assign_2d finish) behind a memset of its status.  m2 != NULL: lpf_assign_2d (the cost is scored from m2's detections and boxes).
+#define LPF_AS_MAX_FRAMES 65535             // frames per launch: the pack grid's y
+static_assert(LPF_AS_CAP == LPF_ASSIGN_MAX, "the kernels' cap is the header's");
+
+static int assign_batch(lpf_ctx *c, const char *who, int F, const int32_t *det_off, const int32_t *box_off, const double *cost_in,
+                        const lpf_match2d_input *m2, const int32_t *front, bool host_in, const lpf_assign2d_params *prm, int32_t *col_out,
+                        int32_t *status_out, const lpf_assign2d_outputs *o2, bool host_out)
+{
+    int rc;
+    if (!det_off || !box_off)
+        return fail(c, LPF_ERR_ARG, "%s: det_off=%p box_off=%p (both are required, F + 1 entries each)", who, (const void *)det_off, (const void *)box_off);
+    if ((rc = check_offsets(c, who, "det_off", det_off, F)) || (rc = check_offsets(c, who, "box_off", box_off, F))) return rc;
+    if (F == 0) return LPF_OK;
+    const size_t esz = m2 && m2->dets_f64 ? 8 : 4;
+
+    // ---- the frame table and the ranges of frames; cost[f]: the bytes of scratch and staging of the frames before f ---------------------
+    std::vector<LpfM2Frame> tab((size_t)F + 1);               // (one past the end: where the pairs end)
+    std::vector<size_t> cost((size_t)F + 1, 0);
+    long long p = 0;
+    for (int f = 0; f < F; ++f) {
+        LpfM2Frame &t = tab[(size_t)f];
+        t.d0 = det_off[f]; t.D = det_off[f + 1] - t.d0;
+        t.b0 = box_off[f]; t.B = box_off[f + 1] - t.b0;
+        t.p0 = p;
+        p += (long long)t.D * t.B;
+        int live = t.B;                                       // (columns in device memory are not counted here: all of them may be live)
+        if (front && host_in) {
+            live = 0;
+            for (int b = 0; b < t.B; ++b) live += front[t.b0 + b] > 0;
+        }
+        if (t.D > LPF_ASSIGN_MAX || live > LPF_ASSIGN_MAX)
+            return fail(c, LPF_ERR_ARG, "%s: frame %d: %d rows and %d live columns, a frame takes at most LPF_ASSIGN_MAX = %d of either", who, f,
+                        t.D, live, LPF_ASSIGN_MAX);
+        const size_t pairs = (size_t)t.D * (size_t)t.B;
+        cost[(size_t)f + 1] = cost[(size_t)f] + pairs * 8 + (size_t)t.B * 4 + 4 +
+                              (host_in ? (m2 ? (size_t)t.D * 4 * esz + (size_t)t.B * 36 : pairs * 8 + (size_t)t.B * 4) : 0) +
+                              (size_t)t.D * (m2 ? 40 : 4) + 4;
+    }
+    tab[(size_t)F].p0 = p;
+    if (!m2 && p > 0 && !cost_in) return fail(c, LPF_ERR_ARG, "%s: cost=%p with %lld pairs (required with pairs)", who, (const void *)cost_in, p);
+    // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+
+    lpf_ctx::CallBufs &D = c->asgn;
+    const std::vector<Span> ranges = plan_ranges((size_t)F, LPF_AS_MAX_FRAMES, [&](size_t f, size_t n) { return cost[f + n] - cost[f]; });
+    const size_t most_d = largest(ranges, [&](size_t f, size_t n) { return det_off[f + n] - det_off[f]; });
+    const size_t most_b = largest(ranges, [&](size_t f, size_t n) { return box_off[f + n] - box_off[f]; });
+    const size_t most_p = largest(ranges, [&](size_t f, size_t n) { return tab[f + n].p0 - tab[f].p0; });
+    const size_t most_f = largest(ranges, [](size_t, size_t n) { return n; });
+    if ((rc = upload_table(c, D.tab, tab.data(), (size_t)F))) return rc;
+
+    LpfAsParams Q;
+    memset(&Q, 0, sizeof Q);
+    if (m2) { Q.w_iou = m2->w_iou; Q.w_center = m2->w_center; Q.w_size = m2->w_size; Q.min_score = prm->min_score_threshold; Q.min_iou = prm->min_iou_threshold; }
+    Stage I(host_in), S(false), O(host_out);
+    I.add(Q.cost, m2 ? nullptr : cost_in, 8, most_p);
+    I.add(Q.dets, m2 ? m2->dets : nullptr, 4 * esz, most_d);
+    I.add(Q.bbox2d, m2 ? m2->bbox2d : nullptr, 32, most_b);
+    I.add(Q.front, front, 4, most_b);
+    if ((rc = I.commit(c, D.in))) return rc;
+    S.add(Q.scratch, nullptr, 8, most_p, true);
+    S.add(Q.colmap, nullptr, 4, most_b, true);
+    S.add(Q.nlive, nullptr, 4, most_f, true);
+    if ((rc = S.commit(c, D.pts))) return rc;
+    O.add(Q.col, col_out, 4, most_d, true);                  // (the call needs both itself)
+    O.add(Q.status, status_out, 4, most_f, true);
+    O.add(Q.iou, o2 ? o2->iou : nullptr, 8, most_d);
+    O.add(Q.center, o2 ? o2->center_score : nullptr, 8, most_d);
+    O.add(Q.size, o2 ? o2->size_score : nullptr, 8, most_d);
+    O.add(Q.total, o2 ? o2->total_score : nullptr, 8, most_d);
+    O.add(Q.accepted, o2 ? o2->accepted : nullptr, 4, most_d);
+    if ((rc = O.commit(c, D.out))) return rc;
+    const bool col_staged = host_out || !col_out, status_staged = host_out || !status_out;
+    int *const status0 = Q.status;
+    const bool finish = m2 && (Q.iou || Q.center || Q.size || Q.total || Q.accepted);
+    for (const Span &r : ranges) {
+        const size_t fa = r.first, fb = fa + r.count;
+        const size_t d0 = (size_t)det_off[fa], nd = (size_t)det_off[fb] - d0, b0 = (size_t)box_off[fa], nb = (size_t)box_off[fb] - b0;
+        const size_t p0 = (size_t)tab[fa].p0, np = (size_t)tab[fb].p0 - p0;
+        int most_rows = 0;
+        for (size_t f = fa; f < fb; ++f) most_rows = std::max(most_rows, tab[f].D);
+        Q.frames = (const LpfM2Frame *)D.tab.p + fa;
+        if ((rc = I.in(c, {{p0, np}, {d0, nd}, {b0, nb}, {b0, nb}}))) return rc;                     // cost | dets | bbox2d | front
+        // staged arrays begin at the range's first detection, box, pair and frame; the caller's own at the batch's
+        Q.det_base = host_in ? (int)d0 : 0; Q.box_base = host_in ? (int)b0 : 0; Q.pair_base = host_in ? (long long)p0 : 0;
+        Q.scr_pair_base = (long long)p0; Q.scr_box_base = (int)b0;
+        Q.col_base = col_staged ? (int)d0 : 0; Q.score_base = host_out ? (int)d0 : 0;
+        Q.status = status0 + (status_staged ? 0 : fa);
+        LPF_HIP(c, hipMemsetAsync(Q.status, 0, r.count * 4, c->stream));
+        const dim3 g((unsigned)std::max((most_rows + LPF_M2_ROWS - 1) / LPF_M2_ROWS, 1), (unsigned)r.count);
+        if (!m2) hipLaunchKernelGGL((lpf_as_pack<0>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
+        else if (m2->dets_f64) hipLaunchKernelGGL((lpf_as_pack<2>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
+        else hipLaunchKernelGGL((lpf_as_pack<1>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
+        LPF_HIP(c, hipGetLastError());
+        hipLaunchKernelGGL(lpf_as_solve, dim3((unsigned)r.count), dim3(64), 0, c->stream, Q);
+        LPF_HIP(c, hipGetLastError());
+        if (finish) {
+            if (m2->dets_f64) hipLaunchKernelGGL((lpf_as_finish<double>), dim3((unsigned)r.count), dim3(LPF_BLOCK), 0, c->stream, Q);
+            else hipLaunchKernelGGL((lpf_as_finish<float>), dim3((unsigned)r.count), dim3(LPF_BLOCK), 0, c->stream, Q);
+            LPF_HIP(c, hipGetLastError());
+        }
+        // col | status | iou | center | size | total | accepted
+        if ((rc = O.back(c, {{d0, nd}, {fa, r.count}, {d0, nd}, {d0, nd}, {d0, nd}, {d0, nd}, {d0, nd}}))) return rc;
+    }
+    if (host_in || host_out) LPF_HIP(c, host_wait(c));       // host outputs filled, host inputs free to be reused
+    return LPF_OK;
+}
+
+int lpf_assign_costs(lpf_ctx *c, int F, const lpf_assign_input *in, const lpf_assign_outputs *out)
+{
+    int rc;
+    if ((rc = enter(c, "lpf_assign_costs", false))) return rc;
+    if (!in || !out || F < 0) return fail(c, LPF_ERR_ARG, "assign_costs: in=%p out=%p F=%d", (const void *)in, (const void *)out, F);
+    return assign_batch(c, "assign_costs", F, in->det_off, in->box_off, in->cost, nullptr, in->front, !in->on_device, nullptr, out->col_of_row,
+                        out->status, nullptr, !out->on_device);
+}
+
+int lpf_assign_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_assign2d_params *p, const lpf_assign2d_outputs *out)
+{
+    int rc;
+    if ((rc = enter(c, "lpf_assign_2d", false))) return rc;
+    if (!in || !p || !out || F < 0)
+        return fail(c, LPF_ERR_ARG, "assign_2d: in=%p p=%p out=%p F=%d", (const void *)in, (const void *)p, (const void *)out, F);
+    if (in->det_off && in->box_off && F > 0) {
+        if ((rc = check_offsets(c, "assign_2d", "det_off", in->det_off, F)) || (rc = check_offsets(c, "assign_2d", "box_off", in->box_off, F))) return rc;
+        const int Dtot = in->det_off[F], Btot = in->box_off[F];
+        if ((Dtot > 0 && !in->dets) || (Btot > 0 && (!in->bbox2d || !in->front)))
+            return fail(c, LPF_ERR_ARG, "assign_2d: dets=%p bbox2d=%p front=%p with %d detections and %d boxes (dets is required with detections, bbox2d and front with boxes)",
+                        in->dets, (const void *)in->bbox2d, (const void *)in->front, Dtot, Btot);
+    }
+    if (!std::isfinite(in->w_iou) || !std::isfinite(in->w_center) || !std::isfinite(in->w_size))
+        return fail(c, LPF_ERR_ARG, "assign_2d: weights=%g %g %g must be finite", in->w_iou, in->w_center, in->w_size);
+    if (std::isnan(p->min_score_threshold) || std::isnan(p->min_iou_threshold))
+        return fail(c, LPF_ERR_ARG, "assign_2d: min_score_threshold=%g min_iou_threshold=%g must be numbers", p->min_score_threshold, p->min_iou_threshold);
+    return assign_batch(c, "assign_2d", F, in->det_off, in->box_off, nullptr, in, in->front, !in->on_device, p, out->box_of_det, out->status, out,
+                        !out->on_device);
 }
 
 // ---- lpf_inside_masks (include/lpf.h): V3's inside / outside split of every car of a batch, kernel in lpf_inside.hip.h -----------------

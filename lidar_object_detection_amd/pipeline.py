@@ -671,10 +671,52 @@ def _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device=0, 
     return out
 
 
+def _improved_device_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, min_score_threshold=0.3, min_iou_threshold=0.15, device=0,
+                            ctx=None, rects=None):
+    """_improved_scores with the assignment made on the GPU as well (one lpf_assign_2d call per detection dtype): per frame None, or
+    (valid_idx, pairs) with the assigned pairs in row order as (detection, compact column, iou, center, size, total, accepted) --
+    what _improved_assign reads instead of the matrices.  A frame beyond LPF_ASSIGN_MAX detections or projected boxes gets
+    _improved_scores' entry: it is assigned on the host."""
+    from ._native import LPF_ASSIGN_MAX, LpfContext
+    live = [bool(b) and d is not None and len(d) > 0 for d, b in zip(boxes_2d_per_frame, bboxes_3d_per_frame)]
+    dets = [_match2d_dets(d) if ok else None for d, ok in zip(boxes_2d_per_frame, live)]
+    out = [None] * len(live)
+    if not any(live):
+        return out
+    ctx = ctx or get_context(device)
+    if rects is None:
+        rects = _match2d_rects([b if ok else [] for b, ok in zip(bboxes_3d_per_frame, live)], camera, ctx)
+    else:
+        rects = [r if ok else (np.zeros((0, 4), np.float64), np.zeros(0, np.int32)) for r, ok in zip(rects, live)]
+    over = {f for f, ok in enumerate(live) if ok and (len(dets[f]) > LPF_ASSIGN_MAX or int((rects[f][1] > 0).sum()) > LPF_ASSIGN_MAX)}
+    for dt in (np.float32, np.float64):
+        idx = [f for f, d in enumerate(dets) if d is not None and d.dtype == dt and len(d) and len(rects[f][0]) and f not in over]
+        if not idx:
+            continue
+        res = ctx.assign_2d([dets[f] for f in idx], [rects[f][0] for f in idx], [rects[f][1] for f in idx],
+                            min_score_threshold=min_score_threshold, min_iou_threshold=min_iou_threshold)
+        for k, f in enumerate(idx):
+            if res["status"][k]:                             # (what scipy's solver raises for the frame's matrix)
+                raise ValueError(LpfContext.ASSIGN_MESSAGES[int(res["status"][k])])
+            valid = np.flatnonzero(rects[f][1] > 0)
+            box = res["box_of_det"][k]
+            rows = np.flatnonzero(box >= 0)
+            cols = np.searchsorted(valid, box[rows])         # the box's rank among the projected ones: V5's column
+            pairs = list(zip(rows.tolist(), cols.tolist(), *(res[n][k][rows].tolist() for n in ("iou", "center", "size", "total")),
+                             (res["accepted"][k][rows] != 0).tolist()))
+            out[f] = (valid.tolist(), pairs)
+    if over:
+        host = _improved_scores([d if f in over else None for f, d in enumerate(boxes_2d_per_frame)],
+                                [b if f in over else [] for f, b in enumerate(bboxes_3d_per_frame)], camera, device, ctx, rects=rects)
+        for f in over:
+            out[f] = host[f]
+    return out
+
+
 def _improved_assign(boxes_2d, bboxes_3d, mask_colors, scores, min_score_threshold=0.3, min_iou_threshold=0.15):
     """improved_match_detections_to_bboxes from its cost matrix on: the assignment, the thresholds, the returned list and every
-    printed line, with the pair scores read from lpf_match_2d's matrices (``scores``: a frame's entry of _improved_scores)."""
-    from scipy.optimize import linear_sum_assignment
+    printed line, with the pair scores read from lpf_match_2d's matrices (``scores``: a frame's entry of _improved_scores), or from
+    the pairs lpf_assign_2d assigned (a frame's entry of _improved_device_scores)."""
     matched = []
     if not bboxes_3d or boxes_2d is None or len(boxes_2d) == 0:
         print("[INFO] No detections or 3D bounding boxes to match")
@@ -684,11 +726,17 @@ def _improved_assign(boxes_2d, bboxes_3d, mask_colors, scores, min_score_thresho
     if not valid_idx:
         print("[WARN] No valid 3D bbox projections found")
         return matched
-    rows, cols = linear_sum_assignment(m["cost"])
-    iou, center, size, total = m["iou"], m["center"], m["size"], m["total"]
+    if isinstance(m, list):                                 # assigned on the GPU
+        pairs = m
+    else:
+        from scipy.optimize import linear_sum_assignment
+        rows, cols = linear_sum_assignment(m["cost"])
+        iou, center, size, total = m["iou"], m["center"], m["size"], m["total"]
+        pairs = [(i, j, iou[i, j], center[i, j], size[i, j], total[i, j], total[i, j] >= min_score_threshold and iou[i, j] >= min_iou_threshold)
+                 for i, j in zip(rows, cols)]
     used = set()
-    for i, j in zip(rows, cols):
-        if total[i, j] >= min_score_threshold and iou[i, j] >= min_iou_threshold:
+    for i, j, iou_ij, center_ij, size_ij, total_ij, accepted in pairs:
+        if accepted:
             orig = valid_idx[j]
             used.add(orig)
             bbox = bboxes_3d[orig]
@@ -700,12 +748,12 @@ def _improved_assign(boxes_2d, bboxes_3d, mask_colors, scores, min_score_thresho
                     color = np.array([1.0, 0.0, 0.0])
                 matched.append((np.array(bbox["corners_velo"]), color))
                 print(f"[INFO] Matched detection {i} with 3D bbox {orig}")
-                print(f"        Scores - IoU: {iou[i, j]:.3f}, Center: {center[i, j]:.3f}, "
-                      f"Size: {size[i, j]:.3f}, Total: {total[i, j]:.3f}")
+                print(f"        Scores - IoU: {iou_ij:.3f}, Center: {center_ij:.3f}, "
+                      f"Size: {size_ij:.3f}, Total: {total_ij:.3f}")
             else:
                 print(f"[WARN] No Velodyne corners found for bbox {orig}")
         else:
-            print(f"[INFO] Rejected match det{i}-bbox{j}: score={total[i, j]:.3f}, IoU={iou[i, j]:.3f}")
+            print(f"[INFO] Rejected match det{i}-bbox{j}: score={total_ij:.3f}, IoU={iou_ij:.3f}")
     for i, bbox in enumerate(bboxes_3d):
         if i not in used and "corners_velo" in bbox:
             matched.append((np.array(bbox["corners_velo"]), [0.7, 0.7, 0.7]))
@@ -713,18 +761,38 @@ def _improved_assign(boxes_2d, bboxes_3d, mask_colors, scores, min_score_thresho
     return matched
 
 
+def _assign_route(assign):
+    if assign not in ("host", "device"):
+        raise ValueError("assign is \"host\" (scipy's solver on the downloaded cost matrices) or \"device\" (lpf_assign_2d), got %r" % (assign,))
+    return assign == "device"
+
+
 def improved_match_detections_frames(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame, camera, min_score_threshold=0.3,
-                                     min_iou_threshold=0.15, device=0, ctx=None):
+                                     min_iou_threshold=0.15, device=0, ctx=None, assign="host"):
     """improved_match_detections_to_bboxes (V5:307-416) for a list of frames: per frame exactly the list that function returns and
-    the same printed lines in the same order.  The score of every (detection, box) pair of the batch comes from ONE lpf_match_2d
-    call; the assignment stays scipy's linear_sum_assignment on the cost matrix of the boxes that have a projection."""
+    the same printed lines in the same order.  assign="host": the score of every (detection, box) pair of the batch comes from ONE
+    lpf_match_2d call; the assignment is scipy's linear_sum_assignment on the downloaded cost matrix of the boxes that have a
+    projection.  assign="device": scores, assignment and thresholds are ONE lpf_assign_2d call -- SciPy's assignment, ties included
+    -- and a few words per detection come back instead of five [D,B] matrices; a frame beyond LPF_ASSIGN_MAX detections or
+    projected boxes takes the host route."""
     boxes_2d_per_frame, bboxes_3d_per_frame = list(boxes_2d_per_frame), list(bboxes_3d_per_frame)
     colors_per_frame = list(colors_per_frame)
     if not (len(boxes_2d_per_frame) == len(bboxes_3d_per_frame) == len(colors_per_frame)):
         raise ValueError("one entry per frame in each list")
-    scores = _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device, ctx)
+    if _assign_route(assign):
+        scores = _improved_device_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, min_score_threshold, min_iou_threshold, device, ctx)
+    else:
+        scores = _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device, ctx)
     return [_improved_assign(d, b, c, s, min_score_threshold, min_iou_threshold)
             for d, b, c, s in zip(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame, scores)]
+
+
+def linear_sum_assignment_frames(costs, front=None, device=0, ctx=None):
+    """scipy.optimize.linear_sum_assignment for a list of cost matrices in ONE native call (lpf_assign_costs): per frame (rows,
+    cols) as SciPy returns them, its choice among equally good assignments included.  front: per frame [B] integers, a column with
+    front <= 0 is left out (V5:337-341) and the columns keep their numbers.  ValueError with SciPy's message for a matrix with
+    NaN or -inf entries, or without a complete assignment."""
+    return (ctx or get_context(device)).assign_costs(costs, front)
 
 
 # ---------------------------------------------------------------------------------------
@@ -998,12 +1066,14 @@ def project_3d_bboxes_to_2d_frames(bboxes_per_frame, camera, detailed=True, devi
 
 
 def secondtest_match_frames(boxes_2d_per_frame, bboxes_raw_per_frame, colors_per_frame, camera, TrVeloToCam, verbose=True,
-                            min_score_threshold=0.3, min_iou_threshold=0.15, device=0, ctx=None):
+                            min_score_threshold=0.3, min_iou_threshold=0.15, device=0, ctx=None, assign="host"):
     """secondtest.py:599-611 and :703 for a list of frames: filter_bboxes_in_camera_view, then transform_bboxes_to_velodyne on the
     kept boxes, then improved_match_detections_to_bboxes.  Per frame (matched_pairs, filter_stats, bboxes_3d); the results and the
     printed lines equal the scalar composition of the package's three functions, and -- as there -- the kept dicts gain
     'corners_velo' in place and nothing else.  Two native calls per batch: lpf_box_views, whose front bbox2d / front of the kept
-    boxes and whose corners_velo feed the matcher, and lpf_match_2d."""
+    boxes and whose corners_velo feed the matcher, and lpf_match_2d -- or, with assign="device", lpf_assign_2d, which assigns on the
+    GPU as well (improved_match_detections_frames)."""
+    to_device = _assign_route(assign)
     boxes_2d_per_frame, colors_per_frame = list(boxes_2d_per_frame), list(colors_per_frame)
     bboxes_raw_per_frame = [list(b) if b else [] for b in bboxes_raw_per_frame]
     if not (len(boxes_2d_per_frame) == len(bboxes_raw_per_frame) == len(colors_per_frame)):
@@ -1033,7 +1103,10 @@ def secondtest_match_frames(boxes_2d_per_frame, bboxes_raw_per_frame, colors_per
                     bb[k], fr[k] = info["bbox"], 8
         rects.append((bb, fr))
     kept_per_frame = [k for k, _ in filtered]
-    scores = _improved_scores(boxes_2d_per_frame, kept_per_frame, camera, device, ctx, rects=rects)
+    if to_device:
+        scores = _improved_device_scores(boxes_2d_per_frame, kept_per_frame, camera, min_score_threshold, min_iou_threshold, device, ctx, rects=rects)
+    else:
+        scores = _improved_scores(boxes_2d_per_frame, kept_per_frame, camera, device, ctx, rects=rects)
     out = []
     for f, (kept, stats) in enumerate(filtered):
         sys.stdout.write(lines[f])
@@ -2247,10 +2320,12 @@ def process_frame(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_p
 
 
 def projectVeloToImage(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_path=None, visualizer=None,
-                       frames=None, device=0):
+                       frames=None, device=0, assign="host"):
     """V5's entry point (V5:419-571): every annotated box (no visibility filter), depth < 30 clip,
     per-mask point sets, ``bg_assigned`` and the score + Hungarian box matching; ``visualizer`` receives
-    (frame, car_point_sets, colors, remaining_points, matched_pairs) instead of the Open3D window."""
+    (frame, car_point_sets, colors, remaining_points, matched_pairs) instead of the Open3D window.  assign: where the Hungarian
+    assignment runs, "host" (scipy) or "device" (lpf_assign_2d), as improved_match_detections_frames'."""
+    to_device = _assign_route(assign)
     if segmenter is None:
         raise ValueError("projectVeloToImage needs the segmentation callable")
     root = kitti360_path or os.environ["KITTI360_DATASET"]
@@ -2259,7 +2334,10 @@ def projectVeloToImage(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti
                                  keep_all_boxes=True)
     results = []
     # the pair scores of every frame in one lpf_match_2d call; the assignment and its printed lines stay in the frame's turn
-    scores = _improved_scores([i.boxes_2d for i in items], [i.bboxes_3d for i in items], camera, device)
+    if to_device:
+        scores = _improved_device_scores([i.boxes_2d for i in items], [i.bboxes_3d for i in items], camera, device=device)
+    else:
+        scores = _improved_scores([i.boxes_2d for i in items], [i.bboxes_3d for i in items], camera, device)
     for r, item, sc in zip(run_frames(items, velo_to_rect, camera, 30.0, 10, True, 0, False, device), items, scores):
         print(f"[DEBUG] Frame {r['frame']}: {r['n_valid']} points passed validation filter")
         if r["n_valid"] == 0:

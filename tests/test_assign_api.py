@@ -1,0 +1,156 @@
+"""lpf_assign_costs / lpf_assign_2d without a GPU: the Python restatement of the solver (tests/assign_ref.py) against
+scipy.optimize.linear_sum_assignment on the seeded case list and on small matrices, the golden file against both, the header and the
+library's exports, and the pipeline's shared reporting code with pairs assigned elsewhere."""
+import contextlib
+import ctypes
+import hashlib
+import io
+import os
+import re
+
+import numpy as np
+import pytest
+from scipy.optimize import linear_sum_assignment
+
+import assign_ref as A
+from conftest import GOLDEN
+from lidar_object_detection_amd import _build, _native, pipeline
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def case_list():
+    return A.cases()
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(os.path.join(GOLDEN, "assign_golden.npz"))
+
+
+def _same(got, exp):
+    return np.array_equal(got[0], exp[0]) and np.array_equal(got[1], exp[1])
+
+
+def test_restatement_equals_scipy_on_the_case_list(case_list):
+    assert len(case_list) == 12 * 5 + 2 and {m.shape for _, m in case_list} == set(A.SHAPES)
+    for name, m in case_list:
+        st, rows, cols = A.solve(m)
+        assert st == A.OK and _same((rows, cols), linear_sum_assignment(m)), name
+        assert rows.dtype == np.int64 and cols.dtype == np.int64
+
+
+def test_restatement_equals_scipy_on_3000_small_matrices_with_both_forms_of_the_argmin():
+    wrong_first = wrong_asc = n_int = 0
+    for k, m in enumerate(A.small_cases(3000)):
+        exp = linear_sum_assignment(m)
+        assert _same(A.solve(m)[1:], exp), k
+        assert _same(A.solve(m, argmin=A._argmin_scan)[1:], exp), k
+        if k % 4 == 0 and k < 1600:                          # the tie-heavy integer kind: the two wrong solvers do disagree
+            n_int += 1
+            wrong_first += not _same(A.solve(m, first_min=True)[1:], exp)
+            wrong_asc += not _same(A.solve(m, ascending=True)[1:], exp)
+    assert n_int == 400 and wrong_first > 100 and wrong_asc > 100, (wrong_first, wrong_asc)
+
+
+def test_status_and_front():
+    m = np.array([[1.0, np.inf, 3.0], [np.inf, np.inf, 2.0]])
+    st, rows, cols = A.solve(m)
+    assert st == A.OK and _same((rows, cols), linear_sum_assignment(m))
+    bad = np.array([[1.0, np.inf], [2.0, np.inf]])
+    assert A.solve(bad)[0] == A.INFEASIBLE
+    with pytest.raises(ValueError, match="cost matrix is infeasible"):
+        linear_sum_assignment(bad)
+    for v in (np.nan, -np.inf):
+        x = np.ones((3, 4))
+        x[1, 2] = v
+        assert A.solve(x)[0] == A.INVALID
+        with pytest.raises(ValueError, match="matrix contains invalid numeric entries"):
+            linear_sum_assignment(x)
+    assert A.solve(np.zeros((0, 4)))[0] == A.OK and A.solve(np.zeros((3, 0)))[0] == A.OK
+    rng = np.random.default_rng(3)
+    c = A.matrix(rng, "int012", 9, 14)
+    front = (np.arange(14) % 3 != 1).astype(np.int32)
+    st, rows, cols = A.solve_front(c, front)
+    live = np.flatnonzero(front)
+    er, ec = linear_sum_assignment(c[:, live])
+    assert st == A.OK and np.array_equal(rows, er) and np.array_equal(cols, live[ec])
+    x = c.copy()
+    x[:, 1] = np.nan                                         # a dropped column's entries do not count
+    assert A.solve_front(x, front)[0] == A.OK
+
+
+def test_golden_case_list_is_the_seeded_one_with_scipys_answers(case_list, gold):
+    assert gold["case_names"].tolist() == [n for n, _ in case_list]
+    stored = 0
+    for name, m in case_list:
+        if "case_" + name in gold.files:
+            assert np.array_equal(gold["case_" + name], m), name
+            stored += 1
+        else:
+            assert str(gold["case_" + name + "_sha"]) == hashlib.sha256(np.ascontiguousarray(m).tobytes()).hexdigest(), name
+        st, rows, cols = A.solve(m)
+        assert np.array_equal(rows, gold["case_" + name + "_rows"]) and np.array_equal(cols, gold["case_" + name + "_cols"]), name
+    assert stored >= 45
+
+
+def test_golden_v5_runs(gold):
+    frames, counts = gold["frames"].tolist(), gold["counts"].tolist()
+    assert len(frames) == 19 and counts == [5, 32, 256]
+    tall = wide = rejected = 0
+    for f in frames:
+        for n in counts:
+            key = "%d_%d_" % (f, n)
+            assert gold[key + "dets"].shape == (n, 4) and gold[key + "dets"].dtype == np.float32
+            rows, cols = gold[key + "rows"], gold[key + "cols"]
+            assert len(rows) == len(cols) and (np.diff(rows) > 0).all() and len(set(cols.tolist())) == len(cols)
+            tall += len(rows) < n
+            wide += len(rows) == n
+            rejected += "Rejected match" in str(gold[key + "v5_stdout"])
+            assert len(gold[key + "v5_box"]) == len(gold[key + "v5_colors"])
+    assert tall >= 10 and wide >= 10 and rejected >= 10
+
+
+def test_header_declares_the_entry_points_and_the_library_exports_them():
+    text = open(os.path.join(REPO, "include", "lpf.h")).read()
+    assert re.search(r"#define LPF_ABI_VERSION 8\b", text) and re.search(r"#define LPF_ASSIGN_MAX 1024\b", text)
+    plain = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    assert re.search(r"int lpf_assign_costs\(lpf_ctx \*ctx, int F, const lpf_assign_input \*in, const lpf_assign_outputs \*out\);", plain)
+    assert re.search(r"int lpf_assign_2d\(lpf_ctx \*ctx, int F, const lpf_match2d_input \*in, const lpf_assign2d_params \*p, "
+                     r"const lpf_assign2d_outputs \*out\);", plain)
+    _build.build()
+    lib = ctypes.CDLL(_native.library_path())
+    assert hasattr(lib, "lpf_assign_costs") and hasattr(lib, "lpf_assign_2d")
+    lib.lpf_abi_version.restype = ctypes.c_int
+    assert lib.lpf_abi_version() == 8
+    assert _native.LPF_ASSIGN_MAX == 1024 == A.CAP
+    assert ctypes.sizeof(_native.AssignInput) == 40 and ctypes.sizeof(_native.AssignOutputs) == 24
+    assert ctypes.sizeof(_native.Assign2dParams) == 16 and ctypes.sizeof(_native.Assign2dOutputs) == 64
+
+
+def test_report_from_assigned_pairs_equals_the_report_from_matrices():
+    """_improved_assign with the pairs a device call returns (detection, COMPACT column, scores, accepted) against the same function
+    on the matrices: the lists and every printed line, the "Rejected match" line's compact column among them."""
+    rng = np.random.default_rng(11)
+    D, B = 9, 14
+    valid = [j for j in range(B) if j % 4 != 2]
+    m = {k: rng.random((D, len(valid))) for k in ("iou", "center", "size", "total")}
+    m["cost"] = 1.0 - m["total"]
+    boxes = [{"corners_velo": rng.random((8, 3)).tolist()} if j != 5 else {} for j in range(B)]
+    colors = [(10 * i, 20, 30) for i in range(D - 2)]
+    dets = np.zeros((D, 4), np.float32)
+    rows, cols = linear_sum_assignment(m["cost"])
+    pairs = [(int(i), int(j), float(m["iou"][i, j]), float(m["center"][i, j]), float(m["size"][i, j]), float(m["total"][i, j]),
+              bool(m["total"][i, j] >= 0.3 and m["iou"][i, j] >= 0.15)) for i, j in zip(rows, cols)]
+    a, b = io.StringIO(), io.StringIO()
+    with contextlib.redirect_stdout(a):
+        host = pipeline._improved_assign(dets, boxes, colors, (valid, m))
+    with contextlib.redirect_stdout(b):
+        dev = pipeline._improved_assign(dets, boxes, colors, (valid, pairs))
+    assert a.getvalue() == b.getvalue() and "Rejected match" in a.getvalue() and "Matched detection" in a.getvalue()
+    assert len(host) == len(dev) > 0
+    for (hc, hcol), (dc, dcol) in zip(host, dev):
+        assert np.array_equal(hc, dc) and type(hcol) is type(dcol) and np.array_equal(np.asarray(hcol), np.asarray(dcol))
+    with pytest.raises(ValueError, match="assign is"):
+        pipeline.improved_match_detections_frames([], [], [], None, assign="gpu")
