@@ -1468,6 +1468,15 @@ class LpfContext:
                     "cost": ("float64", ("P",), None)}
 
     @staticmethod
+    def _pair_offsets(who, rows, cols, nouns):
+        """The int32 [F+1] offsets (det_off, box_off) of a batch from its per-frame row and column counts; ValueError where either sum
+        does not fit (nouns: what ``who`` calls rows and columns)."""
+        det_off, box_off = (np.concatenate([[0], np.cumsum(n, dtype=np.int64)]) for n in (rows, cols))
+        if det_off[-1] > 0x7fffffff or box_off[-1] > 0x7fffffff:
+            raise ValueError("%s: %d %s and %d %s, a call takes fewer than 2^31 of each" % (who, det_off[-1], nouns[0], box_off[-1], nouns[1]))
+        return det_off.astype(np.int32), box_off.astype(np.int32)
+
+    @staticmethod
     def match2d_batch(dets, bbox2d, front):
         """The per-frame lists of match_2d checked and described: (on_device, dets dtype name, det_off int32 [F+1], box_off int32
         [F+1]).  ValueError for frame counts that differ, detections that are not float32 / float64 [D,4] of one dtype, rectangles that
@@ -1477,8 +1486,7 @@ class LpfContext:
             raise ValueError("match_2d: one entry per frame in each list, got %d detections, %d bbox2d, %d front" % (len(dets), len(bbox2d), len(front)))
         dev = LpfContext._on_gpu("match_2d", dets + bbox2d + front, "inputs")
         name = lambda a: str(a.dtype).replace("torch.", "")
-        dtypes = set()
-        det_off, box_off = np.zeros(len(dets) + 1, np.int64), np.zeros(len(dets) + 1, np.int64)
+        dtypes, D, B = set(), [], []
         for f, (d, b, fr) in enumerate(zip(dets, bbox2d, front)):
             if not dev:
                 d, b, fr = np.asarray(d), np.asarray(b), np.asarray(fr)
@@ -1495,33 +1503,19 @@ class LpfContext:
                 raise ValueError("match_2d: frame %d: GPU bbox2d must be float64 and front int32, got %s and %s" % (f, name(b), name(fr)))
             if not dev and (np.asarray(b).dtype.kind not in "fiu" or np.asarray(fr).dtype.kind not in "iub"):
                 raise ValueError("match_2d: frame %d: bbox2d must be numbers and front integers, got %s and %s" % (f, name(b), name(fr)))
-            det_off[f + 1] = det_off[f] + d.shape[0]
-            box_off[f + 1] = box_off[f] + b.shape[0]
+            D.append(d.shape[0])
+            B.append(b.shape[0])
         if len(dtypes) > 1:
             raise ValueError("match_2d: the detections of a call share one dtype, got %s" % sorted(dtypes))
-        if det_off[-1] > 0x7fffffff or box_off[-1] > 0x7fffffff:
-            raise ValueError("match_2d: %d detections and %d boxes, a call takes fewer than 2^31 of each" % (det_off[-1], box_off[-1]))
-        return dev, (dtypes.pop() if dtypes else "float32"), det_off.astype(np.int32), box_off.astype(np.int32)
+        return (dev, dtypes.pop() if dtypes else "float32", *LpfContext._pair_offsets("match_2d", D, B, ("detections", "boxes")))
 
-    def match_2d(self, dets, bbox2d, front, min_iou=0.25, weights=(0.5, 0.3, 0.2), want=("best",)):
-        """V4's and V5's detection-to-box scoring for a batch of frames in ONE native call (lpf_match_2d).  Per frame: ``dets`` [D,4]
-        float32 (the detector's boxes.xyxy) or float64, ``bbox2d`` float64 [B,4] and ``front`` int32 [B] as prepare_boxes returns them;
-        all host arrays or all GPU tensors.  ``want`` picks the outputs: "best" (V4: best_box int32 [D], the first strict maximum of the
-        IoU above min_iou into the frame's boxes or -1, and best_iou float64 [D]) and the [D,B] float64 matrices "iou", "center",
-        "size", "total", "cost" of V5 (cost = 1 - total: what V5 hands to linear_sum_assignment; a column of a box with front == 0 is
-        iou 0, scores 0, cost 1).  Returns a dict of per-frame lists, keys "best_box", "best_iou" and the matrices' names.  The
-        arithmetic is the reference's, type for type (include/lpf.h).  Host arrays: NumPy results after one host wait; GPU tensors:
-        torch tensors on their device in torch's stream order (the call only enqueues work)."""
-        want = self._want("match_2d", want, self.MATCH2D_WANT)
-        weights = tuple(float(w) for w in weights)
-        if len(weights) != 3 or not all(np.isfinite(weights)) or not np.isfinite(float(min_iou)):
-            raise ValueError("match_2d: min_iou and the three weights (iou, center, size) must be finite numbers")
+    def _match2d_input(self, dets, bbox2d, front, min_iou, weights):
+        """What match_2d and assign_2d hand to the library for their per-frame lists: (the filled Match2dInput, the torch device or None
+        for host arrays, det_off, box_off, the concatenated arrays behind the struct's pointers -- the caller holds them across the
+        call)."""
         dets, bbox2d, front = list(dets), list(bbox2d), list(front)
         dev, dt, det_off, box_off = self.match2d_batch(dets, bbox2d, front)
-        F = len(dets)
         Dtot, Btot = int(det_off[-1]), int(box_off[-1])
-        D, B = np.diff(det_off).astype(np.int64), np.diff(box_off).astype(np.int64)
-        pair_off = np.concatenate([[0], np.cumsum(D * B)]).astype(np.int64)
         device = dd = bb = ff = None
         if dev:
             import torch
@@ -1536,13 +1530,33 @@ class LpfContext:
             if Btot:
                 bb = np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in bbox2d]), dtype=np.float64)
                 ff = np.ascontiguousarray(np.concatenate([np.asarray(x) for x in front]), dtype=np.int32)
+        inp = Match2dInput()
+        inp.dets, inp.bbox2d, inp.front, inp.det_off, inp.box_off = _ptr(dd), _ptr(bb), _ptr(ff), det_off.ctypes.data, box_off.ctypes.data
+        inp.dets_f64, inp.on_device = int(dt == "float64"), int(dev)
+        inp.min_iou, (inp.w_iou, inp.w_center, inp.w_size) = float(min_iou), weights
+        return inp, device, det_off, box_off, (dd, bb, ff)
+
+    def match_2d(self, dets, bbox2d, front, min_iou=0.25, weights=(0.5, 0.3, 0.2), want=("best",)):
+        """V4's and V5's detection-to-box scoring for a batch of frames in ONE native call (lpf_match_2d).  Per frame: ``dets`` [D,4]
+        float32 (the detector's boxes.xyxy) or float64, ``bbox2d`` float64 [B,4] and ``front`` int32 [B] as prepare_boxes returns them;
+        all host arrays or all GPU tensors.  ``want`` picks the outputs: "best" (V4: best_box int32 [D], the first strict maximum of the
+        IoU above min_iou into the frame's boxes or -1, and best_iou float64 [D]) and the [D,B] float64 matrices "iou", "center",
+        "size", "total", "cost" of V5 (cost = 1 - total: what V5 hands to linear_sum_assignment; a column of a box with front == 0 is
+        iou 0, scores 0, cost 1).  Returns a dict of per-frame lists, keys "best_box", "best_iou" and the matrices' names.  The
+        arithmetic is the reference's, type for type (include/lpf.h).  Host arrays: NumPy results after one host wait; GPU tensors:
+        torch tensors on their device in torch's stream order (the call only enqueues work)."""
+        want = self._want("match_2d", want, self.MATCH2D_WANT)
+        weights = tuple(float(w) for w in weights)
+        if len(weights) != 3 or not all(np.isfinite(weights)) or not np.isfinite(float(min_iou)):
+            raise ValueError("match_2d: min_iou and the three weights (iou, center, size) must be finite numbers")
+        inp, device, det_off, box_off, held = self._match2d_input(dets, bbox2d, front, min_iou, weights)
+        F, Dtot = len(det_off) - 1, int(det_off[-1])
+        D, B = np.diff(det_off).astype(np.int64), np.diff(box_off).astype(np.int64)
+        pair_off = np.concatenate([[0], np.cumsum(D * B)]).astype(np.int64)
         mats = [w for w in want if w != "best"]
-        inp, o = Match2dInput(), Match2dOutputs()
+        o = Match2dOutputs()
         flat = self._outputs("match_2d", o, (["best_box", "best_iou"] if "best" in want else []) + mats, self._MATCH2D_OUT,
                              dict(D=Dtot, P=int(pair_off[-1])), device, fields=self._MATCH2D_FIELD)
-        inp.dets, inp.bbox2d, inp.front, inp.det_off, inp.box_off = _ptr(dd), _ptr(bb), _ptr(ff), det_off.ctypes.data, box_off.ctypes.data
-        inp.dets_f64, inp.on_device = int(dt == "float64"), o.on_device
-        inp.min_iou, (inp.w_iou, inp.w_center, inp.w_size) = float(min_iou), weights
         if F and Dtot:
             self._call_in_order(device, self._lib.lpf_match_2d, F, ctypes.byref(inp), ctypes.byref(o))
         res = {k: [flat[k][det_off[f]:det_off[f + 1]] for f in range(F)] for k in ("best_box", "best_iou") if k in flat}
@@ -1569,7 +1583,6 @@ class LpfContext:
             raise ValueError("assign_costs: one entry per frame in each list, got %d costs and %d front" % (F, len(fronts)))
         dev = self._on_gpu("assign_costs", costs + (fronts or []), "inputs")
         name = lambda a: str(a.dtype).replace("torch.", "")
-        det_off, box_off = np.zeros(F + 1, np.int64), np.zeros(F + 1, np.int64)
         if not dev:
             costs = [np.asarray(m) for m in costs]
             fronts = None if fronts is None else [np.asarray(a) for a in fronts]
@@ -1586,11 +1599,7 @@ class LpfContext:
                     raise ValueError("assign_costs: frame %d: front must be [B] = [%d], got %s" % (f, m.shape[1], tuple(fr.shape)))
                 if (dev and name(fr) != "int32") or (not dev and fr.dtype.kind not in "iub"):
                     raise ValueError("assign_costs: frame %d: front must be integers (int32 on the GPU), got %s" % (f, name(fr)))
-            det_off[f + 1] = det_off[f] + m.shape[0]
-            box_off[f + 1] = box_off[f] + m.shape[1]
-        if det_off[-1] > 0x7fffffff or box_off[-1] > 0x7fffffff:
-            raise ValueError("assign_costs: %d rows and %d columns, a call takes fewer than 2^31 of each" % (det_off[-1], box_off[-1]))
-        det_off, box_off = det_off.astype(np.int32), box_off.astype(np.int32)
+        det_off, box_off = self._pair_offsets("assign_costs", [m.shape[0] for m in costs], [m.shape[1] for m in costs], ("rows", "columns"))
         Dtot, Btot = int(det_off[-1]), int(box_off[-1])
         device = cc = ff = None
         if dev:
@@ -1642,29 +1651,10 @@ class LpfContext:
         thr = (float(min_score_threshold), float(min_iou_threshold))
         if len(weights) != 3 or not all(np.isfinite(weights)) or any(np.isnan(thr)):
             raise ValueError("assign_2d: the three weights (iou, center, size) must be finite and the two thresholds numbers")
-        dets, bbox2d, front = list(dets), list(bbox2d), list(front)
-        dev, dt, det_off, box_off = self.match2d_batch(dets, bbox2d, front)
-        F = len(dets)
-        Dtot, Btot = int(det_off[-1]), int(box_off[-1])
-        device = dd = bb = ff = None
-        if dev:
-            import torch
-            device = dets[0].device
-            if Dtot:
-                dd = torch.cat([x.reshape(-1, 4) for x in dets]).contiguous()
-            if Btot:
-                bb, ff = torch.cat([x.reshape(-1, 4) for x in bbox2d]).contiguous(), torch.cat(front).contiguous()
-        else:
-            if Dtot:
-                dd = np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in dets]), dtype=dt)
-            if Btot:
-                bb = np.ascontiguousarray(np.concatenate([np.asarray(x).reshape(-1, 4) for x in bbox2d]), dtype=np.float64)
-                ff = np.ascontiguousarray(np.concatenate([np.asarray(x) for x in front]), dtype=np.int32)
-        inp, prm, o = Match2dInput(), Assign2dParams(*thr), Assign2dOutputs()
-        flat = self._outputs("assign_2d", o, want, self._ASSIGN2D_OUT, dict(D=Dtot, F=F), device, fields=self._MATCH2D_FIELD)
-        inp.dets, inp.bbox2d, inp.front, inp.det_off, inp.box_off = _ptr(dd), _ptr(bb), _ptr(ff), det_off.ctypes.data, box_off.ctypes.data
-        inp.dets_f64, inp.on_device = int(dt == "float64"), o.on_device
-        inp.min_iou, (inp.w_iou, inp.w_center, inp.w_size) = 0.0, weights
+        inp, device, det_off, box_off, held = self._match2d_input(dets, bbox2d, front, 0.0, weights)
+        F = len(det_off) - 1
+        prm, o = Assign2dParams(*thr), Assign2dOutputs()
+        flat = self._outputs("assign_2d", o, want, self._ASSIGN2D_OUT, dict(D=int(det_off[-1]), F=F), device, fields=self._MATCH2D_FIELD)
         if F:
             self._call_in_order(device, self._lib.lpf_assign_2d, F, ctypes.byref(inp), ctypes.byref(prm), ctypes.byref(o))
         res = {k: [flat[k][det_off[f]:det_off[f + 1]] for f in range(F)] for k in want if k != "status"}

@@ -683,6 +683,58 @@ int check_offsets(lpf_ctx *c, const char *who, const char *name, const int32_t *
     return LPF_OK;
 }
 
+// ---- what lpf_match_2d and lpf_assign_costs / lpf_assign_2d share on the host: a batch of frames of D x B pairs -------------------------
+// The arrays and weights of a lpf_match2d_input (who: the call, as the refusals say it).  arrays: det_off and box_off are there to be
+// read -- they are checked here, and dets / bbox2d / front against their totals.  with_min_iou: min_iou is in use and has to be finite.
+int check_m2_input(lpf_ctx *c, const char *who, int F, const lpf_match2d_input *in, bool arrays, bool with_min_iou)
+{
+    int rc;
+    if (arrays) {
+        if ((rc = check_offsets(c, who, "det_off", in->det_off, F)) || (rc = check_offsets(c, who, "box_off", in->box_off, F))) return rc;
+        const int Dtot = in->det_off[F], Btot = in->box_off[F];
+        if ((Dtot > 0 && !in->dets) || (Btot > 0 && (!in->bbox2d || !in->front)))
+            return fail(c, LPF_ERR_ARG, "%s: dets=%p bbox2d=%p front=%p with %d detections and %d boxes (dets is required with detections, bbox2d and front with boxes)",
+                        who, in->dets, (const void *)in->bbox2d, (const void *)in->front, Dtot, Btot);
+    }
+    const bool weights = std::isfinite(in->w_iou) && std::isfinite(in->w_center) && std::isfinite(in->w_size);
+    if (with_min_iou && !(weights && std::isfinite(in->min_iou)))
+        return fail(c, LPF_ERR_ARG, "%s: min_iou=%g weights=%g %g %g must be finite", who, in->min_iou, in->w_iou, in->w_center, in->w_size);
+    if (!weights) return fail(c, LPF_ERR_ARG, "%s: weights=%g %g %g must be finite", who, in->w_iou, in->w_center, in->w_size);
+    return LPF_OK;
+}
+
+// The pair table of a batch and its ranges of consecutive frames (plan_ranges; bytes(t): what frame t adds to a range's staging and
+// scratch), with the most detections, boxes, pairs and frames of any range: what the call's buffers are reserved for.
+struct M2Range { size_t fa, nf, d0, nd, b0, nb, p0, np; int most_rows; };   // first frame and count; detections, boxes, pairs; the tallest frame
+struct M2Plan { std::vector<LpfM2Frame> tab; std::vector<M2Range> ranges; size_t most_d = 0, most_b = 0, most_p = 0, most_f = 0; };
+template <typename Bytes> M2Plan m2_plan(const int32_t *det_off, const int32_t *box_off, int F, size_t most_frames, Bytes &&bytes)
+{
+    M2Plan P;
+    P.tab.resize((size_t)F + 1);                              // (one past the end: where the detections, boxes and pairs end)
+    std::vector<size_t> cost((size_t)F + 1, 0);               // cost[f]: the bytes of the frames before f
+    long long p = 0;
+    for (int f = 0; f < F; ++f) {
+        LpfM2Frame &t = P.tab[(size_t)f];
+        t.d0 = det_off[f]; t.D = det_off[f + 1] - t.d0;
+        t.b0 = box_off[f]; t.B = box_off[f + 1] - t.b0;
+        t.p0 = p;
+        p += (long long)t.D * t.B;
+        cost[(size_t)f + 1] = cost[(size_t)f] + bytes(t);
+    }
+    P.tab[(size_t)F] = {det_off[F], 0, box_off[F], 0, p};
+    for (const Span &r : plan_ranges((size_t)F, most_frames, [&](size_t f, size_t n) { return cost[f + n] - cost[f]; })) {
+        const LpfM2Frame &a = P.tab[r.first], &b = P.tab[r.first + r.count];
+        M2Range R = {r.first, r.count, (size_t)a.d0, (size_t)(b.d0 - a.d0), (size_t)a.b0, (size_t)(b.b0 - a.b0), (size_t)a.p0, (size_t)(b.p0 - a.p0), 0};
+        for (size_t f = R.fa; f < R.fa + R.nf; ++f) R.most_rows = std::max(R.most_rows, P.tab[f].D);
+        P.most_d = std::max(P.most_d, R.nd); P.most_b = std::max(P.most_b, R.nb); P.most_p = std::max(P.most_p, R.np); P.most_f = std::max(P.most_f, R.nf);
+        P.ranges.push_back(R);
+    }
+    return P;
+}
+
+// Every *_base of a range by one rule: a staged array begins at the range's first item, the caller's own at the batch's
+template <typename T> T range_base(bool staged, T first) { return staged ? first : (T)0; }
+
 // The box set in force, for a call `who` that tests the points of F frames against it: there must be one, set for F frames.
 int boxes_in_force(lpf_ctx *c, const char *who, int F, lpf_ctx::BoxSet **BX)
 {
@@ -2767,13 +2819,7 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
         return fail(c, LPF_ERR_ARG, "match_2d: det_off=%p box_off=%p (both are required, F + 1 entries each)", (const void *)in->det_off, (const void *)in->box_off);
     if (in->det_off[0] < 0 || in->box_off[0] < 0)
         return fail(c, LPF_ERR_ARG, "match_2d: det_off[0]=%d box_off[0]=%d (offsets start at 0 or above)", in->det_off[0], in->box_off[0]);
-    if ((rc = check_offsets(c, "match_2d", "det_off", in->det_off, F)) || (rc = check_offsets(c, "match_2d", "box_off", in->box_off, F))) return rc;
-    const int Dtot = in->det_off[F], Btot = in->box_off[F];
-    if ((Dtot > 0 && !in->dets) || (Btot > 0 && (!in->bbox2d || !in->front)))
-        return fail(c, LPF_ERR_ARG, "match_2d: dets=%p bbox2d=%p front=%p with %d detections and %d boxes (dets is required with detections, bbox2d and front with boxes)",
-                    in->dets, (const void *)in->bbox2d, (const void *)in->front, Dtot, Btot);
-    if (!std::isfinite(in->min_iou) || !std::isfinite(in->w_iou) || !std::isfinite(in->w_center) || !std::isfinite(in->w_size))
-        return fail(c, LPF_ERR_ARG, "match_2d: min_iou=%g weights=%g %g %g must be finite", in->min_iou, in->w_iou, in->w_center, in->w_size);
+    if ((rc = check_m2_input(c, "match_2d", F, in, true, true))) return rc;
     double *const mats_out[5] = {out->iou, out->center_score, out->size_score, out->total_score, out->cost};
     int nmat = 0;
     for (double *m : mats_out) nmat += m != nullptr;
@@ -2786,56 +2832,36 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
     const bool host_in = !in->on_device, host_out = !out->on_device;
     const size_t esz = in->dets_f64 ? 8 : 4;
 
-    // ---- the frame table and the ranges of frames; cost[f]: the bytes staged for the frames before f ---------------------------------
-    std::vector<LpfM2Frame> tab((size_t)F + 1);               // (one past the end: where the pairs end)
-    std::vector<size_t> cost((size_t)F + 1, 0);
-    long long p = 0;
-    for (int f = 0; f < F; ++f) {
-        LpfM2Frame &t = tab[(size_t)f];
-        t.d0 = in->det_off[f]; t.D = in->det_off[f + 1] - t.d0;
-        t.b0 = in->box_off[f]; t.B = in->box_off[f + 1] - t.b0;
-        t.p0 = p;
-        p += (long long)t.D * t.B;
-        cost[(size_t)f + 1] = cost[(size_t)f] + (host_in ? (size_t)t.D * 4 * esz + (size_t)t.B * 36 : 0) +
-                              (host_out ? (size_t)t.D * 12 + (size_t)nmat * 8 * (size_t)t.D * (size_t)t.B : 0);
-    }
-    tab[(size_t)F].p0 = p;
-    const std::vector<Span> ranges = plan_ranges((size_t)F, LPF_M2_MAX_FRAMES, [&](size_t f, size_t n) { return cost[f + n] - cost[f]; });
-    const size_t most_d = largest(ranges, [&](size_t f, size_t n) { return in->det_off[f + n] - in->det_off[f]; });
-    const size_t most_b = largest(ranges, [&](size_t f, size_t n) { return in->box_off[f + n] - in->box_off[f]; });
-    const size_t most_p = largest(ranges, [&](size_t f, size_t n) { return tab[f + n].p0 - tab[f].p0; });
-    if ((rc = upload_table(c, D.tab, tab.data(), (size_t)F))) return rc;
+    // ---- the frame table and the ranges of frames: a frame stages its host inputs and host outputs --------------------------------------
+    const M2Plan P = m2_plan(in->det_off, in->box_off, F, LPF_M2_MAX_FRAMES, [&](const LpfM2Frame &t) {
+        return (host_in ? (size_t)t.D * 4 * esz + (size_t)t.B * 36 : 0) + (host_out ? (size_t)t.D * 12 + (size_t)nmat * 8 * (size_t)t.D * (size_t)t.B : 0);
+    });
+    if ((rc = upload_table(c, D.tab, P.tab.data(), (size_t)F))) return rc;
 
     LpfM2Params Q;
     memset(&Q, 0, sizeof Q);
     Q.min_iou = in->min_iou; Q.w_iou = in->w_iou; Q.w_center = in->w_center; Q.w_size = in->w_size;
     Stage I(host_in), O(host_out);
-    I.add(Q.dets, in->dets, 4 * esz, most_d);
-    I.add(Q.bbox2d, in->bbox2d, 32, most_b);
-    I.add(Q.front, in->front, 4, most_b);
+    I.add(Q.dets, in->dets, 4 * esz, P.most_d);
+    I.add(Q.bbox2d, in->bbox2d, 32, P.most_b);
+    I.add(Q.front, in->front, 4, P.most_b);
     if ((rc = I.commit(c, D.in))) return rc;
-    O.add(Q.best_box, out->best_box, 4, most_d);
-    O.add(Q.best_iou, out->best_iou, 8, most_d);
-    O.add(Q.iou, out->iou, 8, most_p);
-    O.add(Q.center, out->center_score, 8, most_p);
-    O.add(Q.size, out->size_score, 8, most_p);
-    O.add(Q.total, out->total_score, 8, most_p);
-    O.add(Q.cost, out->cost, 8, most_p);
+    O.add(Q.best_box, out->best_box, 4, P.most_d);
+    O.add(Q.best_iou, out->best_iou, 8, P.most_d);
+    O.add(Q.iou, out->iou, 8, P.most_p);
+    O.add(Q.center, out->center_score, 8, P.most_p);
+    O.add(Q.size, out->size_score, 8, P.most_p);
+    O.add(Q.total, out->total_score, 8, P.most_p);
+    O.add(Q.cost, out->cost, 8, P.most_p);
     if ((rc = O.commit(c, D.out))) return rc;
     const bool scores = out->center_score || out->size_score || out->total_score || out->cost;
-    for (const Span &r : ranges) {
-        const size_t fa = r.first, fb = fa + r.count;
-        const size_t d0 = (size_t)in->det_off[fa], nd = (size_t)in->det_off[fb] - d0, b0 = (size_t)in->box_off[fa], nb = (size_t)in->box_off[fb] - b0;
-        const size_t p0 = (size_t)tab[fa].p0, np = (size_t)tab[fb].p0 - p0;
-        int most_rows = 0;
-        for (size_t f = fa; f < fb; ++f) most_rows = std::max(most_rows, tab[f].D);
-        if (most_rows == 0) continue;                       // no detections in the range: nothing to write
-        Q.frames = (const LpfM2Frame *)D.tab.p + fa;
-        if ((rc = I.in(c, {{d0, nd}, {b0, nb}, {b0, nb}}))) return rc;                               // dets | bbox2d | front
-        // staged arrays begin at the range's first detection, box and pair; the caller's own at the batch's
-        Q.det_base = host_in ? (int)d0 : 0; Q.box_base = host_in ? (int)b0 : 0;
-        Q.det_out_base = host_out ? (int)d0 : 0; Q.pair_base = host_out ? (long long)p0 : 0;
-        const dim3 g((unsigned)((most_rows + LPF_M2_ROWS - 1) / LPF_M2_ROWS), (unsigned)r.count);
+    for (const M2Range &R : P.ranges) {
+        if (R.most_rows == 0) continue;                     // no detections in the range: nothing to write
+        Q.frames = (const LpfM2Frame *)D.tab.p + R.fa;
+        if ((rc = I.in(c, {{R.d0, R.nd}, {R.b0, R.nb}, {R.b0, R.nb}}))) return rc;                   // dets | bbox2d | front
+        Q.det_base = range_base(host_in, (int)R.d0); Q.box_base = range_base(host_in, (int)R.b0);
+        Q.det_out_base = range_base(host_out, (int)R.d0); Q.pair_base = range_base(host_out, (long long)R.p0);
+        const dim3 g((unsigned)((R.most_rows + LPF_M2_ROWS - 1) / LPF_M2_ROWS), (unsigned)R.nf);
         if (in->dets_f64) {
             if (scores) hipLaunchKernelGGL((lpf_m2_pairs<double, true>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
             else hipLaunchKernelGGL((lpf_m2_pairs<double, false>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
@@ -2845,7 +2871,8 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
         }
         LPF_HIP(c, hipGetLastError());
         // best_box | best_iou | iou | center | size | total | cost
-        if ((rc = O.back(c, {{d0, nd}, {d0, nd}, {p0, np}, {p0, np}, {p0, np}, {p0, np}, {p0, np}}))) return rc;
+        const Span dets = {R.d0, R.nd}, pairs = {R.p0, R.np};
+        if ((rc = O.back(c, {dets, dets, pairs, pairs, pairs, pairs, pairs}))) return rc;
     }
     if (host_in || host_out) LPF_HIP(c, host_wait(c));       // host outputs filled, host inputs free to be reused
     return LPF_OK;
@@ -2869,94 +2896,74 @@ static int assign_batch(lpf_ctx *c, const char *who, int F, const int32_t *det_o
     if (F == 0) return LPF_OK;
     const size_t esz = m2 && m2->dets_f64 ? 8 : 4;
 
-    // ---- the frame table and the ranges of frames; cost[f]: the bytes of scratch and staging of the frames before f ---------------------
-    std::vector<LpfM2Frame> tab((size_t)F + 1);               // (one past the end: where the pairs end)
-    std::vector<size_t> cost((size_t)F + 1, 0);
-    long long p = 0;
     for (int f = 0; f < F; ++f) {
-        LpfM2Frame &t = tab[(size_t)f];
-        t.d0 = det_off[f]; t.D = det_off[f + 1] - t.d0;
-        t.b0 = box_off[f]; t.B = box_off[f + 1] - t.b0;
-        t.p0 = p;
-        p += (long long)t.D * t.B;
-        int live = t.B;                                       // (columns in device memory are not counted here: all of them may be live)
-        if (front && host_in) {
-            live = 0;
-            for (int b = 0; b < t.B; ++b) live += front[t.b0 + b] > 0;
-        }
-        if (t.D > LPF_ASSIGN_MAX || live > LPF_ASSIGN_MAX)
+        const int rows = det_off[f + 1] - det_off[f], cols = box_off[f + 1] - box_off[f];
+        int live = cols;                                      // (columns in device memory are not counted here: all of them may be live)
+        if (front && host_in) live = (int)std::count_if(front + box_off[f], front + box_off[f + 1], [](int32_t v) { return v > 0; });
+        if (rows > LPF_ASSIGN_MAX || live > LPF_ASSIGN_MAX)
             return fail(c, LPF_ERR_ARG, "%s: frame %d: %d rows and %d live columns, a frame takes at most LPF_ASSIGN_MAX = %d of either", who, f,
-                        t.D, live, LPF_ASSIGN_MAX);
-        const size_t pairs = (size_t)t.D * (size_t)t.B;
-        cost[(size_t)f + 1] = cost[(size_t)f] + pairs * 8 + (size_t)t.B * 4 + 4 +
-                              (host_in ? (m2 ? (size_t)t.D * 4 * esz + (size_t)t.B * 36 : pairs * 8 + (size_t)t.B * 4) : 0) +
-                              (size_t)t.D * (m2 ? 40 : 4) + 4;
+                        rows, live, LPF_ASSIGN_MAX);
     }
-    tab[(size_t)F].p0 = p;
-    if (!m2 && p > 0 && !cost_in) return fail(c, LPF_ERR_ARG, "%s: cost=%p with %lld pairs (required with pairs)", who, (const void *)cost_in, p);
+    // ---- the frame table and the ranges of frames: a frame's scratch, its staged host inputs, its outputs ------------------------------
+    const M2Plan P = m2_plan(det_off, box_off, F, LPF_AS_MAX_FRAMES, [&](const LpfM2Frame &t) {
+        const size_t pairs = (size_t)t.D * (size_t)t.B, staged = m2 ? (size_t)t.D * 4 * esz + (size_t)t.B * 36 : pairs * 8 + (size_t)t.B * 4;
+        return pairs * 8 + (size_t)t.B * 4 + 4 + (host_in ? staged : 0) + (size_t)t.D * (m2 ? 40 : 4) + 4;
+    });
+    const long long pairs = P.tab[(size_t)F].p0;
+    if (!m2 && pairs > 0 && !cost_in) return fail(c, LPF_ERR_ARG, "%s: cost=%p with %lld pairs (required with pairs)", who, (const void *)cost_in, pairs);
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
 
     lpf_ctx::CallBufs &D = c->asgn;
-    const std::vector<Span> ranges = plan_ranges((size_t)F, LPF_AS_MAX_FRAMES, [&](size_t f, size_t n) { return cost[f + n] - cost[f]; });
-    const size_t most_d = largest(ranges, [&](size_t f, size_t n) { return det_off[f + n] - det_off[f]; });
-    const size_t most_b = largest(ranges, [&](size_t f, size_t n) { return box_off[f + n] - box_off[f]; });
-    const size_t most_p = largest(ranges, [&](size_t f, size_t n) { return tab[f + n].p0 - tab[f].p0; });
-    const size_t most_f = largest(ranges, [](size_t, size_t n) { return n; });
-    if ((rc = upload_table(c, D.tab, tab.data(), (size_t)F))) return rc;
+    if ((rc = upload_table(c, D.tab, P.tab.data(), (size_t)F))) return rc;
 
     LpfAsParams Q;
     memset(&Q, 0, sizeof Q);
     if (m2) { Q.w_iou = m2->w_iou; Q.w_center = m2->w_center; Q.w_size = m2->w_size; Q.min_score = prm->min_score_threshold; Q.min_iou = prm->min_iou_threshold; }
     Stage I(host_in), S(false), O(host_out);
-    I.add(Q.cost, m2 ? nullptr : cost_in, 8, most_p);
-    I.add(Q.dets, m2 ? m2->dets : nullptr, 4 * esz, most_d);
-    I.add(Q.bbox2d, m2 ? m2->bbox2d : nullptr, 32, most_b);
-    I.add(Q.front, front, 4, most_b);
+    I.add(Q.cost, m2 ? nullptr : cost_in, 8, P.most_p);
+    I.add(Q.dets, m2 ? m2->dets : nullptr, 4 * esz, P.most_d);
+    I.add(Q.bbox2d, m2 ? m2->bbox2d : nullptr, 32, P.most_b);
+    I.add(Q.front, front, 4, P.most_b);
     if ((rc = I.commit(c, D.in))) return rc;
-    S.add(Q.scratch, nullptr, 8, most_p, true);
-    S.add(Q.colmap, nullptr, 4, most_b, true);
-    S.add(Q.nlive, nullptr, 4, most_f, true);
+    S.add(Q.scratch, nullptr, 8, P.most_p, true);
+    S.add(Q.colmap, nullptr, 4, P.most_b, true);
+    S.add(Q.nlive, nullptr, 4, P.most_f, true);
     if ((rc = S.commit(c, D.pts))) return rc;
-    O.add(Q.col, col_out, 4, most_d, true);                  // (the call needs both itself)
-    O.add(Q.status, status_out, 4, most_f, true);
-    O.add(Q.iou, o2 ? o2->iou : nullptr, 8, most_d);
-    O.add(Q.center, o2 ? o2->center_score : nullptr, 8, most_d);
-    O.add(Q.size, o2 ? o2->size_score : nullptr, 8, most_d);
-    O.add(Q.total, o2 ? o2->total_score : nullptr, 8, most_d);
-    O.add(Q.accepted, o2 ? o2->accepted : nullptr, 4, most_d);
+    O.add(Q.col, col_out, 4, P.most_d, true);                  // (the call needs both itself)
+    O.add(Q.status, status_out, 4, P.most_f, true);
+    O.add(Q.iou, o2 ? o2->iou : nullptr, 8, P.most_d);
+    O.add(Q.center, o2 ? o2->center_score : nullptr, 8, P.most_d);
+    O.add(Q.size, o2 ? o2->size_score : nullptr, 8, P.most_d);
+    O.add(Q.total, o2 ? o2->total_score : nullptr, 8, P.most_d);
+    O.add(Q.accepted, o2 ? o2->accepted : nullptr, 4, P.most_d);
     if ((rc = O.commit(c, D.out))) return rc;
     const bool col_staged = host_out || !col_out, status_staged = host_out || !status_out;
     int *const status0 = Q.status;
     const bool finish = m2 && (Q.iou || Q.center || Q.size || Q.total || Q.accepted);
-    for (const Span &r : ranges) {
-        const size_t fa = r.first, fb = fa + r.count;
-        const size_t d0 = (size_t)det_off[fa], nd = (size_t)det_off[fb] - d0, b0 = (size_t)box_off[fa], nb = (size_t)box_off[fb] - b0;
-        const size_t p0 = (size_t)tab[fa].p0, np = (size_t)tab[fb].p0 - p0;
-        int most_rows = 0;
-        for (size_t f = fa; f < fb; ++f) most_rows = std::max(most_rows, tab[f].D);
-        Q.frames = (const LpfM2Frame *)D.tab.p + fa;
-        if ((rc = I.in(c, {{p0, np}, {d0, nd}, {b0, nb}, {b0, nb}}))) return rc;                     // cost | dets | bbox2d | front
-        // staged arrays begin at the range's first detection, box, pair and frame; the caller's own at the batch's
-        Q.det_base = host_in ? (int)d0 : 0; Q.box_base = host_in ? (int)b0 : 0; Q.pair_base = host_in ? (long long)p0 : 0;
-        Q.scr_pair_base = (long long)p0; Q.scr_box_base = (int)b0;
-        Q.col_base = col_staged ? (int)d0 : 0; Q.score_base = host_out ? (int)d0 : 0;
-        Q.status = status0 + (status_staged ? 0 : fa);
-        LPF_HIP(c, hipMemsetAsync(Q.status, 0, r.count * 4, c->stream));
-        const dim3 g((unsigned)std::max((most_rows + LPF_M2_ROWS - 1) / LPF_M2_ROWS, 1), (unsigned)r.count);
+    for (const M2Range &R : P.ranges) {
+        const Span dets = {R.d0, R.nd}, boxes = {R.b0, R.nb};
+        Q.frames = (const LpfM2Frame *)D.tab.p + R.fa;
+        if ((rc = I.in(c, {{R.p0, R.np}, dets, boxes, boxes}))) return rc;                           // cost | dets | bbox2d | front
+        Q.det_base = range_base(host_in, (int)R.d0); Q.box_base = range_base(host_in, (int)R.b0); Q.pair_base = range_base(host_in, (long long)R.p0);
+        Q.scr_pair_base = (long long)R.p0; Q.scr_box_base = (int)R.b0;                               // (the scratch is the range's own)
+        Q.col_base = range_base(col_staged, (int)R.d0); Q.score_base = range_base(host_out, (int)R.d0);
+        Q.status = status0 + (status_staged ? 0 : R.fa);      // (a pointer, not a base: the caller's own array is entered at the range's first frame)
+        LPF_HIP(c, hipMemsetAsync(Q.status, 0, R.nf * 4, c->stream));
+        const dim3 g((unsigned)std::max((R.most_rows + LPF_M2_ROWS - 1) / LPF_M2_ROWS, 1), (unsigned)R.nf);
         if (!m2) hipLaunchKernelGGL((lpf_as_pack<0>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
         else if (m2->dets_f64) hipLaunchKernelGGL((lpf_as_pack<2>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
         else hipLaunchKernelGGL((lpf_as_pack<1>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
         LPF_HIP(c, hipGetLastError());
-        hipLaunchKernelGGL(lpf_as_solve, dim3((unsigned)r.count), dim3(64), 0, c->stream, Q);
+        hipLaunchKernelGGL(lpf_as_solve, dim3((unsigned)R.nf), dim3(64), 0, c->stream, Q);
         LPF_HIP(c, hipGetLastError());
         if (finish) {
-            if (m2->dets_f64) hipLaunchKernelGGL((lpf_as_finish<double>), dim3((unsigned)r.count), dim3(LPF_BLOCK), 0, c->stream, Q);
-            else hipLaunchKernelGGL((lpf_as_finish<float>), dim3((unsigned)r.count), dim3(LPF_BLOCK), 0, c->stream, Q);
+            if (m2->dets_f64) hipLaunchKernelGGL((lpf_as_finish<double>), dim3((unsigned)R.nf), dim3(LPF_BLOCK), 0, c->stream, Q);
+            else hipLaunchKernelGGL((lpf_as_finish<float>), dim3((unsigned)R.nf), dim3(LPF_BLOCK), 0, c->stream, Q);
             LPF_HIP(c, hipGetLastError());
         }
         // col | status | iou | center | size | total | accepted
-        if ((rc = O.back(c, {{d0, nd}, {fa, r.count}, {d0, nd}, {d0, nd}, {d0, nd}, {d0, nd}, {d0, nd}}))) return rc;
+        if ((rc = O.back(c, {dets, {R.fa, R.nf}, dets, dets, dets, dets, dets}))) return rc;
     }
     if (host_in || host_out) LPF_HIP(c, host_wait(c));       // host outputs filled, host inputs free to be reused
     return LPF_OK;
@@ -2977,15 +2984,7 @@ int lpf_assign_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_assi
     if ((rc = enter(c, "lpf_assign_2d", false))) return rc;
     if (!in || !p || !out || F < 0)
         return fail(c, LPF_ERR_ARG, "assign_2d: in=%p p=%p out=%p F=%d", (const void *)in, (const void *)p, (const void *)out, F);
-    if (in->det_off && in->box_off && F > 0) {
-        if ((rc = check_offsets(c, "assign_2d", "det_off", in->det_off, F)) || (rc = check_offsets(c, "assign_2d", "box_off", in->box_off, F))) return rc;
-        const int Dtot = in->det_off[F], Btot = in->box_off[F];
-        if ((Dtot > 0 && !in->dets) || (Btot > 0 && (!in->bbox2d || !in->front)))
-            return fail(c, LPF_ERR_ARG, "assign_2d: dets=%p bbox2d=%p front=%p with %d detections and %d boxes (dets is required with detections, bbox2d and front with boxes)",
-                        in->dets, (const void *)in->bbox2d, (const void *)in->front, Dtot, Btot);
-    }
-    if (!std::isfinite(in->w_iou) || !std::isfinite(in->w_center) || !std::isfinite(in->w_size))
-        return fail(c, LPF_ERR_ARG, "assign_2d: weights=%g %g %g must be finite", in->w_iou, in->w_center, in->w_size);
+    if ((rc = check_m2_input(c, "assign_2d", F, in, in->det_off && in->box_off && F > 0, false))) return rc;   // (the rest is assign_batch's to refuse)
     if (std::isnan(p->min_score_threshold) || std::isnan(p->min_iou_threshold))
         return fail(c, LPF_ERR_ARG, "assign_2d: min_score_threshold=%g min_iou_threshold=%g must be numbers", p->min_score_threshold, p->min_iou_threshold);
     return assign_batch(c, "assign_2d", F, in->det_off, in->box_off, nullptr, in, in->front, !in->on_device, p, out->box_of_det, out->status, out,

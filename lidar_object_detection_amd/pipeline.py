@@ -532,10 +532,21 @@ def improved_match_detections_to_bboxes(boxes_2d, bboxes_3d, mask_colors, camera
             cost[i, j] = 1 - score
             details[(i, j)] = det
     rows, cols = linear_sum_assignment(cost)
-    used = set()
+    pairs = []
     for i, j in zip(rows, cols):
         sc = details[(i, j)]
-        if sc["total_score"] >= min_score_threshold and sc["iou"] >= min_iou_threshold:
+        pairs.append((i, j, sc["iou"], sc["center_score"], sc["size_score"], sc["total_score"],
+                      sc["total_score"] >= min_score_threshold and sc["iou"] >= min_iou_threshold))
+    return _report_matches(bboxes_3d, mask_colors, valid_idx, pairs)
+
+
+def _report_matches(bboxes_3d, mask_colors, valid_idx, pairs):
+    """V5's matcher from its assignment on (V5:366-416), for the scalar function and the batched ones alike: the returned list and
+    every printed line.  pairs: the assigned pairs in row order as (detection, column, iou, center, size, total, accepted); valid_idx:
+    the box of each column -- V5's columns are the boxes that have a projection."""
+    matched, used = [], set()
+    for i, j, iou, center, size, total, accepted in pairs:
+        if accepted:
             orig = valid_idx[j]
             used.add(orig)
             bbox = bboxes_3d[orig]
@@ -547,12 +558,11 @@ def improved_match_detections_to_bboxes(boxes_2d, bboxes_3d, mask_colors, camera
                     color = np.array([1.0, 0.0, 0.0])
                 matched.append((np.array(bbox["corners_velo"]), color))
                 print(f"[INFO] Matched detection {i} with 3D bbox {orig}")
-                print(f"        Scores - IoU: {sc['iou']:.3f}, Center: {sc['center_score']:.3f}, "
-                      f"Size: {sc['size_score']:.3f}, Total: {sc['total_score']:.3f}")
+                print(f"        Scores - IoU: {iou:.3f}, Center: {center:.3f}, Size: {size:.3f}, Total: {total:.3f}")
             else:
                 print(f"[WARN] No Velodyne corners found for bbox {orig}")
         else:
-            print(f"[INFO] Rejected match det{i}-bbox{j}: score={sc['total_score']:.3f}, IoU={sc['iou']:.3f}")
+            print(f"[INFO] Rejected match det{i}-bbox{j}: score={total:.3f}, IoU={iou:.3f}")
     for i, bbox in enumerate(bboxes_3d):
         if i not in used and "corners_velo" in bbox:
             matched.append((np.array(bbox["corners_velo"]), [0.7, 0.7, 0.7]))
@@ -606,15 +616,46 @@ def _match2d_rects(bboxes_per_frame, camera, ctx):
     return rects
 
 
-def _match2d_call(dets, rects, ctx, want, min_iou=0.25):
-    """ctx.match_2d over the frames that have detections and boxes, one call per detection dtype: per frame the dict of that frame's
-    outputs, or None for a frame the matchers leave before they score anything."""
-    out = [None] * len(dets)
+def _per_frame_lists(*lists):
+    """the per-frame arguments of a batched matcher as lists, one entry per frame in each"""
+    lists = [list(x) for x in lists]
+    if len({len(x) for x in lists}) > 1:
+        raise ValueError("one entry per frame in each list")
+    return lists
+
+
+def _match2d_plan(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device=0, ctx=None, rects=None):
+    """What the batched matchers hand to the native calls: (live, dets, rects, ctx).  live[f]: the frame has detections and boxes (the
+    matchers leave any other frame before they score); dets[f]: its detections (_match2d_dets), None for a dead frame; rects[f]: the
+    (bbox2d, front) of every dict of its list, none for a dead frame -- the caller's ``rects`` where it has them already
+    (lpf_box_views'), else _match2d_rects'.  Without a live frame rects and ctx are None: there is nothing to call."""
+    live = [bool(b) and d is not None and len(d) > 0 for d, b in zip(boxes_2d_per_frame, bboxes_3d_per_frame)]
+    dets = [_match2d_dets(d) if ok else None for d, ok in zip(boxes_2d_per_frame, live)]
+    if not any(live):
+        return live, dets, None, None
+    ctx = ctx or get_context(device)
+    if rects is None:
+        rects = _match2d_rects([b if ok else [] for b, ok in zip(bboxes_3d_per_frame, live)], camera, ctx)
+    else:
+        rects = [r if ok else (np.zeros((0, 4), np.float64), np.zeros(0, np.int32)) for r, ok in zip(rects, live)]
+    return live, dets, rects, ctx
+
+
+def _dtype_groups(dets, rects, skip=()):
+    """The frames of a plan that a native call takes -- those with detections and boxes, but for ``skip`` -- as (frames, dets, bbox2d,
+    front) per detection dtype: a call's detections share one."""
     for dt in (np.float32, np.float64):
-        idx = [f for f, d in enumerate(dets) if d is not None and d.dtype == dt and len(d) and len(rects[f][0])]
-        if not idx:
-            continue
-        res = ctx.match_2d([dets[f] for f in idx], [rects[f][0] for f in idx], [rects[f][1] for f in idx], min_iou=min_iou, want=want)
+        idx = [f for f, d in enumerate(dets) if d is not None and d.dtype == dt and len(d) and len(rects[f][0]) and f not in skip]
+        if idx:
+            yield idx, [dets[f] for f in idx], [rects[f][0] for f in idx], [rects[f][1] for f in idx]
+
+
+def _match2d_call(dets, rects, ctx, want, min_iou=0.25, skip=()):
+    """ctx.match_2d over the frames that have detections and boxes, one call per detection dtype: per frame the dict of that frame's
+    outputs, or None for a frame the matchers leave before they score anything (and for the frames of ``skip``)."""
+    out = [None] * len(dets)
+    for idx, d, bb, fr in _dtype_groups(dets, rects, skip):
+        res = ctx.match_2d(d, bb, fr, min_iou=min_iou, want=want)
         for k, f in enumerate(idx):
             out[f] = {name: vals[k] for name, vals in res.items()}
     return out
@@ -624,17 +665,11 @@ def match_detections_frames(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_
     """match_detections_to_bboxes (V4:140-183) for a list of frames: per frame exactly the list that function returns, with the
     IoU of every (detection, box) pair and each detection's first strict maximum computed by ONE lpf_match_2d call for the batch.
     Box dicts without '_bbox2d' are projected for the whole batch by one lpf_prepare_boxes call."""
-    boxes_2d_per_frame, bboxes_3d_per_frame = list(boxes_2d_per_frame), list(bboxes_3d_per_frame)
-    colors_per_frame = list(colors_per_frame)
-    if not (len(boxes_2d_per_frame) == len(bboxes_3d_per_frame) == len(colors_per_frame)):
-        raise ValueError("one entry per frame in each list")
-    live = [bool(b) and d is not None and len(d) > 0 for d, b in zip(boxes_2d_per_frame, bboxes_3d_per_frame)]
-    dets = [_match2d_dets(d) if ok else None for d, ok in zip(boxes_2d_per_frame, live)]
+    boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame = _per_frame_lists(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame)
+    live, dets, rects, ctx = _match2d_plan(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device, ctx)
     out = [[] for _ in live]
-    if not any(live):
+    if ctx is None:
         return out
-    ctx = ctx or get_context(device)
-    rects = _match2d_rects([b if ok else [] for b, ok in zip(bboxes_3d_per_frame, live)], camera, ctx)
     res = _match2d_call(dets, rects, ctx, ("best",), min_iou)
     for f, r in enumerate(res):
         if r is None:
@@ -647,22 +682,11 @@ def match_detections_frames(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_
     return out
 
 
-def _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device=0, ctx=None, rects=None):
-    """The score matrices of improved_match_detections_frames for a list of frames (one lpf_match_2d call): per frame None (the
-    matcher leaves before it scores) or (valid_idx, dict of [D, len(valid_idx)] matrices) -- V5's columns, the boxes with a projection.
-    ``rects``: per frame the (bbox2d, front) of every dict of its list where the caller has them already (lpf_box_views')."""
-    live = [bool(b) and d is not None and len(d) > 0 for d, b in zip(boxes_2d_per_frame, bboxes_3d_per_frame)]
-    dets = [_match2d_dets(d) if ok else None for d, ok in zip(boxes_2d_per_frame, live)]
-    if not any(live):
-        return [None] * len(live)
-    ctx = ctx or get_context(device)
-    if rects is None:
-        rects = _match2d_rects([b if ok else [] for b, ok in zip(bboxes_3d_per_frame, live)], camera, ctx)
-    else:
-        rects = [r if ok else (np.zeros((0, 4), np.float64), np.zeros(0, np.int32)) for r, ok in zip(rects, live)]
-    res = _match2d_call(dets, rects, ctx, ("iou", "center", "size", "total", "cost"))
+def _host_scores(dets, rects, ctx, skip=()):
+    """The score matrices of a plan's frames (one lpf_match_2d call per detection dtype): per frame None (the matcher leaves before it
+    scores; a frame of ``skip``) or (valid_idx, dict of [D, len(valid_idx)] matrices) -- V5's columns, the boxes with a projection."""
     out = []
-    for f, r in enumerate(res):
+    for f, r in enumerate(_match2d_call(dets, rects, ctx, ("iou", "center", "size", "total", "cost"), skip=skip)):
         if r is None:
             out.append(None)
             continue
@@ -671,30 +695,16 @@ def _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device=0, 
     return out
 
 
-def _improved_device_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, min_score_threshold=0.3, min_iou_threshold=0.15, device=0,
-                            ctx=None, rects=None):
-    """_improved_scores with the assignment made on the GPU as well (one lpf_assign_2d call per detection dtype): per frame None, or
+def _device_scores(dets, rects, ctx, min_score_threshold, min_iou_threshold):
+    """_host_scores with the assignment made on the GPU as well (one lpf_assign_2d call per detection dtype): per frame None, or
     (valid_idx, pairs) with the assigned pairs in row order as (detection, compact column, iou, center, size, total, accepted) --
     what _improved_assign reads instead of the matrices.  A frame beyond LPF_ASSIGN_MAX detections or projected boxes gets
-    _improved_scores' entry: it is assigned on the host."""
+    _host_scores' entry: it is assigned on the host."""
     from ._native import LPF_ASSIGN_MAX, LpfContext
-    live = [bool(b) and d is not None and len(d) > 0 for d, b in zip(boxes_2d_per_frame, bboxes_3d_per_frame)]
-    dets = [_match2d_dets(d) if ok else None for d, ok in zip(boxes_2d_per_frame, live)]
-    out = [None] * len(live)
-    if not any(live):
-        return out
-    ctx = ctx or get_context(device)
-    if rects is None:
-        rects = _match2d_rects([b if ok else [] for b, ok in zip(bboxes_3d_per_frame, live)], camera, ctx)
-    else:
-        rects = [r if ok else (np.zeros((0, 4), np.float64), np.zeros(0, np.int32)) for r, ok in zip(rects, live)]
-    over = {f for f, ok in enumerate(live) if ok and (len(dets[f]) > LPF_ASSIGN_MAX or int((rects[f][1] > 0).sum()) > LPF_ASSIGN_MAX)}
-    for dt in (np.float32, np.float64):
-        idx = [f for f, d in enumerate(dets) if d is not None and d.dtype == dt and len(d) and len(rects[f][0]) and f not in over]
-        if not idx:
-            continue
-        res = ctx.assign_2d([dets[f] for f in idx], [rects[f][0] for f in idx], [rects[f][1] for f in idx],
-                            min_score_threshold=min_score_threshold, min_iou_threshold=min_iou_threshold)
+    over = {f for f, d in enumerate(dets) if d is not None and (len(d) > LPF_ASSIGN_MAX or int((rects[f][1] > 0).sum()) > LPF_ASSIGN_MAX)}
+    out = [None] * len(dets)
+    for idx, d, bb, fr in _dtype_groups(dets, rects, over):
+        res = ctx.assign_2d(d, bb, fr, min_score_threshold=min_score_threshold, min_iou_threshold=min_iou_threshold)
         for k, f in enumerate(idx):
             if res["status"][k]:                             # (what scipy's solver raises for the frame's matrix)
                 raise ValueError(LpfContext.ASSIGN_MESSAGES[int(res["status"][k])])
@@ -706,26 +716,43 @@ def _improved_device_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, min
                              (res["accepted"][k][rows] != 0).tolist()))
             out[f] = (valid.tolist(), pairs)
     if over:
-        host = _improved_scores([d if f in over else None for f, d in enumerate(boxes_2d_per_frame)],
-                                [b if f in over else [] for f, b in enumerate(bboxes_3d_per_frame)], camera, device, ctx, rects=rects)
+        host = _host_scores(dets, rects, ctx, skip=set(range(len(dets))) - over)
         for f in over:
             out[f] = host[f]
     return out
 
 
+def _assign_route(assign):
+    if assign not in ("host", "device"):
+        raise ValueError("assign is \"host\" (scipy's solver on the downloaded cost matrices) or \"device\" (lpf_assign_2d), got %r" % (assign,))
+    return assign == "device"
+
+
+def _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, min_score_threshold=0.3, min_iou_threshold=0.15, device=0, ctx=None,
+                     rects=None, assign="host"):
+    """What _improved_assign reads for each frame of a list, by either route: _host_scores' entries (assign="host") or _device_scores'
+    (assign="device").  ``rects``: per frame the (bbox2d, front) of every dict of its list where the caller has them already."""
+    to_device = _assign_route(assign)
+    live, dets, rects, ctx = _match2d_plan(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device, ctx, rects)
+    if ctx is None:
+        return [None] * len(live)
+    if to_device:
+        return _device_scores(dets, rects, ctx, min_score_threshold, min_iou_threshold)
+    return _host_scores(dets, rects, ctx)
+
+
 def _improved_assign(boxes_2d, bboxes_3d, mask_colors, scores, min_score_threshold=0.3, min_iou_threshold=0.15):
     """improved_match_detections_to_bboxes from its cost matrix on: the assignment, the thresholds, the returned list and every
-    printed line, with the pair scores read from lpf_match_2d's matrices (``scores``: a frame's entry of _improved_scores), or from
-    the pairs lpf_assign_2d assigned (a frame's entry of _improved_device_scores)."""
-    matched = []
+    printed line, with the pair scores read from lpf_match_2d's matrices (``scores``: a frame's entry of _host_scores), or from
+    the pairs lpf_assign_2d assigned (a frame's entry of _device_scores)."""
     if not bboxes_3d or boxes_2d is None or len(boxes_2d) == 0:
         print("[INFO] No detections or 3D bounding boxes to match")
-        return matched
+        return []
     print(f"[INFO] Matching {len(boxes_2d)} 2D detections with {len(bboxes_3d)} 3D bboxes")
     valid_idx, m = scores
     if not valid_idx:
         print("[WARN] No valid 3D bbox projections found")
-        return matched
+        return []
     if isinstance(m, list):                                 # assigned on the GPU
         pairs = m
     else:
@@ -734,37 +761,7 @@ def _improved_assign(boxes_2d, bboxes_3d, mask_colors, scores, min_score_thresho
         iou, center, size, total = m["iou"], m["center"], m["size"], m["total"]
         pairs = [(i, j, iou[i, j], center[i, j], size[i, j], total[i, j], total[i, j] >= min_score_threshold and iou[i, j] >= min_iou_threshold)
                  for i, j in zip(rows, cols)]
-    used = set()
-    for i, j, iou_ij, center_ij, size_ij, total_ij, accepted in pairs:
-        if accepted:
-            orig = valid_idx[j]
-            used.add(orig)
-            bbox = bboxes_3d[orig]
-            if "corners_velo" in bbox:
-                if i < len(mask_colors):
-                    c = mask_colors[i]
-                    color = np.array([c[2], c[1], c[0]], dtype=float) / 255.0
-                else:
-                    color = np.array([1.0, 0.0, 0.0])
-                matched.append((np.array(bbox["corners_velo"]), color))
-                print(f"[INFO] Matched detection {i} with 3D bbox {orig}")
-                print(f"        Scores - IoU: {iou_ij:.3f}, Center: {center_ij:.3f}, "
-                      f"Size: {size_ij:.3f}, Total: {total_ij:.3f}")
-            else:
-                print(f"[WARN] No Velodyne corners found for bbox {orig}")
-        else:
-            print(f"[INFO] Rejected match det{i}-bbox{j}: score={total_ij:.3f}, IoU={iou_ij:.3f}")
-    for i, bbox in enumerate(bboxes_3d):
-        if i not in used and "corners_velo" in bbox:
-            matched.append((np.array(bbox["corners_velo"]), [0.7, 0.7, 0.7]))
-            print(f"[INFO] Added unmatched 3D bbox {i} in default color")
-    return matched
-
-
-def _assign_route(assign):
-    if assign not in ("host", "device"):
-        raise ValueError("assign is \"host\" (scipy's solver on the downloaded cost matrices) or \"device\" (lpf_assign_2d), got %r" % (assign,))
-    return assign == "device"
+    return _report_matches(bboxes_3d, mask_colors, valid_idx, pairs)
 
 
 def improved_match_detections_frames(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame, camera, min_score_threshold=0.3,
@@ -775,14 +772,8 @@ def improved_match_detections_frames(boxes_2d_per_frame, bboxes_3d_per_frame, co
     projection.  assign="device": scores, assignment and thresholds are ONE lpf_assign_2d call -- SciPy's assignment, ties included
     -- and a few words per detection come back instead of five [D,B] matrices; a frame beyond LPF_ASSIGN_MAX detections or
     projected boxes takes the host route."""
-    boxes_2d_per_frame, bboxes_3d_per_frame = list(boxes_2d_per_frame), list(bboxes_3d_per_frame)
-    colors_per_frame = list(colors_per_frame)
-    if not (len(boxes_2d_per_frame) == len(bboxes_3d_per_frame) == len(colors_per_frame)):
-        raise ValueError("one entry per frame in each list")
-    if _assign_route(assign):
-        scores = _improved_device_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, min_score_threshold, min_iou_threshold, device, ctx)
-    else:
-        scores = _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, device, ctx)
+    boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame = _per_frame_lists(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame)
+    scores = _improved_scores(boxes_2d_per_frame, bboxes_3d_per_frame, camera, min_score_threshold, min_iou_threshold, device, ctx, assign=assign)
     return [_improved_assign(d, b, c, s, min_score_threshold, min_iou_threshold)
             for d, b, c, s in zip(boxes_2d_per_frame, bboxes_3d_per_frame, colors_per_frame, scores)]
 
@@ -1073,11 +1064,9 @@ def secondtest_match_frames(boxes_2d_per_frame, bboxes_raw_per_frame, colors_per
     'corners_velo' in place and nothing else.  Two native calls per batch: lpf_box_views, whose front bbox2d / front of the kept
     boxes and whose corners_velo feed the matcher, and lpf_match_2d -- or, with assign="device", lpf_assign_2d, which assigns on the
     GPU as well (improved_match_detections_frames)."""
-    to_device = _assign_route(assign)
-    boxes_2d_per_frame, colors_per_frame = list(boxes_2d_per_frame), list(colors_per_frame)
+    _assign_route(assign)                                  # (refused here, before anything is filtered or printed)
+    boxes_2d_per_frame, bboxes_raw_per_frame, colors_per_frame = _per_frame_lists(boxes_2d_per_frame, bboxes_raw_per_frame, colors_per_frame)
     bboxes_raw_per_frame = [list(b) if b else [] for b in bboxes_raw_per_frame]
-    if not (len(boxes_2d_per_frame) == len(bboxes_raw_per_frame) == len(colors_per_frame)):
-        raise ValueError("one entry per frame in each list")
     slots, res, depth, raw = _filter_setup(bboxes_raw_per_frame, camera, verbose, device, ctx, ("front", "bbox2d", "corners_velo"),
                                            np.linalg.inv(TrVeloToCam))
     filtered, lines, rects = [], [], []
@@ -1103,10 +1092,7 @@ def secondtest_match_frames(boxes_2d_per_frame, bboxes_raw_per_frame, colors_per
                     bb[k], fr[k] = info["bbox"], 8
         rects.append((bb, fr))
     kept_per_frame = [k for k, _ in filtered]
-    if to_device:
-        scores = _improved_device_scores(boxes_2d_per_frame, kept_per_frame, camera, min_score_threshold, min_iou_threshold, device, ctx, rects=rects)
-    else:
-        scores = _improved_scores(boxes_2d_per_frame, kept_per_frame, camera, device, ctx, rects=rects)
+    scores = _improved_scores(boxes_2d_per_frame, kept_per_frame, camera, min_score_threshold, min_iou_threshold, device, ctx, rects, assign)
     out = []
     for f, (kept, stats) in enumerate(filtered):
         sys.stdout.write(lines[f])
@@ -2325,7 +2311,7 @@ def projectVeloToImage(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti
     per-mask point sets, ``bg_assigned`` and the score + Hungarian box matching; ``visualizer`` receives
     (frame, car_point_sets, colors, remaining_points, matched_pairs) instead of the Open3D window.  assign: where the Hungarian
     assignment runs, "host" (scipy) or "device" (lpf_assign_2d), as improved_match_detections_frames'."""
-    to_device = _assign_route(assign)
+    _assign_route(assign)
     if segmenter is None:
         raise ValueError("projectVeloToImage needs the segmentation callable")
     root = kitti360_path or os.environ["KITTI360_DATASET"]
@@ -2334,10 +2320,7 @@ def projectVeloToImage(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti
                                  keep_all_boxes=True)
     results = []
     # the pair scores of every frame in one lpf_match_2d call; the assignment and its printed lines stay in the frame's turn
-    if to_device:
-        scores = _improved_device_scores([i.boxes_2d for i in items], [i.bboxes_3d for i in items], camera, device=device)
-    else:
-        scores = _improved_scores([i.boxes_2d for i in items], [i.bboxes_3d for i in items], camera, device)
+    scores = _improved_scores([i.boxes_2d for i in items], [i.bboxes_3d for i in items], camera, device=device, assign=assign)
     for r, item, sc in zip(run_frames(items, velo_to_rect, camera, 30.0, 10, True, 0, False, device), items, scores):
         print(f"[DEBUG] Frame {r['frame']}: {r['n_valid']} points passed validation filter")
         if r["n_valid"] == 0:

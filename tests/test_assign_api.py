@@ -1,6 +1,7 @@
 """lpf_assign_costs / lpf_assign_2d without a GPU: the Python restatement of the solver (tests/assign_ref.py) against
 scipy.optimize.linear_sum_assignment on the seeded case list and on small matrices, the golden file against both, the header and the
-library's exports, and the pipeline's shared reporting code with pairs assigned elsewhere."""
+library's exports, the pipeline's shared reporting code with pairs assigned elsewhere, and the batched matchers' device route on a
+context whose lpf_assign_2d is the restatements."""
 import contextlib
 import ctypes
 import hashlib
@@ -13,8 +14,10 @@ import pytest
 from scipy.optimize import linear_sum_assignment
 
 import assign_ref as A
+import match2d_ref as R
 from conftest import GOLDEN
 from lidar_object_detection_amd import _build, _native, pipeline
+from test_match2d_api import _RefContext, _boxes_of, _golden, golden_frame
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -154,3 +157,89 @@ def test_report_from_assigned_pairs_equals_the_report_from_matrices():
         assert np.array_equal(hc, dc) and type(hcol) is type(dcol) and np.array_equal(np.asarray(hcol), np.asarray(dcol))
     with pytest.raises(ValueError, match="assign is"):
         pipeline.improved_match_detections_frames([], [], [], None, assign="gpu")
+
+
+class _RefAssignContext(_RefContext):
+    """_RefContext with lpf_assign_2d as well: the score restatement, the solver restatement on the cost, the two thresholds"""
+    def __init__(self):
+        super().__init__()
+        self.assign_calls, self.match_frames = 0, []
+
+    def match_2d(self, dets, bbox2d, front, **kw):
+        self.match_frames.append([len(d) for d in dets])
+        return super().match_2d(dets, bbox2d, front, **kw)
+
+    def assign_2d(self, dets, bbox2d, front, weights=(0.5, 0.3, 0.2), min_score_threshold=0.3, min_iou_threshold=0.15,
+                  want=_native.LpfContext.ASSIGN2D_WANT):
+        self.assign_calls += 1
+        _native.LpfContext.match2d_batch(dets, bbox2d, front)
+        res = {k: [] for k in want if k != "status"}
+        status = np.zeros(len(dets), np.int32)
+        for f, (d, b, fr) in enumerate(zip(dets, bbox2d, front)):
+            assert len(d) <= A.CAP and int((np.asarray(fr) > 0).sum()) <= A.CAP, "the library refuses this frame"
+            m = R.score(d, b, fr, weights)
+            status[f], rows, cols = A.solve_front(m["cost"], (np.asarray(fr) > 0).astype(np.int32))
+            one = {"box_of_det": np.full(len(d), -1, np.int32), "accepted": np.zeros(len(d), np.int32)}
+            one["box_of_det"][rows] = cols
+            for k in ("iou", "center", "size", "total"):
+                one[k] = np.zeros(len(d), np.float64)
+                one[k][rows] = m[k][rows, cols]
+            one["accepted"][rows] = (m["total"][rows, cols] >= min_score_threshold) & (m["iou"][rows, cols] >= min_iou_threshold)
+            for k in res:
+                res[k].append(one[k])
+        if "status" in want:
+            res["status"] = status
+        return res
+
+
+def _same_lists(got, exp):
+    assert len(got) == len(exp)
+    for (gc, gcol), (ec, ecol) in zip(got, exp):
+        assert type(gc) is type(ec) and gc.dtype == ec.dtype and np.array_equal(gc, ec)
+        assert type(gcol) is type(ecol) and np.array_equal(np.asarray(gcol), np.asarray(ecol))
+
+
+def test_device_route_of_the_batched_matcher_equals_the_scalar_one_on_the_golden_frames():
+    """improved_match_detections_frames with assign="device" and assign="host" against improved_match_detections_to_bboxes frame by
+    frame, lists and printed lines: the 19 golden frames, a frame without detections, one without boxes, one with two boxes that were
+    never transformed -- and then with a frame beyond LPF_ASSIGN_MAX detections among them, which alone takes the host route."""
+    z = _golden()
+    gs = [golden_frame(z, f) for f in z["frames"].tolist()]
+    assert len(gs) == 19 and sum(bool((g["front"] <= 0).any()) for g in gs) >= 10       # a compact column is not the box's index
+    dets = [g["dets"] for g in gs] + [np.zeros((0, 4), np.float32), gs[0]["dets"]]
+    boxes = [_boxes_of(g, True) for g in gs] + [_boxes_of(gs[0], True), []]
+    for j in (1, 4):
+        del boxes[2][j]["corners_velo"]
+    big_d, big_bb, big_front = R.cases(5, _native.LPF_ASSIGN_MAX + 1, 3, fraction=True)
+    big_front[:] = 8
+    dets_big = dets[:4] + [big_d] + dets[4:]
+    boxes_big = boxes[:4] + [_boxes_of({"bbox2d": big_bb, "front": big_front}, True)] + boxes[4:]
+
+    def scalar(dets, boxes, colors):
+        out, buf = [], io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            for d, b, c in zip(dets, boxes, colors):
+                out.append(pipeline.improved_match_detections_to_bboxes(d, b, c, None))
+        return out, buf.getvalue()
+
+    def batched(dets, boxes, colors, assign):
+        ctx, buf = _RefAssignContext(), io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            out = pipeline.improved_match_detections_frames(dets, boxes, colors, None, ctx=ctx, assign=assign)
+        return out, buf.getvalue(), ctx
+
+    for ds, bs, big in ((dets, boxes, None), (dets_big, boxes_big, 4)):
+        colors = [pipeline.generate_consistent_colors(max(len(d) - 1, 0)) for d in ds]      # one short: V5's red fallback
+        exp, exp_text = scalar(ds, bs, colors)
+        for line in ("Matched detection", "Rejected match", "No valid 3D bbox projections found", "Added unmatched"):
+            assert line in exp_text, line
+        got, text, ctx = batched(ds, bs, colors, "device")
+        assert ctx.assign_calls == 1 and ctx.match_frames == ([] if big is None else [[_native.LPF_ASSIGN_MAX + 1]])
+        for g, e in zip(got, exp):
+            _same_lists(g, e)
+        assert len(got) == len(exp) and text == exp_text
+        got, text, ctx = batched(ds, bs, colors, "host")
+        assert ctx.assign_calls == 0 and len(ctx.match_frames) == 1
+        for g, e in zip(got, exp):
+            _same_lists(g, e)
+        assert len(got) == len(exp) and text == exp_text

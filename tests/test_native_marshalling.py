@@ -31,6 +31,9 @@ DT = {
     "DepthOverlayOutputs": dict(images="u1", max_depth="f8"),
     "Match2dInput": dict(dets="f4", det_off="i4", bbox2d="f8", front="i4", box_off="i4"),
     "Match2dOutputs": dict(best_box="i4", best_iou="f8", iou="f8", center_score="f8", size_score="f8", total_score="f8", cost="f8"),
+    "AssignInput": dict(cost="f8", front="i4", det_off="i4", box_off="i4"),
+    "AssignOutputs": dict(col_of_row="i4", status="i4"),
+    "Assign2dOutputs": dict(box_of_det="i4", iou="f8", center_score="f8", size_score="f8", total_score="f8", accepted="i4", status="i4"),
     "InsideInput": dict(inst_idx="i8", inst_off="i8", best_box="i4", best_cnt="i8"),
     "InsideOutputs": dict(inside="u1", part_idx="i8", part_xyz="f4", n_inside="i8", matched="i4"),
     "BoxPointsInput": dict(valid_idx="i8", n_valid="i8", label_valid_words="u4"),
@@ -274,6 +277,33 @@ def _match_2d(D=(2, 1), B=(2, 1), dtype=np.float32, **kw):
     return stub, res
 
 
+def _assign_costs(shapes=((2, 3), (3, 1)), front=False, status=None, **kw):
+    """status: what the library reports per frame (zeros: every frame solved; the ramp would be an error).  Every third row is unassigned."""
+    F = len(shapes)
+    costs = [((np.arange(d * b) * (f + 2)) % 7).astype(np.float64).reshape(d, b) for f, (d, b) in enumerate(shapes)]
+    fronts = [(np.arange(b, dtype=np.int32) + f) % 3 for f, (d, b) in enumerate(shapes)] if front else None
+    Dtot, Btot, P = sum(d for d, _ in shapes), sum(b for _, b in shapes), sum(d * b for d, b in shapes)
+    writes = dict(col_of_row=np.arange(Dtot) % 3 - 1, status=np.zeros(F, np.int32) if status is None else np.asarray(status, np.int32))
+    stub = Stub(dict(cost=P, front=Btot, det_off=F + 1, box_off=F + 1, col_of_row=Dtot, status=F), [writes], ("col_of_row", "status"))
+    try:
+        res = Ctx(stub).assign_costs(costs, fronts, **kw)
+    except ValueError as e:
+        res = "ValueError: %s" % e
+    return stub, res
+
+
+def _assign_2d(D=(2, 1), B=(2, 1), dtype=np.float32, **kw):
+    F = len(D)
+    dets = [(np.arange(4 * d) + f).astype(dtype).reshape(d, 4) for f, d in enumerate(D)]
+    bbox2d = [np.arange(4.0 * b).reshape(b, 4) * (f + 1) for f, b in enumerate(B)]
+    front = [np.arange(b, dtype=np.int32) + f for f, b in enumerate(B)]
+    Dtot, Btot = sum(D), sum(B)
+    stub = Stub(dict(dets=Dtot * (2 if dtype == np.float64 else 1) * 4, det_off=F + 1, bbox2d=Btot * 4, front=Btot, box_off=F + 1, box_of_det=Dtot,
+                     iou=Dtot, center_score=Dtot, size_score=Dtot, total_score=Dtot, accepted=Dtot, status=F), filled=tuple(DT["Assign2dOutputs"]))
+    res = Ctx(stub).assign_2d(dets, bbox2d, front, **kw)
+    return stub, res
+
+
 INSIDE_DT = dict(inside=np.uint8, part_idx=np.int64, part_xyz=np.float32, n_inside=np.int64, matched=np.int32)
 
 
@@ -367,6 +397,18 @@ CASES = {
     "match_2d F=1": P(_match_2d, D=(2,), B=(3,), want=("best", "cost")),
     "match_2d no detections": P(_match_2d, D=(0, 0), want=("best", "iou")),
     "match_2d no boxes": P(_match_2d, B=(0, 0), want=("best", "iou")),
+    "assign_costs": P(_assign_costs),
+    "assign_costs front": P(_assign_costs, front=True),
+    "assign_costs raw": P(_assign_costs, raw=True),
+    "assign_costs F=1": P(_assign_costs, shapes=((2, 3),)),
+    "assign_costs no rows, no columns": P(_assign_costs, shapes=((0, 3), (2, 0)), front=True),
+    "assign_costs a frame without an assignment": P(_assign_costs, status=(0, 2)),
+    "assign_2d": P(_assign_2d),
+    "assign_2d float64": P(_assign_2d, dtype=np.float64, weights=(0.25, 0.5, 0.125), min_score_threshold=0.5, min_iou_threshold=0.125),
+    "assign_2d two outputs": P(_assign_2d, want=("box_of_det", "status")),
+    "assign_2d F=1": P(_assign_2d, D=(2,), B=(3,)),
+    "assign_2d no detections": P(_assign_2d, D=(0, 0)),
+    "assign_2d no boxes": P(_assign_2d, B=(0, 0)),
     **{"inside_masks %s" % w: P(_inside, want=(w,)) for w in N.LpfContext.INSIDE_WANT},
     "inside_masks all": P(_inside, min_points=3),
     "inside_masks F=1": P(_inside, F=1),
@@ -414,6 +456,13 @@ def test_slicing_of_the_analysis_calls():
     o = stub.calls[0][3][0]
     assert o["best_box"].startswith("out[3] was ") and o["iou"] == "NULL" and o["cost"].startswith("out[5]")
     assert [a.tolist() for a in res["best_box"]] == [[0, 1], [2]] and [a.tolist() for a in res["cost"]] == [[[42, 43], [44, 45]], [[46]]]
+    stub, res = _assign_2d()                                   # per-frame cuts of the ramp at det_off; status comes back whole
+    assert [a.tolist() for a in res["box_of_det"]] == [[0, 1], [2]] and [a.tolist() for a in res["total"]] == [[28, 29], [30]]
+    assert [a.tolist() for a in res["accepted"]] == [[35, 36], [37]] and res["status"].tolist() == [42, 43]
+    stub, raw = _assign_costs(raw=True, status=(0, 1))
+    assert raw["col_of_row"].tolist() == [-1, 0, 1, -1, 0] and raw["status"].tolist() == [0, 1]
+    stub, pairs = _assign_costs()                            # rows 0 .. 1 and 2 .. 4 of col_of_row, the rows without a column left out
+    assert [[a.tolist() for a in fr] for fr in pairs] == [[[1], [0]], [[0, 2], [1, 0]]]
     stub, maps = _depth_maps(cap=4, overflow=True)
     assert [c[6][0]["cap"] for c in stub.calls] == [4, 7]                  # the second launch asks for what the first one needed
     assert [[c[0].tolist() for c in fr] for fr in maps] == [[[0], [1, 2]], [[7, 8], []]]
@@ -1049,6 +1098,110 @@ EXPECT = {
              'total_score': 'NULL', 'cost': 'NULL', 'on_device': 0, 'reserved': 0}]]],
          {'best_box': ['<i4[2] [0, 1]', '<i4[1] [2]'], 'best_iou': ['<f8[2] [7.0, 8.0]', '<f8[1] [9.0]'],
           'iou': ['<f8[2, 0] [[], []]', '<f8[1, 0] [[]]']}],
+    'assign_costs':
+        [[['lpf_assign_costs',
+           2,
+           [{'cost': 'in[9] 8a90cc92f878', 'det_off': 'in[3] be73167ff39f', 'box_off': 'in[3] 4b9e096d5cbe', 'front': 'NULL', 'on_device': 0,
+             'reserved': 0}],
+           [{'col_of_row': 'out[5] was all -1', 'status': 'out[2] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         [['<i8[1] [1]', '<i8[1] [0]'], ['<i8[2] [0, 2]', '<i8[2] [1, 0]']]],
+    'assign_costs front':
+        [[['lpf_assign_costs',
+           2,
+           [{'cost': 'in[9] 8a90cc92f878', 'det_off': 'in[3] be73167ff39f', 'box_off': 'in[3] 4b9e096d5cbe', 'front': 'in[4] d862455f3f46',
+             'on_device': 0, 'reserved': 0}],
+           [{'col_of_row': 'out[5] was all -1', 'status': 'out[2] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         [['<i8[1] [1]', '<i8[1] [0]'], ['<i8[2] [0, 2]', '<i8[2] [1, 0]']]],
+    'assign_costs raw':
+        [[['lpf_assign_costs',
+           2,
+           [{'cost': 'in[9] 8a90cc92f878', 'det_off': 'in[3] be73167ff39f', 'box_off': 'in[3] 4b9e096d5cbe', 'front': 'NULL', 'on_device': 0,
+             'reserved': 0}],
+           [{'col_of_row': 'out[5] was all -1', 'status': 'out[2] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         {'col_of_row': '<i4[5] [-1, 0, 1, -1, 0]', 'status': '<i4[2] [0, 0]'}],
+    'assign_costs F=1':
+        [[['lpf_assign_costs',
+           1,
+           [{'cost': 'in[6] de6a6a2af671', 'det_off': 'in[2] 391dabcb730f', 'box_off': 'in[2] 1499246f5a6a', 'front': 'NULL', 'on_device': 0,
+             'reserved': 0}],
+           [{'col_of_row': 'out[2] was all -1', 'status': 'out[1] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         [['<i8[1] [1]', '<i8[1] [0]']]],
+    'assign_costs no rows, no columns':
+        [[['lpf_assign_costs',
+           2,
+           [{'cost': 'NULL', 'det_off': 'in[3] 0c38220b7676', 'box_off': 'in[3] 3f5d427fff4f', 'front': 'in[3] 727432515ae3', 'on_device': 0,
+             'reserved': 0}],
+           [{'col_of_row': 'out[2] was all -1', 'status': 'out[2] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         [['<i8[0] []', '<i8[0] []'], ['<i8[1] [1]', '<i8[1] [0]']]],
+    'assign_costs a frame without an assignment':
+        [[['lpf_assign_costs',
+           2,
+           [{'cost': 'in[9] 8a90cc92f878', 'det_off': 'in[3] be73167ff39f', 'box_off': 'in[3] 4b9e096d5cbe', 'front': 'NULL', 'on_device': 0,
+             'reserved': 0}],
+           [{'col_of_row': 'out[5] was all -1', 'status': 'out[2] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         'ValueError: assign_costs: frame 1: cost matrix is infeasible'],
+    'assign_2d':
+        [[['lpf_assign_2d',
+           2,
+           [{'dets': 'in[12] cb3910689d7e', 'det_off': 'in[3] dbd6951f6833', 'bbox2d': 'in[12] a6a44d538b13', 'front': 'in[3] 43f1e6e3bac3',
+             'box_off': 'in[3] dbd6951f6833', 'dets_f64': 0, 'on_device': 0, 'min_iou': 0.0, 'w_iou': 0.5, 'w_center': 0.3, 'w_size': 0.2}],
+           [{'min_score_threshold': 0.3, 'min_iou_threshold': 0.15}],
+           [{'box_of_det': 'out[3] was all -1', 'iou': 'out[3] was all 0.0', 'center_score': 'out[3] was all 0.0', 'size_score': 'out[3] was all 0.0',
+             'total_score': 'out[3] was all 0.0', 'accepted': 'out[3] was all 0', 'status': 'out[2] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         {'box_of_det': ['<i4[2] [0, 1]', '<i4[1] [2]'], 'iou': ['<f8[2] [7.0, 8.0]', '<f8[1] [9.0]'],
+          'center': ['<f8[2] [14.0, 15.0]', '<f8[1] [16.0]'], 'size': ['<f8[2] [21.0, 22.0]', '<f8[1] [23.0]'],
+          'total': ['<f8[2] [28.0, 29.0]', '<f8[1] [30.0]'], 'accepted': ['<i4[2] [35, 36]', '<i4[1] [37]'], 'status': '<i4[2] [42, 43]'}],
+    'assign_2d float64':
+        [[['lpf_assign_2d',
+           2,
+           [{'dets': 'in[24] 39ea56ef0b82', 'det_off': 'in[3] dbd6951f6833', 'bbox2d': 'in[12] a6a44d538b13', 'front': 'in[3] 43f1e6e3bac3',
+             'box_off': 'in[3] dbd6951f6833', 'dets_f64': 1, 'on_device': 0, 'min_iou': 0.0, 'w_iou': 0.25, 'w_center': 0.5, 'w_size': 0.125}],
+           [{'min_score_threshold': 0.5, 'min_iou_threshold': 0.125}],
+           [{'box_of_det': 'out[3] was all -1', 'iou': 'out[3] was all 0.0', 'center_score': 'out[3] was all 0.0', 'size_score': 'out[3] was all 0.0',
+             'total_score': 'out[3] was all 0.0', 'accepted': 'out[3] was all 0', 'status': 'out[2] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         {'box_of_det': ['<i4[2] [0, 1]', '<i4[1] [2]'], 'iou': ['<f8[2] [7.0, 8.0]', '<f8[1] [9.0]'],
+          'center': ['<f8[2] [14.0, 15.0]', '<f8[1] [16.0]'], 'size': ['<f8[2] [21.0, 22.0]', '<f8[1] [23.0]'],
+          'total': ['<f8[2] [28.0, 29.0]', '<f8[1] [30.0]'], 'accepted': ['<i4[2] [35, 36]', '<i4[1] [37]'], 'status': '<i4[2] [42, 43]'}],
+    'assign_2d two outputs':
+        [[['lpf_assign_2d',
+           2,
+           [{'dets': 'in[12] cb3910689d7e', 'det_off': 'in[3] dbd6951f6833', 'bbox2d': 'in[12] a6a44d538b13', 'front': 'in[3] 43f1e6e3bac3',
+             'box_off': 'in[3] dbd6951f6833', 'dets_f64': 0, 'on_device': 0, 'min_iou': 0.0, 'w_iou': 0.5, 'w_center': 0.3, 'w_size': 0.2}],
+           [{'min_score_threshold': 0.3, 'min_iou_threshold': 0.15}],
+           [{'box_of_det': 'out[3] was all -1', 'iou': 'NULL', 'center_score': 'NULL', 'size_score': 'NULL', 'total_score': 'NULL', 'accepted': 'NULL',
+             'status': 'out[2] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         {'box_of_det': ['<i4[2] [0, 1]', '<i4[1] [2]'], 'status': '<i4[2] [42, 43]'}],
+    'assign_2d F=1':
+        [[['lpf_assign_2d',
+           1,
+           [{'dets': 'in[8] a00dc06e2530', 'det_off': 'in[2] 391dabcb730f', 'bbox2d': 'in[12] dd81ba74486e', 'front': 'in[3] 727432515ae3',
+             'box_off': 'in[2] 1499246f5a6a', 'dets_f64': 0, 'on_device': 0, 'min_iou': 0.0, 'w_iou': 0.5, 'w_center': 0.3, 'w_size': 0.2}],
+           [{'min_score_threshold': 0.3, 'min_iou_threshold': 0.15}],
+           [{'box_of_det': 'out[2] was all -1', 'iou': 'out[2] was all 0.0', 'center_score': 'out[2] was all 0.0', 'size_score': 'out[2] was all 0.0',
+             'total_score': 'out[2] was all 0.0', 'accepted': 'out[2] was all 0', 'status': 'out[1] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         {'box_of_det': ['<i4[2] [0, 1]'], 'iou': ['<f8[2] [7.0, 8.0]'], 'center': ['<f8[2] [14.0, 15.0]'], 'size': ['<f8[2] [21.0, 22.0]'],
+          'total': ['<f8[2] [28.0, 29.0]'], 'accepted': ['<i4[2] [35, 36]'], 'status': '<i4[1] [42]'}],
+    'assign_2d no detections':
+        [[['lpf_assign_2d',
+           2,
+           [{'dets': 'NULL', 'det_off': 'in[3] 2c513f149e73', 'bbox2d': 'in[12] a6a44d538b13', 'front': 'in[3] 43f1e6e3bac3',
+             'box_off': 'in[3] dbd6951f6833', 'dets_f64': 0, 'on_device': 0, 'min_iou': 0.0, 'w_iou': 0.5, 'w_center': 0.3, 'w_size': 0.2}],
+           [{'min_score_threshold': 0.3, 'min_iou_threshold': 0.15}],
+           [{'box_of_det': 'NULL', 'iou': 'NULL', 'center_score': 'NULL', 'size_score': 'NULL', 'total_score': 'NULL', 'accepted': 'NULL',
+             'status': 'out[2] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         {'box_of_det': ['<i4[0] []', '<i4[0] []'], 'iou': ['<f8[0] []', '<f8[0] []'], 'center': ['<f8[0] []', '<f8[0] []'],
+          'size': ['<f8[0] []', '<f8[0] []'], 'total': ['<f8[0] []', '<f8[0] []'], 'accepted': ['<i4[0] []', '<i4[0] []'], 'status': '<i4[2] [42, 43]'}],
+    'assign_2d no boxes':
+        [[['lpf_assign_2d',
+           2,
+           [{'dets': 'in[12] cb3910689d7e', 'det_off': 'in[3] dbd6951f6833', 'bbox2d': 'NULL', 'front': 'NULL', 'box_off': 'in[3] 2c513f149e73',
+             'dets_f64': 0, 'on_device': 0, 'min_iou': 0.0, 'w_iou': 0.5, 'w_center': 0.3, 'w_size': 0.2}],
+           [{'min_score_threshold': 0.3, 'min_iou_threshold': 0.15}],
+           [{'box_of_det': 'out[3] was all -1', 'iou': 'out[3] was all 0.0', 'center_score': 'out[3] was all 0.0', 'size_score': 'out[3] was all 0.0',
+             'total_score': 'out[3] was all 0.0', 'accepted': 'out[3] was all 0', 'status': 'out[2] was all 0', 'on_device': 0, 'reserved': 0}]]],
+         {'box_of_det': ['<i4[2] [0, 1]', '<i4[1] [2]'], 'iou': ['<f8[2] [7.0, 8.0]', '<f8[1] [9.0]'],
+          'center': ['<f8[2] [14.0, 15.0]', '<f8[1] [16.0]'], 'size': ['<f8[2] [21.0, 22.0]', '<f8[1] [23.0]'],
+          'total': ['<f8[2] [28.0, 29.0]', '<f8[1] [30.0]'], 'accepted': ['<i4[2] [35, 36]', '<i4[1] [37]'], 'status': '<i4[2] [42, 43]'}],
     'inside_masks inside':
         [[['lpf_inside_masks', 2, 0, [0, 6, 10], 'efcda280bd2d',
            [{'inst_idx': 'in[10] 7edd5894cbbf', 'inst_cap': 5, 'inst_off': 'in[6] 4d626ca2d8bf', 'best_box': 'in[4] 8b58583b8ad1',

@@ -4,7 +4,7 @@
            linear_sum_assignment once per frame
   device   the same function with assign="device": one lpf_assign_2d call (pair scores, SciPy's assignment and the thresholds on the
            GPU), a few words per detection downloaded
-The two alternate in one process, pass by pass, prints swallowed; the median and the minimum of --passes passes each.  Also the raw
+The two alternate in one process, pass by pass, prints swallowed; the median, the minimum and the maximum of --passes passes each.  Also the raw
 LpfContext.assign_2d call on GPU tensors, timed to completion.  Workload: tools/match2d_bench.py's -- the boxes of
 the four full-size golden frames in turn to 146 frames with 5, 32 and 256 seeded float32 detections per frame -- and one frame alone
 (256 detections against the 314-box frame).  Appends one JSON line per (frames, detections) with the library's build id.
@@ -93,9 +93,10 @@ def main():
             if p >= a.warmup:
                 raw.append((time.perf_counter() - t0) * 1e3)
         kw = dict(frames=frames, dets_per_frame=D, pairs=sum(len(d) * len(b) for d, b in zip(dets, bbs)), passes=a.passes,
-                  host_ms_median=round(statistics.median(routes["host"]), 3), host_ms_min=round(min(routes["host"]), 3),
+                  host_ms_median=round(statistics.median(routes["host"]), 3), host_ms_min=round(min(routes["host"]), 3), host_ms_max=round(max(routes["host"]), 3),
                   device_ms_median=round(statistics.median(routes["device"]), 3), device_ms_min=round(min(routes["device"]), 3),
-                  raw_assign_2d_ms_median=round(statistics.median(raw), 3), raw_assign_2d_ms_min=round(min(raw), 3),
+                  device_ms_max=round(max(routes["device"]), 3),
+                  raw_assign_2d_ms_median=round(statistics.median(raw), 3), raw_assign_2d_ms_min=round(min(raw), 3), raw_assign_2d_ms_max=round(max(raw), 3),
                   source_id=_build.library_id(_build.LIB))
         lines.append(kw)
         print(json.dumps(kw), flush=True)

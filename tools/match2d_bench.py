@@ -57,7 +57,7 @@ def timed(fn, passes, warmup):
         t0 = time.perf_counter()
         fn()
         ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts), min(ts)
+    return statistics.median(ts), min(ts), max(ts)
 
 
 def main():
@@ -114,21 +114,21 @@ def main():
             def on_device():
                 ctx.match_2d(*dev, want=want)
                 torch.cuda.synchronize()
-            med, lo = timed(on_device, a.passes, a.warmup)
-            emit(route="batched", mode=mode, where="device", ms_per_batch_median=round(med, 3), ms_per_batch_min=round(lo, 3),
+            med, lo, hi = timed(on_device, a.passes, a.warmup)
+            emit(route="batched", mode=mode, where="device", ms_per_batch_median=round(med, 3), ms_per_batch_min=round(lo, 3), ms_per_batch_max=round(hi, 3),
                  pairs_per_s=round(pairs / (lo * 1e-3)), passes=a.passes, **base)
-            med, lo = timed(lambda: ctx.match_2d(dets, bbs, fronts, want=want), a.passes, a.warmup)
-            emit(route="batched", mode=mode, where="numpy", ms_per_batch_median=round(med, 3), ms_per_batch_min=round(lo, 3),
+            med, lo, hi = timed(lambda: ctx.match_2d(dets, bbs, fronts, want=want), a.passes, a.warmup)
+            emit(route="batched", mode=mode, where="numpy", ms_per_batch_median=round(med, 3), ms_per_batch_min=round(lo, 3), ms_per_batch_max=round(hi, 3),
                  pairs_per_s=round(pairs / (lo * 1e-3)), passes=a.passes, **base)
         # batched: the pipeline functions, lists and printed lines included
-        med, lo = timed(lambda: pipeline.match_detections_frames(dets, boxes, [colors] * FRAMES, cam, ctx=ctx), max(a.passes // 4, 3), 1)
-        emit(route="batched", mode="v4", where="pipeline", ms_per_batch_median=round(med, 3), ms_per_batch_min=round(lo, 3), **base)
+        med, lo, hi = timed(lambda: pipeline.match_detections_frames(dets, boxes, [colors] * FRAMES, cam, ctx=ctx), max(a.passes // 4, 3), 1)
+        emit(route="batched", mode="v4", where="pipeline", ms_per_batch_median=round(med, 3), ms_per_batch_min=round(lo, 3), ms_per_batch_max=round(hi, 3), **base)
 
         def v5_frames():
             with contextlib.redirect_stdout(io.StringIO()):
                 pipeline.improved_match_detections_frames(dets, boxes, [colors] * FRAMES, cam, ctx=ctx)
-        med, lo = timed(v5_frames, max(a.passes // 4, 3), 1)
-        emit(route="batched", mode="v5", where="pipeline", ms_per_batch_median=round(med, 3), ms_per_batch_min=round(lo, 3), **base)
+        med, lo, hi = timed(v5_frames, max(a.passes // 4, 3), 1)
+        emit(route="batched", mode="v5", where="pipeline", ms_per_batch_median=round(med, 3), ms_per_batch_min=round(lo, 3), ms_per_batch_max=round(hi, 3), **base)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:
         for kw in lines:
