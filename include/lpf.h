@@ -63,7 +63,9 @@ extern "C" {
                                       8 (continued): lpf_box_views_input, lpf_box_views_outputs, lpf_box_views (added; nothing else
                                          changed)
                                       8 (continued): LPF_ASSIGN_MAX, lpf_assign_input, lpf_assign_outputs, lpf_assign_costs,
-                                         lpf_assign2d_params, lpf_assign2d_outputs, lpf_assign_2d (added; nothing else changed) */
+                                         lpf_assign2d_params, lpf_assign2d_outputs, lpf_assign_2d (added; nothing else changed)
+                                      8 (continued): lpf_first_match_input, lpf_first_match_outputs, lpf_first_match (added; nothing else
+                                         changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -877,6 +879,57 @@ int lpf_get_stats(lpf_ctx *ctx, int64_t *out, int n, int reset);
  * communicator has made the call.  ncclAllReduce is taken from the RCCL already loaded in the process (so that it is the
  * library the communicator came from); only a process with none gets the system's librccl loaded at the first call. */
 int lpf_allreduce_metrics(lpf_ctx *ctx, int64_t *vec, int n, int op, void *rccl_comm);
+
+/* lpf_first_match: the exclusive, first-mask-wins labelling of Same_color.py:113-132 for a batch of F frames in ONE call.  Frame f owns
+ * points frame_off[f] .. frame_off[f + 1] and masks in->masks[f][0 .. M).  Projection and clip are lpf_set_camera's (the script's
+ * depth window is (0, 30)); LPF_ERR_STATE without a camera.  For each valid point of a frame, in ascending index order, the FIRST m in
+ * 0 .. M-1 with  v < mh && u < mw && mask[f][m][v][u] > 0.5  takes the point: a car point of mask m.  A valid point no mask takes is
+ * background.  float32 masks: NaN, 0.5 and negative values are not members; uint8 masks: nonzero is a member.  mh x mw is the masks'
+ * OWN size -- smaller or larger than the image; nothing is resized (the script never does), and nothing outside [0, mh) x [0, mw) is
+ * read.  M is the same for every frame: pad a frame that has fewer masks with empty planes.
+ *   first_mask  dense, per point: -2 not valid, -1 valid and in no mask, else the first mask.
+ *   car_idx / car_mask / car_xyz / car_rgb   the car points of frame f from entry frame_off[f] on, n_car[f] of them, ascending: the
+ *               index within the frame, the first mask, points[idx, :3] (colored_points) and colors[f][mask] (colored_colors).
+ *   bg_idx / bg_xyz   the same for the n_bg[f] background points (full_points).
+ *   n_valid = n_car + n_bg; mask_count[f][m]: the points whose first mask is m (their sum is n_car[f]).
+ * Entries of a frame's span at or beyond its count are NOT WRITTEN.  All sums are integers: the same bytes on every run.  The camera,
+ * masks, rectangles, boxes and label state of every other call are left as they were.  Not capturable (LPF_ERR_STATE between
+ * lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it first launches what the pipeline owes (no host wait), then
+ * runs in order.  pts (pts_on_device), the masks and colours (in->on_device) and the outputs (out->on_device) are each in host or device
+ * memory; frame_off is host memory.  With everything in device memory the call only enqueues work; with any host pointer it returns
+ * after one host wait, host outputs filled (a host caller's lists travel up first and come back whole, so that what is not written
+ * stays as it was).  Nothing is read or written out of bounds whatever the points and masks hold.
+ * LPF_ERR_ARG (the message names the argument): NULL in / out / frame_off, F < 0, frame_off that does not start at 0 or decreases, M
+ * outside 0 .. LPF_MAX_MASKS_WIDE, masks NULL or mh / mw <= 0 with M > 0, car_rgb without colors, NULL n_car or n_bg, pts NULL with
+ * points.  F = 0 and Ntot = 0 are fine.
+ * Device memory: 8 (F + 1) bytes; frames go through in ranges of consecutive frames that keep what is staged within 256 MiB (a frame
+ * that needs more is a range of its own): 4 bytes per point for the codes unless first_mask is given, 16 bytes per 1024 points and
+ * per frame for the tile counters, 16 bytes per point for host points, the masks and colours of a range when they are host memory,
+ * and 4 .. 72 bytes per point + (24 + 8 M) per frame for host outputs (grow-only, allocated on first use). */
+typedef struct lpf_first_match_input {
+    const void   *masks;      /* [F][M][mh][mw] uint8 (nonzero = member) or float32 (member <=> > 0.5) */
+    const double *colors;     /* optional [F][M][3]: the rows car_rgb gathers (the binding passes np.array(mask_colors[i]) / 255.0); same
+                                 memory as masks */
+    int32_t M;                /* 0 .. LPF_MAX_MASKS_WIDE, the same for every frame (pad with empty planes) */
+    int32_t mh, mw;           /* the masks' own size, > 0 when M > 0 */
+    int32_t f32;              /* 0: uint8, 1: float32 */
+    int32_t on_device;        /* 0: host, copied by the call; else device memory lent until the work has completed */
+    int32_t reserved;
+} lpf_first_match_input;
+typedef struct lpf_first_match_outputs {   /* any list may be NULL; all host or all device per on_device; Ntot = frame_off[F] */
+    int32_t *first_mask;      /* [Ntot]     dense: -2 not valid, -1 valid and in no mask, else the first mask */
+    int64_t *car_idx;         /* [Ntot]     frame f's at frame_off[f]: n_car[f] indices within the frame, ascending */
+    int32_t *car_mask;        /* [Ntot]     same order: the first mask of each */
+    float   *car_xyz;         /* [Ntot][3]  colored_points */
+    double  *car_rgb;         /* [Ntot][3]  colored_colors (needs in->colors) */
+    int64_t *bg_idx;          /* [Ntot]     n_bg[f] indices, ascending */
+    float   *bg_xyz;          /* [Ntot][3]  full_points */
+    int64_t *n_valid, *n_car, *n_bg;   /* [F] (n_car and n_bg required) */
+    int64_t *mask_count;      /* [F][M]     points whose first mask is m */
+    int32_t  on_device, reserved;
+} lpf_first_match_outputs;
+int lpf_first_match(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
+                    const lpf_first_match_input *in, const lpf_first_match_outputs *out);
 
 /* ---- scan reader ------------------------------------------------------------------------------
  * Double-buffered velodyne .bin reader for frame loops and the 10 Hz stream.  Stands where the

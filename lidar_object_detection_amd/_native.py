@@ -137,6 +137,18 @@ class BoxPointsOutputs(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class FirstMatchInput(ctypes.Structure):
+    """lpf_first_match_input (include/lpf.h): the masks of a batch at their own size and the colour rows car_rgb gathers"""
+    _fields_ = [("masks", _P), ("colors", _P), ("M", ctypes.c_int32), ("mh", ctypes.c_int32), ("mw", ctypes.c_int32), ("f32", ctypes.c_int32),
+                ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class FirstMatchOutputs(ctypes.Structure):
+    """lpf_first_match_outputs (include/lpf.h): the dense first-mask codes, the compact car and background lists, the counts"""
+    _fields_ = [("first_mask", _P), ("car_idx", _P), ("car_mask", _P), ("car_xyz", _P), ("car_rgb", _P), ("bg_idx", _P), ("bg_xyz", _P),
+                ("n_valid", _P), ("n_car", _P), ("n_bg", _P), ("mask_count", _P), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class BoxViewsInput(ctypes.Structure):
     """lpf_box_views_input (include/lpf.h): the cam-0 corners of a batch of frames' boxes and the filter's thresholds"""
     _fields_ = [("corners_cam0", _P), ("box_off", _P), ("T_cam_to_velo", _P), ("on_device", ctypes.c_int32),
@@ -323,6 +335,7 @@ def load(path=None):
     lib.lpf_inside_masks.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(InsideInput), ctypes.POINTER(InsideOutputs)]
     lib.lpf_box_points.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(BoxPointsInput), ctypes.POINTER(BoxPointsOutputs)]
     lib.lpf_box_views.argtypes = [_P, ctypes.c_int, ctypes.POINTER(BoxViewsInput), ctypes.POINTER(BoxViewsOutputs)]
+    lib.lpf_first_match.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FirstMatchInput), ctypes.POINTER(FirstMatchOutputs)]
     lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_cams_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(WideOutputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
@@ -360,7 +373,8 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_reader_create", "lpf_reader_submit", "lpf_reader_next", "lpf_reader_wait", "lpf_reader_destroy",
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
             "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d",
-            "lpf_inside_masks", "lpf_set_erosion_element", "lpf_box_points", "lpf_box_views", "lpf_assign_costs", "lpf_assign_2d")
+            "lpf_inside_masks", "lpf_set_erosion_element", "lpf_box_points", "lpf_box_views", "lpf_assign_costs", "lpf_assign_2d",
+            "lpf_first_match")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -1774,6 +1788,96 @@ class LpfContext:
         inp.LW, inp.on_device = LW, o.on_device
         if F:
             self._call_in_order(device, self._lib.lpf_box_points, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o))
+        return res
+
+    _FIRST_MATCH_OUT = {"first_mask": ("int32", ("N",), -2), "car_idx": ("int64", ("N",), -1), "car_mask": ("int32", ("N",), -1),
+                        "car_xyz": ("float32", ("N", 3), 0), "car_rgb": ("float64", ("N", 3), 0), "bg_idx": ("int64", ("N",), -1),
+                        "bg_xyz": ("float32", ("N", 3), 0), "n_valid": ("int64", ("F",), 0), "n_car": ("int64", ("F",), 0),
+                        "n_bg": ("int64", ("F",), 0), "mask_count": ("int64", ("F", "M"), 0)}
+    FIRST_MATCH_WANT = tuple(_FIRST_MATCH_OUT)
+    _FIRST_MATCH_LISTS = ("car_idx", "car_mask", "car_xyz", "car_rgb", "bg_idx", "bg_xyz")
+
+    @staticmethod
+    def first_match_batch(masks, colors, F):
+        """The masks [F,M,mh,mw] (or [M,mh,mw] for one frame) and colours [F,M,3] (or [M,3]; None: none) of first_match checked against
+        a batch of F frames: (on_device, M, mh, mw, f32, masks, colors) with the two arrays contiguous, uint8 or float32 and float64.
+        ValueError for other shapes, more than LPF_MAX_MASKS_WIDE masks, an empty plane with M > 0, host arrays mixed with GPU tensors
+        and GPU tensors of another dtype than uint8 / bool / float32 and float64."""
+        dev = LpfContext._on_gpu("first_match", [a for a in (masks, colors) if a is not None], "arrays")
+        if not dev:
+            masks = np.asarray(masks)
+        shp = tuple(masks.shape)
+        if len(shp) == 3 and F == 1:
+            masks, shp = masks[None], (1,) + shp
+        if len(shp) != 4 or shp[0] != F:
+            raise ValueError("first_match: masks [F,M,mh,mw] for %d frames (or [M,mh,mw] for one), got %s" % (F, shp))
+        M, mh, mw = (int(x) for x in shp[1:])
+        if M > LPF_MAX_MASKS_WIDE:
+            raise ValueError("first_match: %d masks per frame, one call takes %d" % (M, LPF_MAX_MASKS_WIDE))
+        if M > 0 and (mh < 1 or mw < 1):
+            raise ValueError("first_match: masks of %d x %d pixels" % (mh, mw))
+        name = str(masks.dtype).replace("torch.", "")
+        f32 = name not in ("uint8", "bool")
+        if dev:
+            import torch
+            if name not in ("uint8", "bool", "float32"):
+                raise ValueError("first_match: GPU masks must be uint8, bool or float32, got %s" % name)
+            masks = (masks.to(torch.uint8) if name == "bool" else masks).contiguous()
+        else:
+            if masks.dtype.kind not in "buif":
+                raise ValueError("first_match: masks must be uint8, bool or float, got %s" % name)
+            masks = np.ascontiguousarray(masks, dtype=np.float32 if f32 else np.uint8)
+        if colors is not None:
+            if not dev:
+                colors = np.ascontiguousarray(colors, dtype=np.float64)
+            cs = tuple(colors.shape)
+            if len(cs) == 2 and F == 1:
+                colors, cs = colors[None], (1,) + cs
+            if cs != (F, M, 3):
+                raise ValueError("first_match: colors [F,M,3] = %s, got %s" % ((F, M, 3), cs))
+            if dev:
+                if str(colors.dtype) != "torch.float64":
+                    raise ValueError("first_match: GPU colors must be float64, got %s" % colors.dtype)
+                colors = colors.contiguous()
+        return dev, M, mh, mw, int(f32), masks, colors
+
+    def first_match(self, pts_per_frame, masks, colors=None, want=None, out=None, staged=None):
+        """Same_color.py:113-132's exclusive labels of a batch of frames in ONE native call (lpf_first_match): every valid point goes
+        to the FIRST mask of its frame with ``v < mh and u < mw and mask[v, u] > 0.5`` (uint8 / bool masks: nonzero), or to the
+        background.  pts_per_frame: as run_batch's frames -- f32 [N_f,4] host arrays, Scans of a ScanReader, float32 [N,4] GPU tensors
+        (or ``staged=stage_points(frames)``).  masks: [F,M,mh,mw] (or [M,mh,mw] for one frame) at the masks' OWN size, which need not
+        be the camera's; colors: float64 [F,M,3], the rows "car_rgb" gathers -- both host arrays or both GPU tensors.  The camera,
+        transform and depth window are set_camera's.  ``want`` picks the outputs (FIRST_MATCH_WANT; "n_car" and "n_bg" always come;
+        None: all of them, "car_rgb" when there are colors):
+        "first_mask" int32 [Ntot] (-2 not valid, -1 background, else the mask), the compact lists "car_idx" int64 / "car_mask" int32 /
+        "car_xyz" float32 [.,3] / "car_rgb" float64 [.,3] / "bg_idx" / "bg_xyz" -- frame f's entries from the frame's first point on,
+        n_car[f] resp. n_bg[f] of them, ascending -- and "n_valid", "n_car", "n_bg" int64 [F], "mask_count" int64 [F,M].  Returns a dict
+        of them plus "frame_off": NumPy arrays after one host wait, or GPU tensors in torch's stream order when the masks are GPU
+        tensors (the call only enqueues work).  Entries the call does not write (beyond a frame's count) are -1 / 0, or what ``out``
+        -- a dict of the caller's own arrays under the same names -- held."""
+        if want is None:
+            want = tuple(w for w in self.FIRST_MATCH_WANT if w != "car_rgb" or colors is not None)
+        want = self._want("first_match", want, self.FIRST_MATCH_WANT)
+        want = want + tuple(w for w in ("n_car", "n_bg") if w not in want)
+        if "car_rgb" in want and colors is None:
+            raise ValueError("first_match: car_rgb is wanted, colors is None")
+        off, pts_ptr, pts_dev, _keep = staged or self._stage_points(pts_per_frame)      # (_keep: alive until the call returns)
+        F, Ntot = len(off) - 1, int(off[-1])
+        dev, M, mh, mw, f32, masks, colors = self.first_match_batch(masks, colors, F)
+        device = masks.device if dev else None
+        inp, o = FirstMatchInput(), FirstMatchOutputs()
+        res = self._outputs("first_match", o, want, self._FIRST_MATCH_OUT, dict(N=Ntot, F=F, M=M), device, out)
+        if Ntot == 0:                                       # (an empty array has no address: nothing would be written to it)
+            for w in self._FIRST_MATCH_LISTS + ("first_mask",):
+                setattr(o, w, None)
+        inp.masks = _ptr(masks) if M else None
+        inp.colors = _ptr(colors) if (colors is not None and M) else None
+        if inp.colors is None:
+            o.car_rgb = None                                # (no mask, no car point: nothing to gather)
+        inp.M, inp.mh, inp.mw, inp.f32, inp.on_device = M, mh, mw, f32, int(dev)
+        if F:
+            self._call_in_order(device, self._lib.lpf_first_match, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o))
+        res["frame_off"] = off
         return res
 
     _BOX_VIEWS_OUT = {"keep": ("uint8", ("B",), 0), "reason": ("int32", ("B",), 0), "corners_in_view": ("int32", ("B",), 0),

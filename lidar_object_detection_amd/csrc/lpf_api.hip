@@ -13,6 +13,7 @@
 #include "lpf_inside.hip.h"
 #include "lpf_box_points.hip.h"
 #include "lpf_box_views.hip.h"
+#include "lpf_first_match.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -220,6 +221,9 @@ struct lpf_ctx {
     // images), staged host outputs (grow-only, allocated on first use; a call leaves empty what it does not stage)
     struct CallBufs { DevBuf tab, pts, in, out; } dovl, m2d, insd, bpts, bviews;       // lpf_depth_overlays, lpf_match_2d, lpf_inside_masks, lpf_box_points, lpf_box_views
     CallBufs asgn;                    // lpf_assign_costs / lpf_assign_2d (pts: the scratch matrices, live-column maps and counts of a range)
+    // lpf_first_match: the analysis calls' four (tab: the frame offsets; in: a range's staged masks and colours) and its scratch -- a
+    // range's 4-byte codes when the dense output is not asked for, and its tile counters
+    struct FirstMatch : CallBufs { DevBuf code, tiles; } fmat;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -1530,8 +1534,10 @@ void lpf_destroy(lpf_ctx *c)
     for (DevBuf *b : {&c->dmaps.pack.planes_a, &c->dmaps.pack.planes_b, &c->dmaps.foff, &c->dmaps.win, &c->dmaps.cnt, &c->dmaps.in,
                       &c->dmaps.pts, &c->dmaps.out})
         release(*b);
-    for (lpf_ctx::CallBufs *D : {&c->dovl, &c->m2d, &c->insd, &c->bpts, &c->bviews, &c->asgn})
+    for (lpf_ctx::CallBufs *D : {&c->dovl, &c->m2d, &c->insd, &c->bpts, &c->bviews, &c->asgn, (lpf_ctx::CallBufs *)&c->fmat})
         for (DevBuf *b : {&D->tab, &D->pts, &D->in, &D->out}) release(*b);
+    release(c->fmat.code);
+    release(c->fmat.tiles);
     DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
     for (DevBuf *b : all) release(*b);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
@@ -3282,6 +3288,133 @@ int lpf_box_views(lpf_ctx *c, int F, const lpf_box_views_input *in, const lpf_bo
                              {fa, r.count}, {b0, nb}}))) return rc;
     }
     if (host_in || host_out) LPF_HIP(c, host_wait(c));       // host outputs filled, host inputs free to be reused
+    return LPF_OK;
+}
+
+// ---- lpf_first_match (include/lpf.h): Same_color's first-mask labels of a batch, kernels in lpf_first_match.hip.h ---------------------
+// Frames go through in ranges of consecutive frames (plan_ranges): a range stages its points, masks and colours when they are in host
+// memory, its outputs when those are, and needs 4 bytes per point for the codes (unless the dense output takes them) plus 16 bytes per
+// tile of 1024 points.  A host caller's lists go UP before the range's kernels and come back whole after them, as lpf_box_points does
+// with a first_box it cannot size: what the kernels do not write -- a frame's span at or beyond its count -- returns as it was, and
+// the call still ends with ONE host wait.
+#define LPF_FM_MAX_FRAMES 65535             // frames per launch: the grid's y
+
+int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_first_match_input *in,
+                    const lpf_first_match_outputs *out)
+{
+    int rc;
+    if ((rc = enter(c, "lpf_first_match", true))) return rc;
+    if (!in || !out || F < 0 || !frame_off)
+        return fail(c, LPF_ERR_ARG, "first_match: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
+    const int M = in->M;
+    if (M < 0 || M > LPF_MAX_MASKS_WIDE)
+        return fail(c, LPF_ERR_ARG, "first_match: M=%d masks per frame, lpf_first_match takes 0 .. LPF_MAX_MASKS_WIDE = %d", M, LPF_MAX_MASKS_WIDE);
+    if (M > 0 && (!in->masks || in->mh <= 0 || in->mw <= 0))
+        return fail(c, LPF_ERR_ARG, "first_match: masks=%p mh=%d mw=%d (with M > 0 masks is required and mh, mw are > 0)", in->masks, in->mh, in->mw);
+    if (out->car_rgb && !in->colors) return fail(c, LPF_ERR_ARG, "first_match: car_rgb is asked for, colors is NULL");
+    if (!out->n_car || !out->n_bg)
+        return fail(c, LPF_ERR_ARG, "first_match: n_car=%p n_bg=%p (both are required)", (void *)out->n_car, (void *)out->n_bg);
+    if (F == 0) return LPF_OK;
+    if ((rc = check_frames(c, "first_match", pts, frame_off, F, LPF_FM_TILE))) return rc;
+    // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
+    if ((rc = flush_pending(c))) return rc;
+
+    lpf_ctx::FirstMatch &D = c->fmat;
+    const size_t Ntot = (size_t)frame_off[F], nM = (size_t)M;
+    const size_t plane = M > 0 ? (size_t)in->mh * (size_t)in->mw : 0, esz = in->f32 ? 4 : 1;
+    const bool host_masks = M > 0 && !in->on_device, host_pts = Ntot > 0 && !pts_on_device, host_io = !out->on_device;
+    const bool dense = out->first_mask != nullptr;
+    const bool lists = out->car_idx || out->car_mask || out->car_xyz || out->car_rgb || out->bg_idx || out->bg_xyz;
+    auto given = [](const void *p, size_t b) { return p ? b : (size_t)0; };
+    const size_t out_pt = given(out->first_mask, 4) + given(out->car_idx, 8) + given(out->car_mask, 4) + given(out->car_xyz, 12) +
+                          given(out->car_rgb, 24) + given(out->bg_idx, 8) + given(out->bg_xyz, 12);
+    const size_t per_pt = (host_pts ? 16 : 0) + (dense ? 0 : 4) + (host_io ? out_pt : 0);
+    const size_t per_fr = 16 + (host_masks ? nM * plane * esz + given(in->colors, nM * 24) : 0) + (host_io ? 24 + nM * 8 : 0);
+    auto pts_of = [&](size_t f0, size_t n) { return (size_t)(frame_off[f0 + n] - frame_off[f0]); };
+    const std::vector<Span> ranges = plan_ranges((size_t)F, LPF_FM_MAX_FRAMES, [&](size_t f0, size_t n) {
+        return pts_of(f0, n) * per_pt + pts_of(f0, n) / LPF_FM_TILE * 16 + n * per_fr;
+    });
+    const size_t most_pts = largest(ranges, pts_of), most_f = largest(ranges, [](size_t, size_t n) { return n; });
+
+    // ---- buffers, reserved for the largest range -------------------------------------------------------------------------------------
+    const size_t most_tiles = most_pts / LPF_FM_TILE + most_f;
+    if ((rc = reserve(c, D.tab, (size_t)(F + 1) * 8))) return rc;
+    if (!dense && (rc = reserve(c, D.code, most_pts * 4))) return rc;
+    if ((rc = reserve(c, D.tiles, most_tiles * 16))) return rc;
+    if (host_pts && (rc = reserve(c, D.pts, most_pts * 16))) return rc;       // (here, not by the first range with points: no range waits)
+    if ((rc = upload(c, D.tab.p, frame_off, (size_t)(F + 1) * 8))) return rc;
+
+    LpfFmParams P;
+    memset(&P, 0, sizeof P);
+    set_cam(P.cam, ctx_cam(c));
+    P.M = M; P.mh = in->mh; P.mw = in->mw;
+    P.foff = (const long long *)D.tab.p;
+    P.tcnt = (int2 *)D.tiles.p;
+    P.tpre = P.tcnt + most_tiles;
+    const char *masks_k = nullptr;                            // a range's staged masks and colours, or the caller's
+    const double *colors_k = nullptr;
+    Stage I(host_masks);
+    I.add(masks_k, M > 0 ? in->masks : nullptr, nM * plane * esz, most_f);
+    I.add(colors_k, M > 0 ? in->colors : nullptr, nM * 24, most_f);
+    if ((rc = I.commit(c, D.in))) return rc;
+    // a host caller's outputs are staged range by range, a device caller's are written in place
+    const size_t np = host_io ? most_pts : Ntot, nf = host_io ? most_f : (size_t)F;
+    int *dense_k = nullptr;
+    Stage S(host_io);
+    S.add(dense_k, out->first_mask, 4, np);
+    S.add(P.car_idx, out->car_idx, 8, np);
+    S.add(P.car_mask, out->car_mask, 4, np);
+    S.add(P.car_xyz, out->car_xyz, 12, np);
+    S.add(P.car_rgb, out->car_rgb, 24, np);
+    S.add(P.bg_idx, out->bg_idx, 8, np);
+    S.add(P.bg_xyz, out->bg_xyz, 12, np);
+    S.add(P.n_valid, out->n_valid, 8, nf);
+    S.add(P.n_car, out->n_car, 8, nf);
+    S.add(P.n_bg, out->n_bg, 8, nf);
+    S.add(P.mask_count, out->mask_count, 8, nf * nM);
+    if ((rc = S.commit(c, D.out))) return rc;
+
+    // ---- the ranges -----------------------------------------------------------------------------------------------------------------
+    bool pts_in = false;
+    for (const Span &r : ranges) {
+        const int f0 = (int)r.first, fc = (int)r.count;
+        const long long a = frame_off[f0], nc = frame_off[f0 + fc] - a;
+        long long mc = 0;                                     // points of the range's largest frame: the grid's x
+        for (int f = f0; f < f0 + fc; ++f) mc = std::max(mc, (long long)(frame_off[f + 1] - frame_off[f]));
+        P.f0 = f0; P.pt_base = a;
+        P.out_base = range_base(host_io, a); P.fr_base = range_base(host_io, (long long)f0);
+        P.code = dense ? dense_k : (int *)D.code.p;
+        P.code_base = dense ? P.out_base : a;
+        if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, (size_t)a, (size_t)nc, most_pts, &P.cam.pts, &pts_in))) return rc;
+        if (nc == 0) P.cam.pts = nullptr;
+        if (M > 0) {
+            if ((rc = I.in(c, {{r.first, r.count}, {r.first, r.count}}))) return rc;                 // masks | colors
+            P.masks = host_masks ? masks_k : masks_k + r.first * nM * plane * esz;
+            P.colors = host_masks || !colors_k ? colors_k : colors_k + r.first * nM * 3;
+        }
+        const Span sp = {(size_t)a, (size_t)nc}, sf = {r.first, r.count}, none = {0, 0};
+        // first_mask | car_idx | car_mask | car_xyz | car_rgb | bg_idx | bg_xyz | n_valid | n_car | n_bg | mask_count: the lists as the
+        // caller has them
+        if (host_io && lists && (rc = S.in(c, {none, sp, sp, sp, sp, sp, sp, none, none, none, none}))) return rc;
+        if (P.mask_count && M > 0)
+            LPF_HIP(c, hipMemsetAsync(P.mask_count + (size_t)(f0 - P.fr_base) * nM, 0, (size_t)fc * nM * 8, c->stream));
+        const dim3 g((unsigned)((mc + LPF_FM_TILE - 1) / LPF_FM_TILE), (unsigned)fc);
+        if (mc > 0) {
+            with_flag(in->f32 != 0, [&](auto f32) {
+                typedef typename std::conditional<decltype(f32)::value, float, uint8_t>::type T;
+                hipLaunchKernelGGL(lpf_fm_count<T>, g, dim3(LPF_BLOCK), 0, c->stream, P);
+            });
+            LPF_HIP(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(lpf_fm_scan, dim3((unsigned)fc), dim3(LPF_BLOCK), 0, c->stream, P);
+        LPF_HIP(c, hipGetLastError());
+        if (mc > 0 && lists) {
+            hipLaunchKernelGGL(lpf_fm_scatter, g, dim3(LPF_BLOCK), 0, c->stream, P);
+            LPF_HIP(c, hipGetLastError());
+        }
+        if (host_io && (rc = S.back(c, {sp, sp, sp, sp, sp, sp, sp, sf, sf, sf, {r.first * nM, r.count * nM}}))) return rc;
+    }
+    if (host_io || host_masks || pts_in) LPF_HIP(c, host_wait(c));   // host outputs filled, host inputs free to be reused
     return LPF_OK;
 }
 

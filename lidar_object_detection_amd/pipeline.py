@@ -1164,6 +1164,166 @@ def label_points_first_match(points, TrVeloToRect, camera, masks, mask_colors=No
     return out
 
 
+def _first_match_planes(masks):
+    """One frame's masks for first_match_frames: (a GPU tensor [M,h,w], or a list of 2-D host arrays; is any of them float)."""
+    if masks is None:
+        return [], False
+    if _is_device_tensor(masks):
+        if masks.dim() != 3:
+            raise ValueError("device masks must be [M,h,w], got %s" % (tuple(masks.shape),))
+        return masks, str(masks.dtype) not in ("torch.uint8", "torch.bool")
+    planes = [np.asarray(mk) for mk in masks]
+    for pl in planes:
+        if pl.ndim != 2:
+            raise ValueError("masks must be a list of [h,w] arrays or an [M,h,w] array, got a mask of shape %s" % (pl.shape,))
+    return planes, any(pl.dtype.kind == "f" for pl in planes)
+
+
+def _first_match_masks(frames, camera):
+    """The frames' masks as ONE [F,M,mh,mw] batch for lpf_first_match (M = the most masks of a frame; the others pad with empty
+    planes) and each frame's own count.  Masks that all share one size go down AT THAT SIZE, whatever the camera's -- Same_color.py:125
+    reads every mask at its own size -- and a ragged list falls back to _same_color_canvas (each mask cropped / zero-padded to the
+    camera's size, which holds the same members).  float masks are read as ``mask > 0.5``, the others as ``> 0``; a batch that mixes
+    them goes as float32.  GPU tensors stay on the GPU."""
+    per = [_first_match_planes(f.masks) for f in frames]
+    sizes = {tuple(pl.shape[-2:]) for planes, _ in per for pl in planes}
+    if len(sizes) > 1:                                      # ragged: the canvas at the camera's size
+        per = [(_same_color_canvas(f.masks, camera), flt) if len(planes) else (planes, flt) for f, (planes, flt) in zip(frames, per)]
+        sizes = {(int(camera.height), int(camera.width))}
+    mh, mw = sizes.pop() if sizes else (1, 1)
+    Ms = [len(planes) for planes, _ in per]
+    M = max(Ms) if Ms else 0
+    flt = any(f for (planes, f) in per if len(planes))
+    on_gpu = [planes for planes, _ in per if _is_device_tensor(planes) and len(planes)]
+    if on_gpu:
+        import torch
+        dev = on_gpu[0].device
+        batch = torch.zeros((len(per), M, mh, mw), dtype=torch.float32 if flt else torch.uint8, device=dev)
+        for i, (planes, _) in enumerate(per):
+            if len(planes):
+                t = planes if _is_device_tensor(planes) else torch.from_numpy(np.stack(planes)).to(dev)
+                batch[i, :len(planes)].copy_(t if flt else (t > 0))
+        return batch, Ms
+    batch = np.zeros((len(per), M, mh, mw), np.float32 if flt else np.uint8)
+    for i, (planes, _) in enumerate(per):
+        for j, pl in enumerate(planes):
+            batch[i, j] = pl if flt else (pl > 0)
+    return batch, Ms
+
+
+def first_match_frames(frames, TrVeloToRect, camera, depth_max=30.0, mask_colors=None, device=0, ctx=None):
+    """Same_color.py:113-132 for a list of FrameInputs: one native call (lpf_first_match) per group of up to 256 masks for the whole
+    batch, no limit on the masks of a frame.  Per frame the dict label_points_first_match returns -- ``car_idx``, ``car_mask``,
+    ``background_idx``, ``colored_points``, ``colored_colors``, ``full_points`` -- plus ``mask_count`` (int64, the points whose first
+    mask is m, per mask of the frame).  mask_colors: one list of colours per frame (colored_colors = colour / 255.0, as the script
+    computes it); None takes each frame's ``colors``.  Points: host arrays, Scans of the read-ahead reader or GPU tensors; masks: a
+    list, an array or a GPU tensor [M,h,w] AT THEIR OWN SIZE, float (> 0.5) or uint8 / bool (nonzero); frames may differ in their
+    mask counts.  A later group can only claim points no earlier group claimed: with more than 256 masks the groups' dense codes are
+    merged and the lists are made from the merged codes.  The depth window is (0, depth_max)."""
+    frames = list(frames)
+    if not frames:
+        return []
+    if mask_colors is not None and len(mask_colors) != len(frames):
+        raise ValueError("mask_colors: one list of colours per frame (%d frames, %d lists)" % (len(frames), len(mask_colors)))
+    batch, Ms = _first_match_masks(frames, camera)
+    F, M = len(frames), int(batch.shape[1])
+    table = np.zeros((F, M, 3), np.float64)
+    for f, fr in enumerate(frames):
+        cols = fr.colors if mask_colors is None else mask_colors[f]
+        if len(cols) < Ms[f]:
+            raise ValueError("frame %s: %d masks, %d colours" % (fr.frame, Ms[f], len(cols)))
+        for i in range(Ms[f]):
+            table[f, i] = np.array(cols[i]) / 255.0
+    ctx = ctx or get_context(device)
+    ctx.set_camera(TrVeloToRect, camera.K, camera.width, camera.height, 0.0, float(depth_max))
+    gpu = _is_device_tensor(batch)
+
+    def host(a):
+        return a.cpu().numpy() if _is_device_tensor(a) else a
+
+    def colours(part):
+        if not gpu:
+            return part
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(part)).to(batch.device)
+
+    staged = ctx.stage_points([f.points for f in frames])
+    off = staged[0]
+    out = []
+    if M <= LPF_MAX_MASKS_WIDE:                             # one call: the lists as the GPU made them
+        r = ctx.first_match(None, batch, colours(table), want=("car_idx", "car_mask", "car_xyz", "car_rgb", "bg_idx", "bg_xyz", "mask_count"),
+                            staged=staged)
+        r = {k: host(v) for k, v in r.items()}
+        for f in range(F):
+            a, nc, nb = int(off[f]), int(r["n_car"][f]), int(r["n_bg"][f])
+            out.append({"car_idx": r["car_idx"][a:a + nc].copy(), "car_mask": r["car_mask"][a:a + nc].astype(np.int64),
+                        "background_idx": r["bg_idx"][a:a + nb].copy(), "colored_points": r["car_xyz"][a:a + nc].copy(),
+                        "full_points": r["bg_xyz"][a:a + nb].copy(), "colored_colors": r["car_rgb"][a:a + nc].copy(),
+                        "mask_count": r["mask_count"][f, :Ms[f]].copy()})
+        return out
+    code = None
+    for g in range(0, M, LPF_MAX_MASKS_WIDE):               # groups of 256 masks, merged on the dense codes
+        part = batch[:, g:g + LPF_MAX_MASKS_WIDE]
+        part = part.contiguous() if gpu else np.ascontiguousarray(part)
+        cur = host(ctx.first_match(None, part, want=("first_mask",), staged=staged)["first_mask"])
+        code = cur if code is None else np.where((code == -1) & (cur >= 0), cur + np.int32(g), code)
+    for f, fr in enumerate(frames):
+        cf = code[int(off[f]):int(off[f + 1])]
+        car, bg = np.flatnonzero(cf >= 0), np.flatnonzero(cf == -1)
+        first = cf[car].astype(np.int64)
+        p = fr.points.points if isinstance(fr.points, Scan) else host(fr.points)
+        out.append({"car_idx": car, "car_mask": first, "background_idx": bg, "colored_points": p[car, :3], "full_points": p[bg, :3],
+                    "colored_colors": table[f][first], "mask_count": np.bincount(first, minlength=Ms[f]).astype(np.int64)})
+    return out
+
+
+def process_frames_same_color(seq=0, cam_id=0, segmenter=None, image_loader=None, kitti360_path=None, frames=None, depth_max=30.0,
+                              device=0):
+    """Same_color.projectVeloToImage's frame loop (Same_color.py:80-138) without the Open3D window: yields ``(frame, result)`` with
+    result first_match_frames' dict for every frame that has a valid LiDAR point.  Scans are read in order by the native read-ahead
+    reader.  ``segmenter(image) -> (img, masks, mask_colors)`` is the segmentation stage (it stays outside this package).  The
+    script's ``[INFO]`` / ``[DEBUG]`` / ``[WARN]`` / ``[ERROR]`` lines are printed verbatim: a scan that cannot be read and a missing
+    image skip the frame (:88-90, :102-104), ``masks is None`` shows the plain cloud (:109-111), a frame without a valid point is
+    skipped with the script's warning (:136-138)."""
+    if segmenter is None:
+        raise ValueError("process_frames_same_color needs the segmentation callable (YOLO stays outside this package)")
+    root = kitti360_path or os.environ["KITTI360_DATASET"]
+    sequence, camera, velo_to_cam, velo_to_rect, velo = sequence_setup(root, seq, cam_id)
+    todo = velo.available_frames() if frames is None else list(frames)
+    paths = [os.path.join(velo.raw3DPcdPath, "%010d.bin" % f) for f in todo]
+    print(f"[INFO] Found {len(todo)} Velodyne frames.")
+    if not paths:
+        return
+    ctx = get_context(device)
+    sizes = [os.path.getsize(p) // 16 for p in paths if os.path.isfile(p)]
+    with ScanReader(ctx, paths, n_buffers=3, max_points=max(sizes + [1])) as reader:
+        for frame_idx, frame in enumerate(todo):
+            print(f"\n[INFO] Processing frame {frame} ({frame_idx + 1}/{len(todo)})...")
+            try:
+                scan = next(reader)
+                print(f"[DEBUG] Loaded {len(scan.points)} points from frame {frame}")
+            except Exception as e:
+                print(f"[ERROR] Failed to load velodyne data for frame {frame}: {e}")
+                continue
+            image_path = os.path.join(root, "data_2d_raw", sequence, f"image_{cam_id:02d}",
+                                      "data_rect" if cam_id in [0, 1] else "data_rgb", "%010d.png" % frame)
+            if not os.path.isfile(image_path):
+                print(f"[WARN] Image not found: {image_path}")
+                continue
+            _, masks, colors = segmenter(image_loader(image_path) if image_loader else image_path)[:3]
+            if masks is None:
+                print(f"[INFO] No cars detected in frame {frame}, showing plain cloud.")
+                masks, colors = [], []
+            r = first_match_frames([FrameInputs(frame, scan, masks, colors=colors)], velo_to_rect, camera, depth_max, None, device, ctx)[0]
+            n_car, n_bg = len(r["car_idx"]), len(r["background_idx"])
+            print(f"[DEBUG] Frame {frame}: {n_car + n_bg} points passed validation filter")
+            print(f"[DEBUG] Frame {frame}: {n_car} car points, {n_bg} background points")
+            if not n_car and not n_bg:
+                print(f"[WARN] No valid LiDAR points in frame {frame}")
+                continue
+            yield frame, r
+
+
 # ---------------------------------------------------------------------------------------
 # reporting (V3:431-468, cvs_erosion.py:232-295)
 # ---------------------------------------------------------------------------------------
