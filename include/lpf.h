@@ -41,7 +41,8 @@ extern "C" {
                                          the run's launch; on_device = 2 = lent corners in lpf_set_boxes_ex / lpf_set_boxes_cam0);
                                          geometry tables per run (a new batch shape no longer drains the pipeline);
                                          lpf_set_pipelined modes 1 / 3 and lpf_set_cu_partition removed (measured slower, DESIGN.md
-                                         section 8); lpf_set_geometry only in lab builds (-DLPF_LAB)
+                                         section 8); lpf_set_geometry only in lab builds (-DLPF_LAB), as are
+                                         lpf_lab_set_range_limits and lpf_lab_last_ranges
                                       6: lpf_set_mask_rects, lpf_resize_masks_u8 (added; nothing else changed)
                                       7: lpf_build_id, lpf_host_alloc / lpf_host_free, lpf_run_frame, lpf_erode_masks_u8 (added; nothing else changed)
                                       8: lpf_reader_submit_frame, lpf_reader_boxes, lpf_parse_boxes_json (added); lpf_resize_masks_u8 no longer
@@ -182,6 +183,15 @@ int  lpf_set_geometry(lpf_ctx *ctx, int mode);
  * counts, 4 mask pack, 5 project+label tiles) {first block start, last block end, sum of block durations, blocks, longest block}
  * in ticks of the 100 MHz wall clock, accumulated since the last reset.  The first call switches it on.  Synchronises. */
 int  lpf_lab_role_clock(lpf_ctx *ctx, unsigned long long *out, int reset);
+/* Range limits of the batched analysis calls (lpf_match_2d, lpf_assign_costs, lpf_assign_2d, lpf_inside_masks, lpf_box_points,
+ * lpf_box_views, lpf_first_match, lpf_depth_maps, lpf_depth_overlays), so that small batches reach the second and later ranges of
+ * large ones.  stage_budget_bytes replaces the staging budget of a range (256 MiB); max_items caps the items -- frames, images --
+ * of every range and of every per-launch frame loop at min(the product's limit, max_items).  0 for either = the product's value.
+ * Results do not depend on them. */
+int  lpf_lab_set_range_limits(lpf_ctx *ctx, long long stage_budget_bytes, int max_items);
+/* The ranges (chunks) the last batched analysis call planned; for lpf_inside_masks and lpf_box_points the launches of their frame
+ * loop; 0 when the call returned before it planned any. */
+int  lpf_lab_last_ranges(lpf_ctx *ctx);
 #endif
 
 /* ---- per-sequence state --------------------------------------------------------

@@ -309,6 +309,8 @@ def load(path=None):
     if hasattr(lib, "lpf_set_geometry"):                     # lab builds only (-DLPF_LAB)
         lib.lpf_set_geometry.argtypes = [_P, ctypes.c_int]
         lib.lpf_lab_role_clock.argtypes = [_P, _P, ctypes.c_int]
+        lib.lpf_lab_set_range_limits.argtypes = [_P, ctypes.c_longlong, ctypes.c_int]
+        lib.lpf_lab_last_ranges.argtypes = [_P]
     lib.lpf_allreduce_metrics.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, _P]
     lib.lpf_set_camera.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double]
     lib.lpf_set_masks_u8.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -638,6 +640,21 @@ class LpfContext:
         if not hasattr(self._lib, "lpf_set_geometry"):
             raise LpfError(-3, "lpf_set_geometry exists in lab builds only (python -m lidar_object_detection_amd._build lab; LPF_LIBRARY=...)")
         self._check(self._lib.lpf_set_geometry(self._h, {"auto": 0, "small": 1, "large": 2, "large-scan": 3, "small-narrow": 4, "small-1024": 5}[mode]))
+
+    def set_range_limits(self, budget=0, max_items=0):
+        """LAB BUILDS ONLY.  Range limits of the batched analysis calls (match_2d, assign_costs, assign_2d, inside_masks, box_points,
+        box_views, first_match, depth_maps, depth_overlays): budget = the staging bytes of a range, max_items = the most frames / images
+        of a range or launch (never above the product's limit); 0 = the product's value.  Same results."""
+        if not hasattr(self._lib, "lpf_lab_set_range_limits"):
+            raise LpfError(-3, "lpf_lab_set_range_limits exists in lab builds only (python -m lidar_object_detection_amd._build lab; LPF_LIBRARY=...)")
+        self._check(self._lib.lpf_lab_set_range_limits(self._h, int(budget), int(max_items)))
+
+    def last_ranges(self):
+        """LAB BUILDS ONLY.  The ranges (chunks) the last batched analysis call planned; for inside_masks and box_points the launches
+        of their frame loop."""
+        if not hasattr(self._lib, "lpf_lab_last_ranges"):
+            raise LpfError(-3, "lpf_lab_last_ranges exists in lab builds only (python -m lidar_object_detection_amd._build lab; LPF_LIBRARY=...)")
+        return int(self._lib.lpf_lab_last_ranges(self._h))
 
     ROLES = ("summaries", "box job", "lists", "box counts", "mask pack", "project+label tiles")
 

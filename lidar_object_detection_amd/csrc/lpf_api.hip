@@ -190,6 +190,8 @@ struct lpf_ctx {
     DevBuf resize_buf;                // lpf_resize_masks_u8: weight tables (+ staging for host callers)
     const int4 *rects_pending = nullptr; int rects_F = 0, rects_M = 0;
     DevBuf lab_clk;                   // LPF_LAB builds (lpf_lab_role_clock): 6 roles x 5 counters, or empty
+    long long lab_budget = 0;         // LPF_LAB builds (lpf_lab_set_range_limits): a range's staging budget and most items, 0 = the product's
+    int lab_max_items = 0, lab_ranges = 0;   // ... and the ranges the last batched call planned (lpf_lab_last_ranges)
     int geometry = 0;                 // LPF_LAB builds (lpf_set_geometry): 0 by launch size, 1 small, 2 large, 3 large + scan-kernel prefixes, 4 small + narrow tail
 
     // Pinned host ring for small uploads (tables, host corners) that must not block: the source of an asynchronous copy has to
@@ -633,15 +635,28 @@ template <typename T> int upload_table(lpf_ctx *c, DevBuf &buf, const T *tab, si
 // that needs more by itself is a range of its own.  The ranges are planned, and every buffer reserved for the largest of them
 // (largest()), before the first launch, so no range waits for the one before it.
 #define LPF_STAGE_BUDGET (256ull << 20)
-template <typename Cost> std::vector<Span> plan_ranges(size_t items, size_t most_items, Cost &&cost)
+// The budget, the most items of a range or launch (most: the product's limit) and the count lpf_lab_last_ranges reports: constants and
+// nothing in the product, lpf_lab_set_range_limits' in a lab build
+#ifdef LPF_LAB
+static size_t stage_budget(const lpf_ctx *c) { return c->lab_budget > 0 ? (size_t)c->lab_budget : (size_t)LPF_STAGE_BUDGET; }
+static size_t most_of(const lpf_ctx *c, size_t most) { return c->lab_max_items > 0 ? std::min(most, (size_t)c->lab_max_items) : most; }
+static void note_ranges(lpf_ctx *c, size_t n) { c->lab_ranges = (int)n; }
+#else
+static constexpr size_t stage_budget(const lpf_ctx *) { return (size_t)LPF_STAGE_BUDGET; }
+static constexpr size_t most_of(const lpf_ctx *, size_t most) { return most; }
+static void note_ranges(lpf_ctx *, size_t) {}
+#endif
+template <typename Cost> std::vector<Span> plan_ranges(lpf_ctx *c, size_t items, size_t most_items, Cost &&cost)
 {
+    const size_t budget = stage_budget(c), most = most_of(c, most_items);
     std::vector<Span> ranges;
     for (size_t i0 = 0; i0 < items;) {
         size_t n = 1;
-        while (i0 + n < items && n < most_items && cost(i0, n + 1) <= LPF_STAGE_BUDGET) ++n;
+        while (i0 + n < items && n < most && cost(i0, n + 1) <= budget) ++n;
         ranges.push_back({i0, n});
         i0 += n;
     }
+    note_ranges(c, ranges.size());
     return ranges;
 }
 template <typename Qty> size_t largest(const std::vector<Span> &ranges, Qty &&qty)
@@ -659,6 +674,7 @@ int enter(lpf_ctx *c, const char *who, bool need_camera)
     if (use_device(c)) return LPF_ERR_HIP;
     if (c->capturing) return fail(c, LPF_ERR_STATE, "%s cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end)", who);
     if (need_camera && !c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera has not been called");
+    note_ranges(c, 0);
     return LPF_OK;
 }
 
@@ -711,7 +727,7 @@ int check_m2_input(lpf_ctx *c, const char *who, int F, const lpf_match2d_input *
 // scratch), with the most detections, boxes, pairs and frames of any range: what the call's buffers are reserved for.
 struct M2Range { size_t fa, nf, d0, nd, b0, nb, p0, np; int most_rows; };   // first frame and count; detections, boxes, pairs; the tallest frame
 struct M2Plan { std::vector<LpfM2Frame> tab; std::vector<M2Range> ranges; size_t most_d = 0, most_b = 0, most_p = 0, most_f = 0; };
-template <typename Bytes> M2Plan m2_plan(const int32_t *det_off, const int32_t *box_off, int F, size_t most_frames, Bytes &&bytes)
+template <typename Bytes> M2Plan m2_plan(lpf_ctx *c, const int32_t *det_off, const int32_t *box_off, int F, size_t most_frames, Bytes &&bytes)
 {
     M2Plan P;
     P.tab.resize((size_t)F + 1);                              // (one past the end: where the detections, boxes and pairs end)
@@ -726,7 +742,7 @@ template <typename Bytes> M2Plan m2_plan(const int32_t *det_off, const int32_t *
         cost[(size_t)f + 1] = cost[(size_t)f] + bytes(t);
     }
     P.tab[(size_t)F] = {det_off[F], 0, box_off[F], 0, p};
-    for (const Span &r : plan_ranges((size_t)F, most_frames, [&](size_t f, size_t n) { return cost[f + n] - cost[f]; })) {
+    for (const Span &r : plan_ranges(c, (size_t)F, most_frames, [&](size_t f, size_t n) { return cost[f + n] - cost[f]; })) {
         const LpfM2Frame &a = P.tab[r.first], &b = P.tab[r.first + r.count];
         M2Range R = {r.first, r.count, (size_t)a.d0, (size_t)(b.d0 - a.d0), (size_t)a.b0, (size_t)(b.b0 - a.b0), (size_t)a.p0, (size_t)(b.p0 - a.p0), 0};
         for (size_t f = R.fa; f < R.fa + R.nf; ++f) R.most_rows = std::max(R.most_rows, P.tab[f].D);
@@ -1645,6 +1661,20 @@ int lpf_lab_role_clock(lpf_ctx *c, unsigned long long *out, int reset)
     if (reset && hipMemcpy(c->lab_clk.p, init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) return fail(c, LPF_ERR_HIP, "lpf_lab_role_clock: hipMemcpy");
     return LPF_OK;
 }
+
+// Range limits of the batched analysis calls, so that small batches reach the second and later ranges of large ones (plan_ranges, and
+// the frame loops of lpf_inside_masks and lpf_box_points): 0 = the product's value; max_items never raises a product limit.
+int lpf_lab_set_range_limits(lpf_ctx *c, long long stage_budget_bytes, int max_items)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (stage_budget_bytes < 0 || max_items < 0)
+        return fail(c, LPF_ERR_ARG, "lpf_lab_set_range_limits: stage_budget_bytes=%lld max_items=%d (neither may be negative; 0 = the product's value)", stage_budget_bytes, max_items);
+    c->lab_budget = stage_budget_bytes;
+    c->lab_max_items = max_items;
+    return LPF_OK;
+}
+
+int lpf_lab_last_ranges(lpf_ctx *c) { return c ? c->lab_ranges : LPF_ERR_ARG; }
 #endif
 
 // Rectangles for the masks of the NEXT lpf_set_masks_* call: rects[F][M] = {x0, y0, x1, y1}, half open, pixels; the caller's
@@ -2617,7 +2647,7 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     const bool use_rects = M > 0 && rects_hold(*in);
     const size_t per_frame = hwp * 4 + (size_t)M * ntile * 12 + (planes ? (size_t)LW * hw * 4 * (in->erode_iters > 1 ? 2 : 1) : 0) +
                              (host_masks ? (size_t)M * (hw * esz + 16) : 0) + (host_pts ? (size_t)maxN * 16 : 0);
-    const std::vector<Span> chunks = plan_ranges((size_t)F, (size_t)F, [&](size_t, size_t n) { return n * per_frame; });
+    const std::vector<Span> chunks = plan_ranges(c, (size_t)F, (size_t)F, [&](size_t, size_t n) { return n * per_frame; });
     const size_t Fc = chunks[0].count;
     const size_t most_pts = largest(chunks, [&](size_t f0, size_t n) { return frame_off[f0 + n] - frame_off[f0]; });
 
@@ -2765,7 +2795,7 @@ int lpf_depth_overlays(lpf_ctx *c, int F, const lpf_depth_overlay_input *in, con
 
     // ---- the chunks: [i0, i0 + n) of the F * M images, of frames [fa, fa + nf) ----------------------------------------------------
     auto frames_of = [&](size_t i0, size_t n) { return (i0 + n - 1) / M - i0 / M + 1; };
-    const std::vector<Span> chunks = plan_ranges(total, LPF_DO_MAX_IMAGES, [&](size_t i0, size_t n) { return n * per_image + frames_of(i0, n) * per_frame; });
+    const std::vector<Span> chunks = plan_ranges(c, total, LPF_DO_MAX_IMAGES, [&](size_t i0, size_t n) { return n * per_image + frames_of(i0, n) * per_frame; });
     const size_t most_img = largest(chunks, [](size_t, size_t n) { return n; }), most_fr = largest(chunks, frames_of);
 
     LpfDoParams Q;
@@ -2839,7 +2869,7 @@ int lpf_match_2d(lpf_ctx *c, int F, const lpf_match2d_input *in, const lpf_match
     const size_t esz = in->dets_f64 ? 8 : 4;
 
     // ---- the frame table and the ranges of frames: a frame stages its host inputs and host outputs --------------------------------------
-    const M2Plan P = m2_plan(in->det_off, in->box_off, F, LPF_M2_MAX_FRAMES, [&](const LpfM2Frame &t) {
+    const M2Plan P = m2_plan(c, in->det_off, in->box_off, F, LPF_M2_MAX_FRAMES, [&](const LpfM2Frame &t) {
         return (host_in ? (size_t)t.D * 4 * esz + (size_t)t.B * 36 : 0) + (host_out ? (size_t)t.D * 12 + (size_t)nmat * 8 * (size_t)t.D * (size_t)t.B : 0);
     });
     if ((rc = upload_table(c, D.tab, P.tab.data(), (size_t)F))) return rc;
@@ -2911,7 +2941,7 @@ static int assign_batch(lpf_ctx *c, const char *who, int F, const int32_t *det_o
                         rows, live, LPF_ASSIGN_MAX);
     }
     // ---- the frame table and the ranges of frames: a frame's scratch, its staged host inputs, its outputs ------------------------------
-    const M2Plan P = m2_plan(det_off, box_off, F, LPF_AS_MAX_FRAMES, [&](const LpfM2Frame &t) {
+    const M2Plan P = m2_plan(c, det_off, box_off, F, LPF_AS_MAX_FRAMES, [&](const LpfM2Frame &t) {
         const size_t pairs = (size_t)t.D * (size_t)t.B, staged = m2 ? (size_t)t.D * 4 * esz + (size_t)t.B * 36 : pairs * 8 + (size_t)t.B * 4;
         return pairs * 8 + (size_t)t.B * 4 + 4 + (host_in ? staged : 0) + (size_t)t.D * (m2 ? 40 : 4) + 4;
     });
@@ -3080,9 +3110,11 @@ int lpf_inside_masks(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
     O.add(Q.matched, out->matched, 4, fm);
     if ((rc = O.commit(c, D.out))) return rc;
     if (Q.inside || Q.part_idx || Q.part_xyz || Q.n_inside || Q.matched) {
-        for (int f0 = 0; f0 < F; f0 += LPF_IN_MAX_FRAMES) {
+        const int per_launch = (int)most_of(c, LPF_IN_MAX_FRAMES);
+        note_ranges(c, ((size_t)F + per_launch - 1) / per_launch);
+        for (int f0 = 0; f0 < F; f0 += per_launch) {
             Q.f0 = f0;
-            const dim3 g((unsigned)M, (unsigned)std::min(F - f0, LPF_IN_MAX_FRAMES));
+            const dim3 g((unsigned)M, (unsigned)std::min(F - f0, per_launch));
             with_flag(BX.oriented != 0, [&](auto oriented) {
                 hipLaunchKernelGGL((lpf_inside_cars<decltype(oriented)::value>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
             });
@@ -3182,9 +3214,11 @@ int lpf_box_points(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     const bool first_whole = host_out && !host_in && out->first_box && Ntot;
     if (first_whole) LPF_HIP(c, hipMemcpyAsync(Q.first_box, out->first_box, Ntot * 4, hipMemcpyHostToDevice, c->stream));
     const unsigned gx = (unsigned)std::max<int64_t>((most + LPF_BP_CHUNK - 1) / LPF_BP_CHUNK, 1);     // (a block per frame writes frame_counts[f][0])
-    for (int f0 = 0; f0 < F; f0 += LPF_BP_MAX_FRAMES) {
+    const int per_launch = (int)most_of(c, LPF_BP_MAX_FRAMES);
+    note_ranges(c, ((size_t)F + per_launch - 1) / per_launch);
+    for (int f0 = 0; f0 < F; f0 += per_launch) {
         Q.f0 = f0;
-        const dim3 g(gx, (unsigned)std::min(F - f0, LPF_BP_MAX_FRAMES));
+        const dim3 g(gx, (unsigned)std::min(F - f0, per_launch));
         with_flag(BX.oriented != 0, [&](auto oriented) {
             hipLaunchKernelGGL((lpf_box_points_kernel<decltype(oriented)::value>), g, dim3(LPF_BLOCK), 0, c->stream, Q);
         });
@@ -3244,7 +3278,7 @@ int lpf_box_views(lpf_ctx *c, int F, const lpf_box_views_input *in, const lpf_bo
         t.b0 = in->box_off[f]; t.B = in->box_off[f + 1] - t.b0;
         cost[(size_t)f + 1] = cost[(size_t)f] + (host_in ? (size_t)t.B * 192 : 0) + (host_out ? (size_t)t.B * out_bytes + 24 : 0);
     }
-    const std::vector<Span> ranges = plan_ranges((size_t)F, (size_t)F, [&](size_t f, size_t n) { return cost[f + n] - cost[f]; });
+    const std::vector<Span> ranges = plan_ranges(c, (size_t)F, (size_t)F, [&](size_t f, size_t n) { return cost[f + n] - cost[f]; });
     const size_t most_b = largest(ranges, [&](size_t f, size_t n) { return in->box_off[f + n] - in->box_off[f]; });
     const size_t most_f = largest(ranges, [](size_t, size_t n) { return n; });
     if ((rc = upload_table(c, D.tab, tab.data(), (size_t)F))) return rc;
@@ -3331,7 +3365,7 @@ int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int 
     const size_t per_pt = (host_pts ? 16 : 0) + (dense ? 0 : 4) + (host_io ? out_pt : 0);
     const size_t per_fr = 16 + (host_masks ? nM * plane * esz + given(in->colors, nM * 24) : 0) + (host_io ? 24 + nM * 8 : 0);
     auto pts_of = [&](size_t f0, size_t n) { return (size_t)(frame_off[f0 + n] - frame_off[f0]); };
-    const std::vector<Span> ranges = plan_ranges((size_t)F, LPF_FM_MAX_FRAMES, [&](size_t f0, size_t n) {
+    const std::vector<Span> ranges = plan_ranges(c, (size_t)F, LPF_FM_MAX_FRAMES, [&](size_t f0, size_t n) {
         return pts_of(f0, n) * per_pt + pts_of(f0, n) / LPF_FM_TILE * 16 + n * per_fr;
     });
     const size_t most_pts = largest(ranges, pts_of), most_f = largest(ranges, [](size_t, size_t n) { return n; });
