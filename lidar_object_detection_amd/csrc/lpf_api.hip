@@ -1199,7 +1199,7 @@ int stage_masks(lpf_ctx *c, const lpf_wide_input &m, int F, size_t hw, DevBuf &d
     return LPF_OK;
 }
 
-// a camera as the kernels take it (LpfParams' T, K, dmin, dmax, W, H): the context's (lpf_set_camera) or a lpf_cam_input's
+// a camera as the kernels take it (LpfCam): the context's (lpf_set_camera) or a lpf_cam_input's
 struct Cam {
     const double *T, *K;              // T: rows 0..2 are used (as lpf_set_camera)
     double dmin, dmax;
@@ -1207,7 +1207,7 @@ struct Cam {
 };
 Cam ctx_cam(const lpf_ctx *c) { return Cam{c->T, c->K, c->dmin, c->dmax, c->W, c->H}; }
 Cam input_cam(const lpf_cam_input &I) { return Cam{I.T_velo_to_rect, I.K, I.depth_min_excl, I.depth_max_excl, I.W, I.H}; }
-void set_cam(LpfParams &P, const Cam &k)
+void set_cam(LpfCam &P, const Cam &k)
 {
     memcpy(P.T, k.T, sizeof P.T);
     memcpy(P.K, k.K, sizeof P.K);
@@ -2202,13 +2202,11 @@ int lpf_depth_image(lpf_ctx *c, const float *pts, int64_t N, int on_device, doub
     LPF_HIP(c, hipMemsetAsync(dD, 0, hw * 8, c->stream));
     LPF_HIP(c, hipMemsetAsync(dW, 0, hw * 4, c->stream));
     if (N > 0) {
-        LpfParams P;
-        memset(&P, 0, sizeof P);
+        LpfCam P;
         set_cam(P, ctx_cam(c));
-        P.pts = (const float4 *)dP;
         const dim3 g((unsigned)((N + LPF_BLOCK - 1) / LPF_BLOCK));
-        hipLaunchKernelGGL((lpf_depth_image_kernel<0>), g, dim3(LPF_BLOCK), 0, c->stream, P, (int)N, dW, dD);
-        hipLaunchKernelGGL((lpf_depth_image_kernel<1>), g, dim3(LPF_BLOCK), 0, c->stream, P, (int)N, dW, dD);
+        hipLaunchKernelGGL((lpf_depth_image_kernel<0>), g, dim3(LPF_BLOCK), 0, c->stream, P, (const float4 *)dP, (int)N, dW, dD);
+        hipLaunchKernelGGL((lpf_depth_image_kernel<1>), g, dim3(LPF_BLOCK), 0, c->stream, P, (const float4 *)dP, (int)N, dW, dD);
         LPF_HIP(c, hipGetLastError());
     }
     if (!on_device) {
@@ -2693,8 +2691,8 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
         long long mc = 0;
         for (int f = f0; f < f0 + fc; ++f) mc = std::max(mc, (long long)(frame_off[f + 1] - frame_off[f]));
         P.f0 = f0; P.pt_base = a;
-        if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, (size_t)a, (size_t)nc, most_pts, &P.cam.pts, &pts_in))) return rc;
-        if (nc == 0) P.cam.pts = nullptr;
+        if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, (size_t)a, (size_t)nc, most_pts, &P.pts, &pts_in))) return rc;
+        if (nc == 0) P.pts = nullptr;
         if (M > 0) {
             if ((rc = I.in(c, {{ch.first, ch.count}, {ch.first, ch.count}}))) return rc;             // masks | rects
             const void *dm = host_masks ? masks_k : (const char *)masks_k + ch.first * M * hw * esz;
@@ -3419,8 +3417,8 @@ int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int 
         P.out_base = range_base(host_io, a); P.fr_base = range_base(host_io, (long long)f0);
         P.code = dense ? dense_k : (int *)D.code.p;
         P.code_base = dense ? P.out_base : a;
-        if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, (size_t)a, (size_t)nc, most_pts, &P.cam.pts, &pts_in))) return rc;
-        if (nc == 0) P.cam.pts = nullptr;
+        if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, (size_t)a, (size_t)nc, most_pts, &P.pts, &pts_in))) return rc;
+        if (nc == 0) P.pts = nullptr;
         if (M > 0) {
             if ((rc = I.in(c, {{r.first, r.count}, {r.first, r.count}}))) return rc;                 // masks | colors
             P.masks = host_masks ? masks_k : masks_k + r.first * nM * plane * esz;

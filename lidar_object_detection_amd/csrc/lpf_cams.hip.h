@@ -24,6 +24,7 @@ struct LpfCamsArgs {
     int C;                             // cameras
     int ntail[LPF_MAX_CAMS_DEV];       // tail blocks of camera c (count blocks first, then list blocks: lpf_tail_block)
 };
+static_assert(sizeof(LpfCamsArgs) <= 4096, "a kernel's argument segment holds 4 KB");
 
 template <int ROWS, typename LT>
 __global__ __launch_bounds__(LPF_BLOCK) void lpf_cams_stream(const LpfCamsArgs A)

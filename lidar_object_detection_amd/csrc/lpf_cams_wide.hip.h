@@ -12,7 +12,7 @@
 //   lpf_cams_wide_lists    grid (frames x the most label words of any camera, cameras)
 //   lpf_cams_wide_boxes    grid (the most (frame, word, 64-box word) blocks of any camera, LPF_WIDE_PARTS, cameras)
 //   lpf_cams_wide_best     grid (frames, cameras)
-// A block beyond its own camera's extent returns at once.  The camera records travel by value: C x sizeof(LpfWideParams) = 4 x 848
+// A block beyond its own camera's extent returns at once.  The camera records travel by value: C x sizeof(LpfWideParams) = 4 x 464
 // bytes of the 4 KB of kernel arguments.  Every access to them is indexed by a wave-uniform camera (blockIdx.y / blockIdx.z, or the loop
 // counter), so they stay scalar loads from the argument segment -- no table upload, no dependent global load before the first point.
 // Each camera's masks are packed by lpf_wide_pack / lpf_erode_packed into planes of its own, and its box tables are built by
@@ -25,6 +25,7 @@ struct LpfCamsWideArgs {
     LpfWideParams P[LPF_MAX_CAMS_DEV]; // camera c's lpf_run_wide chain; P[0]'s frame table also gives the pass's chunks
     int C;                             // cameras
 };
+static_assert(sizeof(LpfCamsWideArgs) <= 4096, "a kernel's argument segment holds 4 KB");
 
 __global__ __launch_bounds__(LPF_BLOCK) void lpf_cams_wide_project(const LpfCamsWideArgs A)
 {

@@ -3,7 +3,7 @@
 // seg_with_pointcloud.py:160-170 fills depthMap_m[v,u] = depth of the last valid point inside mask m at that pixel.  The last valid
 // point of a pixel wins whatever the mask, so car m of frame f is flatnonzero(where(member_m, D_f, 0)) with D_f lpf_depth_image's
 // last-writer image.  The kernels below are separate launches in stream order over a chunk of frames; no block waits for another.
-//   lpf_dm_winner   one thread per point: the lpf_depth_image_kernel<0> arithmetic, atomicMax(win[f][pix], i + 1)
+//   lpf_dm_winner   one thread per point: lpf_depth_image_kernel<0>'s lpf_project_point + lpf_pixel, atomicMax(win[f][pix], i + 1)
 //   lpf_dm_raster   one wave per (frame, wave tile of 1024 consecutive pixels, group of 32 masks), slot k of lane l = pixel 64 k + l
 //                   of the tile (the groups' counts and slots are independent: a mask's list only depends on that mask):
 //                   COUNT: members per (mask, tile) with ballot + popcount, at pixels with a winner only
@@ -23,7 +23,8 @@
 #define LPF_DM_MGROUP 32                    // masks per lpf_dm_raster wave (blockIdx.z: the group)
 
 struct LpfDmParams {
-    LpfParams cam;                          // T, K, dmin, dmax, W, H, pts (the chunk's first point); nothing else of it is used
+    LpfCam cam;
+    const float4 *pts;                      // the chunk's first point
     int M, LW, f0, ntile;                   // masks per frame, label words (planes), first frame of the chunk, wave tiles per frame
     long long hwp;                          // pitch of a winner plane: ntile * LPF_DM_TILE (>= W * H, zero beyond)
     long long pt_base;                      // frame_off[f0]
@@ -46,11 +47,11 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_dm_winner(const LpfDmParams P)
     const long long a = P.foff[P.f0 + fl], n = P.foff[P.f0 + fl + 1] - a;
     const long long i = (long long)blockIdx.x * LPF_BLOCK + threadIdx.x;
     if (i >= n) return;
-    const float4 p = P.cam.pts[a - P.pt_base + i];
+    const float4 p = P.pts[a - P.pt_base + i];
     double uf, vf, d;
+    int ui, vi;
     lpf_project_point(P.cam, p.x, p.y, p.z, uf, vf, d);
-    const int ui = lpf_sat_i32(rint(uf)), vi = lpf_sat_i32(rint(vf));
-    if (((unsigned)ui < (unsigned)P.cam.W) && ((unsigned)vi < (unsigned)P.cam.H) && (d > P.cam.dmin) && (d < P.cam.dmax))
+    if (lpf_pixel(P.cam, uf, vf, d, ui, vi))
         atomicMax(&P.win[(size_t)fl * P.hwp + (size_t)vi * P.cam.W + ui], (unsigned)i + 1u);
 }
 
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_dm_raster(const LpfDmParams P)
                     P.pix[o] = p;
                     if (P.pidx) P.pidx[o] = i;
                     if (P.depth) {
-                        const float4 q = P.cam.pts[P.foff[fo] - P.pt_base + i];
+                        const float4 q = P.pts[P.foff[fo] - P.pt_base + i];
                         double uf, vf, d;
                         lpf_project_point(P.cam, q.x, q.y, q.z, uf, vf, d);
                         P.depth[o] = d;

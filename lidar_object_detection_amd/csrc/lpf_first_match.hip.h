@@ -5,7 +5,7 @@
 // read at their OWN size mh x mw: nothing is resized and nothing outside [0, mh) x [0, mw) is read.  Three launches in stream order
 // over a range of frames; no block waits for another.  A block owns a tile of LPF_FM_TILE consecutive points of one frame, four per
 // thread (row j, thread t = point j * 256 + t of the tile: the four 16-byte point loads of a lane are in flight together).
-//   lpf_fm_count    projects and clips as lpf_dm_winner does (lpf_project_point, rint, saturate), then looks for the first mask by
+//   lpf_fm_count    projects and clips as every projecting kernel does (lpf_project_point, lpf_pixel), then looks for the first mask by
 //                   direct reads, LPF_FM_AHEAD masks of every pending row in flight at a time, until no lane of the wave is pending:
 //                   lanes leave the loop at different m.  The 4-byte code of every point (-2 not valid, -1 background, else m) goes
 //                   to the dense output or to scratch; car and background points are counted per tile with wave ballots;
@@ -27,9 +27,10 @@
 #define LPF_FM_AHEAD 4                            // masks of a pending row read before the first of them is tested
 
 struct LpfFmParams {
-    LpfParams cam;                          // T, K, dmin, dmax, W, H, pts (the range's first point); nothing else of it is used
+    LpfCam cam;
+    const float4 *pts;                      // the range's first point
     int M, mh, mw, f0;                      // masks per frame, their own size, first frame of the range
-    long long pt_base;                      // frame_off[f0]: cam.pts and the scratch codes begin there
+    long long pt_base;                      // frame_off[f0]: pts and the scratch codes begin there
     long long code_base;                    // code[frame_off[f] + i - code_base]
     long long out_base, fr_base;            // the per-point / per-frame outputs begin at that point / frame (staged ranges; else 0)
     const long long *foff;                  // [F + 1] the batch's frame offsets
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_fm_count(const LpfFmParams P)
     s_hist[tid] = 0u;
     __syncthreads();
 
-    const float4 *__restrict__ pts = P.cam.pts + (a - P.pt_base);
+    const float4 *__restrict__ pts = P.pts + (a - P.pt_base);
     float4 p[LPF_FM_PER];
 #pragma unroll
     for (int j = 0; j < LPF_FM_PER; ++j) {
@@ -91,9 +92,9 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_fm_count(const LpfFmParams P)
     for (int j = 0; j < LPF_FM_PER; ++j) {
         const long long i = i0 + j * LPF_BLOCK + tid;
         double uf, vf, d;
+        int ui, vi;
         lpf_project_point(P.cam, p[j].x, p[j].y, p[j].z, uf, vf, d);
-        const int ui = lpf_sat_i32(rint(uf)), vi = lpf_sat_i32(rint(vf));
-        const bool valid = i < n && ((unsigned)ui < (unsigned)P.cam.W) && ((unsigned)vi < (unsigned)P.cam.H) && (d > P.cam.dmin) && (d < P.cam.dmax);
+        const bool valid = lpf_pixel(P.cam, uf, vf, d, ui, vi) && i < n;
         code[j] = valid ? -1 : -2;
         pix[j] = 0;
         if (valid && ui < mw && vi < mh) {
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_fm_scatter(const LpfFmParams P)
     }
     __syncthreads();
     const int2 pre = P.tpre[lpf_fm_tile0(P, fl, a) + blockIdx.x];
-    const float4 *__restrict__ pts = P.cam.pts + (a - P.pt_base);
+    const float4 *__restrict__ pts = P.pts + (a - P.pt_base);
     const size_t o0 = (size_t)(a - P.out_base);
     const int M = P.M;
 #pragma unroll

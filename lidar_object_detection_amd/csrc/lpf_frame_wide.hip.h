@@ -6,8 +6,8 @@
 //                            lpf_wide_project writes (uv / depth / u_f / v_f, the LW label words of every point, the flags bytes,
 //                            chunk_cnt), so lpf_wide_scan / _scatter / _lists / _boxes / _best run on its output unchanged.
 //
-// Per point the projection and the validity test are lpf_wide_project_chunk's own (lpf_project_point, rint, lpf_sat_i32): u, v and
-// validity are bit-equal by construction.  Mask m contributes bit m & 31 of word m >> 5 of a valid point at (u, v) iff
+// Both ends of the chunk are lpf_wide_project_chunk's own code: lpf_wide_project_point (projection, validity, the per-point stores)
+// and lpf_wide_chunk_end (flags, chunk_cnt).  Only the label words between them are found differently.  Mask m contributes bit m & 31 of word m >> 5 of a valid point at (u, v) iff
 //   u >= x0 && u < x1 && v >= y0 && v < y1  and  lpf_member<uint8_t, 0>(masks[m][v][u])
 // -- the per-pixel test of lpf_wide_pack with rectangles, so the two forms agree even where a mask has bytes outside its rectangle.
 // The rectangles are only compared, never computed with (INT32_MIN / INT32_MAX mean "no limit").
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_direct_project(const LpfWi
     const int4 *__restrict__ rf = rects + (size_t)f * M;
     const int lane = lpf_lane(), wave = lpf_wave(), tid = threadIdx.x;
 
-    // ---- project: lpf_wide_project_chunk's per-point work ---------------------------------------------------------------------
+    // ---- project -----------------------------------------------------------------------------------------------------------------
     int pu[4], pv[4];
     unsigned okm = 0;                                       // bit r: point r is valid
     int u0 = 0x7fffffff, u1 = -1, v0 = 0x7fffffff, v1 = -1;
@@ -50,17 +50,8 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_direct_project(const LpfWi
         const int i = base + tid * 4 + r;
         if (i >= fr.N) continue;
         const size_t g = (size_t)fr.pt_off + i;
-        const float4 p = W.pts[g];
-        double uf, vf, d;
-        lpf_project_point(W.cam, p.x, p.y, p.z, uf, vf, d);
-        const double ru = rint(uf), rv = rint(vf);        // np.round: half to even
-        const int ui = lpf_sat_i32(ru), vi = lpf_sat_i32(rv);
-        const bool ok = ((unsigned)ui < (unsigned)W.cam.W) && ((unsigned)vi < (unsigned)W.cam.H) && (d > W.cam.dmin) && (d < W.cam.dmax);
-        W.uv[g] = make_int2(ui, vi);
-        if (W.depth) W.depth[g] = d;
-        if (W.uf) W.uf[g] = uf;
-        if (W.vf) W.vf[g] = vf;
-        if (ok) {
+        int ui, vi;
+        if (lpf_wide_project_point(W, g, W.pts[g], ui, vi)) {
             okm |= 1u << r;
             pu[r] = ui; pv[r] = vi;
             u0 = min(u0, ui); u1 = max(u1, ui); v0 = min(v0, vi); v1 = max(v1, vi);
@@ -134,18 +125,9 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_direct_project(const LpfWi
         }
     }
 
-    // ---- flags and the chunk's counts (lpf_wide_project_chunk's) ---------------------------------------------------------------
-    unsigned fl = 0, nv = 0, nm = 0;
+    // ---- flags and the chunk's counts ----------------------------------------------------------------------------------------------
+    unsigned fl = 0;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const bool ok = (okm >> r) & 1u;
-        fl |= ((ok ? 1u : 0u) | (any[r] ? 2u : 0u)) << (8 * r);
-        nv += ok ? 1u : 0u;
-        nm += any[r] ? 1u : 0u;
-    }
-    W.flags[(size_t)c * (LPF_WIDE_CHUNK / 4) + tid] = fl;
-    unsigned tv, tm;
-    lpf_wide_block_excl(nv, s_tmp, tv);
-    lpf_wide_block_excl(nm, s_tmp + 4, tm);
-    if (tid == 0) W.chunk_cnt[c] = make_int2((int)tv, (int)tm);
+    for (int r = 0; r < 4; ++r) fl |= (((okm >> r) & 1u) | (any[r] ? 2u : 0u)) << (8 * r);
+    lpf_wide_chunk_end(W, c, fl, s_tmp);
 }

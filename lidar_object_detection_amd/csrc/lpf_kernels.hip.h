@@ -53,11 +53,14 @@ struct LpfFrame {                // one per frame, device + host copy
     int pad4;
 };
 
-struct LpfParams {
+struct LpfCam {                  // what projects and clips a point (lpf_project_point, lpf_pixel); every projecting kernel carries one
     double T[12];                // rows 0..2 of TrVeloToRect
     double K[9];                 // camera.K[:3,:3]
     double dmin, dmax;
     int W, H;
+};
+
+struct LpfParams : LpfCam {
     int F, M;
     int seg_pts;                 // points per segment: LPF_SEG_QUANTUM or LPF_SEG_SMALL
     int nseg_total;
@@ -109,6 +112,7 @@ struct LpfParams {
                                  // launches keep both loads in one round trip: there the longest block is what counts.
     int tile_pts;                // points per K1 tile of this launch (4 waves)
 };
+static_assert(sizeof(LpfCam) == 192 && sizeof(LpfParams) == 576, "the camera leads LpfParams; neither layout may move");
 
 __device__ __forceinline__ int lpf_lane() { return threadIdx.x & 63; }
 __device__ __forceinline__ int lpf_wave() { return threadIdx.x >> 6; }
@@ -119,16 +123,6 @@ __device__ __forceinline__ int lpf_xcd_remap(int b, int n)
 {
     const int q = n >> 3, r = n & 7, x = b & 7, i = b >> 3;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
-
-__device__ __forceinline__ int lpf_find_frame(const LpfFrame *frames, int F, int sid)
-{
-    int lo = 0, hi = F;                      // last f with seg_off[f] <= sid
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (frames[mid].seg_off <= sid) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 // The frame record of a block: by value from the kernel arguments when the launch has one frame (no dependent load), else
@@ -188,7 +182,7 @@ __device__ __forceinline__ void lpf_div2(double qx, double qy, double ad, double
 
 // One point through K1 + K2 of the reference (V3:565-568): rows of T and K as k-ordered fma
 // chains (= OpenBLAS dgemm on these shapes), depth 0 -> -1e-6, x/|z| and y/|z|.
-__device__ __forceinline__ void lpf_project_point(const LpfParams &P, float fx, float fy, float fz,
+__device__ __forceinline__ void lpf_project_point(const LpfCam &P, float fx, float fy, float fz,
                                                   double &uf, double &vf, double &d)
 {
     const double x = (double)fx, y = (double)fy, z = (double)fz;
@@ -202,20 +196,20 @@ __device__ __forceinline__ void lpf_project_point(const LpfParams &P, float fx, 
     lpf_div2(qx, qy, fabs(d), uf, vf);
 }
 
-// The same with the 21 constants read from memory (LDS: every lane reads the same word, a broadcast) instead of from
-// the kernel arguments: the tail kernel cannot afford the 42 SGPRs next to everything else it keeps.
-__device__ __forceinline__ void lpf_project_point_mem(const double *__restrict__ TK, float fx, float fy, float fz,
-                                                      double &uf, double &vf, double &d)
+// K3, the clip: is pixel (ui, vi) at depth d inside the image and the depth range?  ui, vi come from lpf_sat_i32 of an integral
+// double r, and 0 <= r < W  <=>  (unsigned)sat_i32(r) < W (saturation and NaN -> INT32_MIN both land outside), so the image test
+// runs on the integers.
+__device__ __forceinline__ bool lpf_in_view(const LpfCam &P, int ui, int vi, double d)
 {
-    const double x = (double)fx, y = (double)fy, z = (double)fz;
-    double cx = TK[0] * x; cx = fma(TK[1], y, cx); cx = fma(TK[2],  z, cx); cx = cx + TK[3];
-    double cy = TK[4] * x; cy = fma(TK[5], y, cy); cy = fma(TK[6],  z, cy); cy = cy + TK[7];
-    double cz = TK[8] * x; cz = fma(TK[9], y, cz); cz = fma(TK[10], z, cz); cz = cz + TK[11];
-    double qx = TK[12] * cx; qx = fma(TK[13], cy, qx); qx = fma(TK[14], cz, qx);
-    double qy = TK[15] * cx; qy = fma(TK[16], cy, qy); qy = fma(TK[17], cz, qy);
-    d = TK[18] * cx; d = fma(TK[19], cy, d); d = fma(TK[20], cz, d);
-    if (d == 0.0) d = -1e-6;
-    lpf_div2(qx, qy, fabs(d), uf, vf);
+    return ((unsigned)ui < (unsigned)P.W) && ((unsigned)vi < (unsigned)P.H) && (d > P.dmin) && (d < P.dmax);
+}
+
+// A projected point's pixel: np.round (half to even), the ABI's int32 convention, and whether the point is in view.
+__device__ __forceinline__ bool lpf_pixel(const LpfCam &P, double uf, double vf, double d, int &ui, int &vi)
+{
+    ui = lpf_sat_i32(rint(uf));
+    vi = lpf_sat_i32(rint(vf));
+    return lpf_in_view(P, ui, vi, d);
 }
 
 // ------------------------------------------------------------------------------------
@@ -417,9 +411,9 @@ __device__ __forceinline__ void lpf_k1_tile(const LpfParams &P, const int blk, u
                 lpf_project_point(P, p[r].x, p[r].y, p[r].z, uf, vf, d);
                 ru = rint(uf); rv = rint(vf);                   // np.round: half to even
             }
-            // K3: clip.  ru, rv are integral: 0 <= ru < W  <=>  (unsigned)sat_i32(ru) < W  (saturation and
-            // NaN -> INT32_MIN both land outside), so the image test runs on the integers (u, v)
             const int ui = lpf_sat_i32(ru), vi = lpf_sat_i32(rv);
+            // K3: clip.  lpf_in_view's test behind `live`, written out: as a call the conjunction groups differently, and the compiler
+            // then schedules the narrow kernels differently (this site and the one below are the only ones that do not call it)
             const bool ok = live && ((unsigned)ui < (unsigned)P.W) && ((unsigned)vi < (unsigned)P.H) &&
                             (d > P.dmin) && (d < P.dmax);
             valid[r] = ok;
@@ -460,7 +454,7 @@ __device__ __forceinline__ void lpf_k1_tile(const LpfParams &P, const int blk, u
                 if (__any(l != 0u)) {                        // (wave-uniform)
                     double uf, vf, d;
                     lpf_project_point(P, p[r].x, p[r].y, p[r].z, uf, vf, d);
-                    const int ui = lpf_sat_i32(rint(uf)), vi = lpf_sat_i32(rint(vf));
+                    const int ui = lpf_sat_i32(rint(uf)), vi = lpf_sat_i32(rint(vf));    // lpf_pixel's rounding; a candidate lane is in view
                     const unsigned pix = (unsigned)(vi * P.W + ui);
                     uint32_t any = lpf_wave_or(l), l2 = 0u;
                     while (any) {                           // (wave-uniform: the masks that are a candidate of some lane)
@@ -565,7 +559,6 @@ __device__ __forceinline__ bool lpf_aabb_inside(double px, double py, double pz,
 // row broadcasts -- six v_add_u32 with a DPP modifier; lanes 48..63 end up holding the wave total.
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned lpf_rl(unsigned v, int l) { return (unsigned)__builtin_amdgcn_readlane((int)v, l); }
-__device__ __forceinline__ float lpf_rlf(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 __device__ __forceinline__ unsigned long long lpf_rl64(unsigned long long v, int l)
 {
     return (unsigned long long)lpf_rl((unsigned)v, l) | ((unsigned long long)lpf_rl((unsigned)(v >> 32), l) << 32);
@@ -1159,15 +1152,6 @@ __device__ __forceinline__ void lpf_count_chunk(const LpfParams &P, const LpfFra
     __builtin_amdgcn_wave_barrier();
     exact(qn);
     __builtin_amdgcn_wave_barrier();
-}
-
-// a wave takes a whole segment (big sparse launches: a chunk or so per segment)
-__device__ __forceinline__ void lpf_boxcount_wave(const LpfParams &P, const LpfFrame &fr, const int sid, float4 *s_pt, unsigned *qq,
-                                                  unsigned *s_cnt, const float *s_bq, const double *s_bp, const float *s_dom, const int wd)
-{
-    unsigned im, mbase;
-    const unsigned L = lpf_count_rows(P, fr, sid, im, mbase);
-    for (unsigned e0 = 0; e0 < L; e0 += 64) lpf_count_chunk(P, fr, sid, im, mbase, L, e0, s_pt, qq, s_cnt, s_bq, s_bp, s_dom, wd);
 }
 
 // Box data of word wd of the frame (boxes 64 wd ..) and the domain of its ground grid -> LDS, the block's counters zeroed; and, after the
@@ -1825,16 +1809,16 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_points_in_boxes_kernel(const fl
 // the winner write its depth.  Both stream the cloud once with the K1 arithmetic.
 // ------------------------------------------------------------------------------------
 template <int PASS>
-__global__ __launch_bounds__(LPF_BLOCK) void lpf_depth_image_kernel(const LpfParams P, int n, unsigned *__restrict__ win,
-                                                                    double *__restrict__ D)
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_depth_image_kernel(const LpfCam P, const float4 *__restrict__ pts, int n,
+                                                                    unsigned *__restrict__ win, double *__restrict__ D)
 {
     const int i = blockIdx.x * LPF_BLOCK + threadIdx.x;
     if (i >= n) return;
-    const float4 p = P.pts[i];
+    const float4 p = pts[i];
     double uf, vf, d;
+    int ui, vi;
     lpf_project_point(P, p.x, p.y, p.z, uf, vf, d);
-    const int ui = lpf_sat_i32(rint(uf)), vi = lpf_sat_i32(rint(vf));
-    if (((unsigned)ui < (unsigned)P.W) && ((unsigned)vi < (unsigned)P.H) && (d > P.dmin) && (d < P.dmax)) {
+    if (lpf_pixel(P, uf, vf, d, ui, vi)) {
         const size_t pix = (size_t)vi * P.W + ui;
         if (PASS == 0) atomicMax(&win[pix], (unsigned)i + 1u);
         else if (win[pix] == (unsigned)i + 1u) D[pix] = d;

@@ -1,7 +1,7 @@
 // lpf_wide.hip.h -- frames with up to LPF_MAX_MASKS_WIDE (256) masks in one pass (lpf_run_wide, include/lpf.h).
 //
 // A point's membership is LW = ceil(M / 32) label words instead of one.  Everything per point is the narrow path's own device code
-// -- the k-ordered f64 transform (lpf_project_point: lpf_div2, rint, lpf_sat_i32), the membership rules (lpf_member), the erosion
+// -- the k-ordered f64 transform and the clip (lpf_project_point, lpf_pixel), the membership rules (lpf_member), the erosion
 // (the plus-shaped AND of lpf_pack_erode, and lpf_erode_packed itself for the further iterations), the box tests (boxq bounds, then
 // lpf_oriented_inside / lpf_aabb_inside) and the first strict maximum of lpf_finalize_frame -- so a wide run is bit-equal to the
 // narrow one run once per group of 32 masks.  The kernels here are separate launches in stream order: nothing waits for another
@@ -30,7 +30,7 @@ struct LpfWideFrame {                  // per frame (host-built, uploaded)
 };
 
 struct LpfWideParams {
-    LpfParams cam;                     // T, K, dmin, dmax, W, H (lpf_project_point); nothing else of it is used
+    LpfCam cam;
     int F, M, LW, nchunk, nbw;         // nbw: 64-box words of the frame with the most boxes
     int oriented;
     long long inst_cap;
@@ -165,6 +165,30 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_pack_k(const T *__restrict
 }
 
 // ---- project + label: 1024 points per block, 4 consecutive points per thread ----------------------------------------------------
+// The two ends of a chunk, shared by its packed (lpf_wide_project_chunk) and direct (lpf_wide_direct_project) forms.
+// Point p at g of the concatenated arrays: uv / depth / u_f / v_f, its pixel, and whether it is valid.
+__device__ __forceinline__ bool lpf_wide_project_point(const LpfWideParams &W, const size_t g, const float4 p, int &ui, int &vi)
+{
+    double uf, vf, d;
+    lpf_project_point(W.cam, p.x, p.y, p.z, uf, vf, d);
+    const bool ok = lpf_pixel(W.cam, uf, vf, d, ui, vi);
+    W.uv[g] = make_int2(ui, vi);
+    if (W.depth) W.depth[g] = d;
+    if (W.uf) W.uf[g] = uf;
+    if (W.vf) W.vf[g] = vf;
+    return ok;
+}
+
+// The thread's flags word (a byte per point: bit 0 valid, bit 1 masked) and chunk c's counts of both (s_tmp: 8 words of LDS).
+__device__ __forceinline__ void lpf_wide_chunk_end(const LpfWideParams &W, const int c, const unsigned fl, unsigned *s_tmp)
+{
+    W.flags[(size_t)c * (LPF_WIDE_CHUNK / 4) + threadIdx.x] = fl;
+    unsigned tv, tm;
+    lpf_wide_block_excl(__popc(fl & 0x01010101u), s_tmp, tv);
+    lpf_wide_block_excl(__popc(fl & 0x02020202u), s_tmp + 4, tm);
+    if (threadIdx.x == 0) W.chunk_cnt[c] = make_int2((int)tv, (int)tm);
+}
+
 // Chunk c of frame f (chunk_off and the points depend on the points only: every camera of lpf_cams_wide_project finds the same ones).
 // PRE: the thread's four points are in p[] already (lpf_cams_wide_project loads them once for every camera); else each is read here.
 template <bool PRE>
@@ -174,22 +198,14 @@ __device__ __forceinline__ void lpf_wide_project_chunk(const LpfWideParams &W, c
     const int base = (c - fr.chunk_off) * LPF_WIDE_CHUNK;
     const size_t hw = (size_t)W.cam.W * (size_t)W.cam.H;
     const uint32_t *__restrict__ pl = W.planes ? W.planes + (size_t)f * W.LW * hw : nullptr;
-    unsigned fl = 0, nv = 0, nm = 0;
+    unsigned fl = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int i = base + threadIdx.x * 4 + r;          // frame-relative point
         if (i >= fr.N) break;
         const size_t g = (size_t)fr.pt_off + i;
-        const float4 p = PRE ? p_pre[r] : W.pts[g];
-        double uf, vf, d;
-        lpf_project_point(W.cam, p.x, p.y, p.z, uf, vf, d);
-        const double ru = rint(uf), rv = rint(vf);        // np.round: half to even
-        const int ui = lpf_sat_i32(ru), vi = lpf_sat_i32(rv);
-        const bool ok = ((unsigned)ui < (unsigned)W.cam.W) && ((unsigned)vi < (unsigned)W.cam.H) && (d > W.cam.dmin) && (d < W.cam.dmax);
-        W.uv[g] = make_int2(ui, vi);
-        if (W.depth) W.depth[g] = d;
-        if (W.uf) W.uf[g] = uf;
-        if (W.vf) W.vf[g] = vf;
+        int ui, vi;
+        const bool ok = lpf_wide_project_point(W, g, PRE ? p_pre[r] : W.pts[g], ui, vi);
         unsigned any = 0;
         uint32_t *__restrict__ lw = W.label_words + g * W.LW;
         if (ok && pl) {
@@ -199,14 +215,8 @@ __device__ __forceinline__ void lpf_wide_project_chunk(const LpfWideParams &W, c
             for (int w = 0; w < W.LW; ++w) lw[w] = 0u;
         }
         fl |= ((ok ? 1u : 0u) | (any ? 2u : 0u)) << (8 * r);
-        nv += ok ? 1u : 0u;
-        nm += any ? 1u : 0u;
     }
-    W.flags[(size_t)c * (LPF_WIDE_CHUNK / 4) + threadIdx.x] = fl;
-    unsigned tv, tm;
-    lpf_wide_block_excl(nv, s_tmp, tv);
-    lpf_wide_block_excl(nm, s_tmp + 4, tm);
-    if (threadIdx.x == 0) W.chunk_cnt[c] = make_int2((int)tv, (int)tm);
+    lpf_wide_chunk_end(W, c, fl, s_tmp);
 }
 
 __global__ __launch_bounds__(LPF_BLOCK) void lpf_wide_project(const LpfWideParams W)
