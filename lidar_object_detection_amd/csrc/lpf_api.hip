@@ -1031,13 +1031,17 @@ int set_masks_impl(lpf_ctx *c, const T *masks, int F, int M, int mode, int erode
     const bool per_set = c->fused && on_device && !c->capturing;
     int rc;
     if (!per_set && anything_owed(c) && (rc = sync_all(c))) return rc;    // owed tiles read set 0's label image / the staging copy
-    lpf_ctx::Scratch &S = c->sc[per_set ? c->parity : 0];
+    // (host masks in a pipelined mode: the pipeline has just been drained -- the staging copy is one -- and their label image goes to
+    //  the set of the next run too, where a fused run looks for it, as lpf_set_label_image's does: in set 0 every run but the first after
+    //  a mode switch was refused with "the masks were set for another scratch set")
+    const int set = (c->fused && !c->capturing) ? c->parity : 0;
+    lpf_ctx::Scratch &S = c->sc[set];
     hipStream_t ms = c->stream;
     c->mask_F = 0; c->mask_M = 0; S.label_cur = nullptr;
     // (masks a pipelined lpf_set_masks_* left unpacked stay on record until this call has its buffers -- so also when it is for no
     //  frames: the next run packs them.  Kept as it was)
     if (!c->unpacked.pipelined) forget_unpacked(c);
-    c->mask_set = per_set ? c->parity : 0;
+    c->mask_set = set;
     if (F == 0) return LPF_OK;
     const size_t hw = (size_t)c->H * c->W;
     if ((rc = reserve(c, S.label_a, (size_t)F * hw * 4))) return rc;
