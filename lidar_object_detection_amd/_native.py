@@ -1335,7 +1335,9 @@ class LpfContext:
         out = self._until_lists_fit(launch, inst_cap, off)
         return self._frame_results(off, M, *out)
 
-    def depth_maps(self, frames, masks, binarize="gt0.5", rects=None, erode_iters=0, cap=None, want_point_idx=True):
+    _DEPTH_MAPS_OUT = {"pix": "int64", "depth": "float64", "point_idx": "int64", "car_off": "int64", "need": "int64", "overflow": "int32"}
+
+    def depth_maps(self, frames, masks, binarize="gt0.5", rects=None, erode_iters=0, cap=None, want_point_idx=True, out=None):
         """seg_with_pointcloud's per-car depth maps of a batch of frames in ONE native call (lpf_depth_maps) and one host wait.
         frames: as run_wide's -- f32[N_f,4] host arrays, Scans of a ScanReader, float32 [N,4] GPU tensors.  masks: [M,H,W] or
         [F,M,H,W] at the camera's size (uint8 / bool: nonzero, or float32 under ``binarize``; "gt0.5" is the script's mask > 0.5),
@@ -1343,7 +1345,11 @@ class LpfContext:
         and depth window are set_camera's.  Returns, per frame, M tuples (pix int64, depth float64, point_idx int64 or None): car m
         = np.flatnonzero(np.where(member_m, D, 0)) with D the frame's depth_image, its depths and the winning points.  cap: list
         entries per frame of the first attempt (default from the point counts); a frame that needs more runs the call once more
-        with the exact capacity."""
+        with the exact capacity.
+        out: the caller's own GPU tensors for lpf_depth_maps_outputs -- "pix", "depth", "point_idx" [at least F, cap] (depth and point_idx
+        may be left out), "car_off" int64 [F, M + 1], "need" int64 [F], "overflow" int32 [F] (may be left out) -- with ``cap`` given:
+        ONE call in torch's stream order, no second attempt, nothing read back; entries at or beyond cap and beyond a frame's need are
+        not written (include/lpf.h).  Returns ``out``."""
         F = len(frames)
         if F == 0:
             raise ValueError("no frames")
@@ -1354,6 +1360,26 @@ class LpfContext:
         off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the call returns)
         inp = WideInput()
         self._wide_input(inp, batch, binarize, erode_iters)
+        if out is not None:
+            if cap is None or int(cap) < 1:
+                raise ValueError("depth_maps: out= needs a capacity of at least one entry")
+            unknown = set(out) - set(self._DEPTH_MAPS_OUT)
+            if unknown or "pix" not in out or "car_off" not in out or "need" not in out:
+                raise ValueError("depth_maps: out= holds pix, car_off, need and optionally depth, point_idx, overflow; got %s" % sorted(out))
+            for k, t in out.items():
+                rows = k in ("pix", "depth", "point_idx")
+                want = (F, int(cap)) if rows else (F, M + 1) if k == "car_off" else (F,)
+                shape = tuple(t.shape)
+                if not (_is_torch(t) and t.is_cuda and t.is_contiguous()) or len(shape) != len(want) or shape[1:] != want[1:] or \
+                        (shape[0] < F if rows else shape[0] != F):
+                    raise ValueError("depth_maps: out[%r] must be a contiguous GPU tensor %s, got %s" % (k, want, shape))
+            o = DepthMapsOutputs()
+            for k, dt in self._DEPTH_MAPS_OUT.items():
+                setattr(o, k, _dev_ptr(out.get(k), dt))
+            o.cap, o.on_device = int(cap), 1
+            self._call_in_order(out["pix"].device, self._lib.lpf_depth_maps, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o))
+            self._lent.append((_keep, batch))           # (staged points and masks: alive until the work has run)
+            return out
         if cap is None:                     # a quarter of the largest frame's points: frame 100's five cars are 8 k of its 109 k
             cap = 0 if M == 0 else max(1024, min(int(np.diff(off).max()) // 4, self.W * self.H))
 

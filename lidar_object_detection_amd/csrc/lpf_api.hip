@@ -159,6 +159,8 @@ struct lpf_ctx {
         int label_bytes = 4;          // element size of the label image: 1 (M <= 8), 2 (M <= 16) or 4
         DevBuf rgrid;                 // candidate grid of the masks' rectangles (LpfDirectRect tiles), [F][cells] uint32
         DevBuf rects;                 // lpf_set_mask_rects from host memory: the copy this set's run reads (its tiles may run a launch later)
+        DevBuf out_stage;             // what a pipelined run needs though its caller left it out (narrow_bind): written by this run's tiles,
+                                      // read by its tail a launch later, while the next run's tiles write theirs -- so one per set
         DevBuf tab;                   // [frames | segs | blks]
         std::vector<LpfFrame> tab_frames;         // the frame records `tab` was built from (empty: none) ...
         int tab_csplit = 0;                       // ... and its count blocks per (group, word): the key of the tables (narrow_tables)
@@ -204,7 +206,8 @@ struct lpf_ctx {
     // host-io staging
     DevBuf pib_box, pib_pts, pib_out, boxprep, dimg, coll;
     DevBuf st_pts;                    // staged points of a host caller (lpf_run_batch, lpf_depth_image)
-    DevBuf out_stage;                 // lpf_run_batch: staged outputs of a host caller, and what a run needs though its caller left it out (narrow_bind)
+    DevBuf out_stage;                 // lpf_run_batch: staged outputs of a host caller, and what an IN-ORDER run needs though its caller left it out
+                                      // (narrow_bind); a pipelined run keeps those in its scratch set (Scratch::out_stage)
     std::vector<LpfFrame> h_frames;   // frame records being built (narrow_layout)
     std::vector<char> h_tab;          // [frames | segs | blks] being built
 
@@ -1530,7 +1533,7 @@ void lpf_destroy(lpf_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (auto &S : c->sc) {
-        DevBuf *sb[] = {&S.vbal, &S.mbal, &S.seg_tab, &S.grp_tab, &S.frm_tab, &S.seg_pre, &S.cnt, &S.mlist, &S.label_a, &S.label_b, &S.tab, &S.rects, &S.rgrid};
+        DevBuf *sb[] = {&S.vbal, &S.mbal, &S.seg_tab, &S.grp_tab, &S.frm_tab, &S.seg_pre, &S.cnt, &S.mlist, &S.label_a, &S.label_b, &S.tab, &S.rects, &S.rgrid, &S.out_stage};
         for (DevBuf *b : sb) release(*b);
     }
     for (auto *ring : {c->bx, c->cams.bx})
@@ -1919,7 +1922,9 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
         if (n) LPF_HIP(c, hipMemcpyAsync(c->st_pts.p, pts, n * 16, hipMemcpyHostToDevice, c->stream));
         P.pts = (const float4 *)c->st_pts.p;
     }
-    if ((rc = narrow_bind(c, c->out_stage, *out, n, F, M, Btot, P))) return rc;
+    // (a pipelined run's own pieces -- the dense labels or pixels its compact copies are gathered from, the summaries -- live in its
+    //  scratch set: in the context's one buffer the next run's tiles overwrote the labels this run's tail had yet to read)
+    if ((rc = narrow_bind(c, fused ? S.out_stage : c->out_stage, *out, n, F, M, Btot, P))) return rc;
     if (M > 0) {                         // K1 -> tail hand-off of the masked points (sparse writes into N slots)
         if ((rc = reserve(c, S.mlist, n * 16))) return rc;
         P.mlist = (float4 *)S.mlist.p;

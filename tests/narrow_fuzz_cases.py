@@ -198,13 +198,19 @@ def _draw_boxes(rng, B, TrVeloToCam):
     return np.ascontiguousarray((np.asarray(TrVeloToCam, np.float64) @ homo.T).T[:, :3].reshape(B, 8, 3))
 
 
-def case(seed, calib):
+def case(seed, calib, sizes=None, **over):
     """One case as a dict: seed, the plan's values (W, H, M, kind, binarize, erode, element, source, rects_mode, box_source, outs,
     dmin), dmax, T, K, oriented, want_float, tight_cap, sizes, inside, frames (float32 [N,4] each), on_dmin (per frame: index of
     the point at depth == dmin, or -1), masks ([F,M,H,W] uint8 or float32), member ([F,M,H,W] uint8 0/1, the masks binarised),
-    rects ([F,M,4] int32 or None), cam0 (per frame [B,8,3] cam-0 corners), Tcv, TrVeloToCam."""
+    rects ([F,M,4] int32 or None), cam0 (per frame [B,8,3] cam-0 corners), Tcv, TrVeloToCam.  ``over`` replaces values of the
+    seed's plan (its keys), ``sizes`` the points per frame: for callers that lay out their own cases (tests/sequence_fuzz_cases.py);
+    without them the case is the seed's own."""
     rng = np.random.default_rng(seed)
     p = plan(seed)
+    if over:
+        p.update(over)
+        if p["source"] == "label" or p["M"] == 0:
+            p["rects"] = "none"
     TrVeloToCam, T, K0, W0, H0 = S.default_calibration(calib)
     K0 = np.asarray(K0, np.float64)[:3, :3]
     T = np.asarray(T, np.float64)
@@ -212,7 +218,8 @@ def case(seed, calib):
     M, dmin = p["M"], p["dmin"]
     if dmin != 0.0:
         T = _depth_row_rounded(T)
-    sizes = _frame_sizes(seed, rng, p["layout"])
+    drawn = _frame_sizes(seed, rng, p["layout"])
+    sizes = drawn if sizes is None else list(sizes)
     while len(sizes) > 1 and len(sizes) * M * H * W > MASK_BYTES:
         sizes.pop()
     F = len(sizes)

@@ -263,6 +263,55 @@ def test_host_masks_before_every_pipelined_run(mode):
         _check_queued(cs, refs, h, "%s, run %d" % (mode, k))
 
 
+@pytest.mark.parametrize("mode", ["fused", "fused-pack"])
+def test_queued_run_keeps_its_labels_when_the_next_run_brings_others(mode):
+    """Regression, found by tests/test_gpu_sequence_fuzz.py on its seed 7054: a pipelined run that is asked for label_valid WITHOUT
+    label_bits gathers its compact labels from dense ones of its own, which lived in ONE buffer of the context (narrow_bind), so the
+    tiles of the next run overwrote them in the very launch in which this run's tail read them.  They now live in the run's scratch
+    set.  The case as the fuzz met it, written out: row 10 of PLAN at 150 x 37 with 17 masks -- two frames of 0 and 65 points, float
+    masks under "v3" with one erosion, lent from an unaligned tensor, outputs without label_bits -- run twice; lpf_box_points with host
+    operands (it drains the pipeline); run again with the 3 x 3 element; then, with its masks set again under the 5 x 5 element, once
+    more.  The boxes and the camera are set once.  The third run's label_valid of frame 1 came back as the fourth's in 2 of 16 entries."""
+    import torch
+    from lidar_object_detection_amd._native import LpfContext
+    cs = G.case(G.DEFAULT_SEED_BASE + 10, load_calib(), size=(150, 37), M=17)
+    assert (cs["sizes"], cs["kind"], cs["erode"], cs["element"], cs["source"], cs["outs"]) == ([0, 65], "v3", 1, 3, "lent-unaligned", "no-label_bits")
+    cs5 = dict(cs, element=5)
+    refs, refs5 = G.reference(cs), G.reference(cs5)
+    assert not np.array_equal(refs[1]["label_valid"], refs5[1]["label_valid"])       # the two elements leave other labels
+    fl = G.fields(cs)
+    cap, _ = _capacity(cs, refs)
+    off = np.concatenate([[0], np.cumsum(cs["sizes"])]).astype(np.int64)
+    pts = _dev(np.concatenate(cs["frames"]).reshape(-1, 4))
+    valid_idx, labels = np.zeros(int(off[-1]), np.int64), np.zeros(int(off[-1]), np.uint32)
+    for f, r in enumerate(refs):
+        valid_idx[off[f]:off[f] + r["n_valid"]], labels[off[f]:off[f] + r["n_valid"]] = r["valid_idx"], r["label_valid"]
+    keep, held = [], []
+
+    def run(case, rf, masks):
+        if masks:
+            _set_masks(ctx, case, rf, case["source"], keep)
+        o = _outputs(case, case["sizes"], sum(len(c) for c in case["cam0"]), fl, cap)
+        torch.cuda.synchronize()
+        ctx.run_device(pts, off, **o)
+        held.append((o, rf))
+
+    with LpfContext(0) as ctx:
+        ctx.set_pipelined(mode)
+        ctx.set_camera(cs["T"], cs["K"], cs["W"], cs["H"], cs["dmin"], cs["dmax"])
+        _set_masks(ctx, cs, refs, cs["source"], keep)
+        vis = _set_boxes(ctx, cs, refs, keep, device=True)
+        run(cs, refs, False)
+        run(cs, refs, True)
+        ctx.box_points(cs["frames"], valid_idx, np.array([r["n_valid"] for r in refs], np.int64), labels)
+        run(cs, refs, True)
+        run(cs5, refs5, True)
+        ctx.sync()
+    for k, (o, rf) in enumerate(held):
+        got = _read(cs, o, cs["sizes"], [len(c) for c in cs["cam0"]], vis if k == 0 else None)
+        G.check(cs, got, rf, route="%s, run %d" % (mode, k), inst_cap=cap if "inst_idx" in o else None)
+
+
 @pytest.mark.parametrize("mode", ["off", "fused", "fused-pack"])
 @pytest.mark.parametrize("seed", STEP_SEEDS)
 def test_fuzz_frame_step(seed, mode):
