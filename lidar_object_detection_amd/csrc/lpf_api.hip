@@ -103,8 +103,6 @@ struct lpf_ctx {
     uint32_t erode_spans = 0x01u;
 
     // masks -> label images
-    int mask_F = 0, mask_M = 0;       // 0 frames = no masks set
-    int mask_set = 0;                 // the scratch set whose label image holds them
     DevBuf mask_stage;
     // Masks that are set but not packed (no erosion; the next lpf_run* decides, plan_tile_source).  Left by lpf_set_masks_* of a serial
     // context -- host masks in mask_stage, or device masks the caller lends (on_device 2): a launch of sparse frames reads them directly,
@@ -118,8 +116,26 @@ struct lpf_ctx {
         bool f32 = false, can_ride = false;
         int rule = 0, F = 0, M = 0;
         const int4 *rects = nullptr;
-        void *label = nullptr;        // the label image they are packed into (scratch set mask_set's label_a)
-    } unpacked;
+        void *label = nullptr;        // the label image they are packed into (label_a of the masks' scratch set)
+    };
+    // The masks in force: one record, written through the four transitions below only.  The label image and its element size belong
+    // to scratch set `set`: a call that sets masks names its set first (begin), and every later writer works on that set's buffers.
+    struct Masks {
+        int F = 0, M = 0;             // 0 frames = no masks set
+        int set = 0;                  // the scratch set whose label_a / label_b hold the label image
+        void *img = nullptr;          // the label image: that set's label_a or (after an erosion) label_b
+        int bytes = 4;                // its element size: 1 (M <= 8), 2 (M <= 16) or 4
+        Unpacked unpacked;
+        void forget_unpacked() { unpacked = Unpacked(); }
+        void drop() { F = 0; M = 0; forget_unpacked(); }                // none in force (img stays: nothing reads it while F is 0)
+        // a call that sets masks begins: none in force, what it sets goes to set s.  Lent masks that a pipelined lpf_set_masks_* left
+        // unpacked stay on record (the callers say why)
+        void begin(int s) { F = 0; M = 0; img = nullptr; set = s; if (!unpacked.pipelined) forget_unpacked(); }
+        void packed(int F_, int M_, void *image, int b) { F = F_; M = M_; img = image; bytes = b; }     // in force, packed into `image`
+        // the masks the caller has just recorded in `unpacked` are in force: the next run decides; a pack writes elements of b bytes
+        // (image: on record meanwhile, or NULL)
+        void left_unpacked(void *image, int b) { F = unpacked.F; M = unpacked.M; img = image; bytes = b; }
+    } masks;
 
     // Boxes.  A ring of box sets: in the software-pipelined modes the tail that counts into the boxes of run i executes one
     // or two launches after run i was queued, so a lpf_set_boxes* for the NEXT run must not touch the tables run i's tail is
@@ -154,9 +170,7 @@ struct lpf_ctx {
     // order, without waiting -- instead of draining the pipeline to rewrite shared ones.  A launch of ONE frame needs no table.
     struct Scratch {
         DevBuf vbal, mbal, seg_tab, grp_tab, frm_tab, seg_pre, cnt, mlist;
-        DevBuf label_a, label_b;      // label images [F][H][W] uint32 (b = erosion ping-pong)
-        void *label_cur = nullptr;
-        int label_bytes = 4;          // element size of the label image: 1 (M <= 8), 2 (M <= 16) or 4
+        DevBuf label_a, label_b;      // label images [F][H][W] uint32 (b = erosion ping-pong); which one is current: lpf_ctx::Masks
         DevBuf rgrid;                 // candidate grid of the masks' rectangles (LpfDirectRect tiles), [F][cells] uint32
         DevBuf rects;                 // lpf_set_mask_rects from host memory: the copy this set's run reads (its tiles may run a launch later)
         DevBuf out_stage;             // what a pipelined run needs though its caller left it out (narrow_bind): written by this run's tiles,
@@ -166,24 +180,36 @@ struct lpf_ctx {
         int tab_csplit = 0;                       // ... and its count blocks per (group, word): the key of the tables (narrow_tables)
         size_t o_segs = 0, o_blks = 0, o_cblks = 0;
     } sc[LPF_NSETS];
-    int parity = 0;
     long long run_seq = 0;            // runs queued so far
-    // Software-pipelined modes (lpf_set_pipelined 2 / 4): what earlier runs still owe.  The tail of the last run and the
-    // summaries of the one before ride in the next run's launch (lpf_step_t) -- in mode 4 the last run's streaming kernel
-    // too (pend_k1) -- or are launched by flush_pending().
-    struct Pending {
+    struct Pending {                  // a run, as the step launches that carry its roles take it
         bool valid = false;
         LpfParams P;
         bool pre = false;                 // its prefixes come from the scan kernel
         int ntail = 0;                    // tail blocks
-        int nk1 = 0;                      // (pend_k1) K1 tiles
-        bool small = false;
+        int nk1 = 0;                      // K1 tiles
         TileSource src;                   // where its tiles get their label bits
-    } pend_k1, pend_tail, pend_fin;
-    bool fused = false;               // pipelined: one launch per run (modes 2 / 4)
-    // Mode 4: the mask pack rides as well -- the launch of run i carries the pack of run i's masks, the K1 tiles of run i-1
-    // (pend_k1), the tail of run i-2 and the summaries of run i-3; four scratch sets.
-    bool defer = false;
+    };
+    // Software-pipelined modes (lpf_set_pipelined 2 / 4): the mode, the scratch set of the next fused run and what earlier runs still
+    // owe.  The tail of the last run and the summaries of the one before ride in the next run's launch (lpf_step_t) -- in mode 4 the
+    // last run's streaming kernel too (k1) -- or are launched by flush_pending(); queue_step alone moves a run from role to role.
+    struct Pipeline {
+        bool fused = false;           // pipelined: one launch per run (modes 2 / 4)
+        // Mode 4: the mask pack rides as well -- the launch of run i carries the pack of run i's masks, the K1 tiles of run i-1
+        // (k1), the tail of run i-2 and the summaries of run i-3; four scratch sets.
+        bool defer = false;
+        int parity = 0;               // the scratch set of the next fused run
+        Pending k1, tail, fin;
+        bool owes() const { return k1.valid || tail.valid || fin.valid; }
+        int sets() const { return defer ? 4 : 3; }        // scratch sets in rotation
+        int depth() const { return defer ? 2 : 1; }       // launches from the one that queues a run to the one with its tail
+        // The scratch set that masks and rectangles set NOW go to: the next fused run's, in order set 0.  (A graph capture has no say:
+        // lpf_graph_begin refuses a pipelined context, and lpf_set_pipelined goes through sync_all, which refuses inside a capture.)
+        int set_now() const { return fused ? parity : 0; }
+        int run_set(bool run_fused) const { return run_fused ? parity : 0; }      // a run's set: fused or not is that run's own decision
+        // a fused run whose mask pack rides (src) may not share its launch with the tiles that wait in k1 (why: lpf_run_batch)
+        bool must_drain_before(const TileSource &src) const { return defer && k1.valid && src.ride_pack && (k1.src.reads_masks() || k1.src.label_bytes != src.label_bytes); }
+        bool next_carries_tiles() const { return !defer || (k1.valid && k1.nk1 > 0); }    // the launch that queues the next fused run has tiles
+    } pipe;
     // lpf_get_stats: [0] host waits, [1] drains (owed work launched outside a run), [2] uploads through the pinned ring, [3] step
     // launches, [4] box jobs launched as a kernel of their own, [5] box jobs that rode in a step launch, [6] blocking uploads,
     // [7] lpf_run_frame_wide jobs whose masks were read directly (lpf_wide_direct_project)
@@ -361,7 +387,7 @@ int launch_box_job(lpf_ctx *c, lpf_ctx::BoxSet &B)
 
 // One launch of lpf_step_t: the streaming tiles of run K, the tail blocks of run Q dealt out among them, the summaries of
 // run R, the box job X of the run being queued (a block per frame, in front) and -- mode 4 -- the pack of that run's masks, waiting
-// in c->unpacked, behind the tiles (cur: the source of the run being queued, NULL in a drain; its pack rides if it says so, with label
+// in c->masks.unpacked, behind the tiles (cur: the source of the run being queued, NULL in a drain; its pack rides if it says so, with label
 // elements of its size -- K's when K is there: the host keeps the two equal).  Any of the roles may be absent.  `after` is recorded
 // behind the launch.
 int launch_step(lpf_ctx *c, const lpf_ctx::Pending &KK, const lpf_ctx::Pending &Q, const lpf_ctx::Pending &R, const TileSource *cur,
@@ -406,7 +432,7 @@ int launch_step(lpf_ctx *c, const lpf_ctx::Pending &KK, const lpf_ctx::Pending &
     Y.nk1 = KK.valid ? KK.nk1 : 0;
     Y.npack = 0;
     if (ride) {
-        const lpf_ctx::Unpacked &U = c->unpacked;
+        const lpf_ctx::Unpacked &U = c->masks.unpacked;
         J.masks = (const uint8_t *)U.masks; J.label = U.label; J.M = U.M; J.hw = (long long)c->H * c->W;
         J.rects = U.rects; J.W = c->W;
         J.total16 = (long long)U.F * (J.hw / 16);
@@ -445,22 +471,37 @@ int launch_step(lpf_ctx *c, const lpf_ctx::Pending &KK, const lpf_ctx::Pending &
     return LPF_OK;
 }
 
-bool anything_owed(const lpf_ctx *c) { return c->pend_k1.valid || c->pend_tail.valid || c->pend_fin.valid; }
+// a run as launch_step takes it (the fields: lpf_ctx::Pending)
+lpf_ctx::Pending pending_run(const LpfParams &P, bool pre, int ntail, int nk1, const TileSource &src)
+{
+    return lpf_ctx::Pending{true, P, pre, ntail, nk1, src};
+}
 
-// software-pipelined modes: launch what earlier runs still owe -- the same step launches, with fewer roles each time; a box job
-// that was waiting for its run goes with the first of them (or alone)
+// The pipeline's one rotation: a step launch with the tiles of run K, the tail of run Q and the summaries of run R, after which each
+// of them has moved on by one role.  cur: the run being queued -- its tiles go into this launch (mode 2) or wait for the next (mode 4),
+// its mask pack rides if cur->src says so -- or NULL in a drain: the same launches, with fewer roles each time.
+int queue_step(lpf_ctx *c, const lpf_ctx::Pending *cur, lpf_ctx::BoxSet *XB, hipEvent_t after, const LpfRectJob *RG)
+{
+    lpf_ctx::Pipeline &PL = c->pipe;
+    const bool wait = cur && PL.defer;
+    const lpf_ctx::Pending K = (cur && !wait) ? *cur : PL.k1, Q = PL.tail, R = PL.fin;
+    int rc_ = launch_step(c, K, Q, R, cur ? &cur->src : nullptr, XB, after, RG);
+    if (rc_) return rc_;
+    PL.fin = Q;                            // its tail has just been launched: summaries in the next launch
+    PL.tail = K;
+    if (wait) PL.k1 = *cur; else PL.k1.valid = false;
+    return LPF_OK;
+}
+
+// software-pipelined modes: launch what earlier runs still owe; a box job that was waiting for its run goes with the first of those
+// launches (or alone)
 int flush_pending(lpf_ctx *c)
 {
     lpf_ctx::BoxSet *XB = &c->bx[c->box_cur];
-    if (anything_owed(c)) ++c->stats[1];
-    while (anything_owed(c)) {
-        const lpf_ctx::Pending K = c->pend_k1, Q = c->pend_tail, R = c->pend_fin;
-        int rc_ = launch_step(c, K, Q, R, nullptr, XB, nullptr);
-        if (rc_) return rc_;
-        c->pend_fin = Q;                   // its tail has just been launched: summaries next
-        c->pend_tail = K;
-        c->pend_k1.valid = false;
-    }
+    int rc_;
+    if (c->pipe.owes()) ++c->stats[1];
+    while (c->pipe.owes())
+        if ((rc_ = queue_step(c, nullptr, XB, nullptr, nullptr))) return rc_;
     return launch_box_job(c, *XB);
 }
 
@@ -835,7 +876,7 @@ int box_layout(lpf_ctx *c, const int32_t *box_off, int F, int oriented, const ch
     if (!c->have_camera) return fail(c, LPF_ERR_STATE, "%s: lpf_set_camera must be called first (cam-0 boxes are filtered with its K, W, H)", who);
     int rc;
     lpf_ctx::BoxSet *B = &c->bx[c->box_cur];
-    if (c->fused && !c->capturing) {
+    if (c->pipe.fused) {                                   // (never inside a graph capture: see lpf_ctx::Pipeline::set_now)
         if (B->used) {
             B->job_valid = false;                          // (cannot be: a run launches the job of the set it uses)
             c->box_cur = (c->box_cur + 1) % LPF_NSETS;
@@ -843,8 +884,7 @@ int box_layout(lpf_ctx *c, const int32_t *box_off, int F, int oriented, const ch
         }
         // the tail of the last run that used this set's old tables must have been LAUNCHED before they are rewritten (in stream
         // order); with one set per run and four sets it always has -- else launch what is owed first (still no host wait)
-        const int depth = c->defer ? 2 : 1;
-        if (B->last_ref >= 0 && B->last_ref + depth >= c->run_seq && (rc = flush_pending(c))) return rc;
+        if (B->last_ref >= 0 && B->last_ref + c->pipe.depth() >= c->run_seq && (rc = flush_pending(c))) return rc;
     }
     if ((rc = box_shape(c, *B, box_off, F, oriented))) return rc;
     *out = B;
@@ -959,8 +999,6 @@ int set_boxes_impl(lpf_ctx *c, const double *corners, int on_device, const int32
     return LPF_OK;
 }
 
-void forget_unpacked(lpf_ctx *c) { c->unpacked = lpf_ctx::Unpacked(); }
-
 // masks [F][M][H][W] (uint8 under rule 0, or float under rule 1..3) -> label image with elements of `label_bytes`, on stream ms, into la
 // (lb_ = erosion ping-pong): the context's camera size for the narrow calls (a scratch set's label_a / label_b), camera c's for
 // lpf_run_cams
@@ -1031,20 +1069,17 @@ int set_masks_impl(lpf_ctx *c, const T *masks, int F, int M, int mode, int erode
         return fail(c, LPF_ERR_ARG, "set_masks: F=%d M=%d erode_iters=%d masks=%p", F, M, erode_iters, (const void *)masks);
     // software-pipelined modes + device masks: the label images rotate with the scratch sets (the tiles of the previous run may
     // still have to read theirs); anything else uses set 0, with nothing owed
-    const bool per_set = c->fused && on_device && !c->capturing;
+    const bool per_set = c->pipe.fused && on_device;
     int rc;
-    if (!per_set && anything_owed(c) && (rc = sync_all(c))) return rc;    // owed tiles read set 0's label image / the staging copy
+    if (!per_set && c->pipe.owes() && (rc = sync_all(c))) return rc;      // owed tiles read set 0's label image / the staging copy
     // (host masks in a pipelined mode: the pipeline has just been drained -- the staging copy is one -- and their label image goes to
     //  the set of the next run too, where a fused run looks for it, as lpf_set_label_image's does: in set 0 every run but the first after
     //  a mode switch was refused with "the masks were set for another scratch set")
-    const int set = (c->fused && !c->capturing) ? c->parity : 0;
-    lpf_ctx::Scratch &S = c->sc[set];
-    hipStream_t ms = c->stream;
-    c->mask_F = 0; c->mask_M = 0; S.label_cur = nullptr;
+    lpf_ctx::Masks &MK = c->masks;
+    lpf_ctx::Scratch &S = c->sc[c->pipe.set_now()];
     // (masks a pipelined lpf_set_masks_* left unpacked stay on record until this call has its buffers -- so also when it is for no
     //  frames: the next run packs them.  Kept as it was)
-    if (!c->unpacked.pipelined) forget_unpacked(c);
-    c->mask_set = set;
+    MK.begin(c->pipe.set_now());
     if (F == 0) return LPF_OK;
     const size_t hw = (size_t)c->H * c->W;
     if ((rc = reserve(c, S.label_a, (size_t)F * hw * 4))) return rc;
@@ -1060,42 +1095,39 @@ int set_masks_impl(lpf_ctx *c, const T *masks, int F, int M, int mode, int erode
     const int4 *rects = (((sizeof(T) == 1 && mode == 0) || (sizeof(T) == 4 && mode == 1)) && erode_iters == 0 && c->rects_F == F && c->rects_M == M &&
                          c->W >= 16) ? c->rects_pending : nullptr;         // (W >= 16: a group of 16 pixels of the pack spans at most two rows)
     c->rects_pending = nullptr;
-    forget_unpacked(c);
-    const bool lent_pipelined = c->fused && per_set && on_device == 2, kept_serial = !c->fused && on_device != 1;
+    MK.forget_unpacked();
+    const bool lent_pipelined = per_set && on_device == 2, kept_serial = !c->pipe.fused && on_device != 1;
     if (M > 0 && erode_iters == 0 && (lent_pipelined || kept_serial)) {
         // nothing to erode, and the masks stay where they are (lent by the caller, or -- serial mode -- our staging buffer): packing
         // is left to the next lpf_run* (see lpf_ctx::Unpacked) -- a launch of sparse frames does without it
-        lpf_ctx::Unpacked &U = c->unpacked;
+        lpf_ctx::Unpacked &U = MK.unpacked;                // (forgotten above: every field is at its default)
         U.valid = true; U.pipelined = lent_pipelined; U.masks = d_masks; U.f32 = sizeof(T) == 4; U.rule = mode; U.F = F; U.M = M;
         U.rects = rects; U.label = S.label_a.p;
-        U.can_ride = lent_pipelined && c->defer && sizeof(T) == 1 && hw % 16 == 0 && ((uintptr_t)d_masks & 15) == 0;
-        S.label_bytes = lb;
-        if (lent_pipelined) S.label_cur = S.label_a.p;
-        else if (!on_device) LPF_HIP(c, host_wait(c));
-        c->mask_F = F; c->mask_M = M;
+        U.can_ride = lent_pipelined && c->pipe.defer && sizeof(T) == 1 && hw % 16 == 0 && ((uintptr_t)d_masks & 15) == 0;
+        if (!on_device) LPF_HIP(c, host_wait(c));         // the host buffer may be reused by the caller
+        MK.left_unpacked(lent_pipelined ? S.label_a.p : nullptr, lb);
         return LPF_OK;
     }
     void *cur = nullptr;
-    if ((rc = pack_masks(c, S.label_a, S.label_b, c->W, c->H, ms, d_masks, sizeof(T) == 4, mode, lb, F, M, erode_iters, &cur, rects))) return rc;
-    S.label_bytes = lb;
+    if ((rc = pack_masks(c, S.label_a, S.label_b, c->W, c->H, c->stream, d_masks, sizeof(T) == 4, mode, lb, F, M, erode_iters, &cur, rects))) return rc;
     if (!on_device) LPF_HIP(c, host_wait(c));   // the host buffer may be reused by the caller
-    S.label_cur = cur;
-    c->mask_F = F; c->mask_M = M;
+    MK.packed(F, M, cur, lb);
     return LPF_OK;
 }
 
 // masks that are set but not packed (lpf_ctx::Unpacked) -> packed now, by a launch of their own, into the label image of their scratch
-// set (mask_set: set 0 in serial mode)
+// set (set 0 in serial mode).  The frames and masks in force stay as they are: after lpf_set_label_image they are that image's
 int pack_unpacked(lpf_ctx *c)
 {
-    const lpf_ctx::Unpacked &U = c->unpacked;
+    lpf_ctx::Masks &MK = c->masks;
+    const lpf_ctx::Unpacked &U = MK.unpacked;
     if (!U.valid) return LPF_OK;
-    lpf_ctx::Scratch &S = c->sc[c->mask_set];
+    lpf_ctx::Scratch &S = c->sc[MK.set];
     void *cur = nullptr;
-    int rc = pack_masks(c, S.label_a, S.label_b, c->W, c->H, c->stream, U.masks, U.f32, U.rule, S.label_bytes, U.F, U.M, 0, &cur, U.rects);
+    int rc = pack_masks(c, S.label_a, S.label_b, c->W, c->H, c->stream, U.masks, U.f32, U.rule, MK.bytes, U.F, U.M, 0, &cur, U.rects);
     if (rc) return rc;
-    S.label_cur = cur;
-    forget_unpacked(c);
+    MK.packed(MK.F, MK.M, cur, MK.bytes);
+    MK.forget_unpacked();
     return LPF_OK;
 }
 
@@ -1123,7 +1155,8 @@ int plan_tile_source(lpf_ctx *c, bool fused, bool small, bool sparse_frames, int
 {
     src = TileSource();
     int rc;
-    const lpf_ctx::Unpacked &U = c->unpacked;
+    const lpf_ctx::Masks &MK = c->masks;
+    const lpf_ctx::Unpacked &U = MK.unpacked;
     const bool readable = U.valid && U.pipelined == fused && M > 0 && sparse_frames;
     if (readable && !small && U.rects && ((!U.f32 && U.rule == 0) || (U.f32 && U.rule == 1))) src.kind = TileSource::DIRECT_RECT;
     else if (readable && small) src.kind = TileSource::DIRECT;
@@ -1134,17 +1167,16 @@ int plan_tile_source(lpf_ctx *c, bool fused, bool small, bool sparse_frames, int
     }
     // The label image lives in the scratch set that was current when the masks were set.  A pipelined run must find it in its
     // own set (the sets rotate: masks are set before every run); any other run has nothing owed and reads it where it is.
-    const lpf_ctx::Scratch &SM = c->sc[c->mask_set];
-    if (M > 0 && fused && c->mask_set != c->parity)
+    if (M > 0 && fused && MK.set != c->pipe.run_set(fused))
         return fail(c, LPF_ERR_STATE, "the masks were set for another scratch set: in the pipelined modes the label images rotate with the scratch sets -- call lpf_set_masks_* before every lpf_run* (and after switching modes)");
     if (src.reads_masks()) {
         src.f32 = U.f32; src.rule = U.rule; src.img = U.masks;
         src.rects = U.rects;                               // (the rectangles also gate the tiles that read all M mask bytes: small sparse launches)
     } else if (M > 0) {
-        src.img = SM.label_cur;
+        src.img = MK.img;
     }
     if (M > 0 && !src.img) return fail(c, LPF_ERR_STATE, "no masks for this run's scratch set: in the pipelined modes the label images rotate with the scratch sets -- call lpf_set_masks_* before every lpf_run* (and after switching modes)");
-    src.label_bytes = (M > 0) ? SM.label_bytes : 4;
+    src.label_bytes = (M > 0) ? MK.bytes : 4;
     return LPF_OK;
 }
 
@@ -1704,7 +1736,7 @@ int lpf_set_mask_rects(lpf_ctx *c, const int32_t *rects, int on_device, int F, i
         if (c->capturing) return LPF_OK;                    // (a copy from host memory is not captured: the hint is dropped)
         // the copy lives in the scratch set of the run these masks are for: in the pipelined modes that run's tiles may read the
         // rectangles a launch after the NEXT run's have been uploaded (into the next set); stream-ordered behind the set's last run
-        DevBuf &rb = c->sc[c->fused ? c->parity : 0].rects;
+        DevBuf &rb = c->sc[c->pipe.set_now()].rects;
         int rc = reserve(c, rb, bytes);
         if (rc) return rc;
         if ((rc = upload(c, rb.p, rects, bytes))) return rc;
@@ -1745,10 +1777,10 @@ int lpf_set_pipelined(lpf_ctx *c, int on)
     int rc = sync_all(c);
     if (rc) return rc;
     if ((rc = pack_unpacked(c))) return rc;                // masks that were waiting for a run: packed now, where the next run looks
-    c->fused = on != 0;
-    c->defer = on == 4;
-    c->parity = 0;
-    if (c->mask_F && c->mask_set != 0) { c->mask_F = 0; c->mask_M = 0; }     // label images rotate with the sets: set the masks again
+    c->pipe.fused = on != 0;
+    c->pipe.defer = on == 4;
+    c->pipe.parity = 0;
+    if (c->masks.F && c->masks.set != 0) c->masks.drop();  // label images rotate with the sets: set the masks again
     ++c->generation;
     return LPF_OK;
 }
@@ -1759,13 +1791,13 @@ int lpf_set_camera(lpf_ctx *c, const double T[16], const double K[9], int W, int
     if (!T || !K || W <= 0 || H <= 0 || (long long)W * H > (1ll << 30))
         return fail(c, LPF_ERR_ARG, "set_camera: T=%p K=%p W=%d H=%d", (const void *)T, (const void *)K, W, H);
     // pipelined modes: a run still owed projects / counts boxes with the OLD camera (its box job)
-    if (!c->capturing && (anything_owed(c) || c->bx[c->box_cur].job_valid)) {
+    if (!c->capturing && (c->pipe.owes() || c->bx[c->box_cur].job_valid)) {
         if (use_device(c)) return LPF_ERR_HIP;
         int rc_ = sync_all(c);
         if (rc_) return rc_;
     }
     if (W != c->W || H != c->H) {            // label images (and the visibility filter of cam-0 boxes) are per W x H: set masks / boxes again
-        c->mask_F = 0; c->mask_M = 0; forget_unpacked(c);
+        c->masks.drop();
         for (auto &B : c->bx) { B.F = 0; B.box_off.clear(); B.job_valid = false; }
     }
     memcpy(c->T, T, sizeof c->T);          // row 3 of the 4x4 is never used by the reference either (V3:567 [:, :3])
@@ -1796,19 +1828,15 @@ int lpf_set_label_image(lpf_ctx *c, const uint32_t *label, int F, int M, int on_
     if (F < 0 || M < 0 || M > LPF_MAX_MASKS || (F > 0 && !label)) return fail(c, LPF_ERR_ARG, "set_label_image: F=%d M=%d", F, M);
     int rc;
     if ((rc = sync_all(c))) return rc;
-    lpf_ctx::Scratch &S = c->sc[c->fused ? c->parity : 0];
-    c->mask_F = 0; c->mask_M = 0; S.label_cur = nullptr;
+    lpf_ctx::Scratch &S = c->sc[c->pipe.set_now()];
     // (masks a pipelined lpf_set_masks_* left unpacked stay on record, and the next fused run takes them, not this image.  Kept as it was)
-    if (!c->unpacked.pipelined) forget_unpacked(c);
-    c->mask_set = c->fused ? c->parity : 0;
+    c->masks.begin(c->pipe.set_now());
     if (F == 0) return LPF_OK;
     const size_t bytes = (size_t)F * c->H * c->W * 4;
     if ((rc = reserve(c, S.label_a, bytes))) return rc;
     LPF_HIP(c, hipMemcpyAsync(S.label_a.p, label, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     LPF_HIP(c, host_wait(c));
-    S.label_cur = S.label_a.p;
-    S.label_bytes = 4;
-    c->mask_F = F; c->mask_M = M;
+    c->masks.packed(F, M, S.label_a.p, 4);
     return LPF_OK;
 }
 
@@ -1818,21 +1846,21 @@ int lpf_get_label_image(lpf_ctx *c, uint32_t *out, int on_device)
     if (use_device(c)) return LPF_ERR_HIP;
     { int rc_ = sync_all(c); if (rc_) return rc_; }
     { int rc_ = pack_unpacked(c); if (rc_) return rc_; }
-    lpf_ctx::Scratch &S = c->sc[c->mask_set];
-    if (!S.label_cur || !c->mask_F) return fail(c, LPF_ERR_STATE, "no masks set");
-    const size_t npix = (size_t)c->mask_F * c->H * c->W;
-    if (S.label_bytes == 4) {
-        LPF_HIP(c, hipMemcpyAsync(out, S.label_cur, npix * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    const lpf_ctx::Masks &MK = c->masks;
+    if (!MK.img || !MK.F) return fail(c, LPF_ERR_STATE, "no masks set");
+    const size_t npix = (size_t)MK.F * c->H * c->W;
+    if (MK.bytes == 4) {
+        LPF_HIP(c, hipMemcpyAsync(out, MK.img, npix * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
         LPF_HIP(c, host_wait(c));
         return LPF_OK;
     }
     // narrow label images (M <= 16) are widened on the host: this entry point exists for tests
-    std::vector<uint8_t> raw(npix * (size_t)S.label_bytes);
-    LPF_HIP(c, hipMemcpyAsync(raw.data(), S.label_cur, raw.size(), hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint8_t> raw(npix * (size_t)MK.bytes);
+    LPF_HIP(c, hipMemcpyAsync(raw.data(), MK.img, raw.size(), hipMemcpyDeviceToHost, c->stream));
     LPF_HIP(c, host_wait(c));
     std::vector<uint32_t> wide(npix);
     for (size_t i = 0; i < npix; ++i)
-        wide[i] = S.label_bytes == 1 ? (uint32_t)raw[i] : (uint32_t)reinterpret_cast<const uint16_t *>(raw.data())[i];
+        wide[i] = MK.bytes == 1 ? (uint32_t)raw[i] : (uint32_t)reinterpret_cast<const uint16_t *>(raw.data())[i];
     LPF_HIP(c, hipMemcpyAsync(out, wide.data(), npix * 4, on_device ? hipMemcpyHostToDevice : hipMemcpyHostToHost, c->stream));
     LPF_HIP(c, host_wait(c));
     return LPF_OK;
@@ -1865,12 +1893,12 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     if ((rc = check_frames(c, "run", pts, frame_off, F, LPF_SEG_QUANTUM))) return rc;
     const int64_t Ntot = frame_off[F];
     lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
-    if (c->mask_F != 0 && c->mask_F != F) return fail(c, LPF_ERR_STATE, "masks were set for %d frames, run has %d", c->mask_F, F);
+    if (c->masks.F != 0 && c->masks.F != F) return fail(c, LPF_ERR_STATE, "masks were set for %d frames, run has %d", c->masks.F, F);
     if (BX.F != 0 && BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, run has %d", BX.F, F);
     if (out->inst_idx && out->inst_cap <= 0) return fail(c, LPF_ERR_ARG, "run: inst_idx given with inst_cap=%lld", (long long)out->inst_cap);
     if ((out->uv_valid || out->label_valid) && !out->valid_idx)
         return fail(c, LPF_ERR_ARG, "run: uv_valid / label_valid need valid_idx as well (they share its order)");
-    const int M = c->mask_F ? c->mask_M : 0;
+    const int M = c->masks.F ? c->masks.M : 0;
     const int Btot = BX.F ? BX.box_off[F] : 0;
     const bool host_io = !out->on_device;
 
@@ -1880,15 +1908,15 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     narrow_layout(c, frame_off, F, BX, out->inst_cap, small, L);
     // software-pipelined device runs rotate through the scratch sets (3 in mode 2, 4 in mode 4); everything else uses set 0 with
     // nothing owed
-    const bool fused = c->fused && !host_io && pts_on_device && !c->capturing;   // one launch per run, the tail rides in the next
+    const bool fused = c->pipe.fused && !host_io && pts_on_device;   // one launch per run, the tail rides in the next
     // a frame or two of a real scan (up to 64 list blocks = 262 144 points): the launch is as long as its longest block, so the count
     // blocks are cut in four and the lists use the 16-row wave.  Beyond that both cost more than they save (same box, us per step in a
     // pipelined stream with / without: 20 real frames 29.8 / 25.5 with the cut, 25.2 / 25.5 with the list wave; one 2 M-point
     // synthetic cloud 25.7 / 21.3 and 22.9 / 21.3, in order 42.4 / 38.9 with the list wave).
     L.split(fused && L.few ? 4 : 1);
     if (c->geometry == 3) L.pre_scan = true;
-    if (!fused && anything_owed(c) && (rc = sync_all(c))) return rc;
-    lpf_ctx::Scratch &S = c->sc[fused ? c->parity : 0];
+    if (!fused && c->pipe.owes() && (rc = sync_all(c))) return rc;
+    lpf_ctx::Scratch &S = c->sc[c->pipe.run_set(fused)];
     if ((rc = narrow_reserve(c, S, L, M, Btot))) return rc;
     if ((rc = narrow_tables(c, S, L, false))) return rc;
     LpfParams P;
@@ -1952,17 +1980,16 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     const int ntail = (P.count_boxes ? L.ncblk : 0) + (want_lists ? L.nblk : 0);        // no lists wanted and no boxes: no tail blocks at all
     hipEvent_t e0 = nullptr, e1 = nullptr;
     // mode 4: the mask pack and the tiles of one launch share the label element type -- else the pipeline is drained first
-    if (fused && c->defer && c->pend_k1.valid && src.ride_pack && (c->pend_k1.src.reads_masks() || c->pend_k1.src.label_bytes != src.label_bytes) &&
-        (rc = flush_pending(c)))
-        return rc;
+    if (fused && c->pipe.must_drain_before(src) && (rc = flush_pending(c))) return rc;
     // the candidate grid of the masks' rectangles: where this run's tiles are in this run's own launch(es) -- in order, mode 2 -- a
     // small kernel ahead of them; in mode 4 it rides in the launch below (the tiles come a launch later)
-    if (rect_tiles && nk1 > 0 && !(fused && c->defer)) {
+    const bool tiles_wait = fused && c->pipe.defer;        // this run's tiles go into the NEXT launch
+    if (rect_tiles && nk1 > 0 && !tiles_wait) {
         hipLaunchKernelGGL(lpf_rect_grid_kernel, dim3((unsigned)(RG.F * RG.bpf)), dim3(LPF_BLOCK), 0, c->stream, RG);
         LPF_HIP(c, hipGetLastError());
     }
     // (profiling brackets the launches that carry streaming tiles: in mode 4 the first launch after a drain carries none)
-    const bool carries_k1 = (fused && c->defer) ? (c->pend_k1.valid && c->pend_k1.nk1 > 0) : (nk1 > 0 || fused);
+    const bool carries_k1 = fused ? c->pipe.next_carries_tiles() : nk1 > 0;
     if (carries_k1 && c->profiling && c->ev_used < (1u << 16)) {
         if (c->ev.size() < 2 * (c->ev_used + 1)) {
             hipEvent_t a, b;
@@ -1979,22 +2006,17 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
         //      run before that, and the box job of THIS run (its tables are read by this run's tail, one or two launches on).
         //      Mode 2: the tiles are this run's.  Mode 4: this run's MASK PACK rides as well (lent uint8 masks), the tiles are
         //      the previous run's -- everything one launch later, nothing left on the stream between two steps.
-        lpf_ctx::Pending cur;
-        cur.valid = true; cur.P = P; cur.pre = L.pre_scan; cur.ntail = ntail; cur.nk1 = nk1; cur.small = small; cur.src = src;
-        const lpf_ctx::Pending KK = c->defer ? c->pend_k1 : cur, Q = c->pend_tail, R = c->pend_fin;
-        if ((rc = launch_step(c, KK, Q, R, &src, &BX, e1, (rect_tiles && c->defer) ? &RG : nullptr))) return rc;
-        c->pend_fin = Q;                                   // its tail has just been launched: summaries in a later launch
-        c->pend_tail = KK;
-        if (c->defer) c->pend_k1 = cur;
-        forget_unpacked(c);
-        c->parity = (c->parity + 1) % (c->defer ? 4 : 3);
+        const lpf_ctx::Pending cur = pending_run(P, L.pre_scan, ntail, nk1, src);
+        if ((rc = queue_step(c, &cur, &BX, e1, (rect_tiles && tiles_wait) ? &RG : nullptr))) return rc;
+        c->masks.forget_unpacked();
+        c->pipe.parity = (c->pipe.parity + 1) % c->pipe.sets();
         return LPF_OK;
     }
     if (BX.job_valid && nk1 > 0 && BX.F > 0 && BX.box_off[BX.F] > 0) {
         // in order, with a box job waiting: the tiles and the job share one launch (lpf_step_t with those two roles), the tail
         // that reads the tables follows in the next -- the same number of launches as with boxes that never change
-        lpf_ctx::Pending cur, none;
-        cur.valid = true; cur.P = P; cur.pre = false; cur.ntail = 0; cur.nk1 = nk1; cur.small = small; cur.src = src;
+        const lpf_ctx::Pending cur = pending_run(P, false, 0, nk1, src);
+        lpf_ctx::Pending none;
         if ((rc = launch_step(c, cur, none, none, nullptr, &BX, e1))) return rc;
     } else {
     if ((rc = launch_box_job(c, BX))) return rc;           // (no tiles to ride with)
@@ -2110,7 +2132,7 @@ int lpf_resize_masks_u8(lpf_ctx *c, const uint8_t *src, int n, int h, int w, uin
     const size_t in_bytes = (size_t)n * h * w, out_bytes = (size_t)n * H * W;
     int rc;
     if (c->capturing) return fail(c, LPF_ERR_STATE, "resize_masks inside a graph capture");
-    if (anything_owed(c) && (rc = sync_all(c))) return rc;                // (the staging buffers below may be in use by owed runs)
+    if (c->pipe.owes() && (rc = sync_all(c))) return rc;                 // (the staging buffers below may be in use by owed runs)
     const uint8_t *dS = src;
     uint8_t *dD = dst;
     const bool linear = !area2 && !(h == H && w == W);
@@ -2160,7 +2182,7 @@ int lpf_erode_masks_u8(lpf_ctx *c, const uint8_t *src, int n, int h, int w, int 
     if (n == 0) return LPF_OK;
     if (c->capturing) return fail(c, LPF_ERR_STATE, "erode_masks inside a graph capture");
     int rc;
-    if (anything_owed(c) && (rc = sync_all(c))) return rc;                // (the staging buffer below may be in use by owed runs)
+    if (c->pipe.owes() && (rc = sync_all(c))) return rc;                 // (the staging buffer below may be in use by owed runs)
     const size_t bytes = (size_t)n * h * w;
     // device callers: dst and one scratch plane set ping-pong; host callers: three staging copies
     if ((rc = reserve(c, c->resize_buf, on_device ? bytes : 3 * bytes))) return rc;
@@ -2280,7 +2302,7 @@ int lpf_graph_begin(lpf_ctx *c)
 {
     if (!c) return LPF_ERR_ARG;
     if (use_device(c)) return LPF_ERR_HIP;
-    if (c->fused) return fail(c, LPF_ERR_STATE, "graph capture needs pipelining off");
+    if (c->pipe.fused) return fail(c, LPF_ERR_STATE, "graph capture needs pipelining off");
     if (c->capturing) return fail(c, LPF_ERR_STATE, "already capturing");
     int rc = sync_all(c);
     if (rc) return rc;
