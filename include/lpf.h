@@ -66,7 +66,8 @@ extern "C" {
                                       8 (continued): LPF_ASSIGN_MAX, lpf_assign_input, lpf_assign_outputs, lpf_assign_costs,
                                          lpf_assign2d_params, lpf_assign2d_outputs, lpf_assign_2d (added; nothing else changed)
                                       8 (continued): lpf_first_match_input, lpf_first_match_outputs, lpf_first_match (added; nothing else
-                                         changed) */
+                                         changed)
+                                      8 (continued): lpf_rle_masks, lpf_set_masks_rle (added; nothing else changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -257,6 +258,42 @@ int lpf_set_mask_rects(lpf_ctx *ctx, const int32_t *rects, int on_device, int F,
 int lpf_set_erosion_element(lpf_ctx *ctx, int ksize);
 int lpf_set_masks_f32(lpf_ctx *ctx, const float *masks, int F, int M, int binarize,
                       int erode_iters, int on_device);
+/* Masks of F frames in RUN-LENGTH form, from host memory, decoded on the GPU: the form instance masks are stored and exchanged in
+ * (saved predictions, annotation files, a detector in another process).  A frame's masks are then a few tens of KB on their way to the
+ * device where the dense form is M * H * W bytes (2.6 MB of uint8 for five masks at 1408 x 376), and the copy is what a call with host
+ * masks spends its time on.
+ *   Runs: mask m of frame f owns runs[run_off[f*M+m] .. run_off[f*M+m+1]); a run {start, length} is the pixels start .. start+length-1
+ * of the mask image flattened row-major, pixel (x, y) = y * W + x with W, H of lpf_set_camera.  A pixel is a member of mask m iff it lies
+ * in ANY run of m: the runs of a mask may come in any order and may touch or overlap; length = 0 is an empty run; a run may continue
+ * across row ends.
+ *   Both arrays are host memory and are checked IN FULL before anything is enqueued (there is no device-memory form, so the decode
+ * never reads a list that was not checked): run_off[0] = 0, run_off non-decreasing, start >= 0, length >= 0, start + length <= W * H
+ * (in 64 bits).  A violation is LPF_ERR_ARG, the message names frame, mask and run, and the context is left as it was.  They are copied
+ * before the call returns -- the caller may free them at once; the call may wait for that copy, as lpf_set_masks_u8 does for host masks,
+ * and waits for nothing else.
+ *   Afterwards the context is in the state lpf_set_masks_u8 leaves for the equivalent dense masks (dense[f][m][p] = 1 iff member) with
+ * the same erode_iters and on_device = 0, once those are packed: lpf_get_label_image is bit-for-bit equal, the label elements have the
+ * same width (1 / 2 / 4 bytes for M <= 8 / 16 / 32), F and M are in force, a pending lpf_set_mask_rects hint is consumed (and ignored),
+ * any record of unpacked masks is forgotten, and every later lpf_run / lpf_run_batch / lpf_run_frame (masks == NULL) gives the same
+ * outputs.  The label image is zeroed and the runs are OR-ed into it (integer ORs only: the image does not depend on the order the
+ * hardware takes them in); erode_iters iterations of the context's element (lpf_set_erosion_element) then run on the packed image.
+ * M = 0, or no run at all, zeroes the image and launches no decode; F = 0 does what lpf_set_masks_u8 does with F = 0.  In the
+ * software-pipelined modes (2 / 4) the call behaves as lpf_set_masks_u8 with host masks: what the pipeline owes is drained first, and
+ * the label image goes to the set the next run reads.
+ *   LPF_ERR_STATE before lpf_set_camera, and between lpf_graph_begin and lpf_graph_end (the run counts size the launch).  LPF_ERR_ARG:
+ * in NULL, F < 0, M < 0, erode_iters < 0, reserved != 0, M > LPF_MAX_MASKS (lpf_set_masks_u8's message), run_off NULL with F * M > 0,
+ * runs NULL with runs to read, F * M or the number of runs above 2^31 - 1, or runs that together cover more than 2^24 chunks of 1024 pixels.
+ *   Not taken in this form: the wide calls (lpf_run_wide, lpf_run_frame_wide, lpf_run_cams*, lpf_depth_maps, lpf_first_match) and
+ * lpf_inside_masks' own mask input keep their dense masks; runs are not resized (masks of another size than the camera's: decode them on
+ * the host, lpf_resize_masks_u8); runs in device memory.  Masks that already sit on the GPU gain nothing from this form. */
+typedef struct lpf_rle_masks {
+    const int32_t *runs;     /* host, [Rtot][2] {start, length}, Rtot = run_off[F*M] */
+    const int64_t *run_off;  /* host, [F*M + 1] */
+    int32_t F, M;            /* 0 <= M <= LPF_MAX_MASKS */
+    int32_t erode_iters;     /* >= 0, with the context's element (lpf_set_erosion_element) */
+    int32_t reserved;        /* 0 */
+} lpf_rle_masks;
+int lpf_set_masks_rle(lpf_ctx *ctx, const lpf_rle_masks *in);
 /* Pre-packed label images [F][H][W] (bit m = mask m). */
 int lpf_set_label_image(lpf_ctx *ctx, const uint32_t *label, int F, int M, int on_device);
 /* Read back the label images currently held ([F][H][W]); for tests of the pack/erode kernels. */

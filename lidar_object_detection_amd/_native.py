@@ -55,6 +55,12 @@ class WideInput(ctypes.Structure):
                 ("erode_iters", ctypes.c_int32), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class RleMasksInput(ctypes.Structure):
+    """lpf_rle_masks (include/lpf.h): the run-length masks of an lpf_set_masks_rle call"""
+    _fields_ = [("runs", _P), ("run_off", _P), ("F", ctypes.c_int32), ("M", ctypes.c_int32), ("erode_iters", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class WideOutputs(ctypes.Structure):
     """lpf_wide_outputs (include/lpf.h)"""
     _fields_ = [("uv", _P), ("depth", _P), ("u_f", _P), ("v_f", _P), ("valid_idx", _P), ("uv_valid", _P), ("label_words", _P),
@@ -315,6 +321,7 @@ def load(path=None):
     lib.lpf_set_camera.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double]
     lib.lpf_set_masks_u8.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.lpf_set_mask_rects.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.lpf_set_masks_rle.argtypes = [_P, ctypes.POINTER(RleMasksInput)]
     lib.lpf_set_erosion_element.argtypes = [_P, ctypes.c_int]
     lib.lpf_resize_masks_u8.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
     lib.lpf_erode_masks_u8.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
@@ -376,7 +383,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
             "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d",
             "lpf_inside_masks", "lpf_set_erosion_element", "lpf_box_points", "lpf_box_views", "lpf_assign_costs", "lpf_assign_2d",
-            "lpf_first_match")
+            "lpf_first_match", "lpf_set_masks_rle")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -874,6 +881,48 @@ class LpfContext:
             self._lent.append(keep)
         del keep
         self._check(rc)
+        self.F_masks, self.M = F, M
+
+    @staticmethod
+    def rle_batch(frames_masks, H, W):
+        """``(runs int32 [Rtot,2], run_off int64 [F*M + 1], F, M)`` of one RleMasks or a list of them, one per frame, as lpf_set_masks_rle
+        takes them: frames with fewer masks than the largest are padded with empty masks.  ValueError -- before any native call -- for
+        anything that is not an RleMasks, a size other than H x W, more than LPF_MAX_MASKS masks, and runs of another dtype or shape or
+        out of bounds (they are checked again here: the fields of an RleMasks can be assigned)."""
+        from .rle import RleMasks, check_runs
+        frames = [frames_masks] if isinstance(frames_masks, RleMasks) else list(frames_masks)
+        for f, r in enumerate(frames):
+            if not isinstance(r, RleMasks):
+                raise ValueError("set_masks_rle: frame %d is %s, not RleMasks" % (f, type(r).__name__))
+            if tuple(r.shape[1:]) != (H, W):
+                raise ValueError("set_masks_rle: frame %d has masks of %d x %d, the camera is %d x %d (runs are not resized)"
+                                 % (f, r.shape[2], r.shape[1], W, H))
+            if r.shape[0] > LPF_MAX_MASKS:
+                raise ValueError("set_masks_rle: frame %d has %d masks, one pass takes %d (pipeline.run_frames groups them)"
+                                 % (f, r.shape[0], LPF_MAX_MASKS))
+        F = len(frames)
+        M = max([r.shape[0] for r in frames], default=0)
+        checked = [check_runs(r.runs, r.run_off, r.shape[0], H * W, "set_masks_rle: frame %d" % f) for f, r in enumerate(frames)]
+        run_off = np.zeros(F * M + 1, np.int64)
+        base = 0
+        for f, (runs, off) in enumerate(checked):
+            m = len(off) - 1
+            run_off[f * M + 1:f * M + 1 + m] = base + off[1:]
+            base += len(runs)
+            run_off[f * M + 1 + m:(f + 1) * M + 1] = base
+        runs = np.concatenate([c[0] for c in checked]) if checked else np.zeros((0, 2), np.int32)
+        return np.ascontiguousarray(runs, dtype=np.int32), run_off, F, M
+
+    def set_masks_rle(self, frames_masks, erode_iters=0):
+        """Masks in run-length form (rle.RleMasks: one, or a list with one per frame), decoded on the GPU: what reaches the device is
+        the runs -- a few tens of KB for a frame's masks -- instead of M x H x W bytes.  Afterwards the context is as after
+        ``set_masks(dense uint8 host masks, erode_iters)`` with the same members.  Ragged M is padded with empty masks; the masks must
+        have the camera's size; at most LPF_MAX_MASKS per frame (pipeline.run_frames groups more)."""
+        runs, run_off, F, M = self.rle_batch(frames_masks, self.H, self.W)
+        if int(erode_iters) < 0:
+            raise ValueError("erode_iters must be >= 0, got %r" % (erode_iters,))
+        inp = RleMasksInput(runs.ctypes.data if len(runs) else None, run_off.ctypes.data, F, M, int(erode_iters), 0)
+        self._check(self._lib.lpf_set_masks_rle(self._h, ctypes.byref(inp)))
         self.F_masks, self.M = F, M
 
     def clear_masks(self):

@@ -14,6 +14,7 @@
 #include "lpf_box_points.hip.h"
 #include "lpf_box_views.hip.h"
 #include "lpf_first_match.hip.h"
+#include "lpf_rle.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -104,6 +105,8 @@ struct lpf_ctx {
 
     // masks -> label images
     DevBuf mask_stage;
+    DevBuf rle_stage;                 // lpf_set_masks_rle: [runs | work units | run_off] of the call being decoded
+    std::vector<int2> rle_units;      // ... its work units while the host emits them (kept for its capacity)
     // Masks that are set but not packed (no erosion; the next lpf_run* decides, plan_tile_source).  Left by lpf_set_masks_* of a serial
     // context -- host masks in mask_stage, or device masks the caller lends (on_device 2): a launch of sparse frames reads them directly,
     // anything else packs them first -- or of a pipelined one (lent masks only): a fused launch of sparse frames reads them directly, a
@@ -999,6 +1002,25 @@ int set_boxes_impl(lpf_ctx *c, const double *corners, int on_device, const int32
     return LPF_OK;
 }
 
+// `left` erosion iterations on the packed label image cur ([F][H][W] elements LT), one launch each, on stream ms: the cross, or
+// (element) the context's k x k element.  Ping-pong with lb_, reserved here like every label image at 4 bytes per pixel; cur ends as
+// the buffer that holds the result.  Shared by pack_masks and lpf_set_masks_rle.
+template <typename LT> int erode_packed_iters(lpf_ctx *c, LT *&cur, DevBuf &lb_, const int W, const int H, const int F, hipStream_t ms, int left, bool element)
+{
+    if (left <= 0) return LPF_OK;
+    int rc;
+    if ((rc = reserve(c, lb_, (size_t)F * H * W * 4))) return rc;
+    const dim3 grid((W + LPF_TW - 1) / LPF_TW, (H + LPF_TH - 1) / LPF_TH, F);
+    LT *other = (LT *)lb_.p;
+    for (int it = 0; it < left; ++it) {
+        if (element) hipLaunchKernelGGL((lpf_erode_packed_k<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, H, W, c->erode_r, c->erode_spans);
+        else hipLaunchKernelGGL((lpf_erode_packed<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, H, W);
+        LPF_HIP(c, hipGetLastError());
+        LT *t = cur; cur = other; other = t;
+    }
+    return LPF_OK;
+}
+
 // masks [F][M][H][W] (uint8 under rule 0, or float under rule 1..3) -> label image with elements of `label_bytes`, on stream ms, into la
 // (lb_ = erosion ping-pong): the context's camera size for the narrow calls (a scratch set's label_a / label_b), camera c's for
 // lpf_run_cams
@@ -1039,20 +1061,19 @@ int pack_masks(lpf_ctx *c, DevBuf &la, DevBuf &lb_, const int W, const int H, hi
                 }
             });
             LPF_HIP(c, hipGetLastError());
-            if (left > 0) {
-                if ((rc = reserve(c, lb_, (size_t)F * hw * 4))) return rc;
-                LT *other = (LT *)lb_.p;
-                for (int it = 0; it < left; ++it) {
-                    if (element) hipLaunchKernelGGL((lpf_erode_packed_k<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, H, W, er, spans);
-                    else hipLaunchKernelGGL((lpf_erode_packed<LT>), grid, dim3(LPF_BLOCK), 0, ms, cur, other, H, W);
-                    LPF_HIP(c, hipGetLastError());
-                    LT *t = cur; cur = other; other = t;
-                }
-            }
+            if ((rc = erode_packed_iters(c, cur, lb_, W, H, F, ms, left, element))) return rc;
         }
         *result = cur;
         return LPF_OK;
     });
+}
+
+// the refusal of more masks per frame than a narrow run takes (lpf_set_masks_u8 / _f32 / _rle)
+int too_many_masks(lpf_ctx *c, int M)
+{
+    return fail(c, LPF_ERR_ARG, "set_masks: M=%d masks per frame, a run takes at most LPF_MAX_MASKS = %d (one bit each in label_bits): run the frame "
+                                "once per group of %d masks -- everything per point is the same in every pass (pipeline.run_frames does so)",
+                M, LPF_MAX_MASKS, LPF_MAX_MASKS);
 }
 
 template <typename T>
@@ -1061,10 +1082,7 @@ int set_masks_impl(lpf_ctx *c, const T *masks, int F, int M, int mode, int erode
     if (!c) return LPF_ERR_ARG;
     if (use_device(c)) return LPF_ERR_HIP;
     if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera must be called before masks (W, H)");
-    if (M > LPF_MAX_MASKS)
-        return fail(c, LPF_ERR_ARG, "set_masks: M=%d masks per frame, a run takes at most LPF_MAX_MASKS = %d (one bit each in label_bits): run the frame "
-                                    "once per group of %d masks -- everything per point is the same in every pass (pipeline.run_frames does so)",
-                    M, LPF_MAX_MASKS, LPF_MAX_MASKS);
+    if (M > LPF_MAX_MASKS) return too_many_masks(c, M);
     if (F < 0 || M < 0 || erode_iters < 0 || (F > 0 && M > 0 && !masks))
         return fail(c, LPF_ERR_ARG, "set_masks: F=%d M=%d erode_iters=%d masks=%p", F, M, erode_iters, (const void *)masks);
     // software-pipelined modes + device masks: the label images rotate with the scratch sets (the tiles of the previous run may
@@ -1593,7 +1611,7 @@ void lpf_destroy(lpf_ctx *c)
         for (DevBuf *b : {&D->tab, &D->pts, &D->in, &D->out}) release(*b);
     release(c->fmat.code);
     release(c->fmat.tiles);
-    DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
+    DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->rle_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
     for (DevBuf *b : all) release(*b);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ring.ev) if (e) (void)hipEventDestroy(e);
@@ -1818,6 +1836,95 @@ int lpf_set_masks_f32(lpf_ctx *c, const float *masks, int F, int M, int binarize
 {
     if (c && (binarize < 0 || binarize > 2)) return fail(c, LPF_ERR_ARG, "lpf_set_masks_f32: binarize=%d (0, 1 or 2)", binarize);
     return set_masks_impl<float>(c, masks, F, M, binarize + 1, erode_iters, on_device);
+}
+
+// Run-length masks (include/lpf.h): checked in full on the host, which also emits the work units of the decode (lpf_rle.hip.h); then
+// the state transitions of set_masks_impl with host masks -- drain what a pipelined context owes, the label image of the set the next
+// run reads -- with zero + decode (+ erosion on the packed image) in place of copy + pack.  Always packed at the call.
+int lpf_set_masks_rle(lpf_ctx *c, const lpf_rle_masks *in)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (use_device(c)) return LPF_ERR_HIP;
+    if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera must be called before masks (W, H)");
+    if (c->capturing)
+        return fail(c, LPF_ERR_STATE, "lpf_set_masks_rle cannot be captured into a graph (the run counts size its launch: call it outside "
+                                      "lpf_graph_begin ... lpf_graph_end)");
+    if (!in) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: in=NULL");
+    if (in->M > LPF_MAX_MASKS) return too_many_masks(c, in->M);
+    const int F = in->F, M = in->M;
+    int erode_iters = in->erode_iters;
+    if (F < 0 || M < 0 || erode_iters < 0 || in->reserved != 0)
+        return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: F=%d M=%d erode_iters=%d reserved=%d", F, M, erode_iters, in->reserved);
+    const long long hw = (long long)c->H * c->W;
+    const long long FM = (long long)F * M;
+    if (FM > 0x7fffffffll) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: F * M = %lld masks (at most 2^31 - 1 in one call)", FM);
+    long long Rtot = 0;
+    std::vector<int2> &units = c->rle_units;
+    units.clear();
+    if (FM > 0) {
+        const int64_t *off = in->run_off;
+        if (!off) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: run_off=NULL with F=%d M=%d", F, M);
+        if (off[0] != 0) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: run_off[0]=%lld (must be 0)", (long long)off[0]);
+        for (long long k = 0; k < FM; ++k)
+            if (off[k + 1] < off[k])
+                return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: run_off decreases at frame %lld mask %lld (%lld after %lld)", k / M, k % M,
+                            (long long)off[k + 1], (long long)off[k]);
+        Rtot = off[FM];
+        if (Rtot > 0x7fffffffll) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: %lld runs (at most 2^31 - 1 in one call)", Rtot);
+        if (Rtot > 0 && !in->runs) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: runs=NULL with %lld runs", Rtot);
+        for (long long k = 0; k < FM; ++k)
+            for (long long r = off[k]; r < off[k + 1]; ++r) {
+                const long long start = in->runs[2 * r], length = in->runs[2 * r + 1];
+                if (start < 0 || length < 0 || start + length > hw)
+                    return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: frame %lld mask %lld run %lld: start=%lld length=%lld (0 <= start, 0 <= length, "
+                                                "start + length <= W*H = %lld)", k / M, k % M, r - off[k], start, length, hw);
+                for (long long p = start; p < start + length; p += LPF_RLE_CHUNK) units.push_back(int2{(int)r, (int)p});
+                if (units.size() > LPF_RLE_MAX_UNITS)
+                    return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: the runs cover more than 2^24 chunks of %d pixels (frame %lld mask %lld run %lld): "
+                                                "set fewer frames per call", LPF_RLE_CHUNK, k / M, k % M, r - off[k]);
+            }
+    }
+    // from here on: set_masks_impl with host masks (not per scratch set: what a pipelined context owes is drained first)
+    int rc;
+    if (c->pipe.owes() && (rc = sync_all(c))) return rc;
+    lpf_ctx::Masks &MK = c->masks;
+    lpf_ctx::Scratch &S = c->sc[c->pipe.set_now()];
+    MK.begin(c->pipe.set_now());
+    if (F == 0) return LPF_OK;
+    // 4 bytes per pixel whatever the element: the decode's 32-bit atomics on the last, partial word of an image of 1- or 2-byte
+    // elements stay inside the allocation (lpf_rle.hip.h)
+    if ((rc = reserve(c, S.label_a, (size_t)F * hw * 4))) return rc;
+    const int lb = (M <= 8) ? 1 : (M <= 16) ? 2 : 4;
+    c->rects_pending = nullptr;                             // a pending lpf_set_mask_rects hint is consumed (runs need none)
+    MK.forget_unpacked();
+    LPF_HIP(c, hipMemsetAsync(S.label_a.p, 0, (size_t)F * hw * lb, c->stream));
+    void *cur = S.label_a.p;
+    if (!units.empty()) {
+        const size_t b_runs = align256((size_t)Rtot * sizeof(int2)), b_units = align256(units.size() * sizeof(int2)), b_off = (size_t)(FM + 1) * 8;
+        if ((rc = reserve(c, c->rle_stage, b_runs + b_units + b_off))) return rc;
+        char *d = (char *)c->rle_stage.p;
+        LPF_HIP(c, hipMemcpyAsync(d, in->runs, (size_t)Rtot * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+        LPF_HIP(c, hipMemcpyAsync(d + b_runs, units.data(), units.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+        LPF_HIP(c, hipMemcpyAsync(d + b_runs + b_units, in->run_off, b_off, hipMemcpyHostToDevice, c->stream));
+        LpfRleJob J;
+        J.runs = (const int2 *)d; J.units = (const int2 *)(d + b_runs); J.run_off = (const long long *)(d + b_runs + b_units);
+        J.hw = hw; J.n_units = (int)units.size(); J.M = M; J.FM = (int)FM;
+        const unsigned nb = (unsigned)((units.size() + LPF_RLE_BLOCK / 64 - 1) / (LPF_RLE_BLOCK / 64));
+        if (c->erode_k == 1) erode_iters = 0;              // (the 1 x 1 element: any number of iterations is the identity)
+        rc = with_label(lb, [&](auto lt) -> int {
+            typedef typename decltype(lt)::type LT;
+            hipLaunchKernelGGL((lpf_rle_decode<LT>), dim3(nb), dim3(LPF_RLE_BLOCK), 0, c->stream, J, (uint32_t *)S.label_a.p);
+            LPF_HIP(c, hipGetLastError());
+            LT *img = (LT *)S.label_a.p;
+            int rc_ = erode_packed_iters(c, img, S.label_b, c->W, c->H, F, c->stream, erode_iters, c->erode_k != 3);
+            cur = img;
+            return rc_;
+        });
+        if (rc) return rc;
+        LPF_HIP(c, host_wait(c));                           // the caller's arrays (and the unit table) may be reused
+    }
+    MK.packed(F, M, cur, lb);
+    return LPF_OK;
 }
 
 int lpf_set_label_image(lpf_ctx *c, const uint32_t *label, int F, int M, int on_device)

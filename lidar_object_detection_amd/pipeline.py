@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _native, kitti360
 from ._native import LpfContext, LPF_MAX_CAMS, LPF_MAX_MASKS, LPF_MAX_MASKS_WIDE, Scan, ScanReader
+from .rle import RleMasks
 
 _CONTEXTS = {}
 
@@ -1592,6 +1593,45 @@ def _mask_batch(stacks, M, H, W, ctx):
     return batch
 
 
+def _rle_frame_masks(frames, camera):
+    """Each frame's RleMasks when the batch's masks come in run-length form (a frame without masks -- None, an empty list -- gets an
+    empty one), None when no frame's do.  ValueError, before anything reaches the library: a batch that mixes RleMasks and dense
+    masks, and RleMasks of another size than the camera's (runs are not resized)."""
+    is_rle = [isinstance(f.masks, RleMasks) for f in frames]
+    if not any(is_rle):
+        return None
+    H, W = camera.height, camera.width
+    out = []
+    for f, r in zip(frames, is_rle):
+        if r:
+            if tuple(f.masks.shape[1:]) != (H, W):
+                raise ValueError("frame %s: RleMasks of %d x %d, the camera is %d x %d (runs are not resized: decode with .to_dense())"
+                                 % (f.frame, f.masks.shape[2], f.masks.shape[1], W, H))
+            out.append(f.masks)
+        elif f.masks is None or len(f.masks) == 0:
+            out.append(RleMasks(np.zeros((0, 2), np.int32), np.zeros(1, np.int64), (0, H, W)))
+        else:
+            raise ValueError("frame %s: dense masks in a batch of RleMasks frames: one form per batch (.to_dense() or RleMasks.from_dense)"
+                             % (f.frame,))
+    return out
+
+
+def _run_frames_rle(frames, rles, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, device, ctx, gather_scans,
+                    erosion_kernel_size):
+    """run_frames for frames whose masks are RleMasks (the camera and the erosion element set): up to 32 masks in one narrow pass behind
+    set_masks_rle -- the runs go to the GPU, not the masks -- more in groups of 32.  On 0/1 masks V3's cast chain is the erosion alone,
+    so v3_pipeline needs nothing beyond erode_iters."""
+    counts = [r.shape[0] for r in rles]
+    if max(counts) > LPF_MAX_MASKS:
+        return _run_frames_in_mask_groups(frames, rles, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, False,
+                                          device, ctx, group=LPF_MAX_MASKS, erosion_kernel_size=erosion_kernel_size)
+    corners, positions = zip(*(_corners_velo(f.bboxes_3d) for f in frames))
+    ctx.set_masks_rle(rles, erode_iters=erode_iters)
+    ctx.set_boxes(list(corners), oriented=use_oriented)
+    res = ctx.run_batch([f.points for f in frames], want_uv=False, want_label=False, want_valid_uv=True, pinned=True)
+    return [_frame_result(f, r, m, pos, min_points, gather_scans) for f, r, m, pos in zip(frames, res, counts, positions)]
+
+
 def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_oriented=True,
                erode_iters=0, v3_pipeline=False, device=0, ctx=None, gather_scans=True, erosion_kernel_size=3):
     """Projection + clip + mask lookup + box counting + best-box scan for a list of
@@ -1602,14 +1642,20 @@ def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_
     ``car_point_sets``) made before the call returns, because the reader recycles the scan's buffers when it moves on;
     ``gather_scans=False`` leaves them lazy like everyone else's -- reading them after the reader has moved on raises.
     ``erosion_kernel_size``: the reference's knob of that name (V3:55, cvs_erosion.py:77) -- ``erode_iters`` iterations erode with the
-    k x k MORPH_ELLIPSE element (odd, 1 .. 15; 3 is the cross).  It is set on the context by every call, the default included."""
+    k x k MORPH_ELLIPSE element (odd, 1 .. 15; 3 is the cross).  It is set on the context by every call, the default included.
+    Frames whose ``masks`` are ``rle.RleMasks`` (at the camera's size; every frame of the batch, a frame without masks aside) take
+    set_masks_rle: the runs are decoded on the GPU, nothing dense crosses to the device; more than 32 masks run in groups of 32."""
     erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     if not frames:
         return []
+    rles = _rle_frame_masks(frames, camera)
     ctx = ctx or get_context(device)
     ctx.set_erosion_element(erosion_kernel_size)
     H, W = camera.height, camera.width
     ctx.set_camera(TrVeloToRect, camera.K, W, H, 0.0, float(depth_max))
+    if rles is not None:
+        return _run_frames_rle(frames, rles, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, device, ctx,
+                               gather_scans, erosion_kernel_size)
     stacks, erode_iters, v3_pipeline = _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline, erosion_kernel_size)
     counts = [s.shape[0] for s in stacks]
     M = max(counts)
