@@ -734,7 +734,7 @@ class LpfContext:
         K3 = np.ascontiguousarray(np.asarray(K, dtype=np.float64)[:3, :3]).reshape(9)
         key = (T.tobytes(), K3.tobytes(), int(width), int(height), float(depth_min), float(depth_max))
         if key == getattr(self, "_camera", None):           # a frame loop sets the same camera every frame: nothing to do (the C call
-            return                                          # would mark captured graphs stale and rebuild the box tables)
+            return                                          # would mark captured graphs stale and wait for work still owed)
         self._check(self._lib.lpf_set_camera(self._h, T.ctypes.data, K3.ctypes.data, int(width), int(height),
                                              float(depth_min), float(depth_max)))
         self._camera = key
@@ -742,7 +742,7 @@ class LpfContext:
 
     def ensure_intrinsics(self, K, width, height):
         """The camera's K, width and height are in force -- all that lpf_prepare_boxes reads of the camera.  A frame loop that prepares
-        boxes and runs frames in turn keeps the run's camera (no lpf_set_camera per frame: that call rebuilds the box tables)."""
+        boxes and runs frames in turn keeps the run's camera (no lpf_set_camera per frame: that call waits for work still owed)."""
         K3 = np.ascontiguousarray(np.asarray(K, dtype=np.float64)[:3, :3]).reshape(9)
         cam = getattr(self, "_camera", None)
         if cam is not None and cam[1] == K3.tobytes() and cam[2] == int(width) and cam[3] == int(height):

@@ -140,12 +140,10 @@ struct lpf_ctx {
         void left_unpacked(void *image, int b) { F = unpacked.F; M = unpacked.M; img = image; bytes = b; }
     } masks;
 
-    // Boxes.  A ring of box sets: in the software-pipelined modes the tail that counts into the boxes of run i executes one
-    // or two launches after run i was queued, so a lpf_set_boxes* for the NEXT run must not touch the tables run i's tail is
-    // going to read -- it takes the next set of the ring instead (no drain, no synchronisation), and the preparation of its
-    // tables (LpfBoxJob) rides in that run's launch.  Serial mode stays on one set: the stream orders everything.
+    // One set of box tables, and the job (LpfBoxJob) that fills them.  F, job_valid, used and last_ref are written by the methods
+    // below and by lpf_ctx::Boxes only.
     struct BoxSet {
-        int F = 0, oriented = 1;
+        int F = 0, oriented = 1;                  // 0 frames = no boxes here
         std::vector<int32_t> box_off;             // F+1
         std::vector<LpfBoxFrame> h_bframes, h_bframes_dev;   // per-frame records: being built / in HBM (F > 1 only)
         std::vector<long long> cand_off;          // [F] first word of frame f's grid
@@ -154,19 +152,64 @@ struct lpf_ctx {
         DevBuf boxp;                              // [Btot][16] double
         DevBuf boxq;                              // [Btot][8] float conservative AABB
         DevBuf cand;                              // ground grids: LPF_GRID_WORDS words per 64 boxes of a frame
-        DevBuf corners;                           // [Btot][8][3] velodyne-frame corners the tables were built from (kept: a camera change rebuilds them)
-        DevBuf enabled;                           // [Btot] bytes: 0 = dropped by filter_visible_bboxes (lpf_set_boxes_cam0)
+        DevBuf corners;                           // [Btot][8][3] velodyne-frame corners the tables were built from (lpf_set_boxes_cam0's host output corners_velo)
+        DevBuf enabled;                           // [Btot] bytes: 0 = dropped by filter_visible_bboxes (lpf_set_boxes_cam0; its host output visible)
         DevBuf aux;                               // lpf_set_boxes_cam0 for host callers: projected 2D boxes + front counts
         DevBuf bframes;                           // [F] LpfBoxFrame
         DevBuf stage;                             // corners copied from the caller (host memory, or device memory that is not lent)
-        bool have_enabled = false;
         bool used = false;                        // a run has been queued with these tables since they were set
-        long long last_ref = -1;                  // ... the last such run (lpf_ctx::run_seq)
+        long long last_ref = -1;                  // ... the last such run (Boxes::run_seq)
         bool job_valid = false;                   // tables not built yet: the job rides in the next run's launch (or is launched by it)
         LpfBoxJob job;
-    } bx[LPF_NSETS];
-    int box_cur = 0;
-    bool cand_dirty = false;          // the camera changed since the current set's tables were built: rebuild from its corners
+        void clear() { F = 0; box_off.clear(); job_valid = false; }      // no boxes here (the buffers stay: nothing reads them while F is 0)
+        void begin() { clear(); used = false; last_ref = -1; }           // a call that sets boxes starts on this set: no run has read what it will hold
+        void shaped(const int32_t *off, int F_, int oriented_) { box_off.assign(off, off + F_ + 1); F = F_; oriented = oriented_ ? 1 : 0; }
+        int total() const { return F ? box_off[(size_t)F] : 0; }         // boxes of all frames
+        // The fields every job has: corners from src (velodyne frame unless the caller adds cam0), this set's tables and its copy of the
+        // corners as outputs.  The job waits for the launch that takes it.
+        LpfBoxJob &new_job(const double *src)
+        {
+            memset(&job, 0, sizeof job);
+            job.src = src; job.oriented = oriented; job.F = F; job.chunks = max_words;
+            job.bframes = (const LpfBoxFrame *)bframes.p;
+            if (F > 0) job.frame0 = h_bframes[0];
+            job.boxp = (double *)boxp.p; job.boxq = (float *)boxq.p; job.cand = (unsigned long long *)cand.p;
+            job.corners_keep = (double *)corners.p;
+            job_valid = true;
+            return job;
+        }
+        bool job_ready() const { return job_valid && total() > 0; }     // a job worth launching
+        bool take_job() { const bool ready = job_ready(); job_valid = false; return ready; }      // by the launch that carries it, if it is ready
+    };
+    // Boxes.  A ring of box sets: in the software-pipelined modes the tail that counts into the boxes of run i executes one
+    // or two launches after run i was queued, so a lpf_set_boxes* for the NEXT run must not touch the tables run i's tail is
+    // going to read -- it takes the next set of the ring instead (no drain, no synchronisation), and the preparation of its
+    // tables (LpfBoxJob) rides in that run's launch.  Serial mode stays on one set: the stream orders everything.
+    struct Boxes {
+        BoxSet ring[LPF_NSETS];
+        int cur = 0;                  // the set in force
+        long long run_seq = 0;        // runs queued so far
+        BoxSet &in_force() { return ring[cur]; }                         // the set a run or an analysis call reads
+        // The set a lpf_set_boxes* call writes.  Pipelined (fused; depth: launches from the one that queues a run to the one with its
+        // tail): the next one of the ring once a run has used the current one -- that run's tail has yet to read its tables -- and
+        // *owed says that the last reader of the set's old tables may not have been LAUNCHED yet: the caller launches what the
+        // pipeline owes before it rewrites them (stream order does the rest; with one set per run and four sets it never happens).
+        // In order: the current set.  (Never inside a graph capture: see Pipeline::set_now.)
+        BoxSet &set_for_write(bool fused, int depth, bool *owed)
+        {
+            *owed = false;
+            if (fused) {
+                if (ring[cur].used) {
+                    ring[cur].job_valid = false;           // (cannot be: a run launches the job of the set it uses)
+                    cur = (cur + 1) % LPF_NSETS;
+                }
+                *owed = ring[cur].last_ref >= 0 && ring[cur].last_ref + depth >= run_seq;
+            }
+            return ring[cur];
+        }
+        void claimed_by_run() { ring[cur].used = true; ring[cur].last_ref = run_seq++; }     // a run has been queued that reads the set in force
+        void drop() { for (BoxSet &B : ring) B.clear(); }                // none in force, in any set
+    } boxes;
 
     // Scratch of one in-flight run, including its geometry tables (frame records, per-segment frame records, tail block table):
     // a run whose batch shape differs from the previous one's uploads its own tables -- through the pinned ring below, in stream
@@ -183,7 +226,6 @@ struct lpf_ctx {
         int tab_csplit = 0;                       // ... and its count blocks per (group, word): the key of the tables (narrow_tables)
         size_t o_segs = 0, o_blks = 0, o_cblks = 0;
     } sc[LPF_NSETS];
-    long long run_seq = 0;            // runs queued so far
     struct Pending {                  // a run, as the step launches that carry its roles take it
         bool valid = false;
         LpfParams P;
@@ -366,27 +408,27 @@ void launch_tail(hipStream_t st, const LpfParams &P, int ntail, bool pre)
 
 // camera-dependent fields of a box job: filled when the job is launched, so a job that waits for its run always sees the
 // camera of that run
-void box_job_camera(const lpf_ctx *c, LpfBoxJob &J)
+void box_job_camera(LpfBoxJob &J, const double K[9], int W, int H)
 {
-    memcpy(J.K, c->K, sizeof J.K);
-    J.W = c->W; J.H = c->H;
+    memcpy(J.K, K, sizeof J.K);
+    J.W = W; J.H = H;
 }
 
 // blocks of a set's box job: frames x 64-box chunks of the frame with the most boxes
 int box_job_blocks(const lpf_ctx::BoxSet &B) { return B.F * B.job.chunks; }
 
-// the box job of a set as a kernel of its own, on the context's stream (serial mode, graph capture, drains)
-int launch_box_job(lpf_ctx *c, lpf_ctx::BoxSet &B)
+// the box job of a set as a kernel of its own, on the context's stream (serial mode, graph capture, drains, a camera of lpf_run_cams),
+// in the camera K, W, H: the context's, unless the caller names another
+int launch_box_job(lpf_ctx *c, lpf_ctx::BoxSet &B, const double K[9], int W, int H)
 {
-    if (!B.job_valid) return LPF_OK;
-    B.job_valid = false;
-    if (B.F == 0 || B.box_off[B.F] == 0) return LPF_OK;
-    box_job_camera(c, B.job);
+    if (!B.take_job()) return LPF_OK;
+    box_job_camera(B.job, K, W, H);
     ++c->stats[4];
     hipLaunchKernelGGL(lpf_box_job_kernel, dim3((unsigned)box_job_blocks(B)), dim3(LPF_BLOCK), 0, c->stream, B.job);
     LPF_HIP(c, hipGetLastError());
     return LPF_OK;
 }
+int launch_box_job(lpf_ctx *c, lpf_ctx::BoxSet &B) { return launch_box_job(c, B, c->K, c->W, c->H); }
 
 // One launch of lpf_step_t: the streaming tiles of run K, the tail blocks of run Q dealt out among them, the summaries of
 // run R, the box job X of the run being queued (a block per frame, in front) and -- mode 4 -- the pack of that run's masks, waiting
@@ -421,9 +463,8 @@ int launch_step(lpf_ctx *c, const lpf_ctx::Pending &KK, const lpf_ctx::Pending &
     Y.clk = (unsigned long long *)c->lab_clk.p;
 #endif
     Y.nfin8 = (Y.nfin + 7) & ~7;
-    const bool boxes = XB && XB->job_valid && XB->F > 0 && XB->box_off[XB->F] > 0;
-    if (XB) XB->job_valid = false;
-    if (boxes) box_job_camera(c, XB->job);
+    const bool boxes = XB && XB->take_job();
+    if (boxes) box_job_camera(XB->job, c->K, c->W, c->H);
     const LpfBoxJob &XJ = boxes ? XB->job : nojob;
     Y.nbox = boxes ? box_job_blocks(*XB) : 0;
     Y.nbox8 = (Y.nbox + 7) & ~7;
@@ -500,7 +541,7 @@ int queue_step(lpf_ctx *c, const lpf_ctx::Pending *cur, lpf_ctx::BoxSet *XB, hip
 // launches (or alone)
 int flush_pending(lpf_ctx *c)
 {
-    lpf_ctx::BoxSet *XB = &c->bx[c->box_cur];
+    lpf_ctx::BoxSet *XB = &c->boxes.in_force();
     int rc_;
     if (c->pipe.owes()) ++c->stats[1];
     while (c->pipe.owes())
@@ -805,7 +846,7 @@ template <typename T> T range_base(bool staged, T first) { return staged ? first
 // The box set in force, for a call `who` that tests the points of F frames against it: there must be one, set for F frames.
 int boxes_in_force(lpf_ctx *c, const char *who, int F, lpf_ctx::BoxSet **BX)
 {
-    *BX = &c->bx[c->box_cur];
+    *BX = &c->boxes.in_force();
     if ((*BX)->F == 0) return fail(c, LPF_ERR_STATE, "%s: no boxes in force (lpf_set_boxes* comes first)", who);
     if ((*BX)->F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, %s has %d", (*BX)->F, who, F);
     return LPF_OK;
@@ -867,9 +908,8 @@ void box_params(const double *c, int oriented, double *o)
 
 int box_shape(lpf_ctx *c, lpf_ctx::BoxSet &B, const int32_t *box_off, int F, int oriented);
 
-// The box set a lpf_set_boxes* call writes: in the software-pipelined modes the next one of the ring once the current one has
-// been used by a run (its tables are still to be read by that run's tail), else the current one.  Then its shapes: per-frame
-// records, grid offsets, buffers.  Nothing here waits for the GPU unless a buffer has to grow.
+// The box set a lpf_set_boxes* call writes (lpf_ctx::Boxes::set_for_write; refused arguments leave the boxes in force as they are),
+// then its shapes: per-frame records, grid offsets, buffers.  Nothing here waits for the GPU unless a buffer has to grow.
 int box_layout(lpf_ctx *c, const int32_t *box_off, int F, int oriented, const char *who, lpf_ctx::BoxSet **out)
 {
     if (F < 0 || (F > 0 && !box_off)) return fail(c, LPF_ERR_ARG, "%s: F=%d box_off=%p", who, F, (const void *)box_off);
@@ -878,28 +918,21 @@ int box_layout(lpf_ctx *c, const int32_t *box_off, int F, int oriented, const ch
         if (box_off[f + 1] < box_off[f]) return fail(c, LPF_ERR_ARG, "%s: box_off not ascending at %d", who, f);
     if (!c->have_camera) return fail(c, LPF_ERR_STATE, "%s: lpf_set_camera must be called first (cam-0 boxes are filtered with its K, W, H)", who);
     int rc;
-    lpf_ctx::BoxSet *B = &c->bx[c->box_cur];
-    if (c->pipe.fused) {                                   // (never inside a graph capture: see lpf_ctx::Pipeline::set_now)
-        if (B->used) {
-            B->job_valid = false;                          // (cannot be: a run launches the job of the set it uses)
-            c->box_cur = (c->box_cur + 1) % LPF_NSETS;
-            B = &c->bx[c->box_cur];
-        }
-        // the tail of the last run that used this set's old tables must have been LAUNCHED before they are rewritten (in stream
-        // order); with one set per run and four sets it always has -- else launch what is owed first (still no host wait)
-        if (B->last_ref >= 0 && B->last_ref + c->pipe.depth() >= c->run_seq && (rc = flush_pending(c))) return rc;
-    }
+    bool owed;
+    lpf_ctx::BoxSet *B = &c->boxes.set_for_write(c->pipe.fused, c->pipe.depth(), &owed);
+    if (owed && (rc = flush_pending(c))) return rc;        // (still no host wait)
     if ((rc = box_shape(c, *B, box_off, F, oriented))) return rc;
     *out = B;
     return LPF_OK;
 }
 
-// a box set's shapes for F frames of box_off: per-frame records, grid offsets, buffers (the job that fills the tables comes later)
+// a box set's shapes for F frames of box_off: per-frame records, grid offsets, buffers (the job that fills the tables comes later);
+// the set holds no boxes until the last buffer is there
 int box_shape(lpf_ctx *c, lpf_ctx::BoxSet &BS, const int32_t *box_off, int F, int oriented)
 {
     int rc;
     lpf_ctx::BoxSet *B = &BS;
-    B->used = false; B->last_ref = -1; B->job_valid = false; B->F = 0;
+    B->begin();
     B->h_bframes.resize((size_t)F);
     B->cand_off.assign((size_t)F, 0);
     B->max_words = 1;
@@ -928,23 +961,22 @@ int box_shape(lpf_ctx *c, lpf_ctx::BoxSet &BS, const int32_t *box_off, int F, in
         }
     }
     B->cand_words = total;
-    B->box_off.assign(box_off, box_off + F + 1);
-    B->F = F; B->oriented = oriented ? 1 : 0;
+    B->shaped(box_off, F, oriented);
     return LPF_OK;
 }
 
-// the job that (re)builds a set's tables from its own copy of the velodyne-frame corners (the camera changed)
-void box_rebuild_job(lpf_ctx::BoxSet &B)
+// The corners a set's job reads: the caller's own when they are lent device memory (on_device 2), else the set's copy of them, made
+// here in stream order (an upload from host memory, a device copy).  nb boxes.
+int stage_corners(lpf_ctx *c, lpf_ctx::BoxSet &B, const double *corners, int on_device, size_t nb, const double **src)
 {
-    LpfBoxJob &J = B.job;
-    memset(&J, 0, sizeof J);
-    J.src = (const double *)B.corners.p;
-    J.enabled_in = B.have_enabled ? (const uint8_t *)B.enabled.p : nullptr;
-    J.oriented = B.oriented; J.F = B.F; J.chunks = B.max_words;
-    J.bframes = (const LpfBoxFrame *)B.bframes.p;
-    if (B.F > 0) J.frame0 = B.h_bframes[0];
-    J.boxp = (double *)B.boxp.p; J.boxq = (float *)B.boxq.p; J.cand = (unsigned long long *)B.cand.p;
-    B.job_valid = true;
+    int rc;
+    *src = corners;
+    if (on_device == 2) return LPF_OK;
+    if ((rc = reserve(c, B.stage, nb * 192))) return rc;
+    if (on_device) LPF_HIP(c, hipMemcpyAsync(B.stage.p, corners, nb * 192, hipMemcpyDeviceToDevice, c->stream));
+    else if ((rc = upload(c, B.stage.p, corners, nb * 192))) return rc;
+    *src = (const double *)B.stage.p;
+    return LPF_OK;
 }
 
 // lpf_set_boxes_ex / lpf_set_boxes_cam0: corners (velodyne or cam-0 frame) -> the job that builds the set's tables.  The job is
@@ -956,39 +988,28 @@ int set_boxes_impl(lpf_ctx *c, const double *corners, int on_device, const int32
     if (!c) return LPF_ERR_ARG;
     if (use_device(c)) return LPF_ERR_HIP;
     if (on_device < 0 || on_device > 2) return fail(c, LPF_ERR_ARG, "%s: on_device=%d (0 host, 1 device, 2 device and lent)", who, on_device);
-    if (F == 0) { lpf_ctx::BoxSet &B0 = c->bx[c->box_cur]; B0.F = 0; B0.box_off.clear(); B0.job_valid = false; return LPF_OK; }
+    if (F == 0) { c->boxes.in_force().clear(); return LPF_OK; }
     if (cam0 && !Tcv) return fail(c, LPF_ERR_ARG, "%s: T_cam_to_velo is NULL", who);
     if (box_off && F > 0 && box_off[F] > 0 && !corners) return fail(c, LPF_ERR_ARG, "%s: corners is NULL", who);
     int rc;
     lpf_ctx::BoxSet *B = nullptr;
     if ((rc = box_layout(c, box_off, F, oriented, who, &B))) return rc;
     const int Btot = box_off[F];
-    B->have_enabled = cam0 && filter_visible != 0;
-    c->cand_dirty = false;                                 // the job reads the camera when it is launched
     if (Btot == 0) return LPF_OK;
     const size_t nb = (size_t)Btot;
-    const double *src = corners;
-    if (on_device != 2) {                                  // not lent: the context's own copy, made in stream order
-        if ((rc = reserve(c, B->stage, nb * 192))) { B->F = 0; return rc; }
-        if (on_device) LPF_HIP(c, hipMemcpyAsync(B->stage.p, corners, nb * 192, hipMemcpyDeviceToDevice, c->stream));
-        else if ((rc = upload(c, B->stage.p, corners, nb * 192))) { B->F = 0; return rc; }
-        src = (const double *)B->stage.p;
-    }
+    const double *src;
+    if ((rc = stage_corners(c, *B, corners, on_device, nb, &src))) { B->clear(); return rc; }
     const bool host_out = !on_device && (visible || corners_velo || bbox2d || front);
-    if (host_out && (rc = reserve(c, B->aux, nb * 36))) { B->F = 0; return rc; }
-    LpfBoxJob &J = B->job;
-    memset(&J, 0, sizeof J);
-    J.src = src; J.cam0 = cam0 ? 1 : 0; J.filter_visible = filter_visible ? 1 : 0; J.oriented = B->oriented; J.F = F; J.chunks = B->max_words;
-    if (cam0) memcpy(J.Tcv, Tcv, sizeof J.Tcv);
-    J.bframes = (const LpfBoxFrame *)B->bframes.p; J.frame0 = B->h_bframes[0];
-    J.boxp = (double *)B->boxp.p; J.boxq = (float *)B->boxq.p; J.cand = (unsigned long long *)B->cand.p;
-    J.corners_keep = (double *)B->corners.p;
+    if (host_out && (rc = reserve(c, B->aux, nb * 36))) { B->clear(); return rc; }
+    LpfBoxJob &J = B->new_job(src);
+    J.filter_visible = filter_visible ? 1 : 0;
     if (cam0) {
+        J.cam0 = 1;
+        memcpy(J.Tcv, Tcv, sizeof J.Tcv);
         J.enabled_out = (uint8_t *)B->enabled.p;
         if (on_device) { J.visible = visible; J.corners_out = corners_velo; J.bbox2d = bbox2d; J.front = front; }
         else if (host_out) { J.bbox2d = (double *)B->aux.p; J.front = (int32_t *)((char *)B->aux.p + nb * 32); }
     }
-    B->job_valid = true;
     // The job waits for the next lpf_run* and rides in the launch of its streaming tiles (every mode: in order too the tables are
     // only read by the tail, one launch later) -- unless the caller wants results in host memory now.
     if (host_out && (rc = launch_box_job(c, *B))) return rc;
@@ -1391,7 +1412,7 @@ void narrow_params(LpfParams &P, const lpf_ctx *c, const Cam &cam, const NarrowL
 {
     memset(&P, 0, sizeof P);
     set_cam(P, cam);
-    const int Btot = BX.F ? BX.box_off[L.F] : 0;
+    const int Btot = BX.total();
     P.F = L.F; P.M = M; P.seg_pts = (int)L.seg_pts; P.nseg_total = L.nseg_total; P.nseg_cap = L.nseg_cap(); P.ngrp_cap = L.ngrp_cap();
     P.oriented = BX.F ? BX.oriented : 1; P.inst_cap = inst_cap;
     P.frame0 = c->h_frames[0];
@@ -1586,7 +1607,7 @@ void lpf_destroy(lpf_ctx *c)
         DevBuf *sb[] = {&S.vbal, &S.mbal, &S.seg_tab, &S.grp_tab, &S.frm_tab, &S.seg_pre, &S.cnt, &S.mlist, &S.label_a, &S.label_b, &S.tab, &S.rects, &S.rgrid, &S.out_stage};
         for (DevBuf *b : sb) release(*b);
     }
-    for (auto *ring : {c->bx, c->cams.bx})
+    for (auto *ring : {c->boxes.ring, c->cams.bx})
         for (int k = 0; k < LPF_NSETS; ++k) {
             lpf_ctx::BoxSet &B = ring[k];
             DevBuf *bb[] = {&B.boxp, &B.boxq, &B.cand, &B.corners, &B.enabled, &B.aux, &B.bframes, &B.stage};
@@ -1808,21 +1829,21 @@ int lpf_set_camera(lpf_ctx *c, const double T[16], const double K[9], int W, int
     if (!c) return LPF_ERR_ARG;
     if (!T || !K || W <= 0 || H <= 0 || (long long)W * H > (1ll << 30))
         return fail(c, LPF_ERR_ARG, "set_camera: T=%p K=%p W=%d H=%d", (const void *)T, (const void *)K, W, H);
-    // pipelined modes: a run still owed projects / counts boxes with the OLD camera (its box job)
-    if (!c->capturing && (c->pipe.owes() || c->bx[c->box_cur].job_valid)) {
+    // pipelined modes: a run still owed projects / counts boxes with the OLD camera (its box job).  Tables already built stay as they
+    // are: they hold velodyne-frame geometry and the visibility decided when they were built, nothing of K, W, H (box state)
+    if (!c->capturing && (c->pipe.owes() || c->boxes.in_force().job_valid)) {
         if (use_device(c)) return LPF_ERR_HIP;
         int rc_ = sync_all(c);
         if (rc_) return rc_;
     }
     if (W != c->W || H != c->H) {            // label images (and the visibility filter of cam-0 boxes) are per W x H: set masks / boxes again
         c->masks.drop();
-        for (auto &B : c->bx) { B.F = 0; B.box_off.clear(); B.job_valid = false; }
+        c->boxes.drop();
     }
     memcpy(c->T, T, sizeof c->T);          // row 3 of the 4x4 is never used by the reference either (V3:567 [:, :3])
     memcpy(c->K, K, sizeof c->K);
     c->W = W; c->H = H; c->dmin = dmin; c->dmax = dmax;
     c->have_camera = true;
-    c->cand_dirty = true;                    // a cam-0 box job filters with K, W, H: the current set's tables are rebuilt
     ++c->generation;                         // T, K, W, H are kernel arguments of a captured graph
     return LPF_OK;
 }
@@ -1999,14 +2020,14 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
     int rc;
     if ((rc = check_frames(c, "run", pts, frame_off, F, LPF_SEG_QUANTUM))) return rc;
     const int64_t Ntot = frame_off[F];
-    lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
+    lpf_ctx::BoxSet &BX = c->boxes.in_force();
     if (c->masks.F != 0 && c->masks.F != F) return fail(c, LPF_ERR_STATE, "masks were set for %d frames, run has %d", c->masks.F, F);
     if (BX.F != 0 && BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, run has %d", BX.F, F);
     if (out->inst_idx && out->inst_cap <= 0) return fail(c, LPF_ERR_ARG, "run: inst_idx given with inst_cap=%lld", (long long)out->inst_cap);
     if ((out->uv_valid || out->label_valid) && !out->valid_idx)
         return fail(c, LPF_ERR_ARG, "run: uv_valid / label_valid need valid_idx as well (they share its order)");
     const int M = c->masks.F ? c->masks.M : 0;
-    const int Btot = BX.F ? BX.box_off[F] : 0;
+    const int Btot = BX.total();
     const bool host_io = !out->on_device;
 
     // ---- segmentation (NarrowLayout) ---------------------------------------------------------------------------------------------
@@ -2065,11 +2086,7 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
         P.mlist = (float4 *)S.mlist.p;
     }
 
-    // the box tables this run's tail counts into: rebuilt if the camera changed since they were made
-    if (BX.F && c->cand_dirty && !BX.job_valid) box_rebuild_job(BX);
-    c->cand_dirty = false;
-    BX.used = true;
-    BX.last_ref = c->run_seq++;
+    c->boxes.claimed_by_run();           // this run's tail counts into the box tables in force
 
     // small clouds: 512-point tiles (more, shorter blocks); large batches: 1024-point tiles
     // Small geometry: 512-point tiles while they fit the chip's block slots in one round (256 CUs x 7 blocks: a real frame is 214
@@ -2119,7 +2136,7 @@ int lpf_run_batch(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F,
         c->pipe.parity = (c->pipe.parity + 1) % c->pipe.sets();
         return LPF_OK;
     }
-    if (BX.job_valid && nk1 > 0 && BX.F > 0 && BX.box_off[BX.F] > 0) {
+    if (BX.job_ready() && nk1 > 0) {
         // in order, with a box job waiting: the tiles and the job share one launch (lpf_step_t with those two roles), the tail
         // that reads the tables follows in the next -- the same number of launches as with boxes that never change
         const lpf_ctx::Pending cur = pending_run(P, false, 0, nk1, src);
@@ -2423,7 +2440,7 @@ int lpf_graph_end(lpf_ctx *c, lpf_graph **out)
     if (!c || !out) return LPF_ERR_ARG;
     if (use_device(c)) return LPF_ERR_HIP;
     if (!c->capturing) return fail(c, LPF_ERR_STATE, "lpf_graph_end without lpf_graph_begin");
-    { int rc_ = launch_box_job(c, c->bx[c->box_cur]); if (rc_) return rc_; }      // boxes set last in the capture, with no run behind them
+    { int rc_ = launch_box_job(c, c->boxes.in_force()); if (rc_) return rc_; }      // boxes set last in the capture, with no run behind them
     c->capturing = false;
     lpf_graph *g = new (std::nothrow) lpf_graph();
     if (!g) return fail(c, LPF_ERR_NOMEM, "out of host memory");
@@ -2661,18 +2678,15 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     if ((rc = check_frames(c, "run_wide", pts, frame_off, F, LPF_WIDE_CHUNK))) return rc;
     const int64_t Ntot = frame_off[F];
     if (out->inst_idx && out->inst_cap <= 0) return fail(c, LPF_ERR_ARG, "run_wide: inst_idx given with inst_cap=%lld", (long long)out->inst_cap);
-    lpf_ctx::BoxSet &BX = c->bx[c->box_cur];
+    lpf_ctx::BoxSet &BX = c->boxes.in_force();
     if (BX.F != 0 && BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, run_wide has %d", BX.F, F);
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
-    if (BX.F && c->cand_dirty && !BX.job_valid) box_rebuild_job(BX);
-    c->cand_dirty = false;
+    c->boxes.claimed_by_run();
     if ((rc = launch_box_job(c, BX))) return rc;
-    BX.used = true;
-    BX.last_ref = c->run_seq++;
 
     const int LW = (M + 31) / 32;
-    const int Btot = BX.F ? BX.box_off[F] : 0;
+    const int Btot = BX.total();
     const bool host_io = !out->on_device;
     const size_t n = (size_t)Ntot;
     lpf_ctx::Wide &D = c->wide;
@@ -3322,7 +3336,7 @@ int lpf_box_points(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     if ((rc = flush_pending(c))) return rc;
 
     lpf_ctx::CallBufs &D = c->bpts;
-    const size_t Ntot = (size_t)frame_off[F], Btot = (size_t)BX.box_off[F];
+    const size_t Ntot = (size_t)frame_off[F], Btot = (size_t)BX.total();
     if ((rc = upload_batch_frames(c, D.tab, frame_off, F, BX))) return rc;
 
     LpfBpParams Q;
@@ -3622,31 +3636,15 @@ static int cams_box_tables(lpf_ctx *c, const lpf_cam_input &I, int k, int F)
 {
     int rc;
     lpf_ctx::BoxSet &B = c->cams.bx[k];
-    B.F = 0; B.box_off.clear(); B.job_valid = false;
+    B.clear();
     if (!I.corners_velo) return LPF_OK;
     if ((rc = box_shape(c, B, I.box_off, F, I.oriented))) return rc;
-    const size_t nb = (size_t)I.box_off[F];
+    const size_t nb = (size_t)B.total();
     if (nb == 0) return LPF_OK;
-    const double *src = I.corners_velo;
-    if (I.boxes_on_device != 2) {                // not lent: the pass's own copy, in stream order
-        if ((rc = reserve(c, B.stage, nb * 192))) return rc;
-        if (I.boxes_on_device) LPF_HIP(c, hipMemcpyAsync(B.stage.p, src, nb * 192, hipMemcpyDeviceToDevice, c->stream));
-        else if ((rc = upload(c, B.stage.p, src, nb * 192))) return rc;
-        src = (const double *)B.stage.p;
-    }
-    B.have_enabled = false;
-    LpfBoxJob &J = B.job;
-    memset(&J, 0, sizeof J);
-    J.src = src; J.oriented = B.oriented; J.F = F; J.chunks = B.max_words;
-    J.bframes = (const LpfBoxFrame *)B.bframes.p; J.frame0 = B.h_bframes[0];
-    J.boxp = (double *)B.boxp.p; J.boxq = (float *)B.boxq.p; J.cand = (unsigned long long *)B.cand.p;
-    J.corners_keep = (double *)B.corners.p;
-    memcpy(J.K, I.K, sizeof J.K);
-    J.W = I.W; J.H = I.H;
-    ++c->stats[4];
-    hipLaunchKernelGGL(lpf_box_job_kernel, dim3((unsigned)box_job_blocks(B)), dim3(LPF_BLOCK), 0, c->stream, J);
-    LPF_HIP(c, hipGetLastError());
-    return LPF_OK;
+    const double *src;
+    if ((rc = stage_corners(c, B, I.corners_velo, I.boxes_on_device, nb, &src))) { B.clear(); return rc; }
+    B.new_job(src);
+    return launch_box_job(c, B, I.K, I.W, I.H);
 }
 
 // Camera c runs as the narrow in-order run would -- the same segments, counters, tables and tail -- in scratch set c, with its own box
@@ -3711,7 +3709,7 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         const lpf_ctx::BoxSet &BX = c->cams.bx[k];
         const lpf_outputs &o = out[k];
         const int M = I.masks.M;
-        const int Btot = BX.F ? BX.box_off[F] : 0;
+        const int Btot = BX.total();
         narrow_layout(c, frame_off, F, BX, o.inst_cap, small, L);
         lpf_ctx::Scratch &S = c->sc[k];
         if ((rc = narrow_reserve(c, S, L, M, Btot))) return rc;
@@ -3767,7 +3765,7 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         const LpfParams &P = A.P[k];
         if (o.on_device) continue;
         any_host = true;
-        const int nMB = P.M * (c->cams.bx[k].F ? c->cams.bx[k].box_off[F] : 0);
+        const int nMB = P.M * c->cams.bx[k].total();
         if ((rc = narrow_back_a(c, o, P, n, nMB, hs.data() + (size_t)k * F, &later[k]))) return rc;
         lists_later |= later[k];
     }
@@ -3808,7 +3806,7 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
     for (int k = 0; k < C; ++k) {
         if ((rc = cams_box_tables(c, cams[k], k, F))) return rc;
         const lpf_ctx::BoxSet &BX = c->cams.bx[k];
-        Btot[k] = BX.F ? BX.box_off[F] : 0;
+        Btot[k] = BX.total();
         nchunk = wide_frames(frame_off, F, BX, fr.data() + (size_t)k * F, &nbw[k]);
     }
     if ((rc = reserve(c, c->camsw.tab, fr.size() * sizeof(LpfWideFrame)))) return rc;

@@ -1540,7 +1540,7 @@ struct LpfBoxJob {               // one box preparation / table set-up (lpf_box_
     const LpfBoxFrame *bframes;  // [F] (F > 1)
     LpfBoxFrame frame0;          // ... by value for one frame
     double *boxp; float *boxq; unsigned long long *cand;
-    double *corners_keep;        // [Btot][8][3] the context's copy of the velodyne-frame corners (a camera change rebuilds from it), or null
+    double *corners_keep;        // [Btot][8][3] the context's copy of the velodyne-frame corners (read back for host callers of lpf_set_boxes_cam0), or null
     uint8_t *enabled_out;        // [Btot] the context's copy of `visible` (cam0 = 1), or null
     uint8_t *visible; double *corners_out; double *bbox2d; int32_t *front;      // optional outputs of lpf_set_boxes_cam0 (device memory)
 };

@@ -848,6 +848,106 @@ static void pack_forms()
     g_ctx = nullptr;
 }
 
+// The box state's transitions (lpf_ctx::Boxes), by what the interface shows of them: a run of another frame count is refused while
+// boxes are in force ("boxes were set for ..."), and lpf_get_stats counts the box jobs ([4] launched alone, [5] riding in a step launch).
+static void box_transitions()
+{
+    Dev D;
+    const int F = 2, M = 2;
+    const int64_t off[F + 1] = {0, 3000, 6000}, off1[2] = {0, 3000};
+    const int32_t boff[F + 1] = {0, 70, 73}, bad0[F + 1] = {1, 70, 73}, desc[F + 1] = {0, 70, 3};     // (two 64-box words in frame 0)
+    float *pts = D.get<float>(4 * off[F]);
+    uint8_t *masks = D.get<uint8_t>((size_t)F * M * W * H);
+    double *corners = D.get<double>(24 * boff[F]);
+    std::vector<double> hcorners(24 * boff[F], 0.5);
+    lpf_outputs o;
+    fill_outputs(D, o, off[F], F, M, boff[F], 500, 1);
+    lpf_wide_input wi;
+    memset(&wi, 0, sizeof wi);
+    wi.masks = masks; wi.M = M; wi.on_device = 1;
+    lpf_wide_outputs ow;
+    fill_wide_outputs(D, ow, off[F], F, M, boff[F], 500, 1);
+    double K2[9];
+    memcpy(K2, K9, sizeof K2);
+    K2[0] = 300.0; K2[2] = 60.0;                                 // same W x H, another K
+    int64_t st[8];
+    auto jobs = [&]() { CHECK(lpf_get_stats(g_ctx, st, 8, 1) == LPF_OK); return st[4] + st[5]; };     // box jobs since the last look
+    auto in_force = [&](lpf_ctx *c) {                            // boxes for F frames are in force: a run of one frame is refused
+        return lpf_run_wide(c, pts, off1, 1, 1, &wi, &ow) == LPF_ERR_STATE && err_is(c, "boxes were set for 2 frames, run_wide has 1");
+    };
+    for (int mode = 0; mode <= 4; mode += 2) {
+        lpf_ctx *c = nullptr;
+        CHECK(lpf_create(&c, 0) == LPF_OK);
+        g_ctx = c;
+        CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+        CHECK(lpf_set_pipelined(c, mode) == LPF_OK);
+        auto run = [&]() {
+            CHECK(lpf_set_masks_u8(c, masks, F, M, 0, 2) == LPF_OK);
+            CHECK(lpf_run_batch(c, pts, off, F, 1, &o) == LPF_OK);
+        };
+        // set boxes, run -- four times round the ring: every set's job is launched once, with its run; the pipeline is never drained
+        jobs();
+        for (int r = 0; r < 16; ++r) {
+            CHECK(lpf_set_boxes_ex(c, r & 1 ? corners : hcorners.data(), r & 1 ? 2 : 0, boff, F, r & 1) == LPF_OK);
+            run();
+        }
+        CHECK(lpf_get_stats(c, st, 8, 1) == LPF_OK && st[4] == 0 && st[5] == 16 && st[1] == 0);
+        // boxes set twice before a run: the second call rewrites the set of the first (no run has read it), one job
+        CHECK(lpf_set_boxes_ex(c, hcorners.data(), 0, boff, F, 1) == LPF_OK);
+        CHECK(lpf_set_boxes_ex(c, hcorners.data(), 0, boff, F, 0) == LPF_OK);
+        run();
+        CHECK(jobs() == 1);
+        // a run with the tables as they are: no job
+        run();
+        CHECK(jobs() == 0);
+        // the camera changes, same W x H: the boxes stay in force and their tables are not built again
+        CHECK(lpf_set_camera(c, T16, K2, W, H, 0, 50) == LPF_OK);
+        CHECK(in_force(c));
+        run();
+        CHECK(jobs() == 0);
+        CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+        CHECK(lpf_run_wide(c, pts, off, F, 1, &wi, &ow) == LPF_OK);
+        CHECK(jobs() == 0);
+        // a job that waits is launched by lpf_set_camera's drain, in the old camera, and not again by the run
+        CHECK(lpf_set_boxes_cam0(c, corners, 2, boff, F, T16, 1, 1, nullptr, nullptr, nullptr, nullptr) == LPF_OK);
+        CHECK(lpf_set_camera(c, T16, K2, W, H, 0, 50) == LPF_OK);
+        CHECK(lpf_get_stats(c, st, 8, 1) == LPF_OK && st[4] == 1 && st[5] == 0);
+        run();
+        CHECK(jobs() == 0);
+        // refused arguments leave the earlier boxes in force
+        CHECK(lpf_set_boxes_ex(c, hcorners.data(), 0, bad0, F, 1) == LPF_ERR_ARG && in_force(c));
+        CHECK(lpf_set_boxes_ex(c, hcorners.data(), 0, desc, F, 1) == LPF_ERR_ARG && in_force(c));
+        CHECK(lpf_set_boxes_ex(c, nullptr, 0, boff, F, 1) == LPF_ERR_ARG && in_force(c));
+        CHECK(lpf_set_boxes_cam0(c, corners, 2, boff, F, nullptr, 1, 1, nullptr, nullptr, nullptr, nullptr) == LPF_ERR_ARG && in_force(c));
+        run();
+        CHECK(jobs() == 0);
+        // lpf_run_cams builds its cameras' tables in sets of its own: the context's boxes stay in force, with their tables
+        lpf_cam_input cam;
+        memset(&cam, 0, sizeof cam);
+        memcpy(cam.T_velo_to_rect, T16, sizeof T16); memcpy(cam.K, K2, sizeof K2); cam.W = W; cam.H = H; cam.depth_max_excl = 50;
+        cam.masks = wi; cam.corners_velo = hcorners.data(); cam.box_off = boff; cam.oriented = 1;
+        CHECK(lpf_run_cams(c, pts, off, F, 1, &cam, 1, &o) == LPF_OK);
+        CHECK(lpf_get_stats(c, st, 8, 1) == LPF_OK && st[4] == 1 && st[5] == 0);      // the camera's own job
+        CHECK(in_force(c));
+        run();
+        CHECK(jobs() == 0);
+        // F == 0 after boxes were set: none in force, a run of any frame count goes through and launches no job
+        CHECK(lpf_set_boxes_ex(c, nullptr, 0, nullptr, 0, 1) == LPF_OK);
+        CHECK(lpf_set_masks_u8(c, masks, 1, M, 0, 2) == LPF_OK);
+        CHECK(lpf_run_batch(c, pts, off1, 1, 1, &o) == LPF_OK);
+        run();
+        CHECK(jobs() == 0);
+        // a camera of another size drops the boxes of every set
+        CHECK(lpf_set_boxes_ex(c, hcorners.data(), 0, boff, F, 1) == LPF_OK);
+        CHECK(lpf_set_camera(c, T16, K9, W / 2, H, 0, 50) == LPF_OK);
+        CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+        CHECK(!in_force(c));
+        CHECK(lpf_sync(c) == LPF_OK);
+        lpf_destroy(c);
+        g_ctx = nullptr;
+    }
+}
+
 // the launches so far and their hash; the hash of the copies and memsets since the section before (the reader's worker threads copy in
 // an order of their own, so the hash of "reader, box_files" differs from run to run -- every other section's is a constant)
 static void section(const char *name)
@@ -887,6 +987,8 @@ int main(int argc, char **argv)
     section("mask_transitions");
     pack_forms();
     section("pack_forms");
+    box_transitions();
+    section("box_transitions");
     fake_hip_trace_flush();
     fprintf(stderr, "drive: %d failed checks, %lld fake launches, trace hash %016llx\n", g_fail, fake_hip_launches(), fake_hip_trace_hash());
     return g_fail ? 1 : 0;
