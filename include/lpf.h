@@ -67,7 +67,9 @@ extern "C" {
                                          lpf_assign2d_params, lpf_assign2d_outputs, lpf_assign_2d (added; nothing else changed)
                                       8 (continued): lpf_first_match_input, lpf_first_match_outputs, lpf_first_match (added; nothing else
                                          changed)
-                                      8 (continued): lpf_rle_masks, lpf_set_masks_rle (added; nothing else changed) */
+                                      8 (continued): lpf_rle_masks, lpf_set_masks_rle (added; nothing else changed)
+                                      8 (continued): LPF_MASKS_U8 / _F32 / _RLE name lpf_wide_input.f32's values; 2 is new (no symbol, no
+                                         layout change; any other value is now refused) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -283,13 +285,14 @@ int lpf_set_masks_f32(lpf_ctx *ctx, const float *masks, int F, int M, int binari
  *   LPF_ERR_STATE before lpf_set_camera, and between lpf_graph_begin and lpf_graph_end (the run counts size the launch).  LPF_ERR_ARG:
  * in NULL, F < 0, M < 0, erode_iters < 0, reserved != 0, M > LPF_MAX_MASKS (lpf_set_masks_u8's message), run_off NULL with F * M > 0,
  * runs NULL with runs to read, F * M or the number of runs above 2^31 - 1, or runs that together cover more than 2^24 chunks of 1024 pixels.
- *   Not taken in this form: the wide calls (lpf_run_wide, lpf_run_frame_wide, lpf_run_cams*, lpf_depth_maps, lpf_first_match) and
- * lpf_inside_masks' own mask input keep their dense masks; runs are not resized (masks of another size than the camera's: decode them on
+ *   The passes that turn a lpf_wide_input into label bits -- lpf_run_wide, lpf_run_cams, lpf_run_cams_wide -- take this struct as their
+ * masks (LPF_MASKS_RLE, at lpf_wide_input; there M goes up to the pass's own limit).  Not taken in this form: lpf_run_frame_wide (device
+ * masks), lpf_depth_maps, lpf_first_match and lpf_inside_masks' own mask input keep their dense masks; runs are not resized (masks of another size than the camera's: decode them on
  * the host, lpf_resize_masks_u8); runs in device memory.  Masks that already sit on the GPU gain nothing from this form. */
 typedef struct lpf_rle_masks {
     const int32_t *runs;     /* host, [Rtot][2] {start, length}, Rtot = run_off[F*M] */
     const int64_t *run_off;  /* host, [F*M + 1] */
-    int32_t F, M;            /* 0 <= M <= LPF_MAX_MASKS */
+    int32_t F, M;            /* 0 <= M <= LPF_MAX_MASKS (as a lpf_wide_input's masks: that pass's limit) */
     int32_t erode_iters;     /* >= 0, with the context's element (lpf_set_erosion_element) */
     int32_t reserved;        /* 0 */
 } lpf_rle_masks;
@@ -367,12 +370,29 @@ int lpf_run_frame(lpf_ctx *ctx, const lpf_frame_job *job);
  * ones of lpf_set_camera.  It leaves the masks, boxes and rectangles of the narrow calls as they were.  Not capturable (LPF_ERR_STATE
  * between lpf_graph_begin and lpf_graph_end); with a software-pipelined mode on it first launches what the pipeline owes (no host
  * wait), then runs in order.  With device outputs the call only enqueues work; with host outputs it returns with them filled. */
+/* The forms of a lpf_wide_input's masks (its `f32` field).
+ *   LPF_MASKS_RLE: `masks` points to ONE lpf_rle_masks in host memory (its runs and run_off in host memory, as for lpf_set_masks_rle),
+ * whose F is the call's F, whose M is the input's M, whose erode_iters is the input's erode_iters and whose reserved is 0; on_device must
+ * be 0; rects and binarize are not read.  Pixel p of a run is y * W + x in the image the masks belong to: the context's (lpf_set_camera)
+ * for lpf_run_wide, cams[c].W, H for lpf_run_cams / lpf_run_cams_wide.  The runs are checked IN FULL on the host -- lpf_set_masks_rle's
+ * rules, limits and 64-bit sums, per camera against that camera's W * H -- before anything is enqueued for the call; a violation is
+ * LPF_ERR_ARG and the message names the call, the camera of a camera pass, and frame, mask and run.  The call waits for the copies of
+ * its tables before it returns (as it does for host masks): the caller may free the arrays at once.  Every output is bit for bit what
+ * the same call gives for the equivalent dense uint8 host masks (dense[f][m][p] = 1 iff p lies in any run of mask m) with the same
+ * erode_iters; the narrow state (masks, label image, rectangles, boxes) is left as it was.  The planes are zeroed, the runs are OR-ed
+ * into them on the GPU (integer ORs only) and every erosion iteration runs on the packed planes: no dense mask exists anywhere.
+ *   Taken by lpf_run_wide, lpf_run_cams and lpf_run_cams_wide.  lpf_depth_maps refuses it (LPF_ERR_ARG, before masks is read), as every
+ * call refuses an f32 other than these three; lpf_run_frame_wide's job has no such field: its masks are uint8 device memory. */
+#define LPF_MASKS_U8  0
+#define LPF_MASKS_F32 1
+#define LPF_MASKS_RLE 2
 typedef struct lpf_wide_input {
-    const void    *masks;          /* [F][M][H][W]: uint8 (nonzero = member) or float32 under `binarize` (lpf_set_masks_f32's rules) */
+    const void    *masks;          /* [F][M][H][W]: uint8 (nonzero = member) or float32 under `binarize` (lpf_set_masks_f32's rules);
+                                      LPF_MASKS_RLE: one lpf_rle_masks (host memory) */
     const int32_t *rects;          /* optional [F][M][4] {x0, y0, x1, y1}: lpf_set_mask_rects' contract (uint8, or float32 with
                                       binarize 0, and no erosion; ignored otherwise); in the same memory as the masks; or NULL */
     int32_t  M;
-    int32_t  f32;                  /* 0: uint8 masks, 1: float32 */
+    int32_t  f32;                  /* LPF_MASKS_U8 0: uint8 masks, LPF_MASKS_F32 1: float32, LPF_MASKS_RLE 2: run-length (above) */
     int32_t  binarize;             /* float32 masks: 0 / 1 / 2 as lpf_set_masks_f32 */
     int32_t  erode_iters;          /* cv2.erode iterations with the context's element (lpf_set_erosion_element; the cross by default), >= 0 */
     int32_t  on_device;            /* 0: masks (and rects) in host memory, copied by the call; else device memory lent until the
@@ -454,7 +474,8 @@ typedef struct lpf_cam_input {
     double         K[9];
     int32_t        W, H;
     double         depth_min_excl, depth_max_excl;
-    lpf_wide_input masks;                  /* [F][M][H][W] + optional rects [F][M][4], M <= LPF_MAX_MASKS (lpf_run_cams_wide: LPF_MAX_MASKS_WIDE) */
+    lpf_wide_input masks;                  /* [F][M][H][W] + optional rects [F][M][4], M <= LPF_MAX_MASKS (lpf_run_cams_wide: LPF_MAX_MASKS_WIDE);
+                                              or LPF_MASKS_RLE: runs in THIS camera's image, pixel = y * W + x with W, H above */
     const double  *corners_velo;           /* [Btot][8][3] velodyne-frame corners (lpf_set_boxes_ex), or NULL: no boxes */
     const int32_t *box_off;                /* [F + 1], host memory (with corners_velo) */
     int32_t        boxes_on_device;        /* 0 / 1 / 2 as lpf_set_boxes_ex's on_device */
@@ -959,7 +980,7 @@ typedef struct lpf_first_match_input {
                                  memory as masks */
     int32_t M;                /* 0 .. LPF_MAX_MASKS_WIDE, the same for every frame (pad with empty planes) */
     int32_t mh, mw;           /* the masks' own size, > 0 when M > 0 */
-    int32_t f32;              /* 0: uint8, 1: float32 */
+    int32_t f32;              /* 0: uint8, 1: float32 (anything else -- LPF_MASKS_RLE included: dense masks only -- is LPF_ERR_ARG) */
     int32_t on_device;        /* 0: host, copied by the call; else device memory lent until the work has completed */
     int32_t reserved;
 } lpf_first_match_input;

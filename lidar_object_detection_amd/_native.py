@@ -225,6 +225,33 @@ def wide_mask_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype"
     return masks, M, is_f, dev, rects
 
 
+LPF_MASKS_U8, LPF_MASKS_F32, LPF_MASKS_RLE = 0, 1, 2           # lpf_wide_input.f32 (include/lpf.h)
+
+
+def wide_rle_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", max_masks=LPF_MAX_MASKS_WIDE, who="run_wide"):
+    """The run-length form of a pass's masks -- one rle.RleMasks, or a list with one per frame -- checked before anything reaches the
+    GPU, in the shape wide_mask_batch returns: ``((runs, run_off, RleMasksInput), M, "rle", False, None)``; None when ``masks`` are not
+    in that form.  Ragged M is padded with empty masks.  ValueError: a list that mixes RleMasks and arrays, another size than H x W,
+    ``rects`` (runs need none), a ``binarize`` other than the default, more than max_masks masks, another frame count than F."""
+    from .rle import RleMasks
+    if not isinstance(masks, RleMasks):
+        if not isinstance(masks, (list, tuple)) or not any(isinstance(m, RleMasks) for m in masks):
+            return None
+        if not all(isinstance(m, RleMasks) for m in masks):
+            raise ValueError("%s: the list mixes RleMasks and arrays: one form per call (.to_dense() or RleMasks.from_dense)" % who)
+    if rects is not None:
+        raise ValueError("%s: rects given with RleMasks (the runs say where the masks are)" % who)
+    if binarize != "astype":
+        raise ValueError("%s: binarize=%r with RleMasks (a pixel is a member or it is not)" % (who, binarize))
+    if int(erode_iters) != erode_iters or erode_iters < 0:
+        raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
+    runs, run_off, Fr, M = LpfContext.rle_batch(masks, H, W, max_masks, who)
+    if Fr != F:
+        raise ValueError("%s: RleMasks for %d frames, the batch has %d" % (who, Fr, F))
+    inp = RleMasksInput(runs.ctypes.data if len(runs) else None, run_off.ctypes.data, F, M, int(erode_iters), 0)
+    return (runs, run_off, inp), M, "rle", False, None
+
+
 class FrameJob(ctypes.Structure):
     """lpf_frame_job (include/lpf.h): one frame of a stream -- scan, masks + rectangles, cam-0 box corners, outputs -- for lpf_run_frame"""
     _fields_ = [("pts", _P), ("n_points", _I64), ("masks", _P), ("mask_rects", _P), ("corners_cam0", _P), ("T_cam_to_velo", _P),
@@ -884,25 +911,26 @@ class LpfContext:
         self.F_masks, self.M = F, M
 
     @staticmethod
-    def rle_batch(frames_masks, H, W):
+    def rle_batch(frames_masks, H, W, max_masks=LPF_MAX_MASKS, who="set_masks_rle"):
         """``(runs int32 [Rtot,2], run_off int64 [F*M + 1], F, M)`` of one RleMasks or a list of them, one per frame, as lpf_set_masks_rle
-        takes them: frames with fewer masks than the largest are padded with empty masks.  ValueError -- before any native call -- for
-        anything that is not an RleMasks, a size other than H x W, more than LPF_MAX_MASKS masks, and runs of another dtype or shape or
-        out of bounds (they are checked again here: the fields of an RleMasks can be assigned)."""
+        -- or a pass that takes up to ``max_masks`` run-length masks per frame (run_wide, run_cams, run_cams_wide) -- takes them: frames
+        with fewer masks than the largest are padded with empty masks.  ValueError -- before any native call, with ``who`` as the
+        message's prefix -- for anything that is not an RleMasks, a size other than H x W, more than max_masks masks, and runs of another
+        dtype or shape or out of bounds (they are checked again here: the fields of an RleMasks can be assigned)."""
         from .rle import RleMasks, check_runs
         frames = [frames_masks] if isinstance(frames_masks, RleMasks) else list(frames_masks)
         for f, r in enumerate(frames):
             if not isinstance(r, RleMasks):
-                raise ValueError("set_masks_rle: frame %d is %s, not RleMasks" % (f, type(r).__name__))
+                raise ValueError("%s: frame %d is %s, not RleMasks" % (who, f, type(r).__name__))
             if tuple(r.shape[1:]) != (H, W):
-                raise ValueError("set_masks_rle: frame %d has masks of %d x %d, the camera is %d x %d (runs are not resized)"
-                                 % (f, r.shape[2], r.shape[1], W, H))
-            if r.shape[0] > LPF_MAX_MASKS:
-                raise ValueError("set_masks_rle: frame %d has %d masks, one pass takes %d (pipeline.run_frames groups them)"
-                                 % (f, r.shape[0], LPF_MAX_MASKS))
+                raise ValueError("%s: frame %d has masks of %d x %d, the camera is %d x %d (runs are not resized)"
+                                 % (who, f, r.shape[2], r.shape[1], W, H))
+            if r.shape[0] > max_masks:
+                raise ValueError("%s: frame %d has %d masks, one pass takes %d (pipeline.run_frames groups them)"
+                                 % (who, f, r.shape[0], max_masks))
         F = len(frames)
         M = max([r.shape[0] for r in frames], default=0)
-        checked = [check_runs(r.runs, r.run_off, r.shape[0], H * W, "set_masks_rle: frame %d" % f) for f, r in enumerate(frames)]
+        checked = [check_runs(r.runs, r.run_off, r.shape[0], H * W, "%s: frame %d" % (who, f)) for f, r in enumerate(frames)]
         run_off = np.zeros(F * M + 1, np.int64)
         base = 0
         for f, (runs, off) in enumerate(checked):
@@ -1262,7 +1290,8 @@ class LpfContext:
             if masks is None:
                 masks = np.zeros((F, 0, H, W), np.uint8)
             erode = cam.get("erode_iters", 0)
-            batch = wide_mask_batch(masks, F, H, W, cam.get("rects"), erode, binarize, self.BINARIZE)
+            batch = wide_rle_batch(masks, F, H, W, cam.get("rects"), erode, binarize, max_masks, "%s: camera %d" % (who, k)) or \
+                wide_mask_batch(masks, F, H, W, cam.get("rects"), erode, binarize, self.BINARIZE)
             masks, M, rects = batch[0], batch[1], batch[4]
             if M > max_masks:
                 raise ValueError("camera %d has %d masks per frame: a multi-camera pass takes at most %d per camera (run_wide takes more)"
@@ -1298,7 +1327,9 @@ class LpfContext:
         run_batch's ``frames``: host arrays, Scans of a ScanReader, float32 [N,4] GPU tensors) and read once by the GPU.
         cams: one dict per camera --
           T_velo_to_rect  4x4, K  (3x3 or larger), width, height, depth_min (0.0), depth_max (50.0)  -- set_camera's arguments
-          masks           [M,H,W] (one frame) or [F,M,H,W], uint8 / bool or float32, NumPy or a contiguous GPU tensor, M <= 32; or None
+          masks           [M,H,W] (one frame) or [F,M,H,W], uint8 / bool or float32, NumPy or a contiguous GPU tensor, M <= 32; or None;
+                          or run-length: one rle.RleMasks, or a list with one per frame, at THIS camera's size (no rects, default
+                          binarize; decoded on the GPU) -- cameras with dense masks and cameras with RleMasks may share a pass
           binarize        float masks: "astype" (default), "v3" or "gt0.5" (set_masks'); v3_pipeline=True means "v3"
           erode_iters     (0), rects: the optional [F,M,4] hint of set_mask_rects (where the masks are)
           boxes           one f64 [B_f,8,3] array of velodyne-frame corners per frame (set_boxes'), or None; oriented (True)
@@ -1343,6 +1374,10 @@ class LpfContext:
         """Fills the lpf_wide_input ``inp`` from what wide_mask_batch returned (``batch``, which must stay alive until the call has
         returned); masks on the GPU were produced on torch's stream, so the call is ordered after it."""
         masks, M, is_f, mdev, rects = batch
+        if is_f == "rle":                                    # wide_rle_batch's: one lpf_rle_masks in host memory (no M = 0 shortcut: the struct says so itself)
+            inp.masks, inp.rects = ctypes.addressof(masks[2]), None
+            inp.M, inp.f32, inp.binarize, inp.erode_iters, inp.on_device = M, LPF_MASKS_RLE, 0, int(erode_iters), 0
+            return
         if mdev:
             import torch
             self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
@@ -1356,7 +1391,10 @@ class LpfContext:
         """Frames with up to 256 masks each in ONE native pass (lpf_run_wide): every point is projected and read once.
         frames: as run_batch's -- f32[N_f,4] host arrays, Scans of a ScanReader (read in HBM where they are), float32 [N,4] GPU
         tensors.  masks: [M,H,W] or [F,M,H,W] (uint8 / bool, or
-        float32 under ``binarize`` as set_masks), host or GPU (lent until the call returns: it waits for its results).  rects: the
+        float32 under ``binarize`` as set_masks), host or GPU (lent until the call returns: it waits for its results); or in run-length
+        form -- one rle.RleMasks, or a list with one per frame (ragged M is padded with empty masks), at the camera's size, without
+        ``rects`` and under the default ``binarize``: the runs are decoded into the label planes on the GPU, nothing dense crosses to the
+        device, and every result equals the one ``.to_dense()`` masks give.  rects: the
         optional [F,M,4] hint of set_mask_rects.  Boxes and camera are the ones in force; the masks, boxes and rectangles of the
         narrow calls are left as they are.  Returns one dict per frame with what run_batch returns -- inst_count, best_box,
         best_cnt of length M, count_mb [M, B_f] -- plus label_words [N_f, LW] (bit b of word w = mask 32 w + b; LW = ceil(M / 32)),
@@ -1366,7 +1404,8 @@ class LpfContext:
         F = len(frames)
         if F == 0:
             raise ValueError("no frames")
-        batch = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
+        batch = wide_rle_batch(masks, F, self.H, self.W, rects, erode_iters, binarize) or \
+            wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
         M = batch[1]
         off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the run returns)
         n = int(off[-1])

@@ -107,6 +107,14 @@ struct lpf_ctx {
     DevBuf mask_stage;
     DevBuf rle_stage;                 // lpf_set_masks_rle: [runs | work units | run_off] of the call being decoded
     std::vector<int2> rle_units;      // ... its work units while the host emits them (kept for its capacity)
+    // run-length masks of a wide or multi-camera pass (LPF_MASKS_RLE): the checked input and its work units, one record per camera
+    // (lpf_run_wide: record 0) -- host storage of its own for every camera until the call's host wait; the tables are staged in the
+    // pass's own buffers (Wide::rle, Cams::rle), never in rle_stage
+    struct RleIn {
+        const lpf_rle_masks *in = nullptr;        // NULL: this camera's masks are dense (or there are none)
+        long long Rtot = 0;
+        std::vector<int2> units;
+    } rle_in[LPF_NSETS];
     // Masks that are set but not packed (no erosion; the next lpf_run* decides, plan_tile_source).  Left by lpf_set_masks_* of a serial
     // context -- host masks in mask_stage, or device masks the caller lends (on_device 2): a launch of sparse frames reads them directly,
     // anything else packs them first -- or of a pipelined one (lent masks only): a fused launch of sparse frames reads them directly, a
@@ -283,10 +291,10 @@ struct lpf_ctx {
     std::vector<char> h_tab;          // [frames | segs | blks] being built
 
     // lpf_run_wide: its own buffers (the narrow masks, label images and staging stay as they are)
-    struct Wide { DevBuf tab, masks, rects, planes_a, planes_b, flags, ccnt, cpre, fcnt, midx, mwords, mpts, cnt, pts, out; } wide;
+    struct Wide { DevBuf tab, masks, rects, rle, planes_a, planes_b, flags, ccnt, cpre, fcnt, midx, mwords, mpts, cnt, pts, out; } wide;
     // lpf_run_cams: camera c's box tables, label images, staged masks / rectangles and host-output staging (grow-only, allocated on
     // first use); its counters and geometry tables are scratch set c's
-    struct Cams { BoxSet bx[LPF_NSETS]; DevBuf label_a[LPF_NSETS], label_b[LPF_NSETS], masks[LPF_NSETS], rects[LPF_NSETS], out[LPF_NSETS], pts; } cams;
+    struct Cams { BoxSet bx[LPF_NSETS]; DevBuf label_a[LPF_NSETS], label_b[LPF_NSETS], masks[LPF_NSETS], rects[LPF_NSETS], rle[LPF_NSETS], out[LPF_NSETS], pts; } cams;
     // lpf_run_cams_wide: camera c's lpf_run_wide buffers (cam[c]: staged masks, planes, scratch, host-output staging), the pass's frame
     // tables and staged points (grow-only, allocated on first use); its box tables are lpf_run_cams' (cams.bx[c])
     struct CamsWide { Wide cam[LPF_NSETS]; DevBuf tab, pts; } camsw;
@@ -1219,6 +1227,65 @@ int plan_tile_source(lpf_ctx *c, bool fused, bool small, bool sparse_frames, int
     return LPF_OK;
 }
 
+// ---- run-length masks: the walk and the staging that lpf_set_masks_rle and the wide / multi-camera passes share --------------------
+
+// The walk of a lpf_rle_masks for an image of hw pixels: every check of include/lpf.h, in 64 bits, and the emission of the decode's work
+// units {run, first pixel} (lpf_rle.hip.h) into `units`.  Nothing is enqueued.  who: the messages' prefix -- "lpf_set_masks_rle", or a
+// pass's "run_wide" / "run_cams_wide: camera 1"
+int rle_walk(lpf_ctx *c, const char *who, const lpf_rle_masks *in, long long hw, std::vector<int2> &units, long long *Rtot_out)
+{
+    const int F = in->F, M = in->M;
+    units.clear();
+    *Rtot_out = 0;
+    if (F < 0 || M < 0 || in->erode_iters < 0 || in->reserved != 0)
+        return fail(c, LPF_ERR_ARG, "%s: F=%d M=%d erode_iters=%d reserved=%d", who, F, M, in->erode_iters, in->reserved);
+    const long long FM = (long long)F * M;
+    if (FM > 0x7fffffffll) return fail(c, LPF_ERR_ARG, "%s: F * M = %lld masks (at most 2^31 - 1 in one call)", who, FM);
+    if (FM == 0) return LPF_OK;
+    const int64_t *off = in->run_off;
+    if (!off) return fail(c, LPF_ERR_ARG, "%s: run_off=NULL with F=%d M=%d", who, F, M);
+    if (off[0] != 0) return fail(c, LPF_ERR_ARG, "%s: run_off[0]=%lld (must be 0)", who, (long long)off[0]);
+    for (long long k = 0; k < FM; ++k)
+        if (off[k + 1] < off[k])
+            return fail(c, LPF_ERR_ARG, "%s: run_off decreases at frame %lld mask %lld (%lld after %lld)", who, k / M, k % M,
+                        (long long)off[k + 1], (long long)off[k]);
+    const long long Rtot = off[FM];
+    if (Rtot > 0x7fffffffll) return fail(c, LPF_ERR_ARG, "%s: %lld runs (at most 2^31 - 1 in one call)", who, Rtot);
+    if (Rtot > 0 && !in->runs) return fail(c, LPF_ERR_ARG, "%s: runs=NULL with %lld runs", who, Rtot);
+    for (long long k = 0; k < FM; ++k)
+        for (long long r = off[k]; r < off[k + 1]; ++r) {
+            const long long start = in->runs[2 * r], length = in->runs[2 * r + 1];
+            if (start < 0 || length < 0 || start + length > hw)
+                return fail(c, LPF_ERR_ARG, "%s: frame %lld mask %lld run %lld: start=%lld length=%lld (0 <= start, 0 <= length, "
+                                            "start + length <= W*H = %lld)", who, k / M, k % M, r - off[k], start, length, hw);
+            for (long long p = start; p < start + length; p += LPF_RLE_CHUNK) units.push_back(int2{(int)r, (int)p});
+            if (units.size() > LPF_RLE_MAX_UNITS)
+                return fail(c, LPF_ERR_ARG, "%s: the runs cover more than 2^24 chunks of %d pixels (frame %lld mask %lld run %lld): "
+                                            "set fewer frames per call", who, LPF_RLE_CHUNK, k / M, k % M, r - off[k]);
+        }
+    *Rtot_out = Rtot;
+    return LPF_OK;
+}
+
+// [runs | units | run_off] of a walked lpf_rle_masks with units (rle_walk), copied into `stage` in stream order -> the decode's job for
+// an image of hw pixels, and its grid.  The caller owes a host_wait before `in`'s arrays and `units` may change
+int rle_stage_tables(lpf_ctx *c, DevBuf &stage, const lpf_rle_masks *in, const std::vector<int2> &units, long long Rtot, long long hw,
+                     LpfRleJob &J, unsigned *nblocks)
+{
+    const long long FM = (long long)in->F * in->M;
+    const size_t b_runs = align256((size_t)Rtot * sizeof(int2)), b_units = align256(units.size() * sizeof(int2)), b_off = (size_t)(FM + 1) * 8;
+    int rc;
+    if ((rc = reserve(c, stage, b_runs + b_units + b_off))) return rc;
+    char *d = (char *)stage.p;
+    LPF_HIP(c, hipMemcpyAsync(d, in->runs, (size_t)Rtot * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+    LPF_HIP(c, hipMemcpyAsync(d + b_runs, units.data(), units.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+    LPF_HIP(c, hipMemcpyAsync(d + b_runs + b_units, in->run_off, b_off, hipMemcpyHostToDevice, c->stream));
+    J.runs = (const int2 *)d; J.units = (const int2 *)(d + b_runs); J.run_off = (const long long *)(d + b_runs + b_units);
+    J.hw = hw; J.n_units = (int)units.size(); J.M = in->M; J.FM = (int)FM;
+    *nblocks = (unsigned)((units.size() + LPF_RLE_BLOCK / 64 - 1) / (LPF_RLE_BLOCK / 64));
+    return LPF_OK;
+}
+
 // ---- setup the run paths share ---------------------------------------------------------------------------------------------------
 
 // frame_off[0..F] (not NULL, F > 0: the caller's checks) starts at 0 and has frames of 0 .. 0x7fffffff - slack points; pts is given if
@@ -1234,18 +1301,47 @@ int check_frames(lpf_ctx *c, const char *who, const float *pts, const int64_t *f
     return LPF_OK;
 }
 
-// a lpf_wide_input: 0 .. max_M masks per frame ("... M=<M> masks per frame, <takes> = <max_M><more>"), erosion, binarisation, masks
-// given if M > 0.  who: the messages' prefix; cam >= 0: the input of that camera of a multi-camera pass
-int check_wide_input(lpf_ctx *c, const char *who, int cam, const lpf_wide_input &m, int max_M, const char *takes, const char *more)
+// a lpf_wide_input: 0 .. max_M masks per frame ("... M=<M> masks per frame, <takes> = <max_M><more>"), its form (f32: LPF_MASKS_U8 /
+// _F32 / _RLE and nothing else; the run-length form only where the call takes it -- takes_rle -- and then in host memory), erosion,
+// binarisation, masks given if M > 0.  Nothing behind m.masks is read.  who: the messages' prefix; cam >= 0: the input of that camera
+// of a multi-camera pass
+int check_wide_input(lpf_ctx *c, const char *who, int cam, const lpf_wide_input &m, int max_M, const char *takes, const char *more,
+                     bool takes_rle = false)
 {
     if (m.M < 0 || m.M > max_M) {
         if (cam < 0) return fail(c, LPF_ERR_ARG, "%s: M=%d masks per frame, %s = %d%s", who, m.M, takes, max_M, more);
         return fail(c, LPF_ERR_ARG, "%s: camera %d has M=%d masks per frame, %s = %d%s", who, cam, m.M, takes, max_M, more);
     }
-    if (m.erode_iters < 0 || (m.f32 && (m.binarize < 0 || m.binarize > 2)) || (m.M > 0 && !m.masks)) {
-        if (cam < 0) return fail(c, LPF_ERR_ARG, "%s: erode_iters=%d f32=%d binarize=%d masks=%p", who, m.erode_iters, m.f32, m.binarize, m.masks);
-        return fail(c, LPF_ERR_ARG, "%s: camera %d: erode_iters=%d f32=%d binarize=%d masks=%p", who, cam, m.erode_iters, m.f32, m.binarize, m.masks);
-    }
+    char w[96];
+    if (cam < 0) snprintf(w, sizeof w, "%s", who); else snprintf(w, sizeof w, "%s: camera %d", who, cam);
+    if (m.f32 != LPF_MASKS_U8 && m.f32 != LPF_MASKS_F32 && m.f32 != LPF_MASKS_RLE)
+        return fail(c, LPF_ERR_ARG, "%s: f32=%d (LPF_MASKS_U8 = 0, LPF_MASKS_F32 = 1 or LPF_MASKS_RLE = 2)", w, m.f32);
+    if (m.f32 == LPF_MASKS_RLE && !takes_rle)
+        return fail(c, LPF_ERR_ARG, "%s: f32=LPF_MASKS_RLE: lpf_%s takes dense masks only (run-length masks: lpf_run_wide, lpf_run_cams, "
+                                    "lpf_run_cams_wide)", w, who);
+    if (m.f32 == LPF_MASKS_RLE && m.on_device != 0)
+        return fail(c, LPF_ERR_ARG, "%s: f32=LPF_MASKS_RLE with on_device=%d: run-length masks are host memory (on_device 0)", w, m.on_device);
+    if (m.erode_iters < 0 || (m.f32 == LPF_MASKS_F32 && (m.binarize < 0 || m.binarize > 2)) || (m.M > 0 && !m.masks))
+        return fail(c, LPF_ERR_ARG, "%s: erode_iters=%d f32=%d binarize=%d masks=%p", w, m.erode_iters, m.f32, m.binarize, m.masks);
+    return LPF_OK;
+}
+
+// The run-length masks of a lpf_wide_input that check_wide_input let through, for a pass of F frames on an image of hw pixels: the
+// struct must describe this call (F, M, erode_iters), then lpf_set_masks_rle's walk with the call's prefix (and camera).  R: the checked
+// input and its work units (R.in stays NULL for dense masks, and where there is no struct to read).  Nothing is enqueued
+int check_wide_rle(lpf_ctx *c, const char *who, int cam, const lpf_wide_input &m, int F, long long hw, lpf_ctx::RleIn &R)
+{
+    R.in = nullptr; R.Rtot = 0; R.units.clear();
+    if (m.f32 != LPF_MASKS_RLE || !m.masks) return LPF_OK;
+    char w[96];
+    if (cam < 0) snprintf(w, sizeof w, "%s", who); else snprintf(w, sizeof w, "%s: camera %d", who, cam);
+    const lpf_rle_masks *in = (const lpf_rle_masks *)m.masks;
+    if (in->F != F || in->M != m.M || in->erode_iters != m.erode_iters)
+        return fail(c, LPF_ERR_ARG, "%s: the run-length masks say F=%d M=%d erode_iters=%d, the call has F=%d M=%d erode_iters=%d", w, in->F,
+                    in->M, in->erode_iters, F, m.M, m.erode_iters);
+    int rc;
+    if ((rc = rle_walk(c, w, in, hw, R.units, &R.Rtot))) return rc;
+    R.in = in;
     return LPF_OK;
 }
 
@@ -1614,12 +1710,12 @@ void lpf_destroy(lpf_ctx *c)
             for (DevBuf *b : bb) release(*b);
         }
     for (int k = 0; k < LPF_NSETS; ++k) {
-        DevBuf *cb[] = {&c->cams.label_a[k], &c->cams.label_b[k], &c->cams.masks[k], &c->cams.rects[k], &c->cams.out[k]};
+        DevBuf *cb[] = {&c->cams.label_a[k], &c->cams.label_b[k], &c->cams.masks[k], &c->cams.rects[k], &c->cams.rle[k], &c->cams.out[k]};
         for (DevBuf *b : cb) release(*b);
     }
     release(c->cams.pts);
     for (lpf_ctx::Wide *D : {&c->wide, &c->camsw.cam[0], &c->camsw.cam[1], &c->camsw.cam[2], &c->camsw.cam[3]}) {
-        DevBuf *wb[] = {&D->tab, &D->masks, &D->rects, &D->planes_a, &D->planes_b, &D->flags, &D->ccnt, &D->cpre, &D->fcnt, &D->midx, &D->mwords,
+        DevBuf *wb[] = {&D->tab, &D->masks, &D->rects, &D->rle, &D->planes_a, &D->planes_b, &D->flags, &D->ccnt, &D->cpre, &D->fcnt, &D->midx, &D->mwords,
                         &D->mpts, &D->cnt, &D->pts, &D->out};
         for (DevBuf *b : wb) release(*b);
     }
@@ -1874,39 +1970,12 @@ int lpf_set_masks_rle(lpf_ctx *c, const lpf_rle_masks *in)
     if (in->M > LPF_MAX_MASKS) return too_many_masks(c, in->M);
     const int F = in->F, M = in->M;
     int erode_iters = in->erode_iters;
-    if (F < 0 || M < 0 || erode_iters < 0 || in->reserved != 0)
-        return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: F=%d M=%d erode_iters=%d reserved=%d", F, M, erode_iters, in->reserved);
     const long long hw = (long long)c->H * c->W;
-    const long long FM = (long long)F * M;
-    if (FM > 0x7fffffffll) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: F * M = %lld masks (at most 2^31 - 1 in one call)", FM);
     long long Rtot = 0;
     std::vector<int2> &units = c->rle_units;
-    units.clear();
-    if (FM > 0) {
-        const int64_t *off = in->run_off;
-        if (!off) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: run_off=NULL with F=%d M=%d", F, M);
-        if (off[0] != 0) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: run_off[0]=%lld (must be 0)", (long long)off[0]);
-        for (long long k = 0; k < FM; ++k)
-            if (off[k + 1] < off[k])
-                return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: run_off decreases at frame %lld mask %lld (%lld after %lld)", k / M, k % M,
-                            (long long)off[k + 1], (long long)off[k]);
-        Rtot = off[FM];
-        if (Rtot > 0x7fffffffll) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: %lld runs (at most 2^31 - 1 in one call)", Rtot);
-        if (Rtot > 0 && !in->runs) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: runs=NULL with %lld runs", Rtot);
-        for (long long k = 0; k < FM; ++k)
-            for (long long r = off[k]; r < off[k + 1]; ++r) {
-                const long long start = in->runs[2 * r], length = in->runs[2 * r + 1];
-                if (start < 0 || length < 0 || start + length > hw)
-                    return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: frame %lld mask %lld run %lld: start=%lld length=%lld (0 <= start, 0 <= length, "
-                                                "start + length <= W*H = %lld)", k / M, k % M, r - off[k], start, length, hw);
-                for (long long p = start; p < start + length; p += LPF_RLE_CHUNK) units.push_back(int2{(int)r, (int)p});
-                if (units.size() > LPF_RLE_MAX_UNITS)
-                    return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: the runs cover more than 2^24 chunks of %d pixels (frame %lld mask %lld run %lld): "
-                                                "set fewer frames per call", LPF_RLE_CHUNK, k / M, k % M, r - off[k]);
-            }
-    }
-    // from here on: set_masks_impl with host masks (not per scratch set: what a pipelined context owes is drained first)
     int rc;
+    if ((rc = rle_walk(c, "lpf_set_masks_rle", in, hw, units, &Rtot))) return rc;
+    // from here on: set_masks_impl with host masks (not per scratch set: what a pipelined context owes is drained first)
     if (c->pipe.owes() && (rc = sync_all(c))) return rc;
     lpf_ctx::Masks &MK = c->masks;
     lpf_ctx::Scratch &S = c->sc[c->pipe.set_now()];
@@ -1921,16 +1990,9 @@ int lpf_set_masks_rle(lpf_ctx *c, const lpf_rle_masks *in)
     LPF_HIP(c, hipMemsetAsync(S.label_a.p, 0, (size_t)F * hw * lb, c->stream));
     void *cur = S.label_a.p;
     if (!units.empty()) {
-        const size_t b_runs = align256((size_t)Rtot * sizeof(int2)), b_units = align256(units.size() * sizeof(int2)), b_off = (size_t)(FM + 1) * 8;
-        if ((rc = reserve(c, c->rle_stage, b_runs + b_units + b_off))) return rc;
-        char *d = (char *)c->rle_stage.p;
-        LPF_HIP(c, hipMemcpyAsync(d, in->runs, (size_t)Rtot * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-        LPF_HIP(c, hipMemcpyAsync(d + b_runs, units.data(), units.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-        LPF_HIP(c, hipMemcpyAsync(d + b_runs + b_units, in->run_off, b_off, hipMemcpyHostToDevice, c->stream));
         LpfRleJob J;
-        J.runs = (const int2 *)d; J.units = (const int2 *)(d + b_runs); J.run_off = (const long long *)(d + b_runs + b_units);
-        J.hw = hw; J.n_units = (int)units.size(); J.M = M; J.FM = (int)FM;
-        const unsigned nb = (unsigned)((units.size() + LPF_RLE_BLOCK / 64 - 1) / (LPF_RLE_BLOCK / 64));
+        unsigned nb = 0;
+        if ((rc = rle_stage_tables(c, c->rle_stage, in, units, Rtot, hw, J, &nb))) return rc;
         if (c->erode_k == 1) erode_iters = 0;              // (the 1 x 1 element: any number of iterations is the identity)
         rc = with_label(lb, [&](auto lt) -> int {
             typedef typename decltype(lt)::type LT;
@@ -2581,13 +2643,43 @@ int lpf_profile_read(lpf_ctx *c, double *k1_ms_sum, int64_t *k1_launches, int re
 
 // masks (host masks are staged into D; device masks are lent) -> LW planes in D (+ erosion); W.planes = the result (NULL: no masks).
 // *host_in: the masks were read from host memory
-static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int F, int Wimg, int Himg, LpfWideParams &W, bool *host_in)
+// R: the input's checked run-length masks (check_wide_rle; R->in NULL, or no R: dense masks)
+static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int F, int Wimg, int Himg, LpfWideParams &W, bool *host_in,
+                     const lpf_ctx::RleIn *R = nullptr)
 {
     int rc;
     const int M = in->M, LW = (M + 31) / 32;
     const size_t hw = (size_t)Wimg * Himg;
     W.planes = nullptr;
-    if (M > 0) {
+    if (M > 0 && R && R->in) {
+        // ---- run-length masks: zero ALL the planes (the bits above M of a frame's last word stay zero, as the dense pack leaves them),
+        //      OR the runs in (lpf_rle_decode_wide), then every erosion iteration on the packed planes.  No dense mask is staged
+        if ((rc = reserve(c, D.planes_a, (size_t)F * LW * hw * 4))) return rc;
+        uint32_t *cur = (uint32_t *)D.planes_a.p;
+        LPF_HIP(c, hipMemsetAsync(cur, 0, (size_t)F * LW * hw * 4, c->stream));
+        if (!R->units.empty()) {                          // (no units: the planes are zero, and erosion keeps them so)
+            LpfRleJob J;
+            unsigned nb = 0;
+            if ((rc = rle_stage_tables(c, D.rle, R->in, R->units, R->Rtot, (long long)hw, J, &nb))) return rc;
+            *host_in = true;
+            hipLaunchKernelGGL(lpf_rle_decode_wide, dim3(nb), dim3(LPF_RLE_BLOCK), 0, c->stream, J, LW, cur);
+            LPF_HIP(c, hipGetLastError());
+            const int iters = c->erode_k == 1 ? 0 : in->erode_iters;      // (the 1 x 1 element: the identity)
+            if (iters > 0) {
+                const bool element = c->erode_k != 3;
+                const dim3 grid((Wimg + LPF_TW - 1) / LPF_TW, (Himg + LPF_TH - 1) / LPF_TH, (unsigned)(F * LW));
+                if ((rc = reserve(c, D.planes_b, (size_t)F * LW * hw * 4))) return rc;
+                uint32_t *other = (uint32_t *)D.planes_b.p;
+                for (int it = 0; it < iters; ++it) {
+                    if (element) hipLaunchKernelGGL((lpf_erode_packed_k<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, Himg, Wimg, c->erode_r, c->erode_spans);
+                    else hipLaunchKernelGGL((lpf_erode_packed<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, Himg, Wimg);
+                    LPF_HIP(c, hipGetLastError());
+                    std::swap(cur, other);
+                }
+            }
+        }
+        W.planes = cur;
+    } else if (M > 0) {
         const void *d_masks = nullptr;
         const int4 *rects = nullptr;
         if ((rc = stage_masks(c, *in, F, hw, D.masks, D.rects, &d_masks, &rects, host_in))) return rc;
@@ -2674,8 +2766,10 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     if ((rc = enter(c, "lpf_run_wide", true))) return rc;
     if (!in || !out || !frame_off || F <= 0) return fail(c, LPF_ERR_ARG, "run_wide: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
     const int M = in->M;
-    if ((rc = check_wide_input(c, "run_wide", -1, *in, LPF_MAX_MASKS_WIDE, "lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE", ""))) return rc;
+    if ((rc = check_wide_input(c, "run_wide", -1, *in, LPF_MAX_MASKS_WIDE, "lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE", "", true))) return rc;
     if ((rc = check_frames(c, "run_wide", pts, frame_off, F, LPF_WIDE_CHUNK))) return rc;
+    lpf_ctx::RleIn &R = c->rle_in[0];                      // run-length masks: checked in full here, before anything is enqueued
+    if ((rc = check_wide_rle(c, "run_wide", -1, *in, F, (long long)c->W * c->H, R))) return rc;
     const int64_t Ntot = frame_off[F];
     if (out->inst_idx && out->inst_cap <= 0) return fail(c, LPF_ERR_ARG, "run_wide: inst_idx given with inst_cap=%lld", (long long)out->inst_cap);
     lpf_ctx::BoxSet &BX = c->boxes.in_force();
@@ -2705,7 +2799,7 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     bool pts_in = false, masks_in = false;
     if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, 0, n, n, &W.pts, &pts_in))) return rc;
     if (direct) W.planes = nullptr;
-    else if ((rc = wide_pack(c, D, in, F, c->W, c->H, W, &masks_in))) return rc;
+    else if ((rc = wide_pack(c, D, in, F, c->W, c->H, W, &masks_in, &R))) return rc;
 
     // ---- buffers: the caller's device pointers, or staging for host callers ---------------------------------------------------
     const size_t nMB = (size_t)M * Btot;
@@ -3493,6 +3587,8 @@ int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int 
     const int M = in->M;
     if (M < 0 || M > LPF_MAX_MASKS_WIDE)
         return fail(c, LPF_ERR_ARG, "first_match: M=%d masks per frame, lpf_first_match takes 0 .. LPF_MAX_MASKS_WIDE = %d", M, LPF_MAX_MASKS_WIDE);
+    if (in->f32 != LPF_MASKS_U8 && in->f32 != LPF_MASKS_F32)
+        return fail(c, LPF_ERR_ARG, "first_match: f32=%d (LPF_MASKS_U8 = 0 or LPF_MASKS_F32 = 1: lpf_first_match takes dense masks only)", in->f32);
     if (M > 0 && (!in->masks || in->mh <= 0 || in->mw <= 0))
         return fail(c, LPF_ERR_ARG, "first_match: masks=%p mh=%d mw=%d (with M > 0 masks is required and mh, mw are > 0)", in->masks, in->mh, in->mw);
     if (out->car_rgb && !in->colors) return fail(c, LPF_ERR_ARG, "first_match: car_rgb is asked for, colors is NULL");
@@ -3619,7 +3715,8 @@ static int cams_check(lpf_ctx *c, const char *who, const float *pts, const int64
         const lpf_cam_input &I = cams[k];
         if (I.W <= 0 || I.H <= 0 || (long long)I.W * I.H > (1ll << 30))
             return fail(c, LPF_ERR_ARG, "%s: camera %d is %d x %d", w, k, I.W, I.H);
-        if ((rc = check_wide_input(c, w, k, I.masks, max_M, takes, more))) return rc;
+        if ((rc = check_wide_input(c, w, k, I.masks, max_M, takes, more, true))) return rc;
+        if ((rc = check_wide_rle(c, w, k, I.masks, F, (long long)I.W * I.H, c->rle_in[k]))) return rc;
         if (I.corners_velo) {
             if (!I.box_off || I.box_off[0] != 0) return fail(c, LPF_ERR_ARG, "%s: camera %d: box_off must be given and start at 0", w, k);
             for (int f = 0; f < F; ++f)
@@ -3683,6 +3780,32 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         const lpf_wide_input &m = I.masks;
         if (m.M == 0) continue;
         const size_t hw = (size_t)I.W * I.H;
+        const lpf_ctx::RleIn &R = c->rle_in[k];
+        if (R.in) {
+            // run-length masks: lpf_set_masks_rle's zero + decode (+ erosion on the packed image) at the pass's element width, into
+            // this camera's label image -- reserved, like every label image, at 4 bytes per pixel: the decode's 32-bit atomics on the
+            // last, partial word of an image of 1- or 2-byte elements stay inside it (lpf_rle.hip.h)
+            DevBuf &la = c->cams.label_a[k];
+            if ((rc = reserve(c, la, (size_t)F * hw * 4))) return rc;
+            LPF_HIP(c, hipMemsetAsync(la.p, 0, (size_t)F * hw * lb_all, c->stream));
+            label_img[k] = la.p;
+            if (R.units.empty()) continue;                 // (the image is zero, and erosion keeps it so)
+            LpfRleJob J;
+            unsigned nb = 0;
+            if ((rc = rle_stage_tables(c, c->cams.rle[k], R.in, R.units, R.Rtot, (long long)hw, J, &nb))) return rc;
+            host_in = true;
+            rc = with_label(lb_all, [&](auto lt) -> int {
+                typedef typename decltype(lt)::type LT;
+                hipLaunchKernelGGL((lpf_rle_decode<LT>), dim3(nb), dim3(LPF_RLE_BLOCK), 0, c->stream, J, (uint32_t *)la.p);
+                LPF_HIP(c, hipGetLastError());
+                LT *img = (LT *)la.p;
+                int rc_ = erode_packed_iters(c, img, c->cams.label_b[k], I.W, I.H, F, c->stream, c->erode_k == 1 ? 0 : m.erode_iters, c->erode_k != 3);
+                label_img[k] = img;
+                return rc_;
+            });
+            if (rc) return rc;
+            continue;
+        }
         const void *d_masks = nullptr;
         const int4 *rects = nullptr;
         if ((rc = stage_masks(c, m, F, hw, c->cams.masks[k], c->cams.rects[k], &d_masks, &rects, &host_in))) return rc;
@@ -3827,7 +3950,7 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
         const int M = I.masks.M, LW = (M + 31) / 32;
         wide_params(W, input_cam(I), F, M, nchunk, nbw[k], BX, out[k].inst_cap, (const LpfWideFrame *)c->camsw.tab.p + (size_t)k * F);
         W.pts = d_pts;
-        if ((rc = wide_pack(c, D, &I.masks, F, I.W, I.H, W, &host_in))) return rc;
+        if ((rc = wide_pack(c, D, &I.masks, F, I.W, I.H, W, &host_in, &c->rle_in[k]))) return rc;
         if ((rc = wide_bind(c, D, &out[k], n, F, Btot[k], W, S[k]))) return rc;
         max_lists = std::max(max_lists, F * std::max(LW, 1));
         if (M > 0 && Btot[k] > 0) {

@@ -68,3 +68,32 @@ __global__ __launch_bounds__(LPF_RLE_BLOCK) void lpf_rle_decode(const LpfRleJob 
         atomicOr(label + w, v);
     }
 }
+
+// The same runs into the wide pass's label planes [F][LW][H][W] uint32, LW = ceil(M / 32) (lpf_run_wide, lpf_run_cams_wide: wide_pack
+// zeroes ALL F * LW * H * W words first, so the bits of the last word above M are zero, as the dense pack leaves them).  The same job,
+// unit table and owner search; mask m of frame f lives in plane f * LW + (m >> 5) as bit m & 31.  An element is a whole word here:
+// lane l ORs the bit into pixels first + l, first + l + 64, ... of the unit -- again 256 contiguous bytes per wave-instruction -- and
+// no word has a neighbour to spare.  No-return integer ORs only: the planes are the same in any order, with overlap, with repeats and
+// with 256 masks on one pixel (eight words, 32 ORs each).
+// Bounds (the host's check, rle_walk in lpf_api.hip): f < F, m < M, so the plane is one of the F * LW that were zeroed; the unit's
+// pixels are [first, min(first + LPF_RLE_CHUNK, start + length)) inside [start, start + length) inside [0, H * W).
+__global__ __launch_bounds__(LPF_RLE_BLOCK) void lpf_rle_decode_wide(const LpfRleJob J, const int LW, uint32_t *__restrict__ planes)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const int u = (int)blockIdx.x * (LPF_RLE_BLOCK / 64) + ((int)threadIdx.x >> 6);
+    if (u >= J.n_units) return;
+    const int2 un = J.units[u];
+    const int2 rn = J.runs[un.x];
+    int lo = 0, hi = J.FM;                                                     // the owner, as lpf_rle_decode finds it
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (J.run_off[mid] <= (long long)un.x) lo = mid; else hi = mid;
+    }
+    const int f = lo / J.M, m = lo - f * J.M;
+    const long long base = ((long long)f * LW + (m >> 5)) * J.hw;
+    const long long e0 = base + un.y;
+    long long e1 = base + (long long)rn.x + rn.y;
+    if (e1 > e0 + LPF_RLE_CHUNK) e1 = e0 + LPF_RLE_CHUNK;
+    const uint32_t bit = 1u << (m & 31);
+    for (long long e = e0 + lane; e < e1; e += 64) atomicOr(planes + e, bit);
+}

@@ -1619,16 +1619,21 @@ def _rle_frame_masks(frames, camera):
 def _run_frames_rle(frames, rles, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, device, ctx, gather_scans,
                     erosion_kernel_size):
     """run_frames for frames whose masks are RleMasks (the camera and the erosion element set): up to 32 masks in one narrow pass behind
-    set_masks_rle -- the runs go to the GPU, not the masks -- more in groups of 32.  On 0/1 masks V3's cast chain is the erosion alone,
-    so v3_pipeline needs nothing beyond erode_iters."""
+    set_masks_rle, 33 to 256 in ONE wide pass (run_wide takes the runs as they are) -- the runs go to the GPU, not the masks -- more in
+    groups of 256.  On 0/1 masks V3's cast chain is the erosion alone, so v3_pipeline needs nothing beyond erode_iters."""
     counts = [r.shape[0] for r in rles]
-    if max(counts) > LPF_MAX_MASKS:
+    if max(counts) > LPF_MAX_MASKS_WIDE:
         return _run_frames_in_mask_groups(frames, rles, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, False,
-                                          device, ctx, group=LPF_MAX_MASKS, erosion_kernel_size=erosion_kernel_size)
+                                          device, ctx, group=LPF_MAX_MASKS_WIDE, erosion_kernel_size=erosion_kernel_size)
     corners, positions = zip(*(_corners_velo(f.bboxes_3d) for f in frames))
-    ctx.set_masks_rle(rles, erode_iters=erode_iters)
-    ctx.set_boxes(list(corners), oriented=use_oriented)
-    res = ctx.run_batch([f.points for f in frames], want_uv=False, want_label=False, want_valid_uv=True, pinned=True)
+    pts = [f.points for f in frames]
+    if max(counts) > LPF_MAX_MASKS:
+        ctx.set_boxes(list(corners), oriented=use_oriented)
+        res = ctx.run_wide(pts, rles, erode_iters=erode_iters, want_uv=False, want_valid_uv=True)
+    else:
+        ctx.set_masks_rle(rles, erode_iters=erode_iters)
+        ctx.set_boxes(list(corners), oriented=use_oriented)
+        res = ctx.run_batch(pts, want_uv=False, want_label=False, want_valid_uv=True, pinned=True)
     return [_frame_result(f, r, m, pos, min_points, gather_scans) for f, r, m, pos in zip(frames, res, counts, positions)]
 
 
@@ -1644,7 +1649,8 @@ def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_
     ``erosion_kernel_size``: the reference's knob of that name (V3:55, cvs_erosion.py:77) -- ``erode_iters`` iterations erode with the
     k x k MORPH_ELLIPSE element (odd, 1 .. 15; 3 is the cross).  It is set on the context by every call, the default included.
     Frames whose ``masks`` are ``rle.RleMasks`` (at the camera's size; every frame of the batch, a frame without masks aside) take
-    set_masks_rle: the runs are decoded on the GPU, nothing dense crosses to the device; more than 32 masks run in groups of 32."""
+    set_masks_rle, or with 33 to 256 masks ONE run_wide pass: the runs are decoded on the GPU, nothing dense crosses to the device; more
+    than 256 masks run in groups of 256."""
     erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     if not frames:
         return []
@@ -1973,6 +1979,8 @@ def run_frames_multicam(frames_per_cam, cams, depth_max=50.0, min_points=10, use
     ``run_frames(frames_per_cam[c], *cams[c], ...)[i]``, car_statistics and the lazy keys included.  A camera with a frame of more than
     32 masks goes through run_frames on its own (the pass takes a 32-bit label word per camera); the results are the same.  (Routing
     such cameras through one LpfContext.run_cams_wide pass measured slower per frame than this)
+    A camera's frames may carry ``rle.RleMasks`` (run_frames' rules: every frame of that camera, at its size); it is routed by its mask
+    count in the same way, and a camera with dense masks and a camera with RleMasks may share the pass.
     ``erosion_kernel_size``: as in run_frames, for every camera."""
     erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     C = len(cams)
@@ -1995,6 +2003,17 @@ def run_frames_multicam(frames_per_cam, cams, depth_max=50.0, min_points=10, use
     results = [None] * C
     passes = []                                           # (camera, stacks, counts, M, erode_iters, v3_pipeline)
     for c, (T, camera) in enumerate(cams):
+        rles = _rle_frame_masks(frames_per_cam[c], camera)
+        if rles is not None:
+            # RleMasks frames: routed by M as dense masks are -- the pass takes the runs as they are, run_frames the wider camera (on
+            # 0/1 masks V3's cast chain is the erosion alone, _run_frames_rle)
+            counts = [r.shape[0] for r in rles]
+            if max(counts) > LPF_MAX_MASKS:
+                results[c] = run_frames(frames_per_cam[c], T, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline, device,
+                                        ctx, gather_scans, erosion_kernel_size)
+            else:
+                passes.append((c, rles, counts, max(counts), erode_iters, False))
+            continue
         # (masks of another size are resized -- and with the V3 block eroded -- at camera c's size: the context's camera for that)
         ctx.set_camera(T, camera.K, camera.width, camera.height, 0.0, float(depth_max))
         stacks, er, v3 = _frame_mask_stacks(frames_per_cam[c], camera, ctx, erode_iters, v3_pipeline, erosion_kernel_size)
@@ -2012,7 +2031,8 @@ def run_frames_multicam(frames_per_cam, cams, depth_max=50.0, min_points=10, use
         corners, pos = zip(*(_corners_velo(f.bboxes_3d) for f in frames_per_cam[c]))
         positions.append(pos)
         specs.append(dict(T_velo_to_rect=T, K=camera.K, width=camera.width, height=camera.height, depth_min=0.0, depth_max=float(depth_max),
-                          masks=_mask_batch(stacks, M, camera.height, camera.width, ctx), binarize="v3" if v3 else "astype",
+                          masks=stacks if isinstance(stacks[0], RleMasks) else _mask_batch(stacks, M, camera.height, camera.width, ctx),
+                          binarize="v3" if v3 else "astype",
                           erode_iters=er, boxes=list(corners), oriented=use_oriented))
     pts = [f.points for f in frames_per_cam[passes[0][0]]]
     # (results arrive in page-locked buffers the context reuses, one set per camera: _frame_result copies out what it hands on)
