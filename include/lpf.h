@@ -68,6 +68,8 @@ extern "C" {
                                       8 (continued): lpf_first_match_input, lpf_first_match_outputs, lpf_first_match (added; nothing else
                                          changed)
                                       8 (continued): lpf_rle_masks, lpf_set_masks_rle (added; nothing else changed)
+                                      8 (continued): lpf_depth_maps_rle, lpf_first_match_rle_input, lpf_first_match_rle (added; nothing else
+                                      changed)
                                       8 (continued): LPF_MASKS_U8 / _F32 / _RLE name lpf_wide_input.f32's values; 2 is new (no symbol, no
                                          layout change; any other value is now refused) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
@@ -286,8 +288,9 @@ int lpf_set_masks_f32(lpf_ctx *ctx, const float *masks, int F, int M, int binari
  * in NULL, F < 0, M < 0, erode_iters < 0, reserved != 0, M > LPF_MAX_MASKS (lpf_set_masks_u8's message), run_off NULL with F * M > 0,
  * runs NULL with runs to read, F * M or the number of runs above 2^31 - 1, or runs that together cover more than 2^24 chunks of 1024 pixels.
  *   The passes that turn a lpf_wide_input into label bits -- lpf_run_wide, lpf_run_cams, lpf_run_cams_wide -- take this struct as their
- * masks (LPF_MASKS_RLE, at lpf_wide_input; there M goes up to the pass's own limit).  Not taken in this form: lpf_run_frame_wide (device
- * masks), lpf_depth_maps, lpf_first_match and lpf_inside_masks' own mask input keep their dense masks; runs are not resized (masks of another size than the camera's: decode them on
+ * masks (LPF_MASKS_RLE, at lpf_wide_input; there M goes up to the pass's own limit).  Not taken in this form: the dense inputs of lpf_run_frame_wide
+ * (device masks), lpf_depth_maps and lpf_first_match -- those two have calls of their own for it, lpf_depth_maps_rle and
+ * lpf_first_match_rle below -- and lpf_inside_masks' instance lists; runs are not resized (masks of another size than the camera's: decode them on
  * the host, lpf_resize_masks_u8); runs in device memory.  Masks that already sit on the GPU gain nothing from this form. */
 typedef struct lpf_rle_masks {
     const int32_t *runs;     /* host, [Rtot][2] {start, length}, Rtot = run_off[F*M] */
@@ -381,8 +384,9 @@ int lpf_run_frame(lpf_ctx *ctx, const lpf_frame_job *job);
  * the same call gives for the equivalent dense uint8 host masks (dense[f][m][p] = 1 iff p lies in any run of mask m) with the same
  * erode_iters; the narrow state (masks, label image, rectangles, boxes) is left as it was.  The planes are zeroed, the runs are OR-ed
  * into them on the GPU (integer ORs only) and every erosion iteration runs on the packed planes: no dense mask exists anywhere.
- *   Taken by lpf_run_wide, lpf_run_cams and lpf_run_cams_wide.  lpf_depth_maps refuses it (LPF_ERR_ARG, before masks is read), as every
- * call refuses an f32 other than these three; lpf_run_frame_wide's job has no such field: its masks are uint8 device memory. */
+ *   Taken by lpf_run_wide, lpf_run_cams and lpf_run_cams_wide.  lpf_depth_maps refuses it in its lpf_wide_input (LPF_ERR_ARG, before masks
+ * is read), as every call refuses an f32 other than these three -- run-length masks go to lpf_depth_maps_rle, and to lpf_first_match_rle
+ * for lpf_first_match, whose input refuses the value too; lpf_run_frame_wide's job has no such field: its masks are uint8 device memory. */
 #define LPF_MASKS_U8  0
 #define LPF_MASKS_F32 1
 #define LPF_MASKS_RLE 2
@@ -549,6 +553,20 @@ typedef struct lpf_depth_maps_outputs {
 } lpf_depth_maps_outputs;
 int lpf_depth_maps(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
                    const lpf_depth_maps_outputs *out);
+/* lpf_depth_maps for masks in RUN-LENGTH form (lpf_rle_masks above: host memory, runs index W x H of lpf_set_camera, masks->F == F,
+ * 0 <= masks->M <= LPF_MAX_MASKS_WIDE, masks->erode_iters with the context's element).  Every output is bit for bit what
+ * lpf_depth_maps gives for the equivalent dense uint8 host masks (dense[f][m][p] = 1 iff p lies in any run of mask m) with the same
+ * erode_iters and no rectangles; output placement, cap / need / overflow, what is not written, the states left alone, "not
+ * capturable", the pipelined modes and the one host wait are lpf_depth_maps'.  The whole input -- every frame of the batch -- is
+ * checked by lpf_set_masks_rle's rules before anything is enqueued (LPF_ERR_ARG, "depth_maps_rle: frame f mask m run r ..."); the
+ * caller may free runs, run_off and the struct when the call returns.  No dense mask exists anywhere: a chunk of frames zeroes its
+ * label planes (4 * ceil(M / 32) bytes per pixel; twice with erosion), ORs its own runs in on the GPU, erodes the packed planes, and
+ * the raster reads bit m & 31 of plane m / 32.  The chunks are planned as lpf_depth_maps plans them, a chunk's run tables counting in
+ * place of its dense masks.  M = 0, or no run at all, launches no decode.
+ * LPF_ERR_ARG besides lpf_depth_maps' output and frame checks: masks NULL, masks->F != F, M out of range, erode_iters < 0,
+ * reserved != 0. */
+int lpf_depth_maps_rle(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
+                       const lpf_rle_masks *masks, const lpf_depth_maps_outputs *out);
 
 /* lpf_depth_overlays: seg_with_pointcloud.py:174-180's per-car overlay images of a batch of F frames in ONE call, from the sparse
  * lists of lpf_depth_maps.  For car m of frame f (entries car_off[f][m] .. car_off[f][m + 1] of row f of pix / depth) image
@@ -998,6 +1016,27 @@ typedef struct lpf_first_match_outputs {   /* any list may be NULL; all host or 
 } lpf_first_match_outputs;
 int lpf_first_match(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
                     const lpf_first_match_input *in, const lpf_first_match_outputs *out);
+/* lpf_first_match for masks in RUN-LENGTH form.  The runs index the masks' OWN size: run pixel (x, y) = y * mw + x, mh x mw smaller or
+ * larger than the image; as in lpf_first_match a point's pixel is tested against mw, mh and the image before anything is read.  Every
+ * output is bit for bit what lpf_first_match gives for the equivalent dense uint8 host masks [F][M][mh][mw] (1 iff the pixel lies in
+ * any run of the mask) and the same colours; output placement, what is not written, the states left alone, "not capturable", the
+ * pipelined modes and the one host wait are lpf_first_match's.  The whole input -- every frame of the batch -- is checked by
+ * lpf_set_masks_rle's rules against mh * mw before anything is enqueued (LPF_ERR_ARG, "first_match_rle: frame f mask m run r ...");
+ * the caller may free runs, run_off and both structs when the call returns.  A range of frames zeroes its label planes
+ * [frames][ceil(M / 32)][mh][mw] uint32, ORs its own runs in on the GPU, and a point's first mask is the lowest set bit of at most
+ * ceil(M / 32) words (lpf_fm_count_planes) where the dense walk reads up to M bytes; the planes and the range's run tables count in
+ * the 256 MiB of a range in place of the dense masks.
+ * LPF_ERR_ARG besides lpf_first_match's output and frame checks: in or in->masks NULL, masks->F != F, M out of range,
+ * masks->erode_iters != 0, reserved != 0 (either struct), mh or mw <= 0 with M > 0. */
+typedef struct lpf_first_match_rle_input {
+    const lpf_rle_masks *masks;   /* host; masks->F == F, 0 <= M <= LPF_MAX_MASKS_WIDE, erode_iters == 0 */
+    const double *colors;         /* optional [F][M][3], as lpf_first_match_input.colors */
+    int32_t mh, mw;               /* the masks' OWN size: run pixel (x, y) = y * mw + x; > 0 when M > 0 */
+    int32_t colors_on_device;     /* 0: colors in host memory, copied by the call; else device memory lent until the work has completed */
+    int32_t reserved;             /* 0 */
+} lpf_first_match_rle_input;
+int lpf_first_match_rle(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
+                        const lpf_first_match_rle_input *in, const lpf_first_match_outputs *out);
 
 /* ---- scan reader ------------------------------------------------------------------------------
  * Double-buffered velodyne .bin reader for frame loops and the 10 Hz stream.  Stands where the

@@ -149,6 +149,12 @@ class FirstMatchInput(ctypes.Structure):
                 ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class FirstMatchRleInput(ctypes.Structure):
+    """lpf_first_match_rle_input (include/lpf.h): a batch's run-length masks at their own size and the colour rows car_rgb gathers"""
+    _fields_ = [("masks", ctypes.POINTER(RleMasksInput)), ("colors", _P), ("mh", ctypes.c_int32), ("mw", ctypes.c_int32),
+                ("colors_on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class FirstMatchOutputs(ctypes.Structure):
     """lpf_first_match_outputs (include/lpf.h): the dense first-mask codes, the compact car and background lists, the counts"""
     _fields_ = [("first_mask", _P), ("car_idx", _P), ("car_mask", _P), ("car_xyz", _P), ("car_rgb", _P), ("bg_idx", _P), ("bg_xyz", _P),
@@ -228,11 +234,13 @@ def wide_mask_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype"
 LPF_MASKS_U8, LPF_MASKS_F32, LPF_MASKS_RLE = 0, 1, 2           # lpf_wide_input.f32 (include/lpf.h)
 
 
-def wide_rle_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", max_masks=LPF_MAX_MASKS_WIDE, who="run_wide"):
+def wide_rle_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", max_masks=LPF_MAX_MASKS_WIDE, who="run_wide",
+                   default_binarize="astype"):
     """The run-length form of a pass's masks -- one rle.RleMasks, or a list with one per frame -- checked before anything reaches the
     GPU, in the shape wide_mask_batch returns: ``((runs, run_off, RleMasksInput), M, "rle", False, None)``; None when ``masks`` are not
     in that form.  Ragged M is padded with empty masks.  ValueError: a list that mixes RleMasks and arrays, another size than H x W,
-    ``rects`` (runs need none), a ``binarize`` other than the default, more than max_masks masks, another frame count than F."""
+    ``rects`` (runs need none), a ``binarize`` other than the entry point's default (``default_binarize``), more than max_masks masks,
+    another frame count than F."""
     from .rle import RleMasks
     if not isinstance(masks, RleMasks):
         if not isinstance(masks, (list, tuple)) or not any(isinstance(m, RleMasks) for m in masks):
@@ -241,7 +249,7 @@ def wide_rle_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype",
             raise ValueError("%s: the list mixes RleMasks and arrays: one form per call (.to_dense() or RleMasks.from_dense)" % who)
     if rects is not None:
         raise ValueError("%s: rects given with RleMasks (the runs say where the masks are)" % who)
-    if binarize != "astype":
+    if binarize != default_binarize:
         raise ValueError("%s: binarize=%r with RleMasks (a pixel is a member or it is not)" % (who, binarize))
     if int(erode_iters) != erode_iters or erode_iters < 0:
         raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
@@ -372,6 +380,9 @@ def load(path=None):
     lib.lpf_box_points.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(BoxPointsInput), ctypes.POINTER(BoxPointsOutputs)]
     lib.lpf_box_views.argtypes = [_P, ctypes.c_int, ctypes.POINTER(BoxViewsInput), ctypes.POINTER(BoxViewsOutputs)]
     lib.lpf_first_match.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FirstMatchInput), ctypes.POINTER(FirstMatchOutputs)]
+    lib.lpf_depth_maps_rle.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RleMasksInput), ctypes.POINTER(DepthMapsOutputs)]
+    lib.lpf_first_match_rle.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(FirstMatchRleInput),
+                                        ctypes.POINTER(FirstMatchOutputs)]
     lib.lpf_run_cams.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(Outputs)]
     lib.lpf_run_cams_wide.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CamInput), ctypes.c_int, ctypes.POINTER(WideOutputs)]
     lib.lpf_points_in_boxes.argtypes = [_P, _P, _I64, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
@@ -410,7 +421,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
             "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d",
             "lpf_inside_masks", "lpf_set_erosion_element", "lpf_box_points", "lpf_box_views", "lpf_assign_costs", "lpf_assign_2d",
-            "lpf_first_match", "lpf_set_masks_rle")
+            "lpf_first_match", "lpf_set_masks_rle", "lpf_depth_maps_rle", "lpf_first_match_rle")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -1429,7 +1440,10 @@ class LpfContext:
         """seg_with_pointcloud's per-car depth maps of a batch of frames in ONE native call (lpf_depth_maps) and one host wait.
         frames: as run_wide's -- f32[N_f,4] host arrays, Scans of a ScanReader, float32 [N,4] GPU tensors.  masks: [M,H,W] or
         [F,M,H,W] at the camera's size (uint8 / bool: nonzero, or float32 under ``binarize``; "gt0.5" is the script's mask > 0.5),
-        host or GPU; rects: the optional [F,M,4] hint of set_mask_rects; erode_iters: cv2.erode iterations.  The camera, transform
+        host or GPU; or in run-length form -- one rle.RleMasks, or a list with one per frame (ragged M is padded with empty masks), at
+        the camera's size, without ``rects`` and under the default ``binarize`` (lpf_depth_maps_rle: the runs are decoded into label
+        planes on the GPU, nothing dense crosses to the device, every result equals the one ``.to_dense()`` masks give);
+        rects: the optional [F,M,4] hint of set_mask_rects; erode_iters: cv2.erode iterations.  The camera, transform
         and depth window are set_camera's.  Returns, per frame, M tuples (pix int64, depth float64, point_idx int64 or None): car m
         = np.flatnonzero(np.where(member_m, D, 0)) with D the frame's depth_image, its depths and the winning points.  cap: list
         entries per frame of the first attempt (default from the point counts); a frame that needs more runs the call once more
@@ -1443,11 +1457,15 @@ class LpfContext:
             raise ValueError("no frames")
         if cap is not None and (isinstance(cap, bool) or int(cap) != cap or cap < 0):
             raise ValueError("cap must be a non-negative integer, got %r" % (cap,))
-        batch = wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
+        batch = wide_rle_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, who="depth_maps", default_binarize="gt0.5") or \
+            wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
         M = batch[1]
         off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the call returns)
-        inp = WideInput()
-        self._wide_input(inp, batch, binarize, erode_iters)
+        if batch[2] == "rle":                               # the lpf_rle_masks itself: the call of its own
+            native, inp = self._lib.lpf_depth_maps_rle, batch[0][2]
+        else:
+            native, inp = self._lib.lpf_depth_maps, WideInput()
+            self._wide_input(inp, batch, binarize, erode_iters)
         if out is not None:
             if cap is None or int(cap) < 1:
                 raise ValueError("depth_maps: out= needs a capacity of at least one entry")
@@ -1465,7 +1483,7 @@ class LpfContext:
             for k, dt in self._DEPTH_MAPS_OUT.items():
                 setattr(o, k, _dev_ptr(out.get(k), dt))
             o.cap, o.on_device = int(cap), 1
-            self._call_in_order(out["pix"].device, self._lib.lpf_depth_maps, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o))
+            self._call_in_order(out["pix"].device, native, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o))
             self._lent.append((_keep, batch))           # (staged points and masks: alive until the work has run)
             return out
         if cap is None:                     # a quarter of the largest frame's points: frame 100's five cars are 8 k of its 109 k
@@ -1480,7 +1498,7 @@ class LpfContext:
             o.pix, o.depth = (pix.ctypes.data, dep.ctypes.data) if cap else (None, None)
             o.point_idx = pid.ctypes.data if (pid is not None and cap) else None
             o.cap, o.car_off, o.need, o.overflow, o.on_device = cap, car_off.ctypes.data, need.ctypes.data, ovf.ctypes.data, 0
-            self._check(self._lib.lpf_depth_maps(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
+            self._check(native(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
             return pix, dep, pid, car_off, need, ovf
 
         pix, dep, pid, car_off, need, ovf = launch(int(cap))
@@ -1972,7 +1990,49 @@ class LpfContext:
                 colors = colors.contiguous()
         return dev, M, mh, mw, int(f32), masks, colors
 
-    def first_match(self, pts_per_frame, masks, colors=None, want=None, out=None, staged=None):
+    @staticmethod
+    def first_match_rle_batch(masks, colors, F, out=None):
+        """first_match's masks in run-length form -- one rle.RleMasks (F = 1), or a list with one per frame -- checked against a batch of
+        F frames before any native call: ``(device, M, mh, mw, (runs, run_off, RleMasksInput), colors)``; None when ``masks`` are not in
+        that form.  The frames share one size, which becomes mh x mw (it need not be the camera's); ragged M is padded with empty
+        masks, up to LPF_MAX_MASKS_WIDE.  The masks stay host memory; device: where the outputs go -- the GPU of ``out``'s tensors or
+        of GPU ``colors``, else None (NumPy).  ValueError: a list that mixes RleMasks and arrays, frames of differing sizes, more than
+        256 masks, another frame count, colours of another shape or dtype."""
+        from .rle import RleMasks
+        if not isinstance(masks, RleMasks):
+            if not isinstance(masks, (list, tuple)) or not any(isinstance(m, RleMasks) for m in masks):
+                return None
+            if not all(isinstance(m, RleMasks) for m in masks):
+                raise ValueError("first_match: the list mixes RleMasks and arrays: one form per call (.to_dense() or RleMasks.from_dense)")
+        frames = [masks] if isinstance(masks, RleMasks) else list(masks)
+        if len(frames) != F:
+            raise ValueError("first_match: RleMasks for %d frames, the batch has %d" % (len(frames), F))
+        sizes = sorted({tuple(r.shape[1:]) for r in frames})
+        if len(sizes) > 1:
+            raise ValueError("first_match: the frames' RleMasks have differing sizes (H, W) = %s: one size per call (runs are not resized)"
+                             % (sizes,))
+        mh, mw = sizes[0] if sizes else (1, 1)
+        runs, run_off, _, M = LpfContext.rle_batch(frames, mh, mw, LPF_MAX_MASKS_WIDE, "first_match")
+        inp = RleMasksInput(runs.ctypes.data if len(runs) else None, run_off.ctypes.data, F, M, 0, 0)
+        device = None
+        if colors is not None:
+            if _is_torch(colors) and colors.is_cuda:
+                if str(colors.dtype) != "torch.float64":
+                    raise ValueError("first_match: GPU colors must be float64, got %s" % colors.dtype)
+                colors, device = colors.contiguous(), colors.device
+            else:
+                colors = np.ascontiguousarray(colors, dtype=np.float64)
+            cs = tuple(colors.shape)
+            if len(cs) == 2 and F == 1:
+                colors, cs = colors[None], (1,) + cs
+            if cs != (F, M, 3):
+                raise ValueError("first_match: colors [F,M,3] = %s, got %s" % ((F, M, 3), cs))
+        for t in (out or {}).values():
+            if _is_torch(t) and t.is_cuda:
+                device = t.device
+        return device, M, int(mh), int(mw), (runs, run_off, inp), colors
+
+    def first_match(self, pts_per_frame, masks, colors=None, want=None, out=None, staged=None, rects=None, binarize=None, erode_iters=0):
         """Same_color.py:113-132's exclusive labels of a batch of frames in ONE native call (lpf_first_match): every valid point goes
         to the FIRST mask of its frame with ``v < mh and u < mw and mask[v, u] > 0.5`` (uint8 / bool masks: nonzero), or to the
         background.  pts_per_frame: as run_batch's frames -- f32 [N_f,4] host arrays, Scans of a ScanReader, float32 [N,4] GPU tensors
@@ -1985,7 +2045,15 @@ class LpfContext:
         n_car[f] resp. n_bg[f] of them, ascending -- and "n_valid", "n_car", "n_bg" int64 [F], "mask_count" int64 [F,M].  Returns a dict
         of them plus "frame_off": NumPy arrays after one host wait, or GPU tensors in torch's stream order when the masks are GPU
         tensors (the call only enqueues work).  Entries the call does not write (beyond a frame's count) are -1 / 0, or what ``out``
-        -- a dict of the caller's own arrays under the same names -- held."""
+        -- a dict of the caller's own arrays under the same names -- held.
+        masks in run-length form -- one rle.RleMasks (one frame), or a list with one per frame, all of ONE size, which is mh x mw
+        (ragged M is padded with empty masks) -- go through lpf_first_match_rle: the runs are decoded into label planes on the GPU,
+        nothing dense crosses to the device, and every result equals the one ``.to_dense()`` masks give.  They stay host memory; the
+        outputs are GPU tensors when ``out`` holds GPU tensors or ``colors`` is one.  The labelling has no rectangles, no binarize
+        rule of its own ("gt0.5" is the rule) and no erosion: ``rects``, another ``binarize`` and ``erode_iters`` are ValueErrors."""
+        if rects is not None or binarize not in (None, "gt0.5") or erode_iters != 0:
+            raise ValueError("first_match: rects=%s binarize=%r erode_iters=%r: the first-mask labelling takes no rectangles, reads masks "
+                             "as > 0.5 / nonzero and has no erosion" % ("given" if rects is not None else None, binarize, erode_iters))
         if want is None:
             want = tuple(w for w in self.FIRST_MATCH_WANT if w != "car_rgb" or colors is not None)
         want = self._want("first_match", want, self.FIRST_MATCH_WANT)
@@ -1994,6 +2062,26 @@ class LpfContext:
             raise ValueError("first_match: car_rgb is wanted, colors is None")
         off, pts_ptr, pts_dev, _keep = staged or self._stage_points(pts_per_frame)      # (_keep: alive until the call returns)
         F, Ntot = len(off) - 1, int(off[-1])
+        rle = self.first_match_rle_batch(masks, colors, F, out)
+        if rle is not None:
+            device, M, mh, mw, tables, colors = rle
+            inp, o = FirstMatchRleInput(), FirstMatchOutputs()
+            res = self._outputs("first_match", o, want, self._FIRST_MATCH_OUT, dict(N=Ntot, F=F, M=M), device, out)
+            if Ntot == 0:
+                for w in self._FIRST_MATCH_LISTS + ("first_mask",):
+                    setattr(o, w, None)
+            inp.masks = ctypes.pointer(tables[2])
+            inp.colors = _ptr(colors) if (colors is not None and M) else None
+            if inp.colors is None:
+                o.car_rgb = None
+            inp.mh, inp.mw, inp.colors_on_device = mh, mw, int(_is_torch(colors))
+            if F:
+                self._call_in_order(device, self._lib.lpf_first_match_rle, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp),
+                                    ctypes.byref(o))
+                if device is not None:
+                    self._lent.append((_keep, tables, colors))      # (staged points, tables and colours: alive until the work has run)
+            res["frame_off"] = off
+            return res
         dev, M, mh, mw, f32, masks, colors = self.first_match_batch(masks, colors, F)
         device = masks.device if dev else None
         inp, o = FirstMatchInput(), FirstMatchOutputs()

@@ -115,6 +115,17 @@ struct lpf_ctx {
         long long Rtot = 0;
         std::vector<int2> units;
     } rle_in[LPF_NSETS];
+    // run-length masks of lpf_depth_maps_rle / lpf_first_match_rle: the whole batch is checked into rle_in[0]; a range of frames decodes
+    // its own slice of it -- the range's runs (the caller's, from `sub.runs` on), run_off rebased to them (off) and the units of those
+    // runs with their run index rebased (R.units), as ONE lpf_rle_masks of the range's frames (sub; R.in points at it).  One record per
+    // range, sized before the first launch and kept until the call's host wait (then cleared): the copies of a range's tables read them
+    // in stream order
+    struct RleSlice {
+        lpf_rle_masks sub;
+        std::vector<int64_t> off;
+        RleIn R;
+    };
+    std::vector<RleSlice> rle_slices;
     // Masks that are set but not packed (no erosion; the next lpf_run* decides, plan_tile_source).  Left by lpf_set_masks_* of a serial
     // context -- host masks in mask_stage, or device masks the caller lends (on_device 2): a launch of sparse frames reads them directly,
     // anything else packs them first -- or of a pipelined one (lent masks only): a fused launch of sparse frames reads them directly, a
@@ -299,7 +310,8 @@ struct lpf_ctx {
     // tables and staged points (grow-only, allocated on first use); its box tables are lpf_run_cams' (cams.bx[c])
     struct CamsWide { Wide cam[LPF_NSETS]; DevBuf tab, pts; } camsw;
     // lpf_depth_maps: frame offsets, a chunk's winner planes, counters, staged masks and rectangles, staged points, host-output staging
-    // and (with erosion) lpf_run_wide's label planes in pack.planes_* (grow-only, allocated on first use)
+    // and (with erosion, or run-length masks) lpf_run_wide's label planes in pack.planes_* and a range's run tables in pack.rle
+    // (grow-only, allocated on first use)
     struct DepthMaps { Wide pack; DevBuf foff, win, cnt, in, pts, out; } dmaps;
     // the analysis calls, each its own: the frame table, staged host points, staged host inputs (lists, detections, corners, segmented
     // images), staged host outputs (grow-only, allocated on first use; a call leaves empty what it does not stage)
@@ -307,7 +319,8 @@ struct lpf_ctx {
     CallBufs asgn;                    // lpf_assign_costs / lpf_assign_2d (pts: the scratch matrices, live-column maps and counts of a range)
     // lpf_first_match: the analysis calls' four (tab: the frame offsets; in: a range's staged masks and colours) and its scratch -- a
     // range's 4-byte codes when the dense output is not asked for, and its tile counters
-    struct FirstMatch : CallBufs { DevBuf code, tiles; } fmat;
+    // (lpf_first_match_rle: a range's label planes [fc][LW][mh][mw] in pack.planes_a, its run tables in pack.rle)
+    struct FirstMatch : CallBufs { DevBuf code, tiles; Wide pack; } fmat;
 
     // optional event bracketing of K1 (lpf_profile_*)
     bool profiling = false;
@@ -1286,6 +1299,40 @@ int rle_stage_tables(lpf_ctx *c, DevBuf &stage, const lpf_rle_masks *in, const s
     return LPF_OK;
 }
 
+// The frames [f0, f0 + fc) of a walked batch A (A.in->M > 0): rle_walk emits the units in run order, so the range's runs and units are
+// contiguous pieces of A's.  rle_units_before: the units of the runs before run r, i.e. the first unit of r (or of the next run that has one)
+size_t rle_units_before(const lpf_ctx::RleIn &A, long long r)
+{
+    return (size_t)(std::lower_bound(A.units.begin(), A.units.end(), r, [](const int2 &u, long long run) { return (long long)u.x < run; }) -
+                    A.units.begin());
+}
+// ... the bytes rle_stage_tables stages for that range
+size_t rle_slice_bytes(const lpf_ctx::RleIn &A, size_t f0, size_t fc)
+{
+    const size_t M = (size_t)A.in->M;
+    const long long r0 = A.in->run_off[f0 * M], r1 = A.in->run_off[(f0 + fc) * M];
+    return align256((size_t)(r1 - r0) * sizeof(int2)) + align256((rle_units_before(A, r1) - rle_units_before(A, r0)) * sizeof(int2)) +
+           (fc * M + 1) * 8;
+}
+// ... and the range as a batch of its own in S (lpf_ctx::RleSlice): what wide_pack's run-length branch takes as its checked input
+void rle_slice(const lpf_ctx::RleIn &A, size_t f0, size_t fc, lpf_ctx::RleSlice &S)
+{
+    const size_t M = (size_t)A.in->M;
+    const int64_t *off = A.in->run_off + f0 * M;
+    const long long r0 = off[0], r1 = off[fc * M];
+    S.off.resize(fc * M + 1);
+    for (size_t k = 0; k <= fc * M; ++k) S.off[k] = off[k] - r0;
+    const size_t u0 = rle_units_before(A, r0), u1 = rle_units_before(A, r1);
+    S.R.units.assign(A.units.begin() + (ptrdiff_t)u0, A.units.begin() + (ptrdiff_t)u1);
+    for (int2 &u : S.R.units) u.x -= (int)r0;
+    S.sub = *A.in;
+    S.sub.F = (int32_t)fc;
+    S.sub.runs = r1 > r0 ? A.in->runs + 2 * r0 : nullptr;
+    S.sub.run_off = S.off.data();
+    S.R.in = &S.sub;
+    S.R.Rtot = r1 - r0;
+}
+
 // ---- setup the run paths share ---------------------------------------------------------------------------------------------------
 
 // frame_off[0..F] (not NULL, F > 0: the caller's checks) starts at 0 and has frames of 0 .. 0x7fffffff - slack points; pts is given if
@@ -1721,7 +1768,8 @@ void lpf_destroy(lpf_ctx *c)
     }
     release(c->camsw.tab);
     release(c->camsw.pts);
-    for (DevBuf *b : {&c->dmaps.pack.planes_a, &c->dmaps.pack.planes_b, &c->dmaps.foff, &c->dmaps.win, &c->dmaps.cnt, &c->dmaps.in,
+    for (DevBuf *b : {&c->dmaps.pack.planes_a, &c->dmaps.pack.planes_b, &c->dmaps.pack.rle, &c->fmat.pack.planes_a, &c->fmat.pack.planes_b,
+                      &c->fmat.pack.rle, &c->dmaps.foff, &c->dmaps.win, &c->dmaps.cnt, &c->dmaps.in,
                       &c->dmaps.pts, &c->dmaps.out})
         release(*b);
     for (lpf_ctx::CallBufs *D : {&c->dovl, &c->m2d, &c->insd, &c->bpts, &c->bviews, &c->asgn, (lpf_ctx::CallBufs *)&c->fmat})
@@ -2862,20 +2910,25 @@ static void dm_raster(lpf_ctx *c, const LpfDmParams &P, dim3 g, bool planes, con
     });
 }
 
-int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
-                   const lpf_depth_maps_outputs *out)
+// What lpf_depth_maps and lpf_depth_maps_rle share, after the checks of their own mask input (who: the messages' prefix).  rle: the
+// run-length masks of lpf_depth_maps_rle, not walked yet -- `in` then carries M and erode_iters only, and the label planes of a chunk are
+// decoded from the chunk's own runs (wide_pack's run-length branch on a lpf_ctx::RleSlice); NULL: the dense masks of `in`
+static int depth_maps_impl(lpf_ctx *c, const char *who, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
+                           const lpf_wide_input *in, const lpf_rle_masks *rle, const lpf_depth_maps_outputs *out)
 {
     int rc;
-    if ((rc = enter(c, "lpf_depth_maps", true))) return rc;
-    if (!in || !out || F < 0 || (F > 0 && !frame_off))
-        return fail(c, LPF_ERR_ARG, "depth_maps: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
     const int M = in->M;
-    if ((rc = check_wide_input(c, "depth_maps", -1, *in, LPF_MAX_MASKS_WIDE, "lpf_depth_maps takes 0 .. LPF_MAX_MASKS_WIDE", ""))) return rc;
     if (out->cap < 0 || !out->car_off || !out->need || (out->cap > 0 && !out->pix))
-        return fail(c, LPF_ERR_ARG, "depth_maps: cap=%lld pix=%p car_off=%p need=%p (car_off and need are required, pix with cap > 0)",
+        return fail(c, LPF_ERR_ARG, "%s: cap=%lld pix=%p car_off=%p need=%p (car_off and need are required, pix with cap > 0)", who,
                     (long long)out->cap, (void *)out->pix, (void *)out->car_off, (void *)out->need);
     if (F == 0) return LPF_OK;
-    if ((rc = check_frames(c, "depth_maps", pts, frame_off, F, LPF_BLOCK))) return rc;
+    if ((rc = check_frames(c, who, pts, frame_off, F, LPF_BLOCK))) return rc;
+    lpf_ctx::RleIn &A = c->rle_in[0];                       // run-length masks: the whole batch checked here, before anything is enqueued
+    if (rle) {
+        if ((rc = rle_walk(c, who, rle, (long long)c->W * c->H, A.units, &A.Rtot))) return rc;
+        A.in = rle;
+    }
+    const bool runs = rle && M > 0;
     long long maxN = 0;
     for (int f = 0; f < F; ++f) maxN = std::max(maxN, (long long)(frame_off[f + 1] - frame_off[f]));
     const int64_t Ntot = frame_off[F];
@@ -2886,13 +2939,17 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     const size_t hw = (size_t)c->W * c->H, esz = in->f32 ? 4 : 1;
     const int ntile = (int)((hw + LPF_DM_TILE - 1) / LPF_DM_TILE), LW = (M + 31) / 32;
     const size_t hwp = (size_t)ntile * LPF_DM_TILE;
-    const bool planes = M > 0 && in->erode_iters > 0;
-    const bool host_masks = M > 0 && !in->on_device, host_pts = Ntot > 0 && !pts_on_device, host_io = !out->on_device;
-    const bool use_rects = M > 0 && rects_hold(*in);
-    const size_t per_frame = hwp * 4 + (size_t)M * ntile * 12 + (planes ? (size_t)LW * hw * 4 * (in->erode_iters > 1 ? 2 : 1) : 0) +
+    const bool planes = M > 0 && (runs || in->erode_iters > 0);
+    const bool host_masks = M > 0 && !runs && !in->on_device, host_pts = Ntot > 0 && !pts_on_device, host_io = !out->on_device;
+    const bool use_rects = M > 0 && !runs && rects_hold(*in);
+    // (decoded planes are eroded from the first iteration on, so they ping-pong with one iteration already; packed ones with two)
+    const size_t plane_sets = in->erode_iters > (runs ? 0 : 1) ? 2 : 1;
+    const size_t per_frame = hwp * 4 + (size_t)M * ntile * 12 + (planes ? (size_t)LW * hw * 4 * plane_sets : 0) +
                              (host_masks ? (size_t)M * (hw * esz + 16) : 0) + (host_pts ? (size_t)maxN * 16 : 0);
-    const std::vector<Span> chunks = plan_ranges(c, (size_t)F, (size_t)F, [&](size_t, size_t n) { return n * per_frame; });
-    const size_t Fc = chunks[0].count;
+    const std::vector<Span> chunks = plan_ranges(c, (size_t)F, (size_t)F, [&](size_t f0, size_t n) {
+        return n * per_frame + (runs ? rle_slice_bytes(A, f0, n) : 0);          // (a chunk's run tables in place of its dense masks)
+    });
+    const size_t Fc = largest(chunks, [](size_t, size_t n) { return n; });      // (the first chunk's, where every frame costs the same)
     const size_t most_pts = largest(chunks, [&](size_t f0, size_t n) { return frame_off[f0 + n] - frame_off[f0]; });
 
     // ---- buffers, reserved for the largest chunk ------------------------------------------------------------------------------------
@@ -2900,11 +2957,18 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     if ((rc = reserve(c, D.win, Fc * hwp * 4))) return rc;
     if (M > 0 && (rc = reserve(c, D.cnt, Fc * M * (2 * ntile + 1) * 4))) return rc;
     if (host_pts && (rc = reserve(c, D.pts, most_pts * 16))) return rc;      // (here, not by the first chunk with points: no chunk waits)
+    if (runs) {                                               // the largest chunk's planes and run tables; every chunk's slice of the runs
+        if ((rc = reserve(c, D.pack.planes_a, Fc * LW * hw * 4))) return rc;
+        if (plane_sets > 1 && (rc = reserve(c, D.pack.planes_b, Fc * LW * hw * 4))) return rc;
+        if ((rc = reserve(c, D.pack.rle, largest(chunks, [&](size_t f0, size_t n) { return rle_slice_bytes(A, f0, n); })))) return rc;
+        c->rle_slices.resize(chunks.size());
+        for (size_t k = 0; k < chunks.size(); ++k) rle_slice(A, chunks[k].first, chunks[k].count, c->rle_slices[k]);
+    }
     const void *masks_k = nullptr;                            // a chunk's staged masks and rectangles, or the caller's
     const int32_t *rects_k = nullptr;
     Stage I(host_masks);
-    I.add(masks_k, M > 0 ? in->masks : nullptr, (size_t)M * hw * esz, Fc);
-    I.add(rects_k, M > 0 ? in->rects : nullptr, (size_t)M * 16, Fc);
+    I.add(masks_k, M > 0 && !runs ? in->masks : nullptr, (size_t)M * hw * esz, Fc);
+    I.add(rects_k, M > 0 && !runs ? in->rects : nullptr, (size_t)M * 16, Fc);
     if ((rc = I.commit(c, D.in))) return rc;
     const size_t cap = (size_t)out->cap, nF = (size_t)F;
     if ((rc = upload(c, D.foff.p, frame_off, (size_t)(F + 1) * 8))) return rc;
@@ -2930,8 +2994,9 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     if ((rc = S.commit(c, D.out))) return rc;
 
     // ---- the chunks ---------------------------------------------------------------------------------------------------------
-    bool pts_in = false;
-    for (const Span &ch : chunks) {
+    bool pts_in = false, runs_in = false;
+    for (size_t k = 0; k < chunks.size(); ++k) {
+        const Span &ch = chunks[k];
         const int f0 = (int)ch.first, fc = (int)ch.count;
         const long long a = frame_off[f0], nc = frame_off[f0 + fc] - a;
         long long mc = 0;
@@ -2941,11 +3006,17 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
         if (nc == 0) P.pts = nullptr;
         if (M > 0) {
             if ((rc = I.in(c, {{ch.first, ch.count}, {ch.first, ch.count}}))) return rc;             // masks | rects
-            const void *dm = host_masks ? masks_k : (const char *)masks_k + ch.first * M * hw * esz;
+            const void *dm = host_masks || runs ? masks_k : (const char *)masks_k + ch.first * M * hw * esz;
             const int32_t *dr = host_masks || !rects_k ? rects_k : rects_k + ch.first * M * 4;
             P.masks = dm;
             P.rects = use_rects ? (const int4 *)dr : nullptr;
-            if (planes) {                                   // erosion: lpf_run_wide's pack + erode into LW planes per frame
+            if (runs) {                                     // the chunk's own runs: zeroed planes, decode, every erosion iteration
+                LpfWideParams Wp;
+                memset(&Wp, 0, sizeof Wp);
+                if ((rc = wide_pack(c, D.pack, in, fc, c->W, c->H, Wp, &runs_in, &c->rle_slices[k].R))) return rc;
+                P.masks = Wp.planes;
+                P.rects = nullptr;
+            } else if (planes) {                            // erosion: lpf_run_wide's pack + erode into LW planes per frame
                 lpf_wide_input sub = *in;
                 sub.masks = dm; sub.rects = dr; sub.on_device = 1;
                 LpfWideParams Wp;
@@ -2975,8 +3046,40 @@ int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F
     }
 
     if (host_io && (rc = S.back(c))) return rc;
-    if (host_io || host_masks || pts_in) LPF_HIP(c, host_wait(c));   // host buffers may be reused
+    if (host_io || host_masks || pts_in || runs_in) LPF_HIP(c, host_wait(c));   // host buffers may be reused
+    if (rle) { c->rle_slices.clear(); A.in = nullptr; }       // (the copies have run: nothing points into the caller's arrays any more)
     return LPF_OK;
+}
+
+int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
+                   const lpf_depth_maps_outputs *out)
+{
+    int rc;
+    if ((rc = enter(c, "lpf_depth_maps", true))) return rc;
+    if (!in || !out || F < 0 || (F > 0 && !frame_off))
+        return fail(c, LPF_ERR_ARG, "depth_maps: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
+    if ((rc = check_wide_input(c, "depth_maps", -1, *in, LPF_MAX_MASKS_WIDE, "lpf_depth_maps takes 0 .. LPF_MAX_MASKS_WIDE", ""))) return rc;
+    return depth_maps_impl(c, "depth_maps", pts, frame_off, F, pts_on_device, in, nullptr, out);
+}
+
+int lpf_depth_maps_rle(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_rle_masks *masks,
+                       const lpf_depth_maps_outputs *out)
+{
+    int rc;
+    if ((rc = enter(c, "lpf_depth_maps_rle", true))) return rc;
+    if (!masks || !out || F < 0 || (F > 0 && !frame_off))
+        return fail(c, LPF_ERR_ARG, "depth_maps_rle: masks=%p out=%p frame_off=%p F=%d", (const void *)masks, (const void *)out,
+                    (const void *)frame_off, F);
+    if (masks->F != F) return fail(c, LPF_ERR_ARG, "depth_maps_rle: the run-length masks say F=%d, the call has F=%d", masks->F, F);
+    if (masks->M < 0 || masks->M > LPF_MAX_MASKS_WIDE)
+        return fail(c, LPF_ERR_ARG, "depth_maps_rle: M=%d masks per frame, lpf_depth_maps_rle takes 0 .. LPF_MAX_MASKS_WIDE = %d", masks->M,
+                    LPF_MAX_MASKS_WIDE);
+    if (masks->erode_iters < 0 || masks->reserved != 0)
+        return fail(c, LPF_ERR_ARG, "depth_maps_rle: erode_iters=%d reserved=%d", masks->erode_iters, masks->reserved);
+    lpf_wide_input in;                                      // M and erode_iters for the shared body; no dense masks behind it
+    memset(&in, 0, sizeof in);
+    in.M = masks->M; in.erode_iters = masks->erode_iters;
+    return depth_maps_impl(c, "depth_maps_rle", pts, frame_off, F, pts_on_device, &in, masks, out);
 }
 
 // ---- lpf_depth_overlays (include/lpf.h): per-car overlay images, kernels in lpf_depth_overlays.hip.h -----------------------------
@@ -3577,42 +3680,46 @@ int lpf_box_views(lpf_ctx *c, int F, const lpf_box_views_input *in, const lpf_bo
 // the call still ends with ONE host wait.
 #define LPF_FM_MAX_FRAMES 65535             // frames per launch: the grid's y
 
-int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_first_match_input *in,
-                    const lpf_first_match_outputs *out)
+// What lpf_first_match and lpf_first_match_rle share, after the checks of their own mask input (who: the messages' prefix).  rle: the
+// run-length masks of lpf_first_match_rle, not walked yet -- `in` then carries M, mh, mw, the colours and where those are (on_device),
+// a range's label planes [fc][LW][mh][mw] are decoded from the range's own runs (wide_pack's run-length branch on a
+// lpf_ctx::RleSlice) and lpf_fm_count_planes reads them; NULL: the dense masks of `in`
+static int first_match_impl(lpf_ctx *c, const char *who, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
+                            const lpf_first_match_input *in, const lpf_rle_masks *rle, const lpf_first_match_outputs *out)
 {
     int rc;
-    if ((rc = enter(c, "lpf_first_match", true))) return rc;
-    if (!in || !out || F < 0 || !frame_off)
-        return fail(c, LPF_ERR_ARG, "first_match: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
     const int M = in->M;
-    if (M < 0 || M > LPF_MAX_MASKS_WIDE)
-        return fail(c, LPF_ERR_ARG, "first_match: M=%d masks per frame, lpf_first_match takes 0 .. LPF_MAX_MASKS_WIDE = %d", M, LPF_MAX_MASKS_WIDE);
-    if (in->f32 != LPF_MASKS_U8 && in->f32 != LPF_MASKS_F32)
-        return fail(c, LPF_ERR_ARG, "first_match: f32=%d (LPF_MASKS_U8 = 0 or LPF_MASKS_F32 = 1: lpf_first_match takes dense masks only)", in->f32);
-    if (M > 0 && (!in->masks || in->mh <= 0 || in->mw <= 0))
-        return fail(c, LPF_ERR_ARG, "first_match: masks=%p mh=%d mw=%d (with M > 0 masks is required and mh, mw are > 0)", in->masks, in->mh, in->mw);
-    if (out->car_rgb && !in->colors) return fail(c, LPF_ERR_ARG, "first_match: car_rgb is asked for, colors is NULL");
+    if (out->car_rgb && !in->colors) return fail(c, LPF_ERR_ARG, "%s: car_rgb is asked for, colors is NULL", who);
     if (!out->n_car || !out->n_bg)
-        return fail(c, LPF_ERR_ARG, "first_match: n_car=%p n_bg=%p (both are required)", (void *)out->n_car, (void *)out->n_bg);
+        return fail(c, LPF_ERR_ARG, "%s: n_car=%p n_bg=%p (both are required)", who, (void *)out->n_car, (void *)out->n_bg);
     if (F == 0) return LPF_OK;
-    if ((rc = check_frames(c, "first_match", pts, frame_off, F, LPF_FM_TILE))) return rc;
+    if ((rc = check_frames(c, who, pts, frame_off, F, LPF_FM_TILE))) return rc;
+    lpf_ctx::RleIn &A = c->rle_in[0];                       // run-length masks: the whole batch checked here, before anything is enqueued
+    if (rle) {
+        if ((rc = rle_walk(c, who, rle, M > 0 ? (long long)in->mh * in->mw : 0, A.units, &A.Rtot))) return rc;
+        A.in = rle;
+    }
+    const bool runs = rle && M > 0;
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
 
     lpf_ctx::FirstMatch &D = c->fmat;
-    const size_t Ntot = (size_t)frame_off[F], nM = (size_t)M;
+    const size_t Ntot = (size_t)frame_off[F], nM = (size_t)M, LW = (nM + 31) / 32;
     const size_t plane = M > 0 ? (size_t)in->mh * (size_t)in->mw : 0, esz = in->f32 ? 4 : 1;
-    const bool host_masks = M > 0 && !in->on_device, host_pts = Ntot > 0 && !pts_on_device, host_io = !out->on_device;
+    // (host_masks: the range's masks AND colours are staged; with runs no mask is, and host_in says where the colours are)
+    const bool host_masks = M > 0 && !runs && !in->on_device, host_in = M > 0 && !in->on_device;
+    const bool host_pts = Ntot > 0 && !pts_on_device, host_io = !out->on_device;
     const bool dense = out->first_mask != nullptr;
     const bool lists = out->car_idx || out->car_mask || out->car_xyz || out->car_rgb || out->bg_idx || out->bg_xyz;
     auto given = [](const void *p, size_t b) { return p ? b : (size_t)0; };
     const size_t out_pt = given(out->first_mask, 4) + given(out->car_idx, 8) + given(out->car_mask, 4) + given(out->car_xyz, 12) +
                           given(out->car_rgb, 24) + given(out->bg_idx, 8) + given(out->bg_xyz, 12);
     const size_t per_pt = (host_pts ? 16 : 0) + (dense ? 0 : 4) + (host_io ? out_pt : 0);
-    const size_t per_fr = 16 + (host_masks ? nM * plane * esz + given(in->colors, nM * 24) : 0) + (host_io ? 24 + nM * 8 : 0);
+    const size_t per_fr = 16 + (host_masks ? nM * plane * esz : 0) + (host_in ? given(in->colors, nM * 24) : 0) +
+                          (runs ? LW * plane * 4 : 0) + (host_io ? 24 + nM * 8 : 0);
     auto pts_of = [&](size_t f0, size_t n) { return (size_t)(frame_off[f0 + n] - frame_off[f0]); };
     const std::vector<Span> ranges = plan_ranges(c, (size_t)F, LPF_FM_MAX_FRAMES, [&](size_t f0, size_t n) {
-        return pts_of(f0, n) * per_pt + pts_of(f0, n) / LPF_FM_TILE * 16 + n * per_fr;
+        return pts_of(f0, n) * per_pt + pts_of(f0, n) / LPF_FM_TILE * 16 + n * per_fr + (runs ? rle_slice_bytes(A, f0, n) : 0);
     });
     const size_t most_pts = largest(ranges, pts_of), most_f = largest(ranges, [](size_t, size_t n) { return n; });
 
@@ -3622,6 +3729,15 @@ int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int 
     if (!dense && (rc = reserve(c, D.code, most_pts * 4))) return rc;
     if ((rc = reserve(c, D.tiles, most_tiles * 16))) return rc;
     if (host_pts && (rc = reserve(c, D.pts, most_pts * 16))) return rc;       // (here, not by the first range with points: no range waits)
+    lpf_wide_input wi;                                        // run-length masks: what wide_pack reads of its input (M; no erosion)
+    memset(&wi, 0, sizeof wi);
+    wi.M = M;
+    if (runs) {                                               // the largest range's planes and run tables; every range's slice of the runs
+        if ((rc = reserve(c, D.pack.planes_a, most_f * LW * plane * 4))) return rc;
+        if ((rc = reserve(c, D.pack.rle, largest(ranges, [&](size_t f0, size_t n) { return rle_slice_bytes(A, f0, n); })))) return rc;
+        c->rle_slices.resize(ranges.size());
+        for (size_t k = 0; k < ranges.size(); ++k) rle_slice(A, ranges[k].first, ranges[k].count, c->rle_slices[k]);
+    }
     if ((rc = upload(c, D.tab.p, frame_off, (size_t)(F + 1) * 8))) return rc;
 
     LpfFmParams P;
@@ -3633,8 +3749,8 @@ int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int 
     P.tpre = P.tcnt + most_tiles;
     const char *masks_k = nullptr;                            // a range's staged masks and colours, or the caller's
     const double *colors_k = nullptr;
-    Stage I(host_masks);
-    I.add(masks_k, M > 0 ? in->masks : nullptr, nM * plane * esz, most_f);
+    Stage I(host_in);
+    I.add(masks_k, M > 0 && !runs ? in->masks : nullptr, nM * plane * esz, most_f);
     I.add(colors_k, M > 0 ? in->colors : nullptr, nM * 24, most_f);
     if ((rc = I.commit(c, D.in))) return rc;
     // a host caller's outputs are staged range by range, a device caller's are written in place
@@ -3655,8 +3771,9 @@ int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int 
     if ((rc = S.commit(c, D.out))) return rc;
 
     // ---- the ranges -----------------------------------------------------------------------------------------------------------------
-    bool pts_in = false;
-    for (const Span &r : ranges) {
+    bool pts_in = false, runs_in = false;
+    for (size_t k = 0; k < ranges.size(); ++k) {
+        const Span &r = ranges[k];
         const int f0 = (int)r.first, fc = (int)r.count;
         const long long a = frame_off[f0], nc = frame_off[f0 + fc] - a;
         long long mc = 0;                                     // points of the range's largest frame: the grid's x
@@ -3669,8 +3786,14 @@ int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int 
         if (nc == 0) P.pts = nullptr;
         if (M > 0) {
             if ((rc = I.in(c, {{r.first, r.count}, {r.first, r.count}}))) return rc;                 // masks | colors
-            P.masks = host_masks ? masks_k : masks_k + r.first * nM * plane * esz;
-            P.colors = host_masks || !colors_k ? colors_k : colors_k + r.first * nM * 3;
+            P.masks = host_masks || runs ? masks_k : masks_k + r.first * nM * plane * esz;
+            P.colors = host_in || !colors_k ? colors_k : colors_k + r.first * nM * 3;
+            if (runs) {                                       // the range's own runs: zeroed planes, then the decode
+                LpfWideParams Wp;
+                memset(&Wp, 0, sizeof Wp);
+                if ((rc = wide_pack(c, D.pack, &wi, fc, in->mw, in->mh, Wp, &runs_in, &c->rle_slices[k].R))) return rc;
+                P.masks = Wp.planes;
+            }
         }
         const Span sp = {(size_t)a, (size_t)nc}, sf = {r.first, r.count}, none = {0, 0};
         // first_mask | car_idx | car_mask | car_xyz | car_rgb | bg_idx | bg_xyz | n_valid | n_car | n_bg | mask_count: the lists as the
@@ -3680,7 +3803,8 @@ int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int 
             LPF_HIP(c, hipMemsetAsync(P.mask_count + (size_t)(f0 - P.fr_base) * nM, 0, (size_t)fc * nM * 8, c->stream));
         const dim3 g((unsigned)((mc + LPF_FM_TILE - 1) / LPF_FM_TILE), (unsigned)fc);
         if (mc > 0) {
-            with_flag(in->f32 != 0, [&](auto f32) {
+            if (rle) hipLaunchKernelGGL(lpf_fm_count_planes, g, dim3(LPF_BLOCK), 0, c->stream, P);
+            else with_flag(in->f32 != 0, [&](auto f32) {
                 typedef typename std::conditional<decltype(f32)::value, float, uint8_t>::type T;
                 hipLaunchKernelGGL(lpf_fm_count<T>, g, dim3(LPF_BLOCK), 0, c->stream, P);
             });
@@ -3694,8 +3818,52 @@ int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int 
         }
         if (host_io && (rc = S.back(c, {sp, sp, sp, sp, sp, sp, sp, sf, sf, sf, {r.first * nM, r.count * nM}}))) return rc;
     }
-    if (host_io || host_masks || pts_in) LPF_HIP(c, host_wait(c));   // host outputs filled, host inputs free to be reused
+    if (host_io || host_in || pts_in || runs_in) LPF_HIP(c, host_wait(c));   // host outputs filled, host inputs free to be reused
+    if (rle) { c->rle_slices.clear(); A.in = nullptr; }       // (the copies have run: nothing points into the caller's arrays any more)
     return LPF_OK;
+}
+
+int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_first_match_input *in,
+                    const lpf_first_match_outputs *out)
+{
+    int rc;
+    if ((rc = enter(c, "lpf_first_match", true))) return rc;
+    if (!in || !out || F < 0 || !frame_off)
+        return fail(c, LPF_ERR_ARG, "first_match: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
+    const int M = in->M;
+    if (M < 0 || M > LPF_MAX_MASKS_WIDE)
+        return fail(c, LPF_ERR_ARG, "first_match: M=%d masks per frame, lpf_first_match takes 0 .. LPF_MAX_MASKS_WIDE = %d", M, LPF_MAX_MASKS_WIDE);
+    if (in->f32 != LPF_MASKS_U8 && in->f32 != LPF_MASKS_F32)
+        return fail(c, LPF_ERR_ARG, "first_match: f32=%d (LPF_MASKS_U8 = 0 or LPF_MASKS_F32 = 1: lpf_first_match takes dense masks only)", in->f32);
+    if (M > 0 && (!in->masks || in->mh <= 0 || in->mw <= 0))
+        return fail(c, LPF_ERR_ARG, "first_match: masks=%p mh=%d mw=%d (with M > 0 masks is required and mh, mw are > 0)", in->masks, in->mh, in->mw);
+    return first_match_impl(c, "first_match", pts, frame_off, F, pts_on_device, in, nullptr, out);
+}
+
+int lpf_first_match_rle(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
+                        const lpf_first_match_rle_input *in, const lpf_first_match_outputs *out)
+{
+    int rc;
+    if ((rc = enter(c, "lpf_first_match_rle", true))) return rc;
+    if (!in || !in->masks || !out || F < 0 || !frame_off)
+        return fail(c, LPF_ERR_ARG, "first_match_rle: in=%p masks=%p out=%p frame_off=%p F=%d", (const void *)in,
+                    (const void *)(in ? in->masks : nullptr), (const void *)out, (const void *)frame_off, F);
+    const lpf_rle_masks *masks = in->masks;
+    const int M = masks->M;
+    if (masks->F != F) return fail(c, LPF_ERR_ARG, "first_match_rle: the run-length masks say F=%d, the call has F=%d", masks->F, F);
+    if (M < 0 || M > LPF_MAX_MASKS_WIDE)
+        return fail(c, LPF_ERR_ARG, "first_match_rle: M=%d masks per frame, lpf_first_match_rle takes 0 .. LPF_MAX_MASKS_WIDE = %d", M,
+                    LPF_MAX_MASKS_WIDE);
+    if (masks->erode_iters != 0)
+        return fail(c, LPF_ERR_ARG, "first_match_rle: erode_iters=%d (the first-mask labelling has no erosion: 0)", masks->erode_iters);
+    if (in->reserved != 0 || masks->reserved != 0)
+        return fail(c, LPF_ERR_ARG, "first_match_rle: reserved=%d, the masks' reserved=%d (both 0)", in->reserved, masks->reserved);
+    if (M > 0 && (in->mh <= 0 || in->mw <= 0))
+        return fail(c, LPF_ERR_ARG, "first_match_rle: mh=%d mw=%d (with M > 0 both are > 0)", in->mh, in->mw);
+    lpf_first_match_input fin;                              // M, the masks' size and the colours for the shared body; no dense masks behind it
+    memset(&fin, 0, sizeof fin);
+    fin.colors = in->colors; fin.M = M; fin.mh = in->mh; fin.mw = in->mw; fin.on_device = in->colors_on_device;
+    return first_match_impl(c, "first_match_rle", pts, frame_off, F, pts_on_device, &fin, masks, out);
 }
 
 // ---- lpf_run_cams (include/lpf.h): one scan in up to LPF_MAX_CAMS cameras, kernels in lpf_cams.hip.h ------------------------------

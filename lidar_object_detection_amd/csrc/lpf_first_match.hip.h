@@ -11,6 +11,8 @@
 //                   to the dense output or to scratch; car and background points are counted per tile with wave ballots;
 //                   mask_count[f][m] is gathered in an LDS histogram and sent with ONE integer atomicAdd per (block, non-zero bin)
 //                   into an output the call zeroed in stream order.
+//   lpf_fm_count_planes   the same for run-length masks (lpf_first_match_rle): the masks are label planes decoded from the runs, and a
+//                   point's first mask is the lowest set bit of at most ceil(M / 32) words (at its definition, below).
 //   lpf_fm_scan     one block per frame: exclusive prefix of the tile counts, and the frame's n_valid / n_car / n_bg.
 //   lpf_fm_scatter  the codes again: a point's slot is its tile's prefix + the counts of the tile's earlier (row, wave) pairs (LDS) +
 //                   the popcount of the wave's ballot below its lane, so both lists ascend within the frame.  xyz is gathered from
@@ -34,7 +36,8 @@ struct LpfFmParams {
     long long code_base;                    // code[frame_off[f] + i - code_base]
     long long out_base, fr_base;            // the per-point / per-frame outputs begin at that point / frame (staged ranges; else 0)
     const long long *foff;                  // [F + 1] the batch's frame offsets
-    const void *masks;                      // [Fc][M][mh][mw] uint8 or float32, the range's frames
+    const void *masks;                      // [Fc][M][mh][mw] uint8 or float32, the range's frames; lpf_fm_count_planes: label planes
+                                            // [Fc][ceil(M / 32)][mh][mw] uint32
     const double *colors;                   // [Fc][M][3] or null
     int *code;                              // the dense output, or scratch
     int2 *tcnt, *tpre;                      // {car, background} points per tile, their exclusive prefix in the frame: frame f0 + fl's
@@ -118,6 +121,89 @@ __global__ __launch_bounds__(LPF_BLOCK) void lpf_fm_count(const LpfFmParams P)
             for (int k = 0; k < LPF_FM_AHEAD; ++k)
                 if (((pend >> j) & 1u) && m0 + k < M && lpf_member<T, MODE>(v[j][k])) {
                     code[j] = m0 + k;
+                    pend &= ~(1u << j);
+                }
+    }
+
+    unsigned ncar = 0, nbg = 0;
+#pragma unroll
+    for (int j = 0; j < LPF_FM_PER; ++j) {
+        const long long i = i0 + j * LPF_BLOCK + tid;
+        if (i < n) P.code[a + i - P.code_base] = code[j];
+        ncar += (unsigned)__popcll(__ballot(code[j] >= 0));
+        nbg += (unsigned)__popcll(__ballot(code[j] == -1));
+        if (P.mask_count && code[j] >= 0) atomicAdd(&s_hist[code[j]], 1u);
+    }
+    if (lane == 0) { s_cnt[0][wave] = ncar; s_cnt[1][wave] = nbg; }
+    __syncthreads();
+    if (tid == 0)
+        P.tcnt[lpf_fm_tile0(P, fl, a) + blockIdx.x] = make_int2((int)(s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3]),
+                                                                   (int)(s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3]));
+    if (P.mask_count && tid < M && s_hist[tid])
+        atomicAdd(&P.mask_count[(size_t)(P.f0 + fl - P.fr_base) * M + tid], (unsigned long long)s_hist[tid]);
+}
+
+// lpf_fm_count for run-length masks (lpf_first_match_rle): P.masks are the range's label planes [Fc][LW][mh][mw] uint32, LW =
+// ceil(M / 32), bit m & 31 of plane m / 32 = mask m (zeroed, then lpf_rle_decode_wide).  The same tile, projection, clip, pend logic,
+// code store, ballots, histogram and atomics as lpf_fm_count -- kept word for word, so that the two stay comparable line by line; only
+// the walk differs: a pending row reads word w of its pixel, LPF_FM_AHEAD words in flight before the first is tested, and its code is
+// 32 w + the lowest set bit of the first nonzero word: at most LW <= 8 reads where the dense walk makes up to M.  Bits at or above M
+// are zero by construction, but nothing relies on it: a code >= M leaves the point background (and ends its walk: no lower mask has
+// it), so s_hist and mask_count are never indexed past M.
+__global__ __launch_bounds__(LPF_BLOCK) void lpf_fm_count_planes(const LpfFmParams P)
+{
+    __shared__ unsigned s_hist[LPF_BLOCK];  // M <= 256 = LPF_BLOCK
+    __shared__ unsigned s_cnt[2][4];
+    const int fl = blockIdx.y, tid = threadIdx.x, lane = lpf_lane(), wave = lpf_wave();
+    long long a, n;
+    lpf_fm_frame(P, fl, a, n);
+    const long long i0 = (long long)blockIdx.x * LPF_FM_TILE;
+    if (i0 >= n) return;
+    const int M = P.M, mw = P.mw, mh = P.mh, LW = (M + 31) >> 5;
+    s_hist[tid] = 0u;
+    __syncthreads();
+
+    const float4 *__restrict__ pts = P.pts + (a - P.pt_base);
+    float4 p[LPF_FM_PER];
+#pragma unroll
+    for (int j = 0; j < LPF_FM_PER; ++j) {
+        const long long i = i0 + j * LPF_BLOCK + tid;
+        p[j] = i < n ? pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    int code[LPF_FM_PER];
+    long long pix[LPF_FM_PER];              // the pixel's place in a plane
+    unsigned pend = 0;                      // bit j: row j is valid, inside the masks' own size, and no mask has taken it yet
+#pragma unroll
+    for (int j = 0; j < LPF_FM_PER; ++j) {
+        const long long i = i0 + j * LPF_BLOCK + tid;
+        double uf, vf, d;
+        int ui, vi;
+        lpf_project_point(P.cam, p[j].x, p[j].y, p[j].z, uf, vf, d);
+        const bool valid = lpf_pixel(P.cam, uf, vf, d, ui, vi) && i < n;
+        code[j] = valid ? -1 : -2;
+        pix[j] = 0;
+        if (valid && ui < mw && vi < mh) {
+            pix[j] = (long long)vi * mw + ui;
+            pend |= 1u << j;
+        }
+    }
+    const size_t plane = (size_t)mh * (size_t)mw;
+    const uint32_t *__restrict__ pl = (const uint32_t *)P.masks + (size_t)fl * (size_t)LW * plane;
+    for (int w0 = 0; w0 < LW; w0 += LPF_FM_AHEAD) {
+        if (!__ballot(pend != 0u)) break;                     // every lane of the wave is done
+        uint32_t v[LPF_FM_PER][LPF_FM_AHEAD];
+#pragma unroll
+        for (int j = 0; j < LPF_FM_PER; ++j)
+#pragma unroll
+            for (int k = 0; k < LPF_FM_AHEAD; ++k)
+                v[j][k] = ((pend >> j) & 1u) ? pl[(size_t)min(w0 + k, LW - 1) * plane + pix[j]] : 0u;
+#pragma unroll
+        for (int j = 0; j < LPF_FM_PER; ++j)
+#pragma unroll
+            for (int k = 0; k < LPF_FM_AHEAD; ++k)
+                if (((pend >> j) & 1u) && w0 + k < LW && v[j][k]) {
+                    const int m = 32 * (w0 + k) + (__ffs((int)v[j][k]) - 1);
+                    if (m < M) code[j] = m;
                     pend &= ~(1u << j);
                 }
     }

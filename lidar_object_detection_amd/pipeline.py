@@ -1212,22 +1212,41 @@ def _first_match_masks(frames, camera):
     return batch, Ms
 
 
+def _first_match_rle_masks(frames):
+    """Each frame's RleMasks when the batch's masks come in run-length form, None when no frame's do: _rle_frame_masks' rules, with the
+    size the frames' RleMasks share in the camera's place -- first_match reads masks at their own size.  ValueError: RleMasks of
+    differing sizes, and what _rle_frame_masks refuses."""
+    sizes = sorted({tuple(f.masks.shape[1:]) for f in frames if isinstance(f.masks, RleMasks)})
+    if not sizes:
+        return None
+    if len(sizes) > 1:
+        raise ValueError("first_match_frames: the frames' RleMasks have differing sizes (H, W) = %s: one size per batch (runs are not "
+                         "resized: decode with .to_dense())" % (sizes,))
+    return _rle_frame_masks(frames, None, size=sizes[0])
+
+
 def first_match_frames(frames, TrVeloToRect, camera, depth_max=30.0, mask_colors=None, device=0, ctx=None):
     """Same_color.py:113-132 for a list of FrameInputs: one native call (lpf_first_match) per group of up to 256 masks for the whole
     batch, no limit on the masks of a frame.  Per frame the dict label_points_first_match returns -- ``car_idx``, ``car_mask``,
     ``background_idx``, ``colored_points``, ``colored_colors``, ``full_points`` -- plus ``mask_count`` (int64, the points whose first
     mask is m, per mask of the frame).  mask_colors: one list of colours per frame (colored_colors = colour / 255.0, as the script
     computes it); None takes each frame's ``colors``.  Points: host arrays, Scans of the read-ahead reader or GPU tensors; masks: a
-    list, an array or a GPU tensor [M,h,w] AT THEIR OWN SIZE, float (> 0.5) or uint8 / bool (nonzero); frames may differ in their
-    mask counts.  A later group can only claim points no earlier group claimed: with more than 256 masks the groups' dense codes are
+    list, an array or a GPU tensor [M,h,w] AT THEIR OWN SIZE, float (> 0.5) or uint8 / bool (nonzero), or ``rle.RleMasks`` (every
+    frame of the batch, a frame without masks aside, all of one size: they go down as runs, nothing dense is made); frames may differ
+    in their mask counts.  A later group can only claim points no earlier group claimed: with more than 256 masks the groups' dense codes are
     merged and the lists are made from the merged codes.  The depth window is (0, depth_max)."""
     frames = list(frames)
     if not frames:
         return []
     if mask_colors is not None and len(mask_colors) != len(frames):
         raise ValueError("mask_colors: one list of colours per frame (%d frames, %d lists)" % (len(frames), len(mask_colors)))
-    batch, Ms = _first_match_masks(frames, camera)
-    F, M = len(frames), int(batch.shape[1])
+    rles = _first_match_rle_masks(frames)
+    if rles is not None:                                    # run-length masks: the runs go down as they are (lpf_first_match_rle)
+        batch, Ms = None, [len(r) for r in rles]
+        F, M = len(frames), max(Ms)
+    else:
+        batch, Ms = _first_match_masks(frames, camera)
+        F, M = len(frames), int(batch.shape[1])
     table = np.zeros((F, M, 3), np.float64)
     for f, fr in enumerate(frames):
         cols = fr.colors if mask_colors is None else mask_colors[f]
@@ -1238,6 +1257,12 @@ def first_match_frames(frames, TrVeloToRect, camera, depth_max=30.0, mask_colors
     ctx = ctx or get_context(device)
     ctx.set_camera(TrVeloToRect, camera.K, camera.width, camera.height, 0.0, float(depth_max))
     gpu = _is_device_tensor(batch)
+
+    def group(g):                                           # masks g .. g + 255 of every frame, as first_match takes them
+        if rles is not None:
+            return [r[g:g + LPF_MAX_MASKS_WIDE] for r in rles]
+        part = batch[:, g:g + LPF_MAX_MASKS_WIDE]
+        return part.contiguous() if gpu else np.ascontiguousarray(part)
 
     def host(a):
         return a.cpu().numpy() if _is_device_tensor(a) else a
@@ -1252,7 +1277,7 @@ def first_match_frames(frames, TrVeloToRect, camera, depth_max=30.0, mask_colors
     off = staged[0]
     out = []
     if M <= LPF_MAX_MASKS_WIDE:                             # one call: the lists as the GPU made them
-        r = ctx.first_match(None, batch, colours(table), want=("car_idx", "car_mask", "car_xyz", "car_rgb", "bg_idx", "bg_xyz", "mask_count"),
+        r = ctx.first_match(None, batch if rles is None else rles, colours(table), want=("car_idx", "car_mask", "car_xyz", "car_rgb", "bg_idx", "bg_xyz", "mask_count"),
                             staged=staged)
         r = {k: host(v) for k, v in r.items()}
         for f in range(F):
@@ -1264,9 +1289,7 @@ def first_match_frames(frames, TrVeloToRect, camera, depth_max=30.0, mask_colors
         return out
     code = None
     for g in range(0, M, LPF_MAX_MASKS_WIDE):               # groups of 256 masks, merged on the dense codes
-        part = batch[:, g:g + LPF_MAX_MASKS_WIDE]
-        part = part.contiguous() if gpu else np.ascontiguousarray(part)
-        cur = host(ctx.first_match(None, part, want=("first_mask",), staged=staged)["first_mask"])
+        cur = host(ctx.first_match(None, group(g), want=("first_mask",), staged=staged)["first_mask"])
         code = cur if code is None else np.where((code == -1) & (cur >= 0), cur + np.int32(g), code)
     for f, fr in enumerate(frames):
         cf = code[int(off[f]):int(off[f + 1])]
@@ -1593,14 +1616,15 @@ def _mask_batch(stacks, M, H, W, ctx):
     return batch
 
 
-def _rle_frame_masks(frames, camera):
+def _rle_frame_masks(frames, camera, size=None):
     """Each frame's RleMasks when the batch's masks come in run-length form (a frame without masks -- None, an empty list -- gets an
     empty one), None when no frame's do.  ValueError, before anything reaches the library: a batch that mixes RleMasks and dense
-    masks, and RleMasks of another size than the camera's (runs are not resized)."""
+    masks, and RleMasks of another size than the camera's (runs are not resized) -- or than ``size`` = (H, W), for a call that reads
+    masks at a size of their own."""
     is_rle = [isinstance(f.masks, RleMasks) for f in frames]
     if not any(is_rle):
         return None
-    H, W = camera.height, camera.width
+    H, W = size or (camera.height, camera.width)
     out = []
     for f, r in zip(frames, is_rle):
         if r:
@@ -2272,24 +2296,33 @@ def depth_maps_frames(frames, TrVeloToRect, camera, depth_max=30.0, device=0, ct
     """seg_with_pointcloud.py:160-170's per-car depth maps of a list of FrameInputs in one native call (lpf_depth_maps) per group
     of up to 256 masks: per frame ``[(car_id, SparseDepthMap)]``, car_id = i + 1 over the frame's masks, each map equal to
     ``per_car_depth_maps``' depthMap (``to_dense()``).  Points: host arrays, Scans of the read-ahead reader or GPU tensors; masks: a
-    list, an array or a GPU tensor [M,H,W] at the camera's size, float (> 0.5) or uint8 / bool (nonzero); frames may differ in
-    their mask counts.  The depth window is (0, depth_max)."""
+    list, an array or a GPU tensor [M,H,W] at the camera's size, float (> 0.5) or uint8 / bool (nonzero), or ``rle.RleMasks`` (every
+    frame of the batch, a frame without masks aside: they go down as runs, nothing dense is made); frames may differ in their mask
+    counts.  The depth window is (0, depth_max)."""
     frames = list(frames)
     if not frames:
         return []
     ctx = ctx or get_context(device)
     ctx.set_camera(TrVeloToRect, camera.K, camera.width, camera.height, 0.0, float(depth_max))
     H, W = int(camera.height), int(camera.width)
-    batch, Ms, flt = _depth_map_masks(frames, H, W)
-    M = batch.shape[1]
+    rles = _rle_frame_masks(frames, camera)
+    if rles is not None:                                    # run-length masks: the runs go down as they are (lpf_depth_maps_rle)
+        Ms = [len(r) for r in rles]
+        M = max(Ms)
+    else:
+        batch, Ms, flt = _depth_map_masks(frames, H, W)
+        M = batch.shape[1]
     out = [[] for _ in frames]
     if M == 0:
         return out
     pts = [f.points for f in frames]
     for g in range(0, M, LPF_MAX_MASKS_WIDE):                   # groups of 256 masks, concatenated
-        part = batch[:, g:g + LPF_MAX_MASKS_WIDE]
-        part = part.contiguous() if _is_device_tensor(part) else np.ascontiguousarray(part)
-        res = ctx.depth_maps(pts, part, binarize="gt0.5" if flt else "astype")
+        if rles is not None:
+            res = ctx.depth_maps(pts, [r[g:g + LPF_MAX_MASKS_WIDE] for r in rles])
+        else:
+            part = batch[:, g:g + LPF_MAX_MASKS_WIDE]
+            part = part.contiguous() if _is_device_tensor(part) else np.ascontiguousarray(part)
+            res = ctx.depth_maps(pts, part, binarize="gt0.5" if flt else "astype")
         for f, cars in enumerate(res):
             for j, (pix, dep, pid) in enumerate(cars):
                 i = g + j

@@ -1,0 +1,190 @@
+"""Run-length masks in the two analysis calls (lpf_depth_maps_rle, lpf_first_match_rle) without a GPU: the header declares both calls
+and the new struct with the ABI and every existing layout unchanged, the ctypes mirror matches the C layout, the library exports both
+symbols and carries lpf_fm_count_planes, every refusal of LpfContext.depth_maps / first_match and of pipeline.depth_maps_frames /
+first_match_frames is a ValueError raised on a context that never opened a device, and the runs staged for ragged frames are the ones
+the independent NumPy restatement of tests/rle_ref.py decodes to the same masks."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import rle_ref as R
+from lidar_object_detection_amd import _build, _native, pipeline
+from lidar_object_detection_amd._native import (DepthMapsOutputs, FirstMatchInput, FirstMatchOutputs, FirstMatchRleInput, RleMasksInput,
+                                                WideInput)
+from lidar_object_detection_amd.rle import RleMasks
+from test_wide_api import HEADER, _c_layout, _NoGpu
+
+
+def test_header_declares_the_calls_and_keeps_the_abi():
+    raw = open(HEADER).read()
+    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    assert re.search(r"\bint\s+lpf_depth_maps_rle\s*\(\s*lpf_ctx\s*\*\s*ctx\s*,\s*const\s+float\s*\*\s*pts\s*,\s*const\s+int64_t\s*\*\s*frame_off\s*,"
+                     r"\s*int\s+F\s*,\s*int\s+pts_on_device\s*,\s*const\s+lpf_rle_masks\s*\*\s*masks\s*,"
+                     r"\s*const\s+lpf_depth_maps_outputs\s*\*\s*out\s*\)\s*;", text)
+    m = re.search(r"typedef\s+struct\s+lpf_first_match_rle_input\s*\{(.*?)\}\s*lpf_first_match_rle_input\s*;", text, flags=re.S)
+    assert m, "lpf_first_match_rle_input is not declared"
+    assert re.search(r"\bconst\s+lpf_rle_masks\s*\*\s*masks\s*;", m.group(1)) and re.search(r"\bconst\s+double\s*\*\s*colors\s*;", m.group(1))
+    for f in ("mh, mw", "colors_on_device", "reserved"):
+        assert re.search(r"\bint32_t\s+%s\s*;" % f, m.group(1)), f
+    assert re.search(r"\bint\s+lpf_first_match_rle\s*\(\s*lpf_ctx\s*\*\s*ctx\s*,\s*const\s+float\s*\*\s*pts\s*,\s*const\s+int64_t\s*\*\s*frame_off\s*,"
+                     r"\s*int\s+F\s*,\s*int\s+pts_on_device\s*,\s*const\s+lpf_first_match_rle_input\s*\*\s*in\s*,"
+                     r"\s*const\s+lpf_first_match_outputs\s*\*\s*out\s*\)\s*;", text)
+    assert re.search(r"#define\s+LPF_ABI_VERSION\s+8\b", raw)
+    assert "lpf_depth_maps_rle" in _native.EXPORTED and "lpf_first_match_rle" in _native.EXPORTED
+    # the paragraphs about where the form is taken point to the two calls
+    para = raw[raw.index("Not taken in this form"):raw.index("typedef struct lpf_rle_masks")]
+    assert "lpf_depth_maps_rle" in para and "lpf_first_match_rle" in para
+    forms = raw[raw.index("The forms of a lpf_wide_input's masks"):raw.index("#define LPF_MASKS_U8")]
+    assert "lpf_depth_maps_rle" in forms and "lpf_first_match_rle" in forms
+
+
+@pytest.mark.parametrize("cls,struct,size,offsets", [
+    (FirstMatchRleInput, "lpf_first_match_rle_input", 32, [0, 8, 16, 20, 24, 28]),
+    # unchanged: the structs the two calls share with the dense ones, and the run-length struct itself
+    (RleMasksInput, "lpf_rle_masks", 32, [0, 8, 16, 20, 24, 28]),
+    (WideInput, "lpf_wide_input", 40, [0, 8, 16, 20, 24, 28, 32, 36]),
+    (FirstMatchInput, "lpf_first_match_input", 40, [0, 8, 16, 20, 24, 28, 32, 36]),
+    (DepthMapsOutputs, "lpf_depth_maps_outputs", 64, [0, 8, 16, 24, 32, 40, 48, 56, 60]),
+    (FirstMatchOutputs, "lpf_first_match_outputs", 96, [0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 80, 88, 92]),
+])
+def test_struct_layouts(tmp_path, cls, struct, size, offsets):
+    names = [f[0] for f in cls._fields_]
+    lay = _c_layout(tmp_path, struct, names)
+    assert lay["sizeof"] == ctypes.sizeof(cls) == size
+    assert [lay[n] for n in names] == [getattr(cls, n).offset for n in names] == offsets
+
+
+@pytest.mark.skipif(not os.path.exists(_build.LIB), reason="liblpf.so has not been built")
+def test_library_exports_the_symbols_and_the_kernel():
+    syms = subprocess.run(["nm", "-D", "--defined-only", _build.LIB], check=True, capture_output=True, text=True).stdout
+    assert re.search(r"\bT lpf_depth_maps_rle\b", syms) and re.search(r"\bT lpf_first_match_rle\b", syms)
+    assert re.search(r"\bT lpf_depth_maps\b", syms) and re.search(r"\bT lpf_first_match\b", syms)
+    every = subprocess.run(["nm", _build.LIB], check=True, capture_output=True, text=True).stdout
+    assert "lpf_fm_count_planes" in every
+    for inst in ("lpf_fm_countIhE", "lpf_fm_countIfE", "lpf_fm_scan", "lpf_fm_scatter", "lpf_rle_decode_wide"):
+        assert inst in every, inst                            # the dense count's two instantiations and the shared kernels are still there
+
+
+def _rle(M, H=48, W=64, seed=0):
+    return RleMasks.from_dense((np.random.default_rng(seed).random((M, H, W)) < 0.1).astype(np.uint8))
+
+
+_PTS = [np.zeros((10, 4), np.float32)]
+
+
+@pytest.mark.parametrize("what", ["mixed list", "mixed list, array first", "rects", "binarize", "wrong size", "257 masks", "two frames for one",
+                                  "erode_iters", "spoiled runs"])
+def test_depth_maps_refuses_before_the_gpu(what):
+    ctx = _NoGpu()                                           # 64 x 48; any native call would be an AttributeError
+    good, dense = _rle(40), np.zeros((40, 48, 64), np.uint8)
+    frames, kw = _PTS, {}
+    if what == "mixed list":
+        frames, masks = _PTS * 2, [good, dense]
+    elif what == "mixed list, array first":
+        frames, masks = _PTS * 2, [dense, good]
+    elif what == "rects":
+        masks, kw = good, dict(rects=np.zeros((1, 40, 4), np.int32))
+    elif what == "binarize":
+        masks, kw = good, dict(binarize="astype")             # (depth_maps' default is "gt0.5")
+    elif what == "wrong size":
+        masks = _rle(40, W=63)
+    elif what == "257 masks":
+        masks = _rle(257)
+    elif what == "two frames for one":
+        masks = [good, good]
+    elif what == "erode_iters":
+        masks, kw = good, dict(erode_iters=-1)
+    else:
+        masks = _rle(40)
+        masks.runs = np.array([[64 * 48 - 2, 3]], np.int32)
+        masks.run_off = np.array([0] + [1] * 40, np.int64)
+    with pytest.raises(ValueError) as e:
+        ctx.depth_maps(frames, masks, **kw)
+    if what in ("rects", "binarize", "wrong size", "257 masks", "two frames for one", "spoiled runs"):
+        assert str(e.value).startswith("depth_maps: "), str(e.value)
+
+
+@pytest.mark.parametrize("what", ["mixed list", "mixed list, array first", "rects", "binarize", "differing sizes", "257 masks",
+                                  "two frames for one", "erode_iters", "spoiled runs", "colors"])
+def test_first_match_refuses_before_the_gpu(what):
+    ctx = _NoGpu()
+    good, dense = _rle(40), np.zeros((40, 48, 64), np.uint8)
+    frames, kw = _PTS, {}
+    if what == "mixed list":
+        frames, masks = _PTS * 2, [good, dense]
+    elif what == "mixed list, array first":
+        frames, masks = _PTS * 2, [dense, good]
+    elif what == "rects":
+        masks, kw = good, dict(rects=np.zeros((1, 40, 4), np.int32))
+    elif what == "binarize":
+        masks, kw = good, dict(binarize="astype")
+    elif what == "differing sizes":
+        frames, masks = _PTS * 2, [good, _rle(40, H=24, W=32)]
+    elif what == "257 masks":
+        masks = _rle(257)
+    elif what == "two frames for one":
+        masks = [good, good]
+    elif what == "erode_iters":
+        masks, kw = good, dict(erode_iters=1)
+    elif what == "colors":
+        masks, kw = good, dict(colors=np.zeros((1, 39, 3)))
+    else:
+        masks = _rle(40)
+        masks.runs = np.array([[64 * 48 - 2, 3]], np.int32)
+        masks.run_off = np.array([0] + [1] * 40, np.int64)
+    with pytest.raises(ValueError) as e:
+        ctx.first_match(frames, masks, **kw)
+    assert str(e.value).startswith("first_match: "), str(e.value)
+
+
+def test_first_match_takes_masks_of_another_size_than_the_camera():
+    # the shared size becomes mh x mw: 24 x 32 masks on the 48 x 64 camera are staged, not refused
+    a, b = _rle(3, H=24, W=32, seed=1), _rle(5, H=24, W=32, seed=2)
+    device, M, mh, mw, (runs, off, inp), colors = _native.LpfContext.first_match_rle_batch([a, b], np.zeros((2, 5, 3)), 2)
+    assert (device, M, mh, mw) == (None, 5, 24, 32) and colors.dtype == np.float64 and colors.shape == (2, 5, 3)
+    assert (inp.F, inp.M, inp.erode_iters, inp.reserved) == (2, 5, 0, 0) and inp.runs == runs.ctypes.data and inp.run_off == off.ctypes.data
+    assert _native.LpfContext.first_match_rle_batch(np.zeros((3, 24, 32), np.uint8), None, 1) is None
+    assert _native.LpfContext.first_match_rle_batch([np.zeros((3, 24, 32), np.uint8)], None, 1) is None
+
+
+def test_staged_runs_for_ragged_frames_match_the_reference():
+    a, b, c = _rle(40, seed=1), _rle(0), _rle(256, seed=2)
+    # depth maps: the camera's size, the default binarize, erosion in the struct
+    (runs, off, inp), M, form, dev, rects = _native.wide_rle_batch([a, b, c], 3, 48, 64, erode_iters=2, binarize="gt0.5", who="depth_maps",
+                                                                   default_binarize="gt0.5")
+    assert (M, form, dev, rects) == (256, "rle", False, None) and (inp.F, inp.M, inp.erode_iters, inp.reserved) == (3, 256, 2, 0)
+    _, _, _, _, (runs2, off2, inp2), _ = _native.LpfContext.first_match_rle_batch([a, b, c], None, 3)
+    assert np.array_equal(runs, runs2) and np.array_equal(off, off2) and (inp2.F, inp2.M, inp2.erode_iters) == (3, 256, 0)
+    assert runs.dtype == np.int32 and off.dtype == np.int64 and off.shape == (3 * 256 + 1,)
+    assert off[0] == 0 and (np.diff(off) >= 0).all() and off[-1] == len(runs) == len(a.runs) + len(c.runs)
+    for f, (r, m) in enumerate(((a, 40), (b, 0), (c, 256))):
+        dense = R.masks_to_dense(runs, off[f * M:(f + 1) * M + 1], M, 48, 64)
+        ref = np.stack([R.runs_to_dense([tuple(int(v) for v in x) for x in r.runs[int(r.run_off[i]):int(r.run_off[i + 1])]], 48, 64)
+                        for i in range(m)]) if m else np.zeros((0, 48, 64), np.uint8)
+        assert np.array_equal(dense[:m], ref) and not dense[m:].any(), f
+
+
+class _Cam:
+    width, height = 64, 48
+    K = np.eye(3)
+
+
+class _Ctx(_NoGpu):                                          # (the camera is set before the masks are looked at)
+    def set_camera(self, *a):
+        pass
+
+
+@pytest.mark.parametrize("entry", ["depth_maps_frames", "first_match_frames"])
+@pytest.mark.parametrize("what", ["mixed", "wrong size"])
+def test_pipeline_refuses_before_the_gpu(entry, what):
+    pts = np.zeros((10, 4), np.float32)
+    dense = np.zeros((2, 48, 64), np.uint8)
+    frames = {"mixed": [pipeline.FrameInputs(1, pts, _rle(2), colors=[(1, 2, 3)] * 2), pipeline.FrameInputs(2, pts, dense, colors=[(1, 2, 3)] * 2)],
+              "wrong size": [pipeline.FrameInputs(1, pts, _rle(2), colors=[(1, 2, 3)] * 2),
+                             pipeline.FrameInputs(2, pts, _rle(2, H=24, W=32), colors=[(1, 2, 3)] * 2)]}[what]
+    with pytest.raises(ValueError):
+        getattr(pipeline, entry)(frames, np.eye(4), _Cam(), ctx=_Ctx())
