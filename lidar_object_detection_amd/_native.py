@@ -60,6 +60,11 @@ class RleMasksInput(ctypes.Structure):
     _fields_ = [("runs", _P), ("run_off", _P), ("F", ctypes.c_int32), ("M", ctypes.c_int32), ("erode_iters", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
 
+    @classmethod
+    def of(cls, runs, run_off, F, M, erode_iters=0):
+        """The struct over rle_batch's tables (which must stay alive as long as it is used)"""
+        return cls(runs.ctypes.data if len(runs) else None, run_off.ctypes.data, F, M, int(erode_iters), 0)
+
 
 class WideOutputs(ctypes.Structure):
     """lpf_wide_outputs (include/lpf.h)"""
@@ -185,9 +190,14 @@ class CamInput(ctypes.Structure):
                 ("corners_velo", _P), ("box_off", _P), ("boxes_on_device", ctypes.c_int32), ("oriented", ctypes.c_int32)]
 
 
+# A pass's masks, checked (wide_mask_batch, wide_rle_batch).  is_float: False / True for dense masks [F,M,H,W], or "rle" for the
+# run-length form, whose ``masks`` is (runs, run_off, RleMasksInput), on_device False and rects None
+MaskBatch = collections.namedtuple("MaskBatch", "masks M is_float on_device rects")
+
+
 def wide_mask_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", binarize_codes=None):
-    """Checks the masks of a wide run before anything reaches the GPU: ``(masks [F,M,H,W], M, is_float, on_device, rects [F,M,4] or
-    None)``.  masks: [M,H,W] (F = 1) or [F,M,H,W], uint8 / bool or float32, a NumPy array or a contiguous GPU tensor; M <= 256."""
+    """Checks the masks of a wide run before anything reaches the GPU: MaskBatch ``(masks [F,M,H,W], M, is_float, on_device, rects
+    [F,M,4] or None)``.  masks: [M,H,W] (F = 1) or [F,M,H,W], uint8 / bool or float32, a NumPy array or a contiguous GPU tensor; M <= 256."""
     codes = binarize_codes or {"astype": 0, "v3": 1, "gt0.5": 2}
     if binarize not in codes:
         raise ValueError("binarize must be one of %s" % sorted(codes))
@@ -228,10 +238,22 @@ def wide_mask_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype"
                 raise ValueError("device rects must be a contiguous int32 tensor")
         else:
             rects = np.ascontiguousarray(np.asarray(rects).reshape(rshape), dtype=np.int32)
-    return masks, M, is_f, dev, rects
+    return MaskBatch(masks, M, is_f, dev, rects)
 
 
 LPF_MASKS_U8, LPF_MASKS_F32, LPF_MASKS_RLE = 0, 1, 2           # lpf_wide_input.f32 (include/lpf.h)
+
+
+def rle_frames(masks, who):
+    """Is this ``masks`` argument in run-length form -- one rle.RleMasks, or a list with one per frame?  The per-frame list of them, or
+    None for anything else; ValueError (``who``: the message's prefix) for a list that mixes RleMasks and arrays."""
+    from .rle import RleMasks
+    frames = [masks] if isinstance(masks, RleMasks) else list(masks) if isinstance(masks, (list, tuple)) else []
+    if not any(isinstance(m, RleMasks) for m in frames):
+        return None
+    if not all(isinstance(m, RleMasks) for m in frames):
+        raise ValueError("%s: the list mixes RleMasks and arrays: one form per call (.to_dense() or RleMasks.from_dense)" % who)
+    return frames
 
 
 def wide_rle_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", max_masks=LPF_MAX_MASKS_WIDE, who="run_wide",
@@ -241,23 +263,19 @@ def wide_rle_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype",
     in that form.  Ragged M is padded with empty masks.  ValueError: a list that mixes RleMasks and arrays, another size than H x W,
     ``rects`` (runs need none), a ``binarize`` other than the entry point's default (``default_binarize``), more than max_masks masks,
     another frame count than F."""
-    from .rle import RleMasks
-    if not isinstance(masks, RleMasks):
-        if not isinstance(masks, (list, tuple)) or not any(isinstance(m, RleMasks) for m in masks):
-            return None
-        if not all(isinstance(m, RleMasks) for m in masks):
-            raise ValueError("%s: the list mixes RleMasks and arrays: one form per call (.to_dense() or RleMasks.from_dense)" % who)
+    frames = rle_frames(masks, who)
+    if frames is None:
+        return None
     if rects is not None:
         raise ValueError("%s: rects given with RleMasks (the runs say where the masks are)" % who)
     if binarize != default_binarize:
         raise ValueError("%s: binarize=%r with RleMasks (a pixel is a member or it is not)" % (who, binarize))
     if int(erode_iters) != erode_iters or erode_iters < 0:
         raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
-    runs, run_off, Fr, M = LpfContext.rle_batch(masks, H, W, max_masks, who)
+    runs, run_off, Fr, M = LpfContext.rle_batch(frames, H, W, max_masks, who)
     if Fr != F:
         raise ValueError("%s: RleMasks for %d frames, the batch has %d" % (who, Fr, F))
-    inp = RleMasksInput(runs.ctypes.data if len(runs) else None, run_off.ctypes.data, F, M, int(erode_iters), 0)
-    return (runs, run_off, inp), M, "rle", False, None
+    return MaskBatch((runs, run_off, RleMasksInput.of(runs, run_off, F, M, erode_iters)), M, "rle", False, None)
 
 
 class FrameJob(ctypes.Structure):
@@ -960,7 +978,7 @@ class LpfContext:
         runs, run_off, F, M = self.rle_batch(frames_masks, self.H, self.W)
         if int(erode_iters) < 0:
             raise ValueError("erode_iters must be >= 0, got %r" % (erode_iters,))
-        inp = RleMasksInput(runs.ctypes.data if len(runs) else None, run_off.ctypes.data, F, M, int(erode_iters), 0)
+        inp = RleMasksInput.of(runs, run_off, F, M, erode_iters)
         self._check(self._lib.lpf_set_masks_rle(self._h, ctypes.byref(inp)))
         self.F_masks, self.M = F, M
 
@@ -1303,7 +1321,7 @@ class LpfContext:
             erode = cam.get("erode_iters", 0)
             batch = wide_rle_batch(masks, F, H, W, cam.get("rects"), erode, binarize, max_masks, "%s: camera %d" % (who, k)) or \
                 wide_mask_batch(masks, F, H, W, cam.get("rects"), erode, binarize, self.BINARIZE)
-            masks, M, rects = batch[0], batch[1], batch[4]
+            masks, M, rects = batch.masks, batch.M, batch.rects
             if M > max_masks:
                 raise ValueError("camera %d has %d masks per frame: a multi-camera pass takes at most %d per camera (run_wide takes more)"
                                  % (k, M, max_masks))
@@ -1417,7 +1435,7 @@ class LpfContext:
             raise ValueError("no frames")
         batch = wide_rle_batch(masks, F, self.H, self.W, rects, erode_iters, binarize) or \
             wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
-        M = batch[1]
+        M = batch.M
         off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the run returns)
         n = int(off[-1])
         inp = WideInput()
@@ -1459,10 +1477,10 @@ class LpfContext:
             raise ValueError("cap must be a non-negative integer, got %r" % (cap,))
         batch = wide_rle_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, who="depth_maps", default_binarize="gt0.5") or \
             wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
-        M = batch[1]
+        M = batch.M
         off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the call returns)
-        if batch[2] == "rle":                               # the lpf_rle_masks itself: the call of its own
-            native, inp = self._lib.lpf_depth_maps_rle, batch[0][2]
+        if batch.is_float == "rle":                         # the lpf_rle_masks itself: the call of its own
+            native, inp = self._lib.lpf_depth_maps_rle, batch.masks[2]
         else:
             native, inp = self._lib.lpf_depth_maps, WideInput()
             self._wide_input(inp, batch, binarize, erode_iters)
@@ -1976,19 +1994,26 @@ class LpfContext:
             if masks.dtype.kind not in "buif":
                 raise ValueError("first_match: masks must be uint8, bool or float, got %s" % name)
             masks = np.ascontiguousarray(masks, dtype=np.float32 if f32 else np.uint8)
-        if colors is not None:
-            if not dev:
-                colors = np.ascontiguousarray(colors, dtype=np.float64)
-            cs = tuple(colors.shape)
-            if len(cs) == 2 and F == 1:
-                colors, cs = colors[None], (1,) + cs
-            if cs != (F, M, 3):
-                raise ValueError("first_match: colors [F,M,3] = %s, got %s" % ((F, M, 3), cs))
-            if dev:
-                if str(colors.dtype) != "torch.float64":
-                    raise ValueError("first_match: GPU colors must be float64, got %s" % colors.dtype)
-                colors = colors.contiguous()
-        return dev, M, mh, mw, int(f32), masks, colors
+        return dev, M, mh, mw, int(f32), masks, LpfContext._first_match_colors(colors, F, M, dev)
+
+    @staticmethod
+    def _first_match_colors(colors, F, M, dev):
+        """first_match's colours [F,M,3] (or [M,3] for one frame; None: none), contiguous float64: a host array (any numbers), or with
+        ``dev`` a GPU tensor, which must be float64."""
+        if colors is None:
+            return None
+        if not dev:
+            colors = np.ascontiguousarray(colors, dtype=np.float64)
+        cs = tuple(colors.shape)
+        if len(cs) == 2 and F == 1:
+            colors, cs = colors[None], (1,) + cs
+        if cs != (F, M, 3):
+            raise ValueError("first_match: colors [F,M,3] = %s, got %s" % ((F, M, 3), cs))
+        if dev:
+            if str(colors.dtype) != "torch.float64":
+                raise ValueError("first_match: GPU colors must be float64, got %s" % colors.dtype)
+            colors = colors.contiguous()
+        return colors
 
     @staticmethod
     def first_match_rle_batch(masks, colors, F, out=None):
@@ -1998,13 +2023,9 @@ class LpfContext:
         masks, up to LPF_MAX_MASKS_WIDE.  The masks stay host memory; device: where the outputs go -- the GPU of ``out``'s tensors or
         of GPU ``colors``, else None (NumPy).  ValueError: a list that mixes RleMasks and arrays, frames of differing sizes, more than
         256 masks, another frame count, colours of another shape or dtype."""
-        from .rle import RleMasks
-        if not isinstance(masks, RleMasks):
-            if not isinstance(masks, (list, tuple)) or not any(isinstance(m, RleMasks) for m in masks):
-                return None
-            if not all(isinstance(m, RleMasks) for m in masks):
-                raise ValueError("first_match: the list mixes RleMasks and arrays: one form per call (.to_dense() or RleMasks.from_dense)")
-        frames = [masks] if isinstance(masks, RleMasks) else list(masks)
+        frames = rle_frames(masks, "first_match")
+        if frames is None:
+            return None
         if len(frames) != F:
             raise ValueError("first_match: RleMasks for %d frames, the batch has %d" % (len(frames), F))
         sizes = sorted({tuple(r.shape[1:]) for r in frames})
@@ -2013,24 +2034,13 @@ class LpfContext:
                              % (sizes,))
         mh, mw = sizes[0] if sizes else (1, 1)
         runs, run_off, _, M = LpfContext.rle_batch(frames, mh, mw, LPF_MAX_MASKS_WIDE, "first_match")
-        inp = RleMasksInput(runs.ctypes.data if len(runs) else None, run_off.ctypes.data, F, M, 0, 0)
-        device = None
-        if colors is not None:
-            if _is_torch(colors) and colors.is_cuda:
-                if str(colors.dtype) != "torch.float64":
-                    raise ValueError("first_match: GPU colors must be float64, got %s" % colors.dtype)
-                colors, device = colors.contiguous(), colors.device
-            else:
-                colors = np.ascontiguousarray(colors, dtype=np.float64)
-            cs = tuple(colors.shape)
-            if len(cs) == 2 and F == 1:
-                colors, cs = colors[None], (1,) + cs
-            if cs != (F, M, 3):
-                raise ValueError("first_match: colors [F,M,3] = %s, got %s" % ((F, M, 3), cs))
+        on_gpu = _is_torch(colors) and colors.is_cuda
+        device = colors.device if on_gpu else None
+        colors = LpfContext._first_match_colors(colors, F, M, on_gpu)
         for t in (out or {}).values():
             if _is_torch(t) and t.is_cuda:
                 device = t.device
-        return device, M, int(mh), int(mw), (runs, run_off, inp), colors
+        return device, M, int(mh), int(mw), (runs, run_off, RleMasksInput.of(runs, run_off, F, M)), colors
 
     def first_match(self, pts_per_frame, masks, colors=None, want=None, out=None, staged=None, rects=None, binarize=None, erode_iters=0):
         """Same_color.py:113-132's exclusive labels of a batch of frames in ONE native call (lpf_first_match): every valid point goes
@@ -2062,40 +2072,33 @@ class LpfContext:
             raise ValueError("first_match: car_rgb is wanted, colors is None")
         off, pts_ptr, pts_dev, _keep = staged or self._stage_points(pts_per_frame)      # (_keep: alive until the call returns)
         F, Ntot = len(off) - 1, int(off[-1])
+        # the two forms differ in the input struct, the native function, where the outputs go and what must outlive the call
         rle = self.first_match_rle_batch(masks, colors, F, out)
         if rle is not None:
             device, M, mh, mw, tables, colors = rle
-            inp, o = FirstMatchRleInput(), FirstMatchOutputs()
-            res = self._outputs("first_match", o, want, self._FIRST_MATCH_OUT, dict(N=Ntot, F=F, M=M), device, out)
-            if Ntot == 0:
-                for w in self._FIRST_MATCH_LISTS + ("first_mask",):
-                    setattr(o, w, None)
+            native, inp = "lpf_first_match_rle", FirstMatchRleInput()
             inp.masks = ctypes.pointer(tables[2])
-            inp.colors = _ptr(colors) if (colors is not None and M) else None
-            if inp.colors is None:
-                o.car_rgb = None
-            inp.mh, inp.mw, inp.colors_on_device = mh, mw, int(_is_torch(colors))
-            if F:
-                self._call_in_order(device, self._lib.lpf_first_match_rle, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp),
-                                    ctypes.byref(o))
-                if device is not None:
-                    self._lent.append((_keep, tables, colors))      # (staged points, tables and colours: alive until the work has run)
-            res["frame_off"] = off
-            return res
-        dev, M, mh, mw, f32, masks, colors = self.first_match_batch(masks, colors, F)
-        device = masks.device if dev else None
-        inp, o = FirstMatchInput(), FirstMatchOutputs()
+            inp.colors_on_device = int(_is_torch(colors))
+            lend = [(_keep, tables, colors)] if device is not None else []      # (staged points, tables and colours: alive until the work has run)
+        else:
+            dev, M, mh, mw, f32, masks, colors = self.first_match_batch(masks, colors, F)
+            device = masks.device if dev else None
+            native, inp = "lpf_first_match", FirstMatchInput()
+            inp.masks = _ptr(masks) if M else None
+            inp.M, inp.f32, inp.on_device = M, f32, int(dev)
+            lend = []
+        o = FirstMatchOutputs()
         res = self._outputs("first_match", o, want, self._FIRST_MATCH_OUT, dict(N=Ntot, F=F, M=M), device, out)
         if Ntot == 0:                                       # (an empty array has no address: nothing would be written to it)
             for w in self._FIRST_MATCH_LISTS + ("first_mask",):
                 setattr(o, w, None)
-        inp.masks = _ptr(masks) if M else None
+        inp.mh, inp.mw = mh, mw
         inp.colors = _ptr(colors) if (colors is not None and M) else None
         if inp.colors is None:
             o.car_rgb = None                                # (no mask, no car point: nothing to gather)
-        inp.M, inp.mh, inp.mw, inp.f32, inp.on_device = M, mh, mw, f32, int(dev)
         if F:
-            self._call_in_order(device, self._lib.lpf_first_match, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o))
+            self._call_in_order(device, getattr(self._lib, native), pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o))
+            self._lent.extend(lend)
         res["frame_off"] = off
         return res
 

@@ -106,20 +106,20 @@ struct lpf_ctx {
     // masks -> label images
     DevBuf mask_stage;
     DevBuf rle_stage;                 // lpf_set_masks_rle: [runs | work units | run_off] of the call being decoded
-    std::vector<int2> rle_units;      // ... its work units while the host emits them (kept for its capacity)
-    // run-length masks of a wide or multi-camera pass (LPF_MASKS_RLE): the checked input and its work units, one record per camera
-    // (lpf_run_wide: record 0) -- host storage of its own for every camera until the call's host wait; the tables are staged in the
-    // pass's own buffers (Wide::rle, Cams::rle), never in rle_stage
+    // run-length masks, walked (rle_walk): the checked input and its work units (kept for their capacity).  One record per camera of a
+    // multi-camera pass; lpf_set_masks_rle, lpf_run_wide and the two analysis calls use record 0.  Host storage of its own for every
+    // camera until the call's host wait.  The tables are staged (rle_stage_tables) in rle_stage by lpf_set_masks_rle, in the pass's own
+    // buffers (Wide::rle, Cams::rle) by everyone else
     struct RleIn {
         const lpf_rle_masks *in = nullptr;        // NULL: this camera's masks are dense (or there are none)
         long long Rtot = 0;
         std::vector<int2> units;
     } rle_in[LPF_NSETS];
-    // run-length masks of lpf_depth_maps_rle / lpf_first_match_rle: the whole batch is checked into rle_in[0]; a range of frames decodes
-    // its own slice of it -- the range's runs (the caller's, from `sub.runs` on), run_off rebased to them (off) and the units of those
-    // runs with their run index rebased (R.units), as ONE lpf_rle_masks of the range's frames (sub; R.in points at it).  One record per
-    // range, sized before the first launch and kept until the call's host wait (then cleared): the copies of a range's tables read them
-    // in stream order
+    // run-length masks of lpf_depth_maps_rle / lpf_first_match_rle (RleCall): the whole batch is checked into rle_in[0]; a range of
+    // frames decodes its own slice of it -- the range's runs (the caller's, from `sub.runs` on), run_off rebased to them (off) and the
+    // units of those runs with their run index rebased (R.units), as ONE lpf_rle_masks of the range's frames (sub; R.in points at it).
+    // One record per range, sized before the first launch and kept until the call returns, past its host wait (the copies of a range's
+    // tables read them in stream order); RleCall then clears them and rle_in[0].in, on every way out
     struct RleSlice {
         lpf_rle_masks sub;
         std::vector<int64_t> off;
@@ -1044,9 +1044,19 @@ int set_boxes_impl(lpf_ctx *c, const double *corners, int on_device, const int32
     return LPF_OK;
 }
 
+// What `iters` erosion iterations come to under the context's element (lpf_set_erosion_element): the 1 x 1 element is the identity, any
+// number of iterations; a k x k element other than the 3 x 3 cross takes its own kernels (the _k ones)
+struct Erosion { int iters; bool element; };
+Erosion erosion(const lpf_ctx *c, int iters)
+{
+    if (c->erode_k == 1) iters = 0;
+    return Erosion{iters, iters > 0 && c->erode_k != 3};
+}
+
 // `left` erosion iterations on the packed label image cur ([F][H][W] elements LT), one launch each, on stream ms: the cross, or
 // (element) the context's k x k element.  Ping-pong with lb_, reserved here like every label image at 4 bytes per pixel; cur ends as
-// the buffer that holds the result.  Shared by pack_masks and lpf_set_masks_rle.
+// the buffer that holds the result.  Every erosion of a packed image goes through here: the narrow label images (pack_masks,
+// rle_label_image) and the wide passes' planes (wide_pack: F * LW images of uint32_t).
 template <typename LT> int erode_packed_iters(lpf_ctx *c, LT *&cur, DevBuf &lb_, const int W, const int H, const int F, hipStream_t ms, int left, bool element)
 {
     if (left <= 0) return LPF_OK;
@@ -1078,14 +1088,11 @@ int pack_masks(lpf_ctx *c, DevBuf &la, DevBuf &lb_, const int W, const int H, hi
         if (M == 0) {
             LPF_HIP(c, hipMemsetAsync(cur, 0, (size_t)F * hw * sizeof(LT), ms));
         } else {
-            if (c->erode_k == 1) erode_iters = 0;          // (the 1 x 1 element: any number of iterations is the identity)
             // the k x k element of lpf_set_erosion_element: its own pack (first erosion fused, whatever the shape) and erosion kernel
-            const bool element = erode_iters > 0 && c->erode_k != 3;
-            const int er = c->erode_r;
-            const uint32_t spans = c->erode_spans;
-            int left = erode_iters;
-            const bool stream16 = !element && hw % 16 == 0 && ((uintptr_t)masks & 15) == 0;
-            if (!stream16 && erode_iters > 0) --left;      // (the tiled pack does the first erosion itself)
+            const Erosion E = erosion(c, erode_iters);
+            int left = E.iters;
+            const bool stream16 = !E.element && hw % 16 == 0 && ((uintptr_t)masks & 15) == 0;
+            if (!stream16 && E.iters > 0) --left;          // (the tiled pack does the first erosion itself)
             with_rule(f32, rule, [&](auto kind) {
                 typedef typename decltype(kind)::elem T;
                 constexpr int RULE = decltype(kind)::rule;
@@ -1096,14 +1103,14 @@ int pack_masks(lpf_ctx *c, DevBuf &la, DevBuf &lb_, const int W, const int H, hi
                     const long long total16 = (long long)F * (long long)(hw / 16);
                     const unsigned nb = (unsigned)((total16 + LPF_BLOCK - 1) / LPF_BLOCK);
                     hipLaunchKernelGGL((lpf_pack16<T, RULE, LT>), dim3(nb), dim3(LPF_BLOCK), 0, ms, (const T *)masks, cur, M, (long long)hw, total16, r, W);
-                } else if (element) {
-                    hipLaunchKernelGGL((lpf_pack_erode_k<T, RULE, LT>), grid, dim3(LPF_BLOCK), 0, ms, (const T *)masks, cur, M, H, W, er, spans);
+                } else if (E.element) {
+                    hipLaunchKernelGGL((lpf_pack_erode_k<T, RULE, LT>), grid, dim3(LPF_BLOCK), 0, ms, (const T *)masks, cur, M, H, W, c->erode_r, c->erode_spans);
                 } else {
-                    hipLaunchKernelGGL((lpf_pack_erode<T, RULE, LT>), grid, dim3(LPF_BLOCK), 0, ms, (const T *)masks, cur, M, H, W, erode_iters > 0 ? 1 : 0, r);
+                    hipLaunchKernelGGL((lpf_pack_erode<T, RULE, LT>), grid, dim3(LPF_BLOCK), 0, ms, (const T *)masks, cur, M, H, W, E.iters > 0 ? 1 : 0, r);
                 }
             });
             LPF_HIP(c, hipGetLastError());
-            if ((rc = erode_packed_iters(c, cur, lb_, W, H, F, ms, left, element))) return rc;
+            if ((rc = erode_packed_iters(c, cur, lb_, W, H, F, ms, left, E.element))) return rc;
         }
         *result = cur;
         return LPF_OK;
@@ -1299,6 +1306,64 @@ int rle_stage_tables(lpf_ctx *c, DevBuf &stage, const lpf_rle_masks *in, const s
     return LPF_OK;
 }
 
+// The narrow label image [F][H][W] of `label_bytes` per pixel from walked run-length masks R (R.in not NULL): zero, decode
+// (lpf_rle_decode), then every erosion iteration on the packed image -- into la (lb_ = erosion ping-pong), the tables staged in `stage`.
+// *result: the buffer that holds the image.  *staged is set once copies from the caller's arrays and R.units are queued: the caller owes
+// the host wait.  For lpf_set_masks_rle (a scratch set's label image) and lpf_run_cams (a camera's)
+int rle_label_image(lpf_ctx *c, DevBuf &la, DevBuf &lb_, DevBuf &stage, const lpf_ctx::RleIn &R, const int W, const int H, int label_bytes,
+                    void **result, bool *staged)
+{
+    const int F = R.in->F;
+    const size_t hw = (size_t)W * H;
+    int rc;
+    // 4 bytes per pixel whatever the element: the decode's 32-bit atomics on the last, partial word of an image of 1- or 2-byte
+    // elements stay inside the allocation (lpf_rle.hip.h)
+    if ((rc = reserve(c, la, (size_t)F * hw * 4))) return rc;
+    LPF_HIP(c, hipMemsetAsync(la.p, 0, (size_t)F * hw * label_bytes, c->stream));
+    *result = la.p;
+    if (R.units.empty()) return LPF_OK;                    // (the image is zero, and erosion keeps it so)
+    LpfRleJob J;
+    unsigned nb = 0;
+    if ((rc = rle_stage_tables(c, stage, R.in, R.units, R.Rtot, (long long)hw, J, &nb))) return rc;
+    *staged = true;
+    const Erosion E = erosion(c, R.in->erode_iters);
+    return with_label(label_bytes, [&](auto lt) -> int {
+        typedef typename decltype(lt)::type LT;
+        hipLaunchKernelGGL((lpf_rle_decode<LT>), dim3(nb), dim3(LPF_RLE_BLOCK), 0, c->stream, J, (uint32_t *)la.p);
+        LPF_HIP(c, hipGetLastError());
+        LT *img = (LT *)la.p;
+        const int rc_ = erode_packed_iters(c, img, lb_, W, H, F, c->stream, E.iters, E.element);
+        *result = img;
+        return rc_;
+    });
+}
+
+// The wide passes' label planes [F][LW][Himg][Wimg] (wide_pack) from walked run-length masks R (R.in not NULL: its F frames, M masks,
+// erosion), in D's planes_a / planes_b, *planes = the buffer that holds the result: zero ALL the planes (the bits above M of a frame's
+// last word stay zero, as the dense pack leaves them), OR the runs in (lpf_rle_decode_wide), then every erosion iteration.  No dense
+// mask is staged.  *host_in is set once copies from the caller's arrays and R.units are queued
+int wide_pack_runs(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_ctx::RleIn &R, int Wimg, int Himg, const uint32_t **planes, bool *host_in)
+{
+    int rc;
+    const int F = R.in->F, LW = (R.in->M + 31) / 32;
+    const size_t hw = (size_t)Wimg * Himg;
+    if ((rc = reserve(c, D.planes_a, (size_t)F * LW * hw * 4))) return rc;
+    uint32_t *cur = (uint32_t *)D.planes_a.p;
+    LPF_HIP(c, hipMemsetAsync(cur, 0, (size_t)F * LW * hw * 4, c->stream));
+    if (!R.units.empty()) {                               // (no units: the planes are zero, and erosion keeps them so)
+        LpfRleJob J;
+        unsigned nb = 0;
+        if ((rc = rle_stage_tables(c, D.rle, R.in, R.units, R.Rtot, (long long)hw, J, &nb))) return rc;
+        *host_in = true;
+        hipLaunchKernelGGL(lpf_rle_decode_wide, dim3(nb), dim3(LPF_RLE_BLOCK), 0, c->stream, J, LW, cur);
+        LPF_HIP(c, hipGetLastError());
+        const Erosion E = erosion(c, R.in->erode_iters);
+        if ((rc = erode_packed_iters(c, cur, D.planes_b, Wimg, Himg, F * LW, c->stream, E.iters, E.element))) return rc;
+    }
+    *planes = cur;
+    return LPF_OK;
+}
+
 // The frames [f0, f0 + fc) of a walked batch A (A.in->M > 0): rle_walk emits the units in run order, so the range's runs and units are
 // contiguous pieces of A's.  rle_units_before: the units of the runs before run r, i.e. the first unit of r (or of the next run that has one)
 size_t rle_units_before(const lpf_ctx::RleIn &A, long long r)
@@ -1314,7 +1379,7 @@ size_t rle_slice_bytes(const lpf_ctx::RleIn &A, size_t f0, size_t fc)
     return align256((size_t)(r1 - r0) * sizeof(int2)) + align256((rle_units_before(A, r1) - rle_units_before(A, r0)) * sizeof(int2)) +
            (fc * M + 1) * 8;
 }
-// ... and the range as a batch of its own in S (lpf_ctx::RleSlice): what wide_pack's run-length branch takes as its checked input
+// ... and the range as a batch of its own in S (lpf_ctx::RleSlice): what wide_pack_runs takes as its checked input
 void rle_slice(const lpf_ctx::RleIn &A, size_t f0, size_t fc, lpf_ctx::RleSlice &S)
 {
     const size_t M = (size_t)A.in->M;
@@ -1332,6 +1397,44 @@ void rle_slice(const lpf_ctx::RleIn &A, size_t f0, size_t fc, lpf_ctx::RleSlice 
     S.R.in = &S.sub;
     S.R.Rtot = r1 - r0;
 }
+
+// The run-length masks of ONE call, walked into rle_in[0] before anything is enqueued (lpf_set_masks_rle; lpf_depth_maps_rle and
+// lpf_first_match_rle, whose batch goes through in ranges of frames: what a range's tables cost, for plan_ranges; the largest range's
+// buffers and every range's slice, lpf_ctx::RleSlice; the pack of range k).  By whatever way the call returns, errors included, nothing
+// of the context points into the caller's arrays afterwards -- on the success path after the call's host wait: the queued copies
+// read them.  Without a walk, or with M = 0, active() is false and bytes() is 0
+struct RleCall {
+    lpf_ctx *c;
+    lpf_ctx::RleIn &A;
+    int W = 0, H = 0;                                     // the masks' image
+    explicit RleCall(lpf_ctx *c_) : c(c_), A(c_->rle_in[0]) { A.in = nullptr; }     // (whatever an earlier pass left there)
+    RleCall(const RleCall &) = delete;
+    ~RleCall() { c->rle_slices.clear(); A.in = nullptr; }
+    bool active() const { return A.in && A.in->M > 0; }
+    int walk(const char *who, const lpf_rle_masks *rle, int W_, int H_)
+    {
+        W = W_; H = H_;
+        const int rc = rle_walk(c, who, rle, (long long)W * H, A.units, &A.Rtot);
+        if (!rc) A.in = rle;
+        return rc;
+    }
+    size_t bytes(size_t f0, size_t n) const { return active() ? rle_slice_bytes(A, f0, n) : 0; }
+    // D's planes for the range of most frames (both sets with erosion: decoded planes are eroded from the first iteration on) and its
+    // run tables for the range that stages most; every range's slice of the runs
+    int reserve_ranges(lpf_ctx::Wide &D, const std::vector<Span> &ranges)
+    {
+        int rc;
+        const size_t planes = largest(ranges, [](size_t, size_t n) { return n; }) * (size_t)((A.in->M + 31) / 32) * W * H * 4;
+        if ((rc = reserve(c, D.planes_a, planes))) return rc;
+        if (A.in->erode_iters > 0 && (rc = reserve(c, D.planes_b, planes))) return rc;
+        if ((rc = reserve(c, D.rle, largest(ranges, [&](size_t f0, size_t n) { return bytes(f0, n); })))) return rc;
+        c->rle_slices.resize(ranges.size());
+        for (size_t k = 0; k < ranges.size(); ++k) rle_slice(A, ranges[k].first, ranges[k].count, c->rle_slices[k]);
+        return LPF_OK;
+    }
+    // range k's planes: zeroed, its own runs decoded, every erosion iteration (wide_pack_runs on its slice)
+    int pack(lpf_ctx::Wide &D, size_t k, const uint32_t **planes, bool *host_in) { return wide_pack_runs(c, D, c->rle_slices[k].R, W, H, planes, host_in); }
+};
 
 // ---- setup the run paths share ---------------------------------------------------------------------------------------------------
 
@@ -2017,43 +2120,22 @@ int lpf_set_masks_rle(lpf_ctx *c, const lpf_rle_masks *in)
     if (!in) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: in=NULL");
     if (in->M > LPF_MAX_MASKS) return too_many_masks(c, in->M);
     const int F = in->F, M = in->M;
-    int erode_iters = in->erode_iters;
-    const long long hw = (long long)c->H * c->W;
-    long long Rtot = 0;
-    std::vector<int2> &units = c->rle_units;
+    RleCall R(c);
     int rc;
-    if ((rc = rle_walk(c, "lpf_set_masks_rle", in, hw, units, &Rtot))) return rc;
+    if ((rc = R.walk("lpf_set_masks_rle", in, c->W, c->H))) return rc;
     // from here on: set_masks_impl with host masks (not per scratch set: what a pipelined context owes is drained first)
     if (c->pipe.owes() && (rc = sync_all(c))) return rc;
     lpf_ctx::Masks &MK = c->masks;
     lpf_ctx::Scratch &S = c->sc[c->pipe.set_now()];
     MK.begin(c->pipe.set_now());
     if (F == 0) return LPF_OK;
-    // 4 bytes per pixel whatever the element: the decode's 32-bit atomics on the last, partial word of an image of 1- or 2-byte
-    // elements stay inside the allocation (lpf_rle.hip.h)
-    if ((rc = reserve(c, S.label_a, (size_t)F * hw * 4))) return rc;
     const int lb = (M <= 8) ? 1 : (M <= 16) ? 2 : 4;
     c->rects_pending = nullptr;                             // a pending lpf_set_mask_rects hint is consumed (runs need none)
     MK.forget_unpacked();
-    LPF_HIP(c, hipMemsetAsync(S.label_a.p, 0, (size_t)F * hw * lb, c->stream));
-    void *cur = S.label_a.p;
-    if (!units.empty()) {
-        LpfRleJob J;
-        unsigned nb = 0;
-        if ((rc = rle_stage_tables(c, c->rle_stage, in, units, Rtot, hw, J, &nb))) return rc;
-        if (c->erode_k == 1) erode_iters = 0;              // (the 1 x 1 element: any number of iterations is the identity)
-        rc = with_label(lb, [&](auto lt) -> int {
-            typedef typename decltype(lt)::type LT;
-            hipLaunchKernelGGL((lpf_rle_decode<LT>), dim3(nb), dim3(LPF_RLE_BLOCK), 0, c->stream, J, (uint32_t *)S.label_a.p);
-            LPF_HIP(c, hipGetLastError());
-            LT *img = (LT *)S.label_a.p;
-            int rc_ = erode_packed_iters(c, img, S.label_b, c->W, c->H, F, c->stream, erode_iters, c->erode_k != 3);
-            cur = img;
-            return rc_;
-        });
-        if (rc) return rc;
-        LPF_HIP(c, host_wait(c));                           // the caller's arrays (and the unit table) may be reused
-    }
+    void *cur = nullptr;
+    bool staged = false;
+    if ((rc = rle_label_image(c, S.label_a, S.label_b, c->rle_stage, R.A, c->W, c->H, lb, &cur, &staged))) return rc;
+    if (staged) LPF_HIP(c, host_wait(c));                   // the caller's arrays (and the unit table) may be reused
     MK.packed(F, M, cur, lb);
     return LPF_OK;
 }
@@ -2430,10 +2512,10 @@ int lpf_erode_masks_u8(lpf_ctx *c, const uint8_t *src, int n, int h, int w, int 
     const long long total = (long long)bytes;
     const dim3 g((unsigned)((total + LPF_BLOCK - 1) / LPF_BLOCK));
     // the last iteration must land in `a` (dst for device callers): with an even count the first one goes to b
-    if (c->erode_k == 1) iters = 0;                        // (the 1 x 1 element of lpf_set_erosion_element: the identity)
+    iters = erosion(c, iters).iters;                       // (the 1 x 1 element of lpf_set_erosion_element: the identity)
     uint8_t *out = (iters % 2 == 1) ? a : b;
     for (int it = 0; it < iters; ++it) {
-        if (c->erode_k != 3) hipLaunchKernelGGL(lpf_erode_u8_k_kernel, g, dim3(LPF_BLOCK), 0, c->stream, cur, out, w, h, total, c->erode_r, c->erode_spans);
+        if (erosion(c, iters).element) hipLaunchKernelGGL(lpf_erode_u8_k_kernel, g, dim3(LPF_BLOCK), 0, c->stream, cur, out, w, h, total, c->erode_r, c->erode_spans);
         else hipLaunchKernelGGL(lpf_erode_u8_kernel, g, dim3(LPF_BLOCK), 0, c->stream, cur, out, w, h, total);
         LPF_HIP(c, hipGetLastError());
         cur = out;
@@ -2689,78 +2771,45 @@ int lpf_profile_read(lpf_ctx *c, double *k1_ms_sum, int64_t *k1_launches, int re
 // ---- lpf_run_wide (include/lpf.h): frames of up to LPF_MAX_MASKS_WIDE masks, kernels in lpf_wide.hip.h ----------------------
 // The parts of a wide run that lpf_run_cams_wide repeats per camera, on that camera's buffers D:
 
-// masks (host masks are staged into D; device masks are lent) -> LW planes in D (+ erosion); W.planes = the result (NULL: no masks).
-// *host_in: the masks were read from host memory
-// R: the input's checked run-length masks (check_wide_rle; R->in NULL, or no R: dense masks)
-static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int F, int Wimg, int Himg, LpfWideParams &W, bool *host_in,
-                     const lpf_ctx::RleIn *R = nullptr)
+// The wide passes' label planes [F][LW][Himg][Wimg] (LW = ceil(M / 32) words per pixel, M > 0), in D's planes_a / planes_b; *planes =
+// the buffer that holds the result.  Erosion runs on the packed planes, as F * LW images of uint32_t (erode_packed_iters).  From
+// run-length masks: wide_pack_runs, above.  From dense masks in device memory [F][M][Himg][Wimg] (uint8, or float under `binarize`; rects: their rectangles where they hold,
+// or NULL): the pack does the first erosion iteration itself, the remaining ones run on the planes
+static int wide_pack_dense(lpf_ctx *c, lpf_ctx::Wide &D, const void *d_masks, const int4 *rects, bool f32, int binarize, int M, int erode_iters,
+                           int F, int Wimg, int Himg, const uint32_t **planes)
 {
     int rc;
-    const int M = in->M, LW = (M + 31) / 32;
-    const size_t hw = (size_t)Wimg * Himg;
-    W.planes = nullptr;
-    if (M > 0 && R && R->in) {
-        // ---- run-length masks: zero ALL the planes (the bits above M of a frame's last word stay zero, as the dense pack leaves them),
-        //      OR the runs in (lpf_rle_decode_wide), then every erosion iteration on the packed planes.  No dense mask is staged
-        if ((rc = reserve(c, D.planes_a, (size_t)F * LW * hw * 4))) return rc;
-        uint32_t *cur = (uint32_t *)D.planes_a.p;
-        LPF_HIP(c, hipMemsetAsync(cur, 0, (size_t)F * LW * hw * 4, c->stream));
-        if (!R->units.empty()) {                          // (no units: the planes are zero, and erosion keeps them so)
-            LpfRleJob J;
-            unsigned nb = 0;
-            if ((rc = rle_stage_tables(c, D.rle, R->in, R->units, R->Rtot, (long long)hw, J, &nb))) return rc;
-            *host_in = true;
-            hipLaunchKernelGGL(lpf_rle_decode_wide, dim3(nb), dim3(LPF_RLE_BLOCK), 0, c->stream, J, LW, cur);
-            LPF_HIP(c, hipGetLastError());
-            const int iters = c->erode_k == 1 ? 0 : in->erode_iters;      // (the 1 x 1 element: the identity)
-            if (iters > 0) {
-                const bool element = c->erode_k != 3;
-                const dim3 grid((Wimg + LPF_TW - 1) / LPF_TW, (Himg + LPF_TH - 1) / LPF_TH, (unsigned)(F * LW));
-                if ((rc = reserve(c, D.planes_b, (size_t)F * LW * hw * 4))) return rc;
-                uint32_t *other = (uint32_t *)D.planes_b.p;
-                for (int it = 0; it < iters; ++it) {
-                    if (element) hipLaunchKernelGGL((lpf_erode_packed_k<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, Himg, Wimg, c->erode_r, c->erode_spans);
-                    else hipLaunchKernelGGL((lpf_erode_packed<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, Himg, Wimg);
-                    LPF_HIP(c, hipGetLastError());
-                    std::swap(cur, other);
-                }
-            }
-        }
-        W.planes = cur;
-    } else if (M > 0) {
-        const void *d_masks = nullptr;
-        const int4 *rects = nullptr;
-        if ((rc = stage_masks(c, *in, F, hw, D.masks, D.rects, &d_masks, &rects, host_in))) return rc;
-        // ---- pack (+ erosion) into LW planes ----------------------------------------------------------------------------------
-        if ((rc = reserve(c, D.planes_a, (size_t)F * LW * hw * 4))) return rc;
-        uint32_t *cur = (uint32_t *)D.planes_a.p;
-        const dim3 grid((Wimg + LPF_TW - 1) / LPF_TW, (Himg + LPF_TH - 1) / LPF_TH, (unsigned)(F * LW));
-        const int iters = c->erode_k == 1 ? 0 : in->erode_iters;      // (the 1 x 1 element: the identity)
-        const int fuse = iters > 0 ? 1 : 0;
-        const bool element = fuse && c->erode_k != 3;     // the k x k element of lpf_set_erosion_element: its own kernels
-        const int er = c->erode_r;
-        const uint32_t spans = c->erode_spans;
-        with_rule(in->f32 != 0, in->binarize + 1, [&](auto kind) {
-            typedef typename decltype(kind)::elem T;
-            if (element)
-                hipLaunchKernelGGL((lpf_wide_pack_k<T, decltype(kind)::rule>), grid, dim3(LPF_BLOCK), 0, c->stream, (const T *)d_masks, cur, M, LW, Himg, Wimg, er, spans);
-            else
-                hipLaunchKernelGGL((lpf_wide_pack<T, decltype(kind)::rule>), grid, dim3(LPF_BLOCK), 0, c->stream, (const T *)d_masks, cur, M, LW, Himg, Wimg, fuse, rects);
-        });
-        LPF_HIP(c, hipGetLastError());
-        if (iters > 1) {                                  // further iterations: the narrow path's own kernel, a plane per (frame, word)
-            if ((rc = reserve(c, D.planes_b, (size_t)F * LW * hw * 4))) return rc;
-            uint32_t *other = (uint32_t *)D.planes_b.p;
-            for (int it = 1; it < iters; ++it) {
-                if (element) hipLaunchKernelGGL((lpf_erode_packed_k<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, Himg, Wimg, er, spans);
-                else hipLaunchKernelGGL((lpf_erode_packed<uint32_t>), grid, dim3(LPF_BLOCK), 0, c->stream, cur, other, Himg, Wimg);
-                LPF_HIP(c, hipGetLastError());
-                std::swap(cur, other);
-            }
-        }
-        W.planes = cur;
-    }
+    const int LW = (M + 31) / 32;
+    if ((rc = reserve(c, D.planes_a, (size_t)F * LW * Wimg * Himg * 4))) return rc;
+    uint32_t *cur = (uint32_t *)D.planes_a.p;
+    const dim3 grid((Wimg + LPF_TW - 1) / LPF_TW, (Himg + LPF_TH - 1) / LPF_TH, (unsigned)(F * LW));
+    const Erosion E = erosion(c, erode_iters);
+    with_rule(f32, binarize + 1, [&](auto kind) {
+        typedef typename decltype(kind)::elem T;
+        if (E.element)                                    // the k x k element of lpf_set_erosion_element: its own kernels
+            hipLaunchKernelGGL((lpf_wide_pack_k<T, decltype(kind)::rule>), grid, dim3(LPF_BLOCK), 0, c->stream, (const T *)d_masks, cur, M, LW, Himg, Wimg, c->erode_r, c->erode_spans);
+        else
+            hipLaunchKernelGGL((lpf_wide_pack<T, decltype(kind)::rule>), grid, dim3(LPF_BLOCK), 0, c->stream, (const T *)d_masks, cur, M, LW, Himg, Wimg, E.iters > 0 ? 1 : 0, rects);
+    });
+    LPF_HIP(c, hipGetLastError());
+    if ((rc = erode_packed_iters(c, cur, D.planes_b, Wimg, Himg, F * LW, c->stream, E.iters - 1, E.element))) return rc;
+    *planes = cur;
     return LPF_OK;
+}
+
+// ... from a pass's lpf_wide_input (host masks are staged into D and *host_in is set; device masks are lent), or, where it is in the
+// run-length form, from R, its walked masks (check_wide_rle).  *planes = NULL without masks
+static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int F, int Wimg, int Himg, const lpf_ctx::RleIn &R,
+                     const uint32_t **planes, bool *host_in)
+{
+    *planes = nullptr;
+    if (in->M == 0) return LPF_OK;
+    if (R.in) return wide_pack_runs(c, D, R, Wimg, Himg, planes, host_in);
+    int rc;
+    const void *d_masks = nullptr;
+    const int4 *rects = nullptr;
+    if ((rc = stage_masks(c, *in, F, (size_t)Wimg * Himg, D.masks, D.rects, &d_masks, &rects, host_in))) return rc;
+    return wide_pack_dense(c, D, d_masks, rects, in->f32 != 0, in->binarize, in->M, in->erode_iters, F, Wimg, Himg, planes);
 }
 
 // outputs and scratch of a wide run of n points, F frames, W.M masks, Btot boxes, W.nchunk chunks, on buffers D -> W's pointers: the
@@ -2847,7 +2896,7 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     bool pts_in = false, masks_in = false;
     if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, 0, n, n, &W.pts, &pts_in))) return rc;
     if (direct) W.planes = nullptr;
-    else if ((rc = wide_pack(c, D, in, F, c->W, c->H, W, &masks_in, &R))) return rc;
+    else if ((rc = wide_pack(c, D, in, F, c->W, c->H, R, &W.planes, &masks_in))) return rc;
 
     // ---- buffers: the caller's device pointers, or staging for host callers ---------------------------------------------------
     const size_t nMB = (size_t)M * Btot;
@@ -2912,7 +2961,7 @@ static void dm_raster(lpf_ctx *c, const LpfDmParams &P, dim3 g, bool planes, con
 
 // What lpf_depth_maps and lpf_depth_maps_rle share, after the checks of their own mask input (who: the messages' prefix).  rle: the
 // run-length masks of lpf_depth_maps_rle, not walked yet -- `in` then carries M and erode_iters only, and the label planes of a chunk are
-// decoded from the chunk's own runs (wide_pack's run-length branch on a lpf_ctx::RleSlice); NULL: the dense masks of `in`
+// decoded from the chunk's own runs (RleCall::pack: wide_pack_runs on a lpf_ctx::RleSlice); NULL: the dense masks of `in`
 static int depth_maps_impl(lpf_ctx *c, const char *who, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
                            const lpf_wide_input *in, const lpf_rle_masks *rle, const lpf_depth_maps_outputs *out)
 {
@@ -2923,12 +2972,9 @@ static int depth_maps_impl(lpf_ctx *c, const char *who, const float *pts, const 
                     (long long)out->cap, (void *)out->pix, (void *)out->car_off, (void *)out->need);
     if (F == 0) return LPF_OK;
     if ((rc = check_frames(c, who, pts, frame_off, F, LPF_BLOCK))) return rc;
-    lpf_ctx::RleIn &A = c->rle_in[0];                       // run-length masks: the whole batch checked here, before anything is enqueued
-    if (rle) {
-        if ((rc = rle_walk(c, who, rle, (long long)c->W * c->H, A.units, &A.Rtot))) return rc;
-        A.in = rle;
-    }
-    const bool runs = rle && M > 0;
+    RleCall R(c);                                           // run-length masks: the whole batch checked here, before anything is enqueued
+    if (rle && (rc = R.walk(who, rle, c->W, c->H))) return rc;
+    const bool runs = R.active();
     long long maxN = 0;
     for (int f = 0; f < F; ++f) maxN = std::max(maxN, (long long)(frame_off[f + 1] - frame_off[f]));
     const int64_t Ntot = frame_off[F];
@@ -2947,7 +2993,7 @@ static int depth_maps_impl(lpf_ctx *c, const char *who, const float *pts, const 
     const size_t per_frame = hwp * 4 + (size_t)M * ntile * 12 + (planes ? (size_t)LW * hw * 4 * plane_sets : 0) +
                              (host_masks ? (size_t)M * (hw * esz + 16) : 0) + (host_pts ? (size_t)maxN * 16 : 0);
     const std::vector<Span> chunks = plan_ranges(c, (size_t)F, (size_t)F, [&](size_t f0, size_t n) {
-        return n * per_frame + (runs ? rle_slice_bytes(A, f0, n) : 0);          // (a chunk's run tables in place of its dense masks)
+        return n * per_frame + R.bytes(f0, n);                // (a chunk's run tables in place of its dense masks)
     });
     const size_t Fc = largest(chunks, [](size_t, size_t n) { return n; });      // (the first chunk's, where every frame costs the same)
     const size_t most_pts = largest(chunks, [&](size_t f0, size_t n) { return frame_off[f0 + n] - frame_off[f0]; });
@@ -2957,13 +3003,7 @@ static int depth_maps_impl(lpf_ctx *c, const char *who, const float *pts, const 
     if ((rc = reserve(c, D.win, Fc * hwp * 4))) return rc;
     if (M > 0 && (rc = reserve(c, D.cnt, Fc * M * (2 * ntile + 1) * 4))) return rc;
     if (host_pts && (rc = reserve(c, D.pts, most_pts * 16))) return rc;      // (here, not by the first chunk with points: no chunk waits)
-    if (runs) {                                               // the largest chunk's planes and run tables; every chunk's slice of the runs
-        if ((rc = reserve(c, D.pack.planes_a, Fc * LW * hw * 4))) return rc;
-        if (plane_sets > 1 && (rc = reserve(c, D.pack.planes_b, Fc * LW * hw * 4))) return rc;
-        if ((rc = reserve(c, D.pack.rle, largest(chunks, [&](size_t f0, size_t n) { return rle_slice_bytes(A, f0, n); })))) return rc;
-        c->rle_slices.resize(chunks.size());
-        for (size_t k = 0; k < chunks.size(); ++k) rle_slice(A, chunks[k].first, chunks[k].count, c->rle_slices[k]);
-    }
+    if (runs && (rc = R.reserve_ranges(D.pack, chunks))) return rc;
     const void *masks_k = nullptr;                            // a chunk's staged masks and rectangles, or the caller's
     const int32_t *rects_k = nullptr;
     Stage I(host_masks);
@@ -3010,22 +3050,13 @@ static int depth_maps_impl(lpf_ctx *c, const char *who, const float *pts, const 
             const int32_t *dr = host_masks || !rects_k ? rects_k : rects_k + ch.first * M * 4;
             P.masks = dm;
             P.rects = use_rects ? (const int4 *)dr : nullptr;
-            if (runs) {                                     // the chunk's own runs: zeroed planes, decode, every erosion iteration
-                LpfWideParams Wp;
-                memset(&Wp, 0, sizeof Wp);
-                if ((rc = wide_pack(c, D.pack, in, fc, c->W, c->H, Wp, &runs_in, &c->rle_slices[k].R))) return rc;
-                P.masks = Wp.planes;
-                P.rects = nullptr;
-            } else if (planes) {                            // erosion: lpf_run_wide's pack + erode into LW planes per frame
-                lpf_wide_input sub = *in;
-                sub.masks = dm; sub.rects = dr; sub.on_device = 1;
-                LpfWideParams Wp;
-                memset(&Wp, 0, sizeof Wp);
-                bool staged = false;
-                if ((rc = wide_pack(c, D.pack, &sub, fc, c->W, c->H, Wp, &staged))) return rc;
-                P.masks = Wp.planes;
-                P.rects = nullptr;
-            }
+            const uint32_t *packed = nullptr;
+            // the chunk's own runs: zeroed planes, decode, every erosion iteration; or, with erosion, lpf_run_wide's pack + erode into
+            // LW planes per frame (no rectangles: they do not hold with erosion, rects_hold)
+            if (runs) rc = R.pack(D.pack, k, &packed, &runs_in);
+            else if (planes) rc = wide_pack_dense(c, D.pack, dm, nullptr, in->f32 != 0, in->binarize, M, in->erode_iters, fc, c->W, c->H, &packed);
+            if (rc) return rc;
+            if (planes) { P.masks = packed; P.rects = nullptr; }
             LPF_HIP(c, hipMemsetAsync(D.win.p, 0, (size_t)fc * hwp * 4, c->stream));
             LPF_HIP(c, hipMemsetAsync(D.cnt.p, 0, (size_t)fc * M * ntile * 4, c->stream));
             if (mc > 0) {
@@ -3047,8 +3078,7 @@ static int depth_maps_impl(lpf_ctx *c, const char *who, const float *pts, const 
 
     if (host_io && (rc = S.back(c))) return rc;
     if (host_io || host_masks || pts_in || runs_in) LPF_HIP(c, host_wait(c));   // host buffers may be reused
-    if (rle) { c->rle_slices.clear(); A.in = nullptr; }       // (the copies have run: nothing points into the caller's arrays any more)
-    return LPF_OK;
+    return LPF_OK;                                            // (R lets go of the caller's arrays here: the copies have run)
 }
 
 int lpf_depth_maps(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
@@ -3682,7 +3712,7 @@ int lpf_box_views(lpf_ctx *c, int F, const lpf_box_views_input *in, const lpf_bo
 
 // What lpf_first_match and lpf_first_match_rle share, after the checks of their own mask input (who: the messages' prefix).  rle: the
 // run-length masks of lpf_first_match_rle, not walked yet -- `in` then carries M, mh, mw, the colours and where those are (on_device),
-// a range's label planes [fc][LW][mh][mw] are decoded from the range's own runs (wide_pack's run-length branch on a
+// a range's label planes [fc][LW][mh][mw] are decoded from the range's own runs (RleCall::pack: wide_pack_runs on a
 // lpf_ctx::RleSlice) and lpf_fm_count_planes reads them; NULL: the dense masks of `in`
 static int first_match_impl(lpf_ctx *c, const char *who, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
                             const lpf_first_match_input *in, const lpf_rle_masks *rle, const lpf_first_match_outputs *out)
@@ -3694,12 +3724,9 @@ static int first_match_impl(lpf_ctx *c, const char *who, const float *pts, const
         return fail(c, LPF_ERR_ARG, "%s: n_car=%p n_bg=%p (both are required)", who, (void *)out->n_car, (void *)out->n_bg);
     if (F == 0) return LPF_OK;
     if ((rc = check_frames(c, who, pts, frame_off, F, LPF_FM_TILE))) return rc;
-    lpf_ctx::RleIn &A = c->rle_in[0];                       // run-length masks: the whole batch checked here, before anything is enqueued
-    if (rle) {
-        if ((rc = rle_walk(c, who, rle, M > 0 ? (long long)in->mh * in->mw : 0, A.units, &A.Rtot))) return rc;
-        A.in = rle;
-    }
-    const bool runs = rle && M > 0;
+    RleCall R(c);                                           // run-length masks: the whole batch checked here, before anything is enqueued
+    if (rle && (rc = R.walk(who, rle, M > 0 ? in->mw : 0, M > 0 ? in->mh : 0))) return rc;
+    const bool runs = R.active();
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
 
@@ -3719,7 +3746,7 @@ static int first_match_impl(lpf_ctx *c, const char *who, const float *pts, const
                           (runs ? LW * plane * 4 : 0) + (host_io ? 24 + nM * 8 : 0);
     auto pts_of = [&](size_t f0, size_t n) { return (size_t)(frame_off[f0 + n] - frame_off[f0]); };
     const std::vector<Span> ranges = plan_ranges(c, (size_t)F, LPF_FM_MAX_FRAMES, [&](size_t f0, size_t n) {
-        return pts_of(f0, n) * per_pt + pts_of(f0, n) / LPF_FM_TILE * 16 + n * per_fr + (runs ? rle_slice_bytes(A, f0, n) : 0);
+        return pts_of(f0, n) * per_pt + pts_of(f0, n) / LPF_FM_TILE * 16 + n * per_fr + R.bytes(f0, n);
     });
     const size_t most_pts = largest(ranges, pts_of), most_f = largest(ranges, [](size_t, size_t n) { return n; });
 
@@ -3729,15 +3756,7 @@ static int first_match_impl(lpf_ctx *c, const char *who, const float *pts, const
     if (!dense && (rc = reserve(c, D.code, most_pts * 4))) return rc;
     if ((rc = reserve(c, D.tiles, most_tiles * 16))) return rc;
     if (host_pts && (rc = reserve(c, D.pts, most_pts * 16))) return rc;       // (here, not by the first range with points: no range waits)
-    lpf_wide_input wi;                                        // run-length masks: what wide_pack reads of its input (M; no erosion)
-    memset(&wi, 0, sizeof wi);
-    wi.M = M;
-    if (runs) {                                               // the largest range's planes and run tables; every range's slice of the runs
-        if ((rc = reserve(c, D.pack.planes_a, most_f * LW * plane * 4))) return rc;
-        if ((rc = reserve(c, D.pack.rle, largest(ranges, [&](size_t f0, size_t n) { return rle_slice_bytes(A, f0, n); })))) return rc;
-        c->rle_slices.resize(ranges.size());
-        for (size_t k = 0; k < ranges.size(); ++k) rle_slice(A, ranges[k].first, ranges[k].count, c->rle_slices[k]);
-    }
+    if (runs && (rc = R.reserve_ranges(D.pack, ranges))) return rc;
     if ((rc = upload(c, D.tab.p, frame_off, (size_t)(F + 1) * 8))) return rc;
 
     LpfFmParams P;
@@ -3788,12 +3807,9 @@ static int first_match_impl(lpf_ctx *c, const char *who, const float *pts, const
             if ((rc = I.in(c, {{r.first, r.count}, {r.first, r.count}}))) return rc;                 // masks | colors
             P.masks = host_masks || runs ? masks_k : masks_k + r.first * nM * plane * esz;
             P.colors = host_in || !colors_k ? colors_k : colors_k + r.first * nM * 3;
-            if (runs) {                                       // the range's own runs: zeroed planes, then the decode
-                LpfWideParams Wp;
-                memset(&Wp, 0, sizeof Wp);
-                if ((rc = wide_pack(c, D.pack, &wi, fc, in->mw, in->mh, Wp, &runs_in, &c->rle_slices[k].R))) return rc;
-                P.masks = Wp.planes;
-            }
+            const uint32_t *decoded = nullptr;                // the range's own runs: zeroed planes, then the decode
+            if (runs && (rc = R.pack(D.pack, k, &decoded, &runs_in))) return rc;
+            if (runs) P.masks = decoded;
         }
         const Span sp = {(size_t)a, (size_t)nc}, sf = {r.first, r.count}, none = {0, 0};
         // first_mask | car_idx | car_mask | car_xyz | car_rgb | bg_idx | bg_xyz | n_valid | n_car | n_bg | mask_count: the lists as the
@@ -3819,8 +3835,7 @@ static int first_match_impl(lpf_ctx *c, const char *who, const float *pts, const
         if (host_io && (rc = S.back(c, {sp, sp, sp, sp, sp, sp, sp, sf, sf, sf, {r.first * nM, r.count * nM}}))) return rc;
     }
     if (host_io || host_in || pts_in || runs_in) LPF_HIP(c, host_wait(c));   // host outputs filled, host inputs free to be reused
-    if (rle) { c->rle_slices.clear(); A.in = nullptr; }       // (the copies have run: nothing points into the caller's arrays any more)
-    return LPF_OK;
+    return LPF_OK;                                            // (R lets go of the caller's arrays here: the copies have run)
 }
 
 int lpf_first_match(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_first_match_input *in,
@@ -3951,27 +3966,10 @@ int lpf_run_cams(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
         const lpf_ctx::RleIn &R = c->rle_in[k];
         if (R.in) {
             // run-length masks: lpf_set_masks_rle's zero + decode (+ erosion on the packed image) at the pass's element width, into
-            // this camera's label image -- reserved, like every label image, at 4 bytes per pixel: the decode's 32-bit atomics on the
-            // last, partial word of an image of 1- or 2-byte elements stay inside it (lpf_rle.hip.h)
-            DevBuf &la = c->cams.label_a[k];
-            if ((rc = reserve(c, la, (size_t)F * hw * 4))) return rc;
-            LPF_HIP(c, hipMemsetAsync(la.p, 0, (size_t)F * hw * lb_all, c->stream));
-            label_img[k] = la.p;
-            if (R.units.empty()) continue;                 // (the image is zero, and erosion keeps it so)
-            LpfRleJob J;
-            unsigned nb = 0;
-            if ((rc = rle_stage_tables(c, c->cams.rle[k], R.in, R.units, R.Rtot, (long long)hw, J, &nb))) return rc;
-            host_in = true;
-            rc = with_label(lb_all, [&](auto lt) -> int {
-                typedef typename decltype(lt)::type LT;
-                hipLaunchKernelGGL((lpf_rle_decode<LT>), dim3(nb), dim3(LPF_RLE_BLOCK), 0, c->stream, J, (uint32_t *)la.p);
-                LPF_HIP(c, hipGetLastError());
-                LT *img = (LT *)la.p;
-                int rc_ = erode_packed_iters(c, img, c->cams.label_b[k], I.W, I.H, F, c->stream, c->erode_k == 1 ? 0 : m.erode_iters, c->erode_k != 3);
-                label_img[k] = img;
-                return rc_;
-            });
-            if (rc) return rc;
+            // this camera's label image
+            void *cur = nullptr;
+            if ((rc = rle_label_image(c, c->cams.label_a[k], c->cams.label_b[k], c->cams.rle[k], R, I.W, I.H, lb_all, &cur, &host_in))) return rc;
+            label_img[k] = cur;
             continue;
         }
         const void *d_masks = nullptr;
@@ -4118,7 +4116,7 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
         const int M = I.masks.M, LW = (M + 31) / 32;
         wide_params(W, input_cam(I), F, M, nchunk, nbw[k], BX, out[k].inst_cap, (const LpfWideFrame *)c->camsw.tab.p + (size_t)k * F);
         W.pts = d_pts;
-        if ((rc = wide_pack(c, D, &I.masks, F, I.W, I.H, W, &host_in, &c->rle_in[k]))) return rc;
+        if ((rc = wide_pack(c, D, &I.masks, F, I.W, I.H, c->rle_in[k], &W.planes, &host_in))) return rc;
         if ((rc = wide_bind(c, D, &out[k], n, F, Btot[k], W, S[k]))) return rc;
         max_lists = std::max(max_lists, F * std::max(LW, 1));
         if (M > 0 && Btot[k] > 0) {

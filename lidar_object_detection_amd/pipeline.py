@@ -1191,25 +1191,42 @@ def _first_match_masks(frames, camera):
     if len(sizes) > 1:                                      # ragged: the canvas at the camera's size
         per = [(_same_color_canvas(f.masks, camera), flt) if len(planes) else (planes, flt) for f, (planes, flt) in zip(frames, per)]
         sizes = {(int(camera.height), int(camera.width))}
-    mh, mw = sizes.pop() if sizes else (1, 1)
-    Ms = [len(planes) for planes, _ in per]
+    return _padded_mask_batch([planes for planes, _ in per], [flt for _, flt in per], sizes.pop() if sizes else (1, 1), lambda a: a > 0)[:2]
+
+
+def _padded_mask_batch(stacks, floats, size, member):
+    """The frames' masks as ONE [F,M,h,w] batch -- M = the most masks of a frame, the others pad with empty planes -- behind
+    _first_match_masks and _depth_map_masks: (batch, each frame's own count, is the batch float32).  stacks: per frame an [M_f,h,w]
+    NumPy array or GPU tensor of ``size`` = (h, w), a list of [h,w] host planes (never stacked on the host: 135 MB per frame at 256
+    masks), or anything empty; floats: is that frame's stack read as float (``> 0.5`` on the GPU).  A batch that mixes float and other masks goes as float32, one without float masks as uint8 under ``member``, the caller's
+    rule for them (``> 0`` or ``!= 0``: they differ for negative integers).  GPU tensors stay on the GPU: the batch is made there."""
+    Ms = [len(m) for m in stacks]
     M = max(Ms) if Ms else 0
-    flt = any(f for (planes, f) in per if len(planes))
-    on_gpu = [planes for planes, _ in per if _is_device_tensor(planes) and len(planes)]
+    flt = any(f for m, f in zip(stacks, floats) if len(m))
+    on_gpu = [m for m in stacks if _is_device_tensor(m) and len(m)]
     if on_gpu:
         import torch
         dev = on_gpu[0].device
-        batch = torch.zeros((len(per), M, mh, mw), dtype=torch.float32 if flt else torch.uint8, device=dev)
-        for i, (planes, _) in enumerate(per):
-            if len(planes):
-                t = planes if _is_device_tensor(planes) else torch.from_numpy(np.stack(planes)).to(dev)
-                batch[i, :len(planes)].copy_(t if flt else (t > 0))
-        return batch, Ms
-    batch = np.zeros((len(per), M, mh, mw), np.float32 if flt else np.uint8)
-    for i, (planes, _) in enumerate(per):
-        for j, pl in enumerate(planes):
-            batch[i, j] = pl if flt else (pl > 0)
-    return batch, Ms
+        batch = torch.zeros((len(stacks), M) + tuple(size), dtype=torch.float32 if flt else torch.uint8, device=dev)
+        for i, m in enumerate(stacks):
+            if len(m):
+                t = (m if _is_device_tensor(m) else torch.from_numpy(np.ascontiguousarray(m))).to(dev)
+                batch[i, :len(m)].copy_(t if flt else member(t))
+        return batch, Ms, flt
+    batch = np.zeros((len(stacks), M) + tuple(size), np.float32 if flt else np.uint8)
+    for i, m in enumerate(stacks):
+        for j, pl in enumerate(m):                            # plane by plane: the temporaries stay small
+            batch[i, j] = pl if flt else member(pl)
+    return batch, Ms, flt
+
+
+def _mask_group(batch, rles, g):
+    """Masks g .. g + 255 of every frame, as first_match and depth_maps take them: the frames' RleMasks sliced, or (rles None) those
+    planes of the dense batch, contiguous."""
+    if rles is not None:
+        return [r[g:g + LPF_MAX_MASKS_WIDE] for r in rles]
+    part = batch[:, g:g + LPF_MAX_MASKS_WIDE]
+    return part.contiguous() if _is_device_tensor(part) else np.ascontiguousarray(part)
 
 
 def _first_match_rle_masks(frames):
@@ -1258,12 +1275,6 @@ def first_match_frames(frames, TrVeloToRect, camera, depth_max=30.0, mask_colors
     ctx.set_camera(TrVeloToRect, camera.K, camera.width, camera.height, 0.0, float(depth_max))
     gpu = _is_device_tensor(batch)
 
-    def group(g):                                           # masks g .. g + 255 of every frame, as first_match takes them
-        if rles is not None:
-            return [r[g:g + LPF_MAX_MASKS_WIDE] for r in rles]
-        part = batch[:, g:g + LPF_MAX_MASKS_WIDE]
-        return part.contiguous() if gpu else np.ascontiguousarray(part)
-
     def host(a):
         return a.cpu().numpy() if _is_device_tensor(a) else a
 
@@ -1289,7 +1300,7 @@ def first_match_frames(frames, TrVeloToRect, camera, depth_max=30.0, mask_colors
         return out
     code = None
     for g in range(0, M, LPF_MAX_MASKS_WIDE):               # groups of 256 masks, merged on the dense codes
-        cur = host(ctx.first_match(None, group(g), want=("first_mask",), staged=staged)["first_mask"])
+        cur = host(ctx.first_match(None, _mask_group(batch, rles, g), want=("first_mask",), staged=staged)["first_mask"])
         code = cur if code is None else np.where((code == -1) & (cur >= 0), cur + np.int32(g), code)
     for f, fr in enumerate(frames):
         cf = code[int(off[f]):int(off[f + 1])]
@@ -2270,26 +2281,10 @@ def _depth_map_masks(frames, H, W):
         if m.shape[0] and tuple(m.shape[1:]) != (H, W):
             raise ValueError("frame %s: masks must be at the camera's size [M,%d,%d], got %s" % (f.frame, H, W, tuple(m.shape)))
         stacks.append(m)
-    Ms = [int(m.shape[0]) for m in stacks]
-    M = max(Ms) if Ms else 0
 
     def is_float(m):
         return (str(m.dtype) in ("torch.float16", "torch.float32", "torch.float64")) if _is_device_tensor(m) else m.dtype.kind == "f"
-    flt = any(is_float(m) for m in stacks if m.shape[0])
-    if any(_is_device_tensor(m) for m in stacks if m.shape[0]):
-        import torch
-        dev = next(m.device for m in stacks if _is_device_tensor(m) and m.shape[0])
-        batch = torch.zeros((len(stacks), M, H, W), dtype=torch.float32 if flt else torch.uint8, device=dev)
-        for i, m in enumerate(stacks):
-            if m.shape[0]:
-                t = m if _is_device_tensor(m) else torch.from_numpy(np.ascontiguousarray(m))
-                batch[i, :m.shape[0]].copy_(t.to(dev) if flt else (t.to(dev) != 0))
-        return batch, Ms, flt
-    batch = np.zeros((len(stacks), M, H, W), np.float32 if flt else np.uint8)
-    for i, m in enumerate(stacks):
-        if m.shape[0]:
-            batch[i, :m.shape[0]] = m if flt else (m != 0)
-    return batch, Ms, flt
+    return _padded_mask_batch(stacks, [is_float(m) for m in stacks], (H, W), lambda a: a != 0)
 
 
 def depth_maps_frames(frames, TrVeloToRect, camera, depth_max=30.0, device=0, ctx=None):
@@ -2306,23 +2301,17 @@ def depth_maps_frames(frames, TrVeloToRect, camera, depth_max=30.0, device=0, ct
     ctx.set_camera(TrVeloToRect, camera.K, camera.width, camera.height, 0.0, float(depth_max))
     H, W = int(camera.height), int(camera.width)
     rles = _rle_frame_masks(frames, camera)
-    if rles is not None:                                    # run-length masks: the runs go down as they are (lpf_depth_maps_rle)
-        Ms = [len(r) for r in rles]
-        M = max(Ms)
+    if rles is not None:                                    # run-length masks: the runs go down as they are (lpf_depth_maps_rle),
+        batch, Ms, flt = None, [len(r) for r in rles], True       # under depth_maps' default rule
     else:
         batch, Ms, flt = _depth_map_masks(frames, H, W)
-        M = batch.shape[1]
+    M = max(Ms)
     out = [[] for _ in frames]
     if M == 0:
         return out
     pts = [f.points for f in frames]
     for g in range(0, M, LPF_MAX_MASKS_WIDE):                   # groups of 256 masks, concatenated
-        if rles is not None:
-            res = ctx.depth_maps(pts, [r[g:g + LPF_MAX_MASKS_WIDE] for r in rles])
-        else:
-            part = batch[:, g:g + LPF_MAX_MASKS_WIDE]
-            part = part.contiguous() if _is_device_tensor(part) else np.ascontiguousarray(part)
-            res = ctx.depth_maps(pts, part, binarize="gt0.5" if flt else "astype")
+        res = ctx.depth_maps(pts, _mask_group(batch, rles, g), binarize="gt0.5" if flt else "astype")
         for f, cars in enumerate(res):
             for j, (pix, dep, pid) in enumerate(cars):
                 i = g + j

@@ -20,6 +20,7 @@ extern "C" long long fake_hip_launches(void);
 extern "C" long long fake_hip_copies(void);
 extern "C" unsigned long long fake_hip_trace_hash(void);
 extern "C" void fake_hip_trace_flush(void);
+extern "C" void fake_hip_fail_malloc_after(long long n);     // n more hipMalloc calls succeed, the next one fails; n < 0: off
 extern "C" int hipMemsetAsync(void *, int, size_t, void *);      // the fake runtime's: a marker line "memset <bytes>" in the trace
 
 static int g_fail = 0;
@@ -386,6 +387,65 @@ static void pipelined(lpf_ctx *c)
     CHECK(in_force(c, 1));
 }
 
+// the dense twins, on two frames WITHOUT points: no dense count or raster is launched, so this driver's trace stays run-length only
+// (tests/test_host_sanitized_rle_analysis.py reads it so) while the host side stages the dense masks and walks every range
+static int dense_call(lpf_ctx *c, bool fm)
+{
+    Dev D;
+    const int F = 2, M = 3;
+    static const int64_t empty[F + 1] = {0, 0, 0};
+    uint8_t *masks = D.get<uint8_t>((size_t)F * M * HW);
+    if (fm) {
+        lpf_first_match_input in;
+        lpf_first_match_outputs o;
+        memset(&in, 0, sizeof in); memset(&o, 0, sizeof o);
+        in.masks = masks; in.M = M; in.mh = H; in.mw = W;
+        o.n_valid = D.get<int64_t>(F); o.n_car = D.get<int64_t>(F); o.n_bg = D.get<int64_t>(F); o.mask_count = D.get<int64_t>(F * M);
+        return lpf_first_match(c, nullptr, empty, F, 0, &in, &o);
+    }
+    lpf_wide_input in;
+    lpf_depth_maps_outputs o;
+    memset(&in, 0, sizeof in); memset(&o, 0, sizeof o);
+    in.masks = masks; in.M = M;
+    o.cap = 10; o.pix = D.get<int64_t>(F * 10); o.car_off = D.get<int64_t>(F * (M + 1)); o.need = D.get<int64_t>(F);
+    return lpf_depth_maps(c, nullptr, empty, F, 0, &in, &o);
+}
+
+// An allocation that fails inside lpf_depth_maps_rle / lpf_first_match_rle -- after the walk, which allocates nothing: every one of the
+// call's allocations in turn, each on a fresh context (fake_hip_fail_malloc_after).  The call returns the allocation's error; the
+// caller's arrays are scribbled over and freed (depth_maps / first_match above); then the SAME context runs both dense calls and both
+// run-length calls: nothing of it may still point into those arrays
+static void failed_allocations()
+{
+    lpf_ctx *outer = g_ctx;
+    Rle e = simple(2, 3, 2);
+    e.erode = 1;
+    for (int which = 0; which < 2; ++which) {
+        int failed = 0;
+        for (int n = 0; n < 64; ++n) {
+            lpf_ctx *c = nullptr;
+            CHECK(lpf_create(&c, 0) == LPF_OK && c);
+            g_ctx = c;
+            CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
+            fake_hip_fail_malloc_after(n);
+            const int rc = which ? first_match(c, simple(2, 3, 2), 2) : depth_maps(c, e, 2);
+            fake_hip_fail_malloc_after(-1);
+            if (rc != LPF_OK) {
+                ++failed;
+                CHECK(rc == LPF_ERR_NOMEM && strncmp(lpf_last_error(c), "hipMalloc(", 10) == 0);
+            }
+            CHECK(dense_call(c, false) == LPF_OK);
+            CHECK(dense_call(c, true) == LPF_OK);
+            CHECK(depth_maps(c, e, 2) == LPF_OK);
+            CHECK(first_match(c, simple(2, 3, 2), 2) == LPF_OK);
+            lpf_destroy(c);
+            g_ctx = outer;
+            if (rc == LPF_OK) break;                         // (n allocations sufficed: the call has no more to fail)
+        }
+        CHECK(failed >= 4);                                  // (the tables, the planes, the run tables and the staging buffers at least)
+    }
+}
+
 int main()
 {
     for (int f = 0; f <= FMAX; ++f) g_off[f] = (int64_t)f * NPTS;
@@ -398,6 +458,7 @@ int main()
     several_ranges(c);
     sizes(c);
     pipelined(c);
+    failed_allocations();
     lpf_destroy(c);
     g_ctx = nullptr;
     fake_hip_trace_flush();

@@ -88,7 +88,16 @@ hipError_t hipSetDevice(int) { return 0; }
 hipError_t hipGetLastError(void) { return 0; }
 const char *hipGetErrorString(hipError_t) { return "fake HIP error"; }
 
-hipError_t hipMalloc(void **p, size_t n) { *p = calloc(n ? n : 1, 1); return *p ? 0 : 2; }
+// A failing allocation, for a driver's error paths: after fake_hip_fail_malloc_after(n), n more hipMalloc calls succeed and the next ONE
+// fails (hipErrorOutOfMemory); n < 0 disarms.  Off unless a driver arms it.
+static std::atomic<long long> g_fail_malloc{-1};
+void fake_hip_fail_malloc_after(long long n) { g_fail_malloc = n; }
+hipError_t hipMalloc(void **p, size_t n)
+{
+    if (g_fail_malloc >= 0 && g_fail_malloc-- == 0) { *p = nullptr; return 2; }
+    *p = calloc(n ? n : 1, 1);
+    return *p ? 0 : 2;
+}
 hipError_t hipFree(void *p) { free(p); return 0; }
 hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n ? n : 1); return *p ? 0 : 2; }
 hipError_t hipHostFree(void *p) { free(p); return 0; }
