@@ -71,7 +71,9 @@ extern "C" {
                                       8 (continued): lpf_depth_maps_rle, lpf_first_match_rle_input, lpf_first_match_rle (added; nothing else
                                       changed)
                                       8 (continued): LPF_MASKS_U8 / _F32 / _RLE name lpf_wide_input.f32's values; 2 is new (no symbol, no
-                                         layout change; any other value is now refused) */
+                                         layout change; any other value is now refused)
+                                      8 (continued): LPF_ID_NONE, lpf_id_masks, lpf_set_masks_ids, lpf_run_wide_ids (added; nothing else
+                                         changed) */
 #define LPF_MAX_MASKS_WIDE 256    /* masks per frame of lpf_run_wide: LW = ceil(M / 32) label words per point */
 #define LPF_MAX_CAMS 4            /* cameras of one lpf_run_cams / lpf_run_cams_wide pass */
 
@@ -300,6 +302,47 @@ typedef struct lpf_rle_masks {
     int32_t reserved;        /* 0 */
 } lpf_rle_masks;
 int lpf_set_masks_rle(lpf_ctx *ctx, const lpf_rle_masks *in);
+/* Masks of F frames as INSTANCE-ID MAPS, decoded on the GPU: one image per frame whose pixel value says which instance owns the pixel
+ * -- the form panoptic ground truth is stored in (KITTI-360's 16-bit PNG files under instance/: pixel = semanticId * 1000 + instanceId) and
+ * panoptic segmenters emit.  What reaches the device is the map, H * W * id_bytes per frame whatever M is (1.06 MB of uint16 at
+ * 1408 x 376, where the dense form is 0.53 MB per mask), or nothing at all when the map already sits there.
+ *   ids: [F][H][W] row-major at W, H of lpf_set_camera, uint16 (id_bytes 2, widened unsigned) or int32 (id_bytes 4), in host or device
+ * memory per on_device, aligned to its element and no further.  sel: host memory, [F][M], each frame's own table.
+ *   Membership: pixel p of frame f is in mask m iff sel[f*M+m] != LPF_ID_NONE and (int64)ids[f][p] == (int64)sel[f*M+m].  An entry
+ * outside 0 .. 65535 matches no pixel of a uint16 map (65536 does not match ID 0, -1 does not match 65535); equal entries in one
+ * frame's table each get their bit; LPF_ID_NONE pads frames with fewer instances and matches nothing, even in an int32 map that holds
+ * INT32_MIN.  No input value is used as an index: any map and any table are valid.
+ *   Afterwards the context is in the state lpf_set_masks_u8 leaves for the equivalent dense masks (dense[f][m][p] = 1 iff member) with
+ * the same erode_iters and on_device = 0, once those are packed: lpf_get_label_image is bit-for-bit equal, the label elements have the
+ * same width (1 / 2 / 4 bytes for M <= 8 / 16 / 32), F and M are in force, a pending lpf_set_mask_rects hint is consumed (and ignored),
+ * any record of unpacked masks is forgotten, and every later lpf_run / lpf_run_batch / lpf_run_frame (masks == NULL) gives the same
+ * outputs.  The masks are always packed at the call: every element of the label image is written exactly once, zeros included, from
+ * one read of its pixel's ID (no zero-fill, no atomics; the image does not depend on scheduling); erode_iters iterations of the
+ * context's element (lpf_set_erosion_element) then run on the packed image.  M = 0 zeroes the image and launches no decode; F = 0 does
+ * what lpf_set_masks_rle does with F = 0.  In the software-pipelined modes (2 / 4) the call behaves as lpf_set_masks_rle: what the
+ * pipeline owes is drained first, and the label image goes to the set the next run reads.
+ *   The call returns once its host arrays are copied -- sel always, ids when on_device = 0 (it may wait for that copy, as
+ * lpf_set_masks_u8 does for host masks) -- and waits for nothing else: both may be freed at once, and device ids may be rewritten in
+ * stream order as soon as the call has returned.
+ *   LPF_ERR_STATE before lpf_set_camera, and between lpf_graph_begin and lpf_graph_end (the table is a host copy; there is no
+ * capturable form).  LPF_ERR_ARG, the message naming the field and the context left as it was: in NULL, F < 0, M < 0, erode_iters < 0,
+ * id_bytes not 2 or 4, on_device not 0 or 1, reserved != 0, M > LPF_MAX_MASKS (lpf_set_masks_u8's message), ids NULL with F > 0, sel
+ * NULL with F * M > 0, F * M above 2^31 - 1.
+ *   lpf_run_wide_ids (below) takes the same struct with M up to LPF_MAX_MASKS_WIDE.  Not taken in this form: lpf_run_cams,
+ * lpf_run_cams_wide, lpf_run_frame_wide, lpf_depth_maps, lpf_first_match, lpf_depth_overlays; maps are not resized, the IDs of a frame are
+ * chosen by the caller (sel), and files are not read.  At M <= 2 a uint16 map is more bytes than the dense masks, and masks that
+ * already sit dense on the GPU gain nothing from this form. */
+#define LPF_ID_NONE INT32_MIN          /* a sel entry that selects nothing */
+typedef struct lpf_id_masks {
+    const void    *ids;        /* [F][H][W] at the camera's size, uint16 or int32 per id_bytes; host or device per on_device */
+    const int32_t *sel;        /* host memory, [F][M]: mask m of frame f = the pixels whose id equals sel[f*M+m] */
+    int32_t F, M;              /* 0 <= M <= LPF_MAX_MASKS (lpf_run_wide_ids: LPF_MAX_MASKS_WIDE) */
+    int32_t id_bytes;          /* 2 (unsigned) or 4 (signed) */
+    int32_t erode_iters;       /* >= 0, with the context's element (lpf_set_erosion_element) */
+    int32_t on_device;         /* 0: ids in host memory, copied before the call returns; 1: device memory */
+    int32_t reserved;          /* 0 */
+} lpf_id_masks;
+int lpf_set_masks_ids(lpf_ctx *ctx, const lpf_id_masks *in);
 /* Pre-packed label images [F][H][W] (bit m = mask m). */
 int lpf_set_label_image(lpf_ctx *ctx, const uint32_t *label, int F, int M, int on_device);
 /* Read back the label images currently held ([F][H][W]); for tests of the pack/erode kernels. */
@@ -428,6 +471,17 @@ typedef struct lpf_wide_outputs {
 } lpf_wide_outputs;
 int lpf_run_wide(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
                  const lpf_wide_outputs *out);
+/* lpf_run_wide with its label planes built from instance-ID maps (lpf_id_masks above: in->F == F, 0 <= in->M <= LPF_MAX_MASKS_WIDE,
+ * in->erode_iters with the context's element): every output is bit for bit what lpf_run_wide gives for the equivalent dense uint8 host
+ * masks (dense[f][m][p] = 1 iff member) with the same erode_iters.  All F * ceil(M / 32) * H * W plane words are written once each from
+ * one read of the pixel's ID, the bits at or above M zero; no dense mask exists anywhere.  The struct is checked by
+ * lpf_set_masks_ids' rules before anything is enqueued and before a pipelined context launches what it owes (LPF_ERR_ARG,
+ * "run_wide_ids: ..."; M above LPF_MAX_MASKS_WIDE and in->F != F among them); everything else -- points, frame_off, outputs, boxes, the
+ * state errors -- is lpf_run_wide's.  The context's narrow masks, rectangles and label image are left as they were.  sel is copied
+ * before the call returns; host ids are copied by the call (it waits for that copy), device ids are lent until the run has
+ * completed, like a lpf_wide_input with on_device != 0: with device points, ids and outputs the call waits for nothing on the GPU. */
+int lpf_run_wide_ids(lpf_ctx *ctx, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
+                     const lpf_id_masks *in, const lpf_wide_outputs *out);
 
 /* One frame of a stream with 0 .. LPF_MAX_MASKS_WIDE masks in ONE call: lpf_run_frame's job for frames with more than 32 masks (crowded
  * frames of KITTI-360 have hundreds of annotated boxes; the reference applies every mask of a frame, V3:220).  Exactly the sequence

@@ -15,7 +15,7 @@ LAB_LIB = os.path.join(_HERE, "liblpf_lab.so")       # the same sources with -DL
 SOURCES = ("lpf_api.hip", "lpf_kernels.hip.h", "lpf_reader.hip.h", "lpf_wide.hip.h", "lpf_cams.hip.h", "lpf_cams_wide.hip.h",
            "lpf_frame_wide.hip.h", "lpf_depth_maps.hip.h", "lpf_depth_overlays.hip.h",
            "lpf_match2d.hip.h", "lpf_inside.hip.h", "lpf_box_points.hip.h", "lpf_box_views.hip.h", "lpf_assign.hip.h",
-           "lpf_first_match.hip.h", "lpf_rle.hip.h")
+           "lpf_first_match.hip.h", "lpf_rle.hip.h", "lpf_ids.hip.h")
 ARCH = "gfx950"
 
 # -ffp-contract=off: the kernels spell out every fma() the reference's BLAS performs;

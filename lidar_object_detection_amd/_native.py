@@ -66,6 +66,12 @@ class RleMasksInput(ctypes.Structure):
         return cls(runs.ctypes.data if len(runs) else None, run_off.ctypes.data, F, M, int(erode_iters), 0)
 
 
+class IdMasksInput(ctypes.Structure):
+    """lpf_id_masks (include/lpf.h): the instance-ID maps of an lpf_set_masks_ids / lpf_run_wide_ids call"""
+    _fields_ = [("ids", _P), ("sel", _P), ("F", ctypes.c_int32), ("M", ctypes.c_int32), ("id_bytes", ctypes.c_int32),
+                ("erode_iters", ctypes.c_int32), ("on_device", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class WideOutputs(ctypes.Structure):
     """lpf_wide_outputs (include/lpf.h)"""
     _fields_ = [("uv", _P), ("depth", _P), ("u_f", _P), ("v_f", _P), ("valid_idx", _P), ("uv_valid", _P), ("label_words", _P),
@@ -190,8 +196,9 @@ class CamInput(ctypes.Structure):
                 ("corners_velo", _P), ("box_off", _P), ("boxes_on_device", ctypes.c_int32), ("oriented", ctypes.c_int32)]
 
 
-# A pass's masks, checked (wide_mask_batch, wide_rle_batch).  is_float: False / True for dense masks [F,M,H,W], or "rle" for the
-# run-length form, whose ``masks`` is (runs, run_off, RleMasksInput), on_device False and rects None
+# A pass's masks, checked (wide_mask_batch, wide_rle_batch, wide_ids_batch).  is_float: False / True for dense masks [F,M,H,W], "rle" for
+# the run-length form, whose ``masks`` is (runs, run_off, RleMasksInput), on_device False and rects None, or "ids" for instance-ID maps,
+# whose ``masks`` is (the maps, sel, IdMasksInput)
 MaskBatch = collections.namedtuple("MaskBatch", "masks M is_float on_device rects")
 
 
@@ -276,6 +283,92 @@ def wide_rle_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype",
     if Fr != F:
         raise ValueError("%s: RleMasks for %d frames, the batch has %d" % (who, Fr, F))
     return MaskBatch((runs, run_off, RleMasksInput.of(runs, run_off, F, M, erode_iters)), M, "rle", False, None)
+
+
+def ids_frames(masks, who):
+    """Is this ``masks`` argument a set of instance-ID maps -- one idmap.IdMasks, or a list with one per frame?  The per-frame list of
+    them, or None for anything else; ValueError (``who``: the message's prefix) for a list that mixes IdMasks with another form."""
+    from .idmap import IdMasks
+    frames = [masks] if isinstance(masks, IdMasks) else list(masks) if isinstance(masks, (list, tuple)) else []
+    if not any(isinstance(m, IdMasks) for m in frames):
+        return None
+    if not all(isinstance(m, IdMasks) for m in frames):
+        raise ValueError("%s: the list mixes IdMasks with another form of masks: one form per call (.to_dense())" % who)
+    return frames
+
+
+def ids_batch(frames_masks, H, W, max_masks=LPF_MAX_MASKS, who="set_masks_ids"):
+    """``(maps, sel int32 [F,M], F, M, id_bytes, on_device)`` of one IdMasks or a list of them, one per frame, as lpf_set_masks_ids -- or
+    lpf_run_wide_ids, with ``max_masks`` = 256 -- takes them.  Frames with fewer masks than the largest are padded with LPF_ID_NONE.
+    Host maps are stacked into ONE [F,H,W] array; GPU maps must already be the frames of one contiguous [F,H,W] tensor (``IdMasks(t[f],
+    ...)``), or F = 1: ``maps`` is then the first frame's tensor.  ValueError -- before any native call, with ``who`` as the message's
+    prefix -- for anything that is not an IdMasks, another size than H x W, more than max_masks masks, differing ID dtypes, host and
+    GPU maps in one call, and GPU maps that are not contiguous or do not follow one another in memory."""
+    from .idmap import IdMasks, LPF_ID_NONE, check_sel
+    frames = [frames_masks] if isinstance(frames_masks, IdMasks) else list(frames_masks)
+    for f, r in enumerate(frames):
+        if not isinstance(r, IdMasks):
+            raise ValueError("%s: frame %d is %s, not IdMasks" % (who, f, type(r).__name__))
+        if tuple(r.shape[1:]) != (H, W):
+            raise ValueError("%s: frame %d has a map of %d x %d, the camera is %d x %d (maps are not resized)"
+                             % (who, f, r.shape[2], r.shape[1], W, H))
+        if r.shape[0] > max_masks:
+            raise ValueError("%s: frame %d has %d masks, one pass takes %d (pipeline.run_frames groups them)"
+                             % (who, f, r.shape[0], max_masks))
+    F = len(frames)
+    M = max([r.shape[0] for r in frames], default=0)
+    sel = np.full((F, M), LPF_ID_NONE, np.int32)
+    for f, r in enumerate(frames):
+        sel[f, :r.shape[0]] = check_sel(r.sel, "%s: frame %d" % (who, f))     # (checked again: the fields of an IdMasks can be assigned)
+    if F == 0:
+        return None, sel, 0, M, 2, False
+    dts = {np.dtype(r.id_dtype) for r in frames}
+    if len(dts) != 1:
+        raise ValueError("%s: the frames' maps have differing ID dtypes %s: one dtype per call" % (who, sorted(d.name for d in dts)))
+    dt = dts.pop()
+    dev = [r.on_device for r in frames]
+    if any(dev) != all(dev):
+        raise ValueError("%s: host and GPU maps in one call: one place per call" % who)
+    if not dev[0]:
+        maps = np.ascontiguousarray(frames[0].ids[None] if F == 1 else np.stack([r.ids for r in frames]), dtype=dt)
+        return maps, sel, F, M, dt.itemsize, False
+    t0 = frames[0].ids
+    for f, r in enumerate(frames):
+        if not r.ids.is_cuda or not r.ids.is_contiguous() or r.ids.data_ptr() != t0.data_ptr() + f * H * W * dt.itemsize:
+            raise ValueError("%s: GPU maps must be the frames of ONE contiguous [F,H,W] tensor (IdMasks(t[f], sel)), or F = 1: frame %d "
+                             "is not where frame 0 + %d frames is" % (who, f, f))
+    return [r.ids for r in frames], sel, F, M, dt.itemsize, True
+
+
+def _ids_input(maps, sel, F, M, id_bytes, on_device, erode_iters):
+    """The lpf_id_masks over ids_batch's arrays (which must stay alive as long as it is used)"""
+    if F == 0:
+        ptr = None
+    elif on_device:
+        ptr = maps[0].data_ptr()
+    else:
+        ptr = maps.ctypes.data
+    return IdMasksInput(ptr, sel.ctypes.data if sel.size else None, F, M, id_bytes, int(erode_iters), 1 if on_device else 0, 0)
+
+
+def wide_ids_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", max_masks=LPF_MAX_MASKS_WIDE, who="run_wide"):
+    """The instance-ID form of a pass's masks -- one idmap.IdMasks, or a list with one per frame -- checked before anything reaches the
+    GPU, in the shape wide_mask_batch returns: ``((maps, sel, IdMasksInput), M, "ids", on_device, None)``; None when ``masks`` are not in
+    that form.  Ragged M is padded with LPF_ID_NONE.  ValueError: what ids_batch refuses, ``rects`` (a map needs none), a ``binarize``
+    other than the default, another frame count than F."""
+    frames = ids_frames(masks, who)
+    if frames is None:
+        return None
+    if rects is not None:
+        raise ValueError("%s: rects given with IdMasks (the map says where the masks are)" % who)
+    if binarize != "astype":
+        raise ValueError("%s: binarize=%r with IdMasks (a pixel is a member or it is not)" % (who, binarize))
+    if int(erode_iters) != erode_iters or erode_iters < 0:
+        raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
+    maps, sel, Fr, M, id_bytes, dev = ids_batch(frames, H, W, max_masks, who)
+    if Fr != F:
+        raise ValueError("%s: IdMasks for %d frames, the batch has %d" % (who, Fr, F))
+    return MaskBatch((maps, sel, _ids_input(maps, sel, F, M, id_bytes, dev, erode_iters)), M, "ids", dev, None)
 
 
 class FrameJob(ctypes.Structure):
@@ -375,6 +468,8 @@ def load(path=None):
     lib.lpf_set_masks_u8.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.lpf_set_mask_rects.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.lpf_set_masks_rle.argtypes = [_P, ctypes.POINTER(RleMasksInput)]
+    lib.lpf_set_masks_ids.argtypes = [_P, ctypes.POINTER(IdMasksInput)]
+    lib.lpf_run_wide_ids.argtypes = [_P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(IdMasksInput), ctypes.POINTER(WideOutputs)]
     lib.lpf_set_erosion_element.argtypes = [_P, ctypes.c_int]
     lib.lpf_resize_masks_u8.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
     lib.lpf_erode_masks_u8.argtypes = [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int]
@@ -439,7 +534,7 @@ EXPORTED = ("lpf_abi_version", "lpf_build_id", "lpf_host_alloc", "lpf_host_free"
             "lpf_reader_submit_frame", "lpf_reader_boxes", "lpf_parse_boxes_json", "lpf_run_wide", "lpf_run_cams",
             "lpf_run_cams_wide", "lpf_run_frame_wide", "lpf_depth_maps", "lpf_depth_overlays", "lpf_match_2d",
             "lpf_inside_masks", "lpf_set_erosion_element", "lpf_box_points", "lpf_box_views", "lpf_assign_costs", "lpf_assign_2d",
-            "lpf_first_match", "lpf_set_masks_rle", "lpf_depth_maps_rle", "lpf_first_match_rle")
+            "lpf_first_match", "lpf_set_masks_rle", "lpf_depth_maps_rle", "lpf_first_match_rle", "lpf_set_masks_ids", "lpf_run_wide_ids")
 
 BOXES_PARSED, BOXES_ABSENT, BOXES_OTHER, BOXES_NONE = 0, 1, 2, 3          # enum lpf_boxes_state
 
@@ -982,6 +1077,28 @@ class LpfContext:
         self._check(self._lib.lpf_set_masks_rle(self._h, ctypes.byref(inp)))
         self.F_masks, self.M = F, M
 
+    def set_masks_ids(self, frames_masks, erode_iters=0):
+        """Masks as instance-ID maps (idmap.IdMasks: one, or a list with one per frame), decoded on the GPU: what reaches the device is
+        the map -- H * W * 2 or 4 bytes per frame whatever M is -- or nothing when the map is a GPU tensor.  Afterwards the context is
+        as after ``set_masks(dense uint8 host masks, erode_iters)`` with the same members.  Ragged M is padded with LPF_ID_NONE; the
+        maps must have the camera's size and one dtype; host maps are stacked into one [F,H,W] array, GPU maps must be the frames of one
+        contiguous [F,H,W] tensor (or F = 1) and are read where they are; at most LPF_MAX_MASKS per frame (pipeline.run_frames groups
+        more)."""
+        if ids_frames(frames_masks, "set_masks_ids") is None and not (isinstance(frames_masks, (list, tuple)) and not len(frames_masks)):
+            raise ValueError("set_masks_ids: masks must be an IdMasks or a list of them, got %s" % type(frames_masks).__name__)
+        if int(erode_iters) != erode_iters or erode_iters < 0:
+            raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
+        maps, sel, F, M, id_bytes, dev = ids_batch(frames_masks, self.H, self.W)
+        if dev:
+            import torch
+            self.wait_for_stream(torch.cuda.current_stream(maps[0].device).cuda_stream)     # the maps were produced on torch's stream
+        inp = _ids_input(maps, sel, F, M, id_bytes, dev, erode_iters)
+        rc = self._lib.lpf_set_masks_ids(self._h, ctypes.byref(inp))
+        if dev:
+            self._lent.append(maps)                          # (the decode reads them in stream order)
+        self._check(rc)
+        self.F_masks, self.M = F, M
+
     def clear_masks(self):
         self._check(self._lib.lpf_set_masks_u8(self._h, None, 0, 0, 0, 0))
         self.F_masks, self.M = 0, 0
@@ -1423,7 +1540,9 @@ class LpfContext:
         float32 under ``binarize`` as set_masks), host or GPU (lent until the call returns: it waits for its results); or in run-length
         form -- one rle.RleMasks, or a list with one per frame (ragged M is padded with empty masks), at the camera's size, without
         ``rects`` and under the default ``binarize``: the runs are decoded into the label planes on the GPU, nothing dense crosses to the
-        device, and every result equals the one ``.to_dense()`` masks give.  rects: the
+        device, and every result equals the one ``.to_dense()`` masks give; or as instance-ID maps -- one idmap.IdMasks, or a list with
+        one per frame (ragged M is padded with LPF_ID_NONE), under set_masks_ids' rules: lpf_run_wide_ids builds the label planes from
+        the map on the GPU, with the same results as ``.to_dense()`` masks.  rects: the
         optional [F,M,4] hint of set_mask_rects.  Boxes and camera are the ones in force; the masks, boxes and rectangles of the
         narrow calls are left as they are.  Returns one dict per frame with what run_batch returns -- inst_count, best_box,
         best_cnt of length M, count_mb [M, B_f] -- plus label_words [N_f, LW] (bit b of word w = mask 32 w + b; LW = ceil(M / 32)),
@@ -1433,20 +1552,27 @@ class LpfContext:
         F = len(frames)
         if F == 0:
             raise ValueError("no frames")
-        batch = wide_rle_batch(masks, F, self.H, self.W, rects, erode_iters, binarize) or \
+        batch = wide_ids_batch(masks, F, self.H, self.W, rects, erode_iters, binarize) or \
+            wide_rle_batch(masks, F, self.H, self.W, rects, erode_iters, binarize) or \
             wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
         M = batch.M
         off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the run returns)
         n = int(off[-1])
-        inp = WideInput()
-        self._wide_input(inp, batch, binarize, erode_iters)
+        if batch.is_float == "ids":                          # instance-ID maps: the call of its own, the struct as wide_ids_batch made it
+            native, inp = self._lib.lpf_run_wide_ids, batch.masks[2]
+            if batch.on_device:
+                import torch
+                self.wait_for_stream(torch.cuda.current_stream(batch.masks[0][0].device).cuda_stream)
+        else:
+            native, inp = self._lib.lpf_run_wide, WideInput()
+            self._wide_input(inp, batch, binarize, erode_iters)
         Btot = int(self.box_off[-1]) if self.box_off is not None else 0
         wants = dict(want_uv=want_uv, want_float=want_float, want_lists=want_lists, want_valid_uv=want_valid_uv)
 
         def launch(inst_cap):
             o = WideOutputs()
             finish = self._wide_host_outputs(o, n, F, M, Btot, inst_cap, **wants)
-            self._check(self._lib.lpf_run_wide(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
+            self._check(native(self._h, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o)))
             return finish()
 
         out = self._until_lists_fit(launch, inst_cap, off)

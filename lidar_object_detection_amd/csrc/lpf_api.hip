@@ -15,6 +15,7 @@
 #include "lpf_box_views.hip.h"
 #include "lpf_first_match.hip.h"
 #include "lpf_rle.hip.h"
+#include "lpf_ids.hip.h"
 #include "../../include/lpf.h"
 
 #include <algorithm>
@@ -105,6 +106,7 @@ struct lpf_ctx {
 
     // masks -> label images
     DevBuf mask_stage;
+    DevBuf ids_stage;                 // lpf_set_masks_ids: [sel | host ids] of the call being decoded (ids_stage_tables)
     DevBuf rle_stage;                 // lpf_set_masks_rle: [runs | work units | run_off] of the call being decoded
     // run-length masks, walked (rle_walk): the checked input and its work units (kept for their capacity).  One record per camera of a
     // multi-camera pass; lpf_set_masks_rle, lpf_run_wide and the two analysis calls use record 0.  Host storage of its own for every
@@ -302,7 +304,7 @@ struct lpf_ctx {
     std::vector<char> h_tab;          // [frames | segs | blks] being built
 
     // lpf_run_wide: its own buffers (the narrow masks, label images and staging stay as they are)
-    struct Wide { DevBuf tab, masks, rects, rle, planes_a, planes_b, flags, ccnt, cpre, fcnt, midx, mwords, mpts, cnt, pts, out; } wide;
+    struct Wide { DevBuf tab, masks, rects, rle, ids, planes_a, planes_b, flags, ccnt, cpre, fcnt, midx, mwords, mpts, cnt, pts, out; } wide;
     // lpf_run_cams: camera c's box tables, label images, staged masks / rectangles and host-output staging (grow-only, allocated on
     // first use); its counters and geometry tables are scratch set c's
     struct Cams { BoxSet bx[LPF_NSETS]; DevBuf label_a[LPF_NSETS], label_b[LPF_NSETS], masks[LPF_NSETS], rects[LPF_NSETS], rle[LPF_NSETS], out[LPF_NSETS], pts; } cams;
@@ -1364,6 +1366,124 @@ int wide_pack_runs(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_ctx::RleIn &R, int Wi
     return LPF_OK;
 }
 
+// ---- instance-ID maps (lpf_id_masks, include/lpf.h): the checks, the staging and the decodes of lpf_set_masks_ids / lpf_run_wide_ids ----
+
+template <typename Fn> auto with_id(int id_bytes, Fn &&fn)
+{
+    if (id_bytes == 2) return fn(TypeTag<uint16_t>());
+    return fn(TypeTag<int32_t>());
+}
+
+// blocks per frame of the ID-map decodes (lpf_ids.hip.h) for images of hw pixels: one thread per 16-byte group of IDs, hw / PER groups
+// at the most whatever the frame's alignment; at least one block, which also takes the frame's head and tail
+size_t ids_blocks(size_t hw, int id_bytes)
+{
+    const size_t nvec = hw / (size_t)(16 / id_bytes);
+    return std::max<size_t>(1, (nvec + LPF_IDS_BLOCK - 1) / LPF_IDS_BLOCK);
+}
+
+// Every check of a lpf_id_masks (not NULL, its M within the call's limit) for images of hw pixels: each refusal names its field.  Nothing
+// behind the two pointers is read -- any map and any table are valid input -- and nothing is enqueued.  who: the messages' prefix
+int check_ids(lpf_ctx *c, const char *who, const lpf_id_masks *in, size_t hw)
+{
+    if (in->F < 0) return fail(c, LPF_ERR_ARG, "%s: F=%d (must be >= 0)", who, in->F);
+    if (in->M < 0) return fail(c, LPF_ERR_ARG, "%s: M=%d (must be >= 0)", who, in->M);
+    if (in->erode_iters < 0) return fail(c, LPF_ERR_ARG, "%s: erode_iters=%d (must be >= 0)", who, in->erode_iters);
+    if (in->id_bytes != 2 && in->id_bytes != 4) return fail(c, LPF_ERR_ARG, "%s: id_bytes=%d (2: uint16 IDs, 4: int32 IDs)", who, in->id_bytes);
+    if (in->on_device != 0 && in->on_device != 1)
+        return fail(c, LPF_ERR_ARG, "%s: on_device=%d (0: ids in host memory, 1: device memory)", who, in->on_device);
+    if (in->reserved != 0) return fail(c, LPF_ERR_ARG, "%s: reserved=%d (must be 0)", who, in->reserved);
+    const long long FM = (long long)in->F * in->M;
+    if (FM > 0x7fffffffll) return fail(c, LPF_ERR_ARG, "%s: F * M = %lld table entries (at most 2^31 - 1 in one call)", who, FM);
+    if (in->F > 0 && !in->ids) return fail(c, LPF_ERR_ARG, "%s: ids=NULL with F=%d", who, in->F);
+    if (FM > 0 && !in->sel) return fail(c, LPF_ERR_ARG, "%s: sel=NULL with F=%d M=%d", who, in->F, in->M);
+    if ((unsigned long long)in->F * ids_blocks(hw, in->id_bytes) > 0x7fffffffull)
+        return fail(c, LPF_ERR_ARG, "%s: F=%d frames of %zu pixels are more blocks than one launch takes (2^31 - 1): set fewer frames per call",
+                    who, in->F, hw);
+    return LPF_OK;
+}
+
+// [sel | host ids] of a checked lpf_id_masks (F * M > 0) for images of hw pixels -> `stage`, in stream order; *sel, *ids: what the decode
+// reads.  sel goes through the pinned upload ring: it is copied when this returns, with no wait on the stream.  Host ids are copied from
+// the caller's memory and *host_in is set -- the caller owes a host_wait before it returns; device ids are read where they are
+int ids_stage_tables(lpf_ctx *c, DevBuf &stage, const lpf_id_masks *in, size_t hw, const int32_t **sel, const void **ids, bool *host_in)
+{
+    const size_t n_sel = (size_t)in->F * in->M * sizeof(int32_t), b_sel = align256(n_sel);
+    const size_t b_ids = in->on_device ? 0 : (size_t)in->F * hw * in->id_bytes;
+    int rc;
+    if ((rc = reserve(c, stage, b_sel + b_ids))) return rc;
+    if ((rc = upload(c, stage.p, in->sel, n_sel))) return rc;
+    *sel = (const int32_t *)stage.p;
+    *ids = in->ids;
+    if (!in->on_device) {
+        LPF_HIP(c, hipMemcpyAsync((char *)stage.p + b_sel, in->ids, b_ids, hipMemcpyHostToDevice, c->stream));
+        *ids = (char *)stage.p + b_sel;
+        *host_in = true;
+    }
+    return LPF_OK;
+}
+
+// The narrow label image [F][H][W] of `label_bytes` per pixel from a checked lpf_id_masks: ONE launch of lpf_ids_label writes every
+// element (no memset in front), then every erosion iteration runs on the packed image -- into la (lb_ = erosion ping-pong), the tables
+// staged in `stage`.  M = 0: the image is zeroed, nothing is launched.  *result: the buffer that holds the image
+int ids_label_image(lpf_ctx *c, DevBuf &la, DevBuf &lb_, DevBuf &stage, const lpf_id_masks *in, const int W, const int H, int label_bytes,
+                    void **result, bool *host_in)
+{
+    const int F = in->F, M = in->M;
+    const size_t hw = (size_t)W * H;
+    int rc;
+    if ((rc = reserve(c, la, (size_t)F * hw * 4))) return rc;        // (4 bytes per pixel, as every label image is reserved)
+    *result = la.p;
+    if (M == 0) {
+        LPF_HIP(c, hipMemsetAsync(la.p, 0, (size_t)F * hw * label_bytes, c->stream));
+        return LPF_OK;
+    }
+    const int32_t *sel = nullptr;
+    const void *ids = nullptr;
+    if ((rc = ids_stage_tables(c, stage, in, hw, &sel, &ids, host_in))) return rc;
+    const unsigned nblk = (unsigned)ids_blocks(hw, in->id_bytes);
+    const Erosion E = erosion(c, in->erode_iters);
+    return with_id(in->id_bytes, [&](auto it) -> int {
+        typedef typename decltype(it)::type IT;
+        return with_label(label_bytes, [&](auto lt) -> int {
+            typedef typename decltype(lt)::type LT;
+            hipLaunchKernelGGL((lpf_ids_label<IT, LT>), dim3(nblk * (unsigned)F), dim3(LPF_IDS_BLOCK), 0, c->stream, (const IT *)ids, sel,
+                               (LT *)la.p, (long long)hw, M, nblk);
+            LPF_HIP(c, hipGetLastError());
+            LT *img = (LT *)la.p;
+            const int rc_ = erode_packed_iters(c, img, lb_, W, H, F, c->stream, E.iters, E.element);
+            *result = img;
+            return rc_;
+        });
+    });
+}
+
+// The wide passes' label planes [F][LW][Himg][Wimg] (wide_pack) from a checked lpf_id_masks (M > 0), in D's planes_a / planes_b,
+// *planes = the buffer that holds the result: ONE launch of lpf_ids_planes writes all F * LW * Himg * Wimg words (no memset in front;
+// the bits at or above M are zero), then every erosion iteration.  No dense mask is staged
+int wide_pack_ids(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_id_masks *in, int Wimg, int Himg, const uint32_t **planes, bool *host_in)
+{
+    int rc;
+    const int F = in->F, M = in->M, LW = (M + 31) / 32;
+    const size_t hw = (size_t)Wimg * Himg;
+    if ((rc = reserve(c, D.planes_a, (size_t)F * LW * hw * 4))) return rc;
+    uint32_t *cur = (uint32_t *)D.planes_a.p;
+    const int32_t *sel = nullptr;
+    const void *ids = nullptr;
+    if ((rc = ids_stage_tables(c, D.ids, in, hw, &sel, &ids, host_in))) return rc;
+    const unsigned nblk = (unsigned)ids_blocks(hw, in->id_bytes);
+    with_id(in->id_bytes, [&](auto it) {
+        typedef typename decltype(it)::type IT;
+        hipLaunchKernelGGL((lpf_ids_planes<IT>), dim3(nblk * (unsigned)F), dim3(LPF_IDS_BLOCK), 0, c->stream, (const IT *)ids, sel, cur,
+                           (long long)hw, M, LW, nblk);
+    });
+    LPF_HIP(c, hipGetLastError());
+    const Erosion E = erosion(c, in->erode_iters);
+    if ((rc = erode_packed_iters(c, cur, D.planes_b, Wimg, Himg, F * LW, c->stream, E.iters, E.element))) return rc;
+    *planes = cur;
+    return LPF_OK;
+}
+
 // The frames [f0, f0 + fc) of a walked batch A (A.in->M > 0): rle_walk emits the units in run order, so the range's runs and units are
 // contiguous pieces of A's.  rle_units_before: the units of the runs before run r, i.e. the first unit of r (or of the next run that has one)
 size_t rle_units_before(const lpf_ctx::RleIn &A, long long r)
@@ -1865,7 +1985,7 @@ void lpf_destroy(lpf_ctx *c)
     }
     release(c->cams.pts);
     for (lpf_ctx::Wide *D : {&c->wide, &c->camsw.cam[0], &c->camsw.cam[1], &c->camsw.cam[2], &c->camsw.cam[3]}) {
-        DevBuf *wb[] = {&D->tab, &D->masks, &D->rects, &D->rle, &D->planes_a, &D->planes_b, &D->flags, &D->ccnt, &D->cpre, &D->fcnt, &D->midx, &D->mwords,
+        DevBuf *wb[] = {&D->tab, &D->masks, &D->rects, &D->rle, &D->ids, &D->planes_a, &D->planes_b, &D->flags, &D->ccnt, &D->cpre, &D->fcnt, &D->midx, &D->mwords,
                         &D->mpts, &D->cnt, &D->pts, &D->out};
         for (DevBuf *b : wb) release(*b);
     }
@@ -1879,7 +1999,7 @@ void lpf_destroy(lpf_ctx *c)
         for (DevBuf *b : {&D->tab, &D->pts, &D->in, &D->out}) release(*b);
     release(c->fmat.code);
     release(c->fmat.tiles);
-    DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->rle_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
+    DevBuf *all[] = {&c->resize_buf, &c->lab_clk, &c->mask_stage, &c->rle_stage, &c->ids_stage, &c->pib_box, &c->pib_pts, &c->pib_out, &c->boxprep, &c->dimg, &c->coll, &c->st_pts, &c->out_stage};
     for (DevBuf *b : all) release(*b);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ring.ev) if (e) (void)hipEventDestroy(e);
@@ -2136,6 +2256,38 @@ int lpf_set_masks_rle(lpf_ctx *c, const lpf_rle_masks *in)
     bool staged = false;
     if ((rc = rle_label_image(c, S.label_a, S.label_b, c->rle_stage, R.A, c->W, c->H, lb, &cur, &staged))) return rc;
     if (staged) LPF_HIP(c, host_wait(c));                   // the caller's arrays (and the unit table) may be reused
+    MK.packed(F, M, cur, lb);
+    return LPF_OK;
+}
+
+// Instance-ID maps (include/lpf.h): the struct is checked before anything is queued, then the state transitions of lpf_set_masks_rle
+// -- drain what a pipelined context owes, the label image of the set the next run reads -- with ONE decode launch that writes every
+// element (+ erosion on the packed image) in place of zero + decode.  Always packed at the call.
+int lpf_set_masks_ids(lpf_ctx *c, const lpf_id_masks *in)
+{
+    if (!c) return LPF_ERR_ARG;
+    if (use_device(c)) return LPF_ERR_HIP;
+    if (!c->have_camera) return fail(c, LPF_ERR_STATE, "lpf_set_camera must be called before masks (W, H)");
+    if (c->capturing)
+        return fail(c, LPF_ERR_STATE, "lpf_set_masks_ids cannot be captured into a graph (the table of selected IDs is a host copy: call it "
+                                      "outside lpf_graph_begin ... lpf_graph_end)");
+    if (!in) return fail(c, LPF_ERR_ARG, "lpf_set_masks_ids: in=NULL");
+    if (in->M > LPF_MAX_MASKS) return too_many_masks(c, in->M);
+    int rc;
+    if ((rc = check_ids(c, "lpf_set_masks_ids", in, (size_t)c->W * c->H))) return rc;
+    const int F = in->F, M = in->M;
+    if (c->pipe.owes() && (rc = sync_all(c))) return rc;
+    lpf_ctx::Masks &MK = c->masks;
+    lpf_ctx::Scratch &S = c->sc[c->pipe.set_now()];
+    MK.begin(c->pipe.set_now());
+    if (F == 0) return LPF_OK;
+    const int lb = (M <= 8) ? 1 : (M <= 16) ? 2 : 4;
+    c->rects_pending = nullptr;                             // a pending lpf_set_mask_rects hint is consumed (a map needs none)
+    MK.forget_unpacked();
+    void *cur = nullptr;
+    bool host_in = false;
+    if ((rc = ids_label_image(c, S.label_a, S.label_b, c->ids_stage, in, c->W, c->H, lb, &cur, &host_in))) return rc;
+    if (host_in) LPF_HIP(c, host_wait(c));                  // the caller's host map may be reused (sel was copied at the call)
     MK.packed(F, M, cur, lb);
     return LPF_OK;
 }
@@ -2798,12 +2950,14 @@ static int wide_pack_dense(lpf_ctx *c, lpf_ctx::Wide &D, const void *d_masks, co
 }
 
 // ... from a pass's lpf_wide_input (host masks are staged into D and *host_in is set; device masks are lent), or, where it is in the
-// run-length form, from R, its walked masks (check_wide_rle).  *planes = NULL without masks
+// run-length form, from R, its walked masks (check_wide_rle), or from `ids`, the checked instance-ID maps of lpf_run_wide_ids (NULL for
+// everyone else; `in` then carries M and erode_iters only).  *planes = NULL without masks
 static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int F, int Wimg, int Himg, const lpf_ctx::RleIn &R,
-                     const uint32_t **planes, bool *host_in)
+                     const lpf_id_masks *ids, const uint32_t **planes, bool *host_in)
 {
     *planes = nullptr;
     if (in->M == 0) return LPF_OK;
+    if (ids) return wide_pack_ids(c, D, ids, Wimg, Himg, planes, host_in);
     if (R.in) return wide_pack_runs(c, D, R, Wimg, Himg, planes, host_in);
     int rc;
     const void *d_masks = nullptr;
@@ -2855,22 +3009,24 @@ static int wide_bind(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_outputs *out, 
 // lpf_run_wide's whole run.  direct: the projecting stage reads the lent uint8 masks inside their rectangles (lpf_wide_direct_project)
 // instead of packing them into planes for lpf_wide_project -- lpf_run_frame_wide's form for sparse frames; the caller has checked that
 // in->masks / in->rects are device memory, uint8, no erosion, M > 0, rects 16-byte aligned.  Everything else is shared: the checks, the
-// box job, the frame table, wide_bind and the launches after projection.
+// box job, the frame table, wide_bind and the launches after projection.  ids: the source of the planes of lpf_run_wide_ids -- its
+// instance-ID maps, checked by the caller (in: their M and erode_iters, masks = the maps); NULL: the planes come from `in`.
 static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
-                         const lpf_wide_outputs *out, bool direct)
+                         const lpf_wide_outputs *out, bool direct, const lpf_id_masks *ids = nullptr)
 {
     int rc;
-    if ((rc = enter(c, "lpf_run_wide", true))) return rc;
-    if (!in || !out || !frame_off || F <= 0) return fail(c, LPF_ERR_ARG, "run_wide: in=%p out=%p frame_off=%p F=%d", (const void *)in, (const void *)out, (const void *)frame_off, F);
+    const char *who = ids ? "run_wide_ids" : "run_wide";
+    if ((rc = enter(c, ids ? "lpf_run_wide_ids" : "lpf_run_wide", true))) return rc;
+    if (!in || !out || !frame_off || F <= 0) return fail(c, LPF_ERR_ARG, "%s: in=%p out=%p frame_off=%p F=%d", who, (const void *)in, (const void *)out, (const void *)frame_off, F);
     const int M = in->M;
-    if ((rc = check_wide_input(c, "run_wide", -1, *in, LPF_MAX_MASKS_WIDE, "lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE", "", true))) return rc;
-    if ((rc = check_frames(c, "run_wide", pts, frame_off, F, LPF_WIDE_CHUNK))) return rc;
+    if ((rc = check_wide_input(c, who, -1, *in, LPF_MAX_MASKS_WIDE, "lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE", "", true))) return rc;
+    if ((rc = check_frames(c, who, pts, frame_off, F, LPF_WIDE_CHUNK))) return rc;
     lpf_ctx::RleIn &R = c->rle_in[0];                      // run-length masks: checked in full here, before anything is enqueued
-    if ((rc = check_wide_rle(c, "run_wide", -1, *in, F, (long long)c->W * c->H, R))) return rc;
+    if ((rc = check_wide_rle(c, who, -1, *in, F, (long long)c->W * c->H, R))) return rc;
     const int64_t Ntot = frame_off[F];
-    if (out->inst_idx && out->inst_cap <= 0) return fail(c, LPF_ERR_ARG, "run_wide: inst_idx given with inst_cap=%lld", (long long)out->inst_cap);
+    if (out->inst_idx && out->inst_cap <= 0) return fail(c, LPF_ERR_ARG, "%s: inst_idx given with inst_cap=%lld", who, (long long)out->inst_cap);
     lpf_ctx::BoxSet &BX = c->boxes.in_force();
-    if (BX.F != 0 && BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, run_wide has %d", BX.F, F);
+    if (BX.F != 0 && BX.F != F) return fail(c, LPF_ERR_STATE, "boxes were set for %d frames, %s has %d", BX.F, who, F);
     // a software-pipelined context launches what it owes first (no host wait): everything below runs in stream order behind it
     if ((rc = flush_pending(c))) return rc;
     c->boxes.claimed_by_run();
@@ -2896,7 +3052,7 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     bool pts_in = false, masks_in = false;
     if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, 0, n, n, &W.pts, &pts_in))) return rc;
     if (direct) W.planes = nullptr;
-    else if ((rc = wide_pack(c, D, in, F, c->W, c->H, R, &W.planes, &masks_in))) return rc;
+    else if ((rc = wide_pack(c, D, in, F, c->W, c->H, R, ids, &W.planes, &masks_in))) return rc;
 
     // ---- buffers: the caller's device pointers, or staging for host callers ---------------------------------------------------
     const size_t nMB = (size_t)M * Btot;
@@ -2940,6 +3096,24 @@ int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, 
                  const lpf_wide_outputs *out)
 {
     return run_wide_impl(c, pts, frame_off, F, pts_on_device, in, out, false);
+}
+
+// lpf_run_wide with its planes built from instance-ID maps: the struct is checked here, before run_wide_impl launches what a pipelined
+// context owes or queues anything; the run itself is lpf_run_wide's, with wide_pack_ids as the source of its planes
+int lpf_run_wide_ids(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_id_masks *in,
+                     const lpf_wide_outputs *out)
+{
+    int rc;
+    if ((rc = enter(c, "lpf_run_wide_ids", true))) return rc;
+    if (!in) return fail(c, LPF_ERR_ARG, "run_wide_ids: in=NULL");
+    if (in->M > LPF_MAX_MASKS_WIDE)
+        return fail(c, LPF_ERR_ARG, "run_wide_ids: M=%d masks per frame, lpf_run_wide_ids takes 0 .. LPF_MAX_MASKS_WIDE = %d", in->M, LPF_MAX_MASKS_WIDE);
+    if ((rc = check_ids(c, "run_wide_ids", in, (size_t)c->W * c->H))) return rc;
+    if (in->F != F) return fail(c, LPF_ERR_ARG, "run_wide_ids: the ID maps say F=%d, the call has F=%d", in->F, F);
+    lpf_wide_input w;
+    memset(&w, 0, sizeof w);
+    w.masks = in->ids; w.M = in->M; w.f32 = LPF_MASKS_U8; w.erode_iters = in->erode_iters; w.on_device = in->on_device;
+    return run_wide_impl(c, pts, frame_off, F, pts_on_device, &w, out, false, in);
 }
 
 // ---- lpf_depth_maps (include/lpf.h): per-car depth maps as sparse lists, kernels in lpf_depth_maps.hip.h ----------------------
@@ -4116,7 +4290,7 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
         const int M = I.masks.M, LW = (M + 31) / 32;
         wide_params(W, input_cam(I), F, M, nchunk, nbw[k], BX, out[k].inst_cap, (const LpfWideFrame *)c->camsw.tab.p + (size_t)k * F);
         W.pts = d_pts;
-        if ((rc = wide_pack(c, D, &I.masks, F, I.W, I.H, c->rle_in[k], &W.planes, &host_in))) return rc;
+        if ((rc = wide_pack(c, D, &I.masks, F, I.W, I.H, c->rle_in[k], nullptr, &W.planes, &host_in))) return rc;
         if ((rc = wide_bind(c, D, &out[k], n, F, Btot[k], W, S[k]))) return rc;
         max_lists = std::max(max_lists, F * std::max(LW, 1));
         if (M > 0 && Btot[k] > 0) {

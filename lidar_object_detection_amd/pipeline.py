@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _native, kitti360
 from ._native import LpfContext, LPF_MAX_CAMS, LPF_MAX_MASKS, LPF_MAX_MASKS_WIDE, Scan, ScanReader
+from .idmap import IdMasks
 from .rle import RleMasks
 
 _CONTEXTS = {}
@@ -1651,11 +1652,40 @@ def _rle_frame_masks(frames, camera, size=None):
     return out
 
 
+def _ids_frame_masks(frames, camera):
+    """Each frame's IdMasks when the batch's masks come as instance-ID maps, None when no frame's do.  A frame without masks -- None, an
+    empty list -- gets an empty one over a zero host map of the batch's ID dtype.  ValueError, before anything reaches the library: a
+    batch that mixes IdMasks with another form, a map of another size than the camera's (maps are not resized), and a frame without
+    masks among GPU maps (the maps of a GPU batch are the frames of one tensor: give that frame ``IdMasks(t[f], [])``)."""
+    is_ids = [isinstance(f.masks, IdMasks) for f in frames]
+    if not any(is_ids):
+        return None
+    H, W = camera.height, camera.width
+    first = next(f.masks for f, r in zip(frames, is_ids) if r)
+    out = []
+    for f, r in zip(frames, is_ids):
+        if r:
+            if tuple(f.masks.shape[1:]) != (H, W):
+                raise ValueError("frame %s: an ID map of %d x %d, the camera is %d x %d (maps are not resized: use .to_dense())"
+                                 % (f.frame, f.masks.shape[2], f.masks.shape[1], W, H))
+            out.append(f.masks)
+        elif f.masks is None or len(f.masks) == 0:
+            if first.on_device:
+                raise ValueError("frame %s: no masks in a batch of GPU ID maps: give it IdMasks(t[f], []) over its frame of the batch's "
+                                 "tensor" % (f.frame,))
+            out.append(IdMasks(np.zeros((H, W), first.id_dtype), []))
+        else:
+            raise ValueError("frame %s: another form of masks in a batch of IdMasks frames: one form per batch (.to_dense())" % (f.frame,))
+    return out
+
+
 def _run_frames_rle(frames, rles, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, device, ctx, gather_scans,
                     erosion_kernel_size):
     """run_frames for frames whose masks are RleMasks (the camera and the erosion element set): up to 32 masks in one narrow pass behind
     set_masks_rle, 33 to 256 in ONE wide pass (run_wide takes the runs as they are) -- the runs go to the GPU, not the masks -- more in
-    groups of 256.  On 0/1 masks V3's cast chain is the erosion alone, so v3_pipeline needs nothing beyond erode_iters."""
+    groups of 256.  On 0/1 masks V3's cast chain is the erosion alone, so v3_pipeline needs nothing beyond erode_iters.
+    Frames whose masks are IdMasks take the same route: set_masks_ids in set_masks_rle's place, run_wide on the maps, groups by slices
+    of the IdMasks (which share the map) -- the map goes to the GPU, or is read where it is."""
     counts = [r.shape[0] for r in rles]
     if max(counts) > LPF_MAX_MASKS_WIDE:
         return _run_frames_in_mask_groups(frames, rles, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, False,
@@ -1666,7 +1696,7 @@ def _run_frames_rle(frames, rles, TrVeloToRect, camera, depth_max, min_points, u
         ctx.set_boxes(list(corners), oriented=use_oriented)
         res = ctx.run_wide(pts, rles, erode_iters=erode_iters, want_uv=False, want_valid_uv=True)
     else:
-        ctx.set_masks_rle(rles, erode_iters=erode_iters)
+        (ctx.set_masks_ids if isinstance(rles[0], IdMasks) else ctx.set_masks_rle)(rles, erode_iters=erode_iters)
         ctx.set_boxes(list(corners), oriented=use_oriented)
         res = ctx.run_batch(pts, want_uv=False, want_label=False, want_valid_uv=True, pinned=True)
     return [_frame_result(f, r, m, pos, min_points, gather_scans) for f, r, m, pos in zip(frames, res, counts, positions)]
@@ -1685,11 +1715,13 @@ def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_
     k x k MORPH_ELLIPSE element (odd, 1 .. 15; 3 is the cross).  It is set on the context by every call, the default included.
     Frames whose ``masks`` are ``rle.RleMasks`` (at the camera's size; every frame of the batch, a frame without masks aside) take
     set_masks_rle, or with 33 to 256 masks ONE run_wide pass: the runs are decoded on the GPU, nothing dense crosses to the device; more
-    than 256 masks run in groups of 256."""
+    than 256 masks run in groups of 256.  Frames whose ``masks`` are ``idmap.IdMasks`` (instance-ID maps at the camera's size, one ID
+    dtype, all in host memory or all the frames of one GPU tensor) take the same route behind set_masks_ids / run_wide: the labels are
+    built from the map on the GPU, and no dense mask exists anywhere.  One form per batch."""
     erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     if not frames:
         return []
-    rles = _rle_frame_masks(frames, camera)
+    rles = _rle_frame_masks(frames, camera) or _ids_frame_masks(frames, camera)
     ctx = ctx or get_context(device)
     ctx.set_erosion_element(erosion_kernel_size)
     H, W = camera.height, camera.width
