@@ -13,6 +13,8 @@ import weakref
 import numpy as np
 
 from . import _build
+from .idmap import IdMasks
+from .rle import RleMasks
 
 LPF_MAX_MASKS = 32
 LPF_ASSIGN_MAX = 1024             # rows and live columns of a frame of lpf_assign_costs / lpf_assign_2d
@@ -196,10 +198,18 @@ class CamInput(ctypes.Structure):
                 ("corners_velo", _P), ("box_off", _P), ("boxes_on_device", ctypes.c_int32), ("oriented", ctypes.c_int32)]
 
 
-# A pass's masks, checked (wide_mask_batch, wide_rle_batch, wide_ids_batch).  is_float: False / True for dense masks [F,M,H,W], "rle" for
-# the run-length form, whose ``masks`` is (runs, run_off, RleMasksInput), on_device False and rects None, or "ids" for instance-ID maps,
-# whose ``masks`` is (the maps, sel, IdMasksInput)
-MaskBatch = collections.namedtuple("MaskBatch", "masks M is_float on_device rects")
+# A pass's masks, checked (wide_mask_batch, compact_mask_batch).  form "dense": ``masks`` [F,M,H,W], ``is_float``, ``rects`` [F,M,4] or
+# None.  form "rle" / "ids" (a row of MASK_FORMS): ``struct`` is the form's ctypes struct as the native calls take it and ``tables`` the
+# two arrays it points into, which must stay alive as long as it is used; ``masks`` and ``rects`` are None.  gpu: a tensor of the inputs
+# when they are GPU memory (``on_device``) -- a call that reads them waits for the stream that made them -- else None.
+MaskBatch = collections.namedtuple("MaskBatch", "masks M is_float on_device rects form struct tables gpu",
+                                   defaults=("dense", None, None, None))
+
+
+def _check_erode_iters(erode_iters):
+    """The erosion count of a checked batch and of set_masks_ids (set_masks_rle keeps a looser check of its own)"""
+    if int(erode_iters) != erode_iters or erode_iters < 0:
+        raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
 
 
 def wide_mask_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", binarize_codes=None):
@@ -208,8 +218,7 @@ def wide_mask_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype"
     codes = binarize_codes or {"astype": 0, "v3": 1, "gt0.5": 2}
     if binarize not in codes:
         raise ValueError("binarize must be one of %s" % sorted(codes))
-    if int(erode_iters) != erode_iters or erode_iters < 0:
-        raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
+    _check_erode_iters(erode_iters)
     dev = _is_torch(masks)
     if not dev:
         masks = np.asarray(masks)
@@ -245,56 +254,10 @@ def wide_mask_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype"
                 raise ValueError("device rects must be a contiguous int32 tensor")
         else:
             rects = np.ascontiguousarray(np.asarray(rects).reshape(rshape), dtype=np.int32)
-    return MaskBatch(masks, M, is_f, dev, rects)
+    return MaskBatch(masks, M, is_f, dev, rects, gpu=masks if dev else None)
 
 
 LPF_MASKS_U8, LPF_MASKS_F32, LPF_MASKS_RLE = 0, 1, 2           # lpf_wide_input.f32 (include/lpf.h)
-
-
-def rle_frames(masks, who):
-    """Is this ``masks`` argument in run-length form -- one rle.RleMasks, or a list with one per frame?  The per-frame list of them, or
-    None for anything else; ValueError (``who``: the message's prefix) for a list that mixes RleMasks and arrays."""
-    from .rle import RleMasks
-    frames = [masks] if isinstance(masks, RleMasks) else list(masks) if isinstance(masks, (list, tuple)) else []
-    if not any(isinstance(m, RleMasks) for m in frames):
-        return None
-    if not all(isinstance(m, RleMasks) for m in frames):
-        raise ValueError("%s: the list mixes RleMasks and arrays: one form per call (.to_dense() or RleMasks.from_dense)" % who)
-    return frames
-
-
-def wide_rle_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", max_masks=LPF_MAX_MASKS_WIDE, who="run_wide",
-                   default_binarize="astype"):
-    """The run-length form of a pass's masks -- one rle.RleMasks, or a list with one per frame -- checked before anything reaches the
-    GPU, in the shape wide_mask_batch returns: ``((runs, run_off, RleMasksInput), M, "rle", False, None)``; None when ``masks`` are not
-    in that form.  Ragged M is padded with empty masks.  ValueError: a list that mixes RleMasks and arrays, another size than H x W,
-    ``rects`` (runs need none), a ``binarize`` other than the entry point's default (``default_binarize``), more than max_masks masks,
-    another frame count than F."""
-    frames = rle_frames(masks, who)
-    if frames is None:
-        return None
-    if rects is not None:
-        raise ValueError("%s: rects given with RleMasks (the runs say where the masks are)" % who)
-    if binarize != default_binarize:
-        raise ValueError("%s: binarize=%r with RleMasks (a pixel is a member or it is not)" % (who, binarize))
-    if int(erode_iters) != erode_iters or erode_iters < 0:
-        raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
-    runs, run_off, Fr, M = LpfContext.rle_batch(frames, H, W, max_masks, who)
-    if Fr != F:
-        raise ValueError("%s: RleMasks for %d frames, the batch has %d" % (who, Fr, F))
-    return MaskBatch((runs, run_off, RleMasksInput.of(runs, run_off, F, M, erode_iters)), M, "rle", False, None)
-
-
-def ids_frames(masks, who):
-    """Is this ``masks`` argument a set of instance-ID maps -- one idmap.IdMasks, or a list with one per frame?  The per-frame list of
-    them, or None for anything else; ValueError (``who``: the message's prefix) for a list that mixes IdMasks with another form."""
-    from .idmap import IdMasks
-    frames = [masks] if isinstance(masks, IdMasks) else list(masks) if isinstance(masks, (list, tuple)) else []
-    if not any(isinstance(m, IdMasks) for m in frames):
-        return None
-    if not all(isinstance(m, IdMasks) for m in frames):
-        raise ValueError("%s: the list mixes IdMasks with another form of masks: one form per call (.to_dense())" % who)
-    return frames
 
 
 def ids_batch(frames_masks, H, W, max_masks=LPF_MAX_MASKS, who="set_masks_ids"):
@@ -304,7 +267,7 @@ def ids_batch(frames_masks, H, W, max_masks=LPF_MAX_MASKS, who="set_masks_ids"):
     ...)``), or F = 1: ``maps`` is then the first frame's tensor.  ValueError -- before any native call, with ``who`` as the message's
     prefix -- for anything that is not an IdMasks, another size than H x W, more than max_masks masks, differing ID dtypes, host and
     GPU maps in one call, and GPU maps that are not contiguous or do not follow one another in memory."""
-    from .idmap import IdMasks, LPF_ID_NONE, check_sel
+    from .idmap import LPF_ID_NONE, check_sel
     frames = [frames_masks] if isinstance(frames_masks, IdMasks) else list(frames_masks)
     for f, r in enumerate(frames):
         if not isinstance(r, IdMasks):
@@ -351,24 +314,55 @@ def _ids_input(maps, sel, F, M, id_bytes, on_device, erode_iters):
     return IdMasksInput(ptr, sel.ctypes.data if sel.size else None, F, M, id_bytes, int(erode_iters), 1 if on_device else 0, 0)
 
 
-def wide_ids_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", max_masks=LPF_MAX_MASKS_WIDE, who="run_wide"):
-    """The instance-ID form of a pass's masks -- one idmap.IdMasks, or a list with one per frame -- checked before anything reaches the
-    GPU, in the shape wide_mask_batch returns: ``((maps, sel, IdMasksInput), M, "ids", on_device, None)``; None when ``masks`` are not in
-    that form.  Ragged M is padded with LPF_ID_NONE.  ValueError: what ids_batch refuses, ``rects`` (a map needs none), a ``binarize``
-    other than the default, another frame count than F."""
-    frames = ids_frames(masks, who)
-    if frames is None:
+# The compact forms of masks, one row each: the class a caller hands over (its name is the word the refusals use), the two texts the
+# forms' refusals differ by, ``batch(frames, H, W, max_masks, who)`` -- a list of them as the tables of one call, (two arrays, F, M,
+# ...) -- and ``struct(*that tuple, erode_iters)``, the ctypes struct over the tables.  An entry point names the forms it takes
+# (``forms=``); a form it does not take is not recognised there and goes the dense way, to that path's own refusal.
+MaskForm = collections.namedtuple("MaskForm", "name cls where mixes batch struct")
+MASK_FORMS = (
+    MaskForm("rle", RleMasks, "the runs say where the masks are",
+             "the list mixes RleMasks and arrays: one form per call (.to_dense() or RleMasks.from_dense)",
+             lambda *a: LpfContext.rle_batch(*a), RleMasksInput.of),
+    MaskForm("ids", IdMasks, "the map says where the masks are",
+             "the list mixes IdMasks with another form of masks: one form per call (.to_dense())", ids_batch, _ids_input))
+
+
+def compact_frames(masks, who, forms):
+    """Is this ``masks`` argument in one of the compact ``forms`` (names of MASK_FORMS, tried in that order) -- one instance of the
+    form's class, or a list with one per frame?  ``(the form's row, the per-frame list)``, or None for anything else; ValueError
+    (``who``: the message's prefix) for a list that mixes the form with anything else."""
+    frames = list(masks) if isinstance(masks, (list, tuple)) else [masks]
+    for form in (f for name in forms for f in MASK_FORMS if f.name == name):
+        if any(isinstance(m, form.cls) for m in frames):
+            if not all(isinstance(m, form.cls) for m in frames):
+                raise ValueError("%s: %s" % (who, form.mixes))
+            return form, frames
+    return None
+
+
+def compact_mask_batch(masks, F, H, W, rects=None, erode_iters=0, binarize="astype", max_masks=LPF_MAX_MASKS_WIDE, who="run_wide",
+                       default_binarize="astype", *, forms):
+    """A compact form of a pass's masks -- one rle.RleMasks or idmap.IdMasks, or a list with one per frame -- checked before anything
+    reaches the GPU: a MaskBatch of that form; None when ``masks`` are in none of ``forms``.  Ragged M is padded (empty masks,
+    LPF_ID_NONE).  ValueError: a list that mixes the form with anything else, ``rects`` (the form needs none), a ``binarize`` other than
+    the entry point's default (``default_binarize``), what the form's batch builder refuses (rle_batch, ids_batch: another size than
+    H x W, more than max_masks masks, ...), another frame count than F."""
+    found = compact_frames(masks, who, forms)
+    if found is None:
         return None
+    form, frames = found
+    noun = form.cls.__name__
     if rects is not None:
-        raise ValueError("%s: rects given with IdMasks (the map says where the masks are)" % who)
-    if binarize != "astype":
-        raise ValueError("%s: binarize=%r with IdMasks (a pixel is a member or it is not)" % (who, binarize))
-    if int(erode_iters) != erode_iters or erode_iters < 0:
-        raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
-    maps, sel, Fr, M, id_bytes, dev = ids_batch(frames, H, W, max_masks, who)
-    if Fr != F:
-        raise ValueError("%s: IdMasks for %d frames, the batch has %d" % (who, Fr, F))
-    return MaskBatch((maps, sel, _ids_input(maps, sel, F, M, id_bytes, dev, erode_iters)), M, "ids", dev, None)
+        raise ValueError("%s: rects given with %s (%s)" % (who, noun, form.where))
+    if binarize != default_binarize:
+        raise ValueError("%s: binarize=%r with %s (a pixel is a member or it is not)" % (who, binarize, noun))
+    _check_erode_iters(erode_iters)
+    tables = form.batch(frames, H, W, max_masks, who)
+    if tables[2] != F:
+        raise ValueError("%s: %s for %d frames, the batch has %d" % (who, noun, tables[2], F))
+    struct = form.struct(*tables, erode_iters)
+    gpu = tables[0][0] if getattr(struct, "on_device", 0) else None      # (GPU maps: the frames' tensors; runs are host memory)
+    return MaskBatch(None, tables[3], False, gpu is not None, None, form.name, struct, tables[:2], gpu)
 
 
 class FrameJob(ctypes.Structure):
@@ -1041,7 +1035,7 @@ class LpfContext:
         with fewer masks than the largest are padded with empty masks.  ValueError -- before any native call, with ``who`` as the
         message's prefix -- for anything that is not an RleMasks, a size other than H x W, more than max_masks masks, and runs of another
         dtype or shape or out of bounds (they are checked again here: the fields of an RleMasks can be assigned)."""
-        from .rle import RleMasks, check_runs
+        from .rle import check_runs
         frames = [frames_masks] if isinstance(frames_masks, RleMasks) else list(frames_masks)
         for f, r in enumerate(frames):
             if not isinstance(r, RleMasks):
@@ -1071,7 +1065,7 @@ class LpfContext:
         ``set_masks(dense uint8 host masks, erode_iters)`` with the same members.  Ragged M is padded with empty masks; the masks must
         have the camera's size; at most LPF_MAX_MASKS per frame (pipeline.run_frames groups more)."""
         runs, run_off, F, M = self.rle_batch(frames_masks, self.H, self.W)
-        if int(erode_iters) < 0:
+        if int(erode_iters) < 0:                            # (not _check_erode_iters: this call has always taken 1.5 as 1, and words it so)
             raise ValueError("erode_iters must be >= 0, got %r" % (erode_iters,))
         inp = RleMasksInput.of(runs, run_off, F, M, erode_iters)
         self._check(self._lib.lpf_set_masks_rle(self._h, ctypes.byref(inp)))
@@ -1084,10 +1078,10 @@ class LpfContext:
         maps must have the camera's size and one dtype; host maps are stacked into one [F,H,W] array, GPU maps must be the frames of one
         contiguous [F,H,W] tensor (or F = 1) and are read where they are; at most LPF_MAX_MASKS per frame (pipeline.run_frames groups
         more)."""
-        if ids_frames(frames_masks, "set_masks_ids") is None and not (isinstance(frames_masks, (list, tuple)) and not len(frames_masks)):
+        if compact_frames(frames_masks, "set_masks_ids", ("ids",)) is None and \
+                not (isinstance(frames_masks, (list, tuple)) and not len(frames_masks)):
             raise ValueError("set_masks_ids: masks must be an IdMasks or a list of them, got %s" % type(frames_masks).__name__)
-        if int(erode_iters) != erode_iters or erode_iters < 0:
-            raise ValueError("erode_iters must be a non-negative integer, got %r" % (erode_iters,))
+        _check_erode_iters(erode_iters)
         maps, sel, F, M, id_bytes, dev = ids_batch(frames_masks, self.H, self.W)
         if dev:
             import torch
@@ -1436,9 +1430,10 @@ class LpfContext:
             if masks is None:
                 masks = np.zeros((F, 0, H, W), np.uint8)
             erode = cam.get("erode_iters", 0)
-            batch = wide_rle_batch(masks, F, H, W, cam.get("rects"), erode, binarize, max_masks, "%s: camera %d" % (who, k)) or \
+            batch = compact_mask_batch(masks, F, H, W, cam.get("rects"), erode, binarize, max_masks, "%s: camera %d" % (who, k),
+                                       forms=("rle",)) or \
                 wide_mask_batch(masks, F, H, W, cam.get("rects"), erode, binarize, self.BINARIZE)
-            masks, M, rects = batch.masks, batch.M, batch.rects
+            M = batch.M
             if M > max_masks:
                 raise ValueError("camera %d has %d masks per frame: a multi-camera pass takes at most %d per camera (run_wide takes more)"
                                  % (k, M, max_masks))
@@ -1462,7 +1457,7 @@ class LpfContext:
                 ci.box_off = box_off.ctypes.data
                 ci.boxes_on_device, ci.oriented = 0, int(bool(cam.get("oriented", True)))
                 keep.append(cat)
-            keep += [masks, rects]
+            keep.append(batch)
             Ms.append(M)
             box_offs.append(box_off)
         return cin, Ms, box_offs, keep
@@ -1516,21 +1511,36 @@ class LpfContext:
         summ = {k: a[k] for k in ("n_valid", "n_labelled", "inst_count", "inst_off", "best_box", "best_cnt")}
         return lambda: finish(summ, a["inst_off"][:, M], a["inst_overflow"])
 
-    def _wide_input(self, inp, batch, binarize, erode_iters):
-        """Fills the lpf_wide_input ``inp`` from what wide_mask_batch returned (``batch``, which must stay alive until the call has
-        returned); masks on the GPU were produced on torch's stream, so the call is ordered after it."""
-        masks, M, is_f, mdev, rects = batch
-        if is_f == "rle":                                    # wide_rle_batch's: one lpf_rle_masks in host memory (no M = 0 shortcut: the struct says so itself)
-            inp.masks, inp.rects = ctypes.addressof(masks[2]), None
-            inp.M, inp.f32, inp.binarize, inp.erode_iters, inp.on_device = M, LPF_MASKS_RLE, 0, int(erode_iters), 0
-            return
-        if mdev:
+    def _wait_for_masks(self, batch):
+        """Masks and maps on the GPU were produced on torch's stream: the call that reads them is ordered after it"""
+        if batch.gpu is not None:
             import torch
-            self.wait_for_stream(torch.cuda.current_stream(masks.device).cuda_stream)
-        inp.masks = _ptr(masks) if M else None
-        inp.rects = _ptr(rects) if M else None
-        inp.M, inp.f32, inp.binarize, inp.erode_iters = M, int(is_f), self.BINARIZE[binarize], int(erode_iters)
-        inp.on_device = 1 if mdev else 0
+            self.wait_for_stream(torch.cuda.current_stream(batch.gpu.device).cuda_stream)
+
+    def _wide_input(self, inp, batch, binarize, erode_iters):
+        """Fills the lpf_wide_input ``inp`` from a MaskBatch (which must stay alive until the call has returned) and orders the call
+        after the stream that made GPU masks: dense masks, or the run-length form, which rides in this struct as LPF_MASKS_RLE -- its
+        ``masks`` is the lpf_rle_masks itself, in host memory (no M = 0 shortcut: the struct says so itself)."""
+        self._wait_for_masks(batch)
+        M = batch.M
+        if batch.form == "rle":
+            inp.masks, inp.f32, inp.binarize = ctypes.addressof(batch.struct), LPF_MASKS_RLE, 0
+        else:
+            inp.masks, inp.f32, inp.binarize = _ptr(batch.masks) if M else None, int(batch.is_float), self.BINARIZE[binarize]
+        inp.rects = _ptr(batch.rects) if M else None
+        inp.M, inp.erode_iters, inp.on_device = M, int(erode_iters), 1 if batch.on_device else 0
+
+    def _masks_call(self, batch, binarize, erode_iters, natives):
+        """The native call a pass makes for its masks.  natives: the functions the entry point has, by form -- "dense" takes a
+        lpf_wide_input, and a compact form without a function of its own rides in that struct; a compact form with one takes the struct
+        compact_mask_batch made.  Returns ``(function, input struct, what must stay alive until the call has returned)``, with the
+        wait for the stream that made GPU masks or maps done."""
+        if batch.form != "dense" and batch.form in natives:
+            self._wait_for_masks(batch)
+            return natives[batch.form], batch.struct, batch
+        inp = WideInput()
+        self._wide_input(inp, batch, binarize, erode_iters)
+        return natives["dense"], inp, batch
 
     def run_wide(self, frames, masks, erode_iters=0, binarize="astype", rects=None, v3_pipeline=False, want_uv=True, want_float=False,
                  want_lists=True, want_valid_uv=False, inst_cap=None, staged=None):
@@ -1552,20 +1562,13 @@ class LpfContext:
         F = len(frames)
         if F == 0:
             raise ValueError("no frames")
-        batch = wide_ids_batch(masks, F, self.H, self.W, rects, erode_iters, binarize) or \
-            wide_rle_batch(masks, F, self.H, self.W, rects, erode_iters, binarize) or \
+        batch = compact_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, forms=("ids", "rle")) or \
             wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
         M = batch.M
         off, pts_ptr, pts_dev, _keep = staged or self._stage_points(frames)      # (_keep: alive until the run returns)
         n = int(off[-1])
-        if batch.is_float == "ids":                          # instance-ID maps: the call of its own, the struct as wide_ids_batch made it
-            native, inp = self._lib.lpf_run_wide_ids, batch.masks[2]
-            if batch.on_device:
-                import torch
-                self.wait_for_stream(torch.cuda.current_stream(batch.masks[0][0].device).cuda_stream)
-        else:
-            native, inp = self._lib.lpf_run_wide, WideInput()
-            self._wide_input(inp, batch, binarize, erode_iters)
+        native, inp, _keep_masks = self._masks_call(batch, binarize, erode_iters,
+                                                    {"dense": self._lib.lpf_run_wide, "ids": self._lib.lpf_run_wide_ids})
         Btot = int(self.box_off[-1]) if self.box_off is not None else 0
         wants = dict(want_uv=want_uv, want_float=want_float, want_lists=want_lists, want_valid_uv=want_valid_uv)
 
@@ -1601,15 +1604,13 @@ class LpfContext:
             raise ValueError("no frames")
         if cap is not None and (isinstance(cap, bool) or int(cap) != cap or cap < 0):
             raise ValueError("cap must be a non-negative integer, got %r" % (cap,))
-        batch = wide_rle_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, who="depth_maps", default_binarize="gt0.5") or \
+        batch = compact_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, who="depth_maps", default_binarize="gt0.5",
+                                   forms=("rle",)) or \
             wide_mask_batch(masks, F, self.H, self.W, rects, erode_iters, binarize, self.BINARIZE)
         M = batch.M
         off, pts_ptr, pts_dev, _keep = self._stage_points(frames)      # (_keep: alive until the call returns)
-        if batch.is_float == "rle":                         # the lpf_rle_masks itself: the call of its own
-            native, inp = self._lib.lpf_depth_maps_rle, batch.masks[2]
-        else:
-            native, inp = self._lib.lpf_depth_maps, WideInput()
-            self._wide_input(inp, batch, binarize, erode_iters)
+        native, inp, _keep_masks = self._masks_call(batch, binarize, erode_iters,
+                                                    {"dense": self._lib.lpf_depth_maps, "rle": self._lib.lpf_depth_maps_rle})
         if out is not None:
             if cap is None or int(cap) < 1:
                 raise ValueError("depth_maps: out= needs a capacity of at least one entry")
@@ -1628,7 +1629,7 @@ class LpfContext:
                 setattr(o, k, _dev_ptr(out.get(k), dt))
             o.cap, o.on_device = int(cap), 1
             self._call_in_order(out["pix"].device, native, pts_ptr, off.ctypes.data, F, pts_dev, ctypes.byref(inp), ctypes.byref(o))
-            self._lent.append((_keep, batch))           # (staged points and masks: alive until the work has run)
+            self._lent.append((_keep, _keep_masks))     # (staged points and masks: alive until the work has run)
             return out
         if cap is None:                     # a quarter of the largest frame's points: frame 100's five cars are 8 k of its 109 k
             cap = 0 if M == 0 else max(1024, min(int(np.diff(off).max()) // 4, self.W * self.H))
@@ -2149,9 +2150,10 @@ class LpfContext:
         masks, up to LPF_MAX_MASKS_WIDE.  The masks stay host memory; device: where the outputs go -- the GPU of ``out``'s tensors or
         of GPU ``colors``, else None (NumPy).  ValueError: a list that mixes RleMasks and arrays, frames of differing sizes, more than
         256 masks, another frame count, colours of another shape or dtype."""
-        frames = rle_frames(masks, "first_match")
-        if frames is None:
+        found = compact_frames(masks, "first_match", ("rle",))
+        if found is None:
             return None
+        frames = found[1]
         if len(frames) != F:
             raise ValueError("first_match: RleMasks for %d frames, the batch has %d" % (len(frames), F))
         sizes = sorted({tuple(r.shape[1:]) for r in frames})

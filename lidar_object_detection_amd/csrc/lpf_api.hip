@@ -1556,6 +1556,31 @@ struct RleCall {
     int pack(lpf_ctx::Wide &D, size_t k, const uint32_t **planes, bool *host_in) { return wide_pack_runs(c, D, c->rle_slices[k].R, W, H, planes, host_in); }
 };
 
+// What lpf_set_masks_rle and lpf_set_masks_ids do once their own checks have passed, for F frames of M <= LPF_MAX_MASKS masks: the
+// state transitions of set_masks_impl with host masks -- drain what a pipelined context owes (not per scratch set), the label image of
+// the set the next run reads -- with the form's decode in place of copy + pack.  Always packed at the call.  build(S, label_bytes, &cur,
+// &host_in): the form's label image in S.label_a / S.label_b, *cur the buffer that holds it; *host_in: copies from the caller's memory
+// were queued, so the call waits before it returns (the caller's arrays may be reused).  A pending lpf_set_mask_rects hint is consumed
+// (neither runs nor a map need one) and unpacked masks are forgotten before the image is reserved.
+template <typename Build> int set_masks_compact(lpf_ctx *c, int F, int M, Build &&build)
+{
+    int rc;
+    if (c->pipe.owes() && (rc = sync_all(c))) return rc;
+    lpf_ctx::Masks &MK = c->masks;
+    lpf_ctx::Scratch &S = c->sc[c->pipe.set_now()];
+    MK.begin(c->pipe.set_now());
+    if (F == 0) return LPF_OK;
+    const int lb = (M <= 8) ? 1 : (M <= 16) ? 2 : 4;
+    c->rects_pending = nullptr;
+    MK.forget_unpacked();
+    void *cur = nullptr;
+    bool host_in = false;
+    if ((rc = build(S, lb, &cur, &host_in))) return rc;
+    if (host_in) LPF_HIP(c, host_wait(c));
+    MK.packed(F, M, cur, lb);
+    return LPF_OK;
+}
+
 // ---- setup the run paths share ---------------------------------------------------------------------------------------------------
 
 // frame_off[0..F] (not NULL, F > 0: the caller's checks) starts at 0 and has frames of 0 .. 0x7fffffff - slack points; pts is given if
@@ -2227,8 +2252,7 @@ int lpf_set_masks_f32(lpf_ctx *c, const float *masks, int F, int M, int binarize
 }
 
 // Run-length masks (include/lpf.h): checked in full on the host, which also emits the work units of the decode (lpf_rle.hip.h); then
-// the state transitions of set_masks_impl with host masks -- drain what a pipelined context owes, the label image of the set the next
-// run reads -- with zero + decode (+ erosion on the packed image) in place of copy + pack.  Always packed at the call.
+// set_masks_compact with zero + decode (+ erosion on the packed image).
 int lpf_set_masks_rle(lpf_ctx *c, const lpf_rle_masks *in)
 {
     if (!c) return LPF_ERR_ARG;
@@ -2239,30 +2263,16 @@ int lpf_set_masks_rle(lpf_ctx *c, const lpf_rle_masks *in)
                                       "lpf_graph_begin ... lpf_graph_end)");
     if (!in) return fail(c, LPF_ERR_ARG, "lpf_set_masks_rle: in=NULL");
     if (in->M > LPF_MAX_MASKS) return too_many_masks(c, in->M);
-    const int F = in->F, M = in->M;
     RleCall R(c);
     int rc;
     if ((rc = R.walk("lpf_set_masks_rle", in, c->W, c->H))) return rc;
-    // from here on: set_masks_impl with host masks (not per scratch set: what a pipelined context owes is drained first)
-    if (c->pipe.owes() && (rc = sync_all(c))) return rc;
-    lpf_ctx::Masks &MK = c->masks;
-    lpf_ctx::Scratch &S = c->sc[c->pipe.set_now()];
-    MK.begin(c->pipe.set_now());
-    if (F == 0) return LPF_OK;
-    const int lb = (M <= 8) ? 1 : (M <= 16) ? 2 : 4;
-    c->rects_pending = nullptr;                             // a pending lpf_set_mask_rects hint is consumed (runs need none)
-    MK.forget_unpacked();
-    void *cur = nullptr;
-    bool staged = false;
-    if ((rc = rle_label_image(c, S.label_a, S.label_b, c->rle_stage, R.A, c->W, c->H, lb, &cur, &staged))) return rc;
-    if (staged) LPF_HIP(c, host_wait(c));                   // the caller's arrays (and the unit table) may be reused
-    MK.packed(F, M, cur, lb);
-    return LPF_OK;
+    return set_masks_compact(c, in->F, in->M, [&](lpf_ctx::Scratch &S, int lb, void **cur, bool *host_in) {
+        return rle_label_image(c, S.label_a, S.label_b, c->rle_stage, R.A, c->W, c->H, lb, cur, host_in);
+    });
 }
 
-// Instance-ID maps (include/lpf.h): the struct is checked before anything is queued, then the state transitions of lpf_set_masks_rle
-// -- drain what a pipelined context owes, the label image of the set the next run reads -- with ONE decode launch that writes every
-// element (+ erosion on the packed image) in place of zero + decode.  Always packed at the call.
+// Instance-ID maps (include/lpf.h): the struct is checked before anything is queued, then set_masks_compact with ONE decode launch that
+// writes every element (+ erosion on the packed image); only a host map is waited for (sel was copied at the call).
 int lpf_set_masks_ids(lpf_ctx *c, const lpf_id_masks *in)
 {
     if (!c) return LPF_ERR_ARG;
@@ -2275,21 +2285,9 @@ int lpf_set_masks_ids(lpf_ctx *c, const lpf_id_masks *in)
     if (in->M > LPF_MAX_MASKS) return too_many_masks(c, in->M);
     int rc;
     if ((rc = check_ids(c, "lpf_set_masks_ids", in, (size_t)c->W * c->H))) return rc;
-    const int F = in->F, M = in->M;
-    if (c->pipe.owes() && (rc = sync_all(c))) return rc;
-    lpf_ctx::Masks &MK = c->masks;
-    lpf_ctx::Scratch &S = c->sc[c->pipe.set_now()];
-    MK.begin(c->pipe.set_now());
-    if (F == 0) return LPF_OK;
-    const int lb = (M <= 8) ? 1 : (M <= 16) ? 2 : 4;
-    c->rects_pending = nullptr;                             // a pending lpf_set_mask_rects hint is consumed (a map needs none)
-    MK.forget_unpacked();
-    void *cur = nullptr;
-    bool host_in = false;
-    if ((rc = ids_label_image(c, S.label_a, S.label_b, c->ids_stage, in, c->W, c->H, lb, &cur, &host_in))) return rc;
-    if (host_in) LPF_HIP(c, host_wait(c));                  // the caller's host map may be reused (sel was copied at the call)
-    MK.packed(F, M, cur, lb);
-    return LPF_OK;
+    return set_masks_compact(c, in->F, in->M, [&](lpf_ctx::Scratch &S, int lb, void **cur, bool *host_in) {
+        return ids_label_image(c, S.label_a, S.label_b, c->ids_stage, in, c->W, c->H, lb, cur, host_in);
+    });
 }
 
 int lpf_set_label_image(lpf_ctx *c, const uint32_t *label, int F, int M, int on_device)
@@ -2949,21 +2947,33 @@ static int wide_pack_dense(lpf_ctx *c, lpf_ctx::Wide &D, const void *d_masks, co
     return LPF_OK;
 }
 
-// ... from a pass's lpf_wide_input (host masks are staged into D and *host_in is set; device masks are lent), or, where it is in the
-// run-length form, from R, its walked masks (check_wide_rle), or from `ids`, the checked instance-ID maps of lpf_run_wide_ids (NULL for
-// everyone else; `in` then carries M and erode_iters only).  *planes = NULL without masks
-static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_input *in, int F, int Wimg, int Himg, const lpf_ctx::RleIn &R,
-                     const lpf_id_masks *ids, const uint32_t **planes, bool *host_in)
+// Where a wide pass's label planes come from: M masks per frame, eroded erode_iters times, in exactly one of three forms, each checked
+// by its pass before anything is enqueued
+struct PlaneSource {
+    int M, erode_iters;
+    const lpf_wide_input *dense = nullptr;              // dense masks (check_wide_input)
+    const lpf_ctx::RleIn *runs = nullptr;               // walked run-length masks (check_wide_rle)
+    const lpf_id_masks *ids = nullptr;                  // instance-ID maps (check_ids)
+    // a pass's lpf_wide_input and what check_wide_rle made of it: R.in is NULL when its masks are dense
+    PlaneSource(const lpf_wide_input &in, const lpf_ctx::RleIn &R)
+        : M(in.M), erode_iters(in.erode_iters), dense(R.in ? nullptr : &in), runs(R.in ? &R : nullptr) {}
+    explicit PlaneSource(const lpf_id_masks &in) : M(in.M), erode_iters(in.erode_iters), ids(&in) {}
+};
+
+// ... from a pass's PlaneSource: dense host masks are staged into D and *host_in is set, device masks are lent; runs and ID maps are
+// decoded (wide_pack_runs, wide_pack_ids).  *planes = NULL without masks
+static int wide_pack(lpf_ctx *c, lpf_ctx::Wide &D, const PlaneSource &src, int F, int Wimg, int Himg, const uint32_t **planes, bool *host_in)
 {
     *planes = nullptr;
-    if (in->M == 0) return LPF_OK;
-    if (ids) return wide_pack_ids(c, D, ids, Wimg, Himg, planes, host_in);
-    if (R.in) return wide_pack_runs(c, D, R, Wimg, Himg, planes, host_in);
+    if (src.M == 0) return LPF_OK;
+    if (src.ids) return wide_pack_ids(c, D, src.ids, Wimg, Himg, planes, host_in);
+    if (src.runs) return wide_pack_runs(c, D, *src.runs, Wimg, Himg, planes, host_in);
     int rc;
+    const lpf_wide_input &in = *src.dense;
     const void *d_masks = nullptr;
     const int4 *rects = nullptr;
-    if ((rc = stage_masks(c, *in, F, (size_t)Wimg * Himg, D.masks, D.rects, &d_masks, &rects, host_in))) return rc;
-    return wide_pack_dense(c, D, d_masks, rects, in->f32 != 0, in->binarize, in->M, in->erode_iters, F, Wimg, Himg, planes);
+    if ((rc = stage_masks(c, in, F, (size_t)Wimg * Himg, D.masks, D.rects, &d_masks, &rects, host_in))) return rc;
+    return wide_pack_dense(c, D, d_masks, rects, in.f32 != 0, in.binarize, src.M, src.erode_iters, F, Wimg, Himg, planes);
 }
 
 // outputs and scratch of a wide run of n points, F frames, W.M masks, Btot boxes, W.nchunk chunks, on buffers D -> W's pointers: the
@@ -3006,23 +3016,16 @@ static int wide_bind(lpf_ctx *c, lpf_ctx::Wide &D, const lpf_wide_outputs *out, 
     return LPF_OK;
 }
 
-// lpf_run_wide's whole run.  direct: the projecting stage reads the lent uint8 masks inside their rectangles (lpf_wide_direct_project)
-// instead of packing them into planes for lpf_wide_project -- lpf_run_frame_wide's form for sparse frames; the caller has checked that
-// in->masks / in->rects are device memory, uint8, no erosion, M > 0, rects 16-byte aligned.  Everything else is shared: the checks, the
-// box job, the frame table, wide_bind and the launches after projection.  ids: the source of the planes of lpf_run_wide_ids -- its
-// instance-ID maps, checked by the caller (in: their M and erode_iters, masks = the maps); NULL: the planes come from `in`.
-static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
-                         const lpf_wide_outputs *out, bool direct, const lpf_id_masks *ids = nullptr)
+// lpf_run_wide's run, behind the checks of the call's arguments, frames and masks (src: where the label planes come from).  who: the
+// messages' prefix.  direct: the projecting stage reads the lent uint8 masks inside their rectangles (lpf_wide_direct_project) instead
+// of packing them into planes for lpf_wide_project -- lpf_run_frame_wide's form for sparse frames; the caller has checked that
+// src.dense's masks / rects are device memory, uint8, no erosion, M > 0, rects 16-byte aligned.  Everything else is shared: the box job,
+// the frame table, wide_bind and the launches after projection.
+static int run_wide_impl(lpf_ctx *c, const char *who, const float *pts, const int64_t *frame_off, int F, int pts_on_device,
+                         const PlaneSource &src, const lpf_wide_outputs *out, bool direct)
 {
     int rc;
-    const char *who = ids ? "run_wide_ids" : "run_wide";
-    if ((rc = enter(c, ids ? "lpf_run_wide_ids" : "lpf_run_wide", true))) return rc;
-    if (!in || !out || !frame_off || F <= 0) return fail(c, LPF_ERR_ARG, "%s: in=%p out=%p frame_off=%p F=%d", who, (const void *)in, (const void *)out, (const void *)frame_off, F);
-    const int M = in->M;
-    if ((rc = check_wide_input(c, who, -1, *in, LPF_MAX_MASKS_WIDE, "lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE", "", true))) return rc;
-    if ((rc = check_frames(c, who, pts, frame_off, F, LPF_WIDE_CHUNK))) return rc;
-    lpf_ctx::RleIn &R = c->rle_in[0];                      // run-length masks: checked in full here, before anything is enqueued
-    if ((rc = check_wide_rle(c, who, -1, *in, F, (long long)c->W * c->H, R))) return rc;
+    const int M = src.M;
     const int64_t Ntot = frame_off[F];
     if (out->inst_idx && out->inst_cap <= 0) return fail(c, LPF_ERR_ARG, "%s: inst_idx given with inst_cap=%lld", who, (long long)out->inst_cap);
     lpf_ctx::BoxSet &BX = c->boxes.in_force();
@@ -3052,7 +3055,7 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     bool pts_in = false, masks_in = false;
     if ((rc = host_points(c, D.pts, pts, pts_on_device != 0, 0, n, n, &W.pts, &pts_in))) return rc;
     if (direct) W.planes = nullptr;
-    else if ((rc = wide_pack(c, D, in, F, c->W, c->H, R, ids, &W.planes, &masks_in))) return rc;
+    else if ((rc = wide_pack(c, D, src, F, c->W, c->H, &W.planes, &masks_in))) return rc;
 
     // ---- buffers: the caller's device pointers, or staging for host callers ---------------------------------------------------
     const size_t nMB = (size_t)M * Btot;
@@ -3062,8 +3065,8 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     // ---- the launch set ------------------------------------------------------------------------------------------------------
     if (nchunk > 0) {
         if (direct)
-            hipLaunchKernelGGL(lpf_wide_direct_project, dim3((unsigned)nchunk), dim3(LPF_BLOCK), 0, c->stream, W, (const uint8_t *)in->masks,
-                               (const int4 *)in->rects);
+            hipLaunchKernelGGL(lpf_wide_direct_project, dim3((unsigned)nchunk), dim3(LPF_BLOCK), 0, c->stream, W, (const uint8_t *)src.dense->masks,
+                               (const int4 *)src.dense->rects);
         else
             hipLaunchKernelGGL(lpf_wide_project, dim3((unsigned)nchunk), dim3(LPF_BLOCK), 0, c->stream, W);
         LPF_HIP(c, hipGetLastError());
@@ -3092,10 +3095,26 @@ static int run_wide_impl(lpf_ctx *c, const float *pts, const int64_t *frame_off,
     return LPF_OK;
 }
 
+// A wide run on a lpf_wide_input (lpf_run_wide, lpf_run_frame_wide): the checks -- run-length masks are checked in full here, into
+// rle_in[0], before anything is enqueued -- then run_wide_impl
+static int run_wide_input(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
+                          const lpf_wide_outputs *out, bool direct)
+{
+    int rc;
+    const char *who = "run_wide";
+    if ((rc = enter(c, "lpf_run_wide", true))) return rc;
+    if (!in || !out || !frame_off || F <= 0) return fail(c, LPF_ERR_ARG, "%s: in=%p out=%p frame_off=%p F=%d", who, (const void *)in, (const void *)out, (const void *)frame_off, F);
+    if ((rc = check_wide_input(c, who, -1, *in, LPF_MAX_MASKS_WIDE, "lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE", "", true))) return rc;
+    if ((rc = check_frames(c, who, pts, frame_off, F, LPF_WIDE_CHUNK))) return rc;
+    lpf_ctx::RleIn &R = c->rle_in[0];
+    if ((rc = check_wide_rle(c, who, -1, *in, F, (long long)c->W * c->H, R))) return rc;
+    return run_wide_impl(c, who, pts, frame_off, F, pts_on_device, PlaneSource(*in, R), out, direct);
+}
+
 int lpf_run_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, int F, int pts_on_device, const lpf_wide_input *in,
                  const lpf_wide_outputs *out)
 {
-    return run_wide_impl(c, pts, frame_off, F, pts_on_device, in, out, false);
+    return run_wide_input(c, pts, frame_off, F, pts_on_device, in, out, false);
 }
 
 // lpf_run_wide with its planes built from instance-ID maps: the struct is checked here, before run_wide_impl launches what a pipelined
@@ -3104,16 +3123,16 @@ int lpf_run_wide_ids(lpf_ctx *c, const float *pts, const int64_t *frame_off, int
                      const lpf_wide_outputs *out)
 {
     int rc;
+    const char *who = "run_wide_ids";
     if ((rc = enter(c, "lpf_run_wide_ids", true))) return rc;
     if (!in) return fail(c, LPF_ERR_ARG, "run_wide_ids: in=NULL");
     if (in->M > LPF_MAX_MASKS_WIDE)
         return fail(c, LPF_ERR_ARG, "run_wide_ids: M=%d masks per frame, lpf_run_wide_ids takes 0 .. LPF_MAX_MASKS_WIDE = %d", in->M, LPF_MAX_MASKS_WIDE);
-    if ((rc = check_ids(c, "run_wide_ids", in, (size_t)c->W * c->H))) return rc;
+    if ((rc = check_ids(c, who, in, (size_t)c->W * c->H))) return rc;
     if (in->F != F) return fail(c, LPF_ERR_ARG, "run_wide_ids: the ID maps say F=%d, the call has F=%d", in->F, F);
-    lpf_wide_input w;
-    memset(&w, 0, sizeof w);
-    w.masks = in->ids; w.M = in->M; w.f32 = LPF_MASKS_U8; w.erode_iters = in->erode_iters; w.on_device = in->on_device;
-    return run_wide_impl(c, pts, frame_off, F, pts_on_device, &w, out, false, in);
+    if (!out || !frame_off || F <= 0) return fail(c, LPF_ERR_ARG, "%s: in=%p out=%p frame_off=%p F=%d", who, (const void *)in, (const void *)out, (const void *)frame_off, F);
+    if ((rc = check_frames(c, who, pts, frame_off, F, LPF_WIDE_CHUNK))) return rc;
+    return run_wide_impl(c, who, pts, frame_off, F, pts_on_device, PlaneSource(*in), out, false);
 }
 
 // ---- lpf_depth_maps (include/lpf.h): per-car depth maps as sparse lists, kernels in lpf_depth_maps.hip.h ----------------------
@@ -4290,7 +4309,7 @@ int lpf_run_cams_wide(lpf_ctx *c, const float *pts, const int64_t *frame_off, in
         const int M = I.masks.M, LW = (M + 31) / 32;
         wide_params(W, input_cam(I), F, M, nchunk, nbw[k], BX, out[k].inst_cap, (const LpfWideFrame *)c->camsw.tab.p + (size_t)k * F);
         W.pts = d_pts;
-        if ((rc = wide_pack(c, D, &I.masks, F, I.W, I.H, c->rle_in[k], nullptr, &W.planes, &host_in))) return rc;
+        if ((rc = wide_pack(c, D, PlaneSource(I.masks, c->rle_in[k]), F, I.W, I.H, &W.planes, &host_in))) return rc;
         if ((rc = wide_bind(c, D, &out[k], n, F, Btot[k], W, S[k]))) return rc;
         max_lists = std::max(max_lists, F * std::max(LW, 1));
         if (M > 0 && Btot[k] > 0) {
@@ -4391,7 +4410,7 @@ int lpf_run_frame_wide(lpf_ctx *c, const lpf_frame_job_wide *j)
     const int64_t off[2] = {0, j->n_points};
     const bool direct = j->mask_rects && ((uintptr_t)j->mask_rects & 15) == 0 && j->n_masks > 0 && j->n_masks <= LPF_FW_DIRECT_MAX &&
                         2 * j->n_points <= (int64_t)c->W * c->H;
-    return run_wide_impl(c, j->pts, off, 1, 1, &in, &j->out, direct);
+    return run_wide_input(c, j->pts, off, 1, 1, &in, &j->out, direct);
 }
 
 }  // extern "C"

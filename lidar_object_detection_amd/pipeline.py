@@ -1231,16 +1231,16 @@ def _mask_group(batch, rles, g):
 
 
 def _first_match_rle_masks(frames):
-    """Each frame's RleMasks when the batch's masks come in run-length form, None when no frame's do: _rle_frame_masks' rules, with the
-    size the frames' RleMasks share in the camera's place -- first_match reads masks at their own size.  ValueError: RleMasks of
-    differing sizes, and what _rle_frame_masks refuses."""
+    """Each frame's RleMasks when the batch's masks come in run-length form, None when no frame's do: _compact_frame_masks' rules, with
+    the size the frames' RleMasks share in the camera's place -- first_match reads masks at their own size.  ValueError: RleMasks of
+    differing sizes, and what _compact_frame_masks refuses."""
     sizes = sorted({tuple(f.masks.shape[1:]) for f in frames if isinstance(f.masks, RleMasks)})
     if not sizes:
         return None
     if len(sizes) > 1:
         raise ValueError("first_match_frames: the frames' RleMasks have differing sizes (H, W) = %s: one size per batch (runs are not "
                          "resized: decode with .to_dense())" % (sizes,))
-    return _rle_frame_masks(frames, None, size=sizes[0])
+    return _compact_frame_masks(frames, None, ("rle",), size=sizes[0])[1]
 
 
 def first_match_frames(frames, TrVeloToRect, camera, depth_max=30.0, mask_colors=None, device=0, ctx=None):
@@ -1628,75 +1628,70 @@ def _mask_batch(stacks, M, H, W, ctx):
     return batch
 
 
-def _rle_frame_masks(frames, camera, size=None):
-    """Each frame's RleMasks when the batch's masks come in run-length form (a frame without masks -- None, an empty list -- gets an
-    empty one), None when no frame's do.  ValueError, before anything reaches the library: a batch that mixes RleMasks and dense
-    masks, and RleMasks of another size than the camera's (runs are not resized) -- or than ``size`` = (H, W), for a call that reads
-    masks at a size of their own."""
-    is_rle = [isinstance(f.masks, RleMasks) for f in frames]
-    if not any(is_rle):
-        return None
-    H, W = size or (camera.height, camera.width)
-    out = []
-    for f, r in zip(frames, is_rle):
-        if r:
-            if tuple(f.masks.shape[1:]) != (H, W):
-                raise ValueError("frame %s: RleMasks of %d x %d, the camera is %d x %d (runs are not resized: decode with .to_dense())"
-                                 % (f.frame, f.masks.shape[2], f.masks.shape[1], W, H))
-            out.append(f.masks)
-        elif f.masks is None or len(f.masks) == 0:
-            out.append(RleMasks(np.zeros((0, 2), np.int32), np.zeros(1, np.int64), (0, H, W)))
-        else:
-            raise ValueError("frame %s: dense masks in a batch of RleMasks frames: one form per batch (.to_dense() or RleMasks.from_dense)"
-                             % (f.frame,))
-    return out
+# What run_frames' collector needs of a compact form of masks beyond its class (_native.MASK_FORMS): the frame a batch gives a frame
+# without masks, and its two refusals
+def _empty_rle(first, H, W, frame):
+    return RleMasks(np.zeros((0, 2), np.int32), np.zeros(1, np.int64), (0, H, W))
 
 
-def _ids_frame_masks(frames, camera):
-    """Each frame's IdMasks when the batch's masks come as instance-ID maps, None when no frame's do.  A frame without masks -- None, an
-    empty list -- gets an empty one over a zero host map of the batch's ID dtype.  ValueError, before anything reaches the library: a
-    batch that mixes IdMasks with another form, a map of another size than the camera's (maps are not resized), and a frame without
-    masks among GPU maps (the maps of a GPU batch are the frames of one tensor: give that frame ``IdMasks(t[f], [])``)."""
-    is_ids = [isinstance(f.masks, IdMasks) for f in frames]
-    if not any(is_ids):
-        return None
-    H, W = camera.height, camera.width
-    first = next(f.masks for f, r in zip(frames, is_ids) if r)
-    out = []
-    for f, r in zip(frames, is_ids):
-        if r:
-            if tuple(f.masks.shape[1:]) != (H, W):
-                raise ValueError("frame %s: an ID map of %d x %d, the camera is %d x %d (maps are not resized: use .to_dense())"
-                                 % (f.frame, f.masks.shape[2], f.masks.shape[1], W, H))
-            out.append(f.masks)
-        elif f.masks is None or len(f.masks) == 0:
-            if first.on_device:
-                raise ValueError("frame %s: no masks in a batch of GPU ID maps: give it IdMasks(t[f], []) over its frame of the batch's "
-                                 "tensor" % (f.frame,))
-            out.append(IdMasks(np.zeros((H, W), first.id_dtype), []))
-        else:
-            raise ValueError("frame %s: another form of masks in a batch of IdMasks frames: one form per batch (.to_dense())" % (f.frame,))
-    return out
+def _empty_ids(first, H, W, frame):
+    if first.on_device:                                     # (the maps of a GPU batch are the frames of one tensor)
+        raise ValueError("frame %s: no masks in a batch of GPU ID maps: give it IdMasks(t[f], []) over its frame of the batch's "
+                         "tensor" % (frame,))
+    return IdMasks(np.zeros((H, W), first.id_dtype), [])
 
 
-def _run_frames_rle(frames, rles, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, device, ctx, gather_scans,
-                    erosion_kernel_size):
-    """run_frames for frames whose masks are RleMasks (the camera and the erosion element set): up to 32 masks in one narrow pass behind
-    set_masks_rle, 33 to 256 in ONE wide pass (run_wide takes the runs as they are) -- the runs go to the GPU, not the masks -- more in
-    groups of 256.  On 0/1 masks V3's cast chain is the erosion alone, so v3_pipeline needs nothing beyond erode_iters.
-    Frames whose masks are IdMasks take the same route: set_masks_ids in set_masks_rle's place, run_wide on the maps, groups by slices
-    of the IdMasks (which share the map) -- the map goes to the GPU, or is read where it is."""
-    counts = [r.shape[0] for r in rles]
+_FRAME_FORMS = {
+    "rle": (RleMasks, _empty_rle, "frame %s: RleMasks of %d x %d, the camera is %d x %d (runs are not resized: decode with .to_dense())",
+            "frame %s: dense masks in a batch of RleMasks frames: one form per batch (.to_dense() or RleMasks.from_dense)"),
+    "ids": (IdMasks, _empty_ids, "frame %s: an ID map of %d x %d, the camera is %d x %d (maps are not resized: use .to_dense())",
+            "frame %s: another form of masks in a batch of IdMasks frames: one form per batch (.to_dense())")}
+
+
+def _compact_frame_masks(frames, camera, forms, size=None):
+    """``(form, each frame's masks in it)`` when the batch's masks come in one of the compact ``forms`` ("rle": RleMasks, "ids":
+    IdMasks; tried in that order), None when no frame's do.  A frame without masks -- None, an empty list -- gets an empty instance:
+    no runs, or no ``sel`` over a zero host map of the batch's ID dtype.  ValueError, before anything reaches the library: a batch
+    that mixes the form with another, masks of another size than the camera's (neither runs nor maps are resized) -- or than ``size`` =
+    (H, W), for a call that reads masks at a size of their own -- and a frame without masks among GPU ID maps."""
+    for form in forms:
+        cls, empty, wrong_size, mixed = _FRAME_FORMS[form]
+        first = next((f.masks for f in frames if isinstance(f.masks, cls)), None)
+        if first is None:
+            continue
+        H, W = size or (camera.height, camera.width)
+        out = []
+        for f in frames:
+            if isinstance(f.masks, cls):
+                if tuple(f.masks.shape[1:]) != (H, W):
+                    raise ValueError(wrong_size % (f.frame, f.masks.shape[2], f.masks.shape[1], W, H))
+                out.append(f.masks)
+            elif f.masks is None or len(f.masks) == 0:
+                out.append(empty(first, H, W, f.frame))
+            else:
+                raise ValueError(mixed % (f.frame,))
+        return form, out
+    return None
+
+
+def _run_frames_compact(frames, form, masks, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, device, ctx,
+                        gather_scans, erosion_kernel_size):
+    """run_frames for frames whose masks are in a compact form -- ``masks``: each frame's RleMasks ("rle") or IdMasks ("ids") -- with
+    the camera and the erosion element set: up to 32 masks in one narrow pass behind set_masks_rle / set_masks_ids, 33 to 256 in ONE
+    wide pass (run_wide takes either form as it is), more in groups of 256, by slices (those of an IdMasks share the map).  The runs
+    or the map go to the GPU -- a GPU map is read where it is -- not the masks.  On 0/1 masks V3's cast chain is the erosion alone, so
+    v3_pipeline needs nothing beyond erode_iters."""
+    counts = [m.shape[0] for m in masks]
     if max(counts) > LPF_MAX_MASKS_WIDE:
-        return _run_frames_in_mask_groups(frames, rles, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, False,
+        return _run_frames_in_mask_groups(frames, masks, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, False,
                                           device, ctx, group=LPF_MAX_MASKS_WIDE, erosion_kernel_size=erosion_kernel_size)
     corners, positions = zip(*(_corners_velo(f.bboxes_3d) for f in frames))
     pts = [f.points for f in frames]
     if max(counts) > LPF_MAX_MASKS:
         ctx.set_boxes(list(corners), oriented=use_oriented)
-        res = ctx.run_wide(pts, rles, erode_iters=erode_iters, want_uv=False, want_valid_uv=True)
+        res = ctx.run_wide(pts, masks, erode_iters=erode_iters, want_uv=False, want_valid_uv=True)
     else:
-        (ctx.set_masks_ids if isinstance(rles[0], IdMasks) else ctx.set_masks_rle)(rles, erode_iters=erode_iters)
+        getattr(ctx, "set_masks_" + form)(masks, erode_iters=erode_iters)       # set_masks_rle, set_masks_ids
         ctx.set_boxes(list(corners), oriented=use_oriented)
         res = ctx.run_batch(pts, want_uv=False, want_label=False, want_valid_uv=True, pinned=True)
     return [_frame_result(f, r, m, pos, min_points, gather_scans) for f, r, m, pos in zip(frames, res, counts, positions)]
@@ -1713,22 +1708,21 @@ def run_frames(frames, TrVeloToRect, camera, depth_max=50.0, min_points=10, use_
     ``gather_scans=False`` leaves them lazy like everyone else's -- reading them after the reader has moved on raises.
     ``erosion_kernel_size``: the reference's knob of that name (V3:55, cvs_erosion.py:77) -- ``erode_iters`` iterations erode with the
     k x k MORPH_ELLIPSE element (odd, 1 .. 15; 3 is the cross).  It is set on the context by every call, the default included.
-    Frames whose ``masks`` are ``rle.RleMasks`` (at the camera's size; every frame of the batch, a frame without masks aside) take
-    set_masks_rle, or with 33 to 256 masks ONE run_wide pass: the runs are decoded on the GPU, nothing dense crosses to the device; more
-    than 256 masks run in groups of 256.  Frames whose ``masks`` are ``idmap.IdMasks`` (instance-ID maps at the camera's size, one ID
-    dtype, all in host memory or all the frames of one GPU tensor) take the same route behind set_masks_ids / run_wide: the labels are
-    built from the map on the GPU, and no dense mask exists anywhere.  One form per batch."""
+    Frames whose ``masks`` are in a compact form -- ``rle.RleMasks``, or ``idmap.IdMasks`` (instance-ID maps of one ID dtype, all in
+    host memory or all the frames of one GPU tensor); at the camera's size; every frame of the batch, a frame without masks aside --
+    take set_masks_rle / set_masks_ids, or with 33 to 256 masks ONE run_wide pass: the labels are built from the runs or the map on
+    the GPU, nothing dense crosses to the device or exists anywhere; more than 256 masks run in groups of 256.  One form per batch."""
     erosion_kernel_size = _erosion_kernel_size(erosion_kernel_size)
     if not frames:
         return []
-    rles = _rle_frame_masks(frames, camera) or _ids_frame_masks(frames, camera)
+    compact = _compact_frame_masks(frames, camera, ("rle", "ids"))
     ctx = ctx or get_context(device)
     ctx.set_erosion_element(erosion_kernel_size)
     H, W = camera.height, camera.width
     ctx.set_camera(TrVeloToRect, camera.K, W, H, 0.0, float(depth_max))
-    if rles is not None:
-        return _run_frames_rle(frames, rles, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, device, ctx,
-                               gather_scans, erosion_kernel_size)
+    if compact is not None:
+        return _run_frames_compact(frames, *compact, TrVeloToRect, camera, depth_max, min_points, use_oriented, erode_iters, device, ctx,
+                                   gather_scans, erosion_kernel_size)
     stacks, erode_iters, v3_pipeline = _frame_mask_stacks(frames, camera, ctx, erode_iters, v3_pipeline, erosion_kernel_size)
     counts = [s.shape[0] for s in stacks]
     M = max(counts)
@@ -2070,10 +2064,11 @@ def run_frames_multicam(frames_per_cam, cams, depth_max=50.0, min_points=10, use
     results = [None] * C
     passes = []                                           # (camera, stacks, counts, M, erode_iters, v3_pipeline)
     for c, (T, camera) in enumerate(cams):
-        rles = _rle_frame_masks(frames_per_cam[c], camera)
-        if rles is not None:
+        compact = _compact_frame_masks(frames_per_cam[c], camera, ("rle",))
+        if compact is not None:
             # RleMasks frames: routed by M as dense masks are -- the pass takes the runs as they are, run_frames the wider camera (on
-            # 0/1 masks V3's cast chain is the erosion alone, _run_frames_rle)
+            # 0/1 masks V3's cast chain is the erosion alone, _run_frames_compact)
+            rles = compact[1]
             counts = [r.shape[0] for r in rles]
             if max(counts) > LPF_MAX_MASKS:
                 results[c] = run_frames(frames_per_cam[c], T, camera, depth_max, min_points, use_oriented, erode_iters, v3_pipeline, device,
@@ -2332,7 +2327,8 @@ def depth_maps_frames(frames, TrVeloToRect, camera, depth_max=30.0, device=0, ct
     ctx = ctx or get_context(device)
     ctx.set_camera(TrVeloToRect, camera.K, camera.width, camera.height, 0.0, float(depth_max))
     H, W = int(camera.height), int(camera.width)
-    rles = _rle_frame_masks(frames, camera)
+    compact = _compact_frame_masks(frames, camera, ("rle",))
+    rles = compact and compact[1]
     if rles is not None:                                    # run-length masks: the runs go down as they are (lpf_depth_maps_rle),
         batch, Ms, flt = None, [len(r) for r in rles], True       # under depth_maps' default rule
     else:

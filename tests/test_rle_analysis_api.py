@@ -154,9 +154,11 @@ def test_first_match_takes_masks_of_another_size_than_the_camera():
 def test_staged_runs_for_ragged_frames_match_the_reference():
     a, b, c = _rle(40, seed=1), _rle(0), _rle(256, seed=2)
     # depth maps: the camera's size, the default binarize, erosion in the struct
-    (runs, off, inp), M, form, dev, rects = _native.wide_rle_batch([a, b, c], 3, 48, 64, erode_iters=2, binarize="gt0.5", who="depth_maps",
-                                                                   default_binarize="gt0.5")
-    assert (M, form, dev, rects) == (256, "rle", False, None) and (inp.F, inp.M, inp.erode_iters, inp.reserved) == (3, 256, 2, 0)
+    batch = _native.compact_mask_batch([a, b, c], 3, 48, 64, erode_iters=2, binarize="gt0.5", who="depth_maps", default_binarize="gt0.5",
+                                       forms=("rle",))
+    (runs, off), inp, M = batch.tables, batch.struct, batch.M
+    assert (M, batch.form, batch.on_device, batch.rects) == (256, "rle", False, None)
+    assert (inp.F, inp.M, inp.erode_iters, inp.reserved) == (3, 256, 2, 0)
     _, _, _, _, (runs2, off2, inp2), _ = _native.LpfContext.first_match_rle_batch([a, b, c], None, 3)
     assert np.array_equal(runs, runs2) and np.array_equal(off, off2) and (inp2.F, inp2.M, inp2.erode_iters) == (3, 256, 0)
     assert runs.dtype == np.int32 and off.dtype == np.int64 and off.shape == (3 * 256 + 1,)

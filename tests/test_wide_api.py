@@ -77,7 +77,10 @@ def test_wide_entry_refuses_bad_shapes_before_the_gpu(masks, kw, frames):
 
 
 def test_wide_mask_batch_accepts_up_to_256():
-    m, M, is_f, dev, rects = _native.wide_mask_batch(np.zeros((256, 4, 5), bool), 1, 4, 5, rects=np.zeros((256, 4), np.int32))
+    b = _native.wide_mask_batch(np.zeros((256, 4, 5), bool), 1, 4, 5, rects=np.zeros((256, 4), np.int32))
+    m, M, is_f, dev, rects = b.masks, b.M, b.is_float, b.on_device, b.rects
     assert m.shape == (1, 256, 4, 5) and m.dtype == np.uint8 and M == 256 and not is_f and not dev and rects.shape == (1, 256, 4)
-    m, M, is_f, _, _ = _native.wide_mask_batch(np.zeros((2, 33, 4, 5), np.float64), 2, 4, 5, binarize="gt0.5")
-    assert m.dtype == np.float32 and M == 33 and is_f
+    assert b.form == "dense" and b.struct is None and b.tables is None and b.gpu is None
+    assert b._fields[:5] == ("masks", "M", "is_float", "on_device", "rects")
+    b = _native.wide_mask_batch(np.zeros((2, 33, 4, 5), np.float64), 2, 4, 5, binarize="gt0.5")
+    assert b.masks.dtype == np.float32 and b.M == 33 and b.is_float is True and b.form == "dense"

@@ -70,19 +70,21 @@ def test_rle_batch_with_the_wide_limit():
         _native.LpfContext.rle_batch(_rle(2, W=63), 48, 64)
 
 
-def test_wide_rle_batch_builds_the_struct():
+def test_compact_mask_batch_builds_the_struct():
     a, b = _rle(40, seed=3), _rle(33, seed=4)
-    (runs, off, inp), M, form, dev, rects = _native.wide_rle_batch([a, b], 2, 48, 64, erode_iters=2)
-    assert (M, form, dev, rects) == (40, "rle", False, None)
+    batch = _native.compact_mask_batch([a, b], 2, 48, 64, erode_iters=2, forms=("rle",))
+    (runs, off), inp, M = batch.tables, batch.struct, batch.M
+    assert (M, batch.form, batch.on_device, batch.rects) == (40, "rle", False, None)
+    assert batch.is_float is False and batch.masks is None and batch.gpu is None
     assert (inp.F, inp.M, inp.erode_iters, inp.reserved) == (2, 40, 2, 0)
     assert inp.runs == runs.ctypes.data and inp.run_off == off.ctypes.data
     ctx = _NoGpu()
     wi = WideInput()
-    ctx._wide_input(wi, ((runs, off, inp), M, form, dev, rects), "astype", 2)
+    ctx._wide_input(wi, batch, "astype", 2)
     assert (wi.masks, wi.rects, wi.M, wi.f32, wi.binarize, wi.erode_iters, wi.on_device) == (ctypes.addressof(inp), None, 40, 2, 0, 2, 0)
     # arrays are not the form: the dense path's business
-    assert _native.wide_rle_batch(np.zeros((40, 48, 64), np.uint8), 1, 48, 64) is None
-    assert _native.wide_rle_batch([np.zeros((40, 48, 64), np.uint8)], 1, 48, 64) is None
+    assert _native.compact_mask_batch(np.zeros((40, 48, 64), np.uint8), 1, 48, 64, forms=("rle",)) is None
+    assert _native.compact_mask_batch([np.zeros((40, 48, 64), np.uint8)], 1, 48, 64, forms=("rle",)) is None
 
 
 _PTS = [np.zeros((10, 4), np.float32)]
