@@ -8,34 +8,11 @@
 // results are not checked here -- the GPU tests do that; what is checked is that every call returns what it should and that the
 // sanitizer stays silent.  Which kernels are launched, with which grids, is recorded by fake_hip.cpp: count and hash are printed after
 // each section, and FAKE_HIP_TRACE=<file> keeps the lines -- two versions of the host code can be compared launch by launch.
-#include "../../include/lpf.h"
-
+#include "drive_common.h"
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-extern "C" long long fake_hip_launches(void);
-extern "C" unsigned long long fake_hip_trace_hash(void);
-extern "C" unsigned long long fake_hip_copy_hash(int restart);
-extern "C" void fake_hip_trace_flush(void);
-
-static int g_fail = 0;
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, ctx_err()); ++g_fail; } } while (0)
-static lpf_ctx *g_ctx = nullptr;
-static const char *ctx_err() { return lpf_last_error(g_ctx); }
-
-static const double T16[16] = {0, -1, 0, 0.1, 0, 0, -1, 0.2, 1, 0, 0, 0.3, 0, 0, 0, 1};
-static const double K9[9] = {552.5, 0, 682.0, 0, 552.5, 238.7, 0, 0, 1};
 static const int W = 128, H = 48;                             // (a small image; pipelined_streams also runs a 1408 x 376 one)
-
-struct Dev {                      // "device" buffers: heap blocks, so that the sanitizer knows their bounds
-    std::vector<void *> all;
-    template <typename T> T *get(size_t n) { void *p = calloc(n ? n : 1, sizeof(T)); all.push_back(p); return (T *)p; }
-    ~Dev() { for (void *p : all) free(p); }
-};
 
 static void fill_outputs(Dev &D, lpf_outputs &o, int64_t n, int F, int M, int Btot, int64_t cap, int on_device)
 {
@@ -230,8 +207,6 @@ static void fill_wide_outputs(Dev &D, lpf_wide_outputs &o, int64_t n, int F, int
     o.on_device = on_device;
 }
 
-static bool err_is(lpf_ctx *c, const char *text) { return strcmp(lpf_last_error(c), text) == 0; }
-
 // lpf_run_cams, lpf_run_cams_wide, lpf_run_wide, lpf_run_frame_wide and lpf_depth_maps: host and device outputs, one and several frames,
 // host and device masks (uint8 and float, with and without rectangles and erosion), and one of each refused argument
 static void wide_and_multicam_runs()
@@ -323,65 +298,65 @@ static void wide_and_multicam_runs()
     lpf_wide_outputs owd;
     fill_wide_outputs(D, owd, 1000, 1, 5, 1, 100, 1);
     const int64_t off1[2] = {0, 1000};
-    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 0, &on) == LPF_ERR_ARG && err_is(c, "run_cams: C=0 cameras, a pass takes 1 .. LPF_MAX_CAMS = 4"));
-    CHECK(lpf_run_cams(c, dpts, bad0, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: frame_off[0] must be 0"));
-    CHECK(lpf_run_cams_wide(c, dpts, neg, 2, 1, &cam, 1, &owd) == LPF_ERR_ARG && err_is(c, "run_cams_wide: frame 1 has -4 points"));
-    CHECK(lpf_run_cams(c, nullptr, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: pts is NULL"));
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 0, &on) == LPF_ERR_ARG && err_is("run_cams: C=0 cameras, a pass takes 1 .. LPF_MAX_CAMS = 4"));
+    CHECK(lpf_run_cams(c, dpts, bad0, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is("run_cams: frame_off[0] must be 0"));
+    CHECK(lpf_run_cams_wide(c, dpts, neg, 2, 1, &cam, 1, &owd) == LPF_ERR_ARG && err_is("run_cams_wide: frame 1 has -4 points"));
+    CHECK(lpf_run_cams(c, nullptr, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is("run_cams: pts is NULL"));
     cam.W = 0;
-    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: camera 0 is 0 x 48"));
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is("run_cams: camera 0 is 0 x 48"));
     cam.W = W; cam.masks.M = 33;
     CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG &&
-          err_is(c, "run_cams: camera 0 has M=33 masks per frame, a pass takes 0 .. LPF_MAX_MASKS = 32 per camera (more: lpf_run_wide for that camera)"));
+          err_is("run_cams: camera 0 has M=33 masks per frame, a pass takes 0 .. LPF_MAX_MASKS = 32 per camera (more: lpf_run_wide for that camera)"));
     cam.masks.M = 257;
     CHECK(lpf_run_cams_wide(c, dpts, off1, 1, 1, &cam, 1, &owd) == LPF_ERR_ARG &&
-          err_is(c, "run_cams_wide: camera 0 has M=257 masks per frame, a pass takes 0 .. LPF_MAX_MASKS_WIDE = 256 per camera"));
+          err_is("run_cams_wide: camera 0 has M=257 masks per frame, a pass takes 0 .. LPF_MAX_MASKS_WIDE = 256 per camera"));
     cam.masks.M = 2;
     CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG &&
-          err_is(c, "run_cams: camera 0: erode_iters=0 f32=0 binarize=0 masks=(nil)"));
+          err_is("run_cams: camera 0: erode_iters=0 f32=0 binarize=0 masks=(nil)"));
     cam.masks.masks = dmasks; cam.masks.f32 = 1; cam.masks.binarize = 3;
     CHECK(lpf_run_cams_wide(c, dpts, off1, 1, 1, &cam, 1, &owd) == LPF_ERR_ARG);
     cam.masks.f32 = 0; cam.masks.binarize = 0;
     cam.corners_velo = dcorners; cam.box_off = boffs[1] + 1;                    // (starts at 3)
-    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: camera 0: box_off must be given and start at 0"));
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is("run_cams: camera 0: box_off must be given and start at 0"));
     const int32_t desc[3] = {0, 5, 2};
     cam.box_off = desc;
     CHECK(lpf_run_cams(c, dpts, neg, 2, 1, &cam, 1, &on) == LPF_ERR_ARG);      // (the frames are checked first)
     const int64_t off2[3] = {0, 500, 1000};
-    CHECK(lpf_run_cams(c, dpts, off2, 2, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: camera 0: box_off not ascending at 1"));
+    CHECK(lpf_run_cams(c, dpts, off2, 2, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is("run_cams: camera 0: box_off not ascending at 1"));
     cam.box_off = boffs[0]; cam.boxes_on_device = 3;
-    CHECK(lpf_run_cams_wide(c, dpts, off1, 1, 1, &cam, 1, &owd) == LPF_ERR_ARG && err_is(c, "run_cams_wide: camera 0: boxes_on_device=3"));
+    CHECK(lpf_run_cams_wide(c, dpts, off1, 1, 1, &cam, 1, &owd) == LPF_ERR_ARG && err_is("run_cams_wide: camera 0: boxes_on_device=3"));
     cam.boxes_on_device = 0;
     on.inst_cap = 0;
-    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is(c, "run_cams: out[0].inst_idx given with inst_cap=0"));
+    CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG && err_is("run_cams: out[0].inst_idx given with inst_cap=0"));
     on.inst_cap = 100; on.valid_idx = nullptr;
     CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_ARG);
     owd.inst_cap = 0;
-    CHECK(lpf_run_cams_wide(c, dpts, off1, 1, 1, &cam, 1, &owd) == LPF_ERR_ARG && err_is(c, "run_cams_wide: out[0].inst_idx given with inst_cap=0"));
-    CHECK(lpf_run_wide(c, dpts, off1, 1, 1, &cam.masks, &owd) == LPF_ERR_ARG && err_is(c, "run_wide: inst_idx given with inst_cap=0"));
+    CHECK(lpf_run_cams_wide(c, dpts, off1, 1, 1, &cam, 1, &owd) == LPF_ERR_ARG && err_is("run_cams_wide: out[0].inst_idx given with inst_cap=0"));
+    CHECK(lpf_run_wide(c, dpts, off1, 1, 1, &cam.masks, &owd) == LPF_ERR_ARG && err_is("run_wide: inst_idx given with inst_cap=0"));
     owd.inst_cap = 100;
     CHECK(lpf_run_wide(c, dpts, off1, 1, 1, nullptr, &owd) == LPF_ERR_ARG);
     lpf_wide_input wi = cam.masks;
     wi.M = 300;
     CHECK(lpf_run_wide(c, dpts, off1, 1, 1, &wi, &owd) == LPF_ERR_ARG &&
-          err_is(c, "run_wide: M=300 masks per frame, lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE = 256"));
+          err_is("run_wide: M=300 masks per frame, lpf_run_wide takes 0 .. LPF_MAX_MASKS_WIDE = 256"));
     wi.M = 2; wi.erode_iters = -1;
     CHECK(lpf_run_wide(c, dpts, off1, 1, 1, &wi, &owd) == LPF_ERR_ARG && strncmp(lpf_last_error(c), "run_wide: erode_iters=-1 f32=0 binarize=0 masks=", 48) == 0);
     wi.erode_iters = 0;
-    CHECK(lpf_run_wide(c, dpts, bad0, 1, 1, &wi, &owd) == LPF_ERR_ARG && err_is(c, "run_wide: frame_off[0] must be 0"));
-    CHECK(lpf_run_wide(c, dpts, huge, 1, 1, &wi, &owd) == LPF_ERR_ARG && err_is(c, "run_wide: frame 0 has 2147483647 points"));
-    CHECK(lpf_run_wide(c, nullptr, off1, 1, 1, &wi, &owd) == LPF_ERR_ARG && err_is(c, "run_wide: pts is NULL"));
+    CHECK(lpf_run_wide(c, dpts, bad0, 1, 1, &wi, &owd) == LPF_ERR_ARG && err_is("run_wide: frame_off[0] must be 0"));
+    CHECK(lpf_run_wide(c, dpts, huge, 1, 1, &wi, &owd) == LPF_ERR_ARG && err_is("run_wide: frame 0 has 2147483647 points"));
+    CHECK(lpf_run_wide(c, nullptr, off1, 1, 1, &wi, &owd) == LPF_ERR_ARG && err_is("run_wide: pts is NULL"));
     lpf_depth_maps_outputs dm;
     memset(&dm, 0, sizeof dm);
     dm.car_off = D.get<int64_t>(8); dm.need = D.get<int64_t>(2); dm.on_device = 1;
     wi.M = 300;
     CHECK(lpf_depth_maps(c, dpts, off1, 1, 1, &wi, &dm) == LPF_ERR_ARG &&
-          err_is(c, "depth_maps: M=300 masks per frame, lpf_depth_maps takes 0 .. LPF_MAX_MASKS_WIDE = 256"));
+          err_is("depth_maps: M=300 masks per frame, lpf_depth_maps takes 0 .. LPF_MAX_MASKS_WIDE = 256"));
     wi.M = 2; wi.f32 = 1; wi.binarize = -1;
     CHECK(lpf_depth_maps(c, dpts, off1, 1, 1, &wi, &dm) == LPF_ERR_ARG && strncmp(lpf_last_error(c), "depth_maps: erode_iters=0 f32=1 binarize=-1", 43) == 0);
     wi.f32 = 0; wi.binarize = 0;
-    CHECK(lpf_depth_maps(c, dpts, bad0, 1, 1, &wi, &dm) == LPF_ERR_ARG && err_is(c, "depth_maps: frame_off[0] must be 0"));
-    CHECK(lpf_depth_maps(c, dpts, neg, 2, 1, &wi, &dm) == LPF_ERR_ARG && err_is(c, "depth_maps: frame 1 has -4 points"));
-    CHECK(lpf_depth_maps(c, nullptr, off1, 1, 1, &wi, &dm) == LPF_ERR_ARG && err_is(c, "depth_maps: pts is NULL"));
+    CHECK(lpf_depth_maps(c, dpts, bad0, 1, 1, &wi, &dm) == LPF_ERR_ARG && err_is("depth_maps: frame_off[0] must be 0"));
+    CHECK(lpf_depth_maps(c, dpts, neg, 2, 1, &wi, &dm) == LPF_ERR_ARG && err_is("depth_maps: frame 1 has -4 points"));
+    CHECK(lpf_depth_maps(c, nullptr, off1, 1, 1, &wi, &dm) == LPF_ERR_ARG && err_is("depth_maps: pts is NULL"));
     dm.car_off = nullptr;
     CHECK(lpf_depth_maps(c, dpts, off1, 1, 1, &wi, &dm) == LPF_ERR_ARG);
     lpf_frame_job_wide j;
@@ -396,7 +371,7 @@ static void wide_and_multicam_runs()
     // every entry point but lpf_run_batch refuses a graph capture
     CHECK(lpf_graph_begin(c) == LPF_OK);
     CHECK(lpf_run_cams(c, dpts, off1, 1, 1, &cam, 1, &on) == LPF_ERR_STATE &&
-          err_is(c, "lpf_run_cams cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end) [the graph capture in progress was abandoned]"));
+          err_is("lpf_run_cams cannot be captured into a graph (call it outside lpf_graph_begin ... lpf_graph_end) [the graph capture in progress was abandoned]"));
     lpf_destroy(c);
     g_ctx = nullptr;
 }
@@ -873,7 +848,7 @@ static void box_transitions()
     int64_t st[8];
     auto jobs = [&]() { CHECK(lpf_get_stats(g_ctx, st, 8, 1) == LPF_OK); return st[4] + st[5]; };     // box jobs since the last look
     auto in_force = [&](lpf_ctx *c) {                            // boxes for F frames are in force: a run of one frame is refused
-        return lpf_run_wide(c, pts, off1, 1, 1, &wi, &ow) == LPF_ERR_STATE && err_is(c, "boxes were set for 2 frames, run_wide has 1");
+        return lpf_run_wide(c, pts, off1, 1, 1, &wi, &ow) == LPF_ERR_STATE && err_is("boxes were set for 2 frames, run_wide has 1");
     };
     for (int mode = 0; mode <= 4; mode += 2) {
         lpf_ctx *c = nullptr;
@@ -989,7 +964,5 @@ int main(int argc, char **argv)
     section("pack_forms");
     box_transitions();
     section("box_transitions");
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive: %d failed checks, %lld fake launches, trace hash %016llx\n", g_fail, fake_hip_launches(), fake_hip_trace_hash());
-    return g_fail ? 1 : 0;
+    return drive_finish("drive", false);
 }

@@ -4,24 +4,8 @@
 // pairs are 164 MB of scratch each: one frame per range under the 256 MiB bound) and no allocation on a second call of a shape.  Kernel
 // launches do nothing here (fake_hip.cpp): the launches and copies are counted, the values are checked on the GPU by
 // tests/test_gpu_assign.py.
-#include "../../include/lpf.h"
-
+#include "drive_common.h"
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-extern "C" long long fake_hip_launches(void);
-extern "C" long long fake_hip_copies(void);
-extern "C" unsigned long long fake_hip_trace_hash(void);
-extern "C" unsigned long long fake_hip_copy_hash(int restart);
-extern "C" void fake_hip_trace_flush(void);
-
-static int g_fail = 0;
-static lpf_ctx *g_ctx = nullptr;
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive_assign.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, lpf_last_error(g_ctx)); ++g_fail; } } while (0)
-static bool err_starts(const char *text) { return strncmp(lpf_last_error(g_ctx), text, strlen(text)) == 0; }
 
 struct Batch {                    // F frames with the given row / detection and column / box counts
     std::vector<int32_t> det_off, box_off, front;
@@ -285,15 +269,9 @@ static void runs(lpf_ctx *c)
 
 int main()
 {
-    lpf_ctx *c = nullptr;
-    CHECK(lpf_create(&c, 0) == LPF_OK && c);
-    g_ctx = c;
+    lpf_ctx *c = drive_begin();
     refusals(c);
     runs(c);
     lpf_destroy(c);
-    g_ctx = nullptr;
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive_assign: %d failed checks, %lld fake launches, trace hash %016llx, %lld copies, copy hash %016llx\n", g_fail, fake_hip_launches(),
-            fake_hip_trace_hash(), fake_hip_copies(), fake_hip_copy_hash(0));
-    return g_fail ? 1 : 0;
+    return drive_finish("drive_assign", true);
 }

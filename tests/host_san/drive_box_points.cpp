@@ -4,23 +4,7 @@
 // combination, LW = 0 and NULL labels, F = 0, a frame with n_valid = 0, a frame without boxes, the checks of host lists, and what goes
 // back to a host caller (only a frame's first n_valid entries of first_box).  Kernel launches do nothing here (fake_hip.cpp): the
 // launches and copies are counted, the values are checked on the GPU by tests/test_gpu_box_points.py.
-#include "../../include/lpf.h"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-extern "C" long long fake_hip_launches(void);
-extern "C" long long fake_hip_copies(void);
-extern "C" unsigned long long fake_hip_trace_hash(void);
-extern "C" unsigned long long fake_hip_copy_hash(int restart);
-extern "C" void fake_hip_trace_flush(void);
-
-static int g_fail = 0;
-static lpf_ctx *g_ctx = nullptr;
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive_box_points.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, lpf_last_error(g_ctx)); ++g_fail; } } while (0)
-static bool err_starts(const char *text) { return strncmp(lpf_last_error(g_ctx), text, strlen(text)) == 0; }
+#include "drive_common.h"
 
 struct Batch {                    // F frames of N points, frame f with nv[f % size] valid points (every other point), B boxes per frame
     int F, N, LW;
@@ -40,13 +24,7 @@ struct Batch {                    // F frames of N points, frame f with nv[f % s
             for (int e = 0; e < n_valid.back(); ++e) valid_idx[(size_t)f * N + e] = 2 * e;
         }
         labels.assign((size_t)F * N * (LW > 0 ? LW : 1), 1u);
-        corners.assign((size_t)F * B * 24, 0.0);
-        for (size_t b = 0; b < (size_t)F * B; ++b)              // unit cubes in the dataset's corner order
-            for (int k = 0; k < 8; ++k) {
-                corners[b * 24 + k * 3 + 0] = (k == 1 || k == 2 || k == 5 || k == 6) ? 1.0 : 0.0;
-                corners[b * 24 + k * 3 + 1] = (k == 2 || k == 3 || k == 6 || k == 7) ? 1.0 : 0.0;
-                corners[b * 24 + k * 3 + 2] = k >= 4 ? 1.0 : 0.0;
-            }
+        unit_cubes(corners, (size_t)F * B);
     }
     lpf_box_points_input input(int on_device) const
     {
@@ -76,12 +54,6 @@ struct Out {
         return o;
     }
 };
-
-static void set_camera(lpf_ctx *c)
-{
-    const double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, K[9] = {500, 0, 320, 0, 500, 240, 0, 0, 1};
-    CHECK(lpf_set_camera(c, T, K, 640, 480, 0.0, 50.0) == LPF_OK);
-}
 
 static void refusals(lpf_ctx *c)
 {
@@ -220,16 +192,10 @@ static void runs(lpf_ctx *c)
 
 int main()
 {
-    lpf_ctx *c = nullptr;
-    CHECK(lpf_create(&c, 0) == LPF_OK && c);
-    g_ctx = c;
+    lpf_ctx *c = drive_begin();
     set_camera(c);
     refusals(c);
     runs(c);
     lpf_destroy(c);
-    g_ctx = nullptr;
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive_box_points: %d failed checks, %lld fake launches, trace hash %016llx, %lld copies, copy hash %016llx\n", g_fail,
-            fake_hip_launches(), fake_hip_trace_hash(), fake_hip_copies(), fake_hip_copy_hash(0));
-    return g_fail ? 1 : 0;
+    return drive_finish("drive_box_points", true);
 }

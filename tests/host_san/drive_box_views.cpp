@@ -3,26 +3,8 @@
 // boxes, F = 0, every selection of outputs, and the loop over frame ranges (three frames of 400 000 boxes with host corners in and
 // host corners_velo out are 154 MB each: one frame per range under the 256 MiB bound).  Kernel launches do nothing here
 // (fake_hip.cpp): the launches and copies are counted, the values are checked on the GPU by tests/test_gpu_box_views.py.
-#include "../../include/lpf.h"
-
+#include "drive_common.h"
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-extern "C" long long fake_hip_launches(void);
-extern "C" long long fake_hip_copies(void);
-extern "C" unsigned long long fake_hip_trace_hash(void);
-extern "C" unsigned long long fake_hip_copy_hash(int restart);
-extern "C" void fake_hip_trace_flush(void);
-
-static int g_fail = 0;
-static lpf_ctx *g_ctx = nullptr;
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive_box_views.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, lpf_last_error(g_ctx)); ++g_fail; } } while (0)
-static bool err_starts(const char *text) { return strncmp(lpf_last_error(g_ctx), text, strlen(text)) == 0; }
-
-static const double IDENT[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 
 struct Batch {                    // F frames with the given box counts
     std::vector<int32_t> box_off;
@@ -196,15 +178,9 @@ static void runs(lpf_ctx *c)
 
 int main()
 {
-    lpf_ctx *c = nullptr;
-    CHECK(lpf_create(&c, 0) == LPF_OK && c);
-    g_ctx = c;
+    lpf_ctx *c = drive_begin();
     refusals(c);
     runs(c);
     lpf_destroy(c);
-    g_ctx = nullptr;
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive_box_views: %d failed checks, %lld fake launches, trace hash %016llx, %lld copies, copy hash %016llx\n", g_fail, fake_hip_launches(),
-            fake_hip_trace_hash(), fake_hip_copies(), fake_hip_copy_hash(0));
-    return g_fail ? 1 : 0;
+    return drive_finish("drive_box_views", true);
 }

@@ -4,30 +4,7 @@
 // lpf_erode_masks_u8.  Kernel launches do nothing here (fake_hip.cpp): they are counted, and their names go to the FAKE_HIP_TRACE
 // file, by which tests/test_host_sanitized_erosion.py checks which kernels each element launches; the values are checked on the GPU
 // by tests/test_gpu_erosion_element.py.
-#include "../../include/lpf.h"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-extern "C" long long fake_hip_launches(void);
-extern "C" unsigned long long fake_hip_trace_hash(void);
-extern "C" void fake_hip_trace_flush(void);
-
-static int g_fail = 0;
-static lpf_ctx *g_ctx = nullptr;
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive_erosion.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, lpf_last_error(g_ctx)); ++g_fail; } } while (0)
-static bool err_is(const char *text) { return strcmp(lpf_last_error(g_ctx), text) == 0; }
-
-static const double T16[16] = {0, -1, 0, 0.1, 0, 0, -1, 0.2, 1, 0, 0, 0.3, 0, 0, 0, 1};
-static const double K9[9] = {552.5, 0, 682.0, 0, 552.5, 238.7, 0, 0, 1};
-
-struct Dev {                      // "device" buffers: heap blocks, so that the sanitizer knows their bounds
-    std::vector<void *> all;
-    template <typename T> T *get(size_t n) { void *p = calloc(n ? n : 1, sizeof(T)); all.push_back(p); return (T *)p; }
-    ~Dev() { for (void *p : all) free(p); }
-};
+#include "drive_common.h"
 
 static void refusals(lpf_ctx *c)
 {
@@ -146,15 +123,10 @@ static void wide_and_values(lpf_ctx *c)
 
 int main()
 {
-    lpf_ctx *c = nullptr;
-    CHECK(lpf_create(&c, 0) == LPF_OK && c);
-    g_ctx = c;
+    lpf_ctx *c = drive_begin();
     refusals(c);
     narrow(c);
     wide_and_values(c);
     lpf_destroy(c);
-    g_ctx = nullptr;
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive_erosion: %d failed checks, %lld fake launches, trace hash %016llx\n", g_fail, fake_hip_launches(), fake_hip_trace_hash());
-    return g_fail ? 1 : 0;
+    return drive_finish("drive_erosion", false);
 }

@@ -5,23 +5,7 @@
 // repeated all-device call without a host wait, and a batch whose host masks pass the staging bound and go through in two ranges.
 // Kernel launches do nothing here (fake_hip.cpp): the launches and copies are counted and the launch lines recorded (FAKE_HIP_TRACE,
 // read by tests/test_host_sanitized_first_match.py); the values are checked on the GPU by tests/test_gpu_first_match.py.
-#include "../../include/lpf.h"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-extern "C" long long fake_hip_launches(void);
-extern "C" long long fake_hip_copies(void);
-extern "C" unsigned long long fake_hip_trace_hash(void);
-extern "C" unsigned long long fake_hip_copy_hash(int restart);
-extern "C" void fake_hip_trace_flush(void);
-
-static int g_fail = 0;
-static lpf_ctx *g_ctx = nullptr;
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive_first_match.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, lpf_last_error(g_ctx)); ++g_fail; } } while (0)
-static bool err_starts(const char *text) { return strncmp(lpf_last_error(g_ctx), text, strlen(text)) == 0; }
+#include "drive_common.h"
 
 struct Batch {                    // F frames of the given sizes, M uint8 masks of mh x mw per frame, a colour row per mask
     int F, M, mh, mw;
@@ -80,12 +64,6 @@ struct Out {
     }
 };
 
-static void set_camera(lpf_ctx *c)
-{
-    const double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, K[9] = {500, 0, 320, 0, 500, 240, 0, 0, 1};
-    CHECK(lpf_set_camera(c, T, K, 640, 480, 0.0, 30.0) == LPF_OK);
-}
-
 static void refusals(lpf_ctx *c)
 {
     Batch b({100, 0, 50}, 3, 20, 30);
@@ -96,7 +74,7 @@ static void refusals(lpf_ctx *c)
     const int64_t *fo = b.frame_off.data();
     CHECK(lpf_first_match(nullptr, pts, fo, 3, 0, &in, &o) == LPF_ERR_ARG);
     CHECK(lpf_first_match(c, pts, fo, 3, 0, &in, &o) == LPF_ERR_STATE && err_starts("lpf_set_camera has not been called"));
-    set_camera(c);
+    set_camera(c, 30.0);
     CHECK(lpf_first_match(c, pts, fo, 3, 0, &in, &o) == LPF_OK);
     CHECK(lpf_first_match(c, pts, fo, 0, 0, &in, &o) == LPF_OK);                  // F = 0 does nothing
     CHECK(lpf_first_match(c, pts, fo, -1, 0, &in, &o) == LPF_ERR_ARG && err_starts("first_match: in="));
@@ -219,16 +197,10 @@ static void chunks(lpf_ctx *c)
 
 int main()
 {
-    lpf_ctx *c = nullptr;
-    CHECK(lpf_create(&c, 0) == LPF_OK && c);
-    g_ctx = c;
+    lpf_ctx *c = drive_begin();
     refusals(c);
     runs(c);
     chunks(c);
     lpf_destroy(c);
-    g_ctx = nullptr;
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive_first_match: %d failed checks, %lld fake launches, trace hash %016llx, %lld copies, copy hash %016llx\n", g_fail,
-            fake_hip_launches(), fake_hip_trace_hash(), fake_hip_copies(), fake_hip_copy_hash(0));
-    return g_fail ? 1 : 0;
+    return drive_finish("drive_first_match", true);
 }

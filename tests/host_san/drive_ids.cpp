@@ -9,30 +9,11 @@
 // tests/test_host_sanitized_ids.py can say from the FAKE_HIP_TRACE file which kernels the form launches and what it copies.  Each
 // successful call with M > 4 prints what its dense twin would have copied ("dense-bytes N") and the bytes of the image or planes it
 // writes ("written-bytes N": no memset of that size may appear).  Results are checked on the GPU by tests/test_gpu_ids.py.
-#include "../../include/lpf.h"
-
+#include "drive_common.h"
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-extern "C" long long fake_hip_launches(void);
-extern "C" long long fake_hip_copies(void);
-extern "C" unsigned long long fake_hip_trace_hash(void);
-extern "C" void fake_hip_trace_flush(void);
-extern "C" int hipMalloc(void **p, size_t n);
-extern "C" int hipFree(void *p);
-
-static int g_fail = 0;
-static lpf_ctx *g_ctx = nullptr;
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive_ids.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, lpf_last_error(g_ctx)); ++g_fail; } } while (0)
-static bool err_is(const char *text) { return strcmp(lpf_last_error(g_ctx), text) == 0; }
-static bool err_has(const char *text) { return strstr(lpf_last_error(g_ctx), text) != nullptr; }
-
-static const double T16[16] = {0, -1, 0, 0.1, 0, 0, -1, 0.2, 1, 0, 0, 0.3, 0, 0, 0, 1};
-static const double K9[9] = {552.5, 0, 682.0, 0, 552.5, 238.7, 0, 0, 1};
 static int W = 37, H = 23, HW = W * H;                       // the camera in force (camera())
+static bool in_force(lpf_ctx *c, int F, int hw = HW);       // (drive_common.h's; the default is read at each call)
 static const int NPTS = 1001;
 
 static void camera(lpf_ctx *c, int w, int h)
@@ -41,12 +22,6 @@ static void camera(lpf_ctx *c, int w, int h)
     W = w; H = h; HW = w * h;
 }
 
-struct Dev {                      // output buffers: heap blocks, so that the sanitizer knows their bounds
-    std::vector<void *> all;
-    template <typename T> T *get(size_t n) { void *p = calloc(n ? n : 1, sizeof(T)); all.push_back(p); return (T *)p; }
-    ~Dev() { for (void *p : all) free(p); }
-};
-
 // one set of ID maps as a caller describes it
 struct Ids {
     int F = 1, M = 1, id_bytes = 2, erode = 0, on_device = 0, reserved = 0;
@@ -54,12 +29,12 @@ struct Ids {
 };
 
 // ... and as it is handed over: sel, host ids and the struct in exactly-sized heap blocks; release(): scribble and free
-struct Held {
+struct HeldIds {
     void *ids = nullptr, *dev = nullptr;
     int32_t *sel = nullptr;
     lpf_id_masks *in = nullptr;
     size_t nb = 0, ns = 0;
-    explicit Held(const Ids &k)
+    explicit HeldIds(const Ids &k)
     {
         const int bytes = k.id_bytes == 4 ? 4 : 2;
         const long long F = k.F > 0 ? k.F : 0, M = k.M > 0 ? k.M : 0;
@@ -119,7 +94,7 @@ static void said(const Ids &k, int lw_or_lb_bytes)
 
 static int set_ids(lpf_ctx *c, const Ids &k)
 {
-    Held h(k);
+    HeldIds h(k);
     const int rc = lpf_set_masks_ids(c, h.in);
     h.release();
     h.release_device(c);
@@ -130,47 +105,18 @@ static int set_ids(lpf_ctx *c, const Ids &k)
 static std::vector<float> g_pts(4 * (size_t)NPTS * 8, 1.0f);
 static int64_t g_off[9] = {0, NPTS, 2 * NPTS, 3 * NPTS, 4 * NPTS, 5 * NPTS, 6 * NPTS, 7 * NPTS, 8 * NPTS};
 
-static void wide_outputs(Dev &D, lpf_wide_outputs &o, int F, int M)
-{
-    const int64_t n = (int64_t)F * NPTS;
-    const int LW = M > 0 ? (M + 31) / 32 : 1;
-    memset(&o, 0, sizeof o);
-    o.uv = D.get<int32_t>(2 * n); o.valid_idx = D.get<int64_t>(n); o.uv_valid = D.get<int32_t>(2 * n); o.label_words = D.get<uint32_t>(n * LW);
-    o.label_valid_words = D.get<uint32_t>(n * LW); o.inst_idx = D.get<int64_t>((size_t)F * 100); o.inst_cap = 100;
-    o.count_mb = D.get<int32_t>((size_t)(M ? M : 1)); o.n_valid = D.get<int64_t>(F); o.n_labelled = D.get<int64_t>(F);
-    o.inst_count = D.get<int64_t>((size_t)F * M + 1); o.inst_off = D.get<int64_t>((size_t)F * (M + 1)); o.best_cnt = D.get<int64_t>((size_t)F * M + 1);
-    o.best_box = D.get<int32_t>((size_t)F * M + 1); o.inst_overflow = D.get<int32_t>(F);
-}
-
-static void narrow_outputs(Dev &D, lpf_outputs &o, int F, int M)
-{
-    const int64_t n = (int64_t)F * NPTS;
-    memset(&o, 0, sizeof o);
-    o.uv = D.get<int32_t>(2 * n); o.label_bits = D.get<uint32_t>(n); o.valid_idx = D.get<int64_t>(n);
-    o.inst_idx = D.get<int64_t>((size_t)F * 100); o.inst_cap = 100; o.count_mb = D.get<int32_t>((size_t)(M ? M : 1));
-    o.summary = D.get<lpf_frame_summary>(F); o.uv_valid = D.get<int32_t>(2 * n); o.label_valid = D.get<uint32_t>(n);
-}
-
 // lpf_run_wide_ids for F frames with k as its maps; the arrays are gone when it returns
 static int run_ids(lpf_ctx *c, const Ids &k, int F)
 {
     Dev D;
     lpf_wide_outputs o;
-    wide_outputs(D, o, F > 0 ? F : 1, k.M > 0 && k.M <= LPF_MAX_MASKS_WIDE ? k.M : 1);
-    Held h(k);
+    wide_outputs(D, o, F > 0 ? F : 1, k.M > 0 && k.M <= LPF_MAX_MASKS_WIDE ? k.M : 1, NPTS);
+    HeldIds h(k);
     const int rc = lpf_run_wide_ids(c, g_pts.data(), g_off, F, 0, h.in, &o);
     h.release();
     h.release_device(c);
     if (rc == LPF_OK) said(k, 4 * ((k.M + 31) / 32));
     return rc;
-}
-
-// the state of the context as a caller sees it: F frames of masks in force (lpf_get_label_image fills F * HW words) or none
-static bool in_force(lpf_ctx *c, int F)
-{
-    std::vector<uint32_t> img((size_t)(F > 0 ? F : 1) * HW);
-    const int rc = lpf_get_label_image(c, img.data(), 0);
-    return F > 0 ? rc == LPF_OK : rc == LPF_ERR_STATE;
 }
 
 static void state_errors(lpf_ctx *c)
@@ -218,7 +164,7 @@ static void refusals(lpf_ctx *c)
     }
     for (int where : {2, -1}) {
         k = ids_of(1, 2);
-        Held h(k);
+        HeldIds h(k);
         h.in->on_device = where;
         snprintf(want, sizeof want, "lpf_set_masks_ids: on_device=%d (0: ids in host memory, 1: device memory)", where);
         CHECK(lpf_set_masks_ids(c, h.in) == LPF_ERR_ARG && err_is(want));
@@ -250,7 +196,7 @@ static void refusals(lpf_ctx *c)
     // lpf_run_wide_ids
     Dev D;
     lpf_wide_outputs o;
-    wide_outputs(D, o, 2, 40);
+    wide_outputs(D, o, 2, 40, NPTS);
     CHECK(lpf_run_wide_ids(c, g_pts.data(), g_off, 2, 0, nullptr, &o) == LPF_ERR_ARG && err_is("run_wide_ids: in=NULL"));
     k = ids_of(2, LPF_MAX_MASKS_WIDE + 1);
     CHECK(run_ids(c, k, 2) == LPF_ERR_ARG && err_is("run_wide_ids: M=257 masks per frame, lpf_run_wide_ids takes 0 .. LPF_MAX_MASKS_WIDE = 256"));
@@ -270,7 +216,7 @@ static void refusals(lpf_ctx *c)
     CHECK(run_ids(c, k, 2) == LPF_ERR_ARG && err_is("run_wide_ids: sel=NULL with F=2 M=40"));
     {
         k = ids_of(2, 40);
-        Held h(k);
+        HeldIds h(k);
         h.in->on_device = 2;
         CHECK(lpf_run_wide_ids(c, g_pts.data(), g_off, 2, 0, h.in, &o) == LPF_ERR_ARG && err_is("run_wide_ids: on_device=2 (0: ids in host memory, 1: device memory)"));
         h.release();
@@ -281,7 +227,7 @@ static void refusals(lpf_ctx *c)
     CHECK(run_ids(c, k, 0) == LPF_ERR_ARG && err_has("run_wide_ids: in=") && err_has("F=0"));
     {                                                        // ... no outputs, no frame_off, a frame_off that does not start at 0
         k = ids_of(2, 40);
-        Held h(k);
+        HeldIds h(k);
         CHECK(lpf_run_wide_ids(c, g_pts.data(), g_off, 2, 0, h.in, nullptr) == LPF_ERR_ARG && err_has("run_wide_ids: in="));
         CHECK(lpf_run_wide_ids(c, g_pts.data(), nullptr, 2, 0, h.in, &o) == LPF_ERR_ARG && err_has("run_wide_ids: in="));
         CHECK(lpf_run_wide_ids(c, g_pts.data(), g_off + 1, 2, 0, h.in, &o) == LPF_ERR_ARG && err_is("run_wide_ids: frame_off[0] must be 0"));
@@ -319,7 +265,7 @@ static void no_decode(lpf_ctx *c)
     {
         Dev D;
         lpf_wide_outputs o;
-        wide_outputs(D, o, 2, 1);
+        wide_outputs(D, o, 2, 1, NPTS);
         lpf_wide_input wi;
         memset(&wi, 0, sizeof wi);
         l0 = fake_hip_launches();
@@ -413,7 +359,7 @@ static void pipelined(lpf_ctx *c)
         CHECK(lpf_set_pipelined(c, mode) == LPF_OK);
         Dev D;
         lpf_outputs o;
-        narrow_outputs(D, o, 1, 32);
+        narrow_outputs(D, o, 1, 32, NPTS);
         for (int it = 0; it < 3; ++it) {
             CHECK(set_ids(c, ids_of(1, 5 + 6 * it, it % 2 ? 4 : 2, 0, it)) == LPF_OK);
             CHECK(lpf_run_batch(c, g_pts.data(), g_off, 1, 0, &o) == LPF_OK);        // owed, in modes 2 / 4
@@ -433,7 +379,7 @@ static void mixed(lpf_ctx *c)
     {
         Dev D;
         lpf_wide_outputs o;
-        wide_outputs(D, o, 2, 70);
+        wide_outputs(D, o, 2, 70, NPTS);
         std::vector<uint8_t> dense((size_t)2 * 70 * HW, 1);
         lpf_wide_input wi;
         memset(&wi, 0, sizeof wi);
@@ -453,9 +399,7 @@ static void mixed(lpf_ctx *c)
 int main(int argc, char **argv)
 {
     const bool only_ids = argc > 1 && !strcmp(argv[1], "ids"), only_mixed = argc > 1 && !strcmp(argv[1], "mixed");
-    lpf_ctx *c = nullptr;
-    CHECK(lpf_create(&c, 0) == LPF_OK && c);
-    g_ctx = c;
+    lpf_ctx *c = drive_begin();
     if (!only_mixed) {
         state_errors(c);
         refusals(c);
@@ -468,8 +412,5 @@ int main(int argc, char **argv)
     }
     if (!only_ids) mixed(c);
     lpf_destroy(c);
-    g_ctx = nullptr;
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive_ids: %d failed checks, %lld fake launches, trace hash %016llx\n", g_fail, fake_hip_launches(), fake_hip_trace_hash());
-    return g_fail ? 1 : 0;
+    return drive_finish("drive_ids", false);
 }

@@ -3,23 +3,7 @@
 // same number of frames), host and device memory for the points, the lists and the outputs in every combination, NULL outputs, M = 0,
 // F = 0, a frame whose lists did not fit, and what goes back to a host caller (only the entries a frame lists).  Kernel launches do
 // nothing here (fake_hip.cpp): the launches and copies are counted, the values are checked on the GPU by tests/test_gpu_inside.py.
-#include "../../include/lpf.h"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-extern "C" long long fake_hip_launches(void);
-extern "C" long long fake_hip_copies(void);
-extern "C" unsigned long long fake_hip_trace_hash(void);
-extern "C" unsigned long long fake_hip_copy_hash(int restart);
-extern "C" void fake_hip_trace_flush(void);
-
-static int g_fail = 0;
-static lpf_ctx *g_ctx = nullptr;
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive_inside.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, lpf_last_error(g_ctx)); ++g_fail; } } while (0)
-static bool err_starts(const char *text) { return strncmp(lpf_last_error(g_ctx), text, strlen(text)) == 0; }
+#include "drive_common.h"
 
 struct Batch {                    // F frames of N points, M cars per frame with the given list lengths, B boxes per frame
     int F, M;
@@ -40,13 +24,7 @@ struct Batch {                    // F frames of N points, M cars per frame with
         }
         best_box.assign((size_t)F * M, B > 0 ? 0 : -1);
         best_cnt.assign((size_t)F * M, 12);
-        corners.assign((size_t)F * B * 24, 0.0);
-        for (size_t b = 0; b < (size_t)F * B; ++b)              // unit cubes in the dataset's corner order
-            for (int k = 0; k < 8; ++k) {
-                corners[b * 24 + k * 3 + 0] = (k == 1 || k == 2 || k == 5 || k == 6) ? 1.0 : 0.0;
-                corners[b * 24 + k * 3 + 1] = (k == 2 || k == 3 || k == 6 || k == 7) ? 1.0 : 0.0;
-                corners[b * 24 + k * 3 + 2] = k >= 4 ? 1.0 : 0.0;
-            }
+        unit_cubes(corners, (size_t)F * B);
     }
     lpf_inside_input input(int on_device) const
     {
@@ -80,12 +58,6 @@ struct Out {
         return o;
     }
 };
-
-static void set_camera(lpf_ctx *c)
-{
-    const double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, K[9] = {500, 0, 320, 0, 500, 240, 0, 0, 1};
-    CHECK(lpf_set_camera(c, T, K, 640, 480, 0.0, 50.0) == LPF_OK);
-}
 
 static void refusals(lpf_ctx *c)
 {
@@ -228,16 +200,10 @@ static void runs(lpf_ctx *c)
 
 int main()
 {
-    lpf_ctx *c = nullptr;
-    CHECK(lpf_create(&c, 0) == LPF_OK && c);
-    g_ctx = c;
+    lpf_ctx *c = drive_begin();
     set_camera(c);
     refusals(c);
     runs(c);
     lpf_destroy(c);
-    g_ctx = nullptr;
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive_inside: %d failed checks, %lld fake launches, trace hash %016llx, %lld copies, copy hash %016llx\n", g_fail, fake_hip_launches(),
-            fake_hip_trace_hash(), fake_hip_copies(), fake_hip_copy_hash(0));
-    return g_fail ? 1 : 0;
+    return drive_finish("drive_inside", true);
 }

@@ -4,22 +4,8 @@
 // the staging spans of every call -- the copies up and back of each range -- run over real heap bounds many times instead of twice.
 // Checked: the return codes, lpf_lab_last_ranges, and the launches of every range.  Kernel launches do nothing here (fake_hip.cpp):
 // the values are checked on the GPU by tests/test_gpu_batch_ranges.py.
-#include "../../include/lpf.h"
+#include "drive_common.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-extern "C" long long fake_hip_launches(void);
-extern "C" void fake_hip_trace_flush(void);
-
-static int g_fail = 0;
-static lpf_ctx *g_ctx = nullptr;
-static const char *g_what = "";
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive_ranges.cpp:%d: CHECK failed (%s): %s  [%s]\n", __LINE__, g_what, #cond, lpf_last_error(g_ctx)); ++g_fail; } } while (0)
-
-static const double IDENT[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
 static const int F = 6;
 static const int DETS[F] = {2, 0, 3, 1, 0, 2}, BOXES[F] = {3, 1, 0, 2, 0, 4}, POINTS[F] = {3, 0, 5, 2, 0, 4};   // no detections | no boxes | empty
 static const int W = 8, H = 6, M = 2;
@@ -48,7 +34,7 @@ static std::vector<int> ranges_of(const Setting &s, int items, bool budget_cuts)
 // one call under every setting: launches(first, count) of a range; budget_cuts: plan_ranges plans the call (not a plain frame loop)
 template <typename Call, typename Launches> static void sweep(const char *what, int items, bool budget_cuts, Call &&call, Launches &&launches)
 {
-    g_what = what;
+    const int failed = g_fail;
     for (const Setting &s : SETTINGS) {
         CHECK(lpf_lab_set_range_limits(g_ctx, s.budget, s.max_items) == LPF_OK);
         const std::vector<int> r = ranges_of(s, items, budget_cuts);
@@ -62,6 +48,7 @@ template <typename Call, typename Launches> static void sweep(const char *what, 
             fprintf(stderr, "  %s under budget %lld, max_items %d: %lld launches, expected %lld\n", what, s.budget, s.max_items, fake_hip_launches() - l0, want);
     }
     CHECK(lpf_lab_set_range_limits(g_ctx, 0, 0) == LPF_OK);
+    if (g_fail != failed) fprintf(stderr, "  (the failed checks above: %s)\n", what);
 }
 
 static int most(const int *n, int first, int count)
@@ -235,9 +222,7 @@ static void views_and_overlays(lpf_ctx *c)
 
 int main()
 {
-    lpf_ctx *c = nullptr;
-    CHECK(lpf_create(&c, 0) == LPF_OK && c);
-    g_ctx = c;
+    lpf_ctx *c = drive_begin();
     CHECK(lpf_lab_set_range_limits(nullptr, 0, 0) == LPF_ERR_ARG && lpf_lab_last_ranges(nullptr) == LPF_ERR_ARG);
     CHECK(lpf_lab_set_range_limits(c, -1, 0) == LPF_ERR_ARG && lpf_lab_set_range_limits(c, 0, -1) == LPF_ERR_ARG);
     CHECK(lpf_lab_last_ranges(c) == 0);
@@ -247,8 +232,5 @@ int main()
     points(c);
     views_and_overlays(c);
     lpf_destroy(c);
-    g_ctx = nullptr;
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive_ranges: %d failed checks, %lld fake launches\n", g_fail, fake_hip_launches());
-    return g_fail ? 1 : 0;
+    return drive_finish("drive_ranges", false);
 }

@@ -8,28 +8,9 @@
 // instantiation ran, no dense count ran, no dense mask was copied (each successful call prints the bytes its dense twin would have
 // copied: "dense-bytes N").  The multi-range section stands between two marker memsets (mark()) in the trace.  Results are checked on
 // the GPU by tests/test_gpu_rle_analysis.py.
-#include "../../include/lpf.h"
-
+#include "drive_common.h"
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-extern "C" long long fake_hip_launches(void);
-extern "C" long long fake_hip_copies(void);
-extern "C" unsigned long long fake_hip_trace_hash(void);
-extern "C" void fake_hip_trace_flush(void);
-extern "C" void fake_hip_fail_malloc_after(long long n);     // n more hipMalloc calls succeed, the next one fails; n < 0: off
-extern "C" int hipMemsetAsync(void *, int, size_t, void *);      // the fake runtime's: a marker line "memset <bytes>" in the trace
-
-static int g_fail = 0;
-static lpf_ctx *g_ctx = nullptr;
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive_rle_analysis.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, lpf_last_error(g_ctx)); ++g_fail; } } while (0)
-static bool err_is(const char *text) { return strcmp(lpf_last_error(g_ctx), text) == 0; }
-
-static const double T16[16] = {0, -1, 0, 0.1, 0, 0, -1, 0.2, 1, 0, 0, 0.3, 0, 0, 0, 1};
-static const double K9[9] = {552.5, 0, 682.0, 0, 552.5, 238.7, 0, 0, 1};
 static const int W = 37, H = 23, HW = W * H;                 // the context's camera
 static const int W1 = 30, H1 = 20, HW1 = W1 * H1;            // masks of their own, smaller size (first match)
 static const int BW = 1408, BH = 376, BHW = BW * BH;         // the large image of the multi-range section
@@ -41,53 +22,9 @@ static void mark()                                           // "memset 7": a si
     hipMemsetAsync(buf, 0, 7, nullptr);
 }
 
-struct Dev {                      // output buffers: heap blocks, so that the sanitizer knows their bounds
-    std::vector<void *> all;
-    template <typename T> T *get(size_t n) { void *p = calloc(n ? n : 1, sizeof(T)); all.push_back(p); return (T *)p; }
-    ~Dev() { for (void *p : all) free(p); }
-};
-
-struct Rle {
-    std::vector<int32_t> runs;          // {start, length} pairs
-    std::vector<int64_t> off;
-    int F = 1, M = 1, erode = 0, reserved = 0;
-};
-struct Held {                           // arrays and struct in exactly-sized heap blocks; release(): scribble and free
-    int32_t *r = nullptr;
-    int64_t *o = nullptr;
-    lpf_rle_masks *in = nullptr;
-    size_t nr = 0, no = 0;
-    explicit Held(const Rle &k) : nr(k.runs.size()), no(k.off.size())
-    {
-        r = nr ? (int32_t *)malloc(nr * sizeof(int32_t)) : nullptr;
-        o = no ? (int64_t *)malloc(no * sizeof(int64_t)) : nullptr;
-        if (r) memcpy(r, k.runs.data(), nr * sizeof(int32_t));
-        if (o) memcpy(o, k.off.data(), no * sizeof(int64_t));
-        in = (lpf_rle_masks *)malloc(sizeof(lpf_rle_masks));
-        memset(in, 0, sizeof *in);
-        in->runs = r; in->run_off = o; in->F = k.F; in->M = k.M; in->erode_iters = k.erode; in->reserved = k.reserved;
-    }
-    void release()
-    {
-        if (r) memset(r, 0xEE, nr * sizeof(int32_t));
-        if (o) memset(o, 0xEE, no * sizeof(int64_t));
-        memset(in, 0xEE, sizeof *in);
-        free(r); free(o); free(in);
-        r = nullptr; o = nullptr; in = nullptr;
-    }
-};
-
-static Rle simple(int F, int M, int runs_per_mask, int length = 3, int hw = HW)
-{
-    Rle k;
-    k.F = F; k.M = M;
-    k.off.push_back(0);
-    for (int i = 0; i < F * M; ++i) {
-        for (int j = 0; j < runs_per_mask; ++j) { k.runs.push_back((i * 7 + j * 11) % (hw - length)); k.runs.push_back(length); }
-        k.off.push_back((int64_t)k.runs.size() / 2);
-    }
-    return k;
-}
+// drive_common.h's, with this driver's image as the default
+static Rle simple(int F, int M, int runs_per_mask, int length = 3, int hw = HW);
+static bool in_force(lpf_ctx *c, int F, int hw = HW);
 
 static std::vector<float> g_pts(4 * (size_t)NPTS * FMAX, 1.0f);
 static int64_t g_off[FMAX + 1];
@@ -138,13 +75,6 @@ static int first_match(lpf_ctx *c, const Rle &k, int F, int mh = H, int mw = W, 
     free(in); free(o); free(colors);
     if (rc == LPF_OK && k.M > 0) fprintf(stderr, "dense-bytes %lld\n", (long long)F * k.M * mh * mw);
     return rc;
-}
-
-static bool in_force(lpf_ctx *c, int F)                      // the narrow state as a caller sees it
-{
-    std::vector<uint32_t> img((size_t)(F > 0 ? F : 1) * HW);
-    const int rc = lpf_get_label_image(c, img.data(), 0);
-    return F > 0 ? rc == LPF_OK : rc == LPF_ERR_STATE;
 }
 
 // F frames of M one-run masks on the large image: frame f, mask m = pixels [(f * M + m) * 64, + 1 + f)
@@ -449,9 +379,7 @@ static void failed_allocations()
 int main()
 {
     for (int f = 0; f <= FMAX; ++f) g_off[f] = (int64_t)f * NPTS;
-    lpf_ctx *c = nullptr;
-    CHECK(lpf_create(&c, 0) == LPF_OK && c);
-    g_ctx = c;
+    lpf_ctx *c = drive_begin();
     CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
     refusals(c);
     no_decode(c);
@@ -460,8 +388,5 @@ int main()
     pipelined(c);
     failed_allocations();
     lpf_destroy(c);
-    g_ctx = nullptr;
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive_rle_analysis: %d failed checks, %lld fake launches, trace hash %016llx\n", g_fail, fake_hip_launches(), fake_hip_trace_hash());
-    return g_fail ? 1 : 0;
+    return drive_finish("drive_rle_analysis", false);
 }

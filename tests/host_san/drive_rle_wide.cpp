@@ -9,119 +9,38 @@
 // bytes its dense twin would have copied: "dense-bytes N"), and erosion is the packed image's.  lpf_run_frame_wide is not driven: its job
 // has no form field (its masks are uint8 device memory), so the form cannot be given to it.  Results are checked on the GPU by
 // tests/test_gpu_wide_rle.py.
-#include "../../include/lpf.h"
-
+#include "drive_common.h"
 #include <climits>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-extern "C" long long fake_hip_launches(void);
-extern "C" long long fake_hip_copies(void);
-extern "C" unsigned long long fake_hip_trace_hash(void);
-extern "C" void fake_hip_trace_flush(void);
-
-static int g_fail = 0;
-static lpf_ctx *g_ctx = nullptr;
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "drive_rle_wide.cpp:%d: CHECK failed: %s  [%s]\n", __LINE__, #cond, lpf_last_error(g_ctx)); ++g_fail; } } while (0)
-static bool err_is(const char *text) { return strcmp(lpf_last_error(g_ctx), text) == 0; }
-
-static const double T16[16] = {0, -1, 0, 0.1, 0, 0, -1, 0.2, 1, 0, 0, 0.3, 0, 0, 0, 1};
-static const double K9[9] = {552.5, 0, 682.0, 0, 552.5, 238.7, 0, 0, 1};
 static const int W = 37, H = 23, HW = W * H;                 // the context's camera, and camera 0 of a camera pass
 static const int W1 = 30, H1 = 20, HW1 = W1 * H1;            // camera 1: smaller
 static const int NPTS = 1001;                                // (16 016 bytes per frame: no multiple of either image's pixel count)
 
-struct Dev {                      // output buffers: heap blocks, so that the sanitizer knows their bounds
-    std::vector<void *> all;
-    template <typename T> T *get(size_t n) { void *p = calloc(n ? n : 1, sizeof(T)); all.push_back(p); return (T *)p; }
-    ~Dev() { for (void *p : all) free(p); }
-};
-
-// one set of run-length masks; held(): its arrays and its struct in exactly-sized heap blocks, release(): scribble and free
-struct Rle {
-    std::vector<int32_t> runs;          // {start, length} pairs
-    std::vector<int64_t> off;
-    int F = 1, M = 1, erode = 0, reserved = 0;
-};
-struct Held {
-    int32_t *r = nullptr;
-    int64_t *o = nullptr;
-    lpf_rle_masks *in = nullptr;
-    size_t nr = 0, no = 0;
-    explicit Held(const Rle &k) : nr(k.runs.size()), no(k.off.size())
-    {
-        r = nr ? (int32_t *)malloc(nr * sizeof(int32_t)) : nullptr;
-        o = no ? (int64_t *)malloc(no * sizeof(int64_t)) : nullptr;
-        if (r) memcpy(r, k.runs.data(), nr * sizeof(int32_t));
-        if (o) memcpy(o, k.off.data(), no * sizeof(int64_t));
-        in = (lpf_rle_masks *)malloc(sizeof(lpf_rle_masks));
-        memset(in, 0, sizeof *in);
-        in->runs = r; in->run_off = o; in->F = k.F; in->M = k.M; in->erode_iters = k.erode; in->reserved = k.reserved;
-    }
-    void release()                                           // the library has its copies: scribble, then free
-    {
-        if (r) memset(r, 0xEE, nr * sizeof(int32_t));
-        if (o) memset(o, 0xEE, no * sizeof(int64_t));
-        memset(in, 0xEE, sizeof *in);
-        free(r); free(o); free(in);
-        r = nullptr; o = nullptr; in = nullptr;
-    }
-    lpf_wide_input input(const Rle &k) const
-    {
-        lpf_wide_input wi;
-        memset(&wi, 0, sizeof wi);
-        wi.masks = in; wi.M = k.M; wi.f32 = LPF_MASKS_RLE; wi.erode_iters = k.erode;
-        wi.rects = (const int32_t *)16; wi.binarize = 77;    // neither is read in this form
-        return wi;
-    }
-};
-
-static Rle simple(int F, int M, int runs_per_mask, int length = 3, int hw = HW)
+// h, the held form of k, as the masks of a wide input
+static lpf_wide_input wide_input(const Held &h, const Rle &k)
 {
-    Rle k;
-    k.F = F; k.M = M;
-    k.off.push_back(0);
-    for (int i = 0; i < F * M; ++i) {
-        for (int j = 0; j < runs_per_mask; ++j) { k.runs.push_back((i * 7 + j * 11) % (hw - length)); k.runs.push_back(length); }
-        k.off.push_back((int64_t)k.runs.size() / 2);
-    }
-    return k;
+    lpf_wide_input wi;
+    memset(&wi, 0, sizeof wi);
+    wi.masks = h.in; wi.M = k.M; wi.f32 = LPF_MASKS_RLE; wi.erode_iters = k.erode;
+    wi.rects = (const int32_t *)16; wi.binarize = 77;    // neither is read in this form
+    return wi;
 }
+
+// drive_common.h's, with this driver's image as the default
+static Rle simple(int F, int M, int runs_per_mask, int length = 3, int hw = HW);
+static bool in_force(lpf_ctx *c, int F, int hw = HW);
 
 static std::vector<float> g_pts(4 * (size_t)NPTS * 3, 1.0f);
 static int64_t g_off[4] = {0, NPTS, 2 * NPTS, 3 * NPTS};
-
-static void wide_outputs(Dev &D, lpf_wide_outputs &o, int F, int M)
-{
-    const int64_t n = (int64_t)F * NPTS;
-    const int LW = M > 0 ? (M + 31) / 32 : 1;
-    memset(&o, 0, sizeof o);
-    o.uv = D.get<int32_t>(2 * n); o.valid_idx = D.get<int64_t>(n); o.uv_valid = D.get<int32_t>(2 * n); o.label_words = D.get<uint32_t>(n * LW);
-    o.label_valid_words = D.get<uint32_t>(n * LW); o.inst_idx = D.get<int64_t>((size_t)F * 100); o.inst_cap = 100;
-    o.count_mb = D.get<int32_t>((size_t)(M ? M : 1)); o.n_valid = D.get<int64_t>(F); o.n_labelled = D.get<int64_t>(F);
-    o.inst_count = D.get<int64_t>((size_t)F * M + 1); o.inst_off = D.get<int64_t>((size_t)F * (M + 1)); o.best_cnt = D.get<int64_t>((size_t)F * M + 1);
-    o.best_box = D.get<int32_t>((size_t)F * M + 1); o.inst_overflow = D.get<int32_t>(F);
-}
-
-static void narrow_outputs(Dev &D, lpf_outputs &o, int F, int M)
-{
-    const int64_t n = (int64_t)F * NPTS;
-    memset(&o, 0, sizeof o);
-    o.uv = D.get<int32_t>(2 * n); o.label_bits = D.get<uint32_t>(n); o.valid_idx = D.get<int64_t>(n);
-    o.inst_idx = D.get<int64_t>((size_t)F * 100); o.inst_cap = 100; o.count_mb = D.get<int32_t>((size_t)(M ? M : 1));
-    o.summary = D.get<lpf_frame_summary>(F); o.uv_valid = D.get<int32_t>(2 * n); o.label_valid = D.get<uint32_t>(n);
-}
 
 // lpf_run_wide with k as its masks; the arrays are gone when it returns
 static int run_wide(lpf_ctx *c, const Rle &k, int F)
 {
     Dev D;
     lpf_wide_outputs o;
-    wide_outputs(D, o, F, k.M > 0 && k.M <= LPF_MAX_MASKS_WIDE ? k.M : 1);
+    wide_outputs(D, o, F, k.M > 0 && k.M <= LPF_MAX_MASKS_WIDE ? k.M : 1, NPTS);
     Held h(k);
-    const lpf_wide_input wi = h.input(k);
+    const lpf_wide_input wi = wide_input(h, k);
     const int rc = lpf_run_wide(c, g_pts.data(), g_off, F, 0, &wi, &o);
     h.release();
     if (rc == LPF_OK && k.M > 0) fprintf(stderr, "dense-bytes %lld\n", (long long)F * k.M * HW);
@@ -151,11 +70,11 @@ static int run_cams(lpf_ctx *c, bool wide, const Rle *k0, const Rle *k1, int F)
     const int limit = wide ? LPF_MAX_MASKS_WIDE : LPF_MAX_MASKS;
     for (int k = 0; k < 2; ++k) {
         const int M = ks[k] && ks[k]->M > 0 && ks[k]->M <= limit ? ks[k]->M : 1;
-        wide_outputs(D, ow[k], F, M);
-        narrow_outputs(D, on[k], F, M);
+        wide_outputs(D, ow[k], F, M, NPTS);
+        narrow_outputs(D, on[k], F, M, NPTS);
         if (!ks[k]) continue;
         held.emplace_back(*ks[k]);
-        cams[k].masks = held.back().input(*ks[k]);
+        cams[k].masks = wide_input(held.back(), *ks[k]);
     }
     const int rc = wide ? lpf_run_cams_wide(c, g_pts.data(), g_off, F, 0, cams, 2, ow) : lpf_run_cams(c, g_pts.data(), g_off, F, 0, cams, 2, on);
     for (Held &h : held) h.release();
@@ -163,14 +82,6 @@ static int run_cams(lpf_ctx *c, bool wide, const Rle *k0, const Rle *k1, int F)
         for (int k = 0; k < 2; ++k)
             if (ks[k] && ks[k]->M > 0) fprintf(stderr, "dense-bytes %lld\n", (long long)F * ks[k]->M * (k ? HW1 : HW));
     return rc;
-}
-
-// the narrow state as a caller sees it: F frames of masks in force
-static bool in_force(lpf_ctx *c, int F)
-{
-    std::vector<uint32_t> img((size_t)(F > 0 ? F : 1) * HW);
-    const int rc = lpf_get_label_image(c, img.data(), 0);
-    return F > 0 ? rc == LPF_OK : rc == LPF_ERR_STATE;
 }
 
 static void refusals(lpf_ctx *c)
@@ -198,10 +109,10 @@ static void refusals(lpf_ctx *c)
     {
         k = simple(1, 5, 2);
         Held h(k);
-        lpf_wide_input wi = h.input(k);
+        lpf_wide_input wi = wide_input(h, k);
         Dev D;
         lpf_wide_outputs o;
-        wide_outputs(D, o, 1, 6);
+        wide_outputs(D, o, 1, 6, NPTS);
         wi.M = 6;
         CHECK(lpf_run_wide(c, g_pts.data(), g_off, 1, 0, &wi, &o) == LPF_ERR_ARG &&
               err_is("run_wide: the run-length masks say F=1 M=5 erode_iters=0, the call has F=1 M=6 erode_iters=0"));
@@ -266,12 +177,12 @@ static void refusals(lpf_ctx *c)
             Held h(a);
             lpf_cam_input cam;
             camera(cam, W, H);
-            cam.masks = h.input(a);
+            cam.masks = wide_input(h, a);
             Dev D;
             lpf_wide_outputs ow;
             lpf_outputs on;
-            wide_outputs(D, ow, 1, 5);
-            narrow_outputs(D, on, 1, 5);
+            wide_outputs(D, ow, 1, 5, NPTS);
+            narrow_outputs(D, on, 1, 5, NPTS);
             auto call = [&] { return wide ? lpf_run_cams_wide(c, g_pts.data(), g_off, 1, 0, &cam, 1, &ow) : lpf_run_cams(c, g_pts.data(), g_off, 1, 0, &cam, 1, &on); };
             cam.masks.on_device = 2;
             snprintf(want, sizeof want, "%s: camera 0: f32=LPF_MASKS_RLE with on_device=2: run-length masks are host memory (on_device 0)", who);
@@ -362,7 +273,7 @@ static void no_decode(lpf_ctx *c)
         wi.f32 = LPF_MASKS_RLE;
         Dev D;
         lpf_wide_outputs o;
-        wide_outputs(D, o, 2, 1);
+        wide_outputs(D, o, 2, 1, NPTS);
         const long long l0 = fake_hip_launches();
         CHECK(lpf_run_wide(c, g_pts.data(), g_off, 2, 0, &wi, &o) == LPF_OK && fake_hip_launches() - l0 == m0);
         wi.f32 = LPF_MASKS_U8;                               // ... as many launches as dense M = 0
@@ -433,9 +344,9 @@ static void sizes(lpf_ctx *c)
         full.F = 1; full.M = 33; full.runs = {0, 1408 * 376}; full.off.assign(34, 0); full.off[33] = 1;
         Dev D;
         lpf_wide_outputs o;
-        wide_outputs(D, o, 1, 33);
+        wide_outputs(D, o, 1, 33, NPTS);
         Held h(full);
-        const lpf_wide_input wi = h.input(full);
+        const lpf_wide_input wi = wide_input(h, full);
         const long long l0 = fake_hip_launches();
         CHECK(lpf_run_wide(c, g_pts.data(), g_off, 1, 0, &wi, &o) == LPF_OK);
         h.release();
@@ -451,7 +362,7 @@ static void pipelined(lpf_ctx *c)
         CHECK(lpf_set_pipelined(c, mode) == LPF_OK);
         Dev D;
         lpf_outputs o;
-        narrow_outputs(D, o, 1, 5);
+        narrow_outputs(D, o, 1, 5, NPTS);
         for (int it = 0; it < 3; ++it) {
             const Rle n = simple(1, 5 + 6 * it, 3);
             Held h(n);
@@ -471,17 +382,12 @@ static void pipelined(lpf_ctx *c)
 
 int main()
 {
-    lpf_ctx *c = nullptr;
-    CHECK(lpf_create(&c, 0) == LPF_OK && c);
-    g_ctx = c;
+    lpf_ctx *c = drive_begin();
     CHECK(lpf_set_camera(c, T16, K9, W, H, 0, 50) == LPF_OK);
     refusals(c);
     no_decode(c);
     sizes(c);
     pipelined(c);
     lpf_destroy(c);
-    g_ctx = nullptr;
-    fake_hip_trace_flush();
-    fprintf(stderr, "drive_rle_wide: %d failed checks, %lld fake launches, trace hash %016llx\n", g_fail, fake_hip_launches(), fake_hip_trace_hash());
-    return g_fail ? 1 : 0;
+    return drive_finish("drive_rle_wide", false);
 }

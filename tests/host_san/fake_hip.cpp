@@ -22,10 +22,11 @@
 #include <mutex>
 #include <string>
 
+#include "fake_hip.h"
+
 extern "C" {
 
-typedef int hipError_t;
-typedef struct fake_stream { int capturing; } *hipStream_t;
+struct fake_stream { int capturing; };
 typedef struct fake_event { std::atomic<int> recorded; } *hipEvent_t;
 typedef struct fake_graph { int n; } *hipGraph_t;
 typedef struct fake_exec { int n; } *hipGraphExec_t;

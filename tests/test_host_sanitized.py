@@ -19,14 +19,14 @@ GPU box, where sanitizer runs are not available):
     section, and FAKE_HIP_TRACE=<file> keeps the lines.
 """
 import os
-import shutil
 import subprocess
 import sys
 
 import pytest
 
+import host_san_run as san
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 def _gcc_lib(name):
@@ -46,16 +46,10 @@ def test_oracle_under_asan_and_ubsan():
     assert "AddressSanitizer" not in text and "runtime error" not in text, text[-3000:]
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not installed")
-@pytest.mark.parametrize("san", ["asan", "tsan"])
-def test_host_side_of_the_library_under_sanitizers(tmp_path, tmp_path_factory, san):
-    out = str(tmp_path_factory.getbasetemp() / "host_san")         # (shared with the other drivers' tests: one lpf_api object per sanitizer)
-    b = subprocess.run(["make", "-C", os.path.join(REPO, "tests", "host_san"), san, "OUT=" + out, "HIPCC=" + HIPCC], capture_output=True, text=True, timeout=900)
-    assert b.returncode == 0, (b.stdout + b.stderr)[-3000:]
+@san.needs_hipcc
+@pytest.mark.parametrize("san_name", ["asan", "tsan"])
+def test_host_side_of_the_library_under_sanitizers(tmp_path, tmp_path_factory, san_name):
+    exe = san.build(tmp_path_factory, "drive", san_name)          # (one build directory for every driver: one lpf_api object per sanitizer)
     scans = tmp_path / "scans"
     scans.mkdir()
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", TSAN_OPTIONS="halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([os.path.join(out, "drive_" + san), str(scans), "12000"], capture_output=True, text=True, timeout=900, env=env)
-    text = r.stdout + r.stderr
-    assert r.returncode == 0 and "drive: 0 failed checks" in text, text[-4000:]
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
+    san.drive(exe, scans, 12000, checks=208276)                 # (the count repeats from run to run, under both sanitizers)

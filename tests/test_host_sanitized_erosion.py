@@ -4,30 +4,14 @@ sanitized lpf_api object is built once per session and shared by every driver), 
 refused sizes and their messages, a NULL context, the default, and set -> set_masks -> run with k = 5, 3, 1 and 15 through the narrow
 path, lpf_run_wide, lpf_depth_maps and lpf_erode_masks_u8.  The fake runtime's launch trace tells which kernels ran: the cross
 launches the 3x3 kernels only, another size the k x k ones."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-SAN = os.path.join(REPO, "tests", "host_san")
+import host_san_run as san
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not installed")
+@san.needs_hipcc
 def test_erosion_element_host_side_under_asan_and_ubsan(tmp_path_factory, tmp_path):
-    out = str(tmp_path_factory.getbasetemp() / "host_san")
-    b = subprocess.run(["make", "-C", SAN, "asan", "DRIVER=drive_erosion", "OUT=" + out, "HIPCC=" + HIPCC], capture_output=True, text=True, timeout=900)
-    assert b.returncode == 0, (b.stdout + b.stderr)[-3000:]
-    trace = str(tmp_path / "launches.txt")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1", FAKE_HIP_TRACE=trace)
-    r = subprocess.run([os.path.join(out, "drive_erosion_asan")], capture_output=True, text=True, timeout=900, env=env)
-    text = r.stdout + r.stderr
-    assert r.returncode == 0 and "drive_erosion: 0 failed checks" in text, text[-4000:]
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    with open(trace) as f:
-        names = [line.split()[0] for line in f if line.strip() and line.split()[0] not in ("copy", "memset")]
+    exe = san.build(tmp_path_factory, "drive_erosion")
+    text, every = san.drive(exe, trace=tmp_path / "launches.txt", checks=149)
+    names = [l[0] for l in every if l[0] not in ("copy", "memset")]
     # the driver starts with the default element (two set_masks calls of two iterations, at 128 x 48 and at 33 x 17): the streaming
     # pack and two erosions, the tiled pack with its fused first erosion and one more -- the 3x3 kernels, none of the k x k ones
     first_k = next(i for i, n in enumerate(names) if "lpf_pack_erode_k" in n)

@@ -7,34 +7,13 @@ with a narrow run owed -- sel, host ids and the struct scribbled over and freed 
 only, so the fake runtime's trace tells what the form costs: the new kernels ran with the expected grids, no memset of what they write
 precedes them, no pack and no run-length decode ran, no dense mask was copied, erosion is the packed image's.  `drive_ids mixed` then
 runs lpf_run_wide with dense masks after lpf_run_wide_ids on one context."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-SAN = os.path.join(REPO, "tests", "host_san")
+import host_san_run as san
 
 
-def _drive(out, tmp_path, section):
-    trace = str(tmp_path / ("launches_%s.txt" % section))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1", FAKE_HIP_TRACE=trace)
-    r = subprocess.run([os.path.join(out, "drive_ids_asan"), section], capture_output=True, text=True, timeout=900, env=env)
-    text = r.stdout + r.stderr
-    assert r.returncode == 0 and "drive_ids: 0 failed checks" in text, text[-4000:]
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    with open(trace) as f:
-        return text, [line.split() for line in f if line.strip()]
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not installed")
+@san.needs_hipcc
 def test_id_maps_host_side_under_asan_and_ubsan(tmp_path_factory, tmp_path):
-    out = str(tmp_path_factory.getbasetemp() / "host_san")
-    b = subprocess.run(["make", "-C", SAN, "asan", "DRIVER=drive_ids", "OUT=" + out, "HIPCC=" + HIPCC], capture_output=True, text=True, timeout=900)
-    assert b.returncode == 0, (b.stdout + b.stderr)[-3000:]
-    text, every = _drive(out, tmp_path, "ids")
+    exe = san.build(tmp_path_factory, "drive_ids")
+    text, every = san.drive(exe, "ids", trace=tmp_path / "launches_ids.txt", checks=211)
     lines = [l for l in every if l[0] not in ("copy", "memset")]
     names = [l[0] for l in lines]
     label = [l for l in lines if "lpf_ids_label" in l[0]]
@@ -78,7 +57,7 @@ def test_id_maps_host_side_under_asan_and_ubsan(tmp_path_factory, tmp_path):
     assert h2d and not {w for w in would if w >= 30000} & set(h2d), sorted({w for w in would if w >= 30000} & set(h2d))
     assert max(h2d) == 2 * 1408 * 376 * 4
     # dense masks after ID maps on the same context, and ID maps after them: the dense pack runs again, beside the new decodes
-    text, every = _drive(out, tmp_path, "mixed")
+    text, every = san.drive(exe, "mixed", trace=tmp_path / "launches_mixed.txt", checks=9)
     names = [l[0] for l in every]
     assert any("lpf_wide_pack" in n for n in names) and sum("lpf_ids_planes" in n for n in names) == 2
     assert sum("lpf_ids_label" in n for n in names) == 2

@@ -7,15 +7,7 @@ the camera's image), M = 0 and masks without runs with no decode launch, growing
 narrow run owed -- the caller's arrays and structs freed right after each call.  The driver runs run-length masks only, so the fake
 runtime's trace tells what the form costs; its multi-range section (17 frames of 256 masks at 1408 x 376: 16.9 MB of planes per frame
 against the 256 MiB of a range) stands between marker lines."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-SAN = os.path.join(REPO, "tests", "host_san")
+import host_san_run as san
 F, M, HW, LW = 17, 256, 1408 * 376, 8                       # the multi-range batch of the driver (several_ranges)
 
 
@@ -31,20 +23,10 @@ def _ranges(section):
     return out
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not installed")
+@san.needs_hipcc
 def test_rle_analysis_host_side_under_asan_and_ubsan(tmp_path_factory, tmp_path):
-    out = str(tmp_path_factory.getbasetemp() / "host_san")
-    b = subprocess.run(["make", "-C", SAN, "asan", "DRIVER=drive_rle_analysis", "OUT=" + out, "HIPCC=" + HIPCC], capture_output=True, text=True,
-                       timeout=900)
-    assert b.returncode == 0, (b.stdout + b.stderr)[-3000:]
-    trace = str(tmp_path / "launches.txt")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1", FAKE_HIP_TRACE=trace)
-    r = subprocess.run([os.path.join(out, "drive_rle_analysis_asan")], capture_output=True, text=True, timeout=900, env=env)
-    text = r.stdout + r.stderr
-    assert r.returncode == 0 and "drive_rle_analysis: 0 failed checks" in text, text[-4000:]
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    with open(trace) as f:
-        every = [line.split() for line in f if line.strip()]
+    exe = san.build(tmp_path_factory, "drive_rle_analysis")
+    text, every = san.drive(exe, trace=tmp_path / "launches.txt", checks=332)
     names = [l[0] for l in every if l[0] not in ("copy", "memset")]
     # the new count kernel and the raster's planes instantiation (uint32, rule 0, PLANES, count and scatter) ran; nothing dense did
     assert any("lpf_fm_count_planes" in n for n in names)

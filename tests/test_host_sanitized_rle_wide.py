@@ -7,30 +7,13 @@ pixel past camera 1's image that fits camera 0's), the form refused by lpf_depth
 and masks without runs with no decode launch, M = 256 with F = 3, two run-length cameras in one pass, growing then shrinking calls, a
 pipelined context with a narrow run owed -- the caller's arrays and struct freed right after each call.  The driver runs run-length
 masks only, so the fake runtime's trace tells what the form costs: the wide decode ran, no dense pack ran, no dense mask was copied."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-SAN = os.path.join(REPO, "tests", "host_san")
+import host_san_run as san
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not installed")
+@san.needs_hipcc
 def test_wide_rle_host_side_under_asan_and_ubsan(tmp_path_factory, tmp_path):
-    out = str(tmp_path_factory.getbasetemp() / "host_san")
-    b = subprocess.run(["make", "-C", SAN, "asan", "DRIVER=drive_rle_wide", "OUT=" + out, "HIPCC=" + HIPCC], capture_output=True, text=True, timeout=900)
-    assert b.returncode == 0, (b.stdout + b.stderr)[-3000:]
-    trace = str(tmp_path / "launches.txt")
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1", FAKE_HIP_TRACE=trace)
-    r = subprocess.run([os.path.join(out, "drive_rle_wide_asan")], capture_output=True, text=True, timeout=900, env=env)
-    text = r.stdout + r.stderr
-    assert r.returncode == 0 and "drive_rle_wide: 0 failed checks" in text, text[-4000:]
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    with open(trace) as f:
-        every = [line.split() for line in f if line.strip()]
+    exe = san.build(tmp_path_factory, "drive_rle_wide")
+    text, every = san.drive(exe, trace=tmp_path / "launches.txt", checks=174)
     lines = [l for l in every if l[0] not in ("copy", "memset")]
     names = [l[0] for l in lines]
     wide = [l for l in lines if "lpf_rle_decode_wide" in l[0]]
